@@ -2,7 +2,7 @@
 """Headline benchmark: candidate decodes/s (front end + scan + softbits + index + LDPC + collect) at
 --search-width=500 --search-step=1 --scan-depth=6 --nbadsync-threshold=3.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" = one decode window (5184 samples) of every channel of the batch: BASELINE.json configs[2],
 1024 synthetic 12 ksps audio channels per MI355X (F=501 x D=6 x 8 = 24 048 candidates per window,
@@ -45,6 +45,7 @@ B_ALG_PER_CANDIDATE = 634.0      # one 632-byte result record wr
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_WAVE_INSTR = 256 * 4 * 2.4e9 / 2.0   # 256 CUs x 4 SIMD-32, one wave64 VALU op per 2 cycles at 2.4 GHz
 COUNTERS_FILE = os.path.join(ROOT, "profiles", "counters.json")
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all (every rank together)
 
 
 def kernel_source_sha() -> str:
@@ -178,6 +179,30 @@ class HipBackend:
 
     def close(self):
         self.dec.close()
+
+
+def dump_outputs(out_dir: str, records: np.ndarray, prefix: str = "", budget: int = DUMP_BYTES, seed: int = 0):
+    """--dump-outputs: the decoded-record list of the last TIMED step - what msk144_results hands its caller - as one .npy per field,
+    <prefix>records_<field>.npy: f0 and xb in float32, every integer field (message bytes included, shape [n, 10]) in float64, which holds
+    them exactly.  Sorted by (channel, item), so that two builds compare array for array.  A list larger than `budget` is cut to a fixed,
+    seeded sample of records; records_sample_index.npy then says which rows of the sorted list were kept.  Returns a summary for the line."""
+    fields = [n for n in records.dtype.names if n != "reserved"]
+    out_dtype = {n: np.float32 if records.dtype[n].base.kind == "f" else np.float64 for n in fields}
+    row_bytes = sum(np.dtype(out_dtype[n]).itemsize * int(np.prod(records.dtype[n].shape, dtype=np.int64)) for n in fields) + 8
+    rec = records[np.lexsort((records["item"], records["channel"]))]
+    total = len(rec)
+    keep = max(0, (budget - 4096) // row_bytes)
+    sample = None
+    if total > keep:
+        sample = np.sort(np.random.default_rng(seed).choice(total, size=keep, replace=False))
+        rec = rec[sample]
+    os.makedirs(out_dir, exist_ok=True)
+    for n in fields:
+        np.save(os.path.join(out_dir, f"{prefix}records_{n}.npy"), rec[n].astype(out_dtype[n]))
+    np.save(os.path.join(out_dir, f"{prefix}records_count.npy"), np.array([total], dtype=np.float64))
+    if sample is not None:
+        np.save(os.path.join(out_dir, f"{prefix}records_sample_index.npy"), sample.astype(np.float64))
+    return {"dir": out_dir, "records": total, "written": len(rec), "sampled": sample is not None}
 
 
 def usable_cores() -> int:
@@ -448,6 +473,9 @@ def parse_args(argv=None):
     ap.add_argument("--every-slot", action="store_true",
                     help="run the TIMED region with the copy hand-over off (msk144_set_copy_handover(h, 0)): `value` is then slots fully evaluated per second, as the "
                          "reference computes them; the value_every_slot_decoded leg is dropped (it would repeat the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write the decoded records of the last TIMED step (sorted by channel, item) to DIR/records_<field>.npy in "
+                         "float32/float64, at most 64 MB in all (a fixed, seeded sample beyond that); ranks > 0 of an N-rank run write rank<r>_records_<field>.npy")
     ap.add_argument("--launcher", action="store_true", help="go through the N-rank launcher even for --gpus 1 (exercises the RCCL gather path)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend-module", default=None, help="TEST HOOK: module providing Backend (e.g. tests/stub_backend.py on gloo); the line is then labelled as such")
@@ -560,9 +588,17 @@ def run_worker(args) -> int:
             # the path's only exchange: fixed-size decoded-record buffers -> rank 0 (RCCL over xGMI)
             gather.step(be.rec_view, be.cnt_view, timed=timing["on"])
 
+    def barrier():
+        # dist.barrier() asks the HIP runtime for its devices even on gloo (torch._C._get_accelerator()), so a CPU-backend rank would
+        # open the GPU; a one-element all_reduce on the backend's device synchronises the ranks without that
+        if Backend.dist_backend == "nccl":
+            dist.barrier()
+        else:
+            dist.all_reduce(torch.zeros(1, device=be.device))
+
     def fence():
         if distributed:
-            dist.barrier()
+            barrier()
         be.fence()
 
     for i in range(args.warmup):
@@ -576,6 +612,7 @@ def run_worker(args) -> int:
         step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
+    timed_records = be.results() if args.dump_outputs else None      # the last timed step's list, read after the clock stopped
 
     rank_ms = [elapsed / args.steps * 1e3]
     if distributed:
@@ -632,6 +669,10 @@ def run_worker(args) -> int:
         except (OverflowError, AssertionError) as e:
             print(f"bench.py: gather validation failed: {e}", file=sys.stderr)
             rc = 3
+
+    dumped = None
+    if timed_records is not None and rc == 0:
+        dumped = dump_outputs(args.dump_outputs, timed_records, prefix=f"rank{rank}_" if rank > 0 else "", budget=DUMP_BYTES // world)
 
     if rank == 0 and rc == 0:
         T_NAMES = be.T_NAMES
@@ -738,6 +779,8 @@ def run_worker(args) -> int:
         out.update(extra)
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
 
     be.close()
@@ -745,7 +788,7 @@ def run_worker(args) -> int:
         flag = torch.tensor([rc], dtype=torch.int32, device=be.device)
         dist.all_reduce(flag, op=dist.ReduceOp.MAX)
         rc = int(flag.item())
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
     return rc
 
@@ -755,6 +798,9 @@ def main(argv=None) -> int:
     args = parse_args(argv)
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and not args.worker and (args.gpus > 1 or args.launcher):
         return launch_ranks(args, argv)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,3 +99,43 @@ def test_gather_overflow_fails_the_run():
     p = _run(["--gpus", "2"], env_extra={"MSK144_STUB_OVERFLOW": "1"})
     assert p.returncode != 0
     assert "gather" in p.stderr and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_writes_the_timed_step_records(tmp_path):
+    """--dump-outputs DIR: one float32/float64 .npy per record field, rank 0 unprefixed, the other ranks rank<r>_; the same arguments write
+    the same arrays.  --steps sets the number of timed steps and the line reports ms_per_step."""
+    seen = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = _run(["--gpus", "2", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert out["dump_outputs"] == {"dir": str(d), "records": 5, "written": 5, "sampled": False}
+        arrays = {f.name: np.load(f) for f in sorted(d.iterdir())}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["records_channel.npy"].tolist() == [0, 1, 2, 3, 4] and arrays["rank1_records_count.npy"].tolist() == [6]
+        assert arrays["records_message.npy"].shape == (5, 10) and arrays["records_f0.npy"].dtype == np.float32
+        seen.append(arrays)
+    assert seen[0].keys() == seen[1].keys() and all(np.array_equal(seen[0][k], seen[1][k]) for k in seen[0])
+
+
+def test_dump_outputs_samples_a_list_over_the_budget(tmp_path):
+    """Over the byte budget the list is cut to a fixed, seeded sample of rows of the sorted list, and says which."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from msk144cudecoder_amd.hipdecoder import RESULT_DTYPE
+    rec = np.zeros(1000, dtype=RESULT_DTYPE)
+    rec["channel"] = np.arange(1000)[::-1] // 4
+    rec["item"] = np.arange(1000) % 4
+    rec["f0"] = np.arange(1000, dtype=np.float32)
+    got = []
+    for run in ("a", "b"):
+        s = bench.dump_outputs(str(tmp_path / run), rec, budget=4096 + 100 * 160)
+        assert s["records"] == 1000 and s["written"] == 100 and s["sampled"]
+        got.append({f.name: np.load(f) for f in sorted((tmp_path / run).iterdir())})
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) < 4096 + 100 * 160 + 13 * 128
+    idx = got[0]["records_sample_index.npy"]
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and np.array_equal(idx, got[1]["records_sample_index.npy"])
+    ch = got[0]["records_channel.npy"]
+    assert np.array_equal(ch, np.sort(rec["channel"])[idx.astype(int)]) and np.array_equal(got[0]["records_f0.npy"], got[1]["records_f0.npy"])

@@ -65,3 +65,20 @@ def test_every_slot_flag_times_the_region_with_the_hand_over_off():
     assert line["copy_handover"] == {"enabled": False, "slots_handed_over_last_step": 0, "share_of_slots": 0.0}
     assert line["config"]["copies_computed_once"] is False and "fully evaluated" in line["config"]["value_counts"]
     assert "value_every_slot_decoded" not in line and "computed again, as in the reference" in line["roofline"]["mode"]
+
+
+def test_dump_outputs_are_the_timed_step_and_repeat(tmp_path):
+    """--dump-outputs writes the records of the last TIMED step: a run with the sustained leg after it (more steps on other windows)
+    dumps the same arrays as one without, and the dump agrees with the line's count of decodes."""
+    import numpy as np
+    runs = []
+    for name, sustain in (("plain", "0"), ("sustained", "1")):
+        d = tmp_path / name
+        line = _bench(["--no-cpu-baseline", "--no-extra-legs", "--sustain-seconds", sustain, "--dump-outputs", str(d)])
+        assert line["steps"] == 5 and line["ms_per_step"] > 0
+        runs.append((line, {f.name: np.load(f) for f in sorted(d.iterdir())}))
+    (plain, a), (_, b) = runs
+    assert plain["dump_outputs"]["records"] == plain["decodes_last_step"] > 0 and not plain["dump_outputs"]["sampled"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
