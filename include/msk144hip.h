@@ -30,6 +30,9 @@
  *                            ResultItem array (result_keeper.cuh:17-32, 105-115) - the stream program never reads them
  *   msk144_set_copy_handover whether slots that fold the same frames as a lower slot of their group are computed again, as
  *   msk144_copy_count        softbits_kernel / ldpc_kernel do for every slot (softbits_kernel.cuh:56-83, ldpc_kernel.cuh:100-249)
+ *   msk144_set_wideband ..   the CPU decimation chain in front of --read-mode=2 (rtl_sdr | csdr fir_decimate_cc ... | convert_f_s8,
+ *   msk144_push_wideband     README.md of the reference), for every channel of one wideband stream at once: a down-converter
+ *                            bank on the device that writes the channels' int8 I/Q hops into the hop ring (no reference counterpart)
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -286,6 +289,61 @@ int msk144_stage_times(msk144_handle* h, float* avg_ms /*[MSK144_T_COUNT]*/, int
  * decode kernels get - the number a sustained-throughput claim needs next to its step time (DVFS: a chip that has idled for a hop
  * period starts its next batch at a lower clock).  Blocks the caller for about spin_us.  spin_us 1..100000. */
 int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz);
+
+/* ---- Wideband channeliser (no reference counterpart) ----
+ *
+ * One wideband complex stream in, `channels` 12 ksps int8 I/Q streams out, each exactly what --read-mode=2 consumes: the
+ * channeliser writes every channel's hop into the hop ring's device staging (as msk144_push_hops would have copied it), then the
+ * hop ring and the IQ front end run unchanged.
+ *
+ *   Input:        interleaved I,Q samples at Fs = D x 12000 Hz, 2 <= D <= 512 (1.92 Msps: D = 160; 2.4 Msps: D = 200), as
+ *                 cu8 (rtl_sdr, (u - 127.5) / 128), cs8 (s / 128) or cs16 (s / 32768).
+ *   Offsets:      integer Hz, |f_c| <= Fs/2 - 6000, one per channel, no grid needed.
+ *   Filter:       a real low-pass h[0..L), L = K x D, 1 <= K <= 64, supplied by the caller.  The default design (K = 16, a
+ *                 Kaiser-windowed sinc at unit DC gain: flat within 0.1 dB to 4 kHz, >= 60 dB down from 8 kHz for D in
+ *                 {40, 80, 160, 200}) is msk144host_wideband_taps in libmsk144host.so, the taps msk144hipdecoder uses.
+ *   Output:       y_c[m] = e^{-j2pi f_c m / 12000} . sum_{k<L} (h[k] e^{+j2pi f_c k / Fs}) . x[mD - k]
+ *                 - mix, filter and decimate by D - with m the 64-bit output index from the first sample of the stream,
+ *                 x[n < 0] = 0, and the phases reduced in integers, (f_c m) mod 12000 and (f_c k) mod Fs, so they do not drift.
+ *                 I and Q are q = clamp(rint(128 . gain . y), -128, 127) each (default gain 100, the csdr gain_ff stage); a
+ *                 component whose rounded value lies outside [-128, 127] counts as clipped.  f32 arithmetic on the device.
+ *   Hops:         a first push carries 5184 x D wideband samples (5184 output samples per channel), every later push 2592 x D
+ *                 (2592).  The filter history (the last L-1 input samples) and m stay on the device between pushes; a first push
+ *                 restarts the stream (m = 0, zero history).
+ *
+ *     msk144_set_wideband(h, &wp);                  read_mode 2 handle, num_offsets == channels; resets history and m
+ *     msk144_wideband_slot(h, s, &buf, &bytes);     pinned, 5184 x D samples; fill 5184 x D (first) or 2592 x D samples
+ *     msk144_push_wideband(h, s, first);            H2D + channeliser + hop ring + IQ front end on the handle's stream
+ *     msk144_decode / msk144_fetch_async / msk144_fetch_wait   as after msk144_push_hops (record channel = channel index)
+ *
+ * Stage times: in wideband mode MSK144_T_FRONTEND includes the channeliser, MSK144_T_H2D the wideband copy. */
+enum
+{
+    MSK144_WB_CU8 = 0,
+    MSK144_WB_CS8 = 1,
+    MSK144_WB_CS16 = 2
+};
+
+typedef struct msk144_wideband_params
+{
+    int64_t rate_hz;          /* Fs = D x 12000 */
+    int32_t format;           /* MSK144_WB_* */
+    int32_t taps_per_phase;   /* K */
+    float gain;               /* output gain before int8 (default 100) */
+    int32_t num_taps;         /* = K x D */
+    const double* taps;       /* h[0 .. num_taps) */
+    const int32_t* offsets_hz;/* f_c of channel 0 .. num_offsets-1 */
+    int32_t num_offsets;      /* = channels */
+} msk144_wideband_params;
+
+int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* params);
+int msk144_wideband_slot(msk144_handle* h, int32_t slot, void** buf, size_t* bytes);
+/* MSK144_ESTATE for a later push (first = 0) before any first push */
+int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first);
+/* the channel's int8 I/Q pairs of the last push: 5184 after a first push, else 2592 */
+int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out);
+/* clipped I and Q components of the last push, all channels */
+int msk144_wideband_clip_count(msk144_handle* h, int64_t* clipped);
 
 #ifdef __cplusplus
 }

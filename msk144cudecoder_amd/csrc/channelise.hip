@@ -1,0 +1,177 @@
+// channelise: the wideband down-converter bank (msk144_push_wideband).
+//
+// For channel c with offset f_c and the prototype low-pass h[0..L), L = K*D, every output sample of a push is
+//     y_c[m] = e^{-j2pi (f_c m mod 12000)/12000} * sum_k G[c][k] x[mD - k],   G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs}
+// (include/msk144hip.h).  The sum is a complex GEMM over a Hankel view of the input, computed only at the output rate.  With
+// k = p + D*q (phase p < D, q < K), x[mD - k] = xp[p][m - q] where xp[p][n] = x[nD - p]: stored phase by phase in LDS, the
+// operand a wave reads for one tap is 32 consecutive floats, so the Hankel view costs no bank conflicts.
+//
+// Tiling: one workgroup = 4 waves = 128 channels x 64 output samples.  Each wave owns 32 channels and two 32-sample halves of the
+// output tile and runs v_mfma_f32_32x32x2_f32 with the two k-slots of the instruction carrying the real and the imaginary part:
+//     Re: A[c][0] = Re G, A[c][1] = -Im G;   Im: A[c][0] = Im G, A[c][1] = Re G;   B[0][m] = Re x, B[1][m] = Im x
+// so 4 MFMAs per tap and wave (Re/Im x two halves), accumulating in f32.  The input span of the tile is converted to f32 once,
+// 32 phases at a time, and shared by the 4 waves; the taps stream from L2 (G is stored [channel/32][p][q][32], the order the
+// loop walks, so a wave reads 256 contiguous bytes per tap) and are reused across the 64 samples of the tile.
+//
+// Output: q = clamp(rint(128 * gain * y), -128, 127) for I and Q, written as int8 pairs straight into the hop ring's staging
+// (first push: samples 0..2591 into first_halves, 2592..5183 into hops; later pushes: hops).  A component counts as clipped when
+// its rounded value lies outside [-128, 127].
+#include "msk144_kernels.h"
+
+namespace msk144
+{
+
+namespace
+{
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kThreads = 256;
+constexpr int kTileChannels = 128;  // 4 waves x 32
+constexpr int kTileSamples = 64;    // 2 x 32 per wave
+constexpr int kPhaseChunk = 32;     // phases staged in LDS at a time
+constexpr int kMaxK = 64;
+constexpr int kMaxSpan = kTileSamples + kMaxK - 1;
+constexpr int kHalf = kWindowSamples / 2;  // 2592 samples per hop
+constexpr int kChannelRate = 12000;
+
+template<int FMT>
+__device__ inline float2 load_sample(const void* __restrict__ raw, int i)
+{
+    if(FMT == 0)
+    {
+        const uchar2 v = static_cast<const uchar2*>(raw)[i];
+        return make_float2((static_cast<float>(v.x) - 127.5f) * (1.0f / 128.0f), (static_cast<float>(v.y) - 127.5f) * (1.0f / 128.0f));
+    }
+    else if(FMT == 1)
+    {
+        const char2 v = static_cast<const char2*>(raw)[i];
+        return make_float2(static_cast<float>(v.x) * (1.0f / 128.0f), static_cast<float>(v.y) * (1.0f / 128.0f));
+    }
+    else
+    {
+        const short2 v = static_cast<const short2*>(raw)[i];
+        return make_float2(static_cast<float>(v.x) * (1.0f / 32768.0f), static_cast<float>(v.y) * (1.0f / 32768.0f));
+    }
+}
+
+template<int FMT>
+__global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __restrict__ raw, const float2* __restrict__ G, const int32_t* __restrict__ fmod,
+                                                              const float2* __restrict__ rot, int8_t* __restrict__ first_halves, int8_t* __restrict__ hops,
+                                                              unsigned long long* __restrict__ clip_count, int channels, int D, int K, int M, int first,
+                                                              long long m_base, float scale)
+{
+    __shared__ float xs[2][kPhaseChunk][kMaxSpan];
+
+    const int L = K * D;
+    const int hist = L - 1;              // raw[0 .. hist) = the L-1 samples before this push
+    const int n_in = hist + M * D;       // samples in raw
+    const int span = kTileSamples + K - 1;
+    const int mt0 = blockIdx.x * kTileSamples;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int j = lane & 31;
+    const int hsel = lane >> 5;          // k-slot of the MFMA: 0 = real part, 1 = imaginary part
+    const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
+    const bool active = cb32 * 32 < channels;
+    const float2* __restrict__ g = G + static_cast<size_t>(cb32) * L * 32 + j;
+
+    f32x16 acc_re0 = {}, acc_im0 = {}, acc_re1 = {}, acc_im1 = {};
+
+    for(int p0 = 0; p0 < D; p0 += kPhaseChunk)
+    {
+        const int pc = min(kPhaseChunk, D - p0);
+        __syncthreads();
+        // xp[p][n] = x at buffer index (mt0 + n + 1)*D - p - 1 (output mt0 + n - (K-1), tap p); consecutive threads take
+        // consecutive phases, i.e. consecutive (descending) input samples
+        for(int e = threadIdx.x; e < pc * span; e += kThreads)
+        {
+            const int pl = e % pc;
+            const int n = e / pc;
+            const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
+            float2 v = make_float2(0.0f, 0.0f);
+            if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
+            xs[0][pl][n] = v.x;
+            xs[1][pl][n] = v.y;
+        }
+        __syncthreads();
+        if(!active) continue;
+        const float2* __restrict__ gp = g + static_cast<size_t>(p0) * K * 32;
+        const float* __restrict__ xrow = &xs[hsel][0][j + K - 1];
+        const int T = pc * K;
+        float2 gnext = gp[0];
+        int pl = 0, q = 0;
+        for(int t = 0; t < T; t++)
+        {
+            const float2 gv = gnext;
+            if(t + 1 < T) gnext = gp[static_cast<size_t>(t + 1) * 32];
+            const float a_re = hsel ? -gv.y : gv.x;
+            const float a_im = hsel ? gv.x : gv.y;
+            const float* xr = xrow + pl * kMaxSpan - q;
+            const float b0 = xr[0];
+            const float b1 = xr[32];
+            acc_re0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b0, acc_re0, 0, 0, 0);
+            acc_im0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b0, acc_im0, 0, 0, 0);
+            acc_re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b1, acc_re1, 0, 0, 0);
+            acc_im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b1, acc_im1, 0, 0, 0);
+            if(++q == K)
+            {
+                q = 0;
+                pl++;
+            }
+        }
+    }
+    if(!active) return;
+
+    // D[row][col]: col = lane & 31 = output sample, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel within the wave
+    unsigned int clipped = 0;
+    const int half = kHalf;
+#pragma unroll
+    for(int s = 0; s < 2; s++)
+    {
+        const int mo = mt0 + s * 32 + j;
+        if(mo >= M) continue;
+        const long long m = m_base + mo;
+        const int mm = static_cast<int>(m % kChannelRate);
+        int8_t* __restrict__ dst = hops;
+        int idx = mo;
+        if(first && mo < half) dst = first_halves;
+        else if(first) idx = mo - half;
+#pragma unroll
+        for(int r = 0; r < 16; r++)
+        {
+            const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+            if(c >= channels) continue;
+            const float yr = s ? acc_re1[r] : acc_re0[r];
+            const float yi = s ? acc_im1[r] : acc_im0[r];
+            const int ph = (fmod[c] * mm) % kChannelRate;
+            const float2 e = rot[ph];
+            const float vr = rintf(scale * (yr * e.x - yi * e.y));
+            const float vi = rintf(scale * (yr * e.y + yi * e.x));
+            clipped += (vr < -128.0f || vr > 127.0f) + (vi < -128.0f || vi > 127.0f);
+            char2 o;
+            o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
+            o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
+            reinterpret_cast<char2*>(dst)[static_cast<size_t>(c) * half + idx] = o;
+        }
+    }
+    for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
+    if(lane == 0 && clipped) atomicAdd(clip_count, static_cast<unsigned long long>(clipped));
+}
+
+}  // namespace
+
+void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
+                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream)
+{
+    const dim3 grid((M + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels);
+    const float scale = 128.0f * gain;
+    if(format == 0)
+        hipLaunchKernelGGL(channelise_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+    else if(format == 1)
+        hipLaunchKernelGGL(channelise_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+    else
+        hipLaunchKernelGGL(channelise_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+}
+
+}  // namespace msk144

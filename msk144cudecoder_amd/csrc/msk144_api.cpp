@@ -5,6 +5,7 @@
 
 #include "msk144_kernels.h"
 #include "msk144_tables.h"
+#include "wideband.h"
 
 #include <hip/hip_runtime.h>
 
@@ -94,6 +95,24 @@ struct msk144_handle
     // msk144_clock_probe: its own stream, so that the probe wave runs beside the decode kernels
     hipStream_t probe_stream = nullptr;
     uint64_t* d_probe = nullptr;
+
+    // wideband channeliser (msk144_set_wideband); buffers are (re)allocated by msk144_set_wideband and freed here, not in allocs
+    struct Wideband
+    {
+        bool configured = false;
+        bool started = false;     // a first push has been made since the configuration
+        bool last_first = false;  // the last push was a first push (5184 samples per channel)
+        int D = 0, K = 0, L = 0, format = 0;
+        float gain = 0.0f;
+        long long m_next = 0;     // output sample index of the next push
+        size_t slot_bytes = 0;    // pinned bytes per slot: 5184*D samples
+        void* pinned[MSK144_SLOTS] = {};
+        void* d_raw = nullptr;    // L-1 history samples + the samples of one push, raw format
+        float2* d_G = nullptr;    // [ceil(channels/32)][D][K][32]
+        int32_t* d_fmod = nullptr;
+        float2* d_rot = nullptr;  // [12000]
+        unsigned long long* d_clip = nullptr;
+    } wb;
 
     std::string error;
 };
@@ -528,6 +547,10 @@ void msk144_destroy(msk144_handle* h)
         if(sl.is_first) (void)hipHostFree(sl.is_first);
         if(sl.done) (void)hipEventDestroy(sl.done);
     }
+    for(void* p : h->wb.pinned)
+        if(p) (void)hipHostFree(p);
+    for(void* p : {h->wb.d_raw, static_cast<void*>(h->wb.d_G), static_cast<void*>(h->wb.d_fmod), static_cast<void*>(h->wb.d_rot), static_cast<void*>(h->wb.d_clip)})
+        if(p) (void)hipFree(p);
     if(h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if(h->probe_stream) (void)hipStreamDestroy(h->probe_stream);
     for(const auto& sp : h->spans_pending)
@@ -1064,6 +1087,216 @@ int msk144_stage_times(msk144_handle* h, float* avg_ms, int32_t* samples, int32_
             h->t_cnt[s] = 0;
         }
     }
+    return MSK144_OK;
+}
+
+}  // extern "C"
+
+// ---- wideband channeliser ----
+
+namespace
+{
+
+void wb_release(msk144_handle* h)
+{
+    auto& w = h->wb;
+    for(void*& p : w.pinned)
+    {
+        if(p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+    for(void** p : {&w.d_raw, reinterpret_cast<void**>(&w.d_G), reinterpret_cast<void**>(&w.d_fmod), reinterpret_cast<void**>(&w.d_rot),
+                    reinterpret_cast<void**>(&w.d_clip)})
+    {
+        if(*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    w.configured = false;
+}
+
+int wb_malloc(msk144_handle* h, void** p, size_t bytes)
+{
+    hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+    if(e != hipSuccess)
+    {
+        *p = nullptr;
+        char buf[160];
+        snprintf(buf, sizeof(buf), "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        return fail(h, MSK144_ENOMEM, buf);
+    }
+    return MSK144_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
+{
+    if(!h || !wp) return fail(h, MSK144_EINVAL, "null argument");
+    if(h->params.read_mode != 2) return fail(h, MSK144_EINVAL, "wideband input needs an IQ handle (read_mode 2)");
+    if(wp->num_offsets != h->params.channels) return fail(h, MSK144_EINVAL, "the number of channel offsets must equal the handle's channels");
+    const std::string why = msk144wb::check_config(wp->rate_hz, wp->format, wp->taps_per_phase, wp->gain, wp->offsets_hz, wp->num_offsets);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    const int D = static_cast<int>(wp->rate_hz / msk144wb::kOutRate);
+    const int K = wp->taps_per_phase;
+    const int L = K * D;
+    if(!wp->taps || wp->num_taps != L) return fail(h, MSK144_EINVAL, "the filter needs taps_per_phase x D taps");
+    for(int k = 0; k < L; k++)
+        if(!std::isfinite(wp->taps[k])) return fail(h, MSK144_EINVAL, "filter taps must be finite");
+
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    int rc = ensure_ring(h);
+    if(rc != MSK144_OK) return rc;
+    wb_release(h);
+    auto& w = h->wb;
+    const int C = h->params.channels;
+    const int C32 = (C + 31) / 32;
+    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(wp->format));
+    w.slot_bytes = static_cast<size_t>(kWindowSamples) * D * sb;
+    for(void*& p : w.pinned)
+        if((rc = host_alloc(h, &p, w.slot_bytes)) != MSK144_OK)
+        {
+            p = nullptr;
+            wb_release(h);
+            return rc;
+        }
+    const size_t g_count = static_cast<size_t>(C32) * L * 32;
+    if((rc = wb_malloc(h, &w.d_raw, (static_cast<size_t>(L) - 1) * sb + w.slot_bytes)) != MSK144_OK ||
+       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_G), g_count * sizeof(float2))) != MSK144_OK ||
+       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_fmod), sizeof(int32_t) * C)) != MSK144_OK ||
+       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_rot), sizeof(float2) * msk144wb::kOutRate)) != MSK144_OK ||
+       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_clip), sizeof(unsigned long long))) != MSK144_OK)
+    {
+        wb_release(h);
+        return rc;
+    }
+
+    // G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs} in double, stored f32 at [c/32][p][q][c%32] with k = p + D*q; phases in integers
+    const long long fs = static_cast<long long>(wp->rate_hz);
+    std::vector<float2> G(g_count, make_float2(0.0f, 0.0f));
+    std::vector<int32_t> fmod(static_cast<size_t>(C));
+    for(int c = 0; c < C; c++)
+    {
+        const long long f = wp->offsets_hz[c];
+        fmod[static_cast<size_t>(c)] = static_cast<int32_t>(((f % msk144wb::kOutRate) + msk144wb::kOutRate) % msk144wb::kOutRate);
+        const long long fpos = ((f % fs) + fs) % fs;
+        for(int p = 0; p < D; p++)
+            for(int q = 0; q < K; q++)
+            {
+                const long long k = p + static_cast<long long>(D) * q;
+                const double ph = 2.0 * M_PI * static_cast<double>((fpos * k) % fs) / static_cast<double>(fs);
+                const double hk = wp->taps[k];
+                G[((static_cast<size_t>(c / 32) * D + p) * K + q) * 32 + (c % 32)] =
+                    make_float2(static_cast<float>(hk * std::cos(ph)), static_cast<float>(hk * std::sin(ph)));
+            }
+    }
+    std::vector<float2> rot(msk144wb::kOutRate);
+    for(int r = 0; r < msk144wb::kOutRate; r++)
+    {
+        const double ph = 2.0 * M_PI * r / msk144wb::kOutRate;
+        rot[static_cast<size_t>(r)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(-std::sin(ph)));
+    }
+    HIP_TRY(h, hipMemcpy(w.d_G, G.data(), g_count * sizeof(float2), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(w.d_fmod, fmod.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(w.d_rot, rot.data(), sizeof(float2) * rot.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
+    w.D = D;
+    w.K = K;
+    w.L = L;
+    w.format = wp->format;
+    w.gain = wp->gain;
+    w.m_next = 0;
+    w.started = false;
+    w.last_first = false;
+    w.configured = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_slot(msk144_handle* h, int32_t slot, void** buf, size_t* bytes)
+{
+    if(!h || !buf || !bytes || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
+    if(!h->wb.configured) return fail(h, MSK144_ESTATE, "msk144_wideband_slot before msk144_set_wideband");
+    *buf = h->wb.pinned[slot];
+    *bytes = h->wb.slot_bytes;
+    return MSK144_OK;
+}
+
+int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
+{
+    if(!h || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
+    auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_ESTATE, "msk144_push_wideband before msk144_set_wideband");
+    if(!first && !w.started) return fail(h, MSK144_ESTATE, "a later wideband push before the first one");
+    msk144_handle::Slot& sl = h->slots[slot];
+    if(sl.pending) return fail(h, MSK144_ESTATE, "slot submitted again before its results were fetched (msk144_fetch_wait)");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    const int C = h->params.channels;
+    const int M = first ? kWindowSamples : kHopSamples;
+    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
+    const size_t hist_bytes = (static_cast<size_t>(w.L) - 1) * sb;
+    const size_t new_bytes = static_cast<size_t>(M) * w.D * sb;
+    if(first) w.m_next = 0;
+    for(int j = 0; j < C; j++)
+    {
+        sl.streams[j] = j;
+        sl.is_first[j] = first ? 1 : 0;
+    }
+    h->call_id++;
+    h->cur_slot = slot;
+    h->active = C;
+    uint8_t* raw = static_cast<uint8_t*>(w.d_raw);
+    ev_begin(h, MSK144_T_H2D);
+    hipError_t e = hipSuccess;
+    // the filter history: the last L-1 samples of the previous push (M*D >= 2592*D >= L-1, so the ranges do not overlap)
+    if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) * w.D * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(raw + hist_bytes, w.pinned[slot], new_bytes, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * C, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, C, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemsetAsync(w.d_clip, 0, sizeof(unsigned long long), h->stream);
+    ev_end(h, MSK144_T_H2D);
+    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
+    ev_begin(h, MSK144_T_FRONTEND);
+    launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, static_cast<int8_t*>(h->d_first), static_cast<int8_t*>(h->d_hops), w.d_clip, C, w.D, w.K, M,
+                      first ? 1 : 0, w.m_next, w.gain, h->stream);
+    ev_end(h, MSK144_T_FRONTEND);
+    HIP_TRY(h, hipGetLastError());
+    w.m_next += M;
+    w.started = true;
+    w.last_first = first != 0;
+    launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, C, h->stream);
+    return run_frontend(h, h->d_input);
+}
+
+int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    if(channel < 0 || channel >= h->params.channels) return fail(h, MSK144_EINVAL, "channel out of range");
+    if(!h->wb.started) return fail(h, MSK144_ESTATE, "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t half = 2 * static_cast<size_t>(kHopSamples);
+    const uint8_t* first = static_cast<const uint8_t*>(h->d_first) + half * channel;
+    const uint8_t* hop = static_cast<const uint8_t*>(h->d_hops) + half * channel;
+    if(h->wb.last_first)
+    {
+        HIP_TRY(h, hipMemcpy(out, first, half, hipMemcpyDeviceToHost));
+        out += half;
+    }
+    HIP_TRY(h, hipMemcpy(out, hop, half, hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_wideband_clip_count(msk144_handle* h, int64_t* clipped)
+{
+    if(!h || !clipped) return fail(h, MSK144_EINVAL, "null argument");
+    if(!h->wb.configured) return fail(h, MSK144_ESTATE, "no wideband configuration");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    unsigned long long v = 0;
+    HIP_TRY(h, hipMemcpy(&v, h->wb.d_clip, sizeof(v), hipMemcpyDeviceToHost));
+    *clipped = static_cast<int64_t>(v);
     return MSK144_OK;
 }
 

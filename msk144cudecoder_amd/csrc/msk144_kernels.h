@@ -75,6 +75,13 @@ void launch_frontend_iq(const DeviceStore& st, const int8_t* d_in, hipStream_t s
 // first_halves[j] + hops[j] when is_first[j]); windows[j] = the stream's new window.  Halves and windows in raw input bytes.
 void launch_hop_ring(void* ring, const void* hops, const void* first_halves, const int32_t* streams, const uint8_t* is_first, void* windows, int n, hipStream_t stream);
 
+// wideband down-converter bank (channelise.hip): raw = the L-1 history samples then M*D new ones (format 0 cu8, 1 cs8, 2 cs16);
+// G = [ceil(channels/32)][D][K][32] taps (tap k = p + D*q at [p][q], zero rows past `channels`); fmod[c] = f_c mod 12000 in
+// 0..11999; rot[r] = e^{-j2pi r/12000}.  Writes the int8 I/Q of output samples m_base .. m_base+M-1 of every channel into the hop
+// ring staging (M = 5184 with first != 0: the first 2592 into first_halves) and adds the clipped components to *clip_count.
+void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
+                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream);
+
 // one wave that spins for `ticks` of the 100 MHz counter; out[0] = shader cycles elapsed, out[1] = 100 MHz ticks elapsed (hopring.hip)
 void launch_clock_probe(uint64_t* out, uint32_t ticks, hipStream_t stream);
 

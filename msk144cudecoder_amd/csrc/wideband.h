@@ -1,0 +1,90 @@
+// Wideband channeliser contract shared by the library (msk144_api.cpp, channelise.hip), the stream program (main.cpp) and the
+// host test library (host_capi.cpp): the rules a wideband configuration must meet and the default prototype filter.
+// Header-only, plain C++ (no HIP), so that every one of those builds gets the same taps and the same checks.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+namespace msk144wb
+{
+
+constexpr int kOutRate = 12000;        // channel output rate, samples per second
+constexpr int kMinDecimation = 2;
+constexpr int kMaxDecimation = 512;
+constexpr int kMaxTapsPerPhase = 64;   // K; L = K*D taps
+constexpr int kDefaultTapsPerPhase = 16;
+constexpr float kDefaultGain = 100.0f; // the `csdr gain_ff 100` stage of a CPU decimation chain
+constexpr int kGuardHz = 6000;         // |f_c| <= Fs/2 - 6000
+constexpr double kPassHz = 4000.0;     // design band edges of the default filter
+constexpr double kStopHz = 8000.0;
+constexpr double kKaiserBeta = 7.0;    // about 70 dB side lobes
+
+enum Format
+{
+    kCu8 = 0,   // rtl_sdr: (u - 127.5) / 128
+    kCs8 = 1,   // s / 128
+    kCs16 = 2   // s / 32768
+};
+
+inline int sample_bytes(int format) { return format == kCs16 ? 4 : 2; }
+
+inline double bessel_i0(double x)
+{
+    double sum = 1.0, term = 1.0;
+    const double q = 0.25 * x * x;
+    for(int k = 1; k < 200; k++)
+    {
+        term *= q / (static_cast<double>(k) * k);
+        sum += term;
+        if(term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+// Default prototype low-pass, L = K*D taps at Fs = D*12000: a Kaiser-windowed sinc with its cut-off half way between the 4 kHz
+// pass edge and the 8 kHz stop edge, scaled to unit DC gain.  Symmetric about (L-1)/2.
+inline std::vector<double> design_taps(int D, int K)
+{
+    const int L = K * D;
+    const double fs = static_cast<double>(D) * kOutRate;
+    const double fc = 0.5 * (kPassHz + kStopHz) / fs;  // cycles per sample
+    const double mid = 0.5 * (L - 1);
+    const double i0b = bessel_i0(kKaiserBeta);
+    std::vector<double> h(static_cast<size_t>(L));
+    double sum = 0.0;
+    for(int k = 0; k < L; k++)
+    {
+        const double t = k - mid;
+        const double arg = 2.0 * fc * t;
+        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
+        const double r = L > 1 ? t / mid : 0.0;
+        const double w = bessel_i0(kKaiserBeta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
+        h[static_cast<size_t>(k)] = sinc * w;
+        sum += h[static_cast<size_t>(k)];
+    }
+    for(double& v : h) v /= sum;
+    return h;
+}
+
+// Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
+inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
+{
+    if(rate_hz <= 0 || rate_hz % kOutRate != 0) return "wideband rate must be a positive multiple of 12000 Hz";
+    const int64_t D = rate_hz / kOutRate;
+    if(D < kMinDecimation || D > kMaxDecimation) return "wideband rate must be D x 12000 Hz with 2 <= D <= 512";
+    if(format != kCu8 && format != kCs8 && format != kCs16) return "wideband format must be cu8, cs8 or cs16";
+    if(K < 1 || K > kMaxTapsPerPhase) return "taps per phase must be 1..64";
+    if(!(gain > 0.0f) || !std::isfinite(gain)) return "wideband gain must be a positive finite number";
+    if(count < 1 || !offsets) return "at least one channel offset is needed";
+    const int64_t lim = rate_hz / 2 - kGuardHz;
+    for(int i = 0; i < count; i++)
+        if(std::llabs(static_cast<long long>(offsets[i])) > lim)
+            return "channel offset " + std::to_string(offsets[i]) + " Hz is outside +-(rate/2 - 6000) = +-" + std::to_string(lim) + " Hz";
+    return std::string();
+}
+
+}  // namespace msk144wb

@@ -30,7 +30,15 @@ ABI_SYMBOLS = (
     "msk144_input_slot", "msk144_submit_slot", "msk144_submit_slot_n", "msk144_fetch_async", "msk144_fetch_wait", "msk144_hop_slot", "msk144_push_hops",
     "msk144_device_count", "msk144_clock_probe", "msk144_set_copy_handover", "msk144_copy_handover", "msk144_copy_count",
     "msk144_set_llr_retention", "msk144_llr_block_channels",
+    "msk144_set_wideband", "msk144_wideband_slot", "msk144_push_wideband", "msk144_dump_wideband_hop", "msk144_wideband_clip_count",
 )
+
+WB_FORMATS = {"cu8": 0, "cs8": 1, "cs16": 2}   # msk144_wideband_params.format
+
+
+class WidebandParams(C.Structure):
+    _fields_ = [("rate_hz", C.c_int64), ("format", C.c_int32), ("taps_per_phase", C.c_int32), ("gain", C.c_float), ("num_taps", C.c_int32),
+                ("taps", C.POINTER(C.c_double)), ("offsets_hz", C.POINTER(C.c_int32)), ("num_offsets", C.c_int32)]
 
 
 class Params(C.Structure):
@@ -117,6 +125,11 @@ def load_library(path: Optional[str] = None):
     L.msk144_llr_block_channels.argtypes = [vp, C.POINTER(i32)]
     L.msk144_copy_handover.argtypes = [vp, C.POINTER(i32)]
     L.msk144_copy_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.msk144_set_wideband.argtypes = [vp, C.POINTER(WidebandParams)]
+    L.msk144_wideband_slot.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.msk144_push_wideband.argtypes = [vp, i32, i32]
+    L.msk144_dump_wideband_hop.argtypes = [vp, i32, vp]
+    L.msk144_wideband_clip_count.argtypes = [vp, C.POINTER(C.c_int64)]
     if path is None:
         _lib = L
     return L
@@ -295,6 +308,52 @@ class HipDecoder:
         records = np.frombuffer((C.c_uint8 * (n.value * RESULT_DTYPE.itemsize)).from_address(rec.value), dtype=RESULT_DTYPE).copy() if n.value else np.zeros(0, dtype=RESULT_DTYPE)
         powers = np.frombuffer((C.c_float * (8 * self.channels)).from_address(seg.value), dtype=np.float32).reshape(self.channels, 8).copy()
         return records, powers
+
+    # ---- wideband channeliser (read_mode 2 handles) ----
+    def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0):
+        """Configure the down-converter bank: one channel per offset (len == channels).  taps=None: the default design of
+        libmsk144host.so (msk144cudecoder_amd.wideband.default_taps)."""
+        if taps is None:
+            from .wideband import default_taps
+            taps = default_taps(int(rate_hz) // 12000, taps_per_phase)
+        self._wb_taps = np.ascontiguousarray(taps, dtype=np.float64)
+        self._wb_offsets = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+        self._wb_format = fmt
+        self._wb_D = int(rate_hz) // 12000
+        wp = WidebandParams(int(rate_hz), WB_FORMATS[fmt], int(taps_per_phase), float(gain), len(self._wb_taps),
+                            self._wb_taps.ctypes.data_as(C.POINTER(C.c_double)), self._wb_offsets.ctypes.data_as(C.POINTER(C.c_int32)),
+                            len(self._wb_offsets))
+        self._chk(self.L.msk144_set_wideband(self.h, C.byref(wp)))
+
+    def wideband_slot(self, slot: int) -> np.ndarray:
+        """The slot's pinned wideband buffer as a numpy view of raw sample components (uint8 / int8 / int16, I,Q interleaved)."""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._chk(self.L.msk144_wideband_slot(self.h, slot, C.byref(ptr), C.byref(nbytes)))
+        dt = {"cu8": np.uint8, "cs8": np.int8, "cs16": np.int16}[self._wb_format]
+        return np.frombuffer((C.c_uint8 * nbytes.value).from_address(ptr.value), dtype=dt)
+
+    def push_wideband(self, slot: int, samples: Optional[np.ndarray] = None, first: bool = False):
+        """samples (raw components, 2*5184*D for a first push, else 2*2592*D) are copied into the slot first when given."""
+        if samples is not None:
+            buf = self.wideband_slot(slot)
+            a = np.asarray(samples).reshape(-1)
+            want = 2 * (5184 if first else 2592) * self._wb_D
+            if a.size != want:
+                raise ValueError(f"a {'first' if first else 'later'} push carries {want} components, got {a.size}")
+            buf[:want] = a
+        self._chk(self.L.msk144_push_wideband(self.h, slot, 1 if first else 0))
+        self._wb_last_first = bool(first)
+
+    def dump_wideband_hop(self, channel: int) -> np.ndarray:
+        """int8 [n][2] I/Q of the channel's last push (n = 5184 after a first push, else 2592)."""
+        out = np.empty((5184 if getattr(self, "_wb_last_first", True) else 2592, 2), dtype=np.int8)
+        self._chk(self.L.msk144_dump_wideband_hop(self.h, channel, _ptr(out)))
+        return out
+
+    def wideband_clip_count(self) -> int:
+        v = C.c_int64()
+        self._chk(self.L.msk144_wideband_clip_count(self.h, C.byref(v)))
+        return int(v.value)
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

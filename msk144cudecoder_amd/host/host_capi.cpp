@@ -2,12 +2,23 @@
 #include "window_decoder.h"
 
 #include "../csrc/msk144_tables.h"
+#include "../csrc/wideband.h"
 
 #include <cstring>
 
 using namespace msk144host;
 
 extern "C" {
+
+// The default wideband prototype filter (csrc/wideband.h), L = K*D taps into out; returns L, or -1 for D outside 2..512 / K outside
+// 1..64.  The same taps msk144hipdecoder hands to msk144_set_wideband.
+int msk144host_wideband_taps(int D, int K, double* out)
+{
+    if(D < msk144wb::kMinDecimation || D > msk144wb::kMaxDecimation || K < 1 || K > msk144wb::kMaxTapsPerPhase) return -1;
+    const std::vector<double> h = msk144wb::design_taps(D, K);
+    if(out) std::memcpy(out, h.data(), sizeof(double) * h.size());
+    return static_cast<int>(h.size());
+}
 
 void* msk144host_table_new() { return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }

@@ -64,6 +64,12 @@ void show_help(const char* prog)
     std::cout << "                   --max-results=N             Capacity of the per-hop decode list of a device (default 256 per stream + 131072). A hop that exceeds it is cut and reported; decoding goes on." << std::endl;
     std::cout << "                   --every-slot                Demodulate and decode every candidate slot on its own, as the reference does. Default off: a slot whose position folds the same frames as a lower slot of its group reports that slot's result (same output), and a candidate the nbadsync gate drops is not demodulated beyond its sync check." << std::endl;
     std::cout << "                   --timing                    With --inputs: per-hop host and device time split (ingest, H2D, GPU, D2H, post-processing) on stderr at the end." << std::endl;
+    std::cout << "                   --wideband-rate=HZ          Read ONE wideband I/Q stream on stdin at HZ = D x 12000 (2 <= D <= 512, e.g. 1920000) and channelise it on the GPU into one 12000 sps IQ stream per channel offset (as --read-mode=2 would read it); lines carry ch=<index>." << std::endl;
+    std::cout << "                   --wideband-format=FMT       cu8 (rtl_sdr), cs8 or cs16 interleaved I,Q. Default=cu8." << std::endl;
+    std::cout << "                   --channel-offsets=F1,F2,... Channel centres in integer Hz from the wideband centre, |F| <= HZ/2 - 6000." << std::endl;
+    std::cout << "                   --channel-grid=F:STEP:N     The same as N offsets F, F+STEP, ..." << std::endl;
+    std::cout << "                   --wideband-gain=G           Gain before each channel's int8 I/Q (the csdr gain_ff stage). Default=100." << std::endl;
+    std::cout << "                   --taps-per-phase=K          Channel filter length K x D taps (1..64). Default=16." << std::endl;
     // clang-format on
 }
 
@@ -143,6 +149,8 @@ int main(int argc, char* const argv[])
     bool timing = false;
     std::vector<std::string> input_paths;
     std::vector<std::string> device_list;
+    bool read_mode_set = false;
+    WidebandOptions wbo;
 
     static struct option long_options[] = {{"help", no_argument, 0, 0},
                                            {"center-frequency", required_argument, 0, 0},
@@ -166,6 +174,12 @@ int main(int argc, char* const argv[])
                                            {"devices", required_argument, 0, 0},
                                            {"max-results", required_argument, 0, 0},
                                            {"every-slot", no_argument, 0, 0},
+                                           {"wideband-rate", required_argument, 0, 0},
+                                           {"wideband-format", required_argument, 0, 0},
+                                           {"channel-offsets", required_argument, 0, 0},
+                                           {"channel-grid", required_argument, 0, 0},
+                                           {"wideband-gain", required_argument, 0, 0},
+                                           {"taps-per-phase", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -180,7 +194,7 @@ int main(int argc, char* const argv[])
         case 2: opt.step_hz = static_cast<float>(atof(optarg)); break;
         case 3: opt.width_hz = static_cast<float>(atof(optarg)); break;
         case 4: opt.scan_depth = atoi(optarg); break;
-        case 5: opt.read_mode = atoi(optarg); break;
+        case 5: opt.read_mode = atoi(optarg); read_mode_set = true; break;
         case 6: opt.analytic_method = atoi(optarg); break;
         case 7: opt.nbadsync_threshold = atoi(optarg); break;
         case 8: opt.reference_cache_quirk = false; break;
@@ -208,8 +222,51 @@ int main(int argc, char* const argv[])
         case 19: split_list(optarg, device_list); break;
         case 20: opt.max_results = atoi(optarg); break;
         case 21: opt.every_slot = true; break;
+        case 22:
+        case 23:
+        case 24:
+        case 25:
+        case 26:
+        case 27:
+        {
+            wbo.any_option = true;
+            long long v = 0;
+            bool good = true;
+            if(idx == 22) good = parse_int(optarg, v) && (wbo.rate_hz = v) > 0;
+            else if(idx == 23) good = parse_wideband_format(optarg, wbo.format);
+            else if(idx == 24) good = parse_offset_list(optarg, wbo.offsets), wbo.offset_sources++;
+            else if(idx == 25) good = parse_offset_grid(optarg, wbo.offsets), wbo.offset_sources++;
+            else if(idx == 26)
+            {
+                char* end = nullptr;
+                wbo.gain = std::strtof(optarg, &end);
+                good = end && *end == 0 && end != optarg;
+            }
+            else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
+            if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + optarg + "'";
+            break;
+        }
         default: show_help(argv[0]); return 0;
         }
+    }
+
+    // --wideband-rate: checked in full before anything touches the library
+    const bool wideband = wbo.any_option;
+    if(wideband)
+    {
+        std::string why;
+        if(!input_paths.empty() || interleaved != 0 || !device_list.empty())
+            why = "--wideband-rate decodes the channels of one stdin stream on one device: it excludes --inputs, --inputs-file, --interleaved and --devices";
+        else if(read_mode_set && opt.read_mode != 2)
+            why = "--wideband-rate produces IQ channels: it excludes --read-mode=" + std::to_string(opt.read_mode);
+        else
+            why = check_wideband_options(wbo);
+        if(!why.empty())
+        {
+            std::cerr << why << std::endl;
+            return 2;
+        }
+        opt.read_mode = 2;
     }
 
     if(!center_set)
@@ -235,8 +292,18 @@ int main(int argc, char* const argv[])
         std::cerr << "--interleaved=N takes N >= 1 streams from stdin and excludes --inputs" << std::endl;
         return 2;
     }
-    const bool batched = interleaved > 0 || !input_paths.empty();
-    const int nch = interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
+    WidebandApi wb_api;
+    if(wideband)
+    {
+        std::string err;
+        if(!wb_api.load(err))
+        {
+            std::cerr << "msk144hip: " << err << std::endl;
+            return 2;
+        }
+    }
+    const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
+    const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
     opt.profile = timing && batched;
     {
         // one descriptor per stream plus what the runtime opens: lift the soft limit when the hard limit allows
@@ -324,7 +391,30 @@ int main(int argc, char* const argv[])
               << std::endl;
     std::cerr << "msk144hipdecoder: " << F << " frequency hypotheses x " << D << " patterns x 8 = " << F * D * 8 << " candidates per window; HIP workgroups per window: scan "
               << F << " x 512, softbits " << F << " x 512, LDPC one wave per gated candidate" << std::endl;
-    if(batched) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
+    if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
+    if(wideband)
+    {
+        const int Dw = static_cast<int>(wbo.rate_hz / msk144wb::kOutRate);
+        static const char* fmt_names[] = {"cu8", "cs8", "cs16"};
+        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, decimation " << Dw << ", filter " << wbo.taps_per_phase << " x " << Dw
+                  << " taps, gain " << wbo.gain << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
+        for(int c = 0; c < nch; c++) std::cerr << "msk144hipdecoder: ch=" << c << " offset " << wbo.offsets[static_cast<size_t>(c)] << " Hz" << std::endl;
+        const std::vector<double> taps = msk144wb::design_taps(Dw, wbo.taps_per_phase);
+        msk144_wideband_params wp{};
+        wp.rate_hz = wbo.rate_hz;
+        wp.format = wbo.format;
+        wp.taps_per_phase = wbo.taps_per_phase;
+        wp.gain = wbo.gain;
+        wp.num_taps = static_cast<int32_t>(taps.size());
+        wp.taps = taps.data();
+        wp.offsets_hz = wbo.offsets.data();
+        wp.num_offsets = nch;
+        if(wb_api.set(dec.handle(), &wp) != MSK144_OK)
+        {
+            std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+            return 2;
+        }
+    }
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
@@ -396,7 +486,8 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
-        if(interleaved > 0) loops[i]->use_feed();
+        if(wideband) loops[i]->use_wideband(&wb_api);
+        else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
         {
             std::cerr << loops[i]->error() << std::endl;
@@ -413,7 +504,29 @@ int main(int argc, char* const argv[])
     const auto run_since = Clock::now();
     for(auto& l : loops) l->start();
 
-    if(interleaved > 0)
+    if(wideband)
+    {
+        // one push per hop on stdin: 5184 x D wideband samples, then 2592 x D
+        const size_t wb_sample = static_cast<size_t>(msk144wb::sample_bytes(wbo.format));
+        const size_t Dw = static_cast<size_t>(wbo.rate_hz / msk144wb::kOutRate);
+        std::vector<unsigned char> block;
+        bool first_block = true;
+        while(!g_stop_requested.load(std::memory_order_relaxed))
+        {
+            block.resize((first_block ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES) * Dw * wb_sample);
+            const size_t got = read_stdin(block.data(), block.size());
+            if(g_stop_requested.load(std::memory_order_relaxed)) break;
+            if(got != block.size())
+            {
+                printer.log("Incomplete read error. rc=" + std::to_string(got / wb_sample));
+                break;
+            }
+            if(!loops[0]->feed_raw(block.data(), block.size())) break;
+            first_block = false;
+        }
+        loops[0]->feed_end();
+    }
+    else if(interleaved > 0)
     {
         // one block per hop on stdin: the hop of stream 0, then of stream 1, ... (the reference's fread, but interruptible); every
         // loop receives the slice of its own streams.  A stop request ends the reader at the next block boundary at the latest: the
@@ -469,6 +582,13 @@ int main(int argc, char* const argv[])
                       << ls.hops << " stream hops, " << ls.late << " late, worst latency " << ls.worst_ms << " ms" << std::endl;
     }
     std::cerr << "msk144hipdecoder: " << batches << " batches, " << total_hops << " stream hops, " << total_late << " late, worst latency " << worst << " ms" << std::endl;
+    if(wideband)
+    {
+        const long long clipped = loops[0]->wideband_clipped(), all = loops[0]->wideband_components();
+        std::cerr << "msk144hipdecoder: wideband: " << clipped << " of " << all << " channel I/Q components clipped to int8";
+        if(all) std::cerr << " (" << 100.0 * static_cast<double>(clipped) / static_cast<double>(all) << " %)";
+        std::cerr << (clipped ? "; lower --wideband-gain" : "") << std::endl;
+    }
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {

@@ -141,6 +141,16 @@ void DeviceLoop::start()
 
 bool DeviceLoop::feed(const unsigned char* data, size_t bytes_per_stream)
 {
+    return enqueue(data, bytes_per_stream * static_cast<size_t>(nch_), bytes_per_stream);
+}
+
+bool DeviceLoop::feed_raw(const unsigned char* data, size_t bytes)
+{
+    return enqueue(data, bytes, 0);
+}
+
+bool DeviceLoop::enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream)
+{
     std::unique_lock<std::mutex> lk(feed_mu_);
     // back-pressure: at most two blocks queued.  The wait wakes every 50 ms for the stop flag (set from a signal handler, which
     // cannot notify a condition variable).
@@ -154,7 +164,7 @@ bool DeviceLoop::feed(const unsigned char* data, size_t bytes_per_stream)
         if(feed_q_.size() < 2) break;
         wait_50ms(feed_cv_, lk);
     }
-    feed_q_.emplace_back(data, data + bytes_per_stream * static_cast<size_t>(nch_));
+    feed_q_.emplace_back(data, data + bytes);
     feed_bytes_.push_back(bytes_per_stream);
     lk.unlock();
     feed_cv_.notify_all();
@@ -194,7 +204,60 @@ int DeviceLoop::join()
         if(s.worst_ms > stats_.worst_ms) stats_.worst_ms = s.worst_ms;
     }
     if(!failed && dec_.ok()) stats_.have_device_ms = dec_.stage_times(stats_.device_ms);
+    if(!failed && wb_ && wb_pending_components_)
+    {
+        int64_t clipped = 0;
+        if(wb_->clip(dec_.handle(), &clipped) == MSK144_OK) wb_clipped_ += clipped;
+        wb_components_ += wb_pending_components_;
+        wb_pending_components_ = 0;
+    }
     return failed ? 2 : 0;
+}
+
+// --wideband-rate: copy the push into the slot's pinned wideband buffer and run channeliser + decode on it.  The clip count of the
+// previous push is read first (it waits for that push's kernels; the GPU runs the hops one after another anyway).
+bool DeviceLoop::submit_wideband(Batch& b)
+{
+    const auto a0 = Clock::now();
+    void* buf = nullptr;
+    size_t cap = 0;
+    if(wb_->slot(dec_.handle(), b.slot, &buf, &cap) != MSK144_OK || wb_block_.size() > cap)
+    {
+        fail(wb_block_.size() > cap ? std::string("wideband push larger than the slot") : std::string(msk144_last_error(dec_.handle())));
+        return false;
+    }
+    if(wb_pending_components_)
+    {
+        int64_t clipped = 0;
+        if(wb_->clip(dec_.handle(), &clipped) != MSK144_OK)
+        {
+            fail(msk144_last_error(dec_.handle()));
+            return false;
+        }
+        wb_clipped_ += clipped;
+        wb_components_ += wb_pending_components_;
+    }
+    memcpy(buf, wb_block_.data(), wb_block_.size());
+    const bool first = wb_first_;
+    wb_pending_components_ = 2ll * nch_ * (first ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES);
+    for(int c = 0; c < nch_; c++)
+    {
+        Stream& s = st_[c];
+        b.streams.push_back(c);
+        b.ready_at.push_back(s.ready_at);
+        s.first = false;
+        s.ready = false;
+    }
+    const auto a1 = Clock::now();
+    if(!dec_.submit_wideband(b.slot, first, wb_->push))
+    {
+        fail(dec_.error());
+        return false;
+    }
+    wb_first_ = false;
+    b.assemble_ms = ms_between(a0, a1);
+    b.submit_ms = ms_between(a1, Clock::now());
+    return true;
 }
 
 DeviceLoop::StreamReport DeviceLoop::stream_report(int local) const
@@ -242,6 +305,18 @@ bool DeviceLoop::take_fed_block(int& open_streams)
         return false;
     }
     const auto now = Clock::now();
+    if(wb_)
+    {
+        // one wideband push: the channeliser makes every stream's hop on the device
+        wb_block_ = std::move(block);
+        for(Stream& st : st_)
+        {
+            st.ready = true;
+            st.ready_at = now;
+        }
+        open_streams = nch_;
+        return true;
+    }
     for(int c = 0; c < nch_; c++)
     {
         st_[c].pending.assign(block.begin() + static_cast<long>(per * c), block.begin() + static_cast<long>(per * (c + 1)));
@@ -391,6 +466,19 @@ void DeviceLoop::ingest_main()
         // 4. hand the new samples of every stream that has a hop to the library, packed back to back in the pinned slot: 2592 per
         // stream (all 5184 of a stream's first hop).  The 50 %-overlap window of each stream (main.cu:284-288) lives on the device
         // (msk144_push_hops); streams without a hop sit this batch out and cost nothing on the GPU
+        if(wb_)
+        {
+            if(!submit_wideband(b))
+                break;
+            stats_.ingest.add(ingest_busy_ms);
+            ingest_busy_ms = 0.0;
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                in_flight_.push_back(std::move(b));
+            }
+            cv_.notify_all();
+            continue;
+        }
         const auto a0 = Clock::now();
         WindowDecoder::HopStage& hs = stage_[b.slot];
         for(int c = 0; c < nch_; c++)

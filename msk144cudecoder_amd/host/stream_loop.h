@@ -9,6 +9,7 @@
 // local index.
 #pragma once
 
+#include "wideband_cli.h"
 #include "window_decoder.h"
 
 #include <atomic>
@@ -89,12 +90,20 @@ public:
     bool open_inputs(const std::vector<std::string>& paths);
     // --interleaved: the hops arrive through feed() instead (one reader thread splits stdin between the loops)
     void use_feed() { fed_ = true; }
+    // --wideband-rate: the blocks arrive through feed_raw() and are wideband samples - one push of the channeliser, which writes
+    // the hop of every stream of this loop on the device (msk144_set_wideband has been called on decoder().handle())
+    void use_wideband(const WidebandApi* api) { fed_ = true; wb_ = api; }
 
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
     // window afterwards).  Blocks while two blocks are already queued (back-pressure into the reader).  false once the loop failed.
     bool feed(const unsigned char* data, size_t bytes_per_stream);
     void feed_end();
+    // --wideband-rate: one push of raw wideband samples (5184 x D the first time, 2592 x D afterwards)
+    bool feed_raw(const unsigned char* data, size_t bytes);
+    // clipped I/Q components of the channeliser output over the run, and all components written (valid after join())
+    long long wideband_clipped() const { return wb_clipped_; }
+    long long wideband_components() const { return wb_components_; }
     int join();  // 0, or 2 after a library failure (already logged)
 
     const LoopStats& stats() const { return stats_; }
@@ -138,6 +147,8 @@ private:
     void drain_descriptors(int& open_streams);
     bool take_fed_block(int& open_streams);
     void fail(const std::string& what);
+    bool enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream);
+    bool submit_wideband(Batch& b);
 
     WindowDecoder dec_;
     const int nch_, base_, device_;
@@ -145,6 +156,10 @@ private:
     LinePrinter& out_;
     std::string error_;
     bool fed_ = false;
+    const WidebandApi* wb_ = nullptr;
+    std::vector<unsigned char> wb_block_;  // the push the ingest thread has taken from the queue
+    bool wb_first_ = true;
+    long long wb_clipped_ = 0, wb_components_ = 0, wb_pending_components_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;
     std::vector<Stream> st_;

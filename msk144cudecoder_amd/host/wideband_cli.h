@@ -1,0 +1,111 @@
+// msk144hipdecoder --wideband-rate: option parsing and the library entries of the wideband channeliser.  Header-only: the entries
+// are resolved with dlsym when the option is given, so a program built against a library without them still links and runs in
+// every other mode.
+#pragma once
+
+#include "../../include/msk144hip.h"
+#include "../csrc/wideband.h"
+
+#include <dlfcn.h>
+
+#include <cerrno>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+namespace msk144host
+{
+
+struct WidebandApi
+{
+    int (*set)(msk144_handle*, const msk144_wideband_params*) = nullptr;
+    int (*slot)(msk144_handle*, int32_t, void**, size_t*) = nullptr;
+    int (*push)(msk144_handle*, int32_t, int32_t) = nullptr;
+    int (*clip)(msk144_handle*, int64_t*) = nullptr;
+
+    bool load(std::string& err)
+    {
+        set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
+        slot = reinterpret_cast<decltype(slot)>(dlsym(RTLD_DEFAULT, "msk144_wideband_slot"));
+        push = reinterpret_cast<decltype(push)>(dlsym(RTLD_DEFAULT, "msk144_push_wideband"));
+        clip = reinterpret_cast<decltype(clip)>(dlsym(RTLD_DEFAULT, "msk144_wideband_clip_count"));
+        if(set && slot && push && clip) return true;
+        err = "the loaded libmsk144hip has no wideband channeliser (msk144_set_wideband)";
+        return false;
+    }
+};
+
+struct WidebandOptions
+{
+    long long rate_hz = 0;  // 0: not in wideband mode
+    int format = msk144wb::kCu8;
+    int taps_per_phase = msk144wb::kDefaultTapsPerPhase;
+    float gain = msk144wb::kDefaultGain;
+    std::vector<int32_t> offsets;
+    bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
+    int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
+    std::string parse_error;  // first malformed value
+};
+
+inline bool parse_int(const std::string& s, long long& v)
+{
+    if(s.empty()) return false;
+    char* end = nullptr;
+    errno = 0;
+    v = std::strtoll(s.c_str(), &end, 10);
+    return errno == 0 && end && *end == 0;
+}
+
+inline bool parse_wideband_format(const std::string& s, int& fmt)
+{
+    if(s == "cu8") fmt = msk144wb::kCu8;
+    else if(s == "cs8") fmt = msk144wb::kCs8;
+    else if(s == "cs16") fmt = msk144wb::kCs16;
+    else return false;
+    return true;
+}
+
+// "f1,f2,..." in integer Hz
+inline bool parse_offset_list(const std::string& list, std::vector<int32_t>& out)
+{
+    size_t a = 0;
+    while(a <= list.size())
+    {
+        const size_t b = list.find(',', a);
+        long long v = 0;
+        if(!parse_int(list.substr(a, b == std::string::npos ? std::string::npos : b - a), v) || v < INT32_MIN || v > INT32_MAX) return false;
+        out.push_back(static_cast<int32_t>(v));
+        if(b == std::string::npos) break;
+        a = b + 1;
+    }
+    return !out.empty();
+}
+
+// "first:step:count" -> first, first+step, ... (count >= 1)
+inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out)
+{
+    const size_t a = spec.find(':');
+    const size_t b = a == std::string::npos ? a : spec.find(':', a + 1);
+    long long first = 0, step = 0, count = 0;
+    if(b == std::string::npos || !parse_int(spec.substr(0, a), first) || !parse_int(spec.substr(a + 1, b - a - 1), step) || !parse_int(spec.substr(b + 1), count))
+        return false;
+    if(count < 1 || count > 1000000) return false;
+    for(long long i = 0; i < count; i++)
+    {
+        const long long f = first + i * step;
+        if(f < INT32_MIN || f > INT32_MAX) return false;
+        out.push_back(static_cast<int32_t>(f));
+    }
+    return true;
+}
+
+// every rule the program checks before it touches the library; empty = valid
+inline std::string check_wideband_options(const WidebandOptions& w)
+{
+    if(!w.parse_error.empty()) return w.parse_error;
+    if(w.rate_hz <= 0) return "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
+    if(w.offset_sources != 1) return "--wideband-rate needs exactly one of --channel-offsets=f1,f2,... or --channel-grid=first:step:count";
+    return msk144wb::check_config(w.rate_hz, w.format, w.taps_per_phase, w.gain, w.offsets.data(), static_cast<int>(w.offsets.size()));
+}
+
+}  // namespace msk144host

@@ -132,6 +132,21 @@ bool WindowDecoder::submit_hops(int slot, int n)
     return true;
 }
 
+bool WindowDecoder::submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t))
+{
+    streams_[slot].resize(static_cast<size_t>(opt_.channels));
+    for(int c = 0; c < opt_.channels; c++) streams_[slot][static_cast<size_t>(c)] = c;
+    int rc = push(handle_, slot, first ? 1 : 0);
+    if(rc == MSK144_OK) rc = msk144_decode(handle_);
+    if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
+    if(rc != MSK144_OK)
+    {
+        error_ = msk144_last_error(handle_);
+        return false;
+    }
+    return true;
+}
+
 bool WindowDecoder::submit(int slot, const std::vector<int>& streams)
 {
     streams_[slot] = streams;

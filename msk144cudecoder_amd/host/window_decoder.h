@@ -111,6 +111,10 @@ public:
     };
     bool hop_stage(int slot, HopStage& out);
     bool submit_hops(int slot, int n);  // the first n entries of the slot's hop stage
+    // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
+    // it at run time): every stream, in order
+    bool submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t));
+    msk144_handle* handle() const { return handle_; }
     void* stage(int slot);
     bool submit(int slot, const std::vector<int>& streams);
     bool collect(int slot, std::vector<std::vector<FilteredResult>>& lines, HopTiming* timing = nullptr);

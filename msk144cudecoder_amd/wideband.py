@@ -1,0 +1,200 @@
+"""Wideband channeliser: float64 numpy model of the contract in include/msk144hip.h, sample-format readers and writers, and a
+wideband scene synthesiser.
+
+The model is the yardstick the device channeliser (csrc/channelise.hip) is tested against: the same prototype taps (the default
+design comes from libmsk144host.so, csrc/wideband.h), the same integer phase reduction, the same int8 quantisation - only in
+float64 where the device computes in f32.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import synth
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
+HOST_LIB = os.path.join(_PKG, "libmsk144host.so")
+
+OUT_RATE = 12000
+FIRST_OUT = 5184   # output samples per channel of a first push
+HOP_OUT = 2592     # ... of every later push
+FORMATS = ("cu8", "cs8", "cs16")
+_RAW_DTYPE = {"cu8": np.uint8, "cs8": np.int8, "cs16": np.int16}
+
+_host = None
+
+
+def _host_lib():
+    global _host
+    if _host is None:
+        if not os.path.exists(HOST_LIB):
+            raise FileNotFoundError(f"{HOST_LIB} not found: build it with `make -C msk144cudecoder_amd/host`")
+        L = C.CDLL(HOST_LIB)
+        L.msk144host_wideband_taps.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.msk144host_wideband_taps.restype = C.c_int
+        _host = L
+    return _host
+
+
+def default_taps(D: int, K: int = 16) -> np.ndarray:
+    """The default prototype low-pass (K*D taps at D*12000 Hz), exactly what the program hands to the library."""
+    L = _host_lib()
+    n = L.msk144host_wideband_taps(int(D), int(K), None)
+    if n < 0:
+        raise ValueError(f"no default filter for D={D}, K={K} (D 2..512, K 1..64)")
+    h = np.empty(n, dtype=np.float64)
+    L.msk144host_wideband_taps(int(D), int(K), h.ctypes.data_as(C.c_void_p))
+    return h
+
+
+# ---- sample formats ----
+
+def read_samples(raw, fmt: str) -> np.ndarray:
+    """Interleaved I,Q components (bytes or array) -> complex128: cu8 (u - 127.5)/128, cs8 s/128, cs16 s/32768."""
+    a = np.frombuffer(raw, dtype=_RAW_DTYPE[fmt]) if isinstance(raw, (bytes, bytearray, memoryview)) else np.asarray(raw, dtype=_RAW_DTYPE[fmt])
+    a = a.astype(np.float64).reshape(-1, 2)
+    if fmt == "cu8":
+        a = (a - 127.5) / 128.0
+    elif fmt == "cs8":
+        a = a / 128.0
+    else:
+        a = a / 32768.0
+    return a[:, 0] + 1j * a[:, 1]
+
+
+def write_samples(x: np.ndarray, fmt: str) -> np.ndarray:
+    """complex -> interleaved raw components in `fmt` (rounded and clipped), the inverse of read_samples."""
+    x = np.asarray(x)
+    v = np.empty(2 * len(x), dtype=np.float64)
+    v[0::2], v[1::2] = x.real, x.imag
+    if fmt == "cu8":
+        return np.clip(np.rint(v * 128.0 + 127.5), 0, 255).astype(np.uint8)
+    if fmt == "cs8":
+        return np.clip(np.rint(v * 128.0), -128, 127).astype(np.int8)
+    return np.clip(np.rint(v * 32768.0), -32768, 32767).astype(np.int16)
+
+
+# ---- the channeliser model ----
+
+def tap_matrix(rate_hz: int, offsets_hz: Sequence[int], taps: np.ndarray) -> np.ndarray:
+    """G[c][k] = h[k] e^{+j2pi ((f_c k) mod Fs)/Fs}, phases reduced in integers."""
+    fs = int(rate_hz)
+    k = np.arange(len(taps), dtype=np.int64)
+    f = np.mod(np.asarray(offsets_hz, dtype=np.int64), fs)
+    ph = np.mod(f[:, None] * k[None, :], fs).astype(np.float64) * (2.0 * np.pi / fs)
+    return taps[None, :] * np.exp(1j * ph)
+
+
+def output_rotation(offsets_hz: Sequence[int], m: np.ndarray) -> np.ndarray:
+    """e^{-j2pi ((f_c m) mod 12000)/12000}, [channel][sample]."""
+    f = np.mod(np.asarray(offsets_hz, dtype=np.int64), OUT_RATE)
+    mm = np.mod(np.asarray(m, dtype=np.int64), OUT_RATE)
+    return np.exp(-2j * np.pi * (np.mod(f[:, None] * mm[None, :], OUT_RATE).astype(np.float64) / OUT_RATE))
+
+
+def quantise(y: np.ndarray, gain: float = 100.0) -> Tuple[np.ndarray, int]:
+    """complex [..] -> (int8 [..][2] I/Q, clipped components): q = clamp(rint(128 gain y), -128, 127)."""
+    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * gain)
+    r = np.rint(v)
+    clipped = int(np.count_nonzero((r < -128) | (r > 127)))
+    return np.clip(r, -128, 127).astype(np.int8), clipped
+
+
+class Channeliser:
+    """The contract, push by push: keeps the last L-1 input samples and the output index m like the device does."""
+
+    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0):
+        if rate_hz % OUT_RATE:
+            raise ValueError("rate must be a multiple of 12000 Hz")
+        self.D = rate_hz // OUT_RATE
+        self.rate = int(rate_hz)
+        self.offsets = np.asarray(offsets_hz, dtype=np.int64)
+        self.taps = default_taps(self.D, K) if taps is None else np.asarray(taps, dtype=np.float64)
+        self.L = len(self.taps)
+        self.gain = gain
+        self.G = tap_matrix(rate_hz, self.offsets, self.taps)
+        self.reset()
+
+    def reset(self):
+        self.hist = np.zeros(self.L - 1, dtype=np.complex128)
+        self.m = 0
+
+    def filter(self, x: np.ndarray) -> np.ndarray:
+        """complex y [channel][M] of the next len(x)/D output samples (history and m advance)."""
+        x = np.asarray(x, dtype=np.complex128)
+        D, L = self.D, self.L
+        if len(x) % D:
+            raise ValueError("a push carries a whole number of output samples")
+        M = len(x) // D
+        xp = np.concatenate([self.hist, x])
+        y = np.empty((len(self.offsets), M), dtype=np.complex128)
+        k = np.arange(L)
+        GT = self.G.T
+        for m0 in range(0, M, 256):
+            ms = np.arange(m0, min(M, m0 + 256))
+            X = xp[ms[:, None] * D - k[None, :] + (L - 1)]   # Hankel rows x[mD - k]
+            y[:, m0:m0 + len(ms)] = (X @ GT).T
+        y *= output_rotation(self.offsets, self.m + np.arange(M))
+        self.hist = xp[len(xp) - (L - 1):].copy() if L > 1 else self.hist
+        self.m += M
+        return y
+
+    def push(self, x: np.ndarray, first: bool = False) -> Tuple[np.ndarray, int]:
+        """(int8 [channel][M][2], clipped components) of one push; first=True restarts the stream."""
+        if first:
+            self.reset()
+        return quantise(self.filter(x), self.gain)
+
+
+def naive_channel(x: np.ndarray, rate_hz: int, offset_hz: int, taps: np.ndarray) -> np.ndarray:
+    """Mix by e^{-j2pi f_c n/Fs}, filter with h, keep every D-th sample: y[m] = (h * (x e^{-j2pi f_c n/Fs}))[mD]."""
+    D = rate_hz // OUT_RATE
+    n = np.arange(len(x), dtype=np.int64)
+    mixed = x * np.exp(-2j * np.pi * np.mod(offset_hz * n, rate_hz).astype(np.float64) / rate_hz)
+    return np.convolve(mixed, taps)[:len(x)][::D]
+
+
+# ---- scene synthesis ----
+
+def _upsample(bb: np.ndarray, D: int) -> np.ndarray:
+    """Band-limited interpolation by D (spectrum zero-padded): a 12 kHz baseband at D*12000 Hz with no images."""
+    n = len(bb)
+    S = np.fft.fft(bb)
+    P = np.zeros(n * D, dtype=np.complex128)
+    h = n // 2
+    P[:h] = S[:h]
+    P[-(n - h):] = S[h:]
+    return np.fft.ifft(P) * D
+
+
+def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Ping]], noise_sigma: float, rng: np.random.Generator,
+                   fmt: str = "cu8") -> np.ndarray:
+    """Raw interleaved components of a wideband scene n_out output samples long (n_out * D wideband samples).
+
+    pings: (channel offset f_c in Hz, synth.Ping) pairs; the Ping's start is in 12 kHz samples and its freq_hz is the frequency
+    inside the channel, so the carrier lands at f_c + freq_hz.  noise_sigma: per rail, in full-scale units (1 = the format's full
+    scale).  SNR in 2500 Hz as in synth.synth_iq: 10log10(A^2 / (2 sigma^2 2500 / Fs))."""
+    D = rate_hz // OUT_RATE
+    N = n_out * D
+    x = rng.normal(0.0, noise_sigma, N) + 1j * rng.normal(0.0, noise_sigma, N) if noise_sigma > 0 else np.zeros(N, dtype=np.complex128)
+    ref = noise_sigma if noise_sigma > 0 else 1.0
+    for f_c, p in pings:
+        bb = synth._ping_baseband(p)
+        amp = np.sqrt(2.0 * ref ** 2 * (2500.0 / rate_hz) * 10.0 ** (p.snr_db / 10.0))
+        up = _upsample(bb, D)
+        n0 = p.start * D
+        n1 = min(N, n0 + len(up))
+        if n1 <= n0:
+            continue
+        n = np.arange(n0, n1)
+        carrier = np.exp(1j * (2 * np.pi * (f_c + p.freq_hz) * n / rate_hz + p.phase))
+        x[n0:n1] += amp * up[:n1 - n0] * carrier
+    return write_samples(x, fmt)
+
+
+def push_sizes(n_pushes: int, D: int):
+    """Raw component counts of a first push followed by n_pushes-1 later ones."""
+    return [2 * FIRST_OUT * D] + [2 * HOP_OUT * D] * (n_pushes - 1)

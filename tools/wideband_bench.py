@@ -1,0 +1,107 @@
+"""Wideband channeliser cost per push (msk144_push_wideband), measured with the library's HIP-event stage times.
+
+For every (channels, D) the handle is pushed `--pushes` later pushes of random cu8 samples.  In wideband mode the front-end stage
+time covers the channeliser and the IQ front end; the same handle is then fed the same number of plain msk144_push_hops calls,
+whose front-end time is the IQ front end alone, and the difference is the channeliser.  FLOP count: channels x 2592 x K*D x 8.
+One JSON line per configuration on stdout.
+
+Then one msk144hipdecoder run over a pre-written 1.92 Msps cu8 file (1024 channels, D = 160, the program's default decode
+configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592 samples at 12 kHz).
+
+    python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--pushes 20] [--program-hops 40]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from msk144cudecoder_amd import hipdecoder  # noqa: E402
+
+FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
+
+
+def measure(C: int, D: int, pushes: int, K: int = 16) -> dict:
+    rng = np.random.default_rng(C + D)
+    rate = D * 12000
+    lim = rate // 2 - 6000
+    offsets = np.linspace(-lim, lim, C).astype(np.int32)
+    with hipdecoder.HipDecoder(center=0.0, width=0.0, step=1.0, depth=1, read_mode=2, channels=C) as d:
+        d.set_wideband(rate, offsets, "cu8", taps_per_phase=K)
+        for s in range(2):
+            d.wideband_slot(s)[:] = rng.integers(120, 136, size=d.wideband_slot(s).size, dtype=np.uint8)
+        d.push_wideband(0, first=True)
+        d.synchronize()
+        d.set_profiling(True)
+        d.stage_times(reset=True)
+        for i in range(pushes):
+            d.push_wideband(i % 2, first=False)
+        wide = d.stage_times(reset=True)
+        for s in range(2):
+            hops, _, streams, is_first = d.hop_slot(s)
+            hops[:] = rng.integers(-8, 8, size=hops.shape, dtype=np.int8)
+            streams[:] = np.arange(C)
+            is_first[:] = 0
+        for i in range(pushes):
+            d.push_hops(i % 2, C)
+        plain = d.stage_times(reset=True)
+    ms = wide["frontend"][0] - plain["frontend"][0]
+    flop = C * 2592 * K * D * 8
+    return dict(channels=C, D=D, K=K, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
+                channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
+                tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
+                fraction_of_fp32_peak=round(flop / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 3) if ms > 0 else None,
+                target_ms=2.0 if (C, D) == (1024, 160) else None)
+
+
+def program_run(hops: int, C: int = 1024, D: int = 160) -> dict:
+    """Wall time of one msk144hipdecoder run over a file of 1 first + (hops - 1) later pushes of cu8 noise."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "msk144cudecoder_amd", "msk144hipdecoder")
+    rate = D * 12000
+    lim = rate // 2 - 6000
+    offsets = np.linspace(-lim, lim, C).astype(np.int64)
+    rng = np.random.default_rng(5)
+    n = 2 * (5184 + (hops - 1) * 2592) * D
+    with tempfile.NamedTemporaryFile(suffix=".cu8") as f:
+        f.write(np.clip(np.rint(127.5 + 6.0 * rng.standard_normal(n)), 0, 255).astype(np.uint8).tobytes())
+        f.flush()
+        args = [exe, f"--wideband-rate={rate}", "--wideband-format=cu8", "--channel-offsets=" + ",".join(str(int(v)) for v in offsets), "--wideband-gain=20"]
+        with open(f.name, "rb") as src:
+            t0 = time.perf_counter()
+            p = subprocess.run(args, stdin=src, capture_output=True, timeout=600)
+            wall = time.perf_counter() - t0
+    if p.returncode != 0:
+        raise RuntimeError(p.stderr.decode()[-2000:])
+    err = p.stderr.decode()
+    m = re.search(r"msk144hipdecoder: (\d+) batches", err)
+    batches = int(m.group(1)) if m else None
+    return dict(program="msk144hipdecoder", channels=C, D=D, hops=batches, wall_s=round(wall, 3), hops_per_s=round(batches / wall, 2) if batches else None,
+                realtime_hops_per_s=4.63, note="wall time of the whole process, handle creation and file reading included")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--channels", default="256,1024,4096")
+    ap.add_argument("--decimations", default="80,160,200")
+    ap.add_argument("--pushes", type=int, default=20)
+    ap.add_argument("--program-hops", type=int, default=40, help="0: skip the program run")
+    a = ap.parse_args()
+    for C in [int(v) for v in a.channels.split(",")]:
+        for D in [int(v) for v in a.decimations.split(",")]:
+            print(json.dumps(measure(C, D, a.pushes)), flush=True)
+    if a.program_hops:
+        print(json.dumps(program_run(a.program_hops)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
