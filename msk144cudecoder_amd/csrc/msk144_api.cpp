@@ -22,6 +22,20 @@ using namespace msk144;
 static_assert(sizeof(msk144_candidate) == kReferenceResultItemBytes, "msk144_candidate must mirror the reference ResultItem");
 static_assert(sizeof(msk144_result) == 52, "msk144_result layout");
 
+// Device and pinned host buffers that are freed together (dev_alloc, host_alloc register them)
+struct Buffers
+{
+    std::vector<void*> device, pinned;
+
+    void release()
+    {
+        for(void* p : device) (void)hipFree(p);
+        for(void* p : pinned) (void)hipHostFree(p);
+        device.clear();
+        pinned.clear();
+    }
+};
+
 struct msk144_handle
 {
     msk144_params params{};
@@ -31,13 +45,13 @@ struct msk144_handle
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
 
-    // device allocations
+    // every buffer of the handle except those of its wideband configuration
+    Buffers mem;
     float* d_freq = nullptr;
     float2* d_cb42 = nullptr;
-    void* d_input = nullptr;  // staging for host-submitted windows
+    uint8_t* d_input = nullptr;  // staging for host-submitted windows
     float2* d_twiddle = nullptr;
     float* d_fft_mask = nullptr;
-    std::vector<void*> allocs;
 
     int llr_block = 1;  // channels per softbits->index->LDPC block
     bool retained = true;  // every LLR row of a decode stays readable (one block covers all channels and msk144_set_llr_retention was not switched off)
@@ -66,7 +80,7 @@ struct msk144_handle
     // st.results of the plain calls; slot 1 has its own, so the list of one slot survives the decode of the other.
     struct Slot
     {
-        void* in = nullptr;                 // pinned windows, input_bytes()
+        uint8_t* in = nullptr;              // pinned windows, input_bytes()
         msk144_result* d_records = nullptr; // device record list this slot's decode writes
         msk144_result* out = nullptr;       // pinned records, max_results
         int32_t* out_count = nullptr;       // pinned
@@ -75,8 +89,8 @@ struct msk144_handle
         hipEvent_t done = nullptr;
         bool pending = false;
         // hop-ring inputs (msk144_hop_slot), pinned, allocated on first use
-        void* hops = nullptr;          // [channels][half window]
-        void* first_halves = nullptr;  // [channels][half window]
+        uint8_t* hops = nullptr;          // [channels][half window]
+        uint8_t* first_halves = nullptr;  // [channels][half window]
         int32_t* streams = nullptr;    // [channels]
         uint8_t* is_first = nullptr;   // [channels]
     };
@@ -86,9 +100,9 @@ struct msk144_handle
     std::atomic<int32_t> last_total{0};      // record count of the last fetched hop: sizes the next asynchronous copy
     hipStream_t copy_stream = nullptr;       // remainder copies of msk144_fetch_wait (may run on a second thread)
     // device side of the hop ring: every stream's current window, and the staging of one batch of hops
-    void* d_ring = nullptr;
-    void* d_hops = nullptr;
-    void* d_first = nullptr;
+    uint8_t* d_ring = nullptr;
+    uint8_t* d_hops = nullptr;
+    uint8_t* d_first = nullptr;
     int32_t* d_streams = nullptr;
     uint8_t* d_isfirst = nullptr;
     bool ring_ready = false;
@@ -96,9 +110,10 @@ struct msk144_handle
     hipStream_t probe_stream = nullptr;
     uint64_t* d_probe = nullptr;
 
-    // wideband channeliser (msk144_set_wideband); buffers are (re)allocated by msk144_set_wideband and freed here, not in allocs
+    // wideband channeliser (msk144_set_wideband); its buffers have their own owner, as a new configuration replaces them
     struct Wideband
     {
+        Buffers mem;
         bool configured = false;
         bool started = false;     // a first push has been made since the configuration
         bool last_first = false;  // the last push was a first push (5184 samples per channel)
@@ -106,8 +121,8 @@ struct msk144_handle
         float gain = 0.0f;
         long long m_next = 0;     // output sample index of the next push
         size_t slot_bytes = 0;    // pinned bytes per slot: 5184*D samples
-        void* pinned[MSK144_SLOTS] = {};
-        void* d_raw = nullptr;    // L-1 history samples + the samples of one push, raw format
+        uint8_t* pinned[MSK144_SLOTS] = {};
+        uint8_t* d_raw = nullptr; // L-1 history samples + the samples of one push, raw format
         float2* d_G = nullptr;    // [ceil(channels/32)][D][K][32]
         int32_t* d_fmod = nullptr;
         float2* d_rot = nullptr;  // [12000]
@@ -140,21 +155,34 @@ int fail(msk144_handle* h, int code, const std::string& msg)
         if(e_ != hipSuccess) return fail(h, MSK144_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while(0)
 
+// count elements of device (hipMalloc) or pinned host (hipHostMalloc) memory, registered with the owner that frees them
 template<typename T>
-int dev_alloc(msk144_handle* h, T** p, size_t count)
+int alloc(msk144_handle* h, Buffers& owner, bool pinned, T** p, size_t count)
 {
     void* q = nullptr;
     const size_t bytes = count * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
+    hipError_t e = pinned ? hipHostMalloc(&q, bytes ? bytes : 1, hipHostMallocDefault) : hipMalloc(&q, bytes ? bytes : 1);
     if(e != hipSuccess)
     {
         char buf[160];
-        snprintf(buf, sizeof(buf), "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+        snprintf(buf, sizeof(buf), "%s(%zu bytes): %s", pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
         return fail(h, MSK144_ENOMEM, buf);
     }
-    h->allocs.push_back(q);
+    (pinned ? owner.pinned : owner.device).push_back(q);
     *p = static_cast<T*>(q);
     return MSK144_OK;
+}
+
+template<typename T>
+int dev_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
+{
+    return alloc(h, owner, false, p, count);
+}
+
+template<typename T>
+int host_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
+{
+    return alloc(h, owner, true, p, count);
 }
 
 size_t window_bytes(const msk144_handle* h)
@@ -176,6 +204,12 @@ DeviceStore active_store(const msk144_handle* h)
     return st;
 }
 
+// the device record list of the current slot, which the last decode wrote; st.results for slot 0 and before any slot exists
+msk144_result* current_records(const msk144_handle* h)
+{
+    return h->slots_ready ? h->slots[h->cur_slot].d_records : static_cast<msk144_result*>(h->st.results);
+}
+
 hipEvent_t ev_take(msk144_handle* h)
 {
     if(!h->ev_free.empty())
@@ -189,7 +223,7 @@ hipEvent_t ev_take(msk144_handle* h)
     return e;
 }
 
-void ev_begin(msk144_handle* h, int)
+void ev_begin(msk144_handle* h)
 {
     if(!h->profiling) return;
     h->ev_open = ev_take(h);
@@ -232,18 +266,6 @@ void harvest_times(msk144_handle* h)
     h->spans_pending.clear();
 }
 
-int host_alloc(msk144_handle* h, void** p, size_t bytes)
-{
-    hipError_t e = hipHostMalloc(p, bytes ? bytes : 1, hipHostMallocDefault);
-    if(e != hipSuccess)
-    {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "hipHostMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
-        return fail(h, MSK144_ENOMEM, buf);
-    }
-    return MSK144_OK;
-}
-
 int ensure_slots(msk144_handle* h)
 {
     if(h->slots_ready) return MSK144_OK;
@@ -253,15 +275,14 @@ int ensure_slots(msk144_handle* h)
     {
         msk144_handle::Slot& sl = h->slots[s];
         int rc = MSK144_OK;
-        if(!sl.in) rc = host_alloc(h, &sl.in, input_bytes(h));
-        if(rc == MSK144_OK && !sl.out) rc = host_alloc(h, reinterpret_cast<void**>(&sl.out), sizeof(msk144_result) * static_cast<size_t>(h->st.max_results));
-        if(rc == MSK144_OK && !sl.out_count) rc = host_alloc(h, reinterpret_cast<void**>(&sl.out_count), sizeof(int32_t));
-        if(rc == MSK144_OK && !sl.out_seg) rc = host_alloc(h, reinterpret_cast<void**>(&sl.out_seg), sizeof(float) * 8 * h->st.channels);
-        if(rc != MSK144_OK) return rc;
+        if(!sl.in && (rc = host_alloc(h, h->mem, &sl.in, input_bytes(h))) != MSK144_OK) return rc;
+        if(!sl.out && (rc = host_alloc(h, h->mem, &sl.out, h->st.max_results)) != MSK144_OK) return rc;
+        if(!sl.out_count && (rc = host_alloc(h, h->mem, &sl.out_count, 1)) != MSK144_OK) return rc;
+        if(!sl.out_seg && (rc = host_alloc(h, h->mem, &sl.out_seg, 8 * static_cast<size_t>(h->st.channels))) != MSK144_OK) return rc;
         if(!sl.d_records)
         {
             if(s == 0) sl.d_records = static_cast<msk144_result*>(h->st.results);
-            else if((rc = dev_alloc(h, &sl.d_records, h->st.max_results)) != MSK144_OK) return rc;
+            else if((rc = dev_alloc(h, h->mem, &sl.d_records, h->st.max_results)) != MSK144_OK) return rc;
         }
         // blocking-sync event: the waiting thread sleeps instead of spinning on a core the ingest thread needs
         if(!sl.done) HIP_TRY(h, hipEventCreateWithFlags(&sl.done, hipEventBlockingSync | hipEventDisableTiming));
@@ -275,24 +296,21 @@ int ensure_ring(msk144_handle* h)
     if(h->ring_ready) return MSK144_OK;
     int rc = ensure_slots(h);
     if(rc != MSK144_OK) return rc;
+    // only what is still missing, so that a retry after a failed allocation allocates nothing twice
     const size_t nch = static_cast<size_t>(h->st.channels);
     const size_t half = window_bytes(h) / 2;
-    uint8_t *ring = nullptr, *hops = nullptr, *first = nullptr;
-    if((rc = dev_alloc(h, &ring, nch * window_bytes(h))) != MSK144_OK) return rc;
-    if((rc = dev_alloc(h, &hops, nch * half)) != MSK144_OK) return rc;
-    if((rc = dev_alloc(h, &first, nch * half)) != MSK144_OK) return rc;
-    if((rc = dev_alloc(h, &h->d_streams, nch)) != MSK144_OK) return rc;
-    if((rc = dev_alloc(h, &h->d_isfirst, nch)) != MSK144_OK) return rc;
-    h->d_ring = ring;
-    h->d_hops = hops;
-    h->d_first = first;
+    if(!h->d_ring && (rc = dev_alloc(h, h->mem, &h->d_ring, nch * window_bytes(h))) != MSK144_OK) return rc;
+    if(!h->d_hops && (rc = dev_alloc(h, h->mem, &h->d_hops, nch * half)) != MSK144_OK) return rc;
+    if(!h->d_first && (rc = dev_alloc(h, h->mem, &h->d_first, nch * half)) != MSK144_OK) return rc;
+    if(!h->d_streams && (rc = dev_alloc(h, h->mem, &h->d_streams, nch)) != MSK144_OK) return rc;
+    if(!h->d_isfirst && (rc = dev_alloc(h, h->mem, &h->d_isfirst, nch)) != MSK144_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_ring, 0, nch * window_bytes(h), h->stream));
     for(auto& sl : h->slots)
     {
-        if((rc = host_alloc(h, &sl.hops, nch * half)) != MSK144_OK) return rc;
-        if((rc = host_alloc(h, &sl.first_halves, nch * half)) != MSK144_OK) return rc;
-        if((rc = host_alloc(h, reinterpret_cast<void**>(&sl.streams), nch * sizeof(int32_t))) != MSK144_OK) return rc;
-        if((rc = host_alloc(h, reinterpret_cast<void**>(&sl.is_first), nch)) != MSK144_OK) return rc;
+        if(!sl.hops && (rc = host_alloc(h, h->mem, &sl.hops, nch * half)) != MSK144_OK) return rc;
+        if(!sl.first_halves && (rc = host_alloc(h, h->mem, &sl.first_halves, nch * half)) != MSK144_OK) return rc;
+        if(!sl.streams && (rc = host_alloc(h, h->mem, &sl.streams, nch)) != MSK144_OK) return rc;
+        if(!sl.is_first && (rc = host_alloc(h, h->mem, &sl.is_first, nch)) != MSK144_OK) return rc;
         std::memset(sl.is_first, 0, nch);
     }
     h->ring_ready = true;
@@ -301,7 +319,7 @@ int ensure_ring(msk144_handle* h)
 
 int copy_windows_in(msk144_handle* h, const void* host_windows)
 {
-    ev_begin(h, MSK144_T_H2D);
+    ev_begin(h);
     hipError_t e = hipMemcpyAsync(h->d_input, host_windows, window_bytes(h) * h->active, hipMemcpyHostToDevice, h->stream);
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("hipMemcpyAsync(windows): ") + hipGetErrorString(e));
@@ -324,7 +342,7 @@ void harvest_finished(msk144_handle* h)
 
 int run_frontend(msk144_handle* h, const void* d_in)
 {
-    ev_begin(h, MSK144_T_FRONTEND);
+    ev_begin(h);
     const DeviceStore st = active_store(h);
     if(h->params.read_mode == 2) launch_frontend_iq(st, static_cast<const int8_t*>(d_in), h->stream);
     else launch_frontend_audio(st, static_cast<const int16_t*>(d_in), h->params.analytic_method, h->d_twiddle, h->d_fft_mask, h->stream);
@@ -333,6 +351,42 @@ int run_frontend(msk144_handle* h, const void* d_in)
     h->have_window = true;
     h->decoded = false;
     return MSK144_OK;
+}
+
+// back to no wideband configuration: its buffers freed, every field reset
+void wb_release(msk144_handle* h)
+{
+    h->wb.mem.release();
+    h->wb = {};
+}
+
+// the slot argument of an entry that begins a hop: in range, and not still waiting for msk144_fetch_wait
+int check_hop_slot(msk144_handle* h, int32_t slot)
+{
+    if(!h || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
+    if(h->slots[slot].pending) return fail(h, MSK144_ESTATE, "slot submitted again before its results were fetched (msk144_fetch_wait)");
+    return MSK144_OK;
+}
+
+// every entry that begins a hop: a new call (one stage-time sample), the slot whose record list the decode writes, its channels
+int begin_hop(msk144_handle* h, int32_t slot, int32_t n)
+{
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    h->call_id++;
+    h->cur_slot = slot;
+    h->active = n;
+    return MSK144_OK;
+}
+
+// msk144_submit_{audio,iq}[_device]: every channel, into slot 0's record list; windows in host memory are staged in d_input first
+int submit_windows(msk144_handle* h, const void* windows, int read_mode, bool host)
+{
+    if(!h || !windows) return fail(h, MSK144_EINVAL, "null argument");
+    if(h->params.read_mode != read_mode)
+        return fail(h, MSK144_ESTATE, read_mode == 1 ? "handle was created for IQ input (read_mode 2)" : "handle was created for audio input (read_mode 1)");
+    int rc = begin_hop(h, 0, h->st.channels);
+    if(rc == MSK144_OK && host) rc = copy_windows_in(h, windows);
+    return rc == MSK144_OK ? run_frontend(h, host ? h->d_input : windows) : rc;
 }
 
 }  // namespace
@@ -395,6 +449,7 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
     h->params.llr_block_channels = h->llr_block;
     for(int s = 0; s < MSK144_T_COUNT; s++) h->last_call[s] = -1;
 
+    // every failure below has set h->error through fail(h, ...)
     auto bail = [&](int code) {
         g_create_error = h->error;
         msk144_destroy(h);
@@ -402,21 +457,9 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
     };
 
     int ndev = 0;
-    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    {
-        h->error = "no HIP device available (libmsk144hip has no CPU fallback)";
-        return bail(MSK144_EHIP);
-    }
-    if(params->device < 0 || params->device >= ndev)
-    {
-        h->error = "device ordinal out of range";
-        return bail(MSK144_EINVAL);
-    }
-    if(hipSetDevice(params->device) != hipSuccess)
-    {
-        h->error = "hipSetDevice failed";
-        return bail(MSK144_EHIP);
-    }
+    if(hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return bail(fail(h, MSK144_EHIP, "no HIP device available (libmsk144hip has no CPU fallback)"));
+    if(params->device < 0 || params->device >= ndev) return bail(fail(h, MSK144_EINVAL, "device ordinal out of range"));
+    if(hipSetDevice(params->device) != hipSuccess) return bail(fail(h, MSK144_EHIP, "hipSetDevice failed"));
 
     h->freq_host = frequency_grid(params->center_hz, params->width_hz, params->step_hz);
     const int F = static_cast<int>(h->freq_host.size());
@@ -441,54 +484,40 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
 
     sync_template(h->tpl.re, h->tpl.im, h->tpl.pp);
     // the kernels skip the multiplications by pp[0] and pp[6] (softbits.hip, scan.hip): exact only for these values
-    if(h->tpl.pp[0] != 0.0f || h->tpl.pp[kPulseSamples / 2] != 1.0f)
-    {
-        h->error = "half-sine pulse table: pp[0] != 0 or pp[6] != 1";
-        return bail(MSK144_EINVAL);
-    }
-
-    if(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
-    {
-        h->error = "hipStreamCreate failed";
-        return bail(MSK144_EHIP);
-    }
+    if(h->tpl.pp[0] != 0.0f || h->tpl.pp[kPulseSamples / 2] != 1.0f) return bail(fail(h, MSK144_EINVAL, "half-sine pulse table: pp[0] != 0 or pp[6] != 1"));
+    if(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(h, MSK144_EHIP, "hipStreamCreate failed"));
     h->stream = h->own_stream;
 
     const size_t ck = static_cast<size_t>(total);
-    int rc = MSK144_OK;
-    auto A = [&](int r) { if(rc == MSK144_OK) rc = r; };
-    A(dev_alloc(h, &h->d_freq, F));
-    A(dev_alloc(h, &h->d_cb42, kSyncTaps));
-    A(dev_alloc(h, &st.analytic, static_cast<size_t>(st.channels) * kWindowSamples));
-    A(dev_alloc(h, &st.seg_power, static_cast<size_t>(st.channels) * 8));
-    A(dev_alloc(h, &st.pos, ck));
-    A(dev_alloc(h, &st.xb, ck));
-    A(dev_alloc(h, &st.nbadsync, ck));
-    A(dev_alloc(h, &st.llr, static_cast<size_t>(h->llr_block) * st.K * kCodeBits));
-    A(dev_alloc(h, &st.idx, ck));
-    A(dev_alloc(h, &st.n_idx, st.channels));
-    A(dev_alloc(h, &st.dec_flag, ck));
-    A(dev_alloc(h, &st.dec_iter, ck));
-    A(dev_alloc(h, &st.dec_nhard, ck));
-    A(dev_alloc(h, &st.dec_msg, ck * 3));
-    A(dev_alloc(h, &st.dec_count, st.channels));
-    A(dev_alloc(h, &st.copy_count, st.channels));
-    A(dev_alloc(h, &st.result_count, 1));
-    {
-        msk144_result* r = nullptr;
-        A(dev_alloc(h, &r, st.max_results));
-        st.results = r;
-    }
-    {
-        uint8_t* in = nullptr;
-        A(dev_alloc(h, &in, input_bytes(h)));
-        h->d_input = in;
-    }
-    if(rc != MSK144_OK) return bail(rc);
+    const size_t nch = static_cast<size_t>(st.channels);
+    Buffers& m = h->mem;
+    msk144_result* results = nullptr;
+    // a failed dev_alloc has set the message; its code is MSK144_ENOMEM
+    bool ok = dev_alloc(h, m, &h->d_freq, F) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &h->d_cb42, kSyncTaps) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.analytic, nch * kWindowSamples) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.seg_power, nch * 8) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.pos, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.xb, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.nbadsync, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.llr, static_cast<size_t>(h->llr_block) * st.K * kCodeBits) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.idx, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.n_idx, nch) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.dec_flag, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.dec_iter, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.dec_nhard, ck) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.dec_msg, ck * 3) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.dec_count, nch) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.copy_count, nch) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.result_count, 1) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &results, st.max_results) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &h->d_input, input_bytes(h)) == MSK144_OK;
+    if(!ok) return bail(MSK144_ENOMEM);
+    st.results = results;
     st.freq = h->d_freq;
     st.cb42 = h->d_cb42;
 
-    bool ok = hipMemcpy(h->d_freq, h->freq_host.data(), sizeof(float) * F, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(h->d_freq, h->freq_host.data(), sizeof(float) * F, hipMemcpyHostToDevice) == hipSuccess;
     {
         float2 cb[kSyncTaps];
         for(int k = 0; k < kSyncTaps; k++) cb[k] = make_float2(h->tpl.re[k], h->tpl.im[k]);
@@ -515,15 +544,11 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
             const double ang = -2.0 * M_PI * j / kFftSize;
             tw[j] = make_float2(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
         }
-        if(dev_alloc(h, &h->d_twiddle, tw.size()) != MSK144_OK || dev_alloc(h, &h->d_fft_mask, mask.size()) != MSK144_OK) return bail(MSK144_ENOMEM);
+        if(dev_alloc(h, m, &h->d_twiddle, tw.size()) != MSK144_OK || dev_alloc(h, m, &h->d_fft_mask, mask.size()) != MSK144_OK) return bail(MSK144_ENOMEM);
         ok = ok && hipMemcpy(h->d_twiddle, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && hipMemcpy(h->d_fft_mask, mask.data(), mask.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if(!ok)
-    {
-        h->error = std::string("device initialisation failed: ") + hipGetErrorString(hipGetLastError());
-        return bail(MSK144_EHIP);
-    }
+    if(!ok) return bail(fail(h, MSK144_EHIP, std::string("device initialisation failed: ") + hipGetErrorString(hipGetLastError())));
     *out = h;
     return MSK144_OK;
 }
@@ -534,23 +559,10 @@ void msk144_destroy(msk144_handle* h)
     (void)hipSetDevice(h->params.device);
     if(h->probe_stream) (void)hipStreamSynchronize(h->probe_stream);
     if(h->stream) (void)hipStreamSynchronize(h->stream);
-    for(void* p : h->allocs) (void)hipFree(p);
+    h->wb.mem.release();
+    h->mem.release();
     for(auto& sl : h->slots)
-    {
-        if(sl.in) (void)hipHostFree(sl.in);
-        if(sl.out) (void)hipHostFree(sl.out);
-        if(sl.out_count) (void)hipHostFree(sl.out_count);
-        if(sl.out_seg) (void)hipHostFree(sl.out_seg);
-        if(sl.hops) (void)hipHostFree(sl.hops);
-        if(sl.first_halves) (void)hipHostFree(sl.first_halves);
-        if(sl.streams) (void)hipHostFree(sl.streams);
-        if(sl.is_first) (void)hipHostFree(sl.is_first);
         if(sl.done) (void)hipEventDestroy(sl.done);
-    }
-    for(void* p : h->wb.pinned)
-        if(p) (void)hipHostFree(p);
-    for(void* p : {h->wb.d_raw, static_cast<void*>(h->wb.d_G), static_cast<void*>(h->wb.d_fmod), static_cast<void*>(h->wb.d_rot), static_cast<void*>(h->wb.d_clip)})
-        if(p) (void)hipFree(p);
     if(h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if(h->probe_stream) (void)hipStreamDestroy(h->probe_stream);
     for(const auto& sp : h->spans_pending)
@@ -592,48 +604,22 @@ int msk144_set_stream(msk144_handle* h, void* hip_stream)
 
 int msk144_submit_audio(msk144_handle* h, const int16_t* windows)
 {
-    if(!h || !windows) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 1) return fail(h, MSK144_ESTATE, "handle was created for IQ input (read_mode 2)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = 0;
-    h->active = h->st.channels;
-    int rc = copy_windows_in(h, windows);
-    return rc == MSK144_OK ? run_frontend(h, h->d_input) : rc;
+    return submit_windows(h, windows, 1, true);
 }
 
 int msk144_submit_iq(msk144_handle* h, const int8_t* windows)
 {
-    if(!h || !windows) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 2) return fail(h, MSK144_ESTATE, "handle was created for audio input (read_mode 1)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = 0;
-    h->active = h->st.channels;
-    int rc = copy_windows_in(h, windows);
-    return rc == MSK144_OK ? run_frontend(h, h->d_input) : rc;
+    return submit_windows(h, windows, 2, true);
 }
 
 int msk144_submit_audio_device(msk144_handle* h, const int16_t* d_windows)
 {
-    if(!h || !d_windows) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 1) return fail(h, MSK144_ESTATE, "handle was created for IQ input (read_mode 2)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = 0;
-    h->active = h->st.channels;
-    return run_frontend(h, d_windows);
+    return submit_windows(h, d_windows, 1, false);
 }
 
 int msk144_submit_iq_device(msk144_handle* h, const int8_t* d_windows)
 {
-    if(!h || !d_windows) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 2) return fail(h, MSK144_ESTATE, "handle was created for audio input (read_mode 1)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = 0;
-    h->active = h->st.channels;
-    return run_frontend(h, d_windows);
+    return submit_windows(h, d_windows, 2, false);
 }
 
 int msk144_submit_analytic(msk144_handle* h, const float* windows)
@@ -663,7 +649,7 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
     const DeviceStore cur = active_store(h);
     if(stages & MSK144_STAGE_SCAN)
     {
-        ev_begin(h, MSK144_T_SCAN);
+        ev_begin(h);
         launch_scan(cur, h->tpl, h->stream);
         ev_end(h, MSK144_T_SCAN);
     }
@@ -678,19 +664,19 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
             blk.nch = cur.channels - ch0 < h->llr_block ? cur.channels - ch0 : h->llr_block;
             if(stages & MSK144_STAGE_SOFTBITS)
             {
-                ev_begin(h, MSK144_T_SOFTBITS);
+                ev_begin(h);
                 launch_softbits(blk, h->tpl, h->stream);
                 ev_end(h, MSK144_T_SOFTBITS);
             }
             if(stages & MSK144_STAGE_INDEX)
             {
-                ev_begin(h, MSK144_T_INDEX);
+                ev_begin(h);
                 launch_index(blk, h->stream);
                 ev_end(h, MSK144_T_INDEX);
             }
             if(stages & MSK144_STAGE_LDPC)
             {
-                ev_begin(h, MSK144_T_LDPC);
+                ev_begin(h);
                 launch_ldpc(blk, h->stream);
                 ev_end(h, MSK144_T_LDPC);
             }
@@ -699,8 +685,8 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
     if(stages & MSK144_STAGE_COLLECT)
     {
         DeviceStore out = cur;
-        if(h->slots_ready) out.results = h->slots[h->cur_slot].d_records;  // the record list of the slot being decoded
-        ev_begin(h, MSK144_T_COLLECT);
+        out.results = current_records(h);
+        ev_begin(h);
         launch_collect(out, h->stream);
         ev_end(h, MSK144_T_COLLECT);
     }
@@ -742,8 +728,7 @@ int msk144_results(msk144_handle* h, msk144_result* out, int32_t cap, int32_t* n
     *n = total;
     int32_t avail = total < h->st.max_results ? total : h->st.max_results;
     int32_t ncopy = avail < cap ? avail : cap;
-    const void* list = h->slots_ready ? h->slots[h->cur_slot].d_records : h->st.results;  // the list the last decode wrote
-    if(ncopy > 0) HIP_TRY(h, hipMemcpy(out, list, sizeof(msk144_result) * ncopy, hipMemcpyDeviceToHost));
+    if(ncopy > 0) HIP_TRY(h, hipMemcpy(out, current_records(h), sizeof(msk144_result) * ncopy, hipMemcpyDeviceToHost));
     if(total > h->st.max_results) return fail(h, MSK144_EOVERFLOW, "more decodes than max_results; list truncated");
     return MSK144_OK;
 }
@@ -751,7 +736,7 @@ int msk144_results(msk144_handle* h, msk144_result* out, int32_t cap, int32_t* n
 int msk144_results_device(msk144_handle* h, const msk144_result** d_records, const int32_t** d_count)
 {
     if(!h || !d_records || !d_count) return fail(h, MSK144_EINVAL, "null argument");
-    *d_records = h->slots_ready ? h->slots[h->cur_slot].d_records : static_cast<const msk144_result*>(h->st.results);
+    *d_records = current_records(h);
     *d_count = h->st.result_count;
     return MSK144_OK;
 }
@@ -839,15 +824,10 @@ int msk144_submit_slot(msk144_handle* h, int32_t slot)
 
 int msk144_submit_slot_n(msk144_handle* h, int32_t slot, int32_t n_channels)
 {
-    if(!h || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
-    if(n_channels < 1 || n_channels > h->st.channels) return fail(h, MSK144_EINVAL, "n_channels must be 1..channels");
-    int rc = ensure_slots(h);
+    int rc = check_hop_slot(h, slot);
     if(rc != MSK144_OK) return rc;
-    if(h->slots[slot].pending) return fail(h, MSK144_ESTATE, "slot submitted again before its results were fetched (msk144_fetch_wait)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = slot;
-    h->active = n_channels;
+    if(n_channels < 1 || n_channels > h->st.channels) return fail(h, MSK144_EINVAL, "n_channels must be 1..channels");
+    if((rc = ensure_slots(h)) != MSK144_OK || (rc = begin_hop(h, slot, n_channels)) != MSK144_OK) return rc;
     rc = copy_windows_in(h, h->slots[slot].in);
     return rc == MSK144_OK ? run_frontend(h, h->d_input) : rc;
 }
@@ -868,11 +848,11 @@ int msk144_hop_slot(msk144_handle* h, int32_t slot, void** hops, void** first_ha
 
 int msk144_push_hops(msk144_handle* h, int32_t slot, int32_t n)
 {
-    if(!h || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
+    int rc = check_hop_slot(h, slot);
+    if(rc != MSK144_OK) return rc;
     if(!h->ring_ready) return fail(h, MSK144_ESTATE, "msk144_push_hops before msk144_hop_slot");
     if(n < 1 || n > h->st.channels) return fail(h, MSK144_EINVAL, "n must be 1..channels");
     msk144_handle::Slot& sl = h->slots[slot];
-    if(sl.pending) return fail(h, MSK144_ESTATE, "slot submitted again before its results were fetched (msk144_fetch_wait)");
     bool any_first = false;
     for(int32_t j = 0; j < n; j++)
     {
@@ -880,12 +860,9 @@ int msk144_push_hops(msk144_handle* h, int32_t slot, int32_t n)
             return fail(h, MSK144_EINVAL, "streams must be ascending stream numbers below channels");
         any_first = any_first || sl.is_first[j] != 0;
     }
-    HIP_TRY(h, hipSetDevice(h->params.device));
-    h->call_id++;
-    h->cur_slot = slot;
-    h->active = n;
+    if((rc = begin_hop(h, slot, n)) != MSK144_OK) return rc;
     const size_t half = window_bytes(h) / 2;
-    ev_begin(h, MSK144_T_H2D);
+    ev_begin(h);
     hipError_t e = hipMemcpyAsync(h->d_hops, sl.hops, half * n, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess && any_first) e = hipMemcpyAsync(h->d_first, sl.first_halves, half * n, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream);
@@ -910,7 +887,7 @@ int msk144_fetch_async(msk144_handle* h, int32_t slot)
     if(guess < 1024) guess = 1024;
     if(guess > h->st.max_results) guess = h->st.max_results;
     sl.copied = static_cast<int32_t>(guess);
-    ev_begin(h, MSK144_T_D2H);
+    ev_begin(h);
     hipError_t e = hipMemcpyAsync(sl.out_count, h->st.result_count, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(sl.out_seg, h->st.seg_power, sizeof(float) * 8 * h->active, hipMemcpyDeviceToHost, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(sl.out, sl.d_records, sizeof(msk144_result) * static_cast<size_t>(sl.copied), hipMemcpyDeviceToHost, h->stream);
@@ -1049,7 +1026,7 @@ int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz)
     if(!h->probe_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->probe_stream, hipStreamNonBlocking));
     if(!h->d_probe)
     {
-        int rc = dev_alloc(h, &h->d_probe, 2);
+        int rc = dev_alloc(h, h->mem, &h->d_probe, 2);
         if(rc != MSK144_OK) return rc;
     }
     launch_clock_probe(h->d_probe, static_cast<uint32_t>(spin_us) * 100u, h->probe_stream);
@@ -1090,46 +1067,7 @@ int msk144_stage_times(msk144_handle* h, float* avg_ms, int32_t* samples, int32_
     return MSK144_OK;
 }
 
-}  // extern "C"
-
 // ---- wideband channeliser ----
-
-namespace
-{
-
-void wb_release(msk144_handle* h)
-{
-    auto& w = h->wb;
-    for(void*& p : w.pinned)
-    {
-        if(p) (void)hipHostFree(p);
-        p = nullptr;
-    }
-    for(void** p : {&w.d_raw, reinterpret_cast<void**>(&w.d_G), reinterpret_cast<void**>(&w.d_fmod), reinterpret_cast<void**>(&w.d_rot),
-                    reinterpret_cast<void**>(&w.d_clip)})
-    {
-        if(*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    w.configured = false;
-}
-
-int wb_malloc(msk144_handle* h, void** p, size_t bytes)
-{
-    hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if(e != hipSuccess)
-    {
-        *p = nullptr;
-        char buf[160];
-        snprintf(buf, sizeof(buf), "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
-        return fail(h, MSK144_ENOMEM, buf);
-    }
-    return MSK144_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
 {
@@ -1155,19 +1093,12 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     const int C32 = (C + 31) / 32;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(wp->format));
     w.slot_bytes = static_cast<size_t>(kWindowSamples) * D * sb;
-    for(void*& p : w.pinned)
-        if((rc = host_alloc(h, &p, w.slot_bytes)) != MSK144_OK)
-        {
-            p = nullptr;
-            wb_release(h);
-            return rc;
-        }
+    for(uint8_t*& p : w.pinned)
+        if(rc == MSK144_OK) rc = host_alloc(h, w.mem, &p, w.slot_bytes);
     const size_t g_count = static_cast<size_t>(C32) * L * 32;
-    if((rc = wb_malloc(h, &w.d_raw, (static_cast<size_t>(L) - 1) * sb + w.slot_bytes)) != MSK144_OK ||
-       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_G), g_count * sizeof(float2))) != MSK144_OK ||
-       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_fmod), sizeof(int32_t) * C)) != MSK144_OK ||
-       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_rot), sizeof(float2) * msk144wb::kOutRate)) != MSK144_OK ||
-       (rc = wb_malloc(h, reinterpret_cast<void**>(&w.d_clip), sizeof(unsigned long long))) != MSK144_OK)
+    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, (static_cast<size_t>(L) - 1) * sb + w.slot_bytes)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_G, g_count)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_fmod, C)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_rot, msk144wb::kOutRate)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK)
     {
         wb_release(h);
         return rc;
@@ -1207,9 +1138,6 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     w.L = L;
     w.format = wp->format;
     w.gain = wp->gain;
-    w.m_next = 0;
-    w.started = false;
-    w.last_first = false;
     w.configured = true;
     return MSK144_OK;
 }
@@ -1225,14 +1153,14 @@ int msk144_wideband_slot(msk144_handle* h, int32_t slot, void** buf, size_t* byt
 
 int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
 {
-    if(!h || slot < 0 || slot >= MSK144_SLOTS) return fail(h, MSK144_EINVAL, "bad argument");
+    int rc = check_hop_slot(h, slot);
+    if(rc != MSK144_OK) return rc;
     auto& w = h->wb;
     if(!w.configured) return fail(h, MSK144_ESTATE, "msk144_push_wideband before msk144_set_wideband");
     if(!first && !w.started) return fail(h, MSK144_ESTATE, "a later wideband push before the first one");
-    msk144_handle::Slot& sl = h->slots[slot];
-    if(sl.pending) return fail(h, MSK144_ESTATE, "slot submitted again before its results were fetched (msk144_fetch_wait)");
-    HIP_TRY(h, hipSetDevice(h->params.device));
     const int C = h->params.channels;
+    if((rc = begin_hop(h, slot, C)) != MSK144_OK) return rc;
+    msk144_handle::Slot& sl = h->slots[slot];
     const int M = first ? kWindowSamples : kHopSamples;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
     const size_t hist_bytes = (static_cast<size_t>(w.L) - 1) * sb;
@@ -1243,11 +1171,8 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         sl.streams[j] = j;
         sl.is_first[j] = first ? 1 : 0;
     }
-    h->call_id++;
-    h->cur_slot = slot;
-    h->active = C;
-    uint8_t* raw = static_cast<uint8_t*>(w.d_raw);
-    ev_begin(h, MSK144_T_H2D);
+    uint8_t* raw = w.d_raw;
+    ev_begin(h);
     hipError_t e = hipSuccess;
     // the filter history: the last L-1 samples of the previous push (M*D >= 2592*D >= L-1, so the ranges do not overlap)
     if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) * w.D * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
@@ -1257,8 +1182,8 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     if(e == hipSuccess) e = hipMemsetAsync(w.d_clip, 0, sizeof(unsigned long long), h->stream);
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
-    ev_begin(h, MSK144_T_FRONTEND);
-    launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, static_cast<int8_t*>(h->d_first), static_cast<int8_t*>(h->d_hops), w.d_clip, C, w.D, w.K, M,
+    ev_begin(h);
+    launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, C, w.D, w.K, M,
                       first ? 1 : 0, w.m_next, w.gain, h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
@@ -1277,8 +1202,8 @@ int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out)
     HIP_TRY(h, hipSetDevice(h->params.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const size_t half = 2 * static_cast<size_t>(kHopSamples);
-    const uint8_t* first = static_cast<const uint8_t*>(h->d_first) + half * channel;
-    const uint8_t* hop = static_cast<const uint8_t*>(h->d_hops) + half * channel;
+    const uint8_t* first = h->d_first + half * channel;
+    const uint8_t* hop = h->d_hops + half * channel;
     if(h->wb.last_first)
     {
         HIP_TRY(h, hipMemcpy(out, first, half, hipMemcpyDeviceToHost));

@@ -20,19 +20,6 @@ LIB_PATH = os.path.join(_PKG, "libmsk144hip.so")
 STAGE_SCAN, STAGE_SOFTBITS, STAGE_INDEX, STAGE_LDPC, STAGE_COLLECT, STAGE_ALL = 1, 2, 4, 8, 16, 31
 T_NAMES = ("frontend", "scan", "softbits", "index", "ldpc", "collect", "h2d", "d2h")
 
-# every symbol include/msk144hip.h declares (tests check the library exports each of them)
-ABI_SYMBOLS = (
-    "msk144_default_params", "msk144_create", "msk144_destroy", "msk144_last_error", "msk144_geometry", "msk144_frequency",
-    "msk144_set_stream", "msk144_submit_audio", "msk144_submit_iq", "msk144_submit_audio_device", "msk144_submit_iq_device",
-    "msk144_submit_analytic", "msk144_decode", "msk144_decode_stages", "msk144_synchronize", "msk144_results",
-    "msk144_result_count", "msk144_results_device", "msk144_set_channel_base", "msk144_segment_power", "msk144_dump_analytic", "msk144_dump_candidates",
-    "msk144_dump_indexes", "msk144_load_candidates", "msk144_set_profiling", "msk144_stage_times",
-    "msk144_input_slot", "msk144_submit_slot", "msk144_submit_slot_n", "msk144_fetch_async", "msk144_fetch_wait", "msk144_hop_slot", "msk144_push_hops",
-    "msk144_device_count", "msk144_clock_probe", "msk144_set_copy_handover", "msk144_copy_handover", "msk144_copy_count",
-    "msk144_set_llr_retention", "msk144_llr_block_channels",
-    "msk144_set_wideband", "msk144_wideband_slot", "msk144_push_wideband", "msk144_dump_wideband_hop", "msk144_wideband_clip_count",
-)
-
 WB_FORMATS = {"cu8": 0, "cs8": 1, "cs16": 2}   # msk144_wideband_params.format
 
 
@@ -46,6 +33,57 @@ class Params(C.Structure):
                 ("nbadsync_threshold", C.c_int32), ("read_mode", C.c_int32), ("analytic_method", C.c_int32), ("channels", C.c_int32),
                 ("device", C.c_int32), ("max_results", C.c_int32), ("llr_block_channels", C.c_int32)]
 
+
+_vp, _i32, _P = C.c_void_p, C.c_int32, C.POINTER
+# name -> (argtypes, restype) of every symbol include/msk144hip.h declares (tests check the library exports each of them)
+PROTOTYPES = {
+    "msk144_default_params": ([_P(Params)], None),
+    "msk144_create": ([_P(Params), _P(_vp)], C.c_int),
+    "msk144_destroy": ([_vp], None),
+    "msk144_last_error": ([_vp], C.c_char_p),
+    "msk144_geometry": ([_vp, _P(_i32), _P(_i32), _P(_i32)], C.c_int),
+    "msk144_frequency": ([_vp, _i32, _P(C.c_float)], C.c_int),
+    "msk144_set_stream": ([_vp, _vp], C.c_int),
+    "msk144_submit_audio": ([_vp, _vp], C.c_int),
+    "msk144_submit_iq": ([_vp, _vp], C.c_int),
+    "msk144_submit_audio_device": ([_vp, _vp], C.c_int),
+    "msk144_submit_iq_device": ([_vp, _vp], C.c_int),
+    "msk144_submit_analytic": ([_vp, _vp], C.c_int),
+    "msk144_decode": ([_vp], C.c_int),
+    "msk144_decode_stages": ([_vp, C.c_uint32], C.c_int),
+    "msk144_synchronize": ([_vp], C.c_int),
+    "msk144_results": ([_vp, _vp, _i32, _P(_i32)], C.c_int),
+    "msk144_result_count": ([_vp, _P(_i32)], C.c_int),
+    "msk144_results_device": ([_vp, _P(_vp), _P(_vp)], C.c_int),
+    "msk144_set_channel_base": ([_vp, _i32], C.c_int),
+    "msk144_segment_power": ([_vp, _vp], C.c_int),
+    "msk144_dump_analytic": ([_vp, _i32, _vp], C.c_int),
+    "msk144_dump_candidates": ([_vp, _i32, _vp], C.c_int),
+    "msk144_dump_indexes": ([_vp, _i32, _vp, _P(_i32)], C.c_int),
+    "msk144_load_candidates": ([_vp, _i32, _vp], C.c_int),
+    "msk144_set_profiling": ([_vp, _i32], C.c_int),
+    "msk144_stage_times": ([_vp, _vp, _vp, _i32], C.c_int),
+    "msk144_input_slot": ([_vp, _i32, _P(_vp), _P(C.c_size_t)], C.c_int),
+    "msk144_submit_slot": ([_vp, _i32], C.c_int),
+    "msk144_submit_slot_n": ([_vp, _i32, _i32], C.c_int),
+    "msk144_fetch_async": ([_vp, _i32], C.c_int),
+    "msk144_fetch_wait": ([_vp, _i32, _P(_vp), _P(_i32), _P(_vp)], C.c_int),
+    "msk144_hop_slot": ([_vp, _i32, _P(_vp), _P(_vp), _P(_vp), _P(_vp)], C.c_int),
+    "msk144_push_hops": ([_vp, _i32, _i32], C.c_int),
+    "msk144_device_count": ([_P(_i32)], C.c_int),
+    "msk144_clock_probe": ([_vp, _i32, _P(C.c_float)], C.c_int),
+    "msk144_set_copy_handover": ([_vp, _i32], C.c_int),
+    "msk144_copy_handover": ([_vp, _P(_i32)], C.c_int),
+    "msk144_copy_count": ([_vp, _P(C.c_int64)], C.c_int),
+    "msk144_set_llr_retention": ([_vp, _i32], C.c_int),
+    "msk144_llr_block_channels": ([_vp, _P(_i32)], C.c_int),
+    "msk144_set_wideband": ([_vp, _P(WidebandParams)], C.c_int),
+    "msk144_wideband_slot": ([_vp, _i32, _P(_vp), _P(C.c_size_t)], C.c_int),
+    "msk144_push_wideband": ([_vp, _i32, _i32], C.c_int),
+    "msk144_dump_wideband_hop": ([_vp, _i32, _vp], C.c_int),
+    "msk144_wideband_clip_count": ([_vp, _P(C.c_int64)], C.c_int),
+}
+ABI_SYMBOLS = tuple(PROTOTYPES)
 
 RESULT_DTYPE = np.dtype([
     ("channel", "<i4"), ("item", "<i4"), ("f0", "<f4"), ("pattern_idx", "<i4"), ("num_avg", "<i4"), ("pos", "<u4"), ("xb", "<f4"),
@@ -84,52 +122,9 @@ def load_library(path: Optional[str] = None):
     if not os.path.exists(p):
         raise FileNotFoundError(f"{p} not found: build it with `python -m msk144cudecoder_amd.build` (hipcc, gfx950)")
     L = C.CDLL(p)
-    vp, i32 = C.c_void_p, C.c_int32
-    L.msk144_default_params.argtypes = [C.POINTER(Params)]
-    L.msk144_default_params.restype = None
-    L.msk144_create.argtypes = [C.POINTER(Params), C.POINTER(vp)]
-    L.msk144_destroy.argtypes = [vp]
-    L.msk144_destroy.restype = None
-    L.msk144_last_error.argtypes = [vp]
-    L.msk144_last_error.restype = C.c_char_p
-    L.msk144_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    L.msk144_frequency.argtypes = [vp, i32, C.POINTER(C.c_float)]
-    L.msk144_set_stream.argtypes = [vp, vp]
-    for n in ("msk144_submit_audio", "msk144_submit_iq", "msk144_submit_audio_device", "msk144_submit_iq_device", "msk144_submit_analytic"):
-        getattr(L, n).argtypes = [vp, vp]
-    L.msk144_decode.argtypes = [vp]
-    L.msk144_decode_stages.argtypes = [vp, C.c_uint32]
-    L.msk144_synchronize.argtypes = [vp]
-    L.msk144_results.argtypes = [vp, vp, i32, C.POINTER(i32)]
-    L.msk144_result_count.argtypes = [vp, C.POINTER(i32)]
-    L.msk144_results_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.msk144_set_channel_base.argtypes = [vp, i32]
-    L.msk144_segment_power.argtypes = [vp, vp]
-    L.msk144_dump_analytic.argtypes = [vp, i32, vp]
-    L.msk144_dump_candidates.argtypes = [vp, i32, vp]
-    L.msk144_dump_indexes.argtypes = [vp, i32, vp, C.POINTER(i32)]
-    L.msk144_load_candidates.argtypes = [vp, i32, vp]
-    L.msk144_set_profiling.argtypes = [vp, i32]
-    L.msk144_stage_times.argtypes = [vp, vp, vp, i32]
-    L.msk144_input_slot.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.msk144_submit_slot.argtypes = [vp, i32]
-    L.msk144_submit_slot_n.argtypes = [vp, i32, i32]
-    L.msk144_hop_slot.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.msk144_push_hops.argtypes = [vp, i32, i32]
-    L.msk144_fetch_async.argtypes = [vp, i32]
-    L.msk144_fetch_wait.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp)]
-    L.msk144_device_count.argtypes = [C.POINTER(i32)]
-    L.msk144_clock_probe.argtypes = [vp, i32, C.POINTER(C.c_float)]
-    L.msk144_set_copy_handover.argtypes = [vp, i32]
-    L.msk144_set_llr_retention.argtypes = [vp, i32]
-    L.msk144_llr_block_channels.argtypes = [vp, C.POINTER(i32)]
-    L.msk144_copy_handover.argtypes = [vp, C.POINTER(i32)]
-    L.msk144_copy_count.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.msk144_set_wideband.argtypes = [vp, C.POINTER(WidebandParams)]
-    L.msk144_wideband_slot.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.msk144_push_wideband.argtypes = [vp, i32, i32]
-    L.msk144_dump_wideband_hop.argtypes = [vp, i32, vp]
-    L.msk144_wideband_clip_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    for name, (argtypes, restype) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.argtypes, f.restype = argtypes, restype
     if path is None:
         _lib = L
     return L

@@ -36,9 +36,8 @@ def _pushes(raw, D):
     return out
 
 
-@pytest.mark.parametrize("D", [80, 160])
-@pytest.mark.parametrize("fmt", wb.FORMATS)
-def test_hops_match_the_model(hip, fmt, D):
+def _hops_match_the_model(d, fmt, D):
+    """Configure d for (fmt, D) and check the int8 hops of five pushes against the float64 model."""
     rate = D * 12000
     offsets = _offsets_64(D)
     rng = np.random.default_rng(1000 + D + len(fmt))
@@ -47,21 +46,35 @@ def test_hops_match_the_model(hip, fmt, D):
     raw = wb.write_samples(x, fmt)
     model = wb.Channeliser(rate, offsets)
     total = exact = 0
-    with hip.HipDecoder(channels=len(offsets), **DECODE_CFG) as d:
-        d.set_wideband(rate, offsets, fmt)
-        for i, part in enumerate(_pushes(raw, D)):
-            first = i == 0
-            d.push_wideband(i % 2, part, first=first)
-            q_ref, clip_ref = model.push(wb.read_samples(part, fmt), first=first)
-            got = np.stack([d.dump_wideband_hop(c) for c in range(len(offsets))])
-            assert got.shape == q_ref.shape
-            diff = np.abs(got.astype(np.int16) - q_ref.astype(np.int16))
-            assert diff.max() <= 1, f"push {i}: |dq| up to {diff.max()}"
-            total += diff.size
-            exact += int(np.count_nonzero(diff == 0))
-            assert d.wideband_clip_count() == clip_ref, f"push {i}"
-        d.synchronize()
+    d.set_wideband(rate, offsets, fmt)
+    for i, part in enumerate(_pushes(raw, D)):
+        first = i == 0
+        d.push_wideband(i % 2, part, first=first)
+        q_ref, clip_ref = model.push(wb.read_samples(part, fmt), first=first)
+        got = np.stack([d.dump_wideband_hop(c) for c in range(len(offsets))])
+        assert got.shape == q_ref.shape
+        diff = np.abs(got.astype(np.int16) - q_ref.astype(np.int16))
+        assert diff.max() <= 1, f"push {i}: |dq| up to {diff.max()}"
+        total += diff.size
+        exact += int(np.count_nonzero(diff == 0))
+        assert d.wideband_clip_count() == clip_ref, f"push {i}"
+    d.synchronize()
     assert exact / total >= 0.999, f"{total - exact} of {total} components differ by one LSB"
+
+
+@pytest.mark.parametrize("D", [80, 160])
+@pytest.mark.parametrize("fmt", wb.FORMATS)
+def test_hops_match_the_model(hip, fmt, D):
+    with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
+        _hops_match_the_model(d, fmt, D)
+
+
+def test_reconfigured_handle_matches_the_model(hip):
+    """msk144_set_wideband again on a handle that has pushed: another D, format and set of offsets (the same count) replace the
+    first configuration entirely."""
+    with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
+        _hops_match_the_model(d, "cu8", 80)
+        _hops_match_the_model(d, "cs16", 160)
 
 
 def test_later_push_before_first_is_refused(hip):
