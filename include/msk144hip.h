@@ -296,23 +296,31 @@ int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz);
  * channeliser writes every channel's hop into the hop ring's device staging (as msk144_push_hops would have copied it), then the
  * hop ring and the IQ front end run unchanged.
  *
- *   Input:        interleaved I,Q samples at Fs = D x 12000 Hz, 2 <= D <= 512 (1.92 Msps: D = 160; 2.4 Msps: D = 200), as
- *                 cu8 (rtl_sdr, (u - 127.5) / 128), cs8 (s / 128) or cs16 (s / 32768).
+ *   Input:        interleaved I,Q samples at Fs = 12000 x P/Q Hz (P/Q in lowest terms), Fs an integer multiple of 125 with
+ *                 24000 <= Fs <= 6144000, i.e. 2 <= P/Q <= 512; Q then divides 96.  Q = 1 is decimation by the integer D = P
+ *                 (1.92 Msps: D = 160; 2.4 Msps: D = 200); otherwise e.g. 2.048 Msps = 12000 x 512/3, 250 ksps = 12000 x 125/6.
+ *                 As cu8 (rtl_sdr, (u - 127.5) / 128), cs8 (s / 128) or cs16 (s / 32768).
  *   Offsets:      integer Hz, |f_c| <= Fs/2 - 6000, one per channel, no grid needed.
- *   Filter:       a real low-pass h[0..L), L = K x D, 1 <= K <= 64, supplied by the caller.  The default design (K = 16, a
- *                 Kaiser-windowed sinc at unit DC gain: flat within 0.1 dB to 4 kHz, >= 60 dB down from 8 kHz for D in
- *                 {40, 80, 160, 200}) is msk144host_wideband_taps in libmsk144host.so, the taps msk144hipdecoder uses.
+ *   Filter:       a real low-pass h[0..L), L = K x P, 1 <= K <= 64, at the upsampled rate Q x Fs = P x 12000, supplied by the
+ *                 caller (num_taps = K x D for Q = 1).  The default design (K = 16, a Kaiser-windowed sinc: flat within 0.1 dB to
+ *                 4 kHz, >= 60 dB down from 8 kHz) sums to Q, so that every branch h[r], h[r + Q], ... has about unit DC gain; it is
+ *                 msk144host_wideband_taps_rate(rate, K) in libmsk144host.so (msk144host_wideband_taps(D, K) for Q = 1, the same
+ *                 taps), the taps msk144hipdecoder uses.
  *   Output:       y_c[m] = e^{-j2pi f_c m / 12000} . sum_{k<L} (h[k] e^{+j2pi f_c k / Fs}) . x[mD - k]
  *                 - mix, filter and decimate by D - with m the 64-bit output index from the first sample of the stream,
  *                 x[n < 0] = 0, and the phases reduced in integers, (f_c m) mod 12000 and (f_c k) mod Fs, so they do not drift.
+ *                 For Q > 1, with n_m = floor(m P / Q) and r_m = (m P) mod Q - mix at Fs, upsample by Q, filter, keep every P-th:
+ *                   y_c[m] = e^{-j2pi ((f_c n_m) mod Fs)/Fs} . sum_{k >= 0, r_m + kQ < L} h[r_m + kQ] e^{+j2pi ((f_c k) mod Fs)/Fs} x[n_m - k]
+ *                 which is the formula above for Q = 1, as (f_c m D) mod (12000 D) = D ((f_c m) mod 12000); phases in 64-bit integers.
  *                 I and Q are q = clamp(rint(128 . gain . y), -128, 127) each (default gain 100, the csdr gain_ff stage); a
  *                 component whose rounded value lies outside [-128, 127] counts as clipped.  f32 arithmetic on the device.
- *   Hops:         a first push carries 5184 x D wideband samples (5184 output samples per channel), every later push 2592 x D
- *                 (2592).  The filter history (the last L-1 input samples) and m stay on the device between pushes; a first push
- *                 restarts the stream (m = 0, zero history).
+ *   Hops:         a first push carries 5184 x P/Q wideband samples (5184 output samples per channel), every later push
+ *                 2592 x P/Q (2592); whole numbers, as Q divides 2592.  The filter history (the last ceil(L/Q) - 1 input samples, L - 1
+ *                 for Q = 1: what the longest branch needs) and m stay on the device between pushes; a first push restarts the stream
+ *                 (m = 0, zero history).
  *
  *     msk144_set_wideband(h, &wp);                  read_mode 2 handle, num_offsets == channels; resets history and m
- *     msk144_wideband_slot(h, s, &buf, &bytes);     pinned, 5184 x D samples; fill 5184 x D (first) or 2592 x D samples
+ *     msk144_wideband_slot(h, s, &buf, &bytes);     pinned, 5184 x P/Q samples; fill 5184 x P/Q (first) or 2592 x P/Q
  *     msk144_push_wideband(h, s, first);            H2D + channeliser + hop ring + IQ front end on the handle's stream
  *     msk144_decode / msk144_fetch_async / msk144_fetch_wait   as after msk144_push_hops (record channel = channel index)
  *
@@ -326,11 +334,11 @@ enum
 
 typedef struct msk144_wideband_params
 {
-    int64_t rate_hz;          /* Fs = D x 12000 */
+    int64_t rate_hz;          /* Fs = 12000 x P/Q (D x 12000 for Q = 1) */
     int32_t format;           /* MSK144_WB_* */
     int32_t taps_per_phase;   /* K */
     float gain;               /* output gain before int8 (default 100) */
-    int32_t num_taps;         /* = K x D */
+    int32_t num_taps;         /* = K x P (K x D for Q = 1) */
     const double* taps;       /* h[0 .. num_taps) */
     const int32_t* offsets_hz;/* f_c of channel 0 .. num_offsets-1 */
     int32_t num_offsets;      /* = channels */

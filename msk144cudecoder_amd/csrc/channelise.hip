@@ -16,6 +16,11 @@
 // Output: q = clamp(rint(128 * gain * y), -128, 127) for I and Q, written as int8 pairs straight into the hop ring's staging
 // (first push: samples 0..2591 into first_halves, 2592..5183 into hops; later pushes: hops).  A component counts as clipped when
 // its rounded value lies outside [-128, 127].
+//
+// Rational rates, Fs = 12000 P/Q with Q > 1 (channelise_rational_kernel): output m = mr + Q a reads n_m = n0 + a P with
+// n0 = floor(mr P/Q) and the taps h[r + kQ], r = mr P mod Q, k < K_r = ceil((L - r)/Q).  Each of the Q residues mr is a
+// decimate-by-P GEMM of its own, tiled as above (blockIdx.z = mr) with k = p + P q: the loop walks exactly the K_r taps of the
+// branch - phases p < s carry ceil(K_r/P) taps, the others one fewer - and the outputs land Q apart in the same staging.
 #include "msk144_kernels.h"
 
 namespace msk144
@@ -159,6 +164,119 @@ __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __rest
     if(lane == 0 && clipped) atomicAdd(clip_count, static_cast<unsigned long long>(clipped));
 }
 
+template<int FMT>
+__global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const void* __restrict__ raw, const float2* __restrict__ G,
+                                                                       const WidebandBranch* __restrict__ branches, const int32_t* __restrict__ fmod,
+                                                                       const float2* __restrict__ rot, int8_t* __restrict__ first_halves,
+                                                                       int8_t* __restrict__ hops, unsigned long long* __restrict__ clip_count, int channels,
+                                                                       int P, int Q, int hist, int M, int first, long long m_base, float scale)
+{
+    __shared__ float xs[2][kPhaseChunk][kMaxSpan];
+
+    const int mr = blockIdx.z;
+    const WidebandBranch br = branches[mr];
+    const int Kr = br.taps;
+    const int Kq = (Kr + P - 1) / P;         // taps of the longest phases
+    const int s_full = Kr - (Kq - 1) * P;    // phases 0 .. s_full-1 have Kq taps, the others Kq-1
+    const int phases = min(P, Kr);
+    const int A = M / Q;                     // outputs of this branch in the push
+    const int n_in = hist + A * P;           // samples in raw
+    const int span = kTileSamples + Kq - 1;
+    const int at0 = blockIdx.x * kTileSamples;
+    const int base = hist + br.n0 + (at0 - Kq + 1) * P;  // raw index of xp[0][0]
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int j = lane & 31;
+    const int hsel = lane >> 5;
+    const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
+    const bool active = cb32 * 32 < channels;
+    const float2* __restrict__ g = G + br.g_off + static_cast<size_t>(cb32) * Kr * 32 + j;
+
+    f32x16 acc_re0 = {}, acc_im0 = {}, acc_re1 = {}, acc_im1 = {};
+
+    for(int p0 = 0; p0 < phases; p0 += kPhaseChunk)
+    {
+        const int pc = min(kPhaseChunk, phases - p0);
+        __syncthreads();
+        // xp[p][n] = raw[base + n P - p]: output at0 + n - (Kq-1), tap p (+ P q for the q-th tap of the phase, read at n - q)
+        for(int e = threadIdx.x; e < pc * span; e += kThreads)
+        {
+            const int pl = e % pc;
+            const int n = e / pc;
+            const int i = base + n * P - (p0 + pl);
+            float2 v = make_float2(0.0f, 0.0f);
+            if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
+            xs[0][pl][n] = v.x;
+            xs[1][pl][n] = v.y;
+        }
+        __syncthreads();
+        if(!active) continue;
+        const int t0 = p0 * Kq - max(0, p0 - s_full);
+        const int T = (p0 + pc) * Kq - max(0, p0 + pc - s_full) - t0;
+        const float2* __restrict__ gp = g + static_cast<size_t>(t0) * 32;
+        const float* __restrict__ xrow = &xs[hsel][0][j + Kq - 1];
+        float2 gnext = gp[0];
+        int pl = 0, q = 0;
+        int kp = p0 < s_full ? Kq : Kq - 1;
+        for(int t = 0; t < T; t++)
+        {
+            const float2 gv = gnext;
+            if(t + 1 < T) gnext = gp[static_cast<size_t>(t + 1) * 32];
+            const float a_re = hsel ? -gv.y : gv.x;
+            const float a_im = hsel ? gv.x : gv.y;
+            const float* xr = xrow + pl * kMaxSpan - q;
+            const float b0 = xr[0];
+            const float b1 = xr[32];
+            acc_re0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b0, acc_re0, 0, 0, 0);
+            acc_im0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b0, acc_im0, 0, 0, 0);
+            acc_re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b1, acc_re1, 0, 0, 0);
+            acc_im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b1, acc_im1, 0, 0, 0);
+            if(++q == kp)
+            {
+                q = 0;
+                pl++;
+                kp = p0 + pl < s_full ? Kq : Kq - 1;
+            }
+        }
+    }
+    if(!active) return;
+
+    unsigned int clipped = 0;
+    const int half = kHalf;
+#pragma unroll
+    for(int s = 0; s < 2; s++)
+    {
+        const int a = at0 + s * 32 + j;
+        if(a >= A) continue;
+        const int mo = mr + Q * a;
+        // f_c n_m / Fs = f_c (m - mr) / 12000 + f_c n0 / Fs; the second term is in G
+        const int mm = static_cast<int>((m_base + static_cast<long long>(Q) * a) % kChannelRate);
+        int8_t* __restrict__ dst = hops;
+        int idx = mo;
+        if(first && mo < half) dst = first_halves;
+        else if(first) idx = mo - half;
+#pragma unroll
+        for(int r = 0; r < 16; r++)
+        {
+            const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+            if(c >= channels) continue;
+            const float yr = s ? acc_re1[r] : acc_re0[r];
+            const float yi = s ? acc_im1[r] : acc_im0[r];
+            const int ph = (fmod[c] * mm) % kChannelRate;
+            const float2 e = rot[ph];
+            const float vr = rintf(scale * (yr * e.x - yi * e.y));
+            const float vi = rintf(scale * (yr * e.y + yi * e.x));
+            clipped += (vr < -128.0f || vr > 127.0f) + (vi < -128.0f || vi > 127.0f);
+            char2 o;
+            o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
+            o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
+            reinterpret_cast<char2*>(dst)[static_cast<size_t>(c) * half + idx] = o;
+        }
+    }
+    for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
+    if(lane == 0 && clipped) atomicAdd(clip_count, static_cast<unsigned long long>(clipped));
+}
+
 }  // namespace
 
 void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
@@ -172,6 +290,23 @@ void launch_channelise(const void* raw, int format, const float2* G, const int32
         hipLaunchKernelGGL(channelise_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
     else
         hipLaunchKernelGGL(channelise_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+}
+
+void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
+                                int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
+                                long long m_base, float gain, hipStream_t stream)
+{
+    const dim3 grid((M / Q + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels, Q);
+    const float scale = 128.0f * gain;
+    if(format == 0)
+        hipLaunchKernelGGL(channelise_rational_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
+                           first, m_base, scale);
+    else if(format == 1)
+        hipLaunchKernelGGL(channelise_rational_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
+                           first, m_base, scale);
+    else
+        hipLaunchKernelGGL(channelise_rational_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
+                           first, m_base, scale);
 }
 
 }  // namespace msk144

@@ -117,13 +117,16 @@ struct msk144_handle
         bool configured = false;
         bool started = false;     // a first push has been made since the configuration
         bool last_first = false;  // the last push was a first push (5184 samples per channel)
-        int D = 0, K = 0, L = 0, format = 0;
+        int P = 0, Q = 0;         // Fs = 12000 P/Q in lowest terms; Q = 1: decimation by D = P
+        int K = 0, L = 0, format = 0;
+        int hist = 0;             // history samples kept between pushes: ceil(L/Q) - 1 (L - 1 for Q = 1)
         float gain = 0.0f;
         long long m_next = 0;     // output sample index of the next push
-        size_t slot_bytes = 0;    // pinned bytes per slot: 5184*D samples
+        size_t slot_bytes = 0;    // pinned bytes per slot: 5184*P/Q samples
         uint8_t* pinned[MSK144_SLOTS] = {};
-        uint8_t* d_raw = nullptr; // L-1 history samples + the samples of one push, raw format
-        float2* d_G = nullptr;    // [ceil(channels/32)][D][K][32]
+        uint8_t* d_raw = nullptr; // history samples + the samples of one push, raw format
+        float2* d_G = nullptr;    // Q = 1: [ceil(channels/32)][D][K][32]; Q > 1: one block per branch (WidebandBranch)
+        WidebandBranch* d_branches = nullptr;  // [Q], Q > 1 only
         int32_t* d_fmod = nullptr;
         float2* d_rot = nullptr;  // [12000]
         unsigned long long* d_clip = nullptr;
@@ -1076,10 +1079,12 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     if(wp->num_offsets != h->params.channels) return fail(h, MSK144_EINVAL, "the number of channel offsets must equal the handle's channels");
     const std::string why = msk144wb::check_config(wp->rate_hz, wp->format, wp->taps_per_phase, wp->gain, wp->offsets_hz, wp->num_offsets);
     if(!why.empty()) return fail(h, MSK144_EINVAL, why);
-    const int D = static_cast<int>(wp->rate_hz / msk144wb::kOutRate);
+    const msk144wb::RateRatio rr = msk144wb::rate_ratio(wp->rate_hz);
+    const int P = rr.P, Q = rr.Q;
     const int K = wp->taps_per_phase;
-    const int L = K * D;
-    if(!wp->taps || wp->num_taps != L) return fail(h, MSK144_EINVAL, "the filter needs taps_per_phase x D taps");
+    const int L = K * P;
+    if(!wp->taps || wp->num_taps != L)
+        return fail(h, MSK144_EINVAL, Q == 1 ? "the filter needs taps_per_phase x D taps" : "the filter needs taps_per_phase x P taps (rate = 12000 x P/Q)");
     for(int k = 0; k < L; k++)
         if(!std::isfinite(wp->taps[k])) return fail(h, MSK144_EINVAL, "filter taps must be finite");
 
@@ -1092,13 +1097,15 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     const int C = h->params.channels;
     const int C32 = (C + 31) / 32;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(wp->format));
-    w.slot_bytes = static_cast<size_t>(kWindowSamples) * D * sb;
+    const int hist = (L + Q - 1) / Q - 1;
+    w.slot_bytes = static_cast<size_t>(kWindowSamples) / Q * P * sb;
     for(uint8_t*& p : w.pinned)
         if(rc == MSK144_OK) rc = host_alloc(h, w.mem, &p, w.slot_bytes);
     const size_t g_count = static_cast<size_t>(C32) * L * 32;
-    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, (static_cast<size_t>(L) - 1) * sb + w.slot_bytes)) != MSK144_OK ||
+    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, static_cast<size_t>(hist) * sb + w.slot_bytes)) != MSK144_OK ||
        (rc = dev_alloc(h, w.mem, &w.d_G, g_count)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_fmod, C)) != MSK144_OK ||
-       (rc = dev_alloc(h, w.mem, &w.d_rot, msk144wb::kOutRate)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK)
+       (rc = dev_alloc(h, w.mem, &w.d_rot, msk144wb::kOutRate)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK ||
+       (Q > 1 && (rc = dev_alloc(h, w.mem, &w.d_branches, Q)) != MSK144_OK))
     {
         wb_release(h);
         return rc;
@@ -1106,13 +1113,40 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
 
     // G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs} in double, stored f32 at [c/32][p][q][c%32] with k = p + D*q; phases in integers
     const long long fs = static_cast<long long>(wp->rate_hz);
+    const int D = P;
     std::vector<float2> G(g_count, make_float2(0.0f, 0.0f));
     std::vector<int32_t> fmod(static_cast<size_t>(C));
+    std::vector<WidebandBranch> branches(Q > 1 ? static_cast<size_t>(Q) : 0);
     for(int c = 0; c < C; c++)
     {
         const long long f = wp->offsets_hz[c];
         fmod[static_cast<size_t>(c)] = static_cast<int32_t>(((f % msk144wb::kOutRate) + msk144wb::kOutRate) % msk144wb::kOutRate);
         const long long fpos = ((f % fs) + fs) % fs;
+        if(Q > 1)
+        {
+            // branch mr (outputs mr + Q a): G_r[c][k] = h[r + kQ] e^{+j2pi (f_c (k - n0) mod Fs)/Fs}, k = p + P q in phase-major order,
+            // blocks one after another by mr, each [c/32][taps][c%32]
+            long long off = 0;
+            for(int mr = 0; mr < Q; mr++)
+            {
+                const int r = static_cast<int>(static_cast<long long>(mr) * P % Q);
+                const int n0 = static_cast<int>(static_cast<long long>(mr) * P / Q);
+                const int Kr = (L - r + Q - 1) / Q;
+                branches[static_cast<size_t>(mr)] = WidebandBranch{off, n0, Kr};
+                const long long rot0 = (fpos * n0) % fs;
+                size_t t = static_cast<size_t>(off) + static_cast<size_t>(c / 32) * Kr * 32 + (c % 32);
+                for(int p = 0; p < std::min(P, Kr); p++)
+                    for(int k = p; k < Kr; k += P, t += 32)
+                    {
+                        const long long ph_i = ((fpos * k) % fs - rot0 + fs) % fs;
+                        const double ph = 2.0 * M_PI * static_cast<double>(ph_i) / static_cast<double>(fs);
+                        const double hk = wp->taps[r + static_cast<size_t>(k) * Q];
+                        G[t] = make_float2(static_cast<float>(hk * std::cos(ph)), static_cast<float>(hk * std::sin(ph)));
+                    }
+                off += static_cast<long long>(C32) * Kr * 32;
+            }
+            continue;
+        }
         for(int p = 0; p < D; p++)
             for(int q = 0; q < K; q++)
             {
@@ -1132,10 +1166,13 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     HIP_TRY(h, hipMemcpy(w.d_G, G.data(), g_count * sizeof(float2), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(w.d_fmod, fmod.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(w.d_rot, rot.data(), sizeof(float2) * rot.size(), hipMemcpyHostToDevice));
+    if(Q > 1) HIP_TRY(h, hipMemcpy(w.d_branches, branches.data(), sizeof(WidebandBranch) * branches.size(), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
-    w.D = D;
+    w.P = P;
+    w.Q = Q;
     w.K = K;
     w.L = L;
+    w.hist = hist;
     w.format = wp->format;
     w.gain = wp->gain;
     w.configured = true;
@@ -1163,8 +1200,8 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     msk144_handle::Slot& sl = h->slots[slot];
     const int M = first ? kWindowSamples : kHopSamples;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
-    const size_t hist_bytes = (static_cast<size_t>(w.L) - 1) * sb;
-    const size_t new_bytes = static_cast<size_t>(M) * w.D * sb;
+    const size_t hist_bytes = static_cast<size_t>(w.hist) * sb;
+    const size_t new_bytes = static_cast<size_t>(M) / w.Q * w.P * sb;
     if(first) w.m_next = 0;
     for(int j = 0; j < C; j++)
     {
@@ -1174,8 +1211,9 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     uint8_t* raw = w.d_raw;
     ev_begin(h);
     hipError_t e = hipSuccess;
-    // the filter history: the last L-1 samples of the previous push (M*D >= 2592*D >= L-1, so the ranges do not overlap)
-    if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) * w.D * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
+    // the filter history: the last hist samples of the previous push (a push has >= 2592*P/Q samples, hist < ceil(64*P/Q), so the
+    // ranges do not overlap)
+    if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Q * w.P * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(raw + hist_bytes, w.pinned[slot], new_bytes, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, C, hipMemcpyHostToDevice, h->stream);
@@ -1183,8 +1221,12 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
     ev_begin(h);
-    launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, C, w.D, w.K, M,
-                      first ? 1 : 0, w.m_next, w.gain, h->stream);
+    if(w.Q == 1)
+        launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, C, w.P, w.K, M,
+                          first ? 1 : 0, w.m_next, w.gain, h->stream);
+    else
+        launch_channelise_rational(w.d_raw, w.format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops),
+                                   w.d_clip, C, w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     w.m_next += M;

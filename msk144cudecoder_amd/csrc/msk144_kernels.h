@@ -82,6 +82,21 @@ void launch_hop_ring(void* ring, const void* hops, const void* first_halves, con
 void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
                        unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream);
 
+// one polyphase branch of a rational-rate channeliser (Fs = 12000 P/Q, Q > 1): the outputs m = mr + Q a of a push read inputs
+// n0 + a P - k, k < taps, with the taps h[r + k Q] (r = mr P mod Q) of its G block, which starts at float2 offset g_off
+struct WidebandBranch
+{
+    long long g_off;  // G block: [ceil(channels/32)][taps in phase-major order, k = p + P q][32]
+    int n0;           // floor(mr P / Q)
+    int taps;         // ceil((L - r) / Q)
+};
+
+// the same for Fs = 12000 P/Q with Q > 1: raw = `hist` history samples then M*P/Q new ones; branches[0..Q) by output residue mr.
+// G carries each branch's constant output rotation e^{-j2pi (f_c n0 mod Fs)/Fs}, so the kernel rotates by (f_c (m - mr)) mod 12000.
+void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
+                                int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
+                                long long m_base, float gain, hipStream_t stream);
+
 // one wave that spins for `ticks` of the 100 MHz counter; out[0] = shader cycles elapsed, out[1] = 100 MHz ticks elapsed (hopring.hip)
 void launch_clock_probe(uint64_t* out, uint32_t ticks, hipStream_t stream);
 

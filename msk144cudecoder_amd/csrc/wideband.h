@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -15,6 +16,9 @@ namespace msk144wb
 constexpr int kOutRate = 12000;        // channel output rate, samples per second
 constexpr int kMinDecimation = 2;
 constexpr int kMaxDecimation = 512;
+constexpr int kRateStepHz = 125;       // Fs = 12000 P/Q: a multiple of 125 Hz, so that a 2592-sample hop is 27 Fs/125 inputs
+constexpr int64_t kMinRateHz = static_cast<int64_t>(kMinDecimation) * 12000;
+constexpr int64_t kMaxRateHz = static_cast<int64_t>(kMaxDecimation) * 12000;
 constexpr int kMaxTapsPerPhase = 64;   // K; L = K*D taps
 constexpr int kDefaultTapsPerPhase = 16;
 constexpr float kDefaultGain = 100.0f; // the `csdr gain_ff 100` stage of a CPU decimation chain
@@ -45,7 +49,8 @@ inline double bessel_i0(double x)
     return sum;
 }
 
-// Default prototype low-pass, L = K*D taps at Fs = D*12000: a Kaiser-windowed sinc with its cut-off half way between the 4 kHz
+// Default prototype low-pass, L = K*D taps at Fs = D*12000 (for a rational rate 12000 P/Q: D = P, at the upsampled rate; see
+// design_taps_rate): a Kaiser-windowed sinc with its cut-off half way between the 4 kHz
 // pass edge and the 8 kHz stop edge, scaled to unit DC gain.  Symmetric about (L-1)/2.
 inline std::vector<double> design_taps(int D, int K)
 {
@@ -70,12 +75,35 @@ inline std::vector<double> design_taps(int D, int K)
     return h;
 }
 
+// Fs / 12000 = P/Q in lowest terms (Q = 1: the integer decimation D = P).  Q divides 96 for every rate that check_config accepts.
+struct RateRatio
+{
+    int P = 0, Q = 0;
+};
+
+inline RateRatio rate_ratio(int64_t rate_hz)
+{
+    const int64_t g = std::gcd(rate_hz, static_cast<int64_t>(kOutRate));
+    return RateRatio{static_cast<int>(rate_hz / g), static_cast<int>(kOutRate / g)};
+}
+
+// The default prototype for Fs = 12000 P/Q: design_taps(P, K) - the same Kaiser-sinc at the upsampled rate Q Fs = 12000 P, L = K P
+// taps - scaled to sum to Q, so that each of the Q polyphase branches h[r], h[r + Q], ... has about unit DC gain.  Q = 1 is
+// design_taps(D, K) exactly.
+inline std::vector<double> design_taps_rate(int64_t rate_hz, int K)
+{
+    const RateRatio rr = rate_ratio(rate_hz);
+    std::vector<double> h = design_taps(rr.P, K);
+    if(rr.Q > 1)
+        for(double& v : h) v *= rr.Q;
+    return h;
+}
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {
-    if(rate_hz <= 0 || rate_hz % kOutRate != 0) return "wideband rate must be a positive multiple of 12000 Hz";
-    const int64_t D = rate_hz / kOutRate;
-    if(D < kMinDecimation || D > kMaxDecimation) return "wideband rate must be D x 12000 Hz with 2 <= D <= 512";
+    if(rate_hz <= 0 || rate_hz % kRateStepHz != 0) return "wideband rate must be a positive multiple of 125 Hz; a multiple of 12000 Hz decimates by an integer";
+    if(rate_hz < kMinRateHz || rate_hz > kMaxRateHz) return "wideband rate must be D x 12000 Hz with 2 <= D <= 512 (D = P/Q may be a fraction: 24000..6144000 Hz)";
     if(format != kCu8 && format != kCs8 && format != kCs16) return "wideband format must be cu8, cs8 or cs16";
     if(K < 1 || K > kMaxTapsPerPhase) return "taps per phase must be 1..64";
     if(!(gain > 0.0f) || !std::isfinite(gain)) return "wideband gain must be a positive finite number";

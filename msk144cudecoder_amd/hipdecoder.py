@@ -307,14 +307,16 @@ class HipDecoder:
     # ---- wideband channeliser (read_mode 2 handles) ----
     def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0):
         """Configure the down-converter bank: one channel per offset (len == channels).  taps=None: the default design of
-        libmsk144host.so (msk144cudecoder_amd.wideband.default_taps)."""
+        libmsk144host.so: wideband.default_taps(D) at rate_hz = D x 12000, wideband.default_taps_for_rate for any other rate
+        12000 x P/Q (K*P taps summing to Q)."""
+        from .wideband import default_taps, default_taps_for_rate, rate_ratio
+        P, Q = rate_ratio(int(rate_hz)) if int(rate_hz) > 0 else (0, 1)
         if taps is None:
-            from .wideband import default_taps
-            taps = default_taps(int(rate_hz) // 12000, taps_per_phase)
+            taps = default_taps(P, taps_per_phase) if Q == 1 else default_taps_for_rate(int(rate_hz), taps_per_phase)
         self._wb_taps = np.ascontiguousarray(taps, dtype=np.float64)
         self._wb_offsets = np.ascontiguousarray(offsets_hz, dtype=np.int32)
         self._wb_format = fmt
-        self._wb_D = int(rate_hz) // 12000
+        self._wb_P, self._wb_Q = P, Q
         wp = WidebandParams(int(rate_hz), WB_FORMATS[fmt], int(taps_per_phase), float(gain), len(self._wb_taps),
                             self._wb_taps.ctypes.data_as(C.POINTER(C.c_double)), self._wb_offsets.ctypes.data_as(C.POINTER(C.c_int32)),
                             len(self._wb_offsets))
@@ -328,11 +330,12 @@ class HipDecoder:
         return np.frombuffer((C.c_uint8 * nbytes.value).from_address(ptr.value), dtype=dt)
 
     def push_wideband(self, slot: int, samples: Optional[np.ndarray] = None, first: bool = False):
-        """samples (raw components, 2*5184*D for a first push, else 2*2592*D) are copied into the slot first when given."""
+        """samples (raw components, 2*5184*P/Q for a first push, else 2*2592*P/Q; P/Q = D at an integer rate) are copied into the
+        slot first when given."""
         if samples is not None:
             buf = self.wideband_slot(slot)
             a = np.asarray(samples).reshape(-1)
-            want = 2 * (5184 if first else 2592) * self._wb_D
+            want = 2 * (5184 if first else 2592) // self._wb_Q * self._wb_P
             if a.size != want:
                 raise ValueError(f"a {'first' if first else 'later'} push carries {want} components, got {a.size}")
             buf[:want] = a

@@ -20,6 +20,18 @@ int msk144host_wideband_taps(int D, int K, double* out)
     return static_cast<int>(h.size());
 }
 
+// The same for any wideband rate Fs = 12000 P/Q (csrc/wideband.h design_taps_rate): L = K*P taps summing to Q into out; returns L,
+// or -1 for a rate the contract refuses (not a multiple of 125 Hz, outside 24000..6144000 Hz) or K outside 1..64.  For Q = 1 the
+// taps of msk144host_wideband_taps(D, K).
+int msk144host_wideband_taps_rate(int64_t rate_hz, int K, double* out)
+{
+    if(rate_hz <= 0 || rate_hz % msk144wb::kRateStepHz != 0 || rate_hz < msk144wb::kMinRateHz || rate_hz > msk144wb::kMaxRateHz || K < 1 || K > msk144wb::kMaxTapsPerPhase)
+        return -1;
+    const std::vector<double> h = msk144wb::design_taps_rate(rate_hz, K);
+    if(out) std::memcpy(out, h.data(), sizeof(double) * h.size());
+    return static_cast<int>(h.size());
+}
+
 void* msk144host_table_new() { return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

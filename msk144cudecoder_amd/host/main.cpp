@@ -64,12 +64,12 @@ void show_help(const char* prog)
     std::cout << "                   --max-results=N             Capacity of the per-hop decode list of a device (default 256 per stream + 131072). A hop that exceeds it is cut and reported; decoding goes on." << std::endl;
     std::cout << "                   --every-slot                Demodulate and decode every candidate slot on its own, as the reference does. Default off: a slot whose position folds the same frames as a lower slot of its group reports that slot's result (same output), and a candidate the nbadsync gate drops is not demodulated beyond its sync check." << std::endl;
     std::cout << "                   --timing                    With --inputs: per-hop host and device time split (ingest, H2D, GPU, D2H, post-processing) on stderr at the end." << std::endl;
-    std::cout << "                   --wideband-rate=HZ          Read ONE wideband I/Q stream on stdin at HZ = D x 12000 (2 <= D <= 512, e.g. 1920000) and channelise it on the GPU into one 12000 sps IQ stream per channel offset (as --read-mode=2 would read it); lines carry ch=<index>." << std::endl;
+    std::cout << "                   --wideband-rate=HZ          Read ONE wideband I/Q stream on stdin at HZ sps and channelise it on the GPU into one 12000 sps IQ stream per channel offset (as --read-mode=2 would read it); lines carry ch=<index>. HZ is a multiple of 125 from 24000 to 6144000: HZ = 12000 x P/Q, 2 <= P/Q <= 512; a multiple of 12000 (e.g. 1920000) decimates by the integer D = HZ/12000, any other rate (e.g. 2048000 = 12000 x 512/3, rtl_sdr's default) resamples by P/Q." << std::endl;
     std::cout << "                   --wideband-format=FMT       cu8 (rtl_sdr), cs8 or cs16 interleaved I,Q. Default=cu8." << std::endl;
     std::cout << "                   --channel-offsets=F1,F2,... Channel centres in integer Hz from the wideband centre, |F| <= HZ/2 - 6000." << std::endl;
     std::cout << "                   --channel-grid=F:STEP:N     The same as N offsets F, F+STEP, ..." << std::endl;
     std::cout << "                   --wideband-gain=G           Gain before each channel's int8 I/Q (the csdr gain_ff stage). Default=100." << std::endl;
-    std::cout << "                   --taps-per-phase=K          Channel filter length K x D taps (1..64). Default=16." << std::endl;
+    std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
 
@@ -394,12 +394,13 @@ int main(int argc, char* const argv[])
     if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
     if(wideband)
     {
-        const int Dw = static_cast<int>(wbo.rate_hz / msk144wb::kOutRate);
+        const msk144wb::RateRatio rr = msk144wb::rate_ratio(wbo.rate_hz);
         static const char* fmt_names[] = {"cu8", "cs8", "cs16"};
-        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, decimation " << Dw << ", filter " << wbo.taps_per_phase << " x " << Dw
-                  << " taps, gain " << wbo.gain << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
+        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, "
+                  << (rr.Q == 1 ? "decimation " + std::to_string(rr.P) : "resampling " + std::to_string(rr.P) + "/" + std::to_string(rr.Q)) << ", filter "
+                  << wbo.taps_per_phase << " x " << rr.P << " taps, gain " << wbo.gain << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
         for(int c = 0; c < nch; c++) std::cerr << "msk144hipdecoder: ch=" << c << " offset " << wbo.offsets[static_cast<size_t>(c)] << " Hz" << std::endl;
-        const std::vector<double> taps = msk144wb::design_taps(Dw, wbo.taps_per_phase);
+        const std::vector<double> taps = msk144wb::design_taps_rate(wbo.rate_hz, wbo.taps_per_phase);
         msk144_wideband_params wp{};
         wp.rate_hz = wbo.rate_hz;
         wp.format = wbo.format;
@@ -506,14 +507,14 @@ int main(int argc, char* const argv[])
 
     if(wideband)
     {
-        // one push per hop on stdin: 5184 x D wideband samples, then 2592 x D
+        // one push per hop on stdin: 5184 x P/Q wideband samples, then 2592 x P/Q (Q divides 2592)
         const size_t wb_sample = static_cast<size_t>(msk144wb::sample_bytes(wbo.format));
-        const size_t Dw = static_cast<size_t>(wbo.rate_hz / msk144wb::kOutRate);
+        const msk144wb::RateRatio rr = msk144wb::rate_ratio(wbo.rate_hz);
         std::vector<unsigned char> block;
         bool first_block = true;
         while(!g_stop_requested.load(std::memory_order_relaxed))
         {
-            block.resize((first_block ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES) * Dw * wb_sample);
+            block.resize((first_block ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES) / static_cast<size_t>(rr.Q) * static_cast<size_t>(rr.P) * wb_sample);
             const size_t got = read_stdin(block.data(), block.size());
             if(g_stop_requested.load(std::memory_order_relaxed)) break;
             if(got != block.size())

@@ -99,7 +99,7 @@ public:
     // window afterwards).  Blocks while two blocks are already queued (back-pressure into the reader).  false once the loop failed.
     bool feed(const unsigned char* data, size_t bytes_per_stream);
     void feed_end();
-    // --wideband-rate: one push of raw wideband samples (5184 x D the first time, 2592 x D afterwards)
+    // --wideband-rate: one push of raw wideband samples (5184 x P/Q the first time, 2592 x P/Q afterwards; P/Q = D for an integer rate)
     bool feed_raw(const unsigned char* data, size_t bytes);
     // clipped I/Q components of the channeliser output over the run, and all components written (valid after join())
     long long wideband_clipped() const { return wb_clipped_; }

@@ -8,6 +8,7 @@ float64 where the device computes in f32.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Iterable, Optional, Sequence, Tuple
 
@@ -35,6 +36,8 @@ def _host_lib():
         L = C.CDLL(HOST_LIB)
         L.msk144host_wideband_taps.argtypes = [C.c_int, C.c_int, C.c_void_p]
         L.msk144host_wideband_taps.restype = C.c_int
+        L.msk144host_wideband_taps_rate.argtypes = [C.c_int64, C.c_int, C.c_void_p]
+        L.msk144host_wideband_taps_rate.restype = C.c_int
         _host = L
     return _host
 
@@ -47,6 +50,24 @@ def default_taps(D: int, K: int = 16) -> np.ndarray:
         raise ValueError(f"no default filter for D={D}, K={K} (D 2..512, K 1..64)")
     h = np.empty(n, dtype=np.float64)
     L.msk144host_wideband_taps(int(D), int(K), h.ctypes.data_as(C.c_void_p))
+    return h
+
+
+def rate_ratio(rate_hz: int) -> Tuple[int, int]:
+    """Fs / 12000 = P/Q in lowest terms; Q = 1 for an integer decimation D = P."""
+    g = math.gcd(int(rate_hz), OUT_RATE)
+    return int(rate_hz) // g, OUT_RATE // g
+
+
+def default_taps_for_rate(rate_hz: int, K: int = 16) -> np.ndarray:
+    """The default prototype for any rate Fs = 12000 P/Q: K*P taps at 12000 P Hz summing to Q (each polyphase branch about unit DC
+    gain); for Q = 1 exactly default_taps(D, K)."""
+    L = _host_lib()
+    n = L.msk144host_wideband_taps_rate(int(rate_hz), int(K), None)
+    if n < 0:
+        raise ValueError(f"no default filter for rate {rate_hz} Hz, K={K} (a multiple of 125 Hz in 24000..6144000, K 1..64)")
+    h = np.empty(n, dtype=np.float64)
+    L.msk144host_wideband_taps_rate(int(rate_hz), int(K), h.ctypes.data_as(C.c_void_p))
     return h
 
 
@@ -104,27 +125,48 @@ def quantise(y: np.ndarray, gain: float = 100.0) -> Tuple[np.ndarray, int]:
 
 
 class Channeliser:
-    """The contract, push by push: keeps the last L-1 input samples and the output index m like the device does."""
+    """The contract, push by push: keeps the history input samples and the output index m like the device does.
+
+    Fs = D x 12000 (Q = 1) runs the integer formula; any other rate Fs = 12000 P/Q its polyphase form, branch by branch (outputs
+    m = mr + Q a read x[n0 + a P - k] with the taps h[r + kQ])."""
 
     def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0):
-        if rate_hz % OUT_RATE:
-            raise ValueError("rate must be a multiple of 12000 Hz")
-        self.D = rate_hz // OUT_RATE
+        if rate_hz <= 0 or rate_hz % 125:
+            raise ValueError("rate must be a positive multiple of 125 Hz")
+        self.P, self.Q = rate_ratio(rate_hz)
         self.rate = int(rate_hz)
         self.offsets = np.asarray(offsets_hz, dtype=np.int64)
-        self.taps = default_taps(self.D, K) if taps is None else np.asarray(taps, dtype=np.float64)
+        if self.Q == 1:
+            self.D = self.P
+            self.taps = default_taps(self.D, K) if taps is None else np.asarray(taps, dtype=np.float64)
+        else:
+            self.taps = default_taps_for_rate(rate_hz, K) if taps is None else np.asarray(taps, dtype=np.float64)
         self.L = len(self.taps)
         self.gain = gain
-        self.G = tap_matrix(rate_hz, self.offsets, self.taps)
+        if self.Q == 1:
+            self.G = tap_matrix(rate_hz, self.offsets, self.taps)
+        else:
+            # branch taps by output residue mr: (r, n0, G_r [channel][K_r])
+            self.branches = []
+            for mr in range(self.Q):
+                r, n0 = mr * self.P % self.Q, mr * self.P // self.Q
+                self.branches.append((r, n0, tap_matrix(rate_hz, self.offsets, self.taps[r::self.Q])))
         self.reset()
 
+    @property
+    def n_hist(self) -> int:
+        """Input samples kept between pushes: ceil(L/Q) - 1 (L - 1 for Q = 1)."""
+        return -(-self.L // self.Q) - 1
+
     def reset(self):
-        self.hist = np.zeros(self.L - 1, dtype=np.complex128)
+        self.hist = np.zeros(self.n_hist, dtype=np.complex128)
         self.m = 0
 
     def filter(self, x: np.ndarray) -> np.ndarray:
-        """complex y [channel][M] of the next len(x)/D output samples (history and m advance)."""
+        """complex y [channel][M] of the next len(x) Q/P output samples (history and m advance)."""
         x = np.asarray(x, dtype=np.complex128)
+        if self.Q > 1:
+            return self._filter_rational(x)
         D, L = self.D, self.L
         if len(x) % D:
             raise ValueError("a push carries a whole number of output samples")
@@ -139,6 +181,31 @@ class Channeliser:
             y[:, m0:m0 + len(ms)] = (X @ GT).T
         y *= output_rotation(self.offsets, self.m + np.arange(M))
         self.hist = xp[len(xp) - (L - 1):].copy() if L > 1 else self.hist
+        self.m += M
+        return y
+
+    def _filter_rational(self, x: np.ndarray) -> np.ndarray:
+        P, Q, H = self.P, self.Q, self.n_hist
+        if len(x) % P:
+            raise ValueError("a push carries a whole number of output samples per branch (a multiple of Q outputs)")
+        M = len(x) * Q // P
+        A = M // Q
+        xp = np.concatenate([self.hist, x])
+        y = np.empty((len(self.offsets), M), dtype=np.complex128)
+        for mr, (r, n0, G) in enumerate(self.branches):
+            k = np.arange(G.shape[1])
+            GT = G.T
+            for a0 in range(0, A, 256):
+                a = np.arange(a0, min(A, a0 + 256))
+                idx = (H + n0 + a * P)[:, None] - k[None, :]
+                X = np.where(idx >= 0, xp[np.maximum(idx, 0)], 0)      # x[n0 + aP - k]; before the stream: 0
+                y[:, mr + Q * a] = (X @ GT).T
+        m = self.m + np.arange(M, dtype=np.int64)
+        n = (m * P) // Q                                                 # n_m, from the first sample of the stream
+        f = np.mod(self.offsets, self.rate)
+        ph = np.mod(f[:, None] * np.mod(n, self.rate)[None, :], self.rate).astype(np.float64) / self.rate
+        y *= np.exp(-2j * np.pi * ph)
+        self.hist = xp[len(xp) - H:].copy() if H > 0 else self.hist
         self.m += M
         return y
 
@@ -157,6 +224,20 @@ def naive_channel(x: np.ndarray, rate_hz: int, offset_hz: int, taps: np.ndarray)
     return np.convolve(mixed, taps)[:len(x)][::D]
 
 
+def naive_resampled_channel(x: np.ndarray, rate_hz: int, offset_hz: int, taps: np.ndarray) -> np.ndarray:
+    """Mix by e^{-j2pi f_c n/Fs}, upsample by Q (zero-stuff), filter with h at Q Fs, keep every P-th sample:
+    y[m] = (h * u)[mP] with u[nQ] = x[n] e^{-j2pi f_c n/Fs} and zeros between.  The filter is evaluated only at the kept samples."""
+    P, Q = rate_ratio(rate_hz)
+    n = np.arange(len(x), dtype=np.int64)
+    mixed = x * np.exp(-2j * np.pi * np.mod(offset_hz * n, rate_hz).astype(np.float64) / rate_hz)
+    u = np.zeros(len(x) * Q, dtype=np.complex128)
+    u[::Q] = mixed
+    M = len(x) * Q // P
+    idx = (np.arange(M, dtype=np.int64) * P)[:, None] - np.arange(len(taps))[None, :]
+    U = np.where(idx >= 0, u[np.maximum(idx, 0)], 0)
+    return U @ taps
+
+
 # ---- scene synthesis ----
 
 def _upsample(bb: np.ndarray, D: int) -> np.ndarray:
@@ -170,13 +251,48 @@ def _upsample(bb: np.ndarray, D: int) -> np.ndarray:
     return np.fft.ifft(P) * D
 
 
+def _resample(bb: np.ndarray, N: int) -> np.ndarray:
+    """Band-limited resampling of a 12 kHz baseband to N samples (spectrum zero-padded from len(bb) to N bins)."""
+    n = len(bb)
+    S = np.fft.fft(bb)
+    R = np.zeros(N, dtype=np.complex128)
+    h = n // 2
+    R[:h] = S[:h]
+    R[-(n - h):] = S[h:]
+    return np.fft.ifft(R) * (N / n)
+
+
+def _synth_wideband_rational(n_out, rate_hz, pings, noise_sigma, rng, fmt):
+    P, Q = rate_ratio(rate_hz)
+    if n_out % Q:
+        raise ValueError(f"n_out must be a multiple of Q = {Q} at {rate_hz} Hz")
+    N = n_out * P // Q
+    x = rng.normal(0.0, noise_sigma, N) + 1j * rng.normal(0.0, noise_sigma, N) if noise_sigma > 0 else np.zeros(N, dtype=np.complex128)
+    ref = noise_sigma if noise_sigma > 0 else 1.0
+    n = np.arange(N)
+    for f_c, p in pings:
+        bb = synth._ping_baseband(p)
+        amp = np.sqrt(2.0 * ref ** 2 * (2500.0 / rate_hz) * 10.0 ** (p.snr_db / 10.0))
+        full = np.zeros(n_out, dtype=np.complex128)
+        m1 = min(n_out, p.start + len(bb))
+        if m1 <= p.start:
+            continue
+        full[p.start:m1] = bb[:m1 - p.start]
+        carrier = np.exp(1j * (2 * np.pi * (f_c + p.freq_hz) * n / rate_hz + p.phase))
+        x += amp * _resample(full, N) * carrier
+    return write_samples(x, fmt)
+
+
 def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Ping]], noise_sigma: float, rng: np.random.Generator,
                    fmt: str = "cu8") -> np.ndarray:
-    """Raw interleaved components of a wideband scene n_out output samples long (n_out * D wideband samples).
+    """Raw interleaved components of a wideband scene n_out output samples long (n_out * P/Q wideband samples; n_out * D for an
+    integer rate, otherwise n_out must be a multiple of Q and each ping is FFT-resampled over the whole scene).
 
     pings: (channel offset f_c in Hz, synth.Ping) pairs; the Ping's start is in 12 kHz samples and its freq_hz is the frequency
     inside the channel, so the carrier lands at f_c + freq_hz.  noise_sigma: per rail, in full-scale units (1 = the format's full
     scale).  SNR in 2500 Hz as in synth.synth_iq: 10log10(A^2 / (2 sigma^2 2500 / Fs))."""
+    if rate_ratio(rate_hz)[1] > 1:
+        return _synth_wideband_rational(n_out, rate_hz, pings, noise_sigma, rng, fmt)
     D = rate_hz // OUT_RATE
     N = n_out * D
     x = rng.normal(0.0, noise_sigma, N) + 1j * rng.normal(0.0, noise_sigma, N) if noise_sigma > 0 else np.zeros(N, dtype=np.complex128)
@@ -198,3 +314,9 @@ def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Pi
 def push_sizes(n_pushes: int, D: int):
     """Raw component counts of a first push followed by n_pushes-1 later ones."""
     return [2 * FIRST_OUT * D] + [2 * HOP_OUT * D] * (n_pushes - 1)
+
+
+def push_sizes_for_rate(n_pushes: int, rate_hz: int):
+    """push_sizes for any rate: 2 x 5184 P/Q components, then 2 x 2592 P/Q."""
+    P, Q = rate_ratio(rate_hz)
+    return [2 * FIRST_OUT * P // Q] + [2 * HOP_OUT * P // Q] * (n_pushes - 1)

@@ -1,19 +1,22 @@
 """Wideband channeliser cost per push (msk144_push_wideband), measured with the library's HIP-event stage times.
 
-For every (channels, D) the handle is pushed `--pushes` later pushes of random cu8 samples.  In wideband mode the front-end stage
+For every (channels, rate) the handle is pushed `--pushes` later pushes of random cu8 samples.  In wideband mode the front-end stage
 time covers the channeliser and the IQ front end; the same handle is then fed the same number of plain msk144_push_hops calls,
-whose front-end time is the IQ front end alone, and the difference is the channeliser.  FLOP count: channels x 2592 x K*D x 8.
-One JSON line per configuration on stdout.
+whose front-end time is the IQ front end alone, and the difference is the channeliser.  FLOP count: channels x 2592 x K x
+(Fs/12000) x 8 (= channels x 2592 x K*D x 8 at Fs = D x 12000).  One JSON line per configuration on stdout.
 
-Then one msk144hipdecoder run over a pre-written 1.92 Msps cu8 file (1024 channels, D = 160, the program's default decode
-configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592 samples at 12 kHz).
+Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --program-rate, default 1.92 Msps, the program's
+default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
+samples at 12 kHz).
 
-    python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--pushes 20] [--program-hops 40]
+    python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
+                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000]
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import re
 import subprocess
@@ -30,9 +33,11 @@ from msk144cudecoder_amd import hipdecoder  # noqa: E402
 FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
 
-def measure(C: int, D: int, pushes: int, K: int = 16) -> dict:
+def measure(C: int, rate: int, pushes: int, K: int = 16) -> dict:
+    D = rate // 12000
     rng = np.random.default_rng(C + D)
-    rate = D * 12000
+    g = math.gcd(rate, 12000)
+    P, Q = rate // g, 12000 // g
     lim = rate // 2 - 6000
     offsets = np.linspace(-lim, lim, C).astype(np.int32)
     with hipdecoder.HipDecoder(center=0.0, width=0.0, step=1.0, depth=1, read_mode=2, channels=C) as d:
@@ -55,23 +60,25 @@ def measure(C: int, D: int, pushes: int, K: int = 16) -> dict:
             d.push_hops(i % 2, C)
         plain = d.stage_times(reset=True)
     ms = wide["frontend"][0] - plain["frontend"][0]
-    flop = C * 2592 * K * D * 8
-    return dict(channels=C, D=D, K=K, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
+    flop = C * 2592 * K * P * 8 // Q
+    ratio = dict(D=D) if Q == 1 else dict(rate_hz=rate, P=P, Q=Q)
+    return dict(channels=C, **ratio, K=K, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
                 channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
                 tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
                 fraction_of_fp32_peak=round(flop / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 3) if ms > 0 else None,
-                target_ms=2.0 if (C, D) == (1024, 160) else None)
+                target_ms=2.0 if C == 1024 and rate in (1920000, 2048000, 2500000) else None)
 
 
-def program_run(hops: int, C: int = 1024, D: int = 160) -> dict:
+def program_run(hops: int, C: int = 1024, rate: int = 1920000) -> dict:
     """Wall time of one msk144hipdecoder run over a file of 1 first + (hops - 1) later pushes of cu8 noise."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "msk144cudecoder_amd", "msk144hipdecoder")
-    rate = D * 12000
+    g = math.gcd(rate, 12000)
+    P, Q = rate // g, 12000 // g
     lim = rate // 2 - 6000
     offsets = np.linspace(-lim, lim, C).astype(np.int64)
     rng = np.random.default_rng(5)
-    n = 2 * (5184 + (hops - 1) * 2592) * D
+    n = 2 * (5184 + (hops - 1) * 2592) * P // Q
     with tempfile.NamedTemporaryFile(suffix=".cu8") as f:
         f.write(np.clip(np.rint(127.5 + 6.0 * rng.standard_normal(n)), 0, 255).astype(np.uint8).tobytes())
         f.flush()
@@ -85,22 +92,26 @@ def program_run(hops: int, C: int = 1024, D: int = 160) -> dict:
     err = p.stderr.decode()
     m = re.search(r"msk144hipdecoder: (\d+) batches", err)
     batches = int(m.group(1)) if m else None
-    return dict(program="msk144hipdecoder", channels=C, D=D, hops=batches, wall_s=round(wall, 3), hops_per_s=round(batches / wall, 2) if batches else None,
+    ratio = dict(D=P) if Q == 1 else dict(rate_hz=rate, P=P, Q=Q)
+    return dict(program="msk144hipdecoder", channels=C, **ratio, hops=batches, wall_s=round(wall, 3), hops_per_s=round(batches / wall, 2) if batches else None,
                 realtime_hops_per_s=4.63, note="wall time of the whole process, handle creation and file reading included")
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--channels", default="256,1024,4096")
-    ap.add_argument("--decimations", default="80,160,200")
+    ap.add_argument("--decimations", default="80,160,200", help="integer rates D x 12000; empty: none")
+    ap.add_argument("--rates", default="", help="any further rates in Hz (multiples of 125, e.g. 2048000,2500000,96125)")
     ap.add_argument("--pushes", type=int, default=20)
     ap.add_argument("--program-hops", type=int, default=40, help="0: skip the program run")
+    ap.add_argument("--program-rate", type=int, default=1920000)
     a = ap.parse_args()
+    rates = [int(v) * 12000 for v in a.decimations.split(",") if v] + [int(v) for v in a.rates.split(",") if v]
     for C in [int(v) for v in a.channels.split(",")]:
-        for D in [int(v) for v in a.decimations.split(",")]:
-            print(json.dumps(measure(C, D, a.pushes)), flush=True)
+        for rate in rates:
+            print(json.dumps(measure(C, rate, a.pushes)), flush=True)
     if a.program_hops:
-        print(json.dumps(program_run(a.program_hops)), flush=True)
+        print(json.dumps(program_run(a.program_hops, rate=a.program_rate)), flush=True)
 
 
 if __name__ == "__main__":
