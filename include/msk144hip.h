@@ -314,6 +314,7 @@ int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz);
  *                 which is the formula above for Q = 1, as (f_c m D) mod (12000 D) = D ((f_c m) mod 12000); phases in 64-bit integers.
  *                 I and Q are q = clamp(rint(128 . gain . y), -128, 127) each (default gain 100, the csdr gain_ff stage); a
  *                 component whose rounded value lies outside [-128, 127] counts as clipped.  f32 arithmetic on the device.
+ *                 0 < gain <= 1e36, so that 128 . gain is finite in f32 (an infinite scale would turn an exact 0 into NaN).
  *   Hops:         a first push carries 5184 x P/Q wideband samples (5184 output samples per channel), every later push
  *                 2592 x P/Q (2592); whole numbers, as Q divides 2592.  The filter history (the last ceil(L/Q) - 1 input samples, L - 1
  *                 for Q = 1: what the longest branch needs) and m stay on the device between pushes; a first push restarts the stream
@@ -337,7 +338,7 @@ typedef struct msk144_wideband_params
     int64_t rate_hz;          /* Fs = 12000 x P/Q (D x 12000 for Q = 1) */
     int32_t format;           /* MSK144_WB_* */
     int32_t taps_per_phase;   /* K */
-    float gain;               /* output gain before int8 (default 100) */
+    float gain;               /* output gain before int8 (default 100), 0 < gain <= 1e36 */
     int32_t num_taps;         /* = K x P (K x D for Q = 1) */
     const double* taps;       /* h[0 .. num_taps) */
     const int32_t* offsets_hz;/* f_c of channel 0 .. num_offsets-1 */

@@ -22,6 +22,7 @@ constexpr int64_t kMaxRateHz = static_cast<int64_t>(kMaxDecimation) * 12000;
 constexpr int kMaxTapsPerPhase = 64;   // K; L = K*D taps
 constexpr int kDefaultTapsPerPhase = 16;
 constexpr float kDefaultGain = 100.0f; // the `csdr gain_ff 100` stage of a CPU decimation chain
+constexpr float kMaxGain = 1e36f;      // the device scales by 128 x gain in f32: finite up to about 2.66e38 / 128
 constexpr int kGuardHz = 6000;         // |f_c| <= Fs/2 - 6000
 constexpr double kPassHz = 4000.0;     // design band edges of the default filter
 constexpr double kStopHz = 8000.0;
@@ -106,7 +107,7 @@ inline std::string check_config(int64_t rate_hz, int format, int K, float gain, 
     if(rate_hz < kMinRateHz || rate_hz > kMaxRateHz) return "wideband rate must be D x 12000 Hz with 2 <= D <= 512 (D = P/Q may be a fraction: 24000..6144000 Hz)";
     if(format != kCu8 && format != kCs8 && format != kCs16) return "wideband format must be cu8, cs8 or cs16";
     if(K < 1 || K > kMaxTapsPerPhase) return "taps per phase must be 1..64";
-    if(!(gain > 0.0f) || !std::isfinite(gain)) return "wideband gain must be a positive finite number";
+    if(!(gain > 0.0f) || !std::isfinite(gain) || gain > kMaxGain) return "wideband gain must be a positive finite number no larger than 1e36";
     if(count < 1 || !offsets) return "at least one channel offset is needed";
     const int64_t lim = rate_hz / 2 - kGuardHz;
     for(int i = 0; i < count; i++)

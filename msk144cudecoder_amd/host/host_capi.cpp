@@ -32,7 +32,20 @@ int msk144host_wideband_taps_rate(int64_t rate_hz, int K, double* out)
     return static_cast<int>(h.size());
 }
 
-void* msk144host_table_new() { return new CallHashTable(); }
+// The contract's configuration rules (csrc/wideband.h check_config), the ones msk144_set_wideband and msk144hipdecoder apply:
+// returns 0 when valid, else -1 with the refusal text in why (NUL-terminated, at most why_len bytes).
+int msk144host_wideband_check(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count, char* why, int why_len)
+{
+    const std::string s = msk144wb::check_config(rate_hz, format, K, gain, offsets, count);
+    if(why && why_len > 0)
+    {
+        std::strncpy(why, s.c_str(), static_cast<size_t>(why_len) - 1);
+        why[why_len - 1] = 0;
+    }
+    return s.empty() ? 0 : -1;
+}
+
+void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }
 unsigned msk144host_hash(const char* call, int bits) { return CallHashTable::hash(call, bits); }

@@ -38,6 +38,8 @@ def _host_lib():
         L.msk144host_wideband_taps.restype = C.c_int
         L.msk144host_wideband_taps_rate.argtypes = [C.c_int64, C.c_int, C.c_void_p]
         L.msk144host_wideband_taps_rate.restype = C.c_int
+        L.msk144host_wideband_check.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+        L.msk144host_wideband_check.restype = C.c_int
         _host = L
     return _host
 
@@ -69,6 +71,15 @@ def default_taps_for_rate(rate_hz: int, K: int = 16) -> np.ndarray:
     h = np.empty(n, dtype=np.float64)
     L.msk144host_wideband_taps_rate(int(rate_hz), int(K), h.ctypes.data_as(C.c_void_p))
     return h
+
+
+def check_config(rate_hz: int, fmt: str, K: int, gain: float, offsets_hz: Sequence[int]) -> str:
+    """The contract's configuration rules as libmsk144host.so applies them (csrc/wideband.h check_config, shared with the library
+    and the program): '' when valid, else the refusal text."""
+    off = np.ascontiguousarray(offsets_hz, dtype=np.int32)
+    why = C.create_string_buffer(256)
+    rc = _host_lib().msk144host_wideband_check(int(rate_hz), FORMATS.index(fmt), int(K), float(gain), off.ctypes.data_as(C.c_void_p), len(off), why, len(why))
+    return "" if rc == 0 else why.value.decode()
 
 
 # ---- sample formats ----

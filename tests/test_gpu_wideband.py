@@ -12,6 +12,7 @@ import pytest
 
 import pack77
 from msk144cudecoder_amd import synth
+import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
 
 pytestmark = pytest.mark.gpu
@@ -36,37 +37,45 @@ def _pushes(raw, D):
     return out
 
 
-def _hops_match_the_model(d, fmt, D):
-    """Configure d for (fmt, D) and check the int8 hops of five pushes against the float64 model."""
+def _hops_match_the_model(d, fmt, D, tally=None):
+    """Configure d for (fmt, D) and check the int8 hops of five pushes against the float64 model: within one LSB, and by the
+    near-tie rule."""
     rate = D * 12000
     offsets = _offsets_64(D)
     rng = np.random.default_rng(1000 + D + len(fmt))
     n_out = wb.FIRST_OUT + 4 * wb.HOP_OUT
     x = 0.03 * (rng.normal(size=n_out * D) + 1j * rng.normal(size=n_out * D))
     raw = wb.write_samples(x, fmt)
-    model = wb.Channeliser(rate, offsets)
+    ref = wc.Reference(rate, offsets)
     total = exact = 0
     d.set_wideband(rate, offsets, fmt)
     for i, part in enumerate(_pushes(raw, D)):
         first = i == 0
         d.push_wideband(i % 2, part, first=first)
-        q_ref, clip_ref = model.push(wb.read_samples(part, fmt), first=first)
+        y, T, N = ref.push(wb.read_samples(part, fmt), first=first)
+        q_ref, clip_ref = wb.quantise(y, ref.gain)
         got = np.stack([d.dump_wideband_hop(c) for c in range(len(offsets))])
         assert got.shape == q_ref.shape
         diff = np.abs(got.astype(np.int16) - q_ref.astype(np.int16))
         assert diff.max() <= 1, f"push {i}: |dq| up to {diff.max()}"
         total += diff.size
         exact += int(np.count_nonzero(diff == 0))
-        assert d.wideband_clip_count() == clip_ref, f"push {i}"
+        clip = d.wideband_clip_count()
+        assert clip == clip_ref, f"push {i}"
+        rep = wc.assert_hops(got, y, T, N, ref.gain, clip, what=f"{fmt} {rate} push {i}")     # the near-tie rule (tests/wideband_check.py)
+        if tally is not None:
+            tally.add(rep)
     d.synchronize()
     assert exact / total >= 0.999, f"{total - exact} of {total} components differ by one LSB"
 
 
 @pytest.mark.parametrize("D", [80, 160])
 @pytest.mark.parametrize("fmt", wb.FORMATS)
-def test_hops_match_the_model(hip, fmt, D):
+def test_hops_match_the_model(hip, parity_report, fmt, D):
+    tally = wc.Tally()
     with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, fmt, D)
+        _hops_match_the_model(d, fmt, D, tally=tally)
+    parity_report(f"wideband_model_{D * 12000}_{fmt}", tally.report())
 
 
 def test_reconfigured_handle_matches_the_model(hip):

@@ -16,6 +16,7 @@ import pytest
 
 import pack77
 from msk144cudecoder_amd import synth
+import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
 
 pytestmark = pytest.mark.gpu
@@ -40,8 +41,9 @@ def _split(raw, rate, n_pushes):
     return out
 
 
-def _hops_match_the_model(d, fmt, rate, n_pushes=5):
-    """Configure d for (fmt, rate) and check the int8 hops of n_pushes pushes against the float64 model."""
+def _hops_match_the_model(d, fmt, rate, n_pushes=5, tally=None):
+    """Configure d for (fmt, rate) and check the int8 hops of n_pushes pushes against the float64 model: within one LSB, and by
+    the near-tie rule."""
     P, Q = wb.rate_ratio(rate)
     offsets = _offsets_64(rate)
     rng = np.random.default_rng(1000 + rate + len(fmt))
@@ -49,35 +51,44 @@ def _hops_match_the_model(d, fmt, rate, n_pushes=5):
     sigma = 0.03 * np.sqrt(rate / 1920000)      # the in-channel level of the 1.92 Msps tests: clipping stays rare
     x = sigma * (rng.normal(size=n_in) + 1j * rng.normal(size=n_in))
     raw = wb.write_samples(x, fmt)
-    model = wb.Channeliser(rate, offsets)
+    ref = wc.Reference(rate, offsets)
     total = exact = 0
     d.set_wideband(rate, offsets, fmt)
     assert d.wideband_slot(0).size == 2 * wb.FIRST_OUT * P // Q
     for i, part in enumerate(_split(raw, rate, n_pushes)):
         first = i == 0
         d.push_wideband(i % 2, part, first=first)
-        q_ref, clip_ref = model.push(wb.read_samples(part, fmt), first=first)
+        y, T, N = ref.push(wb.read_samples(part, fmt), first=first)
+        q_ref, clip_ref = wb.quantise(y, ref.gain)
         got = np.stack([d.dump_wideband_hop(c) for c in range(len(offsets))])
         assert got.shape == q_ref.shape
         diff = np.abs(got.astype(np.int16) - q_ref.astype(np.int16))
         assert diff.max() <= 1, f"push {i}: |dq| up to {diff.max()}"
         total += diff.size
         exact += int(np.count_nonzero(diff == 0))
-        assert d.wideband_clip_count() == clip_ref, f"push {i}"
+        clip = d.wideband_clip_count()
+        assert clip == clip_ref, f"push {i}"
+        rep = wc.assert_hops(got, y, T, N, ref.gain, clip, what=f"{fmt} {rate} push {i}")     # the near-tie rule (tests/wideband_check.py)
+        if tally is not None:
+            tally.add(rep)
     d.synchronize()
     assert exact / total >= 0.999, f"{total - exact} of {total} components differ by one LSB"
 
 
 @pytest.mark.parametrize("fmt", wb.FORMATS)
-def test_hops_match_the_model_2p048_msps(hip, fmt):
+def test_hops_match_the_model_2p048_msps(hip, parity_report, fmt):
+    tally = wc.Tally()
     with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, fmt, RTL_RATE)
+        _hops_match_the_model(d, fmt, RTL_RATE, tally=tally)
+    parity_report(f"wideband_model_{RTL_RATE}_{fmt}", tally.report())
 
 
 @pytest.mark.parametrize("rate, n_pushes", [(250000, 5), (96125, 5), (6142000, 3)])
-def test_hops_match_the_model_other_rates(hip, rate, n_pushes):
+def test_hops_match_the_model_other_rates(hip, parity_report, rate, n_pushes):
+    tally = wc.Tally()
     with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, "cs16", rate, n_pushes)
+        _hops_match_the_model(d, "cs16", rate, n_pushes, tally=tally)
+    parity_report(f"wideband_model_{rate}_cs16", tally.report())
 
 
 def test_reconfigured_integer_rational_integer(hip):

@@ -54,6 +54,7 @@ def _run(exe, args, data=b"", timeout=60):
     (["--wideband-rate=1920000", "--channel-offsets=0", "--wideband-format=cu16"], "bad value for --wideband-format"),
     (["--wideband-rate=1920000", "--channel-offsets=0", "--taps-per-phase=65"], "bad value for --taps-per-phase"),
     (["--wideband-rate=1920000", "--channel-offsets=0", "--wideband-gain=-1"], "gain must be a positive"),
+    (["--wideband-rate=1920000", "--channel-offsets=0", "--wideband-gain=3e38"], "gain must be a positive finite number no larger than 1e36"),
 ])
 def test_bad_combinations_exit_2(exe, args, message):
     r = _run(exe, args)
