@@ -2,11 +2,16 @@
 """Headline benchmark: candidate decodes/s (front end + scan + softbits + index + LDPC + collect) at
 --search-width=500 --search-step=1 --scan-depth=6 --nbadsync-threshold=3.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" = one decode window (5184 samples) of every channel of the batch: BASELINE.json configs[2],
 1024 synthetic 12 ksps audio channels per MI355X (F=501 x D=6 x 8 = 24 048 candidates per window,
 24.6 M candidates per step and GPU).  Inputs are int16 windows already resident in HBM.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line.  `--full` adds everything else the line can carry: `cpu_baseline` (timed first), the `sustained`
+leg after the timed region, and the short legs after it (`value_every_slot_decoded`, `value_incl_h2d`,
+`frontend_method1`, `configs4_iq`).  None of them changes the timed steps or what `--dump-outputs` writes.
 
 N > 1: `python bench.py --gpus N` starts the N ranks ITSELF - the parent process never imports torch.cuda
 or touches HIP; it runs `python -m torch.distributed.run --nproc-per-node N bench.py ... --worker` as a
@@ -459,17 +464,21 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--channels", type=int, default=CHANNELS_PER_GPU, help="channels per GPU (default: the BASELINE config)")
     ap.add_argument("--llr-block", type=int, default=0, help="channels per softbits->index->LDPC block (0 = library default; = channels: retain every LLR row)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, time the CPU baseline, the sustained leg and the extra legs (a plain run does none of them; the options "
+                         "below tune a --full run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="time budget of the CPU baseline's bounded sample")
     ap.add_argument("--force-cpu-baseline", action="store_true",
-                    help="TEST HOOK: time the CPU baseline although --backend-module replaces the GPU backend (rehearsal of the N-rank launch on the CPU)")
-    ap.add_argument("--sustain-seconds", type=float, default=20.0,
+                    help="TEST HOOK: time the CPU baseline, even without --full and although --backend-module replaces the GPU backend (rehearsal of the "
+                         "N-rank launch on the CPU)")
+    ap.add_argument("--sustain-seconds", type=float, default=None,
                     help="after the K timed steps, keep running the same step for about this long (untimed inputs unchanged) and report the step time of its "
-                         "first / middle / last 50 steps and the shader clock: `value` stays the K-step figure (0 = skip)")
+                         "first / middle / last 50 steps and the shader clock: `value` stays the K-step figure (default: 20 with --full, else 0 = skip)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the short legs appended after the timed region: value_every_slot_decoded (the same step with the copy hand-over off; every rank "
-                         "runs it) and, single-GPU runs only, value_incl_h2d (pinned host windows), frontend_method1 (FFT front end beside the FIR one) and "
-                         "configs4_iq (BASELINE configs[4])")
+                    help="--full without the short legs appended after the timed region: value_every_slot_decoded (the same step with the copy hand-over off; "
+                         "every rank runs it) and, single-GPU runs only, value_incl_h2d (pinned host windows), frontend_method1 (FFT front end beside the FIR "
+                         "one) and configs4_iq (BASELINE configs[4])")
     ap.add_argument("--every-slot", action="store_true",
                     help="run the TIMED region with the copy hand-over off (msk144_set_copy_handover(h, 0)): `value` is then slots fully evaluated per second, as the "
                          "reference computes them; the value_every_slot_decoded leg is dropped (it would repeat the timed region)")
@@ -479,7 +488,13 @@ def parse_args(argv=None):
     ap.add_argument("--launcher", action="store_true", help="go through the N-rank launcher even for --gpus 1 (exercises the RCCL gather path)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend-module", default=None, help="TEST HOOK: module providing Backend (e.g. tests/stub_backend.py on gloo); the line is then labelled as such")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # From here on the three switches say what this run does beyond the headline.
+    args.no_cpu_baseline = args.no_cpu_baseline or not (args.full or args.force_cpu_baseline)
+    args.no_extra_legs = args.no_extra_legs or not args.full
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 20.0 if args.full else 0.0
+    return args
 
 
 def launch_ranks(args, argv) -> int:

@@ -87,6 +87,21 @@ def test_gpus1_through_launcher_matches_contract():
     assert out["n_gpus"] == 1 and out["gather"]["records_last_step"] == 5
 
 
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """A plain `bench.py --steps K --warmup W` times the headline alone; --full adds the CPU baseline, the 20 s sustained leg and the
+    extra legs, and the options that tune a --full run still take them away one by one."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(["--steps", "3", "--warmup", "1"])
+    assert plain.no_cpu_baseline and plain.no_extra_legs and plain.sustain_seconds == 0.0
+    full = bench.parse_args(["--steps", "3", "--warmup", "1", "--full"])
+    assert not full.no_cpu_baseline and not full.no_extra_legs and full.sustain_seconds == 20.0
+    trimmed = bench.parse_args(["--full", "--no-cpu-baseline", "--no-extra-legs", "--sustain-seconds", "0"])
+    assert trimmed.no_cpu_baseline and trimmed.no_extra_legs and trimmed.sustain_seconds == 0.0
+    assert not bench.parse_args(["--force-cpu-baseline"]).no_cpu_baseline
+    assert bench.parse_args(["--sustain-seconds", "0.2"]).sustain_seconds == 0.2
+
+
 def test_world_size_mismatch_is_refused():
     """Under torch.distributed.run with WORLD_SIZE != --gpus the worker must refuse rather than print a mislabelled line."""
     p = _run(["--gpus", "2"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29577"})

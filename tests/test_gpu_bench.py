@@ -21,8 +21,8 @@ def _bench(extra):
 
 
 def test_launcher_line_matches_the_plain_run():
-    plain = _bench(["--no-cpu-baseline", "--sustain-seconds", "0"])       # without the sustained leg both runs end on the same window
-    dist = _bench(["--gpus", "1", "--launcher", "--no-cpu-baseline", "--sustain-seconds", "0"])
+    plain = _bench(["--full", "--no-cpu-baseline", "--sustain-seconds", "0"])       # without the sustained leg both runs end on the same window
+    dist = _bench(["--gpus", "1", "--launcher", "--full", "--no-cpu-baseline", "--sustain-seconds", "0"])
     assert plain["n_gpus"] == dist["n_gpus"] == 1
     assert plain["config"]["launch"] == "single process" and dist["config"]["launch"] == "torch.distributed.run"
     g = dist["gather"]
@@ -43,7 +43,7 @@ def test_launcher_line_matches_the_plain_run():
 
 def test_distributed_line_carries_the_cpu_baseline():
     """What a driver's `bench.py --gpus N` prints must be gradeable: roofline, cpu_baseline and gather in one line."""
-    dist = _bench(["--gpus", "1", "--launcher"])
+    dist = _bench(["--gpus", "1", "--launcher", "--full"])
     cb = dist["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "-march=native" in cb["flags"]
     assert "gather" in dist and "roofline" in dist
@@ -58,6 +58,16 @@ def test_distributed_line_carries_the_cpu_baseline():
     assert abs(su["drift_last_vs_first"]) < 0.05
     assert all(1200.0 < su["clock_mhz"][k] < 2700.0 for k in ("first", "mid", "last")), su["clock_mhz"]
     assert dist["gather"]["records_last_step"] == dist["decodes_last_step"]
+
+
+def test_plain_run_is_the_headline_alone():
+    """`bench.py --steps K --warmup W` and nothing else: the timed steps and the line, none of the legs that --full adds."""
+    line = _bench([])
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "candidates/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["config"]["launch"] == "single process" and line["roofline"]["kernel"] == "ldpc_kernel"
+    for key in ("cpu_baseline", "sustained", "value_every_slot_decoded", "value_incl_h2d", "frontend_method1", "configs4_iq"):
+        assert key not in line, key
 
 
 def test_every_slot_flag_times_the_region_with_the_hand_over_off():

@@ -9,12 +9,12 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out
 BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --sustain-seconds 0 --no-extra-legs"
 if [ "${2:-}" != "hostonly" ]; then
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
-python3 bench.py --gpus 1 --launcher --no-cpu-baseline > $OUT/${TAG}_bench_launcher.json 2> $OUT/${TAG}_bench_launcher.err; echo "launcher rc=$?"
-# the default command (timed region + sustained leg + the three extra legs: value_incl_h2d, frontend_method1, configs4_iq) under the kernel trace:
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
+python3 bench.py --gpus 1 --launcher --full --no-cpu-baseline > $OUT/${TAG}_bench_launcher.json 2> $OUT/${TAG}_bench_launcher.err; echo "launcher rc=$?"
+# the --full command (timed region + sustained leg + the three extra legs: value_incl_h2d, frontend_method1, configs4_iq) under the kernel trace:
 # every kernel of every leg in one stats file; and the same without the extra legs, for the agreement of the dominant kernel's average
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 bench.py --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_stats.err; echo "stats rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats_main -o s --output-format csv -- python3 bench.py --no-cpu-baseline --no-extra-legs > $OUT/${TAG}_bench_main_under_rocprof.json 2> $OUT/${TAG}_stats_main.err; echo "stats main rc=$?"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_stats.err; echo "stats rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats_main -o s --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extra-legs > $OUT/${TAG}_bench_main_under_rocprof.json 2> $OUT/${TAG}_stats_main.err; echo "stats main rc=$?"
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/${TAG}_pmc -o fetch --output-format csv -- $BENCH > /dev/null 2>> $OUT/${TAG}_pmc.err; echo "fetch rc=$?"
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/${TAG}_pmc -o write --output-format csv -- $BENCH > /dev/null 2>> $OUT/${TAG}_pmc.err; echo "write rc=$?"
 timeout -k 10 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS --kernel-trace -d $OUT/${TAG}_pmc -o sq1 --output-format csv -- $BENCH > /dev/null 2>> $OUT/${TAG}_pmc.err; echo "sq1 rc=$?"
