@@ -325,7 +325,27 @@ int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz);
  *     msk144_push_wideband(h, s, first);            H2D + channeliser + hop ring + IQ front end on the handle's stream
  *     msk144_decode / msk144_fetch_async / msk144_fetch_wait   as after msk144_push_hops (record channel = channel index)
  *
- * Stage times: in wideband mode MSK144_T_FRONTEND includes the channeliser, MSK144_T_H2D the wideband copy. */
+ * Above 6.144 Msps: a two-stage bank.  Fs a multiple of 8000 Hz with 6144000 < Fs <= 61440000.  Every rate up to 6144000 keeps the
+ * path, contract and results above.
+ *   Stage 1:      a 64-band, 2x oversampled analysis bank; for each band k some channel lies in, at rate Fs/32:
+ *                   s_k[n] = (-1)^(k n) . sum_{l<L1} h1[l] e^{+j2pi (k l mod 64)/64} x[32n - l]
+ *                 n from the first sample of the stream, x[n < 0] = 0, h1 real with L1 = 64 x K1 taps (1 <= K1 <= 16).  This is the
+ *                 Q = 1 formula above with D = 32, offset k Fs/64 and output rate Fs/32 in place of 12000 (the float64 model relies on
+ *                 it).  f32 on the device, kept there, never quantised.
+ *   Channels:     f_c (|f_c| <= Fs/2 - 6000 as above) lies in band k_c = floor((64 f_c + Fs/2) / Fs), in integers, so -32 <= k_c <= 32
+ *                 (band 32 is the stream of band -32), at the residual offset d_c = f_c - k_c Fs/64, an integer with
+ *                 |d_c| <= Fs/128 < Fs/64 - 6000.
+ *   Stage 2:      the contract above, unchanged, applied to s_{k_c} at the rate Fs/32 (a multiple of 250 from 192250 to 1920000, Q
+ *                 dividing 96) with offset d_c, the caller's taps h (taps_per_phase x P taps for Fs/32 = 12000 P/Q), the same gain,
+ *                 int8 quantiser and clip rule; output index m and hop sizes as above (a first push is 5184 Fs/12000 input samples,
+ *                 a later one 2592 Fs/12000, a whole number of 32-sample frames).  The history of both stages stays on the device;
+ *                 a first push restarts both.
+ *   Bank filter:  the default (msk144_set_wideband, or msk144_set_wideband_ex with bank_taps NULL) is K1 = 8, 512 taps, a
+ *                 Kaiser-windowed sinc summing to 1 (so the gain keeps its meaning): flat within 0.1 dB for |f| <= Fs/128 + 4 kHz, at
+ *                 least 60 dB down for |f| >= 3 Fs/128 - 8 kHz, the range the decimation by 32 folds onto a channel's 8 kHz stop edge;
+ *                 msk144host_wideband_bank_taps(rate, K1, out) in libmsk144host.so.
+ *
+ * Stage times: in wideband mode MSK144_T_FRONTEND includes the channeliser (and the bank), MSK144_T_H2D the wideband copy. */
 enum
 {
     MSK144_WB_CU8 = 0,
@@ -335,7 +355,7 @@ enum
 
 typedef struct msk144_wideband_params
 {
-    int64_t rate_hz;          /* Fs = 12000 x P/Q (D x 12000 for Q = 1) */
+    int64_t rate_hz;          /* Fs = 12000 x P/Q (D x 12000 for Q = 1), or a bank rate (the taps are then for Fs/32) */
     int32_t format;           /* MSK144_WB_* */
     int32_t taps_per_phase;   /* K */
     float gain;               /* output gain before int8 (default 100), 0 < gain <= 1e36 */
@@ -346,6 +366,10 @@ typedef struct msk144_wideband_params
 } msk144_wideband_params;
 
 int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* params);
+/* the general form: above 6144000 Hz bank_taps = h1[0 .. bank_num_taps), bank_num_taps = 64 x K1 with 1 <= K1 <= 16, or NULL (and
+ * 0) for the default bank; at or below 6144000 Hz bank_taps must be NULL.  msk144_set_wideband(h, p) is
+ * msk144_set_wideband_ex(h, p, NULL, 0). */
+int msk144_set_wideband_ex(msk144_handle* h, const msk144_wideband_params* params, const double* bank_taps, int32_t bank_num_taps);
 int msk144_wideband_slot(msk144_handle* h, int32_t slot, void** buf, size_t* bytes);
 /* MSK144_ESTATE for a later push (first = 0) before any first push */
 int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first);
@@ -353,6 +377,9 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first);
 int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out);
 /* clipped I and Q components of the last push, all channels */
 int msk144_wideband_clip_count(msk144_handle* h, int64_t* clipped);
+/* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
+ * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
+int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);
 
 #ifdef __cplusplus
 }

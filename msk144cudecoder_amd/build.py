@@ -27,6 +27,7 @@ SOURCES = [
     ("hopring.hip", []),
     ("ldpc.hip", []),
     ("channelise.hip", []),
+    ("bank.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]

@@ -21,7 +21,11 @@
 // n0 = floor(mr P/Q) and the taps h[r + kQ], r = mr P mod Q, k < K_r = ceil((L - r)/Q).  Each of the Q residues mr is a
 // decimate-by-P GEMM of its own, tiled as above (blockIdx.z = mr) with k = p + P q: the loop walks exactly the K_r taps of the
 // branch - phases p < s carry ceil(K_r/P) taps, the others one fewer - and the outputs land Q apart in the same staging.
+//
+// Rates above 6.144 Msps (format kSubbandFormat): both kernels run at the sub-band rate Fs/32 on the complex-f32 streams of the
+// analysis bank (bank.hip), each wave on the band of its 32 channel slots; see channelise_kernel.
 #include "msk144_kernels.h"
+#include "wideband_samples.h"
 
 namespace msk144
 {
@@ -40,33 +44,19 @@ constexpr int kMaxSpan = kTileSamples + kMaxK - 1;
 constexpr int kHalf = kWindowSamples / 2;  // 2592 samples per hop
 constexpr int kChannelRate = 12000;
 
-template<int FMT>
-__device__ inline float2 load_sample(const void* __restrict__ raw, int i)
-{
-    if(FMT == 0)
-    {
-        const uchar2 v = static_cast<const uchar2*>(raw)[i];
-        return make_float2((static_cast<float>(v.x) - 127.5f) * (1.0f / 128.0f), (static_cast<float>(v.y) - 127.5f) * (1.0f / 128.0f));
-    }
-    else if(FMT == 1)
-    {
-        const char2 v = static_cast<const char2*>(raw)[i];
-        return make_float2(static_cast<float>(v.x) * (1.0f / 128.0f), static_cast<float>(v.y) * (1.0f / 128.0f));
-    }
-    else
-    {
-        const short2 v = static_cast<const short2*>(raw)[i];
-        return make_float2(static_cast<float>(v.x) * (1.0f / 32768.0f), static_cast<float>(v.y) * (1.0f / 32768.0f));
-    }
-}
-
+// FMT 3 (the two-stage bank): raw holds one complex-f32 sub-band stream per occupied band, bands.stride apart, and channel slot c
+// (channels grouped by band, each band's group padded to whole waves) belongs to channel bands.slot_channel[c] (-1: padding).  Every
+// wave stages its own band's input in its own quarter of the LDS image (kPhaseChunk/4 phases at a time), so the slots of one tile
+// may lie in four different bands; the taps, branches and loop structure are the same for every band.
 template<int FMT>
 __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __restrict__ raw, const float2* __restrict__ G, const int32_t* __restrict__ fmod,
                                                               const float2* __restrict__ rot, int8_t* __restrict__ first_halves, int8_t* __restrict__ hops,
                                                               unsigned long long* __restrict__ clip_count, int channels, int D, int K, int M, int first,
-                                                              long long m_base, float scale)
+                                                              long long m_base, float scale, WidebandBands bands)
 {
     __shared__ float xs[2][kPhaseChunk][kMaxSpan];
+    constexpr bool kBank = FMT == kSubbandFormat;
+    constexpr int kChunk = kBank ? kPhaseChunk / 4 : kPhaseChunk;
 
     const int L = K * D;
     const int hist = L - 1;              // raw[0 .. hist) = the L-1 samples before this push
@@ -80,29 +70,49 @@ __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __rest
     const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
     const bool active = cb32 * 32 < channels;
     const float2* __restrict__ g = G + static_cast<size_t>(cb32) * L * 32 + j;
+    const int prow = kBank ? wave * kChunk : 0;  // the wave's first phase row of the LDS image
+    const void* src = raw;
+    if(kBank && active) src = static_cast<const float2*>(raw) + bands.stride * bands.wave_band[cb32];
 
     f32x16 acc_re0 = {}, acc_im0 = {}, acc_re1 = {}, acc_im1 = {};
 
-    for(int p0 = 0; p0 < D; p0 += kPhaseChunk)
+    for(int p0 = 0; p0 < D; p0 += kChunk)
     {
-        const int pc = min(kPhaseChunk, D - p0);
+        const int pc = min(kChunk, D - p0);
         __syncthreads();
-        // xp[p][n] = x at buffer index (mt0 + n + 1)*D - p - 1 (output mt0 + n - (K-1), tap p); consecutive threads take
-        // consecutive phases, i.e. consecutive (descending) input samples
-        for(int e = threadIdx.x; e < pc * span; e += kThreads)
+        if(kBank)
         {
-            const int pl = e % pc;
-            const int n = e / pc;
-            const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
-            float2 v = make_float2(0.0f, 0.0f);
-            if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
-            xs[0][pl][n] = v.x;
-            xs[1][pl][n] = v.y;
+            // the image below, of the wave's own band, by the wave's own 64 lanes
+            for(int e = lane; active && e < pc * span; e += 64)
+            {
+                const int pl = e % pc;
+                const int n = e / pc;
+                const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
+                float2 v = make_float2(0.0f, 0.0f);
+                if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(src, i);
+                xs[0][prow + pl][n] = v.x;
+                xs[1][prow + pl][n] = v.y;
+            }
+        }
+        else
+        {
+            // xp[p][n] = x at buffer index (mt0 + n + 1)*D - p - 1 (output mt0 + n - (K-1), tap p); consecutive threads take
+            // consecutive phases, i.e. consecutive (descending) input samples
+            for(int e = threadIdx.x; e < pc * span; e += kThreads)
+            {
+                const int pl = e % pc;
+                const int n = e / pc;
+                const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
+                float2 v = make_float2(0.0f, 0.0f);
+                if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
+                xs[0][pl][n] = v.x;
+                xs[1][pl][n] = v.y;
+            }
         }
         __syncthreads();
         if(!active) continue;
         const float2* __restrict__ gp = g + static_cast<size_t>(p0) * K * 32;
-        const float* __restrict__ xrow = &xs[hsel][0][j + K - 1];
+        const float* __restrict__ xrow = &xs[hsel][prow][j + K - 1];
         const int T = pc * K;
         float2 gnext = gp[0];
         int pl = 0, q = 0;
@@ -147,6 +157,8 @@ __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __rest
         {
             const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
             if(c >= channels) continue;
+            const int ch = kBank ? bands.slot_channel[c] : c;  // the channel of slot c
+            if(ch < 0) continue;
             const float yr = s ? acc_re1[r] : acc_re0[r];
             const float yi = s ? acc_im1[r] : acc_im0[r];
             const int ph = (fmod[c] * mm) % kChannelRate;
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __rest
             char2 o;
             o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
             o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
-            reinterpret_cast<char2*>(dst)[static_cast<size_t>(c) * half + idx] = o;
+            reinterpret_cast<char2*>(dst)[static_cast<size_t>(ch) * half + idx] = o;
         }
     }
     for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
@@ -169,9 +181,12 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
                                                                        const WidebandBranch* __restrict__ branches, const int32_t* __restrict__ fmod,
                                                                        const float2* __restrict__ rot, int8_t* __restrict__ first_halves,
                                                                        int8_t* __restrict__ hops, unsigned long long* __restrict__ clip_count, int channels,
-                                                                       int P, int Q, int hist, int M, int first, long long m_base, float scale)
+                                                                       int P, int Q, int hist, int M, int first, long long m_base, float scale,
+                                                                       WidebandBands bands)
 {
     __shared__ float xs[2][kPhaseChunk][kMaxSpan];
+    constexpr bool kBank = FMT == kSubbandFormat;   // as in channelise_kernel
+    constexpr int kChunk = kBank ? kPhaseChunk / 4 : kPhaseChunk;
 
     const int mr = blockIdx.z;
     const WidebandBranch br = branches[mr];
@@ -191,30 +206,49 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
     const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
     const bool active = cb32 * 32 < channels;
     const float2* __restrict__ g = G + br.g_off + static_cast<size_t>(cb32) * Kr * 32 + j;
+    const int prow = kBank ? wave * kChunk : 0;
+    const void* src = raw;
+    if(kBank && active) src = static_cast<const float2*>(raw) + bands.stride * bands.wave_band[cb32];
 
     f32x16 acc_re0 = {}, acc_im0 = {}, acc_re1 = {}, acc_im1 = {};
 
-    for(int p0 = 0; p0 < phases; p0 += kPhaseChunk)
+    for(int p0 = 0; p0 < phases; p0 += kChunk)
     {
-        const int pc = min(kPhaseChunk, phases - p0);
+        const int pc = min(kChunk, phases - p0);
         __syncthreads();
-        // xp[p][n] = raw[base + n P - p]: output at0 + n - (Kq-1), tap p (+ P q for the q-th tap of the phase, read at n - q)
-        for(int e = threadIdx.x; e < pc * span; e += kThreads)
+        if(kBank)
         {
-            const int pl = e % pc;
-            const int n = e / pc;
-            const int i = base + n * P - (p0 + pl);
-            float2 v = make_float2(0.0f, 0.0f);
-            if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
-            xs[0][pl][n] = v.x;
-            xs[1][pl][n] = v.y;
+            for(int e = lane; active && e < pc * span; e += 64)
+            {
+                const int pl = e % pc;
+                const int n = e / pc;
+                const int i = base + n * P - (p0 + pl);
+                float2 v = make_float2(0.0f, 0.0f);
+                if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(src, i);
+                xs[0][prow + pl][n] = v.x;
+                xs[1][prow + pl][n] = v.y;
+            }
+        }
+        else
+        {
+            // xp[p][n] = raw[base + n P - p]: output at0 + n - (Kq-1), tap p (+ P q for the q-th tap of the phase, read at n - q)
+            for(int e = threadIdx.x; e < pc * span; e += kThreads)
+            {
+                const int pl = e % pc;
+                const int n = e / pc;
+                const int i = base + n * P - (p0 + pl);
+                float2 v = make_float2(0.0f, 0.0f);
+                if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
+                xs[0][pl][n] = v.x;
+                xs[1][pl][n] = v.y;
+            }
         }
         __syncthreads();
         if(!active) continue;
         const int t0 = p0 * Kq - max(0, p0 - s_full);
         const int T = (p0 + pc) * Kq - max(0, p0 + pc - s_full) - t0;
         const float2* __restrict__ gp = g + static_cast<size_t>(t0) * 32;
-        const float* __restrict__ xrow = &xs[hsel][0][j + Kq - 1];
+        const float* __restrict__ xrow = &xs[hsel][prow][j + Kq - 1];
         float2 gnext = gp[0];
         int pl = 0, q = 0;
         int kp = p0 < s_full ? Kq : Kq - 1;
@@ -260,6 +294,8 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
         {
             const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
             if(c >= channels) continue;
+            const int ch = kBank ? bands.slot_channel[c] : c;  // the channel of slot c
+            if(ch < 0) continue;
             const float yr = s ? acc_re1[r] : acc_re0[r];
             const float yi = s ? acc_im1[r] : acc_im0[r];
             const int ph = (fmod[c] * mm) % kChannelRate;
@@ -270,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
             char2 o;
             o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
             o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
-            reinterpret_cast<char2*>(dst)[static_cast<size_t>(c) * half + idx] = o;
+            reinterpret_cast<char2*>(dst)[static_cast<size_t>(ch) * half + idx] = o;
         }
     }
     for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
@@ -280,33 +316,40 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
 }  // namespace
 
 void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
-                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream)
+                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream,
+                       WidebandBands bands)
 {
     const dim3 grid((M + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels);
     const float scale = 128.0f * gain;
     if(format == 0)
-        hipLaunchKernelGGL(channelise_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+        hipLaunchKernelGGL(channelise_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
     else if(format == 1)
-        hipLaunchKernelGGL(channelise_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+        hipLaunchKernelGGL(channelise_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
+    else if(format == 2)
+        hipLaunchKernelGGL(channelise_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
     else
-        hipLaunchKernelGGL(channelise_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale);
+        hipLaunchKernelGGL(channelise_kernel<kSubbandFormat>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first,
+                           m_base, scale, bands);
 }
 
 void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
                                 int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
-                                long long m_base, float gain, hipStream_t stream)
+                                long long m_base, float gain, hipStream_t stream, WidebandBands bands)
 {
     const dim3 grid((M / Q + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels, Q);
     const float scale = 128.0f * gain;
     if(format == 0)
         hipLaunchKernelGGL(channelise_rational_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale);
+                           first, m_base, scale, bands);
     else if(format == 1)
         hipLaunchKernelGGL(channelise_rational_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale);
-    else
+                           first, m_base, scale, bands);
+    else if(format == 2)
         hipLaunchKernelGGL(channelise_rational_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale);
+                           first, m_base, scale, bands);
+    else
+        hipLaunchKernelGGL(channelise_rational_kernel<kSubbandFormat>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q,
+                           hist, M, first, m_base, scale, bands);
 }
 
 }  // namespace msk144

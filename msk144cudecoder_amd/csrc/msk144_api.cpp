@@ -130,6 +130,22 @@ struct msk144_handle
         int32_t* d_fmod = nullptr;
         float2* d_rot = nullptr;  // [12000]
         unsigned long long* d_clip = nullptr;
+        // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
+        int Pin = 0, Qin = 0, raw_hist = 0;
+        // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
+        bool bank = false;
+        int K1 = 0;
+        int slots = 0;                 // channel slots: each band's channels padded to whole waves of 32
+        std::vector<int> band_index;   // occupied band k mod 64 of sub-band stream j
+        long long stride = 0;          // float2 per sub-band stream: hist + 5184 P/Q frames
+        long long n_next = 0;          // bank frame index of the next push
+        int last_frames = 0;           // frames of the last push
+        float* d_h1 = nullptr;
+        int32_t* d_bands = nullptr;
+        float2* d_tw = nullptr;        // [64]
+        float2* d_sub = nullptr;       // [bands][stride]
+        int32_t* d_wave_band = nullptr;
+        int32_t* d_slot_channel = nullptr;
     } wb;
 
     std::string error;
@@ -1074,12 +1090,33 @@ int msk144_stage_times(msk144_handle* h, float* avg_ms, int32_t* samples, int32_
 
 int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
 {
+    return msk144_set_wideband_ex(h, wp, nullptr, 0);
+}
+
+int msk144_set_wideband_ex(msk144_handle* h, const msk144_wideband_params* wp, const double* bank_taps, int32_t bank_num_taps)
+{
     if(!h || !wp) return fail(h, MSK144_EINVAL, "null argument");
     if(h->params.read_mode != 2) return fail(h, MSK144_EINVAL, "wideband input needs an IQ handle (read_mode 2)");
     if(wp->num_offsets != h->params.channels) return fail(h, MSK144_EINVAL, "the number of channel offsets must equal the handle's channels");
     const std::string why = msk144wb::check_config(wp->rate_hz, wp->format, wp->taps_per_phase, wp->gain, wp->offsets_hz, wp->num_offsets);
     if(!why.empty()) return fail(h, MSK144_EINVAL, why);
-    const msk144wb::RateRatio rr = msk144wb::rate_ratio(wp->rate_hz);
+    const bool bank = msk144wb::is_bank_rate(wp->rate_hz);
+    if(!bank && (bank_taps || bank_num_taps)) return fail(h, MSK144_EINVAL, "bank taps are only taken above 6144000 Hz (two-stage bank)");
+    std::vector<double> h1;
+    if(bank)
+    {
+        if(!bank_taps) h1 = msk144wb::design_bank_taps(wp->rate_hz, msk144wb::kDefaultBankTapsPerBand);
+        else
+        {
+            if(bank_num_taps < msk144wb::kBankBands || bank_num_taps > msk144wb::kBankBands * msk144wb::kMaxBankTapsPerBand || bank_num_taps % msk144wb::kBankBands)
+                return fail(h, MSK144_EINVAL, "the bank filter needs 64 x K1 taps, 1 <= K1 <= 16");
+            h1.assign(bank_taps, bank_taps + bank_num_taps);
+            for(double v : h1)
+                if(!std::isfinite(v)) return fail(h, MSK144_EINVAL, "bank taps must be finite");
+        }
+    }
+    const int64_t rate2 = msk144wb::stage2_rate(wp->rate_hz);  // the channeliser's input rate
+    const msk144wb::RateRatio rr = msk144wb::rate_ratio(rate2), rin = msk144wb::rate_ratio(wp->rate_hz);
     const int P = rr.P, Q = rr.Q;
     const int K = wp->taps_per_phase;
     const int L = K * P;
@@ -1095,31 +1132,75 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
     wb_release(h);
     auto& w = h->wb;
     const int C = h->params.channels;
-    const int C32 = (C + 31) / 32;
+
+    // channel slots: without the bank slot c is channel c; with it, the channels of each occupied band (k mod 64, ascending) one
+    // after another, each band's group padded to whole waves, at the residual offset f_c - k Fs/64
+    std::vector<int32_t> slot_channel, wave_band;
+    std::vector<long long> slot_offset;
+    std::vector<int32_t> band_list;
+    if(!bank)
+        for(int c = 0; c < C; c++)
+        {
+            slot_channel.push_back(c);
+            slot_offset.push_back(wp->offsets_hz[c]);
+        }
+    else
+    {
+        std::vector<std::vector<int>> by_band(msk144wb::kBankBands);
+        for(int c = 0; c < C; c++)
+            by_band[static_cast<size_t>(msk144wb::bank_band(wp->rate_hz, wp->offsets_hz[c]) & (msk144wb::kBankBands - 1))].push_back(c);
+        for(int b = 0; b < msk144wb::kBankBands; b++)
+        {
+            const auto& chs = by_band[static_cast<size_t>(b)];
+            if(chs.empty()) continue;
+            const int j = static_cast<int>(band_list.size());
+            band_list.push_back(b);
+            const size_t n = (chs.size() + 31) / 32 * 32;
+            for(size_t i = 0; i < n; i++)
+            {
+                const int c = i < chs.size() ? chs[i] : -1;
+                slot_channel.push_back(c);
+                slot_offset.push_back(c < 0 ? 0 : msk144wb::bank_residual(wp->rate_hz, wp->offsets_hz[c]));
+                if(i % 32 == 0) wave_band.push_back(j);
+            }
+        }
+    }
+    const int S = static_cast<int>(slot_channel.size());
+    const int C32 = (S + 31) / 32;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(wp->format));
     const int hist = (L + Q - 1) / Q - 1;
-    w.slot_bytes = static_cast<size_t>(kWindowSamples) / Q * P * sb;
+    const int raw_hist = bank ? static_cast<int>(h1.size()) - 1 : hist;
+    const int NB = static_cast<int>(band_list.size());
+    const long long stride = bank ? hist + static_cast<long long>(kWindowSamples) / Q * P : 0;
+    w.slot_bytes = static_cast<size_t>(kWindowSamples) / rin.Q * rin.P * sb;
     for(uint8_t*& p : w.pinned)
         if(rc == MSK144_OK) rc = host_alloc(h, w.mem, &p, w.slot_bytes);
     const size_t g_count = static_cast<size_t>(C32) * L * 32;
-    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, static_cast<size_t>(hist) * sb + w.slot_bytes)) != MSK144_OK ||
-       (rc = dev_alloc(h, w.mem, &w.d_G, g_count)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_fmod, C)) != MSK144_OK ||
+    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, static_cast<size_t>(raw_hist) * sb + w.slot_bytes)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_G, g_count)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_fmod, S)) != MSK144_OK ||
        (rc = dev_alloc(h, w.mem, &w.d_rot, msk144wb::kOutRate)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK ||
-       (Q > 1 && (rc = dev_alloc(h, w.mem, &w.d_branches, Q)) != MSK144_OK))
+       (Q > 1 && (rc = dev_alloc(h, w.mem, &w.d_branches, Q)) != MSK144_OK) ||
+       (bank && ((rc = dev_alloc(h, w.mem, &w.d_h1, h1.size())) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_bands, NB)) != MSK144_OK ||
+                 (rc = dev_alloc(h, w.mem, &w.d_tw, msk144wb::kBankBands)) != MSK144_OK ||
+                 (rc = dev_alloc(h, w.mem, &w.d_sub, static_cast<size_t>(NB) * stride)) != MSK144_OK ||
+                 (rc = dev_alloc(h, w.mem, &w.d_wave_band, wave_band.size())) != MSK144_OK ||
+                 (rc = dev_alloc(h, w.mem, &w.d_slot_channel, S)) != MSK144_OK)))
     {
         wb_release(h);
         return rc;
     }
 
-    // G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs} in double, stored f32 at [c/32][p][q][c%32] with k = p + D*q; phases in integers
-    const long long fs = static_cast<long long>(wp->rate_hz);
+    // G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs} in double, stored f32 at [c/32][p][q][c%32] with k = p + D*q; phases in integers.
+    // c is a slot and f_c its offset; Fs the channeliser's rate.
+    const long long fs = static_cast<long long>(rate2);
     const int D = P;
     std::vector<float2> G(g_count, make_float2(0.0f, 0.0f));
-    std::vector<int32_t> fmod(static_cast<size_t>(C));
+    std::vector<int32_t> fmod(static_cast<size_t>(S), 0);
     std::vector<WidebandBranch> branches(Q > 1 ? static_cast<size_t>(Q) : 0);
-    for(int c = 0; c < C; c++)
+    for(int c = 0; c < S; c++)
     {
-        const long long f = wp->offsets_hz[c];
+        if(slot_channel[static_cast<size_t>(c)] < 0) continue;
+        const long long f = slot_offset[static_cast<size_t>(c)];
         fmod[static_cast<size_t>(c)] = static_cast<int32_t>(((f % msk144wb::kOutRate) + msk144wb::kOutRate) % msk144wb::kOutRate);
         const long long fpos = ((f % fs) + fs) % fs;
         if(Q > 1)
@@ -1164,15 +1245,38 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
         rot[static_cast<size_t>(r)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(-std::sin(ph)));
     }
     HIP_TRY(h, hipMemcpy(w.d_G, G.data(), g_count * sizeof(float2), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(w.d_fmod, fmod.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(w.d_fmod, fmod.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(w.d_rot, rot.data(), sizeof(float2) * rot.size(), hipMemcpyHostToDevice));
     if(Q > 1) HIP_TRY(h, hipMemcpy(w.d_branches, branches.data(), sizeof(WidebandBranch) * branches.size(), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
+    if(bank)
+    {
+        std::vector<float> h1f(h1.begin(), h1.end());
+        std::vector<float2> tw(msk144wb::kBankBands);
+        for(int t = 0; t < msk144wb::kBankBands; t++)
+        {
+            const double ph = 2.0 * M_PI * t / msk144wb::kBankBands;
+            tw[static_cast<size_t>(t)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(std::sin(ph)));
+        }
+        HIP_TRY(h, hipMemcpy(w.d_h1, h1f.data(), sizeof(float) * h1f.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(w.d_bands, band_list.data(), sizeof(int32_t) * NB, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(w.d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(w.d_wave_band, wave_band.data(), sizeof(int32_t) * wave_band.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(w.d_slot_channel, slot_channel.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
+        w.K1 = static_cast<int>(h1.size()) / msk144wb::kBankBands;
+        w.band_index.assign(band_list.begin(), band_list.end());
+    }
     w.P = P;
     w.Q = Q;
     w.K = K;
     w.L = L;
     w.hist = hist;
+    w.Pin = rin.P;
+    w.Qin = rin.Q;
+    w.raw_hist = raw_hist;
+    w.bank = bank;
+    w.slots = S;
+    w.stride = stride;
     w.format = wp->format;
     w.gain = wp->gain;
     w.configured = true;
@@ -1200,9 +1304,14 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     msk144_handle::Slot& sl = h->slots[slot];
     const int M = first ? kWindowSamples : kHopSamples;
     const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
-    const size_t hist_bytes = static_cast<size_t>(w.hist) * sb;
-    const size_t new_bytes = static_cast<size_t>(M) / w.Q * w.P * sb;
-    if(first) w.m_next = 0;
+    const size_t hist_bytes = static_cast<size_t>(w.raw_hist) * sb;
+    const size_t new_bytes = static_cast<size_t>(M) / w.Qin * w.Pin * sb;
+    const int frames = M / w.Q * w.P;         // bank: frames of 32 input samples = the channeliser's input samples
+    if(first)
+    {
+        w.m_next = 0;
+        w.n_next = 0;
+    }
     for(int j = 0; j < C; j++)
     {
         sl.streams[j] = j;
@@ -1211,9 +1320,13 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     uint8_t* raw = w.d_raw;
     ev_begin(h);
     hipError_t e = hipSuccess;
-    // the filter history: the last hist samples of the previous push (a push has >= 2592*P/Q samples, hist < ceil(64*P/Q), so the
-    // ranges do not overlap)
-    if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Q * w.P * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
+    // the filter history: the last raw_hist samples of the previous push (a push has >= 2592*P/Q samples, raw_hist < ceil(64*P/Q)
+    // without the bank and 1024 with it, so the ranges do not overlap)
+    if(!first) e = hipMemcpyAsync(raw, raw + static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin * sb, hist_bytes, hipMemcpyDeviceToDevice, h->stream);
+    // the bank's sub-band streams: the channeliser's history, the last hist frames of the previous push, likewise apart
+    if(e == hipSuccess && !first && w.bank && w.hist > 0)
+        e = hipMemcpy2DAsync(w.d_sub, w.stride * sizeof(float2), w.d_sub + w.last_frames, w.stride * sizeof(float2), w.hist * sizeof(float2), w.band_index.size(),
+                             hipMemcpyDeviceToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(raw + hist_bytes, w.pinned[slot], new_bytes, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, C, hipMemcpyHostToDevice, h->stream);
@@ -1221,15 +1334,28 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
     ev_begin(h);
+    const void* in = w.d_raw;
+    int format = w.format;
+    WidebandBands bands;
+    if(w.bank)
+    {
+        launch_bank(w.d_raw, w.format, w.d_h1, w.d_bands, w.d_tw, w.d_sub, static_cast<int>(w.band_index.size()), w.K1, frames, w.stride, w.hist, first ? 1 : 0,
+                    w.n_next, h->stream);
+        in = w.d_sub;
+        format = kSubbandFormat;
+        bands = WidebandBands{w.d_wave_band, w.d_slot_channel, w.stride};
+    }
     if(w.Q == 1)
-        launch_channelise(w.d_raw, w.format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, C, w.P, w.K, M,
-                          first ? 1 : 0, w.m_next, w.gain, h->stream);
+        launch_channelise(in, format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, w.slots, w.P, w.K, M,
+                          first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
     else
-        launch_channelise_rational(w.d_raw, w.format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops),
-                                   w.d_clip, C, w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream);
+        launch_channelise_rational(in, format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops),
+                                   w.d_clip, w.slots, w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     w.m_next += M;
+    w.n_next += frames;
+    w.last_frames = frames;
     w.started = true;
     w.last_first = first != 0;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, C, h->stream);
@@ -1252,6 +1378,22 @@ int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out)
         out += half;
     }
     HIP_TRY(h, hipMemcpy(out, hop, half, hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(!w.started) return fail(h, MSK144_ESTATE, "no wideband push has been made");
+    if(!w.bank) return fail(h, MSK144_ESTATE, "the wideband configuration has no bank (rate <= 6144000 Hz)");
+    if(band < -msk144wb::kBankBands / 2 || band > msk144wb::kBankBands / 2) return fail(h, MSK144_EINVAL, "band out of range (-32..32)");
+    size_t j = 0;
+    while(j < w.band_index.size() && w.band_index[j] != (band & (msk144wb::kBankBands - 1))) j++;
+    if(j == w.band_index.size()) return fail(h, MSK144_EINVAL, "no channel lies in band " + std::to_string(band));
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out, w.d_sub + static_cast<long long>(j) * w.stride + w.hist, sizeof(float2) * w.last_frames, hipMemcpyDeviceToHost));
     return MSK144_OK;
 }
 

@@ -75,12 +75,24 @@ void launch_frontend_iq(const DeviceStore& st, const int8_t* d_in, hipStream_t s
 // first_halves[j] + hops[j] when is_first[j]); windows[j] = the stream's new window.  Halves and windows in raw input bytes.
 void launch_hop_ring(void* ring, const void* hops, const void* first_halves, const int32_t* streams, const uint8_t* is_first, void* windows, int n, hipStream_t stream);
 
+// Above 6.144 Msps the channeliser reads the analysis bank's sub-band streams (format kSubbandFormat: complex f32, one stream per
+// occupied band, stride float2 apart) and its `channels` are channel slots: slot c belongs to channel slot_channel[c] (-1: a padding
+// slot, written nowhere), and wave w (slots 32w .. 32w+31) reads stream wave_band[w].  Unused at the raw formats.
+constexpr int kSubbandFormat = 3;
+struct WidebandBands
+{
+    const int32_t* wave_band = nullptr;
+    const int32_t* slot_channel = nullptr;
+    long long stride = 0;
+};
+
 // wideband down-converter bank (channelise.hip): raw = the L-1 history samples then M*D new ones (format 0 cu8, 1 cs8, 2 cs16);
 // G = [ceil(channels/32)][D][K][32] taps (tap k = p + D*q at [p][q], zero rows past `channels`); fmod[c] = f_c mod 12000 in
 // 0..11999; rot[r] = e^{-j2pi r/12000}.  Writes the int8 I/Q of output samples m_base .. m_base+M-1 of every channel into the hop
 // ring staging (M = 5184 with first != 0: the first 2592 into first_halves) and adds the clipped components to *clip_count.
 void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
-                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream);
+                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream,
+                       WidebandBands bands = {});
 
 // one polyphase branch of a rational-rate channeliser (Fs = 12000 P/Q, Q > 1): the outputs m = mr + Q a of a push read inputs
 // n0 + a P - k, k < taps, with the taps h[r + k Q] (r = mr P mod Q) of its G block, which starts at float2 offset g_off
@@ -95,7 +107,13 @@ struct WidebandBranch
 // G carries each branch's constant output rotation e^{-j2pi (f_c n0 mod Fs)/Fs}, so the kernel rotates by (f_c (m - mr)) mod 12000.
 void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
                                 int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
-                                long long m_base, float gain, hipStream_t stream);
+                                long long m_base, float gain, hipStream_t stream, WidebandBands bands = {});
+
+// the analysis bank in front of the channeliser above 6.144 Msps (bank.hip): raw = the L1-1 history samples then 32 x frames new
+// ones (format 0 cu8, 1 cs8, 2 cs16); h1 = the L1 = 64 K1 bank taps (f32); bands[j] = the occupied band k mod 64 of stream j;
+// tw[t] = e^{+j2pi t/64}.  Writes s_{bands[j]}[n_base + f] of frames f < frames to sub[j * stride + off + f] (complex f32).
+void launch_bank(const void* raw, int format, const float* h1, const int32_t* bands, const float2* tw, float2* sub, int n_bands, int K1, int frames,
+                 long long stride, int off, int first, long long n_base, hipStream_t stream);
 
 // one wave that spins for `ticks` of the 100 MHz counter; out[0] = shader cycles elapsed, out[1] = 100 MHz ticks elapsed (hopring.hip)
 void launch_clock_probe(uint64_t* out, uint32_t ticks, hipStream_t stream);

@@ -28,6 +28,16 @@ constexpr double kPassHz = 4000.0;     // design band edges of the default filte
 constexpr double kStopHz = 8000.0;
 constexpr double kKaiserBeta = 7.0;    // about 70 dB side lobes
 
+// Two-stage bank above 6.144 Msps: a 64-band, 2x oversampled analysis bank (decimation 32) in front of the channeliser, which then
+// runs at the sub-band rate Fs/32 on each channel's band
+constexpr int kBankBands = 64;
+constexpr int kBankDecimation = 32;
+constexpr int kBankRateStepHz = 8000;  // Fs/64 a multiple of 125, Fs/32 a multiple of 250 with Q dividing 96
+constexpr int64_t kMaxBankRateHz = 61440000;
+constexpr int kDefaultBankTapsPerBand = 8;  // K1; L1 = 64 K1 taps
+constexpr int kMaxBankTapsPerBand = 16;
+constexpr double kBankKaiserBeta = 8.0;     // about 80 dB side lobes
+
 enum Format
 {
     kCu8 = 0,   // rtl_sdr: (u - 127.5) / 128
@@ -100,11 +110,64 @@ inline std::vector<double> design_taps_rate(int64_t rate_hz, int K)
     return h;
 }
 
+// A rate above 6.144 Msps that the two-stage bank takes: a multiple of 8000 Hz up to 61.44 Msps
+inline bool is_bank_rate(int64_t rate_hz)
+{
+    return rate_hz > kMaxRateHz && rate_hz <= kMaxBankRateHz && rate_hz % kBankRateStepHz == 0;
+}
+
+// The rate the channeliser runs at: Fs itself, or the sub-band rate Fs/32 behind the bank
+inline int64_t stage2_rate(int64_t rate_hz)
+{
+    return is_bank_rate(rate_hz) ? rate_hz / kBankDecimation : rate_hz;
+}
+
+// Band of channel offset f_c at a bank rate: k = floor((64 f_c + Fs/2) / Fs), -32..32 for |f_c| <= Fs/2 (band 32 is band -32); the
+// residual offset f_c - k Fs/64 is an integer with |f_c - k Fs/64| <= Fs/128
+inline int bank_band(int64_t rate_hz, int64_t f_hz)
+{
+    const int64_t num = kBankBands * f_hz + rate_hz / 2;
+    return static_cast<int>(num >= 0 ? num / rate_hz : -((-num + rate_hz - 1) / rate_hz));
+}
+
+inline int64_t bank_residual(int64_t rate_hz, int64_t f_hz)
+{
+    return f_hz - static_cast<int64_t>(bank_band(rate_hz, f_hz)) * (rate_hz / kBankBands);
+}
+
+// Default analysis-bank prototype, L1 = 64 K1 taps at Fs: a Kaiser-windowed sinc (beta 8) with its cut-off half way between the
+// pass edge Fs/128 + 4 kHz (a channel's 4 kHz pass band at the largest residual offset) and the stop edge 3 Fs/128 - 8 kHz (what
+// the decimation by 32 folds onto a channel's 8 kHz stop edge), scaled to unit DC gain.  Symmetric about (L1-1)/2.
+inline std::vector<double> design_bank_taps(int64_t rate_hz, int K1)
+{
+    const int L = kBankBands * K1;
+    const double fs = static_cast<double>(rate_hz);
+    const double fc = 0.5 * ((fs / 128.0 + kPassHz) + (3.0 * fs / 128.0 - kStopHz)) / fs;
+    const double mid = 0.5 * (L - 1);
+    const double i0b = bessel_i0(kBankKaiserBeta);
+    std::vector<double> h(static_cast<size_t>(L));
+    double sum = 0.0;
+    for(int k = 0; k < L; k++)
+    {
+        const double t = k - mid;
+        const double arg = 2.0 * fc * t;
+        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
+        const double r = L > 1 ? t / mid : 0.0;
+        const double w = bessel_i0(kBankKaiserBeta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
+        h[static_cast<size_t>(k)] = sinc * w;
+        sum += h[static_cast<size_t>(k)];
+    }
+    for(double& v : h) v /= sum;
+    return h;
+}
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {
     if(rate_hz <= 0 || rate_hz % kRateStepHz != 0) return "wideband rate must be a positive multiple of 125 Hz; a multiple of 12000 Hz decimates by an integer";
-    if(rate_hz < kMinRateHz || rate_hz > kMaxRateHz) return "wideband rate must be D x 12000 Hz with 2 <= D <= 512 (D = P/Q may be a fraction: 24000..6144000 Hz)";
+    if((rate_hz < kMinRateHz || rate_hz > kMaxRateHz) && !is_bank_rate(rate_hz))
+        return "wideband rate must be D x 12000 Hz with 2 <= D <= 512 (D = P/Q may be a fraction: 24000..6144000 Hz), or a multiple of 8000 Hz "
+               "above 6144000 up to 61440000 Hz (two-stage bank)";
     if(format != kCu8 && format != kCs8 && format != kCs16) return "wideband format must be cu8, cs8 or cs16";
     if(K < 1 || K > kMaxTapsPerPhase) return "taps per phase must be 1..64";
     if(!(gain > 0.0f) || !std::isfinite(gain) || gain > kMaxGain) return "wideband gain must be a positive finite number no larger than 1e36";

@@ -82,6 +82,8 @@ PROTOTYPES = {
     "msk144_push_wideband": ([_vp, _i32, _i32], C.c_int),
     "msk144_dump_wideband_hop": ([_vp, _i32, _vp], C.c_int),
     "msk144_wideband_clip_count": ([_vp, _P(C.c_int64)], C.c_int),
+    "msk144_set_wideband_ex": ([_vp, _P(WidebandParams), _P(C.c_double), _i32], C.c_int),
+    "msk144_dump_wideband_band": ([_vp, _i32, _vp], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -305,22 +307,30 @@ class HipDecoder:
         return records, powers
 
     # ---- wideband channeliser (read_mode 2 handles) ----
-    def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0):
+    def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0, bank_taps=None):
         """Configure the down-converter bank: one channel per offset (len == channels).  taps=None: the default design of
         libmsk144host.so: wideband.default_taps(D) at rate_hz = D x 12000, wideband.default_taps_for_rate for any other rate
-        12000 x P/Q (K*P taps summing to Q)."""
-        from .wideband import default_taps, default_taps_for_rate, rate_ratio
+        12000 x P/Q (K*P taps summing to Q).  Above 6.144 Msps the taps are the channeliser's at rate_hz/32 (the default: the same
+        design at that rate) and bank_taps the analysis bank's (64 K1 taps; None: the default bank)."""
+        from .wideband import default_taps, default_taps_for_rate, rate_ratio, stage2_rate
+        rate2 = stage2_rate(int(rate_hz)) if int(rate_hz) > 0 else 0
         P, Q = rate_ratio(int(rate_hz)) if int(rate_hz) > 0 else (0, 1)
+        P2, Q2 = rate_ratio(rate2) if rate2 > 0 else (0, 1)
         if taps is None:
-            taps = default_taps(P, taps_per_phase) if Q == 1 else default_taps_for_rate(int(rate_hz), taps_per_phase)
+            taps = default_taps(P2, taps_per_phase) if Q2 == 1 else default_taps_for_rate(rate2, taps_per_phase)
         self._wb_taps = np.ascontiguousarray(taps, dtype=np.float64)
         self._wb_offsets = np.ascontiguousarray(offsets_hz, dtype=np.int32)
         self._wb_format = fmt
         self._wb_P, self._wb_Q = P, Q
+        self._wb_bank_ratio = (P2, Q2)
+        self._wb_bank_taps = None if bank_taps is None else np.ascontiguousarray(bank_taps, dtype=np.float64)
         wp = WidebandParams(int(rate_hz), WB_FORMATS[fmt], int(taps_per_phase), float(gain), len(self._wb_taps),
                             self._wb_taps.ctypes.data_as(C.POINTER(C.c_double)), self._wb_offsets.ctypes.data_as(C.POINTER(C.c_int32)),
                             len(self._wb_offsets))
-        self._chk(self.L.msk144_set_wideband(self.h, C.byref(wp)))
+        if self._wb_bank_taps is None:
+            self._chk(self.L.msk144_set_wideband_ex(self.h, C.byref(wp), None, 0))
+        else:
+            self._chk(self.L.msk144_set_wideband_ex(self.h, C.byref(wp), self._wb_bank_taps.ctypes.data_as(C.POINTER(C.c_double)), len(self._wb_bank_taps)))
 
     def wideband_slot(self, slot: int) -> np.ndarray:
         """The slot's pinned wideband buffer as a numpy view of raw sample components (uint8 / int8 / int16, I,Q interleaved)."""
@@ -346,6 +356,13 @@ class HipDecoder:
         """int8 [n][2] I/Q of the channel's last push (n = 5184 after a first push, else 2592)."""
         out = np.empty((5184 if getattr(self, "_wb_last_first", True) else 2592, 2), dtype=np.int8)
         self._chk(self.L.msk144_dump_wideband_hop(self.h, channel, _ptr(out)))
+        return out
+
+    def dump_wideband_band(self, band: int) -> np.ndarray:
+        """complex64 s_k[n] of band k (-32..32) from the last push at a bank rate: 5184 or 2592 x P/Q samples, P/Q = (rate/32)/12000."""
+        P2, Q2 = self._wb_bank_ratio
+        out = np.empty((5184 if getattr(self, "_wb_last_first", True) else 2592) * P2 // Q2, dtype=np.complex64)
+        self._chk(self.L.msk144_dump_wideband_band(self.h, int(band), _ptr(out)))
         return out
 
     def wideband_clip_count(self) -> int:

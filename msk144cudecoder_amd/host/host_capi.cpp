@@ -32,6 +32,19 @@ int msk144host_wideband_taps_rate(int64_t rate_hz, int K, double* out)
     return static_cast<int>(h.size());
 }
 
+// The default analysis-bank prototype above 6.144 Msps (csrc/wideband.h design_bank_taps): L1 = 64 K1 taps summing to 1 into out;
+// returns L1, or -1 for a rate the bank does not take (a multiple of 8000 Hz above 6144000 up to 61440000) or K1 outside 1..16.
+int msk144host_wideband_bank_taps(int64_t rate_hz, int K1, double* out)
+{
+    if(!msk144wb::is_bank_rate(rate_hz) || K1 < 1 || K1 > msk144wb::kMaxBankTapsPerBand) return -1;
+    const std::vector<double> h = msk144wb::design_bank_taps(rate_hz, K1);
+    if(out) std::memcpy(out, h.data(), sizeof(double) * h.size());
+    return static_cast<int>(h.size());
+}
+
+// The band of channel offset f_hz at a bank rate (csrc/wideband.h bank_band), -32..32
+int msk144host_wideband_band(int64_t rate_hz, int64_t f_hz) { return msk144wb::bank_band(rate_hz, f_hz); }
+
 // The contract's configuration rules (csrc/wideband.h check_config), the ones msk144_set_wideband and msk144hipdecoder apply:
 // returns 0 when valid, else -1 with the refusal text in why (NUL-terminated, at most why_len bytes).
 int msk144host_wideband_check(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count, char* why, int why_len)

@@ -64,7 +64,7 @@ void show_help(const char* prog)
     std::cout << "                   --max-results=N             Capacity of the per-hop decode list of a device (default 256 per stream + 131072). A hop that exceeds it is cut and reported; decoding goes on." << std::endl;
     std::cout << "                   --every-slot                Demodulate and decode every candidate slot on its own, as the reference does. Default off: a slot whose position folds the same frames as a lower slot of its group reports that slot's result (same output), and a candidate the nbadsync gate drops is not demodulated beyond its sync check." << std::endl;
     std::cout << "                   --timing                    With --inputs: per-hop host and device time split (ingest, H2D, GPU, D2H, post-processing) on stderr at the end." << std::endl;
-    std::cout << "                   --wideband-rate=HZ          Read ONE wideband I/Q stream on stdin at HZ sps and channelise it on the GPU into one 12000 sps IQ stream per channel offset (as --read-mode=2 would read it); lines carry ch=<index>. HZ is a multiple of 125 from 24000 to 6144000: HZ = 12000 x P/Q, 2 <= P/Q <= 512; a multiple of 12000 (e.g. 1920000) decimates by the integer D = HZ/12000, any other rate (e.g. 2048000 = 12000 x 512/3, rtl_sdr's default) resamples by P/Q." << std::endl;
+    std::cout << "                   --wideband-rate=HZ          Read ONE wideband I/Q stream on stdin at HZ sps and channelise it on the GPU into one 12000 sps IQ stream per channel offset (as --read-mode=2 would read it); lines carry ch=<index>. HZ is a multiple of 125 from 24000 to 6144000: HZ = 12000 x P/Q, 2 <= P/Q <= 512; a multiple of 12000 (e.g. 1920000) decimates by the integer D = HZ/12000, any other rate (e.g. 2048000 = 12000 x 512/3, rtl_sdr's default) resamples by P/Q. Above that, HZ a multiple of 8000 up to 61440000 (e.g. 10000000, 20000000): a 64-band analysis bank takes each channel's band to HZ/32 first, then the channeliser runs at HZ/32 (--taps-per-phase then counts its taps at HZ/32)." << std::endl;
     std::cout << "                   --wideband-format=FMT       cu8 (rtl_sdr), cs8 or cs16 interleaved I,Q. Default=cu8." << std::endl;
     std::cout << "                   --channel-offsets=F1,F2,... Channel centres in integer Hz from the wideband centre, |F| <= HZ/2 - 6000." << std::endl;
     std::cout << "                   --channel-grid=F:STEP:N     The same as N offsets F, F+STEP, ..." << std::endl;
@@ -394,13 +394,25 @@ int main(int argc, char* const argv[])
     if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
     if(wideband)
     {
-        const msk144wb::RateRatio rr = msk144wb::rate_ratio(wbo.rate_hz);
+        const int64_t rate2 = msk144wb::stage2_rate(wbo.rate_hz);  // the channeliser's rate: Fs, or Fs/32 behind the bank
+        const msk144wb::RateRatio rr = msk144wb::rate_ratio(rate2);
         static const char* fmt_names[] = {"cu8", "cs8", "cs16"};
-        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, "
-                  << (rr.Q == 1 ? "decimation " + std::to_string(rr.P) : "resampling " + std::to_string(rr.P) + "/" + std::to_string(rr.Q)) << ", filter "
+        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, ";
+        if(rate2 != wbo.rate_hz)
+        {
+            std::vector<int> bands;
+            for(int32_t f : wbo.offsets)
+            {
+                const int b = msk144wb::bank_band(wbo.rate_hz, f) & (msk144wb::kBankBands - 1);
+                if(std::find(bands.begin(), bands.end(), b) == bands.end()) bands.push_back(b);
+            }
+            std::cerr << "stage 1: " << msk144wb::kBankBands << "-band analysis bank, " << bands.size() << " bands occupied, sub-band rate " << rate2 << " sps, filter "
+                      << msk144wb::kDefaultBankTapsPerBand << " x " << msk144wb::kBankBands << " taps; stage 2: ";
+        }
+        std::cerr << (rr.Q == 1 ? "decimation " + std::to_string(rr.P) : "resampling " + std::to_string(rr.P) + "/" + std::to_string(rr.Q)) << ", filter "
                   << wbo.taps_per_phase << " x " << rr.P << " taps, gain " << wbo.gain << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
         for(int c = 0; c < nch; c++) std::cerr << "msk144hipdecoder: ch=" << c << " offset " << wbo.offsets[static_cast<size_t>(c)] << " Hz" << std::endl;
-        const std::vector<double> taps = msk144wb::design_taps_rate(wbo.rate_hz, wbo.taps_per_phase);
+        const std::vector<double> taps = msk144wb::design_taps_rate(rate2, wbo.taps_per_phase);
         msk144_wideband_params wp{};
         wp.rate_hz = wbo.rate_hz;
         wp.format = wbo.format;

@@ -23,6 +23,10 @@ OUT_RATE = 12000
 FIRST_OUT = 5184   # output samples per channel of a first push
 HOP_OUT = 2592     # ... of every later push
 FORMATS = ("cu8", "cs8", "cs16")
+MAX_RATE = 6144000          # the single-stage channeliser's top rate
+BANDS = 64                  # the two-stage bank above it: 64 bands, decimation 32, rates multiples of 8000 up to 61.44 Msps
+BANK_DECIMATION = 32
+MAX_BANK_RATE = 61440000
 _RAW_DTYPE = {"cu8": np.uint8, "cs8": np.int8, "cs16": np.int16}
 
 _host = None
@@ -40,6 +44,8 @@ def _host_lib():
         L.msk144host_wideband_taps_rate.restype = C.c_int
         L.msk144host_wideband_check.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_char_p, C.c_int]
         L.msk144host_wideband_check.restype = C.c_int
+        L.msk144host_wideband_bank_taps.argtypes = [C.c_int64, C.c_int, C.c_void_p]
+        L.msk144host_wideband_bank_taps.restype = C.c_int
         _host = L
     return _host
 
@@ -70,6 +76,38 @@ def default_taps_for_rate(rate_hz: int, K: int = 16) -> np.ndarray:
         raise ValueError(f"no default filter for rate {rate_hz} Hz, K={K} (a multiple of 125 Hz in 24000..6144000, K 1..64)")
     h = np.empty(n, dtype=np.float64)
     L.msk144host_wideband_taps_rate(int(rate_hz), int(K), h.ctypes.data_as(C.c_void_p))
+    return h
+
+
+def is_bank_rate(rate_hz: int) -> bool:
+    """A rate the two-stage bank takes: a multiple of 8000 Hz above 6.144 Msps up to 61.44 Msps."""
+    return MAX_RATE < int(rate_hz) <= MAX_BANK_RATE and int(rate_hz) % 8000 == 0
+
+
+def stage2_rate(rate_hz: int) -> int:
+    """The channeliser's rate: rate_hz, or the sub-band rate rate_hz/32 behind the bank."""
+    return int(rate_hz) // BANK_DECIMATION if is_bank_rate(rate_hz) else int(rate_hz)
+
+
+def bank_band(rate_hz: int, offsets_hz) -> np.ndarray:
+    """k_c = floor((64 f_c + Fs/2) / Fs) in integers: -32..32 (band 32 is band -32)."""
+    f = np.asarray(offsets_hz, dtype=np.int64)
+    return np.floor_divide(BANDS * f + int(rate_hz) // 2, int(rate_hz))
+
+
+def bank_residual(rate_hz: int, offsets_hz) -> np.ndarray:
+    """d_c = f_c - k_c Fs/64, an integer with |d_c| <= Fs/128."""
+    return np.asarray(offsets_hz, dtype=np.int64) - bank_band(rate_hz, offsets_hz) * (int(rate_hz) // BANDS)
+
+
+def default_bank_taps(rate_hz: int, K1: int = 8) -> np.ndarray:
+    """The default analysis-bank prototype (64 K1 taps at Fs, summing to 1), exactly what the library uses."""
+    L = _host_lib()
+    n = L.msk144host_wideband_bank_taps(int(rate_hz), int(K1), None)
+    if n < 0:
+        raise ValueError(f"no default bank for rate {rate_hz} Hz, K1={K1} (a multiple of 8000 Hz above 6144000 up to 61440000, K1 1..16)")
+    h = np.empty(n, dtype=np.float64)
+    L.msk144host_wideband_bank_taps(int(rate_hz), int(K1), h.ctypes.data_as(C.c_void_p))
     return h
 
 
@@ -227,6 +265,101 @@ class Channeliser:
         return quantise(self.filter(x), self.gain)
 
 
+class AnalysisBank:
+    """Stage 1 of the two-stage contract, push by push, in polyphase form (16 MACs per input sample at K1 = 8, the DFT only for the
+    requested bands):
+        s_k[n] = (-1)^{k n} sum_{p<64} e^{+j2pi (k p mod 64)/64} u_p[n],   u_p[n] = sum_q h1[p + 64 q] x[32 n - p - 64 q]
+    which is the contract's sum over l = p + 64 q.  Keeps the last L1 - 1 input samples and the frame index n."""
+
+    CHUNK = 1 << 15   # frames per numpy block
+
+    def __init__(self, h1: np.ndarray, bands: Sequence[int]):
+        self.h1 = np.asarray(h1, dtype=np.float64)
+        self.L1 = len(self.h1)
+        if self.L1 % BANDS:
+            raise ValueError("the bank filter has 64 K1 taps")
+        self.K1 = self.L1 // BANDS
+        self.bands = np.mod(np.asarray(bands, dtype=np.int64), BANDS)
+        p = np.arange(BANDS)
+        self.W = np.exp(2j * np.pi * np.mod(p[:, None] * self.bands[None, :], BANDS) / BANDS)   # [p][band]
+        self.reset()
+
+    def reset(self):
+        self.hist = np.zeros(self.L1 - 1, dtype=np.complex128)
+        self.n = 0
+
+    def polyphase(self, x: np.ndarray) -> np.ndarray:
+        """u [frames][64] of the next len(x)/32 frames (history and n are not advanced)."""
+        xp = np.concatenate([self.hist, np.asarray(x, dtype=np.complex128)])
+        F = len(x) // BANK_DECIMATION
+        u = np.empty((F, BANDS), dtype=np.complex128)
+        p = np.arange(BANDS)
+        for f0 in range(0, F, self.CHUNK):
+            f = np.arange(f0, min(F, f0 + self.CHUNK))
+            base = (self.L1 - 1) + BANK_DECIMATION * f[:, None] - p[None, :]
+            acc = np.zeros((len(f), BANDS), dtype=np.complex128)
+            for q in range(self.K1):
+                acc += self.h1[p + BANDS * q][None, :] * xp[base - BANDS * q]
+            u[f0:f0 + len(f)] = acc
+        return u
+
+    def advance(self, x: np.ndarray):
+        xp = np.concatenate([self.hist, np.asarray(x, dtype=np.complex128)])
+        self.hist = xp[len(xp) - (self.L1 - 1):].copy()
+        self.n += len(x) // BANK_DECIMATION
+
+    def push(self, x: np.ndarray) -> np.ndarray:
+        """complex s [band][frames] of the next len(x)/32 frames, for self.bands in order (history and n advance)."""
+        if len(x) % BANK_DECIMATION:
+            raise ValueError("a push carries whole 32-sample frames")
+        u = self.polyphase(x)
+        n = self.n + np.arange(u.shape[0], dtype=np.int64)
+        s = (u @ self.W).T * np.where((self.bands[:, None] * n[None, :]) % 2 == 1, -1.0, 1.0)
+        self.advance(x)
+        return s
+
+
+class TwoStage:
+    """The two-stage contract above 6.144 Msps, push by push: AnalysisBank over the stream, then the existing Channeliser at Fs/32
+    on each occupied band with the residual offsets of its channels.  filter(x) -> y [channel][M] in channel order."""
+
+    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0,
+                 bank_taps: Optional[np.ndarray] = None):
+        if not is_bank_rate(rate_hz):
+            raise ValueError("the two-stage bank takes multiples of 8000 Hz above 6144000 up to 61440000")
+        self.rate = int(rate_hz)
+        self.rate2 = self.rate // BANK_DECIMATION
+        self.offsets = np.asarray(offsets_hz, dtype=np.int64)
+        self.h1 = default_bank_taps(rate_hz) if bank_taps is None else np.asarray(bank_taps, dtype=np.float64)
+        k = np.mod(bank_band(rate_hz, self.offsets), BANDS)
+        self.bands = sorted(set(int(b) for b in k))
+        self.members = [np.flatnonzero(k == b) for b in self.bands]
+        resid = bank_residual(rate_hz, self.offsets)
+        self.stage1 = AnalysisBank(self.h1, self.bands)
+        self.stage2 = [Channeliser(self.rate2, resid[m], taps=taps, K=K, gain=gain) for m in self.members]
+        self.taps = self.stage2[0].taps
+        self.gain = gain
+
+    def reset(self):
+        self.stage1.reset()
+        for ch in self.stage2:
+            ch.reset()
+
+    def filter(self, x: np.ndarray) -> np.ndarray:
+        s = self.stage1.push(x)
+        M = s.shape[1] * self.stage2[0].Q // self.stage2[0].P
+        y = np.empty((len(self.offsets), M), dtype=np.complex128)
+        for j, (m, ch) in enumerate(zip(self.members, self.stage2)):
+            y[m] = ch.filter(s[j])
+        self.last_subbands = s
+        return y
+
+    def push(self, x: np.ndarray, first: bool = False) -> Tuple[np.ndarray, int]:
+        if first:
+            self.reset()
+        return quantise(self.filter(x), self.gain)
+
+
 def naive_channel(x: np.ndarray, rate_hz: int, offset_hz: int, taps: np.ndarray) -> np.ndarray:
     """Mix by e^{-j2pi f_c n/Fs}, filter with h, keep every D-th sample: y[m] = (h * (x e^{-j2pi f_c n/Fs}))[mD]."""
     D = rate_hz // OUT_RATE
@@ -294,6 +427,33 @@ def _synth_wideband_rational(n_out, rate_hz, pings, noise_sigma, rng, fmt):
     return write_samples(x, fmt)
 
 
+def _synth_wideband_bank(n_out, rate_hz, pings, noise_sigma, rng, fmt):
+    """As _synth_wideband_rational, but each ping is FFT-resampled over its own span only (plus a margin), so that a scene at tens of
+    Msps costs what its pings cost; a span starts at a multiple of Q output samples."""
+    P, Q = rate_ratio(rate_hz)
+    if n_out % Q:
+        raise ValueError(f"n_out must be a multiple of Q = {Q} at {rate_hz} Hz")
+    N = n_out * P // Q
+    x = rng.normal(0.0, noise_sigma, N) + 1j * rng.normal(0.0, noise_sigma, N) if noise_sigma > 0 else np.zeros(N, dtype=np.complex128)
+    ref = noise_sigma if noise_sigma > 0 else 1.0
+    margin = 96 * Q
+    for f_c, p in pings:
+        bb = synth._ping_baseband(p)
+        amp = np.sqrt(2.0 * ref ** 2 * (2500.0 / rate_hz) * 10.0 ** (p.snr_db / 10.0))
+        m0 = max(0, (p.start - margin) // Q * Q)
+        m1 = min(n_out, -(-(p.start + len(bb) + margin) // Q) * Q)
+        if min(n_out, p.start + len(bb)) <= p.start:
+            continue
+        seg = np.zeros(m1 - m0, dtype=np.complex128)
+        k1 = min(n_out, p.start + len(bb))
+        seg[p.start - m0:k1 - m0] = bb[:k1 - p.start]
+        n0, n1 = m0 * P // Q, m1 * P // Q
+        n = np.arange(n0, n1)
+        carrier = np.exp(1j * (2 * np.pi * (f_c + p.freq_hz) * n / rate_hz + p.phase))
+        x[n0:n1] += amp * _resample(seg, n1 - n0) * carrier
+    return write_samples(x, fmt)
+
+
 def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Ping]], noise_sigma: float, rng: np.random.Generator,
                    fmt: str = "cu8") -> np.ndarray:
     """Raw interleaved components of a wideband scene n_out output samples long (n_out * P/Q wideband samples; n_out * D for an
@@ -302,6 +462,8 @@ def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Pi
     pings: (channel offset f_c in Hz, synth.Ping) pairs; the Ping's start is in 12 kHz samples and its freq_hz is the frequency
     inside the channel, so the carrier lands at f_c + freq_hz.  noise_sigma: per rail, in full-scale units (1 = the format's full
     scale).  SNR in 2500 Hz as in synth.synth_iq: 10log10(A^2 / (2 sigma^2 2500 / Fs))."""
+    if is_bank_rate(rate_hz):
+        return _synth_wideband_bank(n_out, rate_hz, pings, noise_sigma, rng, fmt)
     if rate_ratio(rate_hz)[1] > 1:
         return _synth_wideband_rational(n_out, rate_hz, pings, noise_sigma, rng, fmt)
     D = rate_hz // OUT_RATE

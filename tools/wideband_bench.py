@@ -3,7 +3,8 @@
 For every (channels, rate) the handle is pushed `--pushes` later pushes of random cu8 samples.  In wideband mode the front-end stage
 time covers the channeliser and the IQ front end; the same handle is then fed the same number of plain msk144_push_hops calls,
 whose front-end time is the IQ front end alone, and the difference is the channeliser.  FLOP count: channels x 2592 x K x
-(Fs/12000) x 8 (= channels x 2592 x K*D x 8 at Fs = D x 12000).  One JSON line per configuration on stdout.
+(Fs/12000) x 8 (= channels x 2592 x K*D x 8 at Fs = D x 12000); above 6.144 Msps (the two-stage bank) the bank's work per push
+plus the channeliser's at Fs/32.  One JSON line per configuration on stdout.
 
 Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --program-rate, default 1.92 Msps, the program's
 default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
@@ -28,7 +29,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from msk144cudecoder_amd import hipdecoder  # noqa: E402
+from msk144cudecoder_amd import hipdecoder, wideband  # noqa: E402
 
 FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
@@ -62,11 +63,22 @@ def measure(C: int, rate: int, pushes: int, K: int = 16) -> dict:
     ms = wide["frontend"][0] - plain["frontend"][0]
     flop = C * 2592 * K * P * 8 // Q
     ratio = dict(D=D) if Q == 1 else dict(rate_hz=rate, P=P, Q=Q)
+    target = 2.0 if C == 1024 and rate in (1920000, 2048000, 2500000) else None
+    if wideband.is_bank_rate(rate):
+        # two stages: the bank's 64 K1 real-by-complex MACs (4 flop) per frame plus 64 complex MACs (8 flop) per occupied band and
+        # frame, then the channeliser at Fs/32 (P2/Q2 = Fs/32/12000), channels x 2592 x K P2/Q2 x 8
+        P2, Q2 = wideband.rate_ratio(rate // 32)
+        frames = 2592 * P2 // Q2
+        bands = len({int(k) % 64 for k in wideband.bank_band(rate, offsets)})
+        flop1 = frames * (64 * 8 * 4 + bands * 64 * 8)
+        flop = flop1 + C * 2592 * K * P2 * 8 // Q2
+        ratio = dict(rate_hz=rate, stage1_bands=bands, stage1_gflop=round(flop1 / 1e9, 3), stage2_P=P2, stage2_Q=Q2)
+        target = {10000000: 2.0, 20000000: 2.0, 61440000: 3.0}.get(rate) if C == 1024 else None
     return dict(channels=C, **ratio, K=K, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
                 channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
                 tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
                 fraction_of_fp32_peak=round(flop / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 3) if ms > 0 else None,
-                target_ms=2.0 if C == 1024 and rate in (1920000, 2048000, 2500000) else None)
+                target_ms=target)
 
 
 def program_run(hops: int, C: int = 1024, rate: int = 1920000) -> dict:
