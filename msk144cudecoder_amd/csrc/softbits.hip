@@ -1,24 +1,31 @@
-// softbits: per-candidate frame fold, carrier-phase estimate, matched filter, LLR scaling, sync check.
+// softbits: matched-filter plane per tile, per-candidate frame fold, carrier-phase estimate, LLR scaling, sync check.
 //
 // Replaces softbits_kernel (softbits_kernel.cuh:9-249).  The reference launches one
 // 160-thread block per candidate and every block re-mixes the whole 5184-sample window; here one
-// workgroup (8 waves) serves all D*8 candidates of a (channel, frequency) pair, mixes the window ONCE
-// into LDS (same float phase as the scan) and then each 64-lane wave demodulates candidates on its own,
-// entirely in registers - no workgroup barrier after the mix and no LDS scratch, so the only LDS is the
-// 48.4 KB window (ring + one frame of pad) and three workgroups (24 waves) fit a CU.
+// workgroup (8 waves) serves all D*8 candidates of a (channel, frequency) pair and mixes the window ONCE
+// into LDS (same float phase as the scan).
 //
-// A candidate is demodulated in two parts: first the slots its sync check needs (slot 0 carries softbits 0..7 and 56..63,
-// slot 2 the partial sum that wraps into softbit 0), the carrier phase and nbadsync; then the middle slot, the
-// normalisation and the LLR row.  In blocked staging (no LLR row outlives its channel block) a candidate the index stage
-// will drop (nbadsync > threshold) stops after part one; with the LLR store retained every candidate is demodulated in full.
+// Filtering and folding are both linear, so they commute.  The workgroup applies the 11-tap half-sine pulse ONCE to the
+// whole ring, P[n] = sum_{s=1..11} pp[s] x[(n + s) mod 5184], and writes P over the mixed window.  Softbit u = 1..143 of a
+// candidate at `pos` with frame mask M is then one component of rot * F(u-1) (Re for odd u, Im for even u), where
+//     F(g) = sum_{m in M} P[pos + 864 m + 6 g]
+// and rot is the carrier phasor: a candidate costs one LDS read and one complex add per frame and 64 softbits, then a rotation.
+// (softbits_kernel.cuh:157-180 sums I bits 12j..12j+11 and Q bits 12j-6..12j+5 of the rotated folded frame: softbit u is the
+// 12-tap sum over groups u-1 and u, i.e. u1[u-1] + u2[u] with u1[g] = sum_{t<6} pp[t] c[6g+t], u2[g] = sum_{t<6} pp[6+t] c[6g+t],
+// and u1[g] + u2[g+1] is the folded P at group g.)  Five half-pulse sums per candidate cannot come from P and are folded from the
+// mixed window before P replaces it: u2[0] and u1[143] (softbit 0 wraps round the folded frame, group 143 -> group 0) and u1[6],
+// u2[56], u1[62] (the sync template covers half a pulse at the edges of each sync word).  Every result is the reference's linear
+// form, associated differently (~1e-7 relative, as filtering before rotating already was).
 //
-// Register layout: the 864-sample folded frame is cut into 144 half-bit groups of 6 samples; group
-// h = lane + 64*s (s = 0,1,2) lives in lane `lane`, slot `s`.  Softbit u needs groups u-1 and u
-// (softbits_kernel.cuh:158-177: I bits 12j..12j+11, Q bits 12j-6..12j+5), so its 12-tap sum starts in
-// the lane of group u-1 (taps pp[0..5]), hops one lane with a DPP wave shift and finishes in lane
-// u%64 with taps pp[6..11], and softbit u ends up in lane u%64 of slot u/64.  The tap sums run on the folded
-// complex samples; the carrier rotation, common to the whole frame, is applied to the two sums of a group.
-// Fold reads are ds_read_b128 (conflict-free at the 48-byte lane stride; see the fold section).
+// Plane layout, residue-major: P_r[k] = P[6 k + r] in six sub-rings of 864 entries plus a 142-entry wrap pad (kPlaneStride apart),
+// so lane l of a candidate reads group g = l + 64 s - 1 at the wave-uniform base ((pos - r)/6 + 144 m) mod 864 of sub-ring
+// r = pos mod 6: one lane-contiguous, conflict-free ds_read_b64 per slot and frame.  The plane overwrites the 48.4 KB window in
+// place (workgroup barriers between the last read of x and the first write of P), so three workgroups (24 waves) still fit a CU.
+//
+// A candidate is demodulated in two parts: first slot 0 (softbits 0..63: both sync words), the carrier phase and nbadsync;
+// then slots 1 and 2, the normalisation and the LLR row.  In blocked staging (no LLR row outlives its channel block) a candidate
+// the index stage will drop (nbadsync > threshold) stops after part one; with the LLR store retained every candidate is
+// demodulated in full.  Softbit u lives in lane u % 64 of slot u / 64.
 // From there the two 144-term sums (softbits_kernel.cuh:186-194) are one per-lane add over the three slots plus a
 // single cross-lane reduction carrying both sums (sum_reduction.cuh:14-44 replaced by two interleaved DPP chains).
 // The phase rotation uses conj(s)/|s| instead of atan2f + sincosf (same unit vector to ~1 ulp); the
@@ -40,10 +47,25 @@ constexpr int kSbWaves = kSbThreads / 64;
 constexpr int kGroup = 6;                                  // samples per half-bit group
 constexpr int kGroups = kFrameSamples / kGroup;            // 144
 constexpr int kSlots = (kGroups + 63) / 64;                // 3
-// The window is a ring of exactly six frames.  LDS carries one more frame (+ one run of samples) behind it, so a
-// folded frame starting anywhere in the ring is 864 CONTIGUOUS samples: its byte address is a wave-uniform frame base
-// (scalar arithmetic) plus a per-lane constant - no per-lane wrap arithmetic in the fold.  48.4 KB, three workgroups per CU.
+// The mixed window is a ring of exactly six frames.  LDS carries one more frame (+ one run of samples) behind it, so a frame
+// starting anywhere in the ring is 864 CONTIGUOUS samples (the side values below) and a filter run never wraps.
 constexpr int kRingPad = kFrameSamples + kGroup - 1;
+constexpr int kWindowLds = kWindowSamples + kRingPad + 3;  // float2 entries of the LDS buffer (48.4 KB)
+
+// The filtered plane, in the same buffer: sub-ring r (r = 0..5) holds P[6 k + r] at entry r * kPlaneStride + k, k < 864, and
+// repeats its first kPlanePad entries behind it, so groups 0..142 of a folded frame starting at any k are contiguous.
+constexpr int kPlaneRing = kWindowSamples / kGroup;        // 864
+constexpr int kPlanePad = kGroups - 2;                     // 142: groups 0..142 come from P (143 wraps into softbit 0)
+// 1009 (not 1006): the eleven-output runs of the plane build then write with at most 2-way bank conflicts (1010: 6-way)
+constexpr int kPlaneStride = 1009;
+static_assert(kPlaneStride >= kPlaneRing + kPlanePad, "sub-ring and its wrap pad");
+static_assert(kGroup * kPlaneStride <= kWindowLds, "the plane fits the window's LDS");
+// P build: thread t filters outputs 11 t .. 11 t + 10 (an odd run: the 88-byte lane stride of its x reads is conflict-free)
+constexpr int kPlaneRun = 11;
+static_assert(kPlaneRun * kSbThreads >= kWindowSamples, "one run per thread covers the ring");
+static_assert((kWindowSamples + kPlaneRun - 1) / kPlaneRun * kPlaneRun - kWindowSamples <= kGroup * kPlanePad,
+              "the last run's outputs past the ring land on wrap-pad entries");
+constexpr int kSideValues = 5;                             // u2[0], u1[143], u1[6], u2[56], u1[62]
 
 struct SoftbitsArgs
 {
@@ -55,131 +77,46 @@ struct SoftbitsArgs
 };
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef const volatile __attribute__((address_space(3))) v2f* lds_v2f_ptr;  // volatile: adjacent reads stay single ds_read_b64
 
-constexpr int kDppWaveShr1 = 0x138;  // lane l <- lane l-1 across the whole wave (GFX9 DPP)
-
-template<int kCtrl>
-__device__ __forceinline__ float dpp_add(float v)
+__device__ __forceinline__ v2f fma2(v2f x, float w, v2f acc)
 {
-    return f32_add(v, dpp_f32<kCtrl>(v));
+    return v2f{fmaf(x.x, w, acc.x), fmaf(x.y, w, acc.y)};
 }
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef const volatile __attribute__((address_space(3))) v2f* lds_v2f_ptr;
-typedef const volatile __attribute__((address_space(3))) v4f* lds_v4f_ptr;
+__device__ __forceinline__ v2f readlane2(v2f v, int lane)
+{
+    return v2f{readlane_f32(v.x, lane), readlane_f32(v.y, lane)};
+}
 
-// Fold of the averaged frames (softbits_kernel.cuh:59-82) for the slots named in kSlotMask.
-// A lane reads its group's six samples (48 B).  With ds_read_b64 the 48-byte lane stride makes lanes l and l + 16 of a
-// 32-lane access group share a bank pair (6*16 = 0 mod 32): a 2-way conflict on every read.  ds_read_b128 services 16 lanes
-// per cycle, and at this stride their sixteen 16-byte pieces tile all 64 banks exactly: conflict-free, 4 cycles per TWO
-// samples.  It needs 16-byte alignment, which depends only on the parity of the candidate position (wave-uniform; group
-// offsets 6g and frame offsets 864m are even): even -> three b128; odd -> b64, two b128, b64.  volatile keeps the compiler
-// from re-merging.  Frame 0 is part of every pattern (msk_context.cuh:231-238): its samples ARE the initial sums.
+// bit 8 p + m: frame m takes part in pattern p (kPatternMask as one word, for a per-lane pattern)
+constexpr uint64_t pattern_bits()
+{
+    uint64_t b = 0;
+    for(int p = 0; p < kScanDepthMax; p++)
+        for(int m = 0; m < kPatternBits; m++)
+            if(kPatternMask[p][m]) b |= uint64_t{1} << (8 * p + m);
+    return b;
+}
+constexpr uint64_t kPatternWord = pattern_bits();
+
+// Fold of the filtered plane over the frames of pattern p (softbits_kernel.cuh:59-82 after the filter) for the slots in kSlotMask.
+// pbytes = this candidate's sub-ring, q = its base entry; frame m starts 144 m entries further round the 864-entry sub-ring.
+// Frame 0 is part of every pattern (msk_context.cuh:231-238): its values ARE the initial sums.
 template<int kSlotMask>
-__device__ __forceinline__ void fold_frames(v2f (&acc)[kSlots][kGroup], const char* xbytes, const uint32_t (&lane8)[kSlots], uint32_t pos, int p)
+__device__ __forceinline__ void fold_plane(v2f (&f)[kSlots], const char* pbytes, const uint32_t (&lane_g8)[kSlots], uint32_t q, int p)
 {
-#ifdef MSK144_LISTING_EVEN_ONLY
-    const bool pos_even = true;  // tools/phase_stamps.py prices ONE of the two alignment paths of a listing (never a run build)
-#else
-    const bool pos_even = (pos & 1u) == 0u;
-#endif
-    if(pos_even)
+#pragma unroll
+    for(int s = 0; s < kSlots; s++)
+        if((kSlotMask >> s) & 1) f[s] = *(lds_v2f_ptr)(pbytes + (lane_g8[s] + q * 8u));
+    for(int m = 1; m < kPatternBits; m++)
     {
+        if(!kPatternMask[p][m]) continue;  // wave-uniform
+        uint32_t b = q + static_cast<uint32_t>(kGroups * m);
+        if(b >= static_cast<uint32_t>(kPlaneRing)) b -= kPlaneRing;
 #pragma unroll
         for(int s = 0; s < kSlots; s++)
-        {
-            if(!((kSlotMask >> s) & 1)) continue;
-            lds_v4f_ptr q = (lds_v4f_ptr)(xbytes + (lane8[s] + pos * 8u));
-            const v4f q0 = q[0], q1 = q[1], q2 = q[2];
-            acc[s][0] = v2f{q0.x, q0.y};
-            acc[s][1] = v2f{q0.z, q0.w};
-            acc[s][2] = v2f{q1.x, q1.y};
-            acc[s][3] = v2f{q1.z, q1.w};
-            acc[s][4] = v2f{q2.x, q2.y};
-            acc[s][5] = v2f{q2.z, q2.w};
-        }
-        for(int m = 1; m < kPatternBits; m++)
-        {
-            if(!kPatternMask[p][m]) continue;  // wave-uniform
-            uint32_t fb = pos + static_cast<uint32_t>(kFrameSamples * m);  // frame base in the ring: scalar
-            if(fb >= static_cast<uint32_t>(kWindowSamples)) fb -= kWindowSamples;
-#pragma unroll
-            for(int s = 0; s < kSlots; s++)
-            {
-                if(!((kSlotMask >> s) & 1)) continue;
-                lds_v4f_ptr q = (lds_v4f_ptr)(xbytes + (lane8[s] + fb * 8u));
-                const v4f q0 = q[0], q1 = q[1], q2 = q[2];
-                acc[s][0] += v2f{q0.x, q0.y};
-                acc[s][1] += v2f{q0.z, q0.w};
-                acc[s][2] += v2f{q1.x, q1.y};
-                acc[s][3] += v2f{q1.z, q1.w};
-                acc[s][4] += v2f{q2.x, q2.y};
-                acc[s][5] += v2f{q2.z, q2.w};
-            }
-        }
-    }
-    else
-    {
-#pragma unroll
-        for(int s = 0; s < kSlots; s++)
-        {
-            if(!((kSlotMask >> s) & 1)) continue;
-            const uint32_t i8 = lane8[s] + pos * 8u;
-            lds_v2f_ptr r = (lds_v2f_ptr)(xbytes + i8);
-            lds_v4f_ptr q = (lds_v4f_ptr)(xbytes + i8 + 8);
-            acc[s][0] = r[0];
-            const v4f q0 = q[0], q1 = q[1];
-            acc[s][5] = r[5];
-            acc[s][1] = v2f{q0.x, q0.y};
-            acc[s][2] = v2f{q0.z, q0.w};
-            acc[s][3] = v2f{q1.x, q1.y};
-            acc[s][4] = v2f{q1.z, q1.w};
-        }
-        for(int m = 1; m < kPatternBits; m++)
-        {
-            if(!kPatternMask[p][m]) continue;  // wave-uniform
-            uint32_t fb = pos + static_cast<uint32_t>(kFrameSamples * m);
-            if(fb >= static_cast<uint32_t>(kWindowSamples)) fb -= kWindowSamples;
-#pragma unroll
-            for(int s = 0; s < kSlots; s++)
-            {
-                if(!((kSlotMask >> s) & 1)) continue;
-                const uint32_t i8 = lane8[s] + fb * 8u;
-                lds_v2f_ptr r = (lds_v2f_ptr)(xbytes + i8);
-                lds_v4f_ptr q = (lds_v4f_ptr)(xbytes + i8 + 8);
-                const v2f x0 = r[0];
-                const v4f q0 = q[0], q1 = q[1];
-                const v2f x5 = r[5];
-                acc[s][0] += x0;
-                acc[s][1] += v2f{q0.x, q0.y};
-                acc[s][2] += v2f{q0.z, q0.w};
-                acc[s][3] += v2f{q1.x, q1.y};
-                acc[s][4] += v2f{q1.z, q1.w};
-                acc[s][5] += x5;
-            }
-        }
-    }
-}
-
-// Matched filter on the folded complex samples of one slot (softbits_kernel.cuh:157-180 before the rotation of :146-153).
-// The rotation is the same for every sample of the frame, so it commutes with the tap sums: filter the folded complex samples
-// first (two real FMAs per sample and pulse half) and rotate the two complex sums of a group afterwards - 28 instead of 36
-// multiply-adds per group.  Same linear form as rotating every sample first, associated differently (~1e-7 relative).
-// pp[0] = sin 0 = 0 and pp[6] = sin pi/2 = 1 exactly (checked at create): the first tap of u1 vanishes, u2's is the sample.
-__device__ __forceinline__ void filter_group(const v2f (&x)[kGroup], const float (&pp)[12], v2f& u1, v2f& u2)
-{
-    u1 = x[1] * pp[1];
-    u2 = x[0];
-#pragma unroll
-    for(int t = 1; t < kGroup; t++)
-    {
-        if(t > 1)
-        {
-            u1.x = fmaf(x[t].x, pp[t], u1.x);
-            u1.y = fmaf(x[t].y, pp[t], u1.y);
-        }
-        u2.x = fmaf(x[t].x, pp[kGroup + t], u2.x);
-        u2.y = fmaf(x[t].y, pp[kGroup + t], u2.y);
+            if((kSlotMask >> s) & 1) f[s] += *(lds_v2f_ptr)(pbytes + (lane_g8[s] + b * 8u));
     }
 }
 
@@ -190,7 +127,8 @@ __device__ __forceinline__ void filter_group(const v2f (&x)[kGroup], const float
 template<bool kGateEarly, bool kHandOver>
 __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float2 s_x[kWindowSamples + kRingPad + 3];
+    __shared__ __attribute__((aligned(16))) float2 s_x[kWindowLds];
+    static_assert(sizeof(s_x) <= 53248, "three workgroups per CU");
 
     const int xcd = blockIdx.x & 7;
     const int tile = xcd * a.tiles_per_xcd + (blockIdx.x >> 3);
@@ -246,6 +184,129 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
     uint64_t st_part1 = 0, st_part2 = 0, st_n2 = 0;  // wave 0: cycles in part one / part two of its candidates, part-two runs
 #endif
 
+    float pp[12];
+#pragma unroll
+    for(int i = 0; i < 12; i++) pp[i] = a.tpl.pp[i];
+    const char* __restrict__ xbytes = reinterpret_cast<const char*>(s_x);
+
+    // ---- side values: the five half-pulse sums of each of this wave's candidates that P cannot give ----
+    // Lane j = i + 8 v: candidate wave + 8 i (pattern i), value v = u2[0], u1[143], u1[6], u2[56], u1[62] of its folded frame, folded
+    // and filtered exactly as a whole group's fold + matched filter would be (same frames in the same order, same operations).
+    // pp[0] = sin 0 = 0 and pp[6] = sin pi/2 = 1 exactly (checked at create): u1 has no tap on sample 0, u2's is the sample.
+    v2f side = v2f{0.0f, 0.0f};
+    {
+        const int si = lane & 7, sv = lane >> 3;
+        const uint32_t spos_raw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (wave + kSbWaves * si), static_cast<int>(pos_of_lane)));
+        if(sv < kSideValues && si < D)
+        {
+            const uint32_t spos = spos_raw >= static_cast<uint32_t>(kWindowSamples) ? spos_raw - kWindowSamples : spos_raw;
+            const bool rising = sv == 0 || sv == 3;  // u2: taps pp[6..11]; else u1: taps pp[0..5]
+            const uint32_t group = sv == 0 ? 0u : sv == 1 ? static_cast<uint32_t>(kGroups - 1) : sv == 2 ? 6u : sv == 3 ? 56u : 62u;
+            const uint32_t mbits = static_cast<uint32_t>(kPatternWord >> (8 * si));
+            v2f acc[kGroup];
+#pragma unroll
+            for(int m = 0; m < kPatternBits; m++)
+            {
+                if(m > 0 && !((mbits >> m) & 1u)) continue;  // per lane; frame 0 is in every pattern
+                uint32_t fb = spos + static_cast<uint32_t>(kFrameSamples * m);
+                if(fb >= static_cast<uint32_t>(kWindowSamples)) fb -= kWindowSamples;
+                lds_v2f_ptr xr = (lds_v2f_ptr)(xbytes + (fb + kGroup * group) * 8u);
+#pragma unroll
+                for(int t = 0; t < kGroup; t++)
+                {
+                    const v2f xt = xr[t];
+                    acc[t] = m == 0 ? xt : acc[t] + xt;
+                }
+            }
+            if(rising)
+            {
+                side = acc[0];
+#pragma unroll
+                for(int t = 1; t < kGroup; t++) side = fma2(acc[t], pp[kGroup + t], side);
+            }
+            else
+            {
+                side = acc[1] * pp[1];
+#pragma unroll
+                for(int t = 2; t < kGroup; t++) side = fma2(acc[t], pp[t], side);
+            }
+        }
+    }
+
+    // Per candidate i only two sums are needed: lane i gets W = u1[143] + u2[0] (softbit 0) and lane 8 + i the sync words' edge
+    // term s7 (u1[6] + u1[62]) - i s0 (u2[0] + u2[56]) of the phase sum; the candidate loop reads them with four readlanes.
+    {
+        const v2f a8 = v2f{__shfl(side.x, lane + 8), __shfl(side.y, lane + 8)};     // lane i: u1[143]; lane 8 + i: u1[6]
+        const v2f a16 = v2f{__shfl(side.x, lane + 16), __shfl(side.y, lane + 16)};  // lane 8 + i: u2[56]
+        const v2f a24 = v2f{__shfl(side.x, lane + 24), __shfl(side.y, lane + 24)};  // lane 8 + i: u1[62]
+        const v2f m8 = v2f{__shfl(side.x, lane - 8), __shfl(side.y, lane - 8)};     // lane 8 + i: u2[0]
+        constexpr float s0 = static_cast<float>(kSync8Pm[0]), s7 = static_cast<float>(kSync8Pm[7]);
+        const v2f edge = v2f{s7 * (a8.x + a24.x) + s0 * (m8.y + a16.y), s7 * (a8.y + a24.y) - s0 * (m8.x + a16.x)};
+        side = lane < 8 ? a8 + side : edge;
+    }
+
+    // ---- P build: thread t filters outputs n = 11 t .. 11 t + 10 of the ring from x[n + 1 .. n + 11] (softbits_kernel.cuh:157-180
+    // before the rotation and the fold), held in registers across the barrier, then writes them over x ----
+    {
+        const uint32_t n0 = static_cast<uint32_t>(tid) * kPlaneRun;
+        v2f pv[kPlaneRun];
+        if(n0 < static_cast<uint32_t>(kWindowSamples))
+        {
+            lds_v2f_ptr xr = (lds_v2f_ptr)(xbytes + (n0 + 1u) * 8u);  // x[n0 + 1 + k]: at most x[5202], inside the ring pad
+            v2f w[kPlaneRun + 2 * kGroup - 2];
+#pragma unroll
+            for(int k = 0; k < kPlaneRun + 2 * kGroup - 2; k++) w[k] = xr[k];
+#pragma unroll
+            for(int j = 0; j < kPlaneRun; j++)
+            {
+                // u1 = taps 1..5 on x[n+1..n+5], u2 = taps 6..11 on x[n+6..n+11] (pp[6] = 1): the half-pulse sums of the old
+                // per-group filter, added
+                v2f u1 = w[j] * pp[1];
+#pragma unroll
+                for(int t = 2; t < kGroup; t++) u1 = fma2(w[j + t - 1], pp[t], u1);
+                v2f u2 = w[j + kGroup - 1];
+#pragma unroll
+                for(int t = 1; t < kGroup; t++) u2 = fma2(w[j + kGroup - 1 + t], pp[kGroup + t], u2);
+                pv[j] = u1 + u2;
+            }
+        }
+        __syncthreads();  // every read of x (side values and plane build) is done
+        // The last run (thread 471) ends 8 outputs past the ring: P[5184 + j] is filtered from the ring pad, x[5185 + ...] =
+        // x[1 + ...], so it IS P[j] and lands on P[j]'s wrap-pad entry (sub-ring j mod 6, entry 864 + j / 6) with the same bits.
+        if(n0 < static_cast<uint32_t>(kWindowSamples))
+        {
+            const uint32_t r0 = n0 % kGroup, k0 = n0 / kGroup;
+            uint32_t r = r0, k = k0;
+#pragma unroll
+            for(int j = 0; j < kPlaneRun; j++)
+            {
+                s_x[r * kPlaneStride + k] = make_float2(pv[j].x, pv[j].y);
+                if(++r == static_cast<uint32_t>(kGroup))
+                {
+                    r = 0;
+                    ++k;
+                }
+            }
+            if(n0 < static_cast<uint32_t>(kGroup * kPlanePad))  // waves 0 and 1 only: the wrap pad
+            {
+                r = r0;
+                k = k0;
+#pragma unroll
+                for(int j = 0; j < kPlaneRun; j++)
+                {
+                    if(k < static_cast<uint32_t>(kPlanePad)) s_x[r * kPlaneStride + k + kPlaneRing] = make_float2(pv[j].x, pv[j].y);
+                    if(++r == static_cast<uint32_t>(kGroup))
+                    {
+                        r = 0;
+                        ++k;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    MSK144_STAMP(7);
+
     // Slots that fold the same frames.  The scan walks 5376 positions of a 5184-sample ring, so positions p and p + 5184 are one
     // place (2.9 % of the slots of a noise window hold such a pair); masks 111111 and 100100 moreover sum the same frames at pos
     // and pos + 864 (+ 2592), so the eight slots of those patterns are mostly the copies of two or three peaks, one per period
@@ -268,51 +329,35 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         same_frames = __ballot(lane < ncand && r == mine);
     }
 
-    // Phase estimate = sum over the two sync words of folded sample x conj(template) (softbits_kernel.cuh:88-137).  The first
-    // sync word covers samples 0..41 = groups 0..6 (lanes 0..6 of slot 0), the second samples 336..377 = groups 56..62.
-    // Inside a group the template is one half of the half-sine pulse on each rail, signed by a sync bit
-    // (msk_context.cuh:188-196: I carries bits 1,1,3,3,5,5,7 and Q bits 0,2,2,4,4,6,6 over the seven groups; even groups
-    // have the rising half on I and the falling half on Q, odd groups the other way round) - so a lane's share of the sum
-    // is a signed combination of the two matched-filter sums u1 = sum x[t] pp[t], u2 = sum x[t] pp[6+t] of its group, which
-    // the demodulator needs anyway:   even: (sI u1.x + sQ u2.y,  sI u1.y - sQ u2.x)    odd: (sI u2.x + sQ u1.y,  sI u2.y - sQ u1.x)
-    // Four per-lane coefficients (0 outside the sync groups) replace the 36 multiply-adds and six table loads per candidate.
-    const int cb_group = (lane < 7) ? lane : (lane >= 56 && lane < 63) ? lane - 56 : -1;
-    float k_u1x = 0.0f, k_u2x = 0.0f, k_u1y = 0.0f, k_u2y = 0.0f;  // pr = k_u1x u1.x + k_u2x u2.x + k_u1y u1.y + k_u2y u2.y
+    // Phase estimate = sum over the two sync words of folded sample x conj(template) (softbits_kernel.cuh:88-137).  Inside a group
+    // the template is one half of the half-sine pulse on each rail, signed by a sync bit (msk_context.cuh:188-196: I carries bits
+    // 1,1,3,3,5,5,7 and Q bits 0,2,2,4,4,6,6 over the seven groups), so the sum over the first sync word is
+    //     s1 F(0) + s3 F(2) + s5 F(4) + s7 u1[6] - i (s0 u2[0] + s2 F(1) + s4 F(3) + s6 F(5))
+    // and the second the same at groups 56..62.  F(u-1) sits in lane u: lanes 1..6 and 57..62 take it with their own sync bit,
+    // on the real part in odd lanes (k_x) and as -i F in even ones (k_y); the four edge values are added after the lane sum.
+    const int sync_lane = (lane >= 1 && lane < 7) ? lane : (lane >= kSecondSyncBit + 1 && lane < kSecondSyncBit + 7) ? lane - kSecondSyncBit : -1;
+    float k_x = 0.0f, k_y = 0.0f;  // pr = k_x F.x + k_y F.y, pi = k_x F.y - k_y F.x
 #pragma unroll
-    for(int g = 0; g < 7; g++)
+    for(int k = 1; k < 7; k++)
     {
-        if(cb_group == g)
+        if(sync_lane == k)
         {
-            const float s_i = static_cast<float>(kSync8Pm[2 * (g / 2) + 1]);
-            const float s_q = static_cast<float>(kSync8Pm[2 * ((g + 1) / 2)]);
-            if(g % 2 == 0)
-            {
-                k_u1x = s_i;
-                k_u2y = s_q;
-            }
-            else
-            {
-                k_u2x = s_i;
-                k_u1y = s_q;
-            }
+            if(k % 2 == 1) k_x = static_cast<float>(kSync8Pm[k]);
+            else k_y = static_cast<float>(kSync8Pm[k]);
         }
     }
     const bool odd = (lane & 1) != 0;
-    float pp[12];
-#pragma unroll
-    for(int i = 0; i < 12; i++) pp[i] = a.tpl.pp[i];
 
-    const char* __restrict__ xbytes = reinterpret_cast<const char*>(s_x);
-
-    // byte offset of this lane's group inside a frame, per slot.  Slot 2 only has groups 128..143: lanes >= 16 re-read
-    // group 143 (harmless, their results are discarded) so the loop stays convergent.
-    uint32_t lane8[kSlots];
+    // byte offset inside a sub-ring of the group this lane reads per slot: softbit u = lane + 64 s needs F(u - 1).  Lane 0 of slot 0
+    // (softbit 0 wraps: it takes the side values) and lanes >= 16 of slot 2 (no softbit) re-read a neighbouring group so the reads
+    // stay in the sub-ring and convergent; their values are replaced or discarded.
+    uint32_t lane_g8[kSlots];
 #pragma unroll
     for(int s = 0; s < kSlots; s++)
     {
-        const int last = kGroups - 64 * s - 1;
-        const int l = lane < last ? lane : last;
-        lane8[s] = static_cast<uint32_t>(kGroup * (l + 64 * s)) * 8u;
+        int g = lane + 64 * s - 1;
+        g = g < 0 ? 0 : g > kPlanePad ? kPlanePad : g;
+        lane_g8[s] = static_cast<uint32_t>(g) * 8u;
     }
     // sync bit this lane checks (softbits 0..7 and 56..63), as +-1; 0 = none
     int sync_pm = 0;
@@ -341,19 +386,19 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         const uint64_t st_t0 = (stamp_row_ && tid < 64) ? stamp_now() : 0;
 #endif
 
-        // ---- part 1: everything the sync check needs.  The sync softbits 0..7 and 56..63 live in slot 0; softbit 0 also takes
-        // the partial sum that starts in group 143 (slot 2, lane 15): the frame is circular.  Slot 1 waits. ----
-        v2f acc[kSlots][kGroup];  // (re, im) pairs
-        v2f u1[kSlots], u2[kSlots];
-        fold_frames<0b101>(acc, xbytes, lane8, pos, p);
-        filter_group(acc[0], pp, u1[0], u2[0]);
-        filter_group(acc[2], pp, u1[2], u2[2]);
+        // ---- part 1: slot 0 (softbits 0..63, both sync words), the carrier phase and the sync check.  Slots 1 and 2 wait. ----
+        const uint32_t q = pos / kGroup;
+        const char* pbytes = xbytes + (pos - q * kGroup) * (kPlaneStride * 8u);  // sub-ring pos mod 6
+        v2f f[kSlots];
+        fold_plane<0b001>(f, pbytes, lane_g8, q, p);
+        const v2f wrap = readlane2(side, p), edge = readlane2(side, kSbWaves + p);  // this candidate's side sums
 
         // carrier phase from the two sync words (softbits_kernel.cuh:88-137): sum c3[k]*conj(cb[k])
-        float pr = fmaf(k_u2y, u2[0].y, fmaf(k_u1y, u1[0].y, fmaf(k_u2x, u2[0].x, k_u1x * u1[0].x)));
-        float pi = fmaf(-k_u2y, u2[0].x, fmaf(-k_u1y, u1[0].x, fmaf(k_u2x, u2[0].y, k_u1x * u1[0].y)));
+        float pr = fmaf(k_y, f[0].y, k_x * f[0].x);
+        float pi = fmaf(-k_y, f[0].x, k_x * f[0].y);
         wave_sum2_f32(pr, pi);
-        const float sre = pr, sim = pi;
+        const float sre = pr + edge.x;
+        const float sim = pi + edge.y;
         // cfac = conj(exp(i*atan2(im,re))) = (re, -im)/|s|
         float cr = 1.0f, ci = 0.0f;
         {
@@ -371,24 +416,13 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
             }
         }
 
-        // de-rotate the filtered sums (softbits_kernel.cuh:146-153)
-        // va = plane that STARTS a softbit in this lane (even group -> I bit u+1 -> real part,
-        // odd group -> Q bit u+1 -> imaginary part); vb = plane that FINISHES softbit u = this group.
-        // re = fr*cr - fi*ci, im = fr*ci + fi*cr: pick the coefficient pair per lane once instead of
-        // selecting per sample.
-        const float a_r = odd ? ci : cr, a_i = odd ? cr : -ci;   // va = fr*a_r + fi*a_i
-        const float b_r = odd ? cr : ci, b_i = odd ? -ci : cr;   // vb = fr*b_r + fi*b_i
-        float start[kSlots], soft[kSlots];
-        start[0] = fmaf(u1[0].y, a_i, u1[0].x * a_r);
-        start[2] = fmaf(u1[2].y, a_i, u1[2].x * a_r);
+        // de-rotate (softbits_kernel.cuh:146-153): softbit u = Re(rot F) for odd u (I bit), Im(rot F) for even u (Q bit), rot = cr + i ci.
+        // re = fr*cr - fi*ci, im = fr*ci + fi*cr: pick the coefficient pair per lane once instead of selecting per value.
+        const float b_r = odd ? cr : ci, b_i = odd ? -ci : cr;
+        float soft[kSlots];
         {
-            // incoming partial sum from group h-1: lane-1 of the same slot; group 0 takes group 143 (slot 2, lane 15)
-            float in = dpp_f32<kDppWaveShr1>(start[0]);
-            const float edge = readlane_f32(start[kSlots - 1], kGroups - 64 * (kSlots - 1) - 1);
-            // lane 0 <- edge (one instruction instead of v_mov + v_cndmask).  `edge` comes out of a v_readlane: on the gfx940 family a
-            // VALU may read an SGPR written by a VALU only two wait states later, and the compiler does not pad asm statements
-            asm("s_nop 1\n\tv_writelane_b32 %0, %1, 0" : "+v"(in) : "s"(edge));
-            soft[0] = in + fmaf(u2[0].y, b_i, u2[0].x * b_r);
+            const v2f f0 = lane == 0 ? wrap : f[0];  // softbit 0: group 143 of the folded frame wraps into group 0
+            soft[0] = fmaf(f0.y, b_i, f0.x * b_r);
         }
 
         // ---- sync-word disagreements (softbits_kernel.cuh:214-241): bits 0..7 and 56..63 ----
@@ -402,20 +436,10 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
 #endif
         if(kGateEarly && nbad > a.st.nbadsync_threshold) continue;  // wave-uniform: the index stage drops this candidate
 
-        // ---- part 2: the middle slot and the rest of the demodulation ----
-        fold_frames<0b010>(acc, xbytes, lane8, pos, p);
-        filter_group(acc[1], pp, u1[1], u2[1]);
-        start[1] = fmaf(u1[1].y, a_i, u1[1].x * a_r);
-#pragma unroll
-        for(int s = 1; s < kSlots; s++)
-        {
-            // lane 0 takes lane 63 of the previous slot
-            float in = dpp_f32<kDppWaveShr1>(start[s]);
-            const float edge = readlane_f32(start[s - 1], 63);
-            asm("s_nop 1\n\tv_writelane_b32 %0, %1, 0" : "+v"(in) : "s"(edge));
-            const float sb = in + fmaf(u2[s].y, b_i, u2[s].x * b_r);
-            soft[s] = (s == kSlots - 1 && lane >= kGroups - 64 * (kSlots - 1)) ? 0.0f : sb;
-        }
+        // ---- part 2: slots 1 and 2 and the rest of the demodulation ----
+        fold_plane<0b110>(f, pbytes, lane_g8, q, p);
+        soft[1] = fmaf(f[1].y, b_i, f[1].x * b_r);
+        soft[2] = lane < kGroups - 64 * (kSlots - 1) ? fmaf(f[2].y, b_i, f[2].x * b_r) : 0.0f;
 
         // ---- normalisation (softbits_kernel.cuh:186-201) ----
         // sum and sum of squares of the 144 softbits: per lane over its three slots first, then ONE cross-lane reduction
@@ -426,10 +450,10 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         float sum_sav, sum_s2av;
         {
             float t = f32_add(f32_add(soft[0], soft[1]), soft[2]);
-            float q = fmaf(soft[2], soft[2], fmaf(soft[1], soft[1], f32_mul(soft[0], soft[0])));
-            wave_sum2_f32(t, q);
+            float q2 = fmaf(soft[2], soft[2], fmaf(soft[1], soft[1], f32_mul(soft[0], soft[0])));
+            wave_sum2_f32(t, q2);
             sum_sav = t;
-            sum_s2av = q;
+            sum_s2av = q2;
         }
         // sav, s2av, ssig and the scale are wave-uniform numbers formed from two 144-term sums that already differ from the
         // reference's by ~1e-7 relative (different association): rounding them correctly on top (a Markstein division by 144,
