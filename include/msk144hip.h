@@ -304,14 +304,15 @@ int msk144_clock_probe(msk144_handle* h, int32_t spin_us, float* shader_mhz);
  *   Filter:       a real low-pass h[0..L), L = K x P, 1 <= K <= 64, at the upsampled rate Q x Fs = P x 12000, supplied by the
  *                 caller (num_taps = K x D for Q = 1).  The default design (K = 16, a Kaiser-windowed sinc: flat within 0.1 dB to
  *                 4 kHz, >= 60 dB down from 8 kHz) sums to Q, so that every branch h[r], h[r + Q], ... has about unit DC gain; it is
- *                 msk144host_wideband_taps_rate(rate, K) in libmsk144host.so (msk144host_wideband_taps(D, K) for Q = 1, the same
- *                 taps), the taps msk144hipdecoder uses.
+ *                 msk144host_wideband_taps_rate(rate, K) in libmsk144host.so (msk144host_wideband_taps(D, K) is that call at
+ *                 rate = D x 12000), the taps msk144hipdecoder uses.
  *   Output:       y_c[m] = e^{-j2pi f_c m / 12000} . sum_{k<L} (h[k] e^{+j2pi f_c k / Fs}) . x[mD - k]
  *                 - mix, filter and decimate by D - with m the 64-bit output index from the first sample of the stream,
  *                 x[n < 0] = 0, and the phases reduced in integers, (f_c m) mod 12000 and (f_c k) mod Fs, so they do not drift.
  *                 For Q > 1, with n_m = floor(m P / Q) and r_m = (m P) mod Q - mix at Fs, upsample by Q, filter, keep every P-th:
  *                   y_c[m] = e^{-j2pi ((f_c n_m) mod Fs)/Fs} . sum_{k >= 0, r_m + kQ < L} h[r_m + kQ] e^{+j2pi ((f_c k) mod Fs)/Fs} x[n_m - k]
  *                 which is the formula above for Q = 1, as (f_c m D) mod (12000 D) = D ((f_c m) mod 12000); phases in 64-bit integers.
+ *                 The library computes every rate in this form: Q polyphase branches, one of them at Q = 1.
  *                 I and Q are q = clamp(rint(128 . gain . y), -128, 127) each (default gain 100, the csdr gain_ff stage); a
  *                 component whose rounded value lies outside [-128, 127] counts as clipped.  f32 arithmetic on the device.
  *                 0 < gain <= 1e36, so that 128 . gain is finite in f32 (an infinite scale would turn an exact 0 into NaN).

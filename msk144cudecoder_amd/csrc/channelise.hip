@@ -1,28 +1,30 @@
-// channelise: the wideband down-converter bank (msk144_push_wideband).
+// channelise: the wideband down-converter bank (msk144_push_wideband), one kernel for every rate Fs = 12000 P/Q, Q >= 1.
 //
-// For channel c with offset f_c and the prototype low-pass h[0..L), L = K*D, every output sample of a push is
-//     y_c[m] = e^{-j2pi (f_c m mod 12000)/12000} * sum_k G[c][k] x[mD - k],   G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs}
-// (include/msk144hip.h).  The sum is a complex GEMM over a Hankel view of the input, computed only at the output rate.  With
-// k = p + D*q (phase p < D, q < K), x[mD - k] = xp[p][m - q] where xp[p][n] = x[nD - p]: stored phase by phase in LDS, the
-// operand a wave reads for one tap is 32 consecutive floats, so the Hankel view costs no bank conflicts.
+// For channel c with offset f_c and the prototype low-pass h[0..L), L = K*P taps at the upsampled rate Q Fs, every output sample is
+//     y_c[m] = e^{-j2pi (f_c n_m mod Fs)/Fs} * sum_k h[r_m + kQ] e^{+j2pi (f_c k mod Fs)/Fs} x[n_m - k],   n_m = floor(mP/Q), r_m = mP mod Q
+// (include/msk144hip.h).  Output m = mr + Q a reads n_m = n0 + a P with n0 = floor(mr P/Q) and the taps h[r + kQ], r = mr P mod Q,
+// k < K_r = ceil((L - r)/Q): each of the Q residues mr is a decimate-by-P branch of its own (blockIdx.z = mr, WidebandBranch) whose
+// outputs land Q apart in the same staging.  An integer rate Fs = D x 12000 is the case Q = 1: one branch with r = 0, n0 = 0 and all
+// L taps, D = P.
 //
-// Tiling: one workgroup = 4 waves = 128 channels x 64 output samples.  Each wave owns 32 channels and two 32-sample halves of the
-// output tile and runs v_mfma_f32_32x32x2_f32 with the two k-slots of the instruction carrying the real and the imaginary part:
+// A branch is a complex GEMM over a Hankel view of the input, computed only at the output rate.  With k = p + P*q (phase p < P),
+// x[n0 + aP - k] = xp[p][a - q] where xp[p][n] = x[n0 + nP - p]: stored phase by phase in LDS, the operand a wave reads for one tap
+// is 32 consecutive floats, so the Hankel view costs no bank conflicts.  The loop walks exactly the K_r taps of the branch: phases
+// p < s carry Kq = ceil(K_r/P) taps, the others one fewer (Q = 1: every phase carries K).
+//
+// Tiling: one workgroup = 4 waves = 128 channels x 64 output samples of one branch.  Each wave owns 32 channels and two 32-sample
+// halves of the output tile and runs v_mfma_f32_32x32x2_f32 with the two k-slots of the instruction carrying the real and the
+// imaginary part:
 //     Re: A[c][0] = Re G, A[c][1] = -Im G;   Im: A[c][0] = Im G, A[c][1] = Re G;   B[0][m] = Re x, B[1][m] = Im x
 // so 4 MFMAs per tap and wave (Re/Im x two halves), accumulating in f32.  The input span of the tile is converted to f32 once,
-// 32 phases at a time, and shared by the 4 waves; the taps stream from L2 (G is stored [channel/32][p][q][32], the order the
-// loop walks, so a wave reads 256 contiguous bytes per tap) and are reused across the 64 samples of the tile.
+// 32 phases at a time, and shared by the 4 waves; the taps stream from L2 (a branch's G block is stored [channel/32][p][q][32], the
+// order the loop walks, so a wave reads 256 contiguous bytes per tap) and are reused across the 64 samples of the tile.
 //
 // Output: q = clamp(rint(128 * gain * y), -128, 127) for I and Q, written as int8 pairs straight into the hop ring's staging
 // (first push: samples 0..2591 into first_halves, 2592..5183 into hops; later pushes: hops).  A component counts as clipped when
 // its rounded value lies outside [-128, 127].
 //
-// Rational rates, Fs = 12000 P/Q with Q > 1 (channelise_rational_kernel): output m = mr + Q a reads n_m = n0 + a P with
-// n0 = floor(mr P/Q) and the taps h[r + kQ], r = mr P mod Q, k < K_r = ceil((L - r)/Q).  Each of the Q residues mr is a
-// decimate-by-P GEMM of its own, tiled as above (blockIdx.z = mr) with k = p + P q: the loop walks exactly the K_r taps of the
-// branch - phases p < s carry ceil(K_r/P) taps, the others one fewer - and the outputs land Q apart in the same staging.
-//
-// Rates above 6.144 Msps (format kSubbandFormat): both kernels run at the sub-band rate Fs/32 on the complex-f32 streams of the
+// Rates above 6.144 Msps (format kSubbandFormat): the kernel runs at the sub-band rate Fs/32 on the complex-f32 streams of the
 // analysis bank (bank.hip), each wave on the band of its 32 channel slots; see channelise_kernel.
 #include "msk144_kernels.h"
 #include "wideband_samples.h"
@@ -49,143 +51,13 @@ constexpr int kChannelRate = 12000;
 // wave stages its own band's input in its own quarter of the LDS image (kPhaseChunk/4 phases at a time), so the slots of one tile
 // may lie in four different bands; the taps, branches and loop structure are the same for every band.
 template<int FMT>
-__global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __restrict__ raw, const float2* __restrict__ G, const int32_t* __restrict__ fmod,
-                                                              const float2* __restrict__ rot, int8_t* __restrict__ first_halves, int8_t* __restrict__ hops,
-                                                              unsigned long long* __restrict__ clip_count, int channels, int D, int K, int M, int first,
-                                                              long long m_base, float scale, WidebandBands bands)
+__global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __restrict__ raw, const float2* __restrict__ G, const WidebandBranch* __restrict__ branches,
+                                                              const int32_t* __restrict__ fmod, const float2* __restrict__ rot, int8_t* __restrict__ first_halves,
+                                                              int8_t* __restrict__ hops, unsigned long long* __restrict__ clip_count, int channels, int P, int Q,
+                                                              int hist, int M, int first, long long m_base, float scale, WidebandBands bands)
 {
     __shared__ float xs[2][kPhaseChunk][kMaxSpan];
     constexpr bool kBank = FMT == kSubbandFormat;
-    constexpr int kChunk = kBank ? kPhaseChunk / 4 : kPhaseChunk;
-
-    const int L = K * D;
-    const int hist = L - 1;              // raw[0 .. hist) = the L-1 samples before this push
-    const int n_in = hist + M * D;       // samples in raw
-    const int span = kTileSamples + K - 1;
-    const int mt0 = blockIdx.x * kTileSamples;
-    const int wave = threadIdx.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const int j = lane & 31;
-    const int hsel = lane >> 5;          // k-slot of the MFMA: 0 = real part, 1 = imaginary part
-    const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
-    const bool active = cb32 * 32 < channels;
-    const float2* __restrict__ g = G + static_cast<size_t>(cb32) * L * 32 + j;
-    const int prow = kBank ? wave * kChunk : 0;  // the wave's first phase row of the LDS image
-    const void* src = raw;
-    if(kBank && active) src = static_cast<const float2*>(raw) + bands.stride * bands.wave_band[cb32];
-
-    f32x16 acc_re0 = {}, acc_im0 = {}, acc_re1 = {}, acc_im1 = {};
-
-    for(int p0 = 0; p0 < D; p0 += kChunk)
-    {
-        const int pc = min(kChunk, D - p0);
-        __syncthreads();
-        if(kBank)
-        {
-            // the image below, of the wave's own band, by the wave's own 64 lanes
-            for(int e = lane; active && e < pc * span; e += 64)
-            {
-                const int pl = e % pc;
-                const int n = e / pc;
-                const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
-                float2 v = make_float2(0.0f, 0.0f);
-                if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(src, i);
-                xs[0][prow + pl][n] = v.x;
-                xs[1][prow + pl][n] = v.y;
-            }
-        }
-        else
-        {
-            // xp[p][n] = x at buffer index (mt0 + n + 1)*D - p - 1 (output mt0 + n - (K-1), tap p); consecutive threads take
-            // consecutive phases, i.e. consecutive (descending) input samples
-            for(int e = threadIdx.x; e < pc * span; e += kThreads)
-            {
-                const int pl = e % pc;
-                const int n = e / pc;
-                const int i = (mt0 + n + 1) * D - (p0 + pl) - 1;
-                float2 v = make_float2(0.0f, 0.0f);
-                if(i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
-                xs[0][pl][n] = v.x;
-                xs[1][pl][n] = v.y;
-            }
-        }
-        __syncthreads();
-        if(!active) continue;
-        const float2* __restrict__ gp = g + static_cast<size_t>(p0) * K * 32;
-        const float* __restrict__ xrow = &xs[hsel][prow][j + K - 1];
-        const int T = pc * K;
-        float2 gnext = gp[0];
-        int pl = 0, q = 0;
-        for(int t = 0; t < T; t++)
-        {
-            const float2 gv = gnext;
-            if(t + 1 < T) gnext = gp[static_cast<size_t>(t + 1) * 32];
-            const float a_re = hsel ? -gv.y : gv.x;
-            const float a_im = hsel ? gv.x : gv.y;
-            const float* xr = xrow + pl * kMaxSpan - q;
-            const float b0 = xr[0];
-            const float b1 = xr[32];
-            acc_re0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b0, acc_re0, 0, 0, 0);
-            acc_im0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b0, acc_im0, 0, 0, 0);
-            acc_re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_re, b1, acc_re1, 0, 0, 0);
-            acc_im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a_im, b1, acc_im1, 0, 0, 0);
-            if(++q == K)
-            {
-                q = 0;
-                pl++;
-            }
-        }
-    }
-    if(!active) return;
-
-    // D[row][col]: col = lane & 31 = output sample, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel within the wave
-    unsigned int clipped = 0;
-    const int half = kHalf;
-#pragma unroll
-    for(int s = 0; s < 2; s++)
-    {
-        const int mo = mt0 + s * 32 + j;
-        if(mo >= M) continue;
-        const long long m = m_base + mo;
-        const int mm = static_cast<int>(m % kChannelRate);
-        int8_t* __restrict__ dst = hops;
-        int idx = mo;
-        if(first && mo < half) dst = first_halves;
-        else if(first) idx = mo - half;
-#pragma unroll
-        for(int r = 0; r < 16; r++)
-        {
-            const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-            if(c >= channels) continue;
-            const int ch = kBank ? bands.slot_channel[c] : c;  // the channel of slot c
-            if(ch < 0) continue;
-            const float yr = s ? acc_re1[r] : acc_re0[r];
-            const float yi = s ? acc_im1[r] : acc_im0[r];
-            const int ph = (fmod[c] * mm) % kChannelRate;
-            const float2 e = rot[ph];
-            const float vr = rintf(scale * (yr * e.x - yi * e.y));
-            const float vi = rintf(scale * (yr * e.y + yi * e.x));
-            clipped += (vr < -128.0f || vr > 127.0f) + (vi < -128.0f || vi > 127.0f);
-            char2 o;
-            o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
-            o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
-            reinterpret_cast<char2*>(dst)[static_cast<size_t>(ch) * half + idx] = o;
-        }
-    }
-    for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
-    if(lane == 0 && clipped) atomicAdd(clip_count, static_cast<unsigned long long>(clipped));
-}
-
-template<int FMT>
-__global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const void* __restrict__ raw, const float2* __restrict__ G,
-                                                                       const WidebandBranch* __restrict__ branches, const int32_t* __restrict__ fmod,
-                                                                       const float2* __restrict__ rot, int8_t* __restrict__ first_halves,
-                                                                       int8_t* __restrict__ hops, unsigned long long* __restrict__ clip_count, int channels,
-                                                                       int P, int Q, int hist, int M, int first, long long m_base, float scale,
-                                                                       WidebandBands bands)
-{
-    __shared__ float xs[2][kPhaseChunk][kMaxSpan];
-    constexpr bool kBank = FMT == kSubbandFormat;   // as in channelise_kernel
     constexpr int kChunk = kBank ? kPhaseChunk / 4 : kPhaseChunk;
 
     const int mr = blockIdx.z;
@@ -195,18 +67,23 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
     const int s_full = Kr - (Kq - 1) * P;    // phases 0 .. s_full-1 have Kq taps, the others Kq-1
     const int phases = min(P, Kr);
     const int A = M / Q;                     // outputs of this branch in the push
-    const int n_in = hist + A * P;           // samples in raw
+    const int n_in = hist + A * P;           // samples in raw: `hist` before this push, then the new ones
     const int span = kTileSamples + Kq - 1;
     const int at0 = blockIdx.x * kTileSamples;
     const int base = hist + br.n0 + (at0 - Kq + 1) * P;  // raw index of xp[0][0]
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
-    const int hsel = lane >> 5;
+    const int hsel = lane >> 5;              // k-slot of the MFMA: 0 = real part, 1 = imaginary part
     const int cb32 = blockIdx.y * (kTileChannels / 32) + wave;
     const bool active = cb32 * 32 < channels;
     const float2* __restrict__ g = G + br.g_off + static_cast<size_t>(cb32) * Kr * 32 + j;
-    const int prow = kBank ? wave * kChunk : 0;
+
+    // who stages what: all 256 threads one image of raw, or (bank) the 64 lanes of each active wave an image of the wave's own band
+    const int e0 = kBank ? lane : threadIdx.x;
+    constexpr int kStageStride = kBank ? 64 : kThreads;
+    const bool stages = !kBank || active;
+    const int prow = kBank ? wave * kChunk : 0;  // the image's first phase row in LDS
     const void* src = raw;
     if(kBank && active) src = static_cast<const float2*>(raw) + bands.stride * bands.wave_band[cb32];
 
@@ -216,32 +93,17 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
     {
         const int pc = min(kChunk, phases - p0);
         __syncthreads();
-        if(kBank)
+        // xp[p][n] = raw[base + n P - p]: output at0 + n - (Kq-1), tap p (+ P q for the q-th tap of the phase, read at n - q);
+        // consecutive threads take consecutive phases, i.e. consecutive (descending) input samples
+        for(int e = e0; stages && e < pc * span; e += kStageStride)
         {
-            for(int e = lane; active && e < pc * span; e += 64)
-            {
-                const int pl = e % pc;
-                const int n = e / pc;
-                const int i = base + n * P - (p0 + pl);
-                float2 v = make_float2(0.0f, 0.0f);
-                if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(src, i);
-                xs[0][prow + pl][n] = v.x;
-                xs[1][prow + pl][n] = v.y;
-            }
-        }
-        else
-        {
-            // xp[p][n] = raw[base + n P - p]: output at0 + n - (Kq-1), tap p (+ P q for the q-th tap of the phase, read at n - q)
-            for(int e = threadIdx.x; e < pc * span; e += kThreads)
-            {
-                const int pl = e % pc;
-                const int n = e / pc;
-                const int i = base + n * P - (p0 + pl);
-                float2 v = make_float2(0.0f, 0.0f);
-                if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(raw, i);
-                xs[0][pl][n] = v.x;
-                xs[1][pl][n] = v.y;
-            }
+            const int pl = e % pc;
+            const int n = e / pc;
+            const int i = base + n * P - (p0 + pl);
+            float2 v = make_float2(0.0f, 0.0f);
+            if(i >= 0 && i < n_in && !(first && i < hist)) v = load_sample<FMT>(src, i);
+            xs[0][prow + pl][n] = v.x;
+            xs[1][prow + pl][n] = v.y;
         }
         __syncthreads();
         if(!active) continue;
@@ -275,6 +137,7 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
     }
     if(!active) return;
 
+    // D[row][col]: col = lane & 31 = output sample, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel within the wave
     unsigned int clipped = 0;
     const int half = kHalf;
 #pragma unroll
@@ -315,41 +178,23 @@ __global__ __launch_bounds__(kThreads) void channelise_rational_kernel(const voi
 
 }  // namespace
 
-void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
-                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream,
-                       WidebandBands bands)
-{
-    const dim3 grid((M + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels);
-    const float scale = 128.0f * gain;
-    if(format == 0)
-        hipLaunchKernelGGL(channelise_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
-    else if(format == 1)
-        hipLaunchKernelGGL(channelise_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
-    else if(format == 2)
-        hipLaunchKernelGGL(channelise_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first, m_base, scale, bands);
-    else
-        hipLaunchKernelGGL(channelise_kernel<kSubbandFormat>, grid, dim3(kThreads), 0, stream, raw, G, fmod, rot, first_halves, hops, clip_count, channels, D, K, M, first,
-                           m_base, scale, bands);
-}
-
-void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
-                                int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
-                                long long m_base, float gain, hipStream_t stream, WidebandBands bands)
+void launch_channelise(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot, int8_t* first_halves,
+                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base, float gain,
+                       hipStream_t stream, WidebandBands bands)
 {
     const dim3 grid((M / Q + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels, Q);
     const float scale = 128.0f * gain;
-    if(format == 0)
-        hipLaunchKernelGGL(channelise_rational_kernel<0>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale, bands);
-    else if(format == 1)
-        hipLaunchKernelGGL(channelise_rational_kernel<1>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale, bands);
-    else if(format == 2)
-        hipLaunchKernelGGL(channelise_rational_kernel<2>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M,
-                           first, m_base, scale, bands);
-    else
-        hipLaunchKernelGGL(channelise_rational_kernel<kSubbandFormat>, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q,
-                           hist, M, first, m_base, scale, bands);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M, first, m_base,
+                           scale, bands);
+    };
+    switch(format)
+    {
+    case 0: launch(channelise_kernel<0>); break;
+    case 1: launch(channelise_kernel<1>); break;
+    case 2: launch(channelise_kernel<2>); break;
+    default: launch(channelise_kernel<kSubbandFormat>); break;
+    }
 }
 
 }  // namespace msk144

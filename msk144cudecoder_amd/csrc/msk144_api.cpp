@@ -125,8 +125,8 @@ struct msk144_handle
         size_t slot_bytes = 0;    // pinned bytes per slot: 5184*P/Q samples
         uint8_t* pinned[MSK144_SLOTS] = {};
         uint8_t* d_raw = nullptr; // history samples + the samples of one push, raw format
-        float2* d_G = nullptr;    // Q = 1: [ceil(channels/32)][D][K][32]; Q > 1: one block per branch (WidebandBranch)
-        WidebandBranch* d_branches = nullptr;  // [Q], Q > 1 only
+        float2* d_G = nullptr;    // one block per branch (WidebandBranch); Q = 1: the one block [ceil(channels/32)][D][K][32]
+        WidebandBranch* d_branches = nullptr;  // [Q]
         int32_t* d_fmod = nullptr;
         float2* d_rot = nullptr;  // [12000]
         unsigned long long* d_clip = nullptr;
@@ -377,6 +377,178 @@ void wb_release(msk144_handle* h)
 {
     h->wb.mem.release();
     h->wb = {};
+}
+
+// ---- msk144_set_wideband_ex, step by step ----
+
+// Every rule a configuration must meet (csrc/wideband.h check_config and the ones that need the handle); h1 = the bank prototype
+// above 6.144 Msps, the caller's or the default one
+int wb_validate(msk144_handle* h, const msk144_wideband_params* wp, const double* bank_taps, int32_t bank_num_taps, std::vector<double>& h1)
+{
+    if(!h || !wp) return fail(h, MSK144_EINVAL, "null argument");
+    if(h->params.read_mode != 2) return fail(h, MSK144_EINVAL, "wideband input needs an IQ handle (read_mode 2)");
+    if(wp->num_offsets != h->params.channels) return fail(h, MSK144_EINVAL, "the number of channel offsets must equal the handle's channels");
+    const std::string why = msk144wb::check_config(wp->rate_hz, wp->format, wp->taps_per_phase, wp->gain, wp->offsets_hz, wp->num_offsets);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    const bool bank = msk144wb::is_bank_rate(wp->rate_hz);
+    if(!bank && (bank_taps || bank_num_taps)) return fail(h, MSK144_EINVAL, "bank taps are only taken above 6144000 Hz (two-stage bank)");
+    if(bank && !bank_taps) h1 = msk144wb::design_bank_taps(wp->rate_hz, msk144wb::kDefaultBankTapsPerBand);
+    else if(bank)
+    {
+        if(bank_num_taps < msk144wb::kBankBands || bank_num_taps > msk144wb::kBankBands * msk144wb::kMaxBankTapsPerBand || bank_num_taps % msk144wb::kBankBands)
+            return fail(h, MSK144_EINVAL, "the bank filter needs 64 x K1 taps, 1 <= K1 <= 16");
+        h1.assign(bank_taps, bank_taps + bank_num_taps);
+        for(double v : h1)
+            if(!std::isfinite(v)) return fail(h, MSK144_EINVAL, "bank taps must be finite");
+    }
+    const msk144wb::RateRatio rr = msk144wb::rate_ratio(msk144wb::stage2_rate(wp->rate_hz));
+    const int L = wp->taps_per_phase * rr.P;
+    if(!wp->taps || wp->num_taps != L)
+        return fail(h, MSK144_EINVAL, rr.Q == 1 ? "the filter needs taps_per_phase x D taps" : "the filter needs taps_per_phase x P taps (rate = 12000 x P/Q)");
+    for(int k = 0; k < L; k++)
+        if(!std::isfinite(wp->taps[k])) return fail(h, MSK144_EINVAL, "filter taps must be finite");
+    return MSK144_OK;
+}
+
+// Channel slots: without the bank slot c is channel c; with it, the channels of each occupied band (k mod 64, ascending) one after
+// another, each band's group padded to whole waves, at the residual offset f_c - k Fs/64
+struct WbSlots
+{
+    std::vector<int32_t> slot_channel;   // the channel of slot c; -1: padding
+    std::vector<long long> slot_offset;  // its offset at the channeliser's rate
+    std::vector<int32_t> wave_band;      // bank: the sub-band stream of each wave of 32 slots
+    std::vector<int32_t> band_list;      // bank: the occupied band k mod 64 of stream j
+};
+
+WbSlots wb_slot_layout(const msk144_wideband_params* wp, bool bank)
+{
+    WbSlots sl;
+    const int C = wp->num_offsets;
+    if(!bank)
+    {
+        for(int c = 0; c < C; c++)
+        {
+            sl.slot_channel.push_back(c);
+            sl.slot_offset.push_back(wp->offsets_hz[c]);
+        }
+        return sl;
+    }
+    std::vector<std::vector<int>> by_band(msk144wb::kBankBands);
+    for(int c = 0; c < C; c++) by_band[static_cast<size_t>(msk144wb::bank_band(wp->rate_hz, wp->offsets_hz[c]) & (msk144wb::kBankBands - 1))].push_back(c);
+    for(int b = 0; b < msk144wb::kBankBands; b++)
+    {
+        const auto& chs = by_band[static_cast<size_t>(b)];
+        if(chs.empty()) continue;
+        const int j = static_cast<int>(sl.band_list.size());
+        sl.band_list.push_back(b);
+        const size_t n = (chs.size() + 31) / 32 * 32;
+        for(size_t i = 0; i < n; i++)
+        {
+            const int c = i < chs.size() ? chs[i] : -1;
+            sl.slot_channel.push_back(c);
+            sl.slot_offset.push_back(c < 0 ? 0 : msk144wb::bank_residual(wp->rate_hz, wp->offsets_hz[c]));
+            if(i % 32 == 0) sl.wave_band.push_back(j);
+        }
+    }
+    return sl;
+}
+
+// The channeliser's tables at Fs = 12000 P/Q (fs = Fs, the rate it runs at), slot by slot with f_c the slot's offset.  Branch mr
+// (outputs mr + Q a) has r = mr P mod Q, n0 = floor(mr P/Q) and the K_r = ceil((L - r)/Q) taps
+//     G_r[c][k] = h[r + kQ] e^{+j2pi (f_c (k - n0) mod Fs)/Fs}
+// computed in double with the phases in integers, stored f32 at [c/32][p][q][c%32] with k = p + P q (phase-major, the order the kernel
+// walks), the blocks one after another by mr.  Q = 1 is the one branch {0, 0, L}: G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs}.
+struct WbTables
+{
+    std::vector<float2> G;
+    std::vector<WidebandBranch> branches;
+    std::vector<int32_t> fmod;  // f_c mod 12000 in 0..11999
+};
+
+WbTables wb_tap_tables(const msk144_wideband_params* wp, const WbSlots& sl, long long fs, int P, int Q)
+{
+    const int L = wp->num_taps;
+    const int S = static_cast<int>(sl.slot_channel.size());
+    const int C32 = (S + 31) / 32;
+    WbTables t;
+    long long off = 0;
+    for(int mr = 0; mr < Q; mr++)
+    {
+        const int r = static_cast<int>(static_cast<long long>(mr) * P % Q);
+        const int Kr = (L - r + Q - 1) / Q;
+        t.branches.push_back(WidebandBranch{off, static_cast<int>(static_cast<long long>(mr) * P / Q), Kr});
+        off += static_cast<long long>(C32) * Kr * 32;
+    }
+    t.G.assign(static_cast<size_t>(off), make_float2(0.0f, 0.0f));  // C32 x L x 32: the branches share the L taps out
+    t.fmod.assign(static_cast<size_t>(S), 0);
+    for(int c = 0; c < S; c++)
+    {
+        if(sl.slot_channel[static_cast<size_t>(c)] < 0) continue;
+        const long long f = sl.slot_offset[static_cast<size_t>(c)];
+        t.fmod[static_cast<size_t>(c)] = static_cast<int32_t>(((f % msk144wb::kOutRate) + msk144wb::kOutRate) % msk144wb::kOutRate);
+        const long long fpos = ((f % fs) + fs) % fs;
+        for(int mr = 0; mr < Q; mr++)
+        {
+            const WidebandBranch& br = t.branches[static_cast<size_t>(mr)];
+            const int r = static_cast<int>(static_cast<long long>(mr) * P % Q);
+            const long long rot0 = (fpos * br.n0) % fs;
+            size_t at = static_cast<size_t>(br.g_off) + static_cast<size_t>(c / 32) * br.taps * 32 + (c % 32);
+            for(int p = 0; p < std::min(P, br.taps); p++)
+                for(int k = p; k < br.taps; k += P, at += 32)
+                {
+                    const long long ph_i = ((fpos * k) % fs - rot0 + fs) % fs;
+                    const double ph = 2.0 * M_PI * static_cast<double>(ph_i) / static_cast<double>(fs);
+                    const double hk = wp->taps[r + static_cast<size_t>(k) * Q];
+                    t.G[at] = make_float2(static_cast<float>(hk * std::cos(ph)), static_cast<float>(hk * std::sin(ph)));
+                }
+        }
+    }
+    return t;
+}
+
+// e^{sign j2pi t/n}, t < n: the output rotation (n = 12000, sign -1) and the bank's twiddles (n = 64, sign +1)
+std::vector<float2> unit_circle(int n, double sign)
+{
+    std::vector<float2> v(static_cast<size_t>(n));
+    for(int t = 0; t < n; t++)
+    {
+        const double ph = 2.0 * M_PI * t / n;
+        v[static_cast<size_t>(t)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(sign * std::sin(ph)));
+    }
+    return v;
+}
+
+// a device table of the wideband configuration, allocated and filled
+template<typename T>
+int wb_table(msk144_handle* h, T** d, const std::vector<T>& v)
+{
+    const int rc = dev_alloc(h, h->wb.mem, d, v.size());
+    if(rc != MSK144_OK) return rc;
+    HIP_TRY(h, hipMemcpy(*d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return MSK144_OK;
+}
+
+// Every buffer of the configuration whose shape h->wb already holds; on failure the caller releases what was allocated
+int wb_allocate(msk144_handle* h, const WbSlots& sl, const WbTables& t, const std::vector<double>& h1)
+{
+    auto& w = h->wb;
+    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
+    w.slot_bytes = static_cast<size_t>(kWindowSamples) / w.Qin * w.Pin * sb;
+    int rc = MSK144_OK;
+    for(uint8_t*& p : w.pinned)
+        if((rc = host_alloc(h, w.mem, &p, w.slot_bytes)) != MSK144_OK) return rc;
+    if((rc = dev_alloc(h, w.mem, &w.d_raw, static_cast<size_t>(w.raw_hist) * sb + w.slot_bytes)) != MSK144_OK) return rc;
+    if((rc = wb_table(h, &w.d_G, t.G)) != MSK144_OK || (rc = wb_table(h, &w.d_branches, t.branches)) != MSK144_OK ||
+       (rc = wb_table(h, &w.d_fmod, t.fmod)) != MSK144_OK || (rc = wb_table(h, &w.d_rot, unit_circle(msk144wb::kOutRate, -1.0))) != MSK144_OK)
+        return rc;
+    if((rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK) return rc;
+    HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
+    if(!w.bank) return MSK144_OK;
+    if((rc = wb_table(h, &w.d_h1, std::vector<float>(h1.begin(), h1.end()))) != MSK144_OK || (rc = wb_table(h, &w.d_bands, sl.band_list)) != MSK144_OK ||
+       (rc = wb_table(h, &w.d_tw, unit_circle(msk144wb::kBankBands, 1.0))) != MSK144_OK || (rc = wb_table(h, &w.d_wave_band, sl.wave_band)) != MSK144_OK ||
+       (rc = wb_table(h, &w.d_slot_channel, sl.slot_channel)) != MSK144_OK)
+        return rc;
+    return dev_alloc(h, w.mem, &w.d_sub, w.band_index.size() * static_cast<size_t>(w.stride));
 }
 
 // the slot argument of an entry that begins a hop: in range, and not still waiting for msk144_fetch_wait
@@ -1095,190 +1267,41 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* wp)
 
 int msk144_set_wideband_ex(msk144_handle* h, const msk144_wideband_params* wp, const double* bank_taps, int32_t bank_num_taps)
 {
-    if(!h || !wp) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 2) return fail(h, MSK144_EINVAL, "wideband input needs an IQ handle (read_mode 2)");
-    if(wp->num_offsets != h->params.channels) return fail(h, MSK144_EINVAL, "the number of channel offsets must equal the handle's channels");
-    const std::string why = msk144wb::check_config(wp->rate_hz, wp->format, wp->taps_per_phase, wp->gain, wp->offsets_hz, wp->num_offsets);
-    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
-    const bool bank = msk144wb::is_bank_rate(wp->rate_hz);
-    if(!bank && (bank_taps || bank_num_taps)) return fail(h, MSK144_EINVAL, "bank taps are only taken above 6144000 Hz (two-stage bank)");
     std::vector<double> h1;
-    if(bank)
-    {
-        if(!bank_taps) h1 = msk144wb::design_bank_taps(wp->rate_hz, msk144wb::kDefaultBankTapsPerBand);
-        else
-        {
-            if(bank_num_taps < msk144wb::kBankBands || bank_num_taps > msk144wb::kBankBands * msk144wb::kMaxBankTapsPerBand || bank_num_taps % msk144wb::kBankBands)
-                return fail(h, MSK144_EINVAL, "the bank filter needs 64 x K1 taps, 1 <= K1 <= 16");
-            h1.assign(bank_taps, bank_taps + bank_num_taps);
-            for(double v : h1)
-                if(!std::isfinite(v)) return fail(h, MSK144_EINVAL, "bank taps must be finite");
-        }
-    }
-    const int64_t rate2 = msk144wb::stage2_rate(wp->rate_hz);  // the channeliser's input rate
-    const msk144wb::RateRatio rr = msk144wb::rate_ratio(rate2), rin = msk144wb::rate_ratio(wp->rate_hz);
-    const int P = rr.P, Q = rr.Q;
-    const int K = wp->taps_per_phase;
-    const int L = K * P;
-    if(!wp->taps || wp->num_taps != L)
-        return fail(h, MSK144_EINVAL, Q == 1 ? "the filter needs taps_per_phase x D taps" : "the filter needs taps_per_phase x P taps (rate = 12000 x P/Q)");
-    for(int k = 0; k < L; k++)
-        if(!std::isfinite(wp->taps[k])) return fail(h, MSK144_EINVAL, "filter taps must be finite");
-
+    int rc = wb_validate(h, wp, bank_taps, bank_num_taps, h1);
+    if(rc != MSK144_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->params.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    int rc = ensure_ring(h);
-    if(rc != MSK144_OK) return rc;
+    if((rc = ensure_ring(h)) != MSK144_OK) return rc;
     wb_release(h);
-    auto& w = h->wb;
-    const int C = h->params.channels;
 
-    // channel slots: without the bank slot c is channel c; with it, the channels of each occupied band (k mod 64, ascending) one
-    // after another, each band's group padded to whole waves, at the residual offset f_c - k Fs/64
-    std::vector<int32_t> slot_channel, wave_band;
-    std::vector<long long> slot_offset;
-    std::vector<int32_t> band_list;
-    if(!bank)
-        for(int c = 0; c < C; c++)
-        {
-            slot_channel.push_back(c);
-            slot_offset.push_back(wp->offsets_hz[c]);
-        }
-    else
-    {
-        std::vector<std::vector<int>> by_band(msk144wb::kBankBands);
-        for(int c = 0; c < C; c++)
-            by_band[static_cast<size_t>(msk144wb::bank_band(wp->rate_hz, wp->offsets_hz[c]) & (msk144wb::kBankBands - 1))].push_back(c);
-        for(int b = 0; b < msk144wb::kBankBands; b++)
-        {
-            const auto& chs = by_band[static_cast<size_t>(b)];
-            if(chs.empty()) continue;
-            const int j = static_cast<int>(band_list.size());
-            band_list.push_back(b);
-            const size_t n = (chs.size() + 31) / 32 * 32;
-            for(size_t i = 0; i < n; i++)
-            {
-                const int c = i < chs.size() ? chs[i] : -1;
-                slot_channel.push_back(c);
-                slot_offset.push_back(c < 0 ? 0 : msk144wb::bank_residual(wp->rate_hz, wp->offsets_hz[c]));
-                if(i % 32 == 0) wave_band.push_back(j);
-            }
-        }
-    }
-    const int S = static_cast<int>(slot_channel.size());
-    const int C32 = (S + 31) / 32;
-    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(wp->format));
-    const int hist = (L + Q - 1) / Q - 1;
-    const int raw_hist = bank ? static_cast<int>(h1.size()) - 1 : hist;
-    const int NB = static_cast<int>(band_list.size());
-    const long long stride = bank ? hist + static_cast<long long>(kWindowSamples) / Q * P : 0;
-    w.slot_bytes = static_cast<size_t>(kWindowSamples) / rin.Q * rin.P * sb;
-    for(uint8_t*& p : w.pinned)
-        if(rc == MSK144_OK) rc = host_alloc(h, w.mem, &p, w.slot_bytes);
-    const size_t g_count = static_cast<size_t>(C32) * L * 32;
-    if(rc != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_raw, static_cast<size_t>(raw_hist) * sb + w.slot_bytes)) != MSK144_OK ||
-       (rc = dev_alloc(h, w.mem, &w.d_G, g_count)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_fmod, S)) != MSK144_OK ||
-       (rc = dev_alloc(h, w.mem, &w.d_rot, msk144wb::kOutRate)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK ||
-       (Q > 1 && (rc = dev_alloc(h, w.mem, &w.d_branches, Q)) != MSK144_OK) ||
-       (bank && ((rc = dev_alloc(h, w.mem, &w.d_h1, h1.size())) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_bands, NB)) != MSK144_OK ||
-                 (rc = dev_alloc(h, w.mem, &w.d_tw, msk144wb::kBankBands)) != MSK144_OK ||
-                 (rc = dev_alloc(h, w.mem, &w.d_sub, static_cast<size_t>(NB) * stride)) != MSK144_OK ||
-                 (rc = dev_alloc(h, w.mem, &w.d_wave_band, wave_band.size())) != MSK144_OK ||
-                 (rc = dev_alloc(h, w.mem, &w.d_slot_channel, S)) != MSK144_OK)))
+    const bool bank = msk144wb::is_bank_rate(wp->rate_hz);
+    const int64_t rate2 = msk144wb::stage2_rate(wp->rate_hz);  // the channeliser's input rate
+    const msk144wb::RateRatio rr = msk144wb::rate_ratio(rate2), rin = msk144wb::rate_ratio(wp->rate_hz);
+    const WbSlots sl = wb_slot_layout(wp, bank);
+    const WbTables t = wb_tap_tables(wp, sl, rate2, rr.P, rr.Q);
+
+    auto& w = h->wb;
+    w.P = rr.P;
+    w.Q = rr.Q;
+    w.K = wp->taps_per_phase;
+    w.L = wp->num_taps;
+    w.hist = (w.L + w.Q - 1) / w.Q - 1;
+    w.Pin = rin.P;
+    w.Qin = rin.Q;
+    w.bank = bank;
+    w.raw_hist = bank ? static_cast<int>(h1.size()) - 1 : w.hist;
+    w.K1 = static_cast<int>(h1.size()) / msk144wb::kBankBands;
+    w.band_index.assign(sl.band_list.begin(), sl.band_list.end());
+    w.stride = bank ? w.hist + static_cast<long long>(kWindowSamples) / w.Q * w.P : 0;
+    w.slots = static_cast<int>(sl.slot_channel.size());
+    w.format = wp->format;
+    w.gain = wp->gain;
+    if((rc = wb_allocate(h, sl, t, h1)) != MSK144_OK)
     {
         wb_release(h);
         return rc;
     }
-
-    // G[c][k] = h[k] e^{+j2pi (f_c k mod Fs)/Fs} in double, stored f32 at [c/32][p][q][c%32] with k = p + D*q; phases in integers.
-    // c is a slot and f_c its offset; Fs the channeliser's rate.
-    const long long fs = static_cast<long long>(rate2);
-    const int D = P;
-    std::vector<float2> G(g_count, make_float2(0.0f, 0.0f));
-    std::vector<int32_t> fmod(static_cast<size_t>(S), 0);
-    std::vector<WidebandBranch> branches(Q > 1 ? static_cast<size_t>(Q) : 0);
-    for(int c = 0; c < S; c++)
-    {
-        if(slot_channel[static_cast<size_t>(c)] < 0) continue;
-        const long long f = slot_offset[static_cast<size_t>(c)];
-        fmod[static_cast<size_t>(c)] = static_cast<int32_t>(((f % msk144wb::kOutRate) + msk144wb::kOutRate) % msk144wb::kOutRate);
-        const long long fpos = ((f % fs) + fs) % fs;
-        if(Q > 1)
-        {
-            // branch mr (outputs mr + Q a): G_r[c][k] = h[r + kQ] e^{+j2pi (f_c (k - n0) mod Fs)/Fs}, k = p + P q in phase-major order,
-            // blocks one after another by mr, each [c/32][taps][c%32]
-            long long off = 0;
-            for(int mr = 0; mr < Q; mr++)
-            {
-                const int r = static_cast<int>(static_cast<long long>(mr) * P % Q);
-                const int n0 = static_cast<int>(static_cast<long long>(mr) * P / Q);
-                const int Kr = (L - r + Q - 1) / Q;
-                branches[static_cast<size_t>(mr)] = WidebandBranch{off, n0, Kr};
-                const long long rot0 = (fpos * n0) % fs;
-                size_t t = static_cast<size_t>(off) + static_cast<size_t>(c / 32) * Kr * 32 + (c % 32);
-                for(int p = 0; p < std::min(P, Kr); p++)
-                    for(int k = p; k < Kr; k += P, t += 32)
-                    {
-                        const long long ph_i = ((fpos * k) % fs - rot0 + fs) % fs;
-                        const double ph = 2.0 * M_PI * static_cast<double>(ph_i) / static_cast<double>(fs);
-                        const double hk = wp->taps[r + static_cast<size_t>(k) * Q];
-                        G[t] = make_float2(static_cast<float>(hk * std::cos(ph)), static_cast<float>(hk * std::sin(ph)));
-                    }
-                off += static_cast<long long>(C32) * Kr * 32;
-            }
-            continue;
-        }
-        for(int p = 0; p < D; p++)
-            for(int q = 0; q < K; q++)
-            {
-                const long long k = p + static_cast<long long>(D) * q;
-                const double ph = 2.0 * M_PI * static_cast<double>((fpos * k) % fs) / static_cast<double>(fs);
-                const double hk = wp->taps[k];
-                G[((static_cast<size_t>(c / 32) * D + p) * K + q) * 32 + (c % 32)] =
-                    make_float2(static_cast<float>(hk * std::cos(ph)), static_cast<float>(hk * std::sin(ph)));
-            }
-    }
-    std::vector<float2> rot(msk144wb::kOutRate);
-    for(int r = 0; r < msk144wb::kOutRate; r++)
-    {
-        const double ph = 2.0 * M_PI * r / msk144wb::kOutRate;
-        rot[static_cast<size_t>(r)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(-std::sin(ph)));
-    }
-    HIP_TRY(h, hipMemcpy(w.d_G, G.data(), g_count * sizeof(float2), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(w.d_fmod, fmod.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(w.d_rot, rot.data(), sizeof(float2) * rot.size(), hipMemcpyHostToDevice));
-    if(Q > 1) HIP_TRY(h, hipMemcpy(w.d_branches, branches.data(), sizeof(WidebandBranch) * branches.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
-    if(bank)
-    {
-        std::vector<float> h1f(h1.begin(), h1.end());
-        std::vector<float2> tw(msk144wb::kBankBands);
-        for(int t = 0; t < msk144wb::kBankBands; t++)
-        {
-            const double ph = 2.0 * M_PI * t / msk144wb::kBankBands;
-            tw[static_cast<size_t>(t)] = make_float2(static_cast<float>(std::cos(ph)), static_cast<float>(std::sin(ph)));
-        }
-        HIP_TRY(h, hipMemcpy(w.d_h1, h1f.data(), sizeof(float) * h1f.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(w.d_bands, band_list.data(), sizeof(int32_t) * NB, hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(w.d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(w.d_wave_band, wave_band.data(), sizeof(int32_t) * wave_band.size(), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(w.d_slot_channel, slot_channel.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
-        w.K1 = static_cast<int>(h1.size()) / msk144wb::kBankBands;
-        w.band_index.assign(band_list.begin(), band_list.end());
-    }
-    w.P = P;
-    w.Q = Q;
-    w.K = K;
-    w.L = L;
-    w.hist = hist;
-    w.Pin = rin.P;
-    w.Qin = rin.Q;
-    w.raw_hist = raw_hist;
-    w.bank = bank;
-    w.slots = S;
-    w.stride = stride;
-    w.format = wp->format;
-    w.gain = wp->gain;
     w.configured = true;
     return MSK144_OK;
 }
@@ -1345,12 +1368,8 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         format = kSubbandFormat;
         bands = WidebandBands{w.d_wave_band, w.d_slot_channel, w.stride};
     }
-    if(w.Q == 1)
-        launch_channelise(in, format, w.d_G, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, w.slots, w.P, w.K, M,
-                          first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
-    else
-        launch_channelise_rational(in, format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops),
-                                   w.d_clip, w.slots, w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
+    launch_channelise(in, format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, w.slots,
+                      w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     w.m_next += M;

@@ -86,28 +86,24 @@ struct WidebandBands
     long long stride = 0;
 };
 
-// wideband down-converter bank (channelise.hip): raw = the L-1 history samples then M*D new ones (format 0 cu8, 1 cs8, 2 cs16);
-// G = [ceil(channels/32)][D][K][32] taps (tap k = p + D*q at [p][q], zero rows past `channels`); fmod[c] = f_c mod 12000 in
-// 0..11999; rot[r] = e^{-j2pi r/12000}.  Writes the int8 I/Q of output samples m_base .. m_base+M-1 of every channel into the hop
-// ring staging (M = 5184 with first != 0: the first 2592 into first_halves) and adds the clipped components to *clip_count.
-void launch_channelise(const void* raw, int format, const float2* G, const int32_t* fmod, const float2* rot, int8_t* first_halves, int8_t* hops,
-                       unsigned long long* clip_count, int channels, int D, int K, int M, int first, long long m_base, float gain, hipStream_t stream,
-                       WidebandBands bands = {});
-
-// one polyphase branch of a rational-rate channeliser (Fs = 12000 P/Q, Q > 1): the outputs m = mr + Q a of a push read inputs
-// n0 + a P - k, k < taps, with the taps h[r + k Q] (r = mr P mod Q) of its G block, which starts at float2 offset g_off
+// one polyphase branch of the channeliser at Fs = 12000 P/Q: the outputs m = mr + Q a of a push read inputs n0 + a P - k, k < taps,
+// with the taps h[r + k Q] (r = mr P mod Q) of its G block, which starts at float2 offset g_off.  An integer rate (Q = 1, D = P) has
+// the one branch {0, 0, L}.
 struct WidebandBranch
 {
-    long long g_off;  // G block: [ceil(channels/32)][taps in phase-major order, k = p + P q][32]
+    long long g_off;  // G block: [ceil(channels/32)][taps in phase-major order, k = p + P q][32], zero rows past `channels`
     int n0;           // floor(mr P / Q)
     int taps;         // ceil((L - r) / Q)
 };
 
-// the same for Fs = 12000 P/Q with Q > 1: raw = `hist` history samples then M*P/Q new ones; branches[0..Q) by output residue mr.
-// G carries each branch's constant output rotation e^{-j2pi (f_c n0 mod Fs)/Fs}, so the kernel rotates by (f_c (m - mr)) mod 12000.
-void launch_channelise_rational(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot,
-                                int8_t* first_halves, int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first,
-                                long long m_base, float gain, hipStream_t stream, WidebandBands bands = {});
+// wideband down-converter bank (channelise.hip) at Fs = 12000 P/Q, Q >= 1: raw = `hist` history samples then M*P/Q new ones (format
+// 0 cu8, 1 cs8, 2 cs16); branches[0..Q) by output residue mr, G their blocks one after another; fmod[c] = f_c mod 12000 in 0..11999;
+// rot[r] = e^{-j2pi r/12000}.  G carries each branch's constant output rotation e^{-j2pi (f_c n0 mod Fs)/Fs}, so the kernel rotates
+// by (f_c (m - mr)) mod 12000.  Writes the int8 I/Q of output samples m_base .. m_base+M-1 of every channel into the hop ring
+// staging (M = 5184 with first != 0: the first 2592 into first_halves) and adds the clipped components to *clip_count.
+void launch_channelise(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot, int8_t* first_halves,
+                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base, float gain,
+                       hipStream_t stream, WidebandBands bands = {});
 
 // the analysis bank in front of the channeliser above 6.144 Msps (bank.hip): raw = the L1-1 history samples then 32 x frames new
 // ones (format 0 cu8, 1 cs8, 2 cs16); h1 = the L1 = 64 K1 bank taps (f32); bands[j] = the occupied band k mod 64 of stream j;

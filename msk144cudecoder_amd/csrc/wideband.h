@@ -60,16 +60,11 @@ inline double bessel_i0(double x)
     return sum;
 }
 
-// Default prototype low-pass, L = K*D taps at Fs = D*12000 (for a rational rate 12000 P/Q: D = P, at the upsampled rate; see
-// design_taps_rate): a Kaiser-windowed sinc with its cut-off half way between the 4 kHz
-// pass edge and the 8 kHz stop edge, scaled to unit DC gain.  Symmetric about (L-1)/2.
-inline std::vector<double> design_taps(int D, int K)
+// Kaiser-windowed sinc of L taps with its cut-off at fc cycles per sample, scaled to unit DC gain.  Symmetric about (L-1)/2.
+inline std::vector<double> kaiser_sinc(int L, double fc, double beta)
 {
-    const int L = K * D;
-    const double fs = static_cast<double>(D) * kOutRate;
-    const double fc = 0.5 * (kPassHz + kStopHz) / fs;  // cycles per sample
     const double mid = 0.5 * (L - 1);
-    const double i0b = bessel_i0(kKaiserBeta);
+    const double i0b = bessel_i0(beta);
     std::vector<double> h(static_cast<size_t>(L));
     double sum = 0.0;
     for(int k = 0; k < L; k++)
@@ -78,12 +73,20 @@ inline std::vector<double> design_taps(int D, int K)
         const double arg = 2.0 * fc * t;
         const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
         const double r = L > 1 ? t / mid : 0.0;
-        const double w = bessel_i0(kKaiserBeta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
+        const double w = bessel_i0(beta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
         h[static_cast<size_t>(k)] = sinc * w;
         sum += h[static_cast<size_t>(k)];
     }
     for(double& v : h) v /= sum;
     return h;
+}
+
+// Default prototype low-pass, L = K*D taps at Fs = D*12000 (for a rational rate 12000 P/Q: D = P, at the upsampled rate; see
+// design_taps_rate): a Kaiser-windowed sinc (beta 7) with its cut-off half way between the 4 kHz pass edge and the 8 kHz stop edge.
+inline std::vector<double> design_taps(int D, int K)
+{
+    const double fs = static_cast<double>(D) * kOutRate;
+    return kaiser_sinc(K * D, 0.5 * (kPassHz + kStopHz) / fs, kKaiserBeta);
 }
 
 // Fs / 12000 = P/Q in lowest terms (Q = 1: the integer decimation D = P).  Q divides 96 for every rate that check_config accepts.
@@ -140,25 +143,8 @@ inline int64_t bank_residual(int64_t rate_hz, int64_t f_hz)
 // the decimation by 32 folds onto a channel's 8 kHz stop edge), scaled to unit DC gain.  Symmetric about (L1-1)/2.
 inline std::vector<double> design_bank_taps(int64_t rate_hz, int K1)
 {
-    const int L = kBankBands * K1;
     const double fs = static_cast<double>(rate_hz);
-    const double fc = 0.5 * ((fs / 128.0 + kPassHz) + (3.0 * fs / 128.0 - kStopHz)) / fs;
-    const double mid = 0.5 * (L - 1);
-    const double i0b = bessel_i0(kBankKaiserBeta);
-    std::vector<double> h(static_cast<size_t>(L));
-    double sum = 0.0;
-    for(int k = 0; k < L; k++)
-    {
-        const double t = k - mid;
-        const double arg = 2.0 * fc * t;
-        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
-        const double r = L > 1 ? t / mid : 0.0;
-        const double w = bessel_i0(kBankKaiserBeta * std::sqrt(std::fmax(0.0, 1.0 - r * r))) / i0b;
-        h[static_cast<size_t>(k)] = sinc * w;
-        sum += h[static_cast<size_t>(k)];
-    }
-    for(double& v : h) v /= sum;
-    return h;
+    return kaiser_sinc(kBankBands * K1, 0.5 * ((fs / 128.0 + kPassHz) + (3.0 * fs / 128.0 - kStopHz)) / fs, kBankKaiserBeta);
 }
 
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.

@@ -309,15 +309,14 @@ class HipDecoder:
     # ---- wideband channeliser (read_mode 2 handles) ----
     def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0, bank_taps=None):
         """Configure the down-converter bank: one channel per offset (len == channels).  taps=None: the default design of
-        libmsk144host.so: wideband.default_taps(D) at rate_hz = D x 12000, wideband.default_taps_for_rate for any other rate
-        12000 x P/Q (K*P taps summing to Q).  Above 6.144 Msps the taps are the channeliser's at rate_hz/32 (the default: the same
+        libmsk144host.so, wideband.default_taps_for_rate (rate_hz = 12000 x P/Q: K*P taps summing to Q).  Above 6.144 Msps the taps are the channeliser's at rate_hz/32 (the default: the same
         design at that rate) and bank_taps the analysis bank's (64 K1 taps; None: the default bank)."""
-        from .wideband import default_taps, default_taps_for_rate, rate_ratio, stage2_rate
+        from .wideband import default_taps_for_rate, rate_ratio, stage2_rate
         rate2 = stage2_rate(int(rate_hz)) if int(rate_hz) > 0 else 0
         P, Q = rate_ratio(int(rate_hz)) if int(rate_hz) > 0 else (0, 1)
         P2, Q2 = rate_ratio(rate2) if rate2 > 0 else (0, 1)
         if taps is None:
-            taps = default_taps(P2, taps_per_phase) if Q2 == 1 else default_taps_for_rate(rate2, taps_per_phase)
+            taps = default_taps_for_rate(rate2, taps_per_phase)
         self._wb_taps = np.ascontiguousarray(taps, dtype=np.float64)
         self._wb_offsets = np.ascontiguousarray(offsets_hz, dtype=np.int32)
         self._wb_format = fmt

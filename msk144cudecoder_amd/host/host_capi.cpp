@@ -10,19 +10,9 @@ using namespace msk144host;
 
 extern "C" {
 
-// The default wideband prototype filter (csrc/wideband.h), L = K*D taps into out; returns L, or -1 for D outside 2..512 / K outside
+// The default wideband prototype filter for any rate Fs = 12000 P/Q (csrc/wideband.h design_taps_rate): L = K*P taps summing to Q
+// into out; returns L, or -1 for a rate the contract refuses (not a multiple of 125 Hz, outside 24000..6144000 Hz) or K outside
 // 1..64.  The same taps msk144hipdecoder hands to msk144_set_wideband.
-int msk144host_wideband_taps(int D, int K, double* out)
-{
-    if(D < msk144wb::kMinDecimation || D > msk144wb::kMaxDecimation || K < 1 || K > msk144wb::kMaxTapsPerPhase) return -1;
-    const std::vector<double> h = msk144wb::design_taps(D, K);
-    if(out) std::memcpy(out, h.data(), sizeof(double) * h.size());
-    return static_cast<int>(h.size());
-}
-
-// The same for any wideband rate Fs = 12000 P/Q (csrc/wideband.h design_taps_rate): L = K*P taps summing to Q into out; returns L,
-// or -1 for a rate the contract refuses (not a multiple of 125 Hz, outside 24000..6144000 Hz) or K outside 1..64.  For Q = 1 the
-// taps of msk144host_wideband_taps(D, K).
 int msk144host_wideband_taps_rate(int64_t rate_hz, int K, double* out)
 {
     if(rate_hz <= 0 || rate_hz % msk144wb::kRateStepHz != 0 || rate_hz < msk144wb::kMinRateHz || rate_hz > msk144wb::kMaxRateHz || K < 1 || K > msk144wb::kMaxTapsPerPhase)
@@ -31,6 +21,9 @@ int msk144host_wideband_taps_rate(int64_t rate_hz, int K, double* out)
     if(out) std::memcpy(out, h.data(), sizeof(double) * h.size());
     return static_cast<int>(h.size());
 }
+
+// The same by integer decimation, Fs = D x 12000 (include/msk144hip.h names it): L = K*D taps, or -1 for D outside 2..512
+int msk144host_wideband_taps(int D, int K, double* out) { return msk144host_wideband_taps_rate(static_cast<int64_t>(D) * msk144wb::kOutRate, K, out); }
 
 // The default analysis-bank prototype above 6.144 Msps (csrc/wideband.h design_bank_taps): L1 = 64 K1 taps summing to 1 into out;
 // returns L1, or -1 for a rate the bank does not take (a multiple of 8000 Hz above 6144000 up to 61440000) or K1 outside 1..16.

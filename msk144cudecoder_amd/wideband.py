@@ -38,8 +38,6 @@ def _host_lib():
         if not os.path.exists(HOST_LIB):
             raise FileNotFoundError(f"{HOST_LIB} not found: build it with `make -C msk144cudecoder_amd/host`")
         L = C.CDLL(HOST_LIB)
-        L.msk144host_wideband_taps.argtypes = [C.c_int, C.c_int, C.c_void_p]
-        L.msk144host_wideband_taps.restype = C.c_int
         L.msk144host_wideband_taps_rate.argtypes = [C.c_int64, C.c_int, C.c_void_p]
         L.msk144host_wideband_taps_rate.restype = C.c_int
         L.msk144host_wideband_check.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_char_p, C.c_int]
@@ -51,14 +49,8 @@ def _host_lib():
 
 
 def default_taps(D: int, K: int = 16) -> np.ndarray:
-    """The default prototype low-pass (K*D taps at D*12000 Hz), exactly what the program hands to the library."""
-    L = _host_lib()
-    n = L.msk144host_wideband_taps(int(D), int(K), None)
-    if n < 0:
-        raise ValueError(f"no default filter for D={D}, K={K} (D 2..512, K 1..64)")
-    h = np.empty(n, dtype=np.float64)
-    L.msk144host_wideband_taps(int(D), int(K), h.ctypes.data_as(C.c_void_p))
-    return h
+    """The default prototype at the integer rate D x 12000 Hz (K*D taps summing to 1)."""
+    return default_taps_for_rate(OUT_RATE * int(D), K)
 
 
 def rate_ratio(rate_hz: int) -> Tuple[int, int]:
@@ -68,8 +60,8 @@ def rate_ratio(rate_hz: int) -> Tuple[int, int]:
 
 
 def default_taps_for_rate(rate_hz: int, K: int = 16) -> np.ndarray:
-    """The default prototype for any rate Fs = 12000 P/Q: K*P taps at 12000 P Hz summing to Q (each polyphase branch about unit DC
-    gain); for Q = 1 exactly default_taps(D, K)."""
+    """The default prototype for any rate Fs = 12000 P/Q, exactly what the program hands to the library: K*P taps at 12000 P Hz
+    summing to Q (each polyphase branch about unit DC gain)."""
     L = _host_lib()
     n = L.msk144host_wideband_taps_rate(int(rate_hz), int(K), None)
     if n < 0:
@@ -176,30 +168,25 @@ def quantise(y: np.ndarray, gain: float = 100.0) -> Tuple[np.ndarray, int]:
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 
-    Fs = D x 12000 (Q = 1) runs the integer formula; any other rate Fs = 12000 P/Q its polyphase form, branch by branch (outputs
-    m = mr + Q a read x[n0 + a P - k] with the taps h[r + kQ])."""
+    Any rate Fs = 12000 P/Q runs the polyphase form, branch by branch: outputs m = mr + Q a read x[n0 + a P - k] with the taps
+    h[r + kQ], r = mr P mod Q, n0 = floor(mr P/Q).  Fs = D x 12000 is Q = 1: the one branch (0, 0, all taps), D = P."""
 
     def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0):
         if rate_hz <= 0 or rate_hz % 125:
             raise ValueError("rate must be a positive multiple of 125 Hz")
         self.P, self.Q = rate_ratio(rate_hz)
-        self.rate = int(rate_hz)
-        self.offsets = np.asarray(offsets_hz, dtype=np.int64)
         if self.Q == 1:
             self.D = self.P
-            self.taps = default_taps(self.D, K) if taps is None else np.asarray(taps, dtype=np.float64)
-        else:
-            self.taps = default_taps_for_rate(rate_hz, K) if taps is None else np.asarray(taps, dtype=np.float64)
+        self.rate = int(rate_hz)
+        self.offsets = np.asarray(offsets_hz, dtype=np.int64)
+        self.taps = default_taps_for_rate(rate_hz, K) if taps is None else np.asarray(taps, dtype=np.float64)
         self.L = len(self.taps)
         self.gain = gain
-        if self.Q == 1:
-            self.G = tap_matrix(rate_hz, self.offsets, self.taps)
-        else:
-            # branch taps by output residue mr: (r, n0, G_r [channel][K_r])
-            self.branches = []
-            for mr in range(self.Q):
-                r, n0 = mr * self.P % self.Q, mr * self.P // self.Q
-                self.branches.append((r, n0, tap_matrix(rate_hz, self.offsets, self.taps[r::self.Q])))
+        # branch taps by output residue mr: (r, n0, G_r [channel][K_r])
+        self.branches = []
+        for mr in range(self.Q):
+            r, n0 = mr * self.P % self.Q, mr * self.P // self.Q
+            self.branches.append((r, n0, tap_matrix(rate_hz, self.offsets, self.taps[r::self.Q])))
         self.reset()
 
     @property
@@ -214,26 +201,6 @@ class Channeliser:
     def filter(self, x: np.ndarray) -> np.ndarray:
         """complex y [channel][M] of the next len(x) Q/P output samples (history and m advance)."""
         x = np.asarray(x, dtype=np.complex128)
-        if self.Q > 1:
-            return self._filter_rational(x)
-        D, L = self.D, self.L
-        if len(x) % D:
-            raise ValueError("a push carries a whole number of output samples")
-        M = len(x) // D
-        xp = np.concatenate([self.hist, x])
-        y = np.empty((len(self.offsets), M), dtype=np.complex128)
-        k = np.arange(L)
-        GT = self.G.T
-        for m0 in range(0, M, 256):
-            ms = np.arange(m0, min(M, m0 + 256))
-            X = xp[ms[:, None] * D - k[None, :] + (L - 1)]   # Hankel rows x[mD - k]
-            y[:, m0:m0 + len(ms)] = (X @ GT).T
-        y *= output_rotation(self.offsets, self.m + np.arange(M))
-        self.hist = xp[len(xp) - (L - 1):].copy() if L > 1 else self.hist
-        self.m += M
-        return y
-
-    def _filter_rational(self, x: np.ndarray) -> np.ndarray:
         P, Q, H = self.P, self.Q, self.n_hist
         if len(x) % P:
             raise ValueError("a push carries a whole number of output samples per branch (a multiple of Q outputs)")
@@ -485,11 +452,11 @@ def synth_wideband(n_out: int, rate_hz: int, pings: Iterable[Tuple[int, synth.Pi
 
 
 def push_sizes(n_pushes: int, D: int):
-    """Raw component counts of a first push followed by n_pushes-1 later ones."""
-    return [2 * FIRST_OUT * D] + [2 * HOP_OUT * D] * (n_pushes - 1)
+    """Raw component counts of a first push followed by n_pushes-1 later ones, at the integer rate D x 12000 Hz."""
+    return push_sizes_for_rate(n_pushes, OUT_RATE * D)
 
 
 def push_sizes_for_rate(n_pushes: int, rate_hz: int):
-    """push_sizes for any rate: 2 x 5184 P/Q components, then 2 x 2592 P/Q."""
+    """The same for any rate: 2 x 5184 P/Q components, then 2 x 2592 P/Q."""
     P, Q = rate_ratio(rate_hz)
     return [2 * FIRST_OUT * P // Q] + [2 * HOP_OUT * P // Q] * (n_pushes - 1)

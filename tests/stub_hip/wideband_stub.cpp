@@ -1,11 +1,15 @@
-// Wideband entries for the stand-in library (compiled together with msk144hip_stub.cpp): no channeliser, the push hands every
-// channel a hop through the stub's own hop ring, marked like the --inputs streams of tests/test_host_loop.py - half-window k of
-// channel c starts with the int16 pair (0x7777, 100 c + k) - so that the records show which push reached which channel.
+// Wideband entries for the stand-in library (compiled together with msk144hip_stub.cpp), for every rate: a slot holds 5184 Fs/12000
+// input samples (5184 P/Q with Fs = 12000 P/Q), and the channel taps the program passes are reported with the rate, so that a test can
+// check they are the design for that rate - above 6.144 Msps the one for Fs/32 (K x P2 taps summing to Q2).  No bank and no
+// channeliser: the push hands every channel a hop through the stub's own hop ring, marked like the --inputs streams of
+// tests/test_host_loop.py - half-window k of channel c starts with the int16 pair (0x7777, 100 c + k) - so that the records show
+// which push reached which channel.
 #include "../../include/msk144hip.h"
 
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <numeric>
 #include <vector>
 
 namespace
@@ -33,7 +37,9 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* p)
     w.rate = p->rate_hz;
     w.format = p->format;
     w.pushes = 0;
-    const size_t bytes = static_cast<size_t>(MSK144_WINDOW_SAMPLES) * static_cast<size_t>(p->rate_hz / 12000) * (p->format == MSK144_WB_CS16 ? 4 : 2);
+    const long long g = std::gcd(static_cast<long long>(p->rate_hz), 12000LL);
+    const size_t P = static_cast<size_t>(p->rate_hz / g), Q = static_cast<size_t>(12000 / g);
+    const size_t bytes = static_cast<size_t>(MSK144_WINDOW_SAMPLES) / Q * P * (p->format == MSK144_WB_CS16 ? 4 : 2);
     for(auto& s : w.slot) s.assign(bytes, 0);
     double sum = 0.0;
     for(int k = 0; k < p->num_taps; k++) sum += p->taps[k];
@@ -41,6 +47,13 @@ int msk144_set_wideband(msk144_handle* h, const msk144_wideband_params* p)
             p->format, p->taps_per_phase, static_cast<double>(p->gain), p->num_taps, sum, p->num_offsets, p->offsets_hz[0], p->offsets_hz[p->num_offsets - 1]);
     return MSK144_OK;
 }
+
+int msk144_set_wideband_ex(msk144_handle* h, const msk144_wideband_params* p, const double*, int32_t)
+{
+    return msk144_set_wideband(h, p);
+}
+
+int msk144_dump_wideband_band(msk144_handle*, int32_t, float*) { return MSK144_ESTATE; }
 
 int msk144_wideband_slot(msk144_handle* h, int32_t s, void** buf, size_t* bytes)
 {

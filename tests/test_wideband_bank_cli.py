@@ -1,5 +1,5 @@
 """msk144hipdecoder --wideband-rate above 6.144 Msps (the two-stage bank), on the CPU: the rate rule (exit 2 before any library call)
-and the wideband loop against the stand-in library - tests/stub_hip/msk144hip_stub.cpp plus tests/stub_hip/wideband_bank_stub.cpp,
+and the wideband loop against the stand-in library - tests/stub_hip/msk144hip_stub.cpp plus tests/stub_hip/wideband_stub.cpp,
 whose slots hold 5184 Fs/12000 samples and whose push hands every channel a marked hop."""
 import os
 import re
@@ -16,7 +16,7 @@ PROGRAM_SOURCES = ("snr_tracker.cpp", "result_filter.cpp", "unpack77.cpp", "post
 def exe(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("wbbstub"))
     subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", os.path.join(d, "libmsk144hip.so")]
-                   + [os.path.join(ROOT, "tests", "stub_hip", s) for s in ("msk144hip_stub.cpp", "wideband_bank_stub.cpp")], check=True)
+                   + [os.path.join(ROOT, "tests", "stub_hip", s) for s in ("msk144hip_stub.cpp", "wideband_stub.cpp")], check=True)
     out = os.path.join(d, "msk144hipdecoder_stub")
     subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", out] + [os.path.join(HOST, f) for f in PROGRAM_SOURCES]
                    + ["-L" + d, "-lmsk144hip", "-Wl,-rpath," + d], check=True)
