@@ -13,9 +13,9 @@ import pytest
 
 import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
+from wideband_gpu import DECODE_CFG, check_stream, dump_hops
 
 pytestmark = pytest.mark.gpu
-DECODE_CFG = dict(center=0.0, width=500.0, step=1.0, depth=6, nbadsync_threshold=1, read_mode=2)
 
 
 @pytest.fixture(scope="module")
@@ -24,23 +24,11 @@ def d33(hip):
         yield d
 
 
-def _dump(d, channels):
-    return np.stack([d.dump_wideband_hop(int(c)) for c in channels])
-
-
 def _check_stream(d, rate, offsets, fmt, taps, K, gain, parts, firsts, tally, sample=None, what=""):
     """Configure d, push parts (firsts[i]: a first push) and hold every push to the near-tie rule on the channels in sample."""
-    C = len(offsets)
-    sample = np.arange(C) if sample is None else np.asarray(sample)
-    ref = wc.Reference(rate, np.asarray(offsets)[sample], taps=taps, K=K, gain=gain)
+    ref = wc.Reference(rate, offsets if sample is None else np.asarray(offsets)[sample], taps=taps, K=K, gain=gain)
     d.set_wideband(rate, offsets, fmt, taps=taps, taps_per_phase=K, gain=gain)
-    for i, (part, first) in enumerate(zip(parts, firsts)):
-        d.push_wideband(i % 2, part, first=first)
-        y, T, N = ref.push(wb.read_samples(part, fmt), first=first)
-        got = _dump(d, sample)
-        assert got.shape == y.shape + (2,)
-        clip = d.wideband_clip_count() if len(sample) == C else None   # the count covers every channel
-        tally.add(wc.assert_hops(got, y, T, N, gain, clip, what=f"{what} push {i}"))
+    check_stream(d, ref, fmt, parts, firsts, what, tally, sample)
 
 
 # ---- 1. impulses ----
@@ -52,7 +40,7 @@ def test_impulse_is_exact(d33, rate, K, j):
     d33.set_wideband(rate, np.zeros(33, dtype=np.int32), "cs8", taps=wc.unit_taps(K * P, j), taps_per_phase=K, gain=1.0)
     for i, part in enumerate(wc.split_pushes(raw, rate, wc.IMPULSE_PUSHES)):
         d33.push_wideband(i % 2, part, first=i == 0)
-        got = _dump(d33, range(33))
+        got = dump_hops(d33, range(33))
         want = wc.impulse_expected(raw, rate, j, wc.push_m0(i), got.shape[1])
         for c in range(33):
             bad = np.count_nonzero(np.any(got[c] != want, axis=1))
@@ -128,7 +116,7 @@ def _impulse_pushes(d, fmt, raw, gain, n_pushes=3):
         M = wb.FIRST_OUT if i == 0 else wb.HOP_OUT
         m = wc.push_m0(i) + np.arange(M)
         comp = np.asarray(raw).reshape(-1, 2)[80 * m].astype(np.float64)
-        yield i, _dump(d, range(33)), comp, d.wideband_clip_count()
+        yield i, dump_hops(d, range(33)), comp, d.wideband_clip_count()
 
 
 def _want(v):
@@ -179,7 +167,7 @@ def test_tiny_gain_gives_zeros(d33):
     d33.set_wideband(QRATE, offsets, "cs16", taps=taps, taps_per_phase=16, gain=1e-30)
     for i, part in enumerate(wc.split_pushes(raw, QRATE, 3)):
         d33.push_wideband(i % 2, part, first=i == 0)
-        assert not np.any(_dump(d33, range(33))), f"push {i}"
+        assert not np.any(dump_hops(d33, range(33))), f"push {i}"
         assert d33.wideband_clip_count() == 0
 
 

@@ -2,104 +2,53 @@
 
 1. The int8 hops the device writes agree with the float64 model of the contract (msk144cudecoder_amd/wideband.py) at 2.048 Msps
    (512/3, every format), 250 ksps (125/6), 96.125 ksps (769/96) and 6.142 Msps (3071/6).
-2. At 2.048 Msps a decode after msk144_push_wideband is byte-identical to one fed the same hops through msk144_push_hops.
-3. One handle reconfigured integer -> rational -> integer matches the model each time.
-4. A synthetic 2.048 Msps cu8 scene: every planted message is decoded on its own channel and on no channel 12 kHz or more away,
-   through the API and through msk144hipdecoder --wideband-rate=2048000.
+2. One handle reconfigured integer -> rational -> integer matches the model each time.
+3. The rate rule and the tap count K x P are enforced.
+The decode at 2.048 Msps is in test_gpu_wideband_decode.py.
 """
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
-import pack77
-from msk144cudecoder_amd import synth
 import wideband_check as wc
+import wideband_gpu as wg
 from msk144cudecoder_amd import wideband as wb
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECODE_CFG = dict(center=0.0, width=500.0, step=1.0, depth=6, nbadsync_threshold=1, read_mode=2)
 RTL_RATE = 2048000
 
 
-def _offsets_64(rate):
-    lim = rate // 2 - 6000
-    rng = np.random.default_rng(rate)
-    fixed = [0, -lim, lim, 5999, -5999, 12000, -12000, 1, -1, lim - 1, -(lim - 1)]
-    rest = rng.integers(-lim, lim + 1, size=64 - len(fixed))      # off any grid
-    return np.array(fixed + list(rest), dtype=np.int32)
+def _case(rate, fmt, pushes=5):
+    """(rate, format, pushes, offsets seed, input seed, level per rail) of wideband_gpu.hops_match_the_model: seeded by the rate, at
+    the in-channel level of the 1.92 Msps tests, so that clipping stays rare."""
+    return rate, fmt, pushes, rate, 1000 + rate + len(fmt), 0.03 * np.sqrt(rate / 1920000)
 
 
-def _split(raw, rate, n_pushes):
-    out, pos = [], 0
-    for n in wb.push_sizes_for_rate(n_pushes, rate):
-        out.append(raw[pos:pos + n])
-        pos += n
-    return out
-
-
-def _hops_match_the_model(d, fmt, rate, n_pushes=5, tally=None):
-    """Configure d for (fmt, rate) and check the int8 hops of n_pushes pushes against the float64 model: within one LSB, and by
-    the near-tie rule."""
-    P, Q = wb.rate_ratio(rate)
-    offsets = _offsets_64(rate)
-    rng = np.random.default_rng(1000 + rate + len(fmt))
-    n_in = (wb.FIRST_OUT + (n_pushes - 1) * wb.HOP_OUT) * P // Q
-    sigma = 0.03 * np.sqrt(rate / 1920000)      # the in-channel level of the 1.92 Msps tests: clipping stays rare
-    x = sigma * (rng.normal(size=n_in) + 1j * rng.normal(size=n_in))
-    raw = wb.write_samples(x, fmt)
-    ref = wc.Reference(rate, offsets)
-    total = exact = 0
-    d.set_wideband(rate, offsets, fmt)
-    assert d.wideband_slot(0).size == 2 * wb.FIRST_OUT * P // Q
-    for i, part in enumerate(_split(raw, rate, n_pushes)):
-        first = i == 0
-        d.push_wideband(i % 2, part, first=first)
-        y, T, N = ref.push(wb.read_samples(part, fmt), first=first)
-        q_ref, clip_ref = wb.quantise(y, ref.gain)
-        got = np.stack([d.dump_wideband_hop(c) for c in range(len(offsets))])
-        assert got.shape == q_ref.shape
-        diff = np.abs(got.astype(np.int16) - q_ref.astype(np.int16))
-        assert diff.max() <= 1, f"push {i}: |dq| up to {diff.max()}"
-        total += diff.size
-        exact += int(np.count_nonzero(diff == 0))
-        clip = d.wideband_clip_count()
-        assert clip == clip_ref, f"push {i}"
-        rep = wc.assert_hops(got, y, T, N, ref.gain, clip, what=f"{fmt} {rate} push {i}")     # the near-tie rule (tests/wideband_check.py)
-        if tally is not None:
-            tally.add(rep)
-    d.synchronize()
-    assert exact / total >= 0.999, f"{total - exact} of {total} components differ by one LSB"
+def _model_case(hip, parity_report, rate, fmt, n_pushes=5):
+    tally = wc.Tally()
+    with hip.HipDecoder(channels=64, **wg.DECODE_CFG) as d:
+        wg.hops_match_the_model(d, *_case(rate, fmt, n_pushes), tally=tally)
+    parity_report(f"wideband_model_{rate}_{fmt}", tally.report())
 
 
 @pytest.mark.parametrize("fmt", wb.FORMATS)
 def test_hops_match_the_model_2p048_msps(hip, parity_report, fmt):
-    tally = wc.Tally()
-    with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, fmt, RTL_RATE, tally=tally)
-    parity_report(f"wideband_model_{RTL_RATE}_{fmt}", tally.report())
+    _model_case(hip, parity_report, RTL_RATE, fmt)
 
 
 @pytest.mark.parametrize("rate, n_pushes", [(250000, 5), (96125, 5), (6142000, 3)])
 def test_hops_match_the_model_other_rates(hip, parity_report, rate, n_pushes):
-    tally = wc.Tally()
-    with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, "cs16", rate, n_pushes, tally=tally)
-    parity_report(f"wideband_model_{rate}_cs16", tally.report())
+    _model_case(hip, parity_report, rate, "cs16", n_pushes)
 
 
 def test_reconfigured_integer_rational_integer(hip):
-    with hip.HipDecoder(channels=64, **DECODE_CFG) as d:
-        _hops_match_the_model(d, "cu8", 960000, 3)
-        _hops_match_the_model(d, "cs8", RTL_RATE, 3)
-        _hops_match_the_model(d, "cs16", 1920000, 3)
+    with hip.HipDecoder(channels=64, **wg.DECODE_CFG) as d:
+        wg.hops_match_the_model(d, *_case(960000, "cu8", 3))
+        wg.hops_match_the_model(d, *_case(RTL_RATE, "cs8", 3))
+        wg.hops_match_the_model(d, *_case(1920000, "cs16", 3))
 
 
 def test_rational_rate_rule_is_enforced(hip):
-    with hip.HipDecoder(channels=1, **DECODE_CFG) as d:
+    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as d:
         for rate in (2048001, 23875, 6144125):
             with pytest.raises(hip.Msk144Error) as e:
                 d.set_wideband(rate, [0], taps=np.ones(16, dtype=np.float64))
@@ -107,134 +56,3 @@ def test_rational_rate_rule_is_enforced(hip):
         with pytest.raises(hip.Msk144Error) as e:     # K x P taps, not K x floor(Fs/12000)
             d.set_wideband(RTL_RATE, [0], taps=np.full(16 * 170, 1.0 / (16 * 170)))
         assert e.value.code == -1 and "taps" in str(e.value)
-
-
-def _scene(n_out, rate, channel_offsets, ping_channels, rng, snr_db=10.0):
-    planted = {}
-    pings = []
-    for k, c in enumerate(ping_channels):
-        msg = pack77.pack_standard("CQ", "K%d%sZ" % (k % 10, "ABCDEFGHIJKLMNOPQRSTUVWXY"[k]), "FN42")
-        start = 1500 + (k * 2311) % (n_out - 6 * 864 - 3000)
-        p = synth.Ping(msg, start, 5, float(rng.uniform(-150, 150)), snr_db, float(rng.uniform(0, 6)))
-        pings.append((int(channel_offsets[c]), p))
-        planted[c] = bytes(np.asarray(msg, dtype=np.uint8))
-    return wb.synth_wideband(n_out, rate, pings, 0.05, rng, "cu8"), planted
-
-
-def _decode_wideband(d, parts):
-    recs, hops = [], []
-    for i, part in enumerate(parts):
-        s = i % 2
-        d.push_wideband(s, part, first=(i == 0))
-        hops.append(np.stack([d.dump_wideband_hop(c) for c in range(d.channels)]))
-        d.decode()
-        d.fetch_async(s)
-        r, _ = d.fetch_wait(s)
-        recs.append(np.sort(r, order=["channel", "item"]))
-    return recs, hops
-
-
-def _decode_hops(d, hops):
-    recs = []
-    for i, h in enumerate(hops):
-        s = i % 2
-        hh, first, streams, is_first = d.hop_slot(s)
-        n = h.shape[0]
-        if i == 0:
-            first[:n] = h[:, :2592].reshape(n, -1)
-            hh[:n] = h[:, 2592:].reshape(n, -1)
-        else:
-            hh[:n] = h.reshape(n, -1)
-        streams[:n] = np.arange(n)
-        is_first[:n] = 1 if i == 0 else 0
-        d.push_hops(s, n)
-        d.decode()
-        d.fetch_async(s)
-        r, _ = d.fetch_wait(s)
-        recs.append(np.sort(r, order=["channel", "item"]))
-    return recs
-
-
-def test_decode_identity_with_push_hops(hip):
-    C = 64
-    rng = np.random.default_rng(78)
-    offsets = np.array([-960000 + 30000 * i for i in range(C)], dtype=np.int32)
-    n_out = wb.FIRST_OUT + 2 * wb.HOP_OUT
-    raw, planted = _scene(n_out, RTL_RATE, offsets, list(range(0, C, 5)), rng)
-    parts = _split(raw, RTL_RATE, 3)
-    with hip.HipDecoder(channels=C, **DECODE_CFG) as a:
-        a.set_wideband(RTL_RATE, offsets, "cu8", gain=16.0)
-        rec_a, hops = _decode_wideband(a, parts)
-    with hip.HipDecoder(channels=C, **DECODE_CFG) as b:
-        rec_b = _decode_hops(b, hops)
-    assert sum(len(r) for r in rec_a) > 0
-    for ra, rb in zip(rec_a, rec_b):
-        assert ra.tobytes() == rb.tobytes()
-
-
-SCENE_DECODE_ARGS = ["--search-width=500", "--search-step=1", "--scan-depth=6", "--nbadsync-threshold=1", "--print-bits"]
-
-
-@pytest.fixture(scope="module")
-def scene(hip):
-    """2.048 Msps cu8, 1.94 s: 16 channels 110 kHz apart, each with a neighbour 12 kHz above it; +10 dB pings in 8 of the 16."""
-    rng = np.random.default_rng(2048)
-    base = [-850000 + 110000 * i for i in range(16)]
-    offsets = np.array(base + [f + 12000 for f in base], dtype=np.int32)
-    n_out = wb.FIRST_OUT + 7 * wb.HOP_OUT
-    raw, planted = _scene(n_out, RTL_RATE, offsets, [0, 2, 3, 5, 8, 11, 13, 15], rng)
-    parts = _split(raw, RTL_RATE, 8)
-    with hip.HipDecoder(channels=len(offsets), **DECODE_CFG) as d:
-        d.set_wideband(RTL_RATE, offsets, "cu8", gain=16.0)
-        recs, hops = _decode_wideband(d, parts)
-        clipped = d.wideband_clip_count()
-    return dict(offsets=offsets, raw=raw, planted=planted, recs=recs, hops=hops, clipped=clipped)
-
-
-def _check_channels(got, planted, offsets):
-    for c, msg in planted.items():
-        assert msg in got.get(c, set()), f"message planted at {offsets[c]} Hz not decoded on ch={c}"
-    for c, msgs in got.items():
-        for m in msgs:
-            owners = [pc for pc, pm in planted.items() if pm == m]
-            assert owners, f"ch={c} decoded a message nobody planted"
-            assert all(abs(int(offsets[c]) - int(offsets[pc])) < 12000 for pc in owners), f"message of ch={owners} also on ch={c}"
-
-
-def test_scene_2p048_msps_decodes_on_own_channel_only(scene):
-    assert scene["clipped"] == 0
-    got = {}
-    for r in np.concatenate(scene["recs"]):
-        got.setdefault(int(r["channel"]), set()).add(bytes(np.unpackbits(r["message"])[:77]))
-    _check_channels(got, scene["planted"], scene["offsets"])
-
-
-def _program(args, data):
-    exe = os.path.join(ROOT, "msk144cudecoder_amd", "msk144hipdecoder")
-    p = subprocess.run([exe] + args, input=data, capture_output=True, timeout=300)
-    assert p.returncode == 0, p.stderr.decode()[-2000:]
-    lines = p.stdout.decode().strip().split("\n")
-    assert lines[-1] == "Done"
-    return [re.sub(r"date=\d{14}", "date=X", l) for l in lines[:-1]], p.stderr.decode()
-
-
-def test_scene_through_the_program(scene):
-    offsets = scene["offsets"]
-    args = ["--wideband-rate=%d" % RTL_RATE, "--wideband-format=cu8", "--channel-offsets=" + ",".join(str(int(f)) for f in offsets),
-            "--wideband-gain=16"] + SCENE_DECODE_ARGS
-    lines, err = _program(args, scene["raw"].tobytes())
-    assert "resampling 512/3, filter 16 x 512 taps" in err
-    assert "wideband: 0 of %d channel I/Q components clipped" % (2 * len(offsets) * (wb.FIRST_OUT + 7 * wb.HOP_OUT)) in err
-    got = {}
-    for line in lines:
-        m = re.match(r"^\*\*\*  ch=(\d+); .*bits='([01]{77})'", line)
-        assert line.startswith("***  ch="), line
-        if not m:
-            continue
-        got.setdefault(int(m.group(1)), set()).add(bytes(int(b) for b in m.group(2)))
-    _check_channels(got, scene["planted"], offsets)
-    # the same channels as 32 interleaved 12 kHz IQ streams (the hops the channeliser wrote): the same stdout, line for line
-    C = len(offsets)
-    block = b"".join(h.tobytes() for h in scene["hops"])
-    ref, _ = _program(["--read-mode=2", "--interleaved=%d" % C] + SCENE_DECODE_ARGS, block)
-    assert lines == ref

@@ -13,47 +13,12 @@ import time
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "msk144cudecoder_amd", "host")
-PROGRAM_SOURCES = ("snr_tracker.cpp", "result_filter.cpp", "unpack77.cpp", "postprocess.cpp", "window_decoder.cpp", "stream_loop.cpp", "main.cpp")
+from host_stub import ROOT, marked_stream, shared_program, windows_seen
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    d = str(tmp_path_factory.mktemp("stubhip"))
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", os.path.join(d, "libmsk144hip.so"),
-                    os.path.join(ROOT, "tests", "stub_hip", "msk144hip_stub.cpp")], check=True)
-    srcs = [os.path.join(HOST, f) for f in PROGRAM_SOURCES]
-    out = os.path.join(d, "msk144hipdecoder_stub")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", out] + srcs + ["-L" + d, "-lmsk144hip", "-Wl,-rpath," + d], check=True)
-    return out
-
-
-def marked_stream(n_hops, tag):
-    """Stream of n_hops + 1 windows; half-window k (2592 samples) starts with 0x7777, tag + k: the stub reports, per window, the
-    second sample of both halves."""
-    x = np.zeros(5184 + n_hops * 2592, dtype=np.int16)
-    for k in range(n_hops + 2):
-        x[k * 2592] = 0x7777
-        x[k * 2592 + 1] = tag + k
-    return x
-
-
-def windows_seen(stdout, n_streams, devices=None):
-    """{channel: [(first half id, second half id), ...]} in output order, from the telemetry text of the stub's records.
-    `devices` (a dict) receives {channel: set of device ordinals whose handle decoded it}."""
-    seen = {c: [] for c in range(n_streams)}
-    for line in stdout.strip().split("\n"):
-        if line == "Done":
-            continue
-        m = re.match(r"^\*\*\*  (?:ch=(\d+); )?.*msg='([0-9A-F]+)'; $", line)
-        assert m, line
-        v = int(m.group(2), 16)
-        ch = int(m.group(1) or 0)     # the stream the host attributes the record to; v >> 32 is only its position in the compact batch
-        seen[ch].append(((v >> 16) & 0xFFFF, v & 0xFFFF))
-        if devices is not None:
-            devices.setdefault(ch, set()).add(v >> 56)
-    return seen
+def exe():
+    return shared_program()
 
 
 def test_files_of_different_length(exe, tmp_path):

@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_host_loop import HOST, PROGRAM_SOURCES, ROOT, marked_stream, windows_seen
+from host_stub import HOST, PROGRAM_SOURCES, ROOT, marked_stream, windows_seen
 
 
 def _build(tmp, flag):

@@ -169,7 +169,7 @@ def gpu_case():
 def test_the_model_passes_its_own_rule(gpu_case):
     for y, d in gpu_case["ref"]:
         q, clip = wb.quantise(y, wc.f32(gpu_case["gain"]))
-        rep = bc.check_hops(q, y, d, gpu_case["gain"], clip)
+        rep = wc.check_hops(q, y, d, gpu_case["gain"], clip)
         assert rep["ok"]
         assert rep["max_delta_lsb"] < 0.5 and rep["near_ties"] < 0.5 * rep["components"]
 
@@ -181,5 +181,5 @@ def test_slips_fail_the_rule(gpu_case, kind):
     bad = 0
     for i, ((y, d), part) in enumerate(zip(g["ref"], wc.split_pushes(g["raw"], g["rate"], g["n"]))):
         q, clip = m.push(wb.read_samples(part, g["fmt"]), first=i == 0)
-        bad += bc.check_hops(q, y, d, g["gain"], clip)["mismatches"]
+        bad += wc.check_hops(q, y, d, g["gain"], clip)["mismatches"]
     assert bad > 0, kind

@@ -173,11 +173,11 @@ def test_slip_fails_the_near_tie_rule(slip, case):
     parts = wc.split_pushes(raw, rate, wc.GRID_PUSHES)[:2]
     failed = []
     for i, part in enumerate(parts):
-        y, T, N = ref.push(wb.read_samples(part, fmt), first=i == 0)
-        ok_rep = wc.check_hops(wb.quantise(y, wc.f32(gain))[0], y, T, N, gain)
+        y, d = ref.push(wb.read_samples(part, fmt), first=i == 0)
+        ok_rep = wc.check_hops(wb.quantise(y, wc.f32(gain))[0], y, d, gain)
         assert ok_rep["ok"], ok_rep                        # the unslipped model passes its own rule
         q, clip = _slipped_push(slip, rate, offsets, taps, gain, part, fmt, i == 0, state)
-        rep = wc.check_hops(q, y, T, N, gain, clip)
+        rep = wc.check_hops(q, y, d, gain, clip)
         failed.append(not rep["ok"])
     assert all(failed), f"{slip} passes the near-tie rule on push(es) {[i for i, f in enumerate(failed) if not f]}"
 
@@ -222,21 +222,20 @@ def test_near_tie_rule_accepts_only_near_ties():
     """The rule itself: an exact tie may round either way; one LSB off elsewhere fails; the clip count may differ only by ties on
     the clip edges."""
     y = np.array([[0.5, 1.25, 127.5, -128.5, 3.0]]) / 128.0 + 0j
-    T = np.full(5, 1.0)
-    N = np.full(5, 16)
+    d = wc.delta(np.full(5, 1.0), np.full(5, 16), 1.0)
     q = wb.quantise(y, 1.0)[0]
-    assert wc.check_hops(q, y, T, N, 1.0, 2)["ok"]
+    assert wc.check_hops(q, y, d, 1.0, 2)["ok"]
     q2 = q.copy()
     q2[0, 0, 0] = 1                                        # the other side of the tie at 0.5
-    assert wc.check_hops(q2, y, T, N, 1.0, 2)["ok"]
+    assert wc.check_hops(q2, y, d, 1.0, 2)["ok"]
     q3 = q.copy()
     q3[0, 1, 0] = 2                                        # 1.25 -> 2: not a tie
-    assert not wc.check_hops(q3, y, T, N, 1.0, 2)["ok"]
-    assert wc.check_hops(q, y, T, N, 1.0, 1)["ok"]         # the model clips 127.5 -> 128, not -128.5 -> -128 (half to even)
-    assert wc.check_hops(q, y, T, N, 1.0, 3)["ok"]         # both are edge ties: 1 +- 2
-    assert not wc.check_hops(q, y, T, N, 1.0, 4)["ok"]
+    assert not wc.check_hops(q3, y, d, 1.0, 2)["ok"]
+    assert wc.check_hops(q, y, d, 1.0, 1)["ok"]         # the model clips 127.5 -> 128, not -128.5 -> -128 (half to even)
+    assert wc.check_hops(q, y, d, 1.0, 3)["ok"]         # both are edge ties: 1 +- 2
+    assert not wc.check_hops(q, y, d, 1.0, 4)["ok"]
     y4 = np.array([[200.0]]) / 128.0 + 0j
-    assert not wc.check_hops(wb.quantise(y4, 1.0)[0], y4, T[:1], N[:1], 1.0, 0)["ok"]
+    assert not wc.check_hops(wb.quantise(y4, 1.0)[0], y4, d[:1], 1.0, 0)["ok"]
 
 
 def test_delta_is_the_documented_bound():

@@ -2,7 +2,7 @@
 
 - BankReference: the float64 two-stage model (wideband.TwoStage) plus, per output, the magnitude sums that bound the device's f32
   rounding in both stages.
-- delta: the two-stage near-tie tolerance (derivation below); check_hops applies tests/wideband_check.py's rule with it.
+- The two-stage near-tie tolerance (derivation below), which BankReference.push returns for tests/wideband_check.py's check_hops.
 - Slip: the same model with one deliberate error in stage 1 or in the band rule, for the sensitivity tests.
 - CASES: the configurations the GPU tests run, so that the CPU tests check the very cases the device is held to.
 
@@ -21,7 +21,7 @@ Not fitted to measured device output.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
 
@@ -75,40 +75,6 @@ class BankReference:
             d[members] = wc.DELTA_FACTOR * wc.U32 * 128.0 * g * (np.sqrt(N + 8.0) * T2 + math.sqrt(self.K1 + STAGE1_EXTRA) * TC)
         self.T1 = T1
         return y, d
-
-
-def check_hops(got: np.ndarray, y: np.ndarray, d: np.ndarray, gain: float, clip_got: Optional[int] = None) -> Dict:
-    """tests/wideband_check.py's near-tie rule with a per-component tolerance d [C][M]: every component equals
-    clamp(rint(v), -128, 127), v = 128 gain y, unless v lies within d of a half-integer; the clip count equals the model's up to the
-    near-ties on the clip edges."""
-    g = wc.f32(gain)
-    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * g)
-    dd = np.broadcast_to(d[..., None], v.shape)
-    r = np.rint(v)
-    want = np.clip(r, -128, 127)
-    fl = np.floor(v)
-    near = np.abs(v - fl - 0.5) < dd
-    q = got.astype(np.float64)
-    alt = near & ((q == np.clip(fl, -128, 127)) | (q == np.clip(fl + 1, -128, 127)))
-    bad = (q != want) & ~alt
-    edge = near & ((np.abs(v - 127.5) < dd) | (np.abs(v + 128.5) < dd))
-    clip_model = int(np.count_nonzero((r < -128) | (r > 127)))
-    rep = dict(components=int(v.size), near_ties=int(np.count_nonzero(near)), edge_ties=int(np.count_nonzero(edge)),
-               mismatches=int(np.count_nonzero(bad)), max_delta_lsb=float(dd.max()), clip_model=clip_model, clip_device=clip_got)
-    rep["clip_ok"] = clip_got is None or abs(int(clip_got) - clip_model) <= rep["edge_ties"]
-    rep["ok"] = rep["mismatches"] == 0 and rep["clip_ok"]
-    if rep["mismatches"]:
-        i = np.argwhere(bad)[0]
-        rep["first_mismatch"] = dict(channel=int(i[0]), sample=int(i[1]), component=int(i[2]), got=int(q[tuple(i)]), v=float(v[tuple(i)]),
-                                     delta=float(dd[tuple(i)]))
-    return rep
-
-
-def assert_hops(got, y, d, gain, clip_got=None, what="") -> Dict:
-    rep = check_hops(got, y, d, gain, clip_got)
-    assert rep["mismatches"] == 0, f"{what}: {rep['mismatches']} components off the near-tie rule, first {rep.get('first_mismatch')}"
-    assert rep["clip_ok"], f"{what}: clip count {clip_got}, model {rep['clip_model']} (+-{rep['edge_ties']} edge ties)"
-    return rep
 
 
 # ---- deliberate slips ----

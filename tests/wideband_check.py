@@ -31,7 +31,7 @@ def f32(x: float) -> float:
 class Reference:
     """The float64 model of the contract with what the near-tie rule needs beside y, push by push.
 
-    push(x, first) -> (y [C][M] complex, T [M], N [M]):
+    push(x, first) -> (y [C][M] complex, d [M]): d = delta(T, N, f32(gain)), the near-tie tolerance of every output, with
       T[m] = sum_k |h_k| |x[n_m - k]| over the taps of output m's branch - the same model run once more with |h| and |x| (channel
              independent: |G[c][k]| = |h_k|), which bounds |Re| and |Im| of every product sum the device forms for output m;
       N[m] = the number of taps in output m's branch (L for Q = 1, K_r = len(h[r::Q]) otherwise)."""
@@ -43,7 +43,7 @@ class Reference:
         P, Q = self.model.P, self.model.Q
         self.branch_taps = np.array([len(self.model.taps[(mr * P) % Q::Q]) for mr in range(Q)], dtype=np.int64)
 
-    def push(self, x: np.ndarray, first: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def push(self, x: np.ndarray, first: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         if first:
             self.model.reset()
             self.mag.reset()
@@ -51,7 +51,7 @@ class Reference:
         y = self.model.filter(x)
         T = self.mag.filter(np.abs(x))[0].real
         N = self.branch_taps[(m0 + np.arange(y.shape[1])) % len(self.branch_taps)]
-        return y, T, N
+        return y, delta(T, N, f32(self.gain))
 
 
 def delta(T: np.ndarray, N: np.ndarray, gain: float) -> np.ndarray:
@@ -69,16 +69,17 @@ def delta(T: np.ndarray, N: np.ndarray, gain: float) -> np.ndarray:
     return DELTA_FACTOR * np.sqrt(N + 8.0) * U32 * (128.0 * gain) * T
 
 
-def check_hops(got: np.ndarray, y: np.ndarray, T: np.ndarray, N: np.ndarray, gain: float, clip_got: Optional[int] = None) -> Dict:
-    """The near-tie rule for one push.  got: int8 [C][M][2] device hops; y: model [C][M]; T, N: from Reference.push; gain: the
-    configured gain (compared at its f32 value, as the ABI carries it); clip_got: the device's wideband_clip_count, or None.
+def check_hops(got: np.ndarray, y: np.ndarray, d: np.ndarray, gain: float, clip_got: Optional[int] = None) -> Dict:
+    """The near-tie rule for one push.  got: int8 [C][M][2] device hops; y: model [C][M]; d: the tolerance per output, [M] or
+    [C][M], from Reference.push or BankReference.push; gain: the configured gain (compared at its f32 value, as the ABI carries
+    it); clip_got: the device's wideband_clip_count, or None.
 
-    Every component must equal clamp(rint(v), -128, 127), v = 128 gain y, unless v lies within delta (see delta()) of a
-    half-integer, where either neighbour is accepted.  The clip count must equal the model's, give or take the near-ties on the
-    127.5 / -128.5 clip edges.  Returns a report; report['ok'] says whether the push passes."""
-    g = f32(gain)
-    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * g)                     # [C][M][2]
-    d = np.broadcast_to(delta(T, N, g)[None, :, None], v.shape)
+    Every component must equal clamp(rint(v), -128, 127), v = 128 gain y, unless v lies within d (see delta(), and
+    wideband_bank_check.py for two stages) of a half-integer, where either neighbour is accepted.  The clip count must equal the
+    model's, give or take the near-ties on the 127.5 / -128.5 clip edges.  Returns a report; report['ok'] says whether the push
+    passes."""
+    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * f32(gain))             # [C][M][2]
+    d = np.broadcast_to(np.asarray(d)[..., None], v.shape)
     r = np.rint(v)
     want = np.clip(r, -128, 127)
     fl = np.floor(v)
@@ -102,8 +103,8 @@ def check_hops(got: np.ndarray, y: np.ndarray, T: np.ndarray, N: np.ndarray, gai
     return rep
 
 
-def assert_hops(got, y, T, N, gain, clip_got=None, what="") -> Dict:
-    rep = check_hops(got, y, T, N, gain, clip_got)
+def assert_hops(got, y, d, gain, clip_got=None, what="") -> Dict:
+    rep = check_hops(got, y, d, gain, clip_got)
     assert rep["mismatches"] == 0, f"{what}: {rep['mismatches']} components off the near-tie rule, first {rep.get('first_mismatch')}"
     assert rep["clip_ok"], f"{what}: clip count {clip_got}, model {rep['clip_model']} (+-{rep['edge_ties']} edge ties)"
     return rep

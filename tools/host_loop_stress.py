@@ -9,7 +9,7 @@ window of every stream once, in order.  Optionally under a sanitizer.
 import os, sys, random, subprocess, threading, time, tempfile, shutil
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
-from test_host_loop import marked_stream, windows_seen, PROGRAM_SOURCES, HOST, ROOT
+from host_stub import marked_stream, windows_seen, PROGRAM_SOURCES, HOST, ROOT
 
 d = tempfile.mkdtemp(prefix="stress_")
 san = sys.argv[2] if len(sys.argv) > 2 else ""
