@@ -33,6 +33,9 @@
  *   msk144_set_wideband ..   the CPU decimation chain in front of --read-mode=2 (rtl_sdr | csdr fir_decimate_cc ... | convert_f_s8,
  *   msk144_push_wideband     README.md of the reference), for every channel of one wideband stream at once: a down-converter
  *                            bank on the device that writes the channels' int8 I/Q hops into the hop ring (no reference counterpart)
+ *   msk144_wideband_levels,  what a bank of channels needs where a single csdr chain has one gain_ff stage: every channel's level and
+ *   msk144_set_wideband_gains, clip count of the last push, a gain per channel, and a stepped AGC that runs on the device one
+ *   msk144_set_wideband_agc  push behind the statistics (no reference counterpart)
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -378,6 +381,62 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first);
 int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out);
 /* clipped I and Q components of the last push, all channels */
 int msk144_wideband_clip_count(msk144_handle* h, int64_t* clipped);
+
+/* ---- Per-channel levels, gains and a stepped AGC (no reference counterpart) ----
+ *
+ * Across a wide band the channels' levels differ by tens of dB, and int8 (the --read-mode=2 contract) has room for about 40.  The
+ * quantiser therefore takes one scale per channel,
+ *     q = clamp(rint(128 . g_c . 2^e_c . y), -128, 127)
+ * with g_c the channel's base gain (msk144_wideband_params.gain until msk144_set_wideband_gains) and e_c its AGC exponent (0 while
+ * the AGC is off, the default).  With nothing below called, every hop, clip count and decode is what it is without these entries.
+ *
+ *   Levels:   every push records, per channel and in integers, sum_sq = the sum of I*I + Q*Q over the int8 values actually stored
+ *             (after the clamp) and clipped = its components that meet the clip rule above.  The numbers are exact and
+ *             deterministic: they equal what msk144_dump_wideband_hop gives, and the clipped counts sum to msk144_wideband_clip_count.
+ *   Gains:    msk144_set_wideband_gains sets g_c (NULL: back to params.gain, held to the same rule) and zeroes the exponents.  0 < g_c, and
+ *             128 . g_c . 2^max_exp (max_exp = 0 while the AGC is off) finite in f32, for the reason given at the gain above.
+ *   AGC:      msk144_set_wideband_agc(h, &p) switches it on, (h, NULL) off; either zeroes the exponents and hold counters.  After a
+ *             push with n = samples, S = sum_sq, k = clipped, per channel, all in 64-bit integers (csrc/wideband.h agc_step):
+ *               k . 10^6 > clip_ppm . 2n  or  S > hi_sq . 2n :  e <- max(e - 1, min_exp), quiet <- 0          (step down at once)
+ *               else S < lo_sq . 2n :  quiet <- quiet + 1; when quiet >= hold: e <- min(e + 1, max_exp), quiet <- 0
+ *               else :  quiet <- 0
+ *             and the next push is quantised with ldexpf(128 . g_c, e), a 6 dB ladder that is exact in f32.  The step runs on the
+ *             device right behind the channeliser: causal with one push of lag, no host round trip.  Only integers decide, so the
+ *             trajectory is a pure function of the reported statistics; a step multiplies the power by 4, so hi_sq > 4 . lo_sq rules
+ *             out a limit cycle on a stationary channel; fast down and slow up suits pings.  Defaults (design parameters, not
+ *             measurements): lo_sq 64 (8 LSB rms per component), hi_sq 1024 (32 LSB rms: Gaussian noise there clips below 100 ppm),
+ *             clip_ppm 1000 (0.1 %), hold 4 pushes (about 0.9 s), min_exp -20, max_exp 20.
+ *             A gain step lands on a hop boundary, which lies inside the 50 %-overlapped decode window: a window that spans a step
+ *             sees a 6 dB jump in its middle.  This applies only while the AGC is on.
+ *   Order:    gains and AGC take effect from the next push.  msk144_set_wideband resets to the scalar gain with the AGC off.  A first
+ *             push (stream restart) zeroes exponents and hold counters, so the same stream pushed twice gives the same bytes.
+ *   Refused:  MSK144_EINVAL outside wideband mode, for hi_sq <= 4 . lo_sq, hold < 1, min_exp > max_exp (or outside -126..126), a
+ *             negative lo_sq or clip_ppm, and for any 128 . g_c . 2^max_exp that is not finite in f32. */
+typedef struct msk144_wideband_level
+{
+    int64_t samples;   /* complex outputs of the last push: 5184 after a first push, else 2592 */
+    int64_t sum_sq;    /* sum of I*I + Q*Q over the stored int8 values */
+    int64_t clipped;   /* clipped components, the existing rule */
+    float gain;        /* the gain this push was quantised with (base gain x 2^exponent) */
+    int32_t exponent;  /* AGC exponent used for this push; 0 when AGC is off */
+} msk144_wideband_level;
+
+typedef struct msk144_wideband_agc
+{
+    int32_t lo_sq, hi_sq; /* mean-square window per component, LSB^2 (defaults 64, 1024) */
+    int32_t clip_ppm;     /* clipped components per million that force a step down (1000) */
+    int32_t hold;         /* pushes in a row below the window before a step up (4) */
+    int32_t min_exp, max_exp; /* (-20, 20) */
+} msk144_wideband_agc;
+
+/* the levels of the last push, out[channels], with the gain and exponent that push was quantised with, whatever was set since;
+ * synchronises like msk144_wideband_clip_count.  MSK144_ESTATE before any push */
+int msk144_wideband_levels(msk144_handle* h, msk144_wideband_level* out);
+/* gains[channels], each 0 < g; NULL: back to params.gain */
+int msk144_set_wideband_gains(msk144_handle* h, const float* gains);
+/* NULL: off */
+int msk144_set_wideband_agc(msk144_handle* h, const msk144_wideband_agc* p);
+
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
 int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);

@@ -20,9 +20,10 @@
 // 32 phases at a time, and shared by the 4 waves; the taps stream from L2 (a branch's G block is stored [channel/32][p][q][32], the
 // order the loop walks, so a wave reads 256 contiguous bytes per tap) and are reused across the 64 samples of the tile.
 //
-// Output: q = clamp(rint(128 * gain * y), -128, 127) for I and Q, written as int8 pairs straight into the hop ring's staging
-// (first push: samples 0..2591 into first_halves, 2592..5183 into hops; later pushes: hops).  A component counts as clipped when
-// its rounded value lies outside [-128, 127].
+// Output: q = clamp(rint(scale_c * y), -128, 127) for I and Q with scale_c = 128 * gain of the channel's slot (times 2^e under the
+// AGC), written as int8 pairs straight into the hop ring's staging (first push: samples 0..2591 into first_halves, 2592..5183 into
+// hops; later pushes: hops).  A component counts as clipped when its rounded value lies outside [-128, 127].  Every channel's
+// sum of I^2 + Q^2 over the stored values and its clipped components are added to levels[channel], in integers.
 //
 // Rates above 6.144 Msps (format kSubbandFormat): the kernel runs at the sub-band rate Fs/32 on the complex-f32 streams of the
 // analysis bank (bank.hip), each wave on the band of its 32 channel slots; see channelise_kernel.
@@ -54,7 +55,8 @@ template<int FMT>
 __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __restrict__ raw, const float2* __restrict__ G, const WidebandBranch* __restrict__ branches,
                                                               const int32_t* __restrict__ fmod, const float2* __restrict__ rot, int8_t* __restrict__ first_halves,
                                                               int8_t* __restrict__ hops, unsigned long long* __restrict__ clip_count, int channels, int P, int Q,
-                                                              int hist, int M, int first, long long m_base, float scale, WidebandBands bands)
+                                                              int hist, int M, int first, long long m_base, const float* __restrict__ scale,
+                                                              unsigned long long* __restrict__ levels, WidebandBands bands)
 {
     __shared__ float xs[2][kPhaseChunk][kMaxSpan];
     constexpr bool kBank = FMT == kSubbandFormat;
@@ -137,56 +139,103 @@ __global__ __launch_bounds__(kThreads) void channelise_kernel(const void* __rest
     }
     if(!active) return;
 
-    // D[row][col]: col = lane & 31 = output sample, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel within the wave
-    unsigned int clipped = 0;
+    // D[row][col]: col = lane & 31 = output sample, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel within the wave.
+    // The two samples of a lane: where they go, and the phase index of their rotation.
+    // f_c n_m / Fs = f_c (m - mr) / 12000 + f_c n0 / Fs; the second term is in G
     const int half = kHalf;
+    bool live[2];
+    int mm[2];
+    char2* dst[2];
 #pragma unroll
     for(int s = 0; s < 2; s++)
     {
         const int a = at0 + s * 32 + j;
-        if(a >= A) continue;
         const int mo = mr + Q * a;
-        // f_c n_m / Fs = f_c (m - mr) / 12000 + f_c n0 / Fs; the second term is in G
-        const int mm = static_cast<int>((m_base + static_cast<long long>(Q) * a) % kChannelRate);
-        int8_t* __restrict__ dst = hops;
+        live[s] = a < A;
+        mm[s] = static_cast<int>((m_base + static_cast<long long>(Q) * a) % kChannelRate);
+        int8_t* base_s = hops;
         int idx = mo;
-        if(first && mo < half) dst = first_halves;
+        if(first && mo < half) base_s = first_halves;
         else if(first) idx = mo - half;
-#pragma unroll
-        for(int r = 0; r < 16; r++)
-        {
-            const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
-            if(c >= channels) continue;
-            const int ch = kBank ? bands.slot_channel[c] : c;  // the channel of slot c
-            if(ch < 0) continue;
-            const float yr = s ? acc_re1[r] : acc_re0[r];
-            const float yi = s ? acc_im1[r] : acc_im0[r];
-            const int ph = (fmod[c] * mm) % kChannelRate;
-            const float2 e = rot[ph];
-            const float vr = rintf(scale * (yr * e.x - yi * e.y));
-            const float vi = rintf(scale * (yr * e.y + yi * e.x));
-            clipped += (vr < -128.0f || vr > 127.0f) + (vi < -128.0f || vi > 127.0f);
-            char2 o;
-            o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
-            o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
-            reinterpret_cast<char2*>(dst)[static_cast<size_t>(ch) * half + idx] = o;
-        }
+        dst[s] = reinterpret_cast<char2*>(base_s) + idx;
     }
+    // Row by row: quantise and store the lane's two samples, then sum the row's statistics over the 32 lanes of the half-wave that
+    // share its channel - sum of I^2 + Q^2 of the stored values in bits 0..23 (<= 2 x 2 x 128^2 a lane, 2^21 a row), clipped
+    // components from bit 24 (<= 4 a lane, 128 a row) - and leave the sum with lane j = r.  Integer sums: any order, same result.
+    unsigned int mine = 0;
+#pragma unroll
+    for(int r = 0; r < 16; r++)
+    {
+        const int c = cb32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hsel;
+        int ch = -1;
+        if(c < channels) ch = kBank ? bands.slot_channel[c] : c;  // the channel of slot c; -1: padding
+        unsigned int v = 0;
+        if(ch >= 0)
+        {
+            const int f = fmod[c];
+            const float scale_c = scale[c];
+#pragma unroll
+            for(int s = 0; s < 2; s++)
+            {
+                if(!live[s]) continue;
+                const float yr = s ? acc_re1[r] : acc_re0[r];
+                const float yi = s ? acc_im1[r] : acc_im0[r];
+                const int ph = (f * mm[s]) % kChannelRate;
+                const float2 e = rot[ph];
+                const float vr = rintf(scale_c * (yr * e.x - yi * e.y));
+                const float vi = rintf(scale_c * (yr * e.y + yi * e.x));
+                const unsigned int over = (vr < -128.0f || vr > 127.0f) + (vi < -128.0f || vi > 127.0f);
+                char2 o;
+                o.x = static_cast<signed char>(fminf(fmaxf(vr, -128.0f), 127.0f));
+                o.y = static_cast<signed char>(fminf(fmaxf(vi, -128.0f), 127.0f));
+                dst[s][static_cast<size_t>(ch) * half] = o;
+                v += static_cast<unsigned int>(o.x * o.x + o.y * o.y) + (over << 24);
+            }
+        }
+        for(int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if(j == r) mine = v;
+    }
+    // one atomic instruction per wave and tile: lane j < 16 of each half adds row j's sums to its channel's word (pack_level)
+    if(j < 16 && mine)
+    {
+        const int c = cb32 * 32 + (j & 3) + 8 * (j >> 2) + 4 * hsel;  // < channels and no padding slot, as mine != 0
+        const int ch = kBank ? bands.slot_channel[c] : c;
+        atomicAdd(&levels[ch], msk144wb::pack_level(mine & 0xffffffu, mine >> 24));
+    }
+    unsigned int clipped = j < 16 ? mine >> 24 : 0;
     for(int off = 32; off > 0; off >>= 1) clipped += __shfl_xor(clipped, off);
     if(lane == 0 && clipped) atomicAdd(clip_count, static_cast<unsigned long long>(clipped));
+}
+
+// The AGC step after a push (msk144_set_wideband_agc), one thread per channel slot: record the exponent the push was quantised
+// with, apply msk144wb::agc_step to the push's statistics, and write the slot's scale for the next push.
+__global__ void agc_step_kernel(const unsigned long long* __restrict__ levels, const int32_t* __restrict__ slot_channel, const float* __restrict__ gains,
+                                int32_t* __restrict__ exps, int32_t* __restrict__ quiet, int32_t* __restrict__ used_exps, float* __restrict__ scale, int slots,
+                                int samples, msk144wb::AgcParams p)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if(c >= slots) return;
+    const int ch = slot_channel ? slot_channel[c] : c;
+    if(ch < 0) return;
+    const unsigned long long w = levels[ch];
+    int32_t e = exps[ch], q = quiet[ch];
+    used_exps[ch] = e;
+    msk144wb::agc_step(p, samples, msk144wb::level_sum_sq(w), msk144wb::level_clipped(w), e, q);
+    exps[ch] = e;
+    quiet[ch] = q;
+    scale[c] = msk144wb::agc_scale(gains[ch], e);
 }
 
 }  // namespace
 
 void launch_channelise(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot, int8_t* first_halves,
-                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base, float gain,
-                       hipStream_t stream, WidebandBands bands)
+                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base,
+                       const float* scale, unsigned long long* levels, hipStream_t stream, WidebandBands bands)
 {
     const dim3 grid((M / Q + kTileSamples - 1) / kTileSamples, (channels + kTileChannels - 1) / kTileChannels, Q);
-    const float scale = 128.0f * gain;
     const auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, stream, raw, G, branches, fmod, rot, first_halves, hops, clip_count, channels, P, Q, hist, M, first, m_base,
-                           scale, bands);
+                           scale, levels, bands);
     };
     switch(format)
     {
@@ -195,6 +244,13 @@ void launch_channelise(const void* raw, int format, const float2* G, const Wideb
     case 2: launch(channelise_kernel<2>); break;
     default: launch(channelise_kernel<kSubbandFormat>); break;
     }
+}
+
+void launch_agc_step(const unsigned long long* levels, const int32_t* slot_channel, const float* gains, int32_t* exps, int32_t* quiet, int32_t* used_exps, float* scale,
+                     int slots, int samples, const msk144wb::AgcParams& p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(agc_step_kernel, dim3((slots + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, levels, slot_channel, gains, exps, quiet, used_exps, scale,
+                       slots, samples, p);
 }
 
 }  // namespace msk144

@@ -130,6 +130,20 @@ struct msk144_handle
         int32_t* d_fmod = nullptr;
         float2* d_rot = nullptr;  // [12000]
         unsigned long long* d_clip = nullptr;
+        // per-channel levels, gains and the stepped AGC (msk144_wideband_levels, msk144_set_wideband_gains, msk144_set_wideband_agc)
+        std::vector<float> gains;              // base gain of every channel (params.gain until msk144_set_wideband_gains)
+        std::vector<float> push_gains;         // the base gains the last push was quantised with, and whether the AGC ran behind it
+        bool push_agc = false;
+        std::vector<int32_t> slot_channel;     // the channel of every slot (-1: padding)
+        bool agc = false;
+        msk144wb::AgcParams agc_params;
+        unsigned long long* d_levels = nullptr;  // [channels] msk144wb::pack_level of the last push
+        float* d_scale = nullptr;              // [slots] what the next push is quantised with: 128 x gain x 2^exponent
+        float* d_base_scale = nullptr;         // [slots] the same at exponent 0
+        float* d_gains = nullptr;              // [channels]
+        int32_t* d_exp = nullptr;              // [channels] AGC exponent of the next push
+        int32_t* d_quiet = nullptr;            // [channels] pushes in a row below the window
+        int32_t* d_used_exp = nullptr;         // [channels] AGC exponent of the last push
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -528,6 +542,36 @@ int wb_table(msk144_handle* h, T** d, const std::vector<T>& v)
     return MSK144_OK;
 }
 
+// The base gains to the device: every slot's scale at exponent 0 (a padding slot's is never read; it gets 0), which is also what
+// the next push is quantised with, and the AGC state back to exponent 0 with no quiet pushes counted.  What the last push was
+// quantised with (push_gains, d_used_exp) stays, for msk144_wideband_levels.
+int wb_upload_gains(msk144_handle* h)
+{
+    auto& w = h->wb;
+    std::vector<float> scale(w.slot_channel.size(), 0.0f);
+    for(size_t c = 0; c < scale.size(); c++)
+        if(w.slot_channel[c] >= 0) scale[c] = msk144wb::agc_scale(w.gains[static_cast<size_t>(w.slot_channel[c])], 0);
+    // on the handle's stream, so that the next push is ordered behind them; waited for, as the sources live on this stack
+    const size_t C = w.gains.size();
+    HIP_TRY(h, hipMemcpyAsync(w.d_base_scale, scale.data(), sizeof(float) * scale.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w.d_scale, scale.data(), sizeof(float) * scale.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w.d_gains, w.gains.data(), sizeof(float) * C, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(w.d_exp, 0, sizeof(int32_t) * C, h->stream));
+    HIP_TRY(h, hipMemsetAsync(w.d_quiet, 0, sizeof(int32_t) * C, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MSK144_OK;
+}
+
+// the entries below change what the next push is quantised with: configured, and nothing of an earlier push still running
+int wb_quiesce(msk144_handle* h, const char* who)
+{
+    if(!h) return fail(h, MSK144_EINVAL, "null argument");
+    if(!h->wb.configured) return fail(h, MSK144_EINVAL, std::string(who) + " needs wideband mode (msk144_set_wideband)");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MSK144_OK;
+}
+
 // Every buffer of the configuration whose shape h->wb already holds; on failure the caller releases what was allocated
 int wb_allocate(msk144_handle* h, const WbSlots& sl, const WbTables& t, const std::vector<double>& h1)
 {
@@ -543,6 +587,15 @@ int wb_allocate(msk144_handle* h, const WbSlots& sl, const WbTables& t, const st
         return rc;
     if((rc = dev_alloc(h, w.mem, &w.d_clip, 1)) != MSK144_OK) return rc;
     HIP_TRY(h, hipMemset(w.d_clip, 0, sizeof(unsigned long long)));
+    const size_t C = w.gains.size(), S = w.slot_channel.size();
+    if((rc = dev_alloc(h, w.mem, &w.d_levels, C)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_scale, S)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_base_scale, S)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_gains, C)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_exp, C)) != MSK144_OK || (rc = dev_alloc(h, w.mem, &w.d_quiet, C)) != MSK144_OK ||
+       (rc = dev_alloc(h, w.mem, &w.d_used_exp, C)) != MSK144_OK)
+        return rc;
+    HIP_TRY(h, hipMemset(w.d_levels, 0, sizeof(unsigned long long) * C));
+    HIP_TRY(h, hipMemset(w.d_used_exp, 0, sizeof(int32_t) * C));
+    if((rc = wb_upload_gains(h)) != MSK144_OK) return rc;
     if(!w.bank) return MSK144_OK;
     if((rc = wb_table(h, &w.d_h1, std::vector<float>(h1.begin(), h1.end()))) != MSK144_OK || (rc = wb_table(h, &w.d_bands, sl.band_list)) != MSK144_OK ||
        (rc = wb_table(h, &w.d_tw, unit_circle(msk144wb::kBankBands, 1.0))) != MSK144_OK || (rc = wb_table(h, &w.d_wave_band, sl.wave_band)) != MSK144_OK ||
@@ -1297,6 +1350,8 @@ int msk144_set_wideband_ex(msk144_handle* h, const msk144_wideband_params* wp, c
     w.slots = static_cast<int>(sl.slot_channel.size());
     w.format = wp->format;
     w.gain = wp->gain;
+    w.gains.assign(static_cast<size_t>(wp->num_offsets), wp->gain);
+    w.slot_channel = sl.slot_channel;
     if((rc = wb_allocate(h, sl, t, h1)) != MSK144_OK)
     {
         wb_release(h);
@@ -1354,6 +1409,14 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemsetAsync(w.d_clip, 0, sizeof(unsigned long long), h->stream);
+    if(e == hipSuccess) e = hipMemsetAsync(w.d_levels, 0, sizeof(unsigned long long) * C, h->stream);
+    if(w.agc && first)
+    {
+        // a stream restart: exponent 0 and no quiet pushes counted, so that the same stream pushed twice gives the same bytes
+        if(e == hipSuccess) e = hipMemcpyAsync(w.d_scale, w.d_base_scale, sizeof(float) * w.slots, hipMemcpyDeviceToDevice, h->stream);
+        if(e == hipSuccess) e = hipMemsetAsync(w.d_exp, 0, sizeof(int32_t) * C, h->stream);
+        if(e == hipSuccess) e = hipMemsetAsync(w.d_quiet, 0, sizeof(int32_t) * C, h->stream);
+    }
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
     ev_begin(h);
@@ -1369,9 +1432,13 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         bands = WidebandBands{w.d_wave_band, w.d_slot_channel, w.stride};
     }
     launch_channelise(in, format, w.d_G, w.d_branches, w.d_fmod, w.d_rot, reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), w.d_clip, w.slots,
-                      w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.gain, h->stream, bands);
+                      w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.d_scale, w.d_levels, h->stream, bands);
+    if(w.agc)
+        launch_agc_step(w.d_levels, w.bank ? w.d_slot_channel : nullptr, w.d_gains, w.d_exp, w.d_quiet, w.d_used_exp, w.d_scale, w.slots, M, w.agc_params, h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
+    w.push_gains = w.gains;
+    w.push_agc = w.agc;
     w.m_next += M;
     w.n_next += frames;
     w.last_frames = frames;
@@ -1425,6 +1492,66 @@ int msk144_wideband_clip_count(msk144_handle* h, int64_t* clipped)
     unsigned long long v = 0;
     HIP_TRY(h, hipMemcpy(&v, h->wb.d_clip, sizeof(v), hipMemcpyDeviceToHost));
     *clipped = static_cast<int64_t>(v);
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_gains(msk144_handle* h, const float* gains)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_gains");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    const int32_t top = w.agc ? w.agc_params.max_exp : 0;
+    if(gains)
+        for(size_t c = 0; c < w.gains.size(); c++)
+            if(!msk144wb::gain_ok(gains[c], top))
+                return fail(h, MSK144_EINVAL, "gain of channel " + std::to_string(c) + " must be positive with 128 x gain x 2^max_exp finite in f32");
+    if(!gains && !msk144wb::gain_ok(w.gain, top))
+        return fail(h, MSK144_EINVAL, "the configured gain cannot be restored while the AGC is on: 128 x gain x 2^max_exp is not finite in f32");
+    if(gains) w.gains.assign(gains, gains + w.gains.size());
+    else w.gains.assign(w.gains.size(), w.gain);
+    return wb_upload_gains(h);
+}
+
+int msk144_set_wideband_agc(msk144_handle* h, const msk144_wideband_agc* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_agc");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(p)
+    {
+        const msk144wb::AgcParams ap{p->lo_sq, p->hi_sq, p->clip_ppm, p->hold, p->min_exp, p->max_exp};
+        const std::string why = msk144wb::check_agc(ap);
+        if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+        for(size_t c = 0; c < w.gains.size(); c++)
+            if(!msk144wb::gain_ok(w.gains[c], ap.max_exp))
+                return fail(h, MSK144_EINVAL, "128 x gain x 2^max_exp of channel " + std::to_string(c) + " is not finite in f32");
+        w.agc_params = ap;
+    }
+    w.agc = p != nullptr;
+    return wb_upload_gains(h);  // exponent 0, nothing counted: the AGC starts, or the base gains hold again
+}
+
+int msk144_wideband_levels(msk144_handle* h, msk144_wideband_level* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, "msk144_wideband_levels needs wideband mode (msk144_set_wideband)");
+    if(!w.started) return fail(h, MSK144_ESTATE, "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t C = w.gains.size();
+    std::vector<unsigned long long> words(C);
+    std::vector<int32_t> exps(C, 0);
+    HIP_TRY(h, hipMemcpy(words.data(), w.d_levels, sizeof(unsigned long long) * C, hipMemcpyDeviceToHost));
+    if(w.push_agc) HIP_TRY(h, hipMemcpy(exps.data(), w.d_used_exp, sizeof(int32_t) * C, hipMemcpyDeviceToHost));
+    for(size_t c = 0; c < C; c++)
+    {
+        out[c].samples = w.last_first ? kWindowSamples : kHopSamples;
+        out[c].sum_sq = msk144wb::level_sum_sq(words[c]);
+        out[c].clipped = msk144wb::level_clipped(words[c]);
+        out[c].gain = ldexpf(w.push_gains[c], exps[c]);
+        out[c].exponent = exps[c];
+    }
     return MSK144_OK;
 }
 

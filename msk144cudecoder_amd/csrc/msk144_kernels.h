@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "msk144_protocol.h"
+#include "wideband.h"
 
 namespace msk144
 {
@@ -100,10 +101,17 @@ struct WidebandBranch
 // 0 cu8, 1 cs8, 2 cs16); branches[0..Q) by output residue mr, G their blocks one after another; fmod[c] = f_c mod 12000 in 0..11999;
 // rot[r] = e^{-j2pi r/12000}.  G carries each branch's constant output rotation e^{-j2pi (f_c n0 mod Fs)/Fs}, so the kernel rotates
 // by (f_c (m - mr)) mod 12000.  Writes the int8 I/Q of output samples m_base .. m_base+M-1 of every channel into the hop ring
-// staging (M = 5184 with first != 0: the first 2592 into first_halves) and adds the clipped components to *clip_count.
+// staging (M = 5184 with first != 0: the first 2592 into first_halves), quantised with scale[c] (128 x the gain of slot c), and adds
+// the clipped components to *clip_count and every channel's statistics to levels[channel] (msk144wb::pack_level; csrc/wideband.h).
 void launch_channelise(const void* raw, int format, const float2* G, const WidebandBranch* branches, const int32_t* fmod, const float2* rot, int8_t* first_halves,
-                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base, float gain,
-                       hipStream_t stream, WidebandBands bands = {});
+                       int8_t* hops, unsigned long long* clip_count, int channels, int P, int Q, int hist, int M, int first, long long m_base,
+                       const float* scale, unsigned long long* levels, hipStream_t stream, WidebandBands bands = {});
+
+// the AGC step after a push of `samples` outputs per channel (channelise.hip): used_exps[ch] = exps[ch], then msk144wb::agc_step on
+// levels[ch] moves (exps[ch], quiet[ch]) and scale[slot] = 128 gains[ch] 2^exps[ch] is what the next push is quantised with.
+// slot_channel: the channel of each slot (NULL: slot c is channel c).
+void launch_agc_step(const unsigned long long* levels, const int32_t* slot_channel, const float* gains, int32_t* exps, int32_t* quiet, int32_t* used_exps, float* scale,
+                     int slots, int samples, const msk144wb::AgcParams& p, hipStream_t stream);
 
 // the analysis bank in front of the channeliser above 6.144 Msps (bank.hip): raw = the L1-1 history samples then 32 x frames new
 // ones (format 0 cu8, 1 cs8, 2 cs16); h1 = the L1 = 64 K1 bank taps (f32); bands[j] = the occupied band k mod 64 of stream j;

@@ -147,6 +147,72 @@ inline std::vector<double> design_bank_taps(int64_t rate_hz, int K1)
     return kaiser_sinc(kBankBands * K1, 0.5 * ((fs / 128.0 + kPassHz) + (3.0 * fs / 128.0 - kStopHz)) / fs, kBankKaiserBeta);
 }
 
+// ---- per-channel levels and the stepped AGC (msk144_set_wideband_gains, msk144_set_wideband_agc, msk144_wideband_levels) ----
+
+#ifdef __HIP__
+#define MSK144WB_HD __host__ __device__
+#else
+#define MSK144WB_HD
+#endif
+
+// msk144_wideband_agc, field for field.  The defaults are design parameters, not measurements: a window of 8 .. 32 LSB rms per
+// component (Gaussian noise at 32 LSB rms clips below 100 ppm), 0.1 % clipped components, 4 quiet pushes (about 0.9 s) before a
+// step up, +-20 steps of 6 dB.
+struct AgcParams
+{
+    int32_t lo_sq = 64, hi_sq = 1024;
+    int32_t clip_ppm = 1000;
+    int32_t hold = 4;
+    int32_t min_exp = -20, max_exp = 20;
+};
+
+// One channel's statistics of a push live in one 64-bit word, so that one atomic per channel, half-wave and tile carries both:
+// sum_sq (< 2^28 per push) in the low half, clipped components (<= 10368) in the high half.
+MSK144WB_HD inline uint64_t pack_level(uint32_t sum_sq, uint32_t clipped) { return static_cast<uint64_t>(sum_sq) | (static_cast<uint64_t>(clipped) << 32); }
+MSK144WB_HD inline int64_t level_sum_sq(uint64_t w) { return static_cast<int64_t>(w & 0xffffffffull); }
+MSK144WB_HD inline int64_t level_clipped(uint64_t w) { return static_cast<int64_t>(w >> 32); }
+
+// The step rule, once: after a push of n complex outputs with S = sum of I^2 + Q^2 over the stored int8 values and k clipped
+// components, channel state (e, quiet) moves one 6 dB step down at once (too many clipped, or above the window), one step up after
+// `hold` pushes in a row below the window.  Only integers decide (64-bit products), so the trajectory is a pure function of the
+// reported statistics; hi_sq > 4 lo_sq (a step multiplies the power by 4) rules out a limit cycle on a stationary channel.
+MSK144WB_HD inline void agc_step(const AgcParams& p, int64_t n, int64_t S, int64_t k, int32_t& e, int32_t& quiet)
+{
+    if(k * 1000000 > static_cast<int64_t>(p.clip_ppm) * 2 * n || S > static_cast<int64_t>(p.hi_sq) * 2 * n)
+    {
+        e = e - 1 > p.min_exp ? e - 1 : p.min_exp;
+        quiet = 0;
+    }
+    else if(S < static_cast<int64_t>(p.lo_sq) * 2 * n)
+    {
+        if(++quiet >= p.hold)
+        {
+            e = e + 1 < p.max_exp ? e + 1 : p.max_exp;
+            quiet = 0;
+        }
+    }
+    else quiet = 0;
+}
+
+// the scale a channel with base gain g is quantised with at exponent e: a 6 dB ladder is exact in f32
+MSK144WB_HD inline float agc_scale(float g, int32_t e) { return ldexpf(128.0f * g, e); }
+
+// The rules of msk144_set_wideband_agc that need no handle.  Empty string = valid.
+inline std::string check_agc(const AgcParams& p)
+{
+    if(p.lo_sq < 0 || static_cast<int64_t>(p.hi_sq) <= 4 * static_cast<int64_t>(p.lo_sq))
+        return "AGC window needs 0 <= lo_sq and hi_sq > 4 x lo_sq (one 6 dB step multiplies the power by 4)";
+    if(p.clip_ppm < 0) return "AGC clip_ppm must not be negative";
+    if(p.hold < 1) return "AGC hold must be at least 1 push";
+    if(p.min_exp > p.max_exp) return "AGC needs min_exp <= max_exp";
+    if(p.min_exp < -126 || p.max_exp > 126) return "AGC exponents must lie within -126..126";
+    return std::string();
+}
+
+// a per-channel gain the quantiser takes at every exponent up to max_exp: 0 < g, and 128 g 2^max_exp finite in f32 (an infinite
+// scale would turn an exact 0 into NaN)
+inline bool gain_ok(float g, int32_t max_exp) { return g > 0.0f && std::isfinite(g) && std::isfinite(agc_scale(g, max_exp)); }
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {

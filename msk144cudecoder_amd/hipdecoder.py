@@ -13,6 +13,7 @@ from typing import Optional
 import numpy as np
 
 from .protocol import ITEM_BYTES
+from .wideband import AGC_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc; msk144_wideband_level
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmsk144hip.so")
@@ -26,6 +27,11 @@ WB_FORMATS = {"cu8": 0, "cs8": 1, "cs16": 2}   # msk144_wideband_params.format
 class WidebandParams(C.Structure):
     _fields_ = [("rate_hz", C.c_int64), ("format", C.c_int32), ("taps_per_phase", C.c_int32), ("gain", C.c_float), ("num_taps", C.c_int32),
                 ("taps", C.POINTER(C.c_double)), ("offsets_hz", C.POINTER(C.c_int32)), ("num_offsets", C.c_int32)]
+
+
+class WidebandAgc(C.Structure):
+    """msk144_wideband_agc; AGC_DEFAULTS holds the defaults of include/msk144hip.h."""
+    _fields_ = [("lo_sq", C.c_int32), ("hi_sq", C.c_int32), ("clip_ppm", C.c_int32), ("hold", C.c_int32), ("min_exp", C.c_int32), ("max_exp", C.c_int32)]
 
 
 class Params(C.Structure):
@@ -84,6 +90,9 @@ PROTOTYPES = {
     "msk144_wideband_clip_count": ([_vp, _P(C.c_int64)], C.c_int),
     "msk144_set_wideband_ex": ([_vp, _P(WidebandParams), _P(C.c_double), _i32], C.c_int),
     "msk144_dump_wideband_band": ([_vp, _i32, _vp], C.c_int),
+    "msk144_wideband_levels": ([_vp, _vp], C.c_int),
+    "msk144_set_wideband_gains": ([_vp, _P(C.c_float)], C.c_int),
+    "msk144_set_wideband_agc": ([_vp, _P(WidebandAgc)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -368,6 +377,35 @@ class HipDecoder:
         v = C.c_int64()
         self._chk(self.L.msk144_wideband_clip_count(self.h, C.byref(v)))
         return int(v.value)
+
+    def set_wideband_gains(self, gains=None):
+        """One gain per channel from the next push on (None: back to the scalar gain of set_wideband); zeroes the AGC exponents."""
+        if gains is None:
+            self._chk(self.L.msk144_set_wideband_gains(self.h, None))
+            return
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if g.size != self.channels:
+            raise ValueError(f"one gain per channel: {self.channels}, got {g.size}")
+        self._chk(self.L.msk144_set_wideband_gains(self.h, g.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_wideband_agc(self, params=True, **kw):
+        """The stepped AGC from the next push on: set_wideband_agc() takes the defaults (AGC_DEFAULTS), keywords replace single ones
+        (lo_sq, hi_sq, clip_ppm, hold, min_exp, max_exp); set_wideband_agc(None) switches it off."""
+        if params is None:
+            self._chk(self.L.msk144_set_wideband_agc(self.h, None))
+            return
+        p = dict(AGC_DEFAULTS)
+        if isinstance(params, dict):
+            p.update(params)
+        p.update(kw)
+        a = WidebandAgc(**{k: int(v) for k, v in p.items()})
+        self._chk(self.L.msk144_set_wideband_agc(self.h, C.byref(a)))
+
+    def wideband_levels(self) -> np.ndarray:
+        """LEVEL_DTYPE [channels]: samples, sum_sq, clipped, gain and AGC exponent of the last push."""
+        out = np.zeros(self.channels, dtype=LEVEL_DTYPE)
+        self._chk(self.L.msk144_wideband_levels(self.h, _ptr(out)))
+        return out
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

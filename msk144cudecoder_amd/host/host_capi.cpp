@@ -51,6 +51,27 @@ int msk144host_wideband_check(int64_t rate_hz, int format, int K, float gain, co
     return s.empty() ? 0 : -1;
 }
 
+// The AGC step rule (csrc/wideband.h agc_step, the function the device runs): p = {lo_sq, hi_sq, clip_ppm, hold, min_exp, max_exp};
+// (*e, *quiet) move by one push of n outputs with sum_sq S and k clipped components.  Returns 0, or -1 for parameters that
+// msk144_set_wideband_agc refuses (the text in why when given).
+int msk144host_wideband_agc_step(const int32_t* p, int64_t n, int64_t S, int64_t k, int32_t* e, int32_t* quiet, char* why, int why_len)
+{
+    const msk144wb::AgcParams ap{p[0], p[1], p[2], p[3], p[4], p[5]};
+    const std::string s = msk144wb::check_agc(ap);
+    if(why && why_len > 0)
+    {
+        std::strncpy(why, s.c_str(), static_cast<size_t>(why_len) - 1);
+        why[why_len - 1] = 0;
+    }
+    if(!s.empty()) return -1;
+    msk144wb::agc_step(ap, n, S, k, *e, *quiet);
+    return 0;
+}
+
+// whether msk144_set_wideband_gains takes gain g with the AGC's top exponent max_exp (0: AGC off), and the f32 scale at exponent e
+int msk144host_wideband_gain_ok(float g, int32_t max_exp) { return msk144wb::gain_ok(g, max_exp) ? 1 : 0; }
+float msk144host_wideband_agc_scale(float g, int32_t e) { return msk144wb::agc_scale(g, e); }
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

@@ -69,6 +69,8 @@ void show_help(const char* prog)
     std::cout << "                   --channel-offsets=F1,F2,... Channel centres in integer Hz from the wideband centre, |F| <= HZ/2 - 6000." << std::endl;
     std::cout << "                   --channel-grid=F:STEP:N     The same as N offsets F, F+STEP, ..." << std::endl;
     std::cout << "                   --wideband-gain=G           Gain before each channel's int8 I/Q (the csdr gain_ff stage). Default=100." << std::endl;
+    std::cout << "                   --wideband-gain=auto[:G0]   Stepped AGC per channel, on the GPU, one hop behind the levels: 6 dB down at once when more than 0.1 % of a hop's components clip or its level exceeds 32 LSB rms, 6 dB up after 4 hops below 8 LSB rms, within G0 x 2^-20 .. G0 x 2^20. G0 default=100. A step lands on a hop boundary." << std::endl;
+    std::cout << "                   --wideband-levels           With --wideband-rate: at the end, on stderr, one line per channel - rms level in LSB over the run, clipped components, last gain, lowest and highest AGC step - and the three most clipped and three quietest channels." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -180,6 +182,7 @@ int main(int argc, char* const argv[])
                                            {"channel-grid", required_argument, 0, 0},
                                            {"wideband-gain", required_argument, 0, 0},
                                            {"taps-per-phase", required_argument, 0, 0},
+                                           {"wideband-levels", no_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -228,6 +231,7 @@ int main(int argc, char* const argv[])
         case 25:
         case 26:
         case 27:
+        case 28:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -236,12 +240,8 @@ int main(int argc, char* const argv[])
             else if(idx == 23) good = parse_wideband_format(optarg, wbo.format);
             else if(idx == 24) good = parse_offset_list(optarg, wbo.offsets), wbo.offset_sources++;
             else if(idx == 25) good = parse_offset_grid(optarg, wbo.offsets), wbo.offset_sources++;
-            else if(idx == 26)
-            {
-                char* end = nullptr;
-                wbo.gain = std::strtof(optarg, &end);
-                good = end && *end == 0 && end != optarg;
-            }
+            else if(idx == 26) good = parse_wideband_gain(optarg, wbo);
+            else if(idx == 28) wbo.levels = true;
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + optarg + "'";
             break;
@@ -296,7 +296,7 @@ int main(int argc, char* const argv[])
     if(wideband)
     {
         std::string err;
-        if(!wb_api.load(err))
+        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
@@ -410,7 +410,7 @@ int main(int argc, char* const argv[])
                       << msk144wb::kDefaultBankTapsPerBand << " x " << msk144wb::kBankBands << " taps; stage 2: ";
         }
         std::cerr << (rr.Q == 1 ? "decimation " + std::to_string(rr.P) : "resampling " + std::to_string(rr.P) + "/" + std::to_string(rr.Q)) << ", filter "
-                  << wbo.taps_per_phase << " x " << rr.P << " taps, gain " << wbo.gain << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
+                  << wbo.taps_per_phase << " x " << rr.P << " taps, gain " << wbo.gain << (wbo.agc ? " x 2^e (AGC, e within +-20)" : "") << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
         for(int c = 0; c < nch; c++) std::cerr << "msk144hipdecoder: ch=" << c << " offset " << wbo.offsets[static_cast<size_t>(c)] << " Hz" << std::endl;
         const std::vector<double> taps = msk144wb::design_taps_rate(rate2, wbo.taps_per_phase);
         msk144_wideband_params wp{};
@@ -426,6 +426,16 @@ int main(int argc, char* const argv[])
         {
             std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
             return 2;
+        }
+        if(wbo.agc)
+        {
+            const msk144wb::AgcParams d;
+            const msk144_wideband_agc agc{d.lo_sq, d.hi_sq, d.clip_ppm, d.hold, d.min_exp, d.max_exp};
+            if(wb_api.set_agc(dec.handle(), &agc) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
         }
     }
     if(shares.size() > 1)
@@ -499,7 +509,7 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
-        if(wideband) loops[i]->use_wideband(&wb_api);
+        if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
         {
@@ -600,7 +610,36 @@ int main(int argc, char* const argv[])
         const long long clipped = loops[0]->wideband_clipped(), all = loops[0]->wideband_components();
         std::cerr << "msk144hipdecoder: wideband: " << clipped << " of " << all << " channel I/Q components clipped to int8";
         if(all) std::cerr << " (" << 100.0 * static_cast<double>(clipped) / static_cast<double>(all) << " %)";
-        std::cerr << (clipped ? "; lower --wideband-gain" : "") << std::endl;
+        std::cerr << (clipped && !wbo.agc ? "; lower --wideband-gain" : "") << std::endl;
+        if(wbo.levels)
+        {
+            const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();
+            std::vector<int> by_clip, by_rms;
+            for(int c = 0; c < static_cast<int>(lv.size()); c++)
+            {
+                fprintf(stderr, "msk144hipdecoder: wideband level ch=%d offset=%d Hz rms=%.2f LSB clipped=%lld gain=%g exp=%d..%d\n", c, wbo.offsets[static_cast<size_t>(c)],
+                        lv[static_cast<size_t>(c)].rms(), lv[static_cast<size_t>(c)].clipped, static_cast<double>(lv[static_cast<size_t>(c)].gain),
+                        lv[static_cast<size_t>(c)].min_exp, lv[static_cast<size_t>(c)].max_exp);
+                by_clip.push_back(c);
+                by_rms.push_back(c);
+            }
+            std::stable_sort(by_clip.begin(), by_clip.end(), [&](int a, int b) { return lv[static_cast<size_t>(a)].clipped > lv[static_cast<size_t>(b)].clipped; });
+            std::stable_sort(by_rms.begin(), by_rms.end(), [&](int a, int b) { return lv[static_cast<size_t>(a)].rms() < lv[static_cast<size_t>(b)].rms(); });
+            std::string line = "msk144hipdecoder: wideband levels: most clipped";
+            char buf[96];
+            for(size_t i = 0; i < 3 && i < by_clip.size(); i++)
+            {
+                snprintf(buf, sizeof(buf), " ch=%d (%lld)", by_clip[i], lv[static_cast<size_t>(by_clip[i])].clipped);
+                line += buf;
+            }
+            line += "; quietest";
+            for(size_t i = 0; i < 3 && i < by_rms.size(); i++)
+            {
+                snprintf(buf, sizeof(buf), " ch=%d (%.2f LSB)", by_rms[i], lv[static_cast<size_t>(by_rms[i])].rms());
+                line += buf;
+            }
+            std::cerr << line << std::endl;
+        }
     }
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)

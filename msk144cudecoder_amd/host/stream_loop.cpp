@@ -5,6 +5,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstring>
 #include <iostream>
@@ -208,6 +209,7 @@ int DeviceLoop::join()
     {
         int64_t clipped = 0;
         if(wb_->clip(dec_.handle(), &clipped) == MSK144_OK) wb_clipped_ += clipped;
+        if(wb_read_levels_) read_wideband_levels();
         wb_components_ += wb_pending_components_;
         wb_pending_components_ = 0;
     }
@@ -236,6 +238,11 @@ bool DeviceLoop::submit_wideband(Batch& b)
         }
         wb_clipped_ += clipped;
         wb_components_ += wb_pending_components_;
+        if(wb_read_levels_ && !read_wideband_levels())
+        {
+            fail(msk144_last_error(dec_.handle()));
+            return false;
+        }
     }
     memcpy(buf, wb_block_.data(), wb_block_.size());
     const bool first = wb_first_;
@@ -257,6 +264,27 @@ bool DeviceLoop::submit_wideband(Batch& b)
     wb_first_ = false;
     b.assemble_ms = ms_between(a0, a1);
     b.submit_ms = ms_between(a1, Clock::now());
+    return true;
+}
+
+// --wideband-levels: the levels of the push just made (read where its clip count is read), summed per channel
+bool DeviceLoop::read_wideband_levels()
+{
+    wb_level_buf_.resize(static_cast<size_t>(nch_));
+    if(wb_->levels(dec_.handle(), wb_level_buf_.data()) != MSK144_OK) return false;
+    const bool fresh = wb_levels_.empty();
+    wb_levels_.resize(static_cast<size_t>(nch_));
+    for(int c = 0; c < nch_; c++)
+    {
+        const msk144_wideband_level& v = wb_level_buf_[static_cast<size_t>(c)];
+        ChannelLevel& a = wb_levels_[static_cast<size_t>(c)];
+        a.samples += v.samples;
+        a.sum_sq += v.sum_sq;
+        a.clipped += v.clipped;
+        a.gain = v.gain;
+        a.min_exp = fresh ? v.exponent : std::min(a.min_exp, static_cast<int>(v.exponent));
+        a.max_exp = fresh ? v.exponent : std::max(a.max_exp, static_cast<int>(v.exponent));
+    }
     return true;
 }
 

@@ -14,6 +14,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -92,7 +93,13 @@ public:
     void use_feed() { fed_ = true; }
     // --wideband-rate: the blocks arrive through feed_raw() and are wideband samples - one push of the channeliser, which writes
     // the hop of every stream of this loop on the device (msk144_set_wideband has been called on decoder().handle())
-    void use_wideband(const WidebandApi* api) { fed_ = true; wb_ = api; }
+    // levels: msk144_wideband_levels is read once per push and accumulated per channel (--wideband-levels)
+    void use_wideband(const WidebandApi* api, bool levels = false)
+    {
+        fed_ = true;
+        wb_ = api;
+        wb_read_levels_ = levels;
+    }
 
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
@@ -104,6 +111,15 @@ public:
     // clipped I/Q components of the channeliser output over the run, and all components written (valid after join())
     long long wideband_clipped() const { return wb_clipped_; }
     long long wideband_components() const { return wb_components_; }
+    // --wideband-levels: every channel's statistics summed over the run, the gain of its last push, the AGC exponents it saw
+    struct ChannelLevel
+    {
+        long long samples = 0, sum_sq = 0, clipped = 0;
+        float gain = 0.0f;
+        int min_exp = 0, max_exp = 0;
+        double rms() const { return samples ? std::sqrt(static_cast<double>(sum_sq) / (2.0 * static_cast<double>(samples))) : 0.0; }
+    };
+    const std::vector<ChannelLevel>& wideband_levels() const { return wb_levels_; }
     int join();  // 0, or 2 after a library failure (already logged)
 
     const LoopStats& stats() const { return stats_; }
@@ -149,6 +165,7 @@ private:
     void fail(const std::string& what);
     bool enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream);
     bool submit_wideband(Batch& b);
+    bool read_wideband_levels();
 
     WindowDecoder dec_;
     const int nch_, base_, device_;
@@ -160,6 +177,9 @@ private:
     std::vector<unsigned char> wb_block_;  // the push the ingest thread has taken from the queue
     bool wb_first_ = true;
     long long wb_clipped_ = 0, wb_components_ = 0, wb_pending_components_ = 0;
+    bool wb_read_levels_ = false;
+    std::vector<ChannelLevel> wb_levels_;
+    std::vector<msk144_wideband_level> wb_level_buf_;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;
     std::vector<Stream> st_;

@@ -22,6 +22,20 @@ struct WidebandApi
     int (*slot)(msk144_handle*, int32_t, void**, size_t*) = nullptr;
     int (*push)(msk144_handle*, int32_t, int32_t) = nullptr;
     int (*clip)(msk144_handle*, int64_t*) = nullptr;
+    // --wideband-gain=auto, --wideband-levels: resolved only when one of them is given (load_levels)
+    int (*levels)(msk144_handle*, msk144_wideband_level*) = nullptr;
+    int (*set_gains)(msk144_handle*, const float*) = nullptr;
+    int (*set_agc)(msk144_handle*, const msk144_wideband_agc*) = nullptr;
+
+    bool load_levels(std::string& err)
+    {
+        levels = reinterpret_cast<decltype(levels)>(dlsym(RTLD_DEFAULT, "msk144_wideband_levels"));
+        set_gains = reinterpret_cast<decltype(set_gains)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_gains"));
+        set_agc = reinterpret_cast<decltype(set_agc)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_agc"));
+        if(levels && set_gains && set_agc) return true;
+        err = "the loaded libmsk144hip has no per-channel levels or AGC (msk144_wideband_levels): --wideband-gain=auto and --wideband-levels need them";
+        return false;
+    }
 
     bool load(std::string& err)
     {
@@ -41,6 +55,8 @@ struct WidebandOptions
     int format = msk144wb::kCu8;
     int taps_per_phase = msk144wb::kDefaultTapsPerPhase;
     float gain = msk144wb::kDefaultGain;
+    bool agc = false;     // --wideband-gain=auto[:G0]: the stepped AGC with the default parameters, base gain `gain`
+    bool levels = false;  // --wideband-levels: the per-channel table in the summary
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -54,6 +70,24 @@ inline bool parse_int(const std::string& s, long long& v)
     errno = 0;
     v = std::strtoll(s.c_str(), &end, 10);
     return errno == 0 && end && *end == 0;
+}
+
+// "G" or "auto[:G0]"
+inline bool parse_wideband_gain(const std::string& s, WidebandOptions& w)
+{
+    std::string g = s;
+    w.agc = false;
+    if(s.compare(0, 4, "auto") == 0)
+    {
+        w.agc = true;
+        w.gain = msk144wb::kDefaultGain;
+        if(s.size() == 4) return true;
+        if(s[4] != ':') return false;
+        g = s.substr(5);
+    }
+    char* end = nullptr;
+    w.gain = std::strtof(g.c_str(), &end);
+    return !g.empty() && end && *end == 0;
 }
 
 inline bool parse_wideband_format(const std::string& s, int& fmt)
@@ -103,9 +137,14 @@ inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out
 inline std::string check_wideband_options(const WidebandOptions& w)
 {
     if(!w.parse_error.empty()) return w.parse_error;
-    if(w.rate_hz <= 0) return "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
+    if(w.rate_hz <= 0)
+        return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
+                        : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
     if(w.offset_sources != 1) return "--wideband-rate needs exactly one of --channel-offsets=f1,f2,... or --channel-grid=first:step:count";
-    return msk144wb::check_config(w.rate_hz, w.format, w.taps_per_phase, w.gain, w.offsets.data(), static_cast<int>(w.offsets.size()));
+    const std::string why = msk144wb::check_config(w.rate_hz, w.format, w.taps_per_phase, w.gain, w.offsets.data(), static_cast<int>(w.offsets.size()));
+    if(why.empty() && w.agc && !msk144wb::gain_ok(w.gain, msk144wb::AgcParams().max_exp))
+        return "--wideband-gain=auto:G0 needs 128 x G0 x 2^20 finite (the top of the AGC's ladder)";
+    return why;
 }
 
 }  // namespace msk144host

@@ -157,12 +157,91 @@ def output_rotation(offsets_hz: Sequence[int], m: np.ndarray) -> np.ndarray:
     return np.exp(-2j * np.pi * (np.mod(f[:, None] * mm[None, :], OUT_RATE).astype(np.float64) / OUT_RATE))
 
 
-def quantise(y: np.ndarray, gain: float = 100.0) -> Tuple[np.ndarray, int]:
-    """complex [..] -> (int8 [..][2] I/Q, clipped components): q = clamp(rint(128 gain y), -128, 127)."""
-    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * gain)
+def quantise(y: np.ndarray, gain=100.0, per_channel: bool = False):
+    """complex [..] -> (int8 [..][2] I/Q, clipped components): q = clamp(rint(128 gain y), -128, 127).  gain: one number, or one per
+    channel for y [channel][M].  per_channel: the clipped components of each channel (int64 [channel]) instead of their total."""
+    g = np.asarray(gain, dtype=np.float64)
+    if g.ndim:
+        g = g.reshape(-1, 1, 1)
+    v = np.stack([y.real, y.imag], axis=-1) * (128.0 * g)
     r = np.rint(v)
-    clipped = int(np.count_nonzero((r < -128) | (r > 127)))
+    over = (r < -128) | (r > 127)
+    clipped = np.count_nonzero(over, axis=(1, 2)).astype(np.int64) if per_channel else int(np.count_nonzero(over))
     return np.clip(r, -128, 127).astype(np.int8), clipped
+
+
+# msk144_wideband_level (include/msk144hip.h); HipDecoder.wideband_levels() returns the same records
+LEVEL_DTYPE = np.dtype([("samples", "<i8"), ("sum_sq", "<i8"), ("clipped", "<i8"), ("gain", "<f4"), ("exponent", "<i4")])
+assert LEVEL_DTYPE.itemsize == 32
+
+
+def levels(q: np.ndarray, clipped=None) -> np.ndarray:
+    """The statistics msk144_wideband_levels reports, from the int8 hops q [channel][M][2] of one push: samples = M and sum_sq = the
+    sum of I*I + Q*Q over the stored values, exactly; clipped = the caller's per-channel counts (quantise(..., per_channel=True);
+    the hops alone do not tell a stored 127 from a clipped one), 0 when not given.  gain and exponent are left 0."""
+    q = np.asarray(q)
+    out = np.zeros(q.shape[0], dtype=LEVEL_DTYPE)
+    out["samples"] = q.shape[1]
+    out["sum_sq"] = np.sum(q.astype(np.int64) ** 2, axis=(1, 2))
+    if clipped is not None:
+        out["clipped"] = clipped
+    return out
+
+
+# the defaults of msk144_wideband_agc (csrc/wideband.h AgcParams); hipdecoder.AGC_DEFAULTS is this dict
+AGC_DEFAULTS = dict(lo_sq=64, hi_sq=1024, clip_ppm=1000, hold=4, min_exp=-20, max_exp=20)
+
+
+class Agc:
+    """The stepped AGC of the contract (include/msk144hip.h) in Python integers: per channel an exponent e and a count of quiet
+    pushes; gains() is what the next push is quantised with, step() moves the state by one push's statistics."""
+
+    def __init__(self, channels: int, gains=100.0, **params):
+        p = dict(AGC_DEFAULTS)
+        unknown = set(params) - set(p)
+        if unknown:
+            raise TypeError(f"unknown AGC parameters {sorted(unknown)}")
+        p.update({k: int(v) for k, v in params.items()})
+        if p["lo_sq"] < 0 or p["hi_sq"] <= 4 * p["lo_sq"]:
+            raise ValueError("hi_sq must exceed 4 x lo_sq >= 0: one 6 dB step multiplies the power by 4")
+        if p["clip_ppm"] < 0:
+            raise ValueError("clip_ppm must not be negative")
+        if p["hold"] < 1:
+            raise ValueError("hold must be at least 1 push")
+        if p["min_exp"] > p["max_exp"] or p["min_exp"] < -126 or p["max_exp"] > 126:
+            raise ValueError("min_exp <= max_exp, both within -126..126")
+        self.p = p
+        self.base = np.broadcast_to(np.asarray(gains, dtype=np.float32), (channels,)).astype(np.float32)
+        with np.errstate(over="ignore"):
+            top = np.ldexp(np.float32(128.0) * self.base, p["max_exp"])
+        if not (np.all(self.base > 0) and np.all(np.isfinite(top))):
+            raise ValueError("every gain must be positive with 128 x gain x 2^max_exp finite in f32")
+        self.reset()
+
+    def reset(self):
+        """A first push: exponent 0, no quiet push counted."""
+        self.e = [0] * len(self.base)
+        self.quiet = [0] * len(self.base)
+
+    def gains(self) -> np.ndarray:
+        """float64 [channel]: base gain x 2^e, exactly the f32 value the device scales with (a 6 dB ladder is exact)."""
+        return np.ldexp(self.base.astype(np.float64), np.asarray(self.e, dtype=np.int64))
+
+    def step(self, lv):
+        """lv: records with samples, sum_sq, clipped per channel (levels(), or HipDecoder.wideband_levels()) of the push just made."""
+        p = self.p
+        for c in range(len(self.e)):
+            n, S, k = int(lv["samples"][c]), int(lv["sum_sq"][c]), int(lv["clipped"][c])
+            if k * 1000000 > p["clip_ppm"] * 2 * n or S > p["hi_sq"] * 2 * n:
+                self.e[c] = max(self.e[c] - 1, p["min_exp"])
+                self.quiet[c] = 0
+            elif S < p["lo_sq"] * 2 * n:
+                self.quiet[c] += 1
+                if self.quiet[c] >= p["hold"]:
+                    self.e[c] = min(self.e[c] + 1, p["max_exp"])
+                    self.quiet[c] = 0
+            else:
+                self.quiet[c] = 0
 
 
 class Channeliser:
@@ -171,7 +250,8 @@ class Channeliser:
     Any rate Fs = 12000 P/Q runs the polyphase form, branch by branch: outputs m = mr + Q a read x[n0 + a P - k] with the taps
     h[r + kQ], r = mr P mod Q, n0 = floor(mr P/Q).  Fs = D x 12000 is Q = 1: the one branch (0, 0, all taps), D = P."""
 
-    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0):
+    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain=100.0):
+        """gain: one number or one per channel; it may be replaced between pushes (self.gain)."""
         if rate_hz <= 0 or rate_hz % 125:
             raise ValueError("rate must be a positive multiple of 125 Hz")
         self.P, self.Q = rate_ratio(rate_hz)
@@ -290,8 +370,9 @@ class TwoStage:
     """The two-stage contract above 6.144 Msps, push by push: AnalysisBank over the stream, then the existing Channeliser at Fs/32
     on each occupied band with the residual offsets of its channels.  filter(x) -> y [channel][M] in channel order."""
 
-    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain: float = 100.0,
+    def __init__(self, rate_hz: int, offsets_hz: Sequence[int], taps: Optional[np.ndarray] = None, K: int = 16, gain=100.0,
                  bank_taps: Optional[np.ndarray] = None):
+        """gain: one number or one per channel, as for Channeliser."""
         if not is_bank_rate(rate_hz):
             raise ValueError("the two-stage bank takes multiples of 8000 Hz above 6144000 up to 61440000")
         self.rate = int(rate_hz)
