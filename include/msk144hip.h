@@ -36,6 +36,9 @@
  *   msk144_wideband_levels,  what a bank of channels needs where a single csdr chain has one gain_ff stage: every channel's level and
  *   msk144_set_wideband_gains, clip count of the last push, a gain per channel, and a stepped AGC that runs on the device one
  *   msk144_set_wideband_agc  push behind the statistics (no reference counterpart)
+ *   msk144_set_wideband_blanker, the noise blanker every SDR receiver chain has ahead of its channel filter, where an impulse is still a
+ *   msk144_wideband_blanker_stats, few samples wide: on the device, ahead of the channeliser and the bank (no reference counterpart)
+ *   msk144_dump_wideband_blanked
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -436,6 +439,61 @@ int msk144_wideband_levels(msk144_handle* h, msk144_wideband_level* out);
 int msk144_set_wideband_gains(msk144_handle* h, const float* gains);
 /* NULL: off */
 int msk144_set_wideband_agc(msk144_handle* h, const msk144_wideband_agc* p);
+
+/* ---- Impulse-noise blanker on the input stream (no reference counterpart) ----
+ *
+ * Power-line arcing, ignition and switching supplies put impulses on the stream that are a few input samples long, tens of dB over
+ * the floor and white, so they land in every channel at once.  The blanker zeroes them at the input rate Fs, ahead of the channeliser
+ * (and of stage 1 at a bank rate): behind the decimation an impulse is smeared over the whole filter.  It is written in integers, a
+ * pure function of the raw samples, and it is a contract per push, as the AGC is.
+ *
+ * Let the N new samples of a push be n = 0 .. N-1 (N = 5184 Fs/12000 for a first push, else 2592 Fs/12000).
+ *   Power:      p[n] = cI^2 + cQ^2 in integer component units of the input format: cu8 c = 2u - 255, cs8 c = s, cs16 c = s.
+ *   Threshold:  one per push, from that push's own samples: S = sum p[n], M = floor(S / N), T = (M . threshold_q4) >> 4; sample n is a
+ *               hit iff p[n] > T (strictly).  S <= 2^56 and M . threshold_q4 < 2^47: unsigned 64 bits hold everything
+ *               (csrc/wideband.h blanker_threshold).  The mean includes the impulses, on purpose: 1 % of the samples at +30 dB raise T
+ *               by 10 dB, and the impulses are still 20 dB over it.
+ *   Guard:      sample n is blanked iff some hit h of this push has h - pre <= n <= h + post, or n < carry_in.  carry_in is what the
+ *               previous push's last hit still owes, max(0, h_last + post - (N_prev - 1)); 0 if that push had no hit, and for a first
+ *               push.  The pre-guard does not reach back across a push boundary: those samples are already channelised.
+ *   Effect:     a blanked sample enters the channeliser or the bank as exactly 0 + 0j, every other sample as exactly the value it has
+ *               without the blanker; the filter history taken from a previous push is the blanked stream.  (cu8 has no byte that means
+ *               zero, so the device keeps a blanked stream as cs16: cu8 (2u - 255) . 128, cs8 s . 256 - the same real numbers, each
+ *               within int16 - which msk144_dump_wideband_blanked returns.)
+ *   Parameters: 16 <= threshold_q4 <= 65535 (the power ratio to the mean in 1/16), 0 <= pre, post <= 4096.  Defaults 256 / 2 / 8: 16 x
+ *               the mean power, which complex Gaussian noise exceeds with probability e^-16, about 1.1e-7, per sample.  The defaults
+ *               are design parameters, not measurements.
+ *   Order:      msk144_set_wideband_blanker(h, &p) sets the blanker, (h, NULL) switches it off; either takes effect at the next first
+ *               push (stream restart).  A running stream keeps what it started with, so the same stream pushed twice gives the same
+ *               bytes.  msk144_set_wideband resets the blanker to off.  With none of these entries called, every hop, clip count,
+ *               level and decode is what it is without them.
+ *   Refused:    MSK144_EINVAL outside wideband mode and for parameters out of range. */
+typedef struct msk144_wideband_blanker
+{
+    int32_t threshold_q4; /* 16 x the power ratio to the push's mean power (256) */
+    int32_t pre, post;    /* samples blanked ahead of and behind every hit (2, 8) */
+} msk144_wideband_blanker;
+
+typedef struct msk144_wideband_blanker_counts
+{
+    /* the last push */
+    int64_t samples;    /* N */
+    int64_t sum_power;  /* S */
+    int64_t threshold;  /* T */
+    int64_t hits;
+    int64_t blanked;    /* samples zeroed, those owed by the push before included */
+    int64_t carry_out;  /* guard samples its last hit owes to the next push */
+    /* since the first push */
+    int64_t total_samples, total_hits, total_blanked;
+} msk144_wideband_blanker_counts;
+
+/* NULL: off */
+int msk144_set_wideband_blanker(msk144_handle* h, const msk144_wideband_blanker* p);
+/* synchronises like msk144_wideband_levels.  MSK144_ESTATE before any push, and while the running stream has no blanker */
+int msk144_wideband_blanker_stats(msk144_handle* h, msk144_wideband_blanker_counts* out);
+/* test and debug, like msk144_dump_wideband_hop: the N new samples of the last push as the channeliser (or the bank) saw them, cs16 I,Q
+ * pairs.  MSK144_ESTATE as above */
+int msk144_dump_wideband_blanked(msk144_handle* h, int16_t* out);
 
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */

@@ -11,6 +11,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -144,6 +145,16 @@ struct msk144_handle
         int32_t* d_exp = nullptr;              // [channels] AGC exponent of the next push
         int32_t* d_quiet = nullptr;            // [channels] pushes in a row below the window
         int32_t* d_used_exp = nullptr;         // [channels] AGC exponent of the last push
+        // impulse-noise blanker (msk144_set_wideband_blanker): what is set applies from the next first push; a running stream keeps
+        // what it started with.  A blanked stream lives on the device as cs16 in d_blanked (history + one push, as d_raw), made from
+        // the raw push in d_stage
+        bool blanker_set = false, blanker_on = false;
+        msk144wb::BlankerParams blanker_next, blanker;
+        uint8_t* d_stage = nullptr;
+        uint8_t* d_blanked = nullptr;
+        BlankerCounters* d_blanker = nullptr;
+        long long blanker_pushes = 0;   // of the running stream: its parity picks the carry word
+        long long blanker_samples = 0;  // input samples since the first push
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -1381,9 +1392,19 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     if((rc = begin_hop(h, slot, C)) != MSK144_OK) return rc;
     msk144_handle::Slot& sl = h->slots[slot];
     const int M = first ? kWindowSamples : kHopSamples;
-    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(w.format));
+    if(first)
+    {
+        w.blanker_on = w.blanker_set;
+        w.blanker = w.blanker_next;
+        w.blanker_pushes = 0;
+        w.blanker_samples = 0;
+    }
+    // a blanked stream is cs16 on the device, whatever the input format
+    const int dev_format = w.blanker_on ? static_cast<int>(msk144wb::kCs16) : w.format;
+    const size_t sb = static_cast<size_t>(msk144wb::sample_bytes(dev_format));
     const size_t hist_bytes = static_cast<size_t>(w.raw_hist) * sb;
-    const size_t new_bytes = static_cast<size_t>(M) / w.Qin * w.Pin * sb;
+    const int new_samples = M / w.Qin * w.Pin;
+    const size_t new_bytes = static_cast<size_t>(new_samples) * sb;
     const int frames = M / w.Q * w.P;         // bank: frames of 32 input samples = the channeliser's input samples
     if(first)
     {
@@ -1395,7 +1416,7 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         sl.streams[j] = j;
         sl.is_first[j] = first ? 1 : 0;
     }
-    uint8_t* raw = w.d_raw;
+    uint8_t* raw = w.blanker_on ? w.d_blanked : w.d_raw;
     ev_begin(h);
     hipError_t e = hipSuccess;
     // the filter history: the last raw_hist samples of the previous push (a push has >= 2592*P/Q samples, raw_hist < ceil(64*P/Q)
@@ -1405,7 +1426,13 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     if(e == hipSuccess && !first && w.bank && w.hist > 0)
         e = hipMemcpy2DAsync(w.d_sub, w.stride * sizeof(float2), w.d_sub + w.last_frames, w.stride * sizeof(float2), w.hist * sizeof(float2), w.band_index.size(),
                              hipMemcpyDeviceToDevice, h->stream);
-    if(e == hipSuccess) e = hipMemcpyAsync(raw + hist_bytes, w.pinned[slot], new_bytes, hipMemcpyHostToDevice, h->stream);
+    if(w.blanker_on)
+    {
+        // the raw push to the staging buffer; the counters of a push start at 0, those of a stream (totals, carry) with its first push
+        if(e == hipSuccess) e = hipMemcpyAsync(w.d_stage, w.pinned[slot], static_cast<size_t>(new_samples) * msk144wb::sample_bytes(w.format), hipMemcpyHostToDevice, h->stream);
+        if(e == hipSuccess) e = hipMemsetAsync(w.d_blanker, 0, first ? sizeof(BlankerCounters) : offsetof(BlankerCounters, carry), h->stream);
+    }
+    else if(e == hipSuccess) e = hipMemcpyAsync(raw + hist_bytes, w.pinned[slot], new_bytes, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, C, hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess) e = hipMemsetAsync(w.d_clip, 0, sizeof(unsigned long long), h->stream);
@@ -1420,12 +1447,18 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
     ev_begin(h);
-    const void* in = w.d_raw;
-    int format = w.format;
+    if(w.blanker_on)
+    {
+        launch_blanker(w.d_stage, w.format, reinterpret_cast<short2*>(raw + hist_bytes), new_samples, w.blanker, static_cast<int>(w.blanker_pushes & 1), w.d_blanker, h->stream);
+        w.blanker_pushes++;
+        w.blanker_samples += new_samples;
+    }
+    const void* in = raw;
+    int format = dev_format;
     WidebandBands bands;
     if(w.bank)
     {
-        launch_bank(w.d_raw, w.format, w.d_h1, w.d_bands, w.d_tw, w.d_sub, static_cast<int>(w.band_index.size()), w.K1, frames, w.stride, w.hist, first ? 1 : 0,
+        launch_bank(raw, dev_format, w.d_h1, w.d_bands, w.d_tw, w.d_sub, static_cast<int>(w.band_index.size()), w.K1, frames, w.stride, w.hist, first ? 1 : 0,
                     w.n_next, h->stream);
         in = w.d_sub;
         format = kSubbandFormat;
@@ -1529,6 +1562,64 @@ int msk144_set_wideband_agc(msk144_handle* h, const msk144_wideband_agc* p)
     }
     w.agc = p != nullptr;
     return wb_upload_gains(h);  // exponent 0, nothing counted: the AGC starts, or the base gains hold again
+}
+
+int msk144_set_wideband_blanker(msk144_handle* h, const msk144_wideband_blanker* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_blanker");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(!p)
+    {
+        w.blanker_set = false;
+        return MSK144_OK;
+    }
+    const msk144wb::BlankerParams bp{p->threshold_q4, p->pre, p->post};
+    const std::string why = msk144wb::check_blanker(bp);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    // the buffers of a blanked stream, once per configuration and never in a push: the raw staging, and history + one push as cs16
+    const size_t cs16 = static_cast<size_t>(msk144wb::sample_bytes(msk144wb::kCs16));
+    if(!w.d_stage && (rc = dev_alloc(h, w.mem, &w.d_stage, w.slot_bytes)) != MSK144_OK) return rc;
+    if(!w.d_blanked && (rc = dev_alloc(h, w.mem, &w.d_blanked, (static_cast<size_t>(w.raw_hist) + static_cast<size_t>(kWindowSamples) / w.Qin * w.Pin) * cs16)) != MSK144_OK) return rc;
+    if(!w.d_blanker && (rc = dev_alloc(h, w.mem, &w.d_blanker, 1)) != MSK144_OK) return rc;
+    w.blanker_next = bp;
+    w.blanker_set = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_blanker_stats(msk144_handle* h, msk144_wideband_blanker_counts* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, "msk144_wideband_blanker_stats needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !w.blanker_on) return fail(h, MSK144_ESTATE, w.started ? "the running wideband stream has no blanker" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    BlankerCounters c;
+    HIP_TRY(h, hipMemcpy(&c, w.d_blanker, sizeof(c), hipMemcpyDeviceToHost));
+    out->samples = (w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin;
+    out->sum_power = static_cast<int64_t>(c.sum_power);
+    out->threshold = static_cast<int64_t>(msk144wb::blanker_threshold(c.sum_power, static_cast<uint64_t>(out->samples), static_cast<uint32_t>(w.blanker.threshold_q4)));
+    out->hits = static_cast<int64_t>(c.hits);
+    out->blanked = static_cast<int64_t>(c.blanked);
+    out->carry_out = static_cast<int64_t>(c.carry[(w.blanker_pushes - 1) & 1]);
+    out->total_samples = w.blanker_samples;
+    out->total_hits = static_cast<int64_t>(c.total_hits);
+    out->total_blanked = static_cast<int64_t>(c.total_blanked);
+    return MSK144_OK;
+}
+
+int msk144_dump_wideband_blanked(msk144_handle* h, int16_t* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(!w.started || !w.blanker_on) return fail(h, MSK144_ESTATE, w.started ? "the running wideband stream has no blanker" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t cs16 = static_cast<size_t>(msk144wb::sample_bytes(msk144wb::kCs16));
+    const size_t n = static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin;
+    HIP_TRY(h, hipMemcpy(out, w.d_blanked + static_cast<size_t>(w.raw_hist) * cs16, n * cs16, hipMemcpyDeviceToHost));
+    return MSK144_OK;
 }
 
 int msk144_wideband_levels(msk144_handle* h, msk144_wideband_level* out)

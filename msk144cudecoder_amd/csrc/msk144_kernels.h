@@ -113,6 +113,21 @@ void launch_channelise(const void* raw, int format, const float2* G, const Wideb
 void launch_agc_step(const unsigned long long* levels, const int32_t* slot_channel, const float* gains, int32_t* exps, int32_t* quiet, int32_t* used_exps, float* scale,
                      int slots, int samples, const msk144wb::AgcParams& p, hipStream_t stream);
 
+// what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
+// before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push
+struct BlankerCounters
+{
+    unsigned long long sum_power, hits, blanked;
+    unsigned long long carry[2];
+    unsigned long long total_hits, total_blanked;
+};
+
+// the impulse-noise blanker ahead of the channeliser or the bank (blanker.hip; contract in include/msk144hip.h): raw = the N new
+// samples of a push (format 0 cu8, 1 cs8, 2 cs16, 16-byte aligned), out = the same N samples as cs16 with every blanked one 0 + 0j.
+// counters->sum_power, hits and blanked must be 0; carry[parity ^ 1] is what the previous push owes (0 for a first push), and
+// carry[parity] receives what this one owes.
+void launch_blanker(const void* raw, int format, short2* out, int N, const msk144wb::BlankerParams& p, int parity, BlankerCounters* counters, hipStream_t stream);
+
 // the analysis bank in front of the channeliser above 6.144 Msps (bank.hip): raw = the L1-1 history samples then 32 x frames new
 // ones (format 0 cu8, 1 cs8, 2 cs16); h1 = the L1 = 64 K1 bank taps (f32); bands[j] = the occupied band k mod 64 of stream j;
 // tw[t] = e^{+j2pi t/64}.  Writes s_{bands[j]}[n_base + f] of frames f < frames to sub[j * stride + off + f] (complex f32).

@@ -213,6 +213,33 @@ inline std::string check_agc(const AgcParams& p)
 // scale would turn an exact 0 into NaN)
 inline bool gain_ok(float g, int32_t max_exp) { return g > 0.0f && std::isfinite(g) && std::isfinite(agc_scale(g, max_exp)); }
 
+// ---- impulse-noise blanker on the input stream (msk144_set_wideband_blanker, msk144_wideband_blanker_stats) ----
+
+constexpr int kBlankerMinThresholdQ4 = 16;  // 1 x mean power
+constexpr int kBlankerMaxThresholdQ4 = 65535;
+constexpr int kBlankerMaxGuard = 4096;      // pre, post: samples; a push has at least 5184, so a guard owes to the next push at most
+
+// msk144_wideband_blanker, field for field.  The defaults are design parameters, not measurements: 16 x the push's mean power
+// (complex Gaussian noise exceeds it with probability e^-16 per sample), 2 samples blanked ahead of a hit and 8 behind it.
+struct BlankerParams
+{
+    int32_t threshold_q4 = 256;
+    int32_t pre = 2, post = 8;
+};
+
+// The threshold of a push, once: N samples whose powers cI^2 + cQ^2 (integer component units of the input format) sum to S give
+// T = (floor(S / N) x threshold_q4) >> 4, and a sample is a hit iff its power exceeds T.  S <= 2^56 and floor(S / N) <= 2^31, so
+// unsigned 64 bits hold every step.
+MSK144WB_HD inline uint64_t blanker_threshold(uint64_t S, uint64_t N, uint32_t threshold_q4) { return ((S / N) * threshold_q4) >> 4; }
+
+// The rules of msk144_set_wideband_blanker that need no handle.  Empty string = valid.
+inline std::string check_blanker(const BlankerParams& p)
+{
+    if(p.threshold_q4 < kBlankerMinThresholdQ4 || p.threshold_q4 > kBlankerMaxThresholdQ4) return "blanker threshold_q4 must lie within 16..65535 (1 .. 4095.94 x mean power)";
+    if(p.pre < 0 || p.pre > kBlankerMaxGuard || p.post < 0 || p.post > kBlankerMaxGuard) return "blanker guards pre and post must lie within 0..4096 samples";
+    return std::string();
+}
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from .protocol import ITEM_BYTES
-from .wideband import AGC_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc; msk144_wideband_level
+from .wideband import AGC_DEFAULTS, BLANKER_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc and _blanker; msk144_wideband_level
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmsk144hip.so")
@@ -32,6 +32,19 @@ class WidebandParams(C.Structure):
 class WidebandAgc(C.Structure):
     """msk144_wideband_agc; AGC_DEFAULTS holds the defaults of include/msk144hip.h."""
     _fields_ = [("lo_sq", C.c_int32), ("hi_sq", C.c_int32), ("clip_ppm", C.c_int32), ("hold", C.c_int32), ("min_exp", C.c_int32), ("max_exp", C.c_int32)]
+
+
+class WidebandBlanker(C.Structure):
+    """msk144_wideband_blanker; BLANKER_DEFAULTS holds the defaults of include/msk144hip.h."""
+    _fields_ = [("threshold_q4", C.c_int32), ("pre", C.c_int32), ("post", C.c_int32)]
+
+
+BLANKER_STATS = ("samples", "sum_power", "threshold", "hits", "blanked", "carry_out", "total_samples", "total_hits", "total_blanked")
+
+
+class WidebandBlankerCounts(C.Structure):
+    """msk144_wideband_blanker_counts."""
+    _fields_ = [(n, C.c_int64) for n in BLANKER_STATS]
 
 
 class Params(C.Structure):
@@ -93,6 +106,9 @@ PROTOTYPES = {
     "msk144_wideband_levels": ([_vp, _vp], C.c_int),
     "msk144_set_wideband_gains": ([_vp, _P(C.c_float)], C.c_int),
     "msk144_set_wideband_agc": ([_vp, _P(WidebandAgc)], C.c_int),
+    "msk144_set_wideband_blanker": ([_vp, _P(WidebandBlanker)], C.c_int),
+    "msk144_wideband_blanker_stats": ([_vp, _P(WidebandBlankerCounts)], C.c_int),
+    "msk144_dump_wideband_blanked": ([_vp, _vp], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -405,6 +421,31 @@ class HipDecoder:
         """LEVEL_DTYPE [channels]: samples, sum_sq, clipped, gain and AGC exponent of the last push."""
         out = np.zeros(self.channels, dtype=LEVEL_DTYPE)
         self._chk(self.L.msk144_wideband_levels(self.h, _ptr(out)))
+        return out
+
+    def set_wideband_blanker(self, params=True, **kw):
+        """The impulse-noise blanker from the next first push on: set_wideband_blanker() takes the defaults (BLANKER_DEFAULTS),
+        keywords replace single ones (threshold_q4, pre, post); set_wideband_blanker(None) switches it off."""
+        if params is None:
+            self._chk(self.L.msk144_set_wideband_blanker(self.h, None))
+            return
+        p = dict(BLANKER_DEFAULTS)
+        if isinstance(params, dict):
+            p.update(params)
+        p.update(kw)
+        b = WidebandBlanker(**{k: int(v) for k, v in p.items()})
+        self._chk(self.L.msk144_set_wideband_blanker(self.h, C.byref(b)))
+
+    def wideband_blanker_stats(self) -> dict:
+        """The blanker's statistics of the last push and its totals since the first push (BLANKER_STATS), as Python integers."""
+        st = WidebandBlankerCounts()
+        self._chk(self.L.msk144_wideband_blanker_stats(self.h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n in BLANKER_STATS}
+
+    def dump_wideband_blanked(self) -> np.ndarray:
+        """int16 [n][2] I/Q: the new samples of the last push as the channeliser saw them (n = 5184 P/Q after a first push, else 2592 P/Q)."""
+        out = np.empty(((5184 if getattr(self, "_wb_last_first", True) else 2592) // self._wb_Q * self._wb_P, 2), dtype=np.int16)
+        self._chk(self.L.msk144_dump_wideband_blanked(self.h, _ptr(out)))
         return out
 
     # ---- parity / debug ----

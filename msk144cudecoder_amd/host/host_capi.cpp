@@ -72,6 +72,14 @@ int msk144host_wideband_agc_step(const int32_t* p, int64_t n, int64_t S, int64_t
 int msk144host_wideband_gain_ok(float g, int32_t max_exp) { return msk144wb::gain_ok(g, max_exp) ? 1 : 0; }
 float msk144host_wideband_agc_scale(float g, int32_t e) { return msk144wb::agc_scale(g, e); }
 
+// The blanker's threshold rule (csrc/wideband.h blanker_threshold, the function the device runs): T of a push of N samples whose
+// powers sum to S, or -1 for N < 1, S < 0 or a threshold_q4 that msk144_set_wideband_blanker refuses.
+int64_t msk144host_wideband_blanker_threshold(int64_t S, int64_t N, int32_t threshold_q4)
+{
+    if(N < 1 || S < 0 || threshold_q4 < msk144wb::kBlankerMinThresholdQ4 || threshold_q4 > msk144wb::kBlankerMaxThresholdQ4) return -1;
+    return static_cast<int64_t>(msk144wb::blanker_threshold(static_cast<uint64_t>(S), static_cast<uint64_t>(N), static_cast<uint32_t>(threshold_q4)));
+}
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

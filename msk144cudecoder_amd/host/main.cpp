@@ -71,6 +71,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-gain=G           Gain before each channel's int8 I/Q (the csdr gain_ff stage). Default=100." << std::endl;
     std::cout << "                   --wideband-gain=auto[:G0]   Stepped AGC per channel, on the GPU, one hop behind the levels: 6 dB down at once when more than 0.1 % of a hop's components clip or its level exceeds 32 LSB rms, 6 dB up after 4 hops below 8 LSB rms, within G0 x 2^-20 .. G0 x 2^20. G0 default=100. A step lands on a hop boundary." << std::endl;
     std::cout << "                   --wideband-levels           With --wideband-rate: at the end, on stderr, one line per channel - rms level in LSB over the run, clipped components, last gain, lowest and highest AGC step - and the three most clipped and three quietest channels." << std::endl;
+    std::cout << "                   --wideband-blanker[=RATIO[:PRE[:POST]]]  With --wideband-rate: impulse-noise blanker on the input stream, on the GPU, ahead of the channel filters: a sample whose power exceeds RATIO x the mean power of its hop is zeroed together with PRE samples before and POST after it (0..4096 each). RATIO 1..4095.9, default=16; PRE default=2, POST default=8. At the end, on stderr, one line with the hits and the blanked samples." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -183,6 +184,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-gain", required_argument, 0, 0},
                                            {"taps-per-phase", required_argument, 0, 0},
                                            {"wideband-levels", no_argument, 0, 0},
+                                           {"wideband-blanker", optional_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -232,6 +234,7 @@ int main(int argc, char* const argv[])
         case 26:
         case 27:
         case 28:
+        case 29:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -242,8 +245,9 @@ int main(int argc, char* const argv[])
             else if(idx == 25) good = parse_offset_grid(optarg, wbo.offsets), wbo.offset_sources++;
             else if(idx == 26) good = parse_wideband_gain(optarg, wbo);
             else if(idx == 28) wbo.levels = true;
+            else if(idx == 29) good = parse_wideband_blanker(optarg, wbo);
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
-            if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + optarg + "'";
+            if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
         }
         default: show_help(argv[0]); return 0;
@@ -296,7 +300,7 @@ int main(int argc, char* const argv[])
     if(wideband)
     {
         std::string err;
-        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)))
+        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
@@ -432,6 +436,15 @@ int main(int argc, char* const argv[])
             const msk144wb::AgcParams d;
             const msk144_wideband_agc agc{d.lo_sq, d.hi_sq, d.clip_ppm, d.hold, d.min_exp, d.max_exp};
             if(wb_api.set_agc(dec.handle(), &agc) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
+        if(wbo.blanker)
+        {
+            const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
+            if(wb_api.set_blanker(dec.handle(), &bl) != MSK144_OK)
             {
                 std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
                 return 2;
@@ -611,6 +624,12 @@ int main(int argc, char* const argv[])
         std::cerr << "msk144hipdecoder: wideband: " << clipped << " of " << all << " channel I/Q components clipped to int8";
         if(all) std::cerr << " (" << 100.0 * static_cast<double>(clipped) / static_cast<double>(all) << " %)";
         std::cerr << (clipped && !wbo.agc ? "; lower --wideband-gain" : "") << std::endl;
+        msk144_wideband_blanker_counts bc{};
+        if(wbo.blanker && wb_api.blanker_stats(loops[0]->decoder().handle(), &bc) == MSK144_OK)  // MSK144_ESTATE: no push was made
+            fprintf(stderr, "msk144hipdecoder: wideband blanker: threshold %g x mean power, guard %d+%d samples, %lld hits, %lld of %lld samples blanked (%.4f %%)\n",
+                    wbo.blanker_params.threshold_q4 / 16.0, wbo.blanker_params.pre, wbo.blanker_params.post, static_cast<long long>(bc.total_hits),
+                    static_cast<long long>(bc.total_blanked), static_cast<long long>(bc.total_samples),
+                    bc.total_samples ? 100.0 * static_cast<double>(bc.total_blanked) / static_cast<double>(bc.total_samples) : 0.0);
         if(wbo.levels)
         {
             const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();

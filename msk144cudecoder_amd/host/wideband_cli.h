@@ -37,6 +37,20 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-blanker: resolved only when it is given (load_blanker)
+    int (*set_blanker)(msk144_handle*, const msk144_wideband_blanker*) = nullptr;
+    int (*blanker_stats)(msk144_handle*, msk144_wideband_blanker_counts*) = nullptr;
+
+    bool load_blanker(std::string& err)
+    {
+        set_blanker = reinterpret_cast<decltype(set_blanker)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_blanker"));
+        blanker_stats = reinterpret_cast<decltype(blanker_stats)>(dlsym(RTLD_DEFAULT, "msk144_wideband_blanker_stats"));
+        if(set_blanker && blanker_stats) return true;
+        err = std::string("the loaded libmsk144hip has no impulse-noise blanker (") + (set_blanker ? "msk144_wideband_blanker_stats" : "msk144_set_wideband_blanker") +
+              "): --wideband-blanker needs it";
+        return false;
+    }
+
     bool load(std::string& err)
     {
         set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
@@ -57,6 +71,8 @@ struct WidebandOptions
     float gain = msk144wb::kDefaultGain;
     bool agc = false;     // --wideband-gain=auto[:G0]: the stepped AGC with the default parameters, base gain `gain`
     bool levels = false;  // --wideband-levels: the per-channel table in the summary
+    bool blanker = false; // --wideband-blanker[=RATIO[:PRE[:POST]]]: the impulse-noise blanker on the input stream
+    msk144wb::BlankerParams blanker_params;
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -88,6 +104,35 @@ inline bool parse_wideband_gain(const std::string& s, WidebandOptions& w)
     char* end = nullptr;
     w.gain = std::strtof(g.c_str(), &end);
     return !g.empty() && end && *end == 0;
+}
+
+// "RATIO[:PRE[:POST]]": RATIO a decimal power ratio to the push's mean power, kept as rint(16 x RATIO); PRE, POST in samples.
+// NULL (the bare option): the defaults.
+inline bool parse_wideband_blanker(const char* arg, WidebandOptions& w)
+{
+    w.blanker = true;
+    w.blanker_params = msk144wb::BlankerParams();
+    if(!arg) return true;
+    const std::string s = arg;
+    const size_t a = s.find(':');
+    const size_t b = a == std::string::npos ? a : s.find(':', a + 1);
+    const std::string ratio = s.substr(0, a);
+    char* end = nullptr;
+    const double r = std::strtod(ratio.c_str(), &end);
+    if(ratio.empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
+    w.blanker_params.threshold_q4 = static_cast<int32_t>(std::lrint(16.0 * r));
+    long long v = 0;
+    if(a != std::string::npos)
+    {
+        if(!parse_int(s.substr(a + 1, b == std::string::npos ? b : b - a - 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
+        w.blanker_params.pre = static_cast<int32_t>(v);
+    }
+    if(b != std::string::npos)
+    {
+        if(!parse_int(s.substr(b + 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
+        w.blanker_params.post = static_cast<int32_t>(v);
+    }
+    return msk144wb::check_blanker(w.blanker_params).empty();
 }
 
 inline bool parse_wideband_format(const std::string& s, int& fmt)
@@ -137,6 +182,7 @@ inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out
 inline std::string check_wideband_options(const WidebandOptions& w)
 {
     if(!w.parse_error.empty()) return w.parse_error;
+    if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";

@@ -244,6 +244,73 @@ class Agc:
                 self.quiet[c] = 0
 
 
+# the defaults of msk144_wideband_blanker (csrc/wideband.h BlankerParams): design parameters, not measurements
+BLANKER_DEFAULTS = dict(threshold_q4=256, pre=2, post=8)
+_CS16_UNIT = {"cu8": 128, "cs8": 256, "cs16": 1}
+
+
+def blanker_components(raw, fmt: str) -> np.ndarray:
+    """int64 [n][2]: the integer components the blanker measures power in - cu8 c = 2u - 255, cs8 and cs16 c = s."""
+    a = np.frombuffer(raw, dtype=_RAW_DTYPE[fmt]) if isinstance(raw, (bytes, bytearray, memoryview)) else np.asarray(raw, dtype=_RAW_DTYPE[fmt])
+    c = a.astype(np.int64).reshape(-1, 2)
+    return 2 * c - 255 if fmt == "cu8" else c
+
+
+def as_cs16(raw, fmt: str) -> np.ndarray:
+    """Raw components of fmt as the cs16 components that read as the same numbers: cu8 (2u - 255) x 128, cs8 s x 256.  What the
+    device keeps of a blanked stream."""
+    return (blanker_components(raw, fmt) * _CS16_UNIT[fmt]).astype(np.int16).reshape(-1)
+
+
+class Blanker:
+    """The impulse-noise blanker of the contract (include/msk144hip.h), push by push: every decision in integers (the powers in
+    int64, exact; their sum, the mean and the threshold in Python integers).  It holds what the last hit of a push still owes to the
+    next one, and the totals since reset()."""
+
+    def __init__(self, fmt: str, **params):
+        if fmt not in FORMATS:
+            raise ValueError(f"format must be one of {FORMATS}")
+        p = dict(BLANKER_DEFAULTS)
+        unknown = set(params) - set(p)
+        if unknown:
+            raise TypeError(f"unknown blanker parameters {sorted(unknown)}")
+        p.update({k: int(v) for k, v in params.items()})
+        if not 16 <= p["threshold_q4"] <= 65535:
+            raise ValueError("threshold_q4 must lie within 16..65535")
+        if not (0 <= p["pre"] <= 4096 and 0 <= p["post"] <= 4096):
+            raise ValueError("pre and post must lie within 0..4096 samples")
+        self.fmt, self.p = fmt, p
+        self.reset()
+
+    def reset(self):
+        """A first push follows: nothing owed, totals at 0."""
+        self.carry = 0
+        self.total = dict(total_samples=0, total_hits=0, total_blanked=0)
+
+    def push(self, raw):
+        """(the push as cs16 components, I,Q interleaved, blanked samples 0; the statistics msk144_wideband_blanker_stats reports)."""
+        c = blanker_components(raw, self.fmt)
+        N = len(c)
+        power = c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]
+        S = int(power.sum(dtype=np.int64))   # at most 2^56: exact in int64
+        T = ((S // N) * self.p["threshold_q4"]) >> 4
+        hits = np.flatnonzero(power > T)
+        edge = np.zeros(N + 1, dtype=np.int64)
+        np.add.at(edge, np.maximum(hits - self.p["pre"], 0), 1)
+        np.add.at(edge, np.minimum(hits + self.p["post"], N - 1) + 1, -1)
+        blanked = np.cumsum(edge[:N]) > 0
+        blanked[:min(self.carry, N)] = True
+        self.carry = max(0, int(hits[-1]) + self.p["post"] - (N - 1)) if len(hits) else 0
+        out = as_cs16(raw, self.fmt).reshape(-1, 2)
+        out[blanked] = 0
+        nb = int(np.count_nonzero(blanked))
+        self.total["total_samples"] += N
+        self.total["total_hits"] += len(hits)
+        self.total["total_blanked"] += nb
+        st = dict(samples=N, sum_power=S, threshold=T, hits=len(hits), blanked=nb, carry_out=self.carry, **self.total)
+        return out.reshape(-1), st
+
+
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 
