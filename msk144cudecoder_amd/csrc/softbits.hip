@@ -22,14 +22,16 @@
 // r = pos mod 6: one lane-contiguous, conflict-free ds_read_b64 per slot and frame.  The plane overwrites the 48.4 KB window in
 // place (workgroup barriers between the last read of x and the first write of P), so three workgroups (24 waves) still fit a CU.
 //
-// A candidate is demodulated in two parts: first slot 0 (softbits 0..63: both sync words), the carrier phase and nbadsync;
-// then slots 1 and 2, the normalisation and the LLR row.  In blocked staging (no LLR row outlives its channel block) a candidate
-// the index stage will drop (nbadsync > threshold) stops after part one; with the LLR store retained every candidate is
-// demodulated in full.  Softbit u lives in lane u % 64 of slot u / 64.
+// A wave demodulates its D candidates (slot `wave` of every pattern) in two steps.  The sync pass runs ONCE per wave, one candidate
+// per 8-lane octet (lane 8 i + j: candidate wave + 8 i, sync bit j): it folds the 16 sync softbits (u = 0..7 and 56..63) of every
+// candidate, forms the carrier phase per octet and stores nbadsync.  The candidate loop then holds part two only: all three slots,
+// the normalisation and the LLR row.  In blocked staging (no LLR row outlives its channel block) a candidate the index stage will
+// drop (nbadsync > threshold) has no part two; with the LLR store retained every candidate is demodulated in full.  In part two
+// softbit u lives in lane u % 64 of slot u / 64.
 // From there the two 144-term sums (softbits_kernel.cuh:186-194) are one per-lane add over the three slots plus a
 // single cross-lane reduction carrying both sums (sum_reduction.cuh:14-44 replaced by two interleaved DPP chains).
 // The phase rotation uses conj(s)/|s| instead of atan2f + sincosf (same unit vector to ~1 ulp); the
-// 84-term phase sum is accumulated per lane and then across lanes (order differs from the reference's
+// 84-term phase sum is accumulated per lane and then across the lanes of an octet (order differs from the reference's
 // 42->32->16 tree: ~1e-7 relative on a rotation angle).
 #include "msk144_kernels.h"
 #include "mix.h"
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
     __syncthreads();
     MSK144_STAMP(2);
 #ifdef MSK144_PHASE_STAMPS
-    uint64_t st_part1 = 0, st_part2 = 0, st_n2 = 0;  // wave 0: cycles in part one / part two of its candidates, part-two runs
+    uint64_t st_sync = 0, st_part2 = 0, st_n2 = 0;  // wave 0: cycles in the sync pass / part two of its kept candidates, part-two runs
 #endif
 
     float pp[12];
@@ -189,20 +191,26 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
     for(int i = 0; i < 12; i++) pp[i] = a.tpl.pp[i];
     const char* __restrict__ xbytes = reinterpret_cast<const char*>(s_x);
 
+    // Octet layout of the side values and of the sync pass: lane 8 i + j works for this wave's candidate of pattern i, c = wave + 8 i
+    // (the `8 p + slot` idiom of the scan's slot rule).  cpos: that candidate's position on the ring.
+    const int oct_i = lane >> 3, oct_j = lane & 7;
+    uint32_t cpos = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (wave + kSbWaves * oct_i), static_cast<int>(pos_of_lane)));
+    if(cpos >= static_cast<uint32_t>(kWindowSamples)) cpos -= kWindowSamples;  // scanned positions reach 5375
+    const uint32_t cmask = static_cast<uint32_t>(kPatternWord >> (8 * oct_i));  // frames of pattern i
+
     // ---- side values: the five half-pulse sums of each of this wave's candidates that P cannot give ----
-    // Lane j = i + 8 v: candidate wave + 8 i (pattern i), value v = u2[0], u1[143], u1[6], u2[56], u1[62] of its folded frame, folded
+    // Lane 8 i + v: candidate wave + 8 i (pattern i), value v = u2[0], u1[143], u1[6], u2[56], u1[62] of its folded frame, folded
     // and filtered exactly as a whole group's fold + matched filter would be (same frames in the same order, same operations).
     // pp[0] = sin 0 = 0 and pp[6] = sin pi/2 = 1 exactly (checked at create): u1 has no tap on sample 0, u2's is the sample.
     v2f side = v2f{0.0f, 0.0f};
     {
-        const int si = lane & 7, sv = lane >> 3;
-        const uint32_t spos_raw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(4 * (wave + kSbWaves * si), static_cast<int>(pos_of_lane)));
+        const int si = oct_i, sv = oct_j;
         if(sv < kSideValues && si < D)
         {
-            const uint32_t spos = spos_raw >= static_cast<uint32_t>(kWindowSamples) ? spos_raw - kWindowSamples : spos_raw;
+            const uint32_t spos = cpos;
             const bool rising = sv == 0 || sv == 3;  // u2: taps pp[6..11]; else u1: taps pp[0..5]
             const uint32_t group = sv == 0 ? 0u : sv == 1 ? static_cast<uint32_t>(kGroups - 1) : sv == 2 ? 6u : sv == 3 ? 56u : 62u;
-            const uint32_t mbits = static_cast<uint32_t>(kPatternWord >> (8 * si));
+            const uint32_t mbits = cmask;
             v2f acc[kGroup];
 #pragma unroll
             for(int m = 0; m < kPatternBits; m++)
@@ -233,16 +241,18 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         }
     }
 
-    // Per candidate i only two sums are needed: lane i gets W = u1[143] + u2[0] (softbit 0) and lane 8 + i the sync words' edge
-    // term s7 (u1[6] + u1[62]) - i s0 (u2[0] + u2[56]) of the phase sum; the candidate loop reads them with four readlanes.
+    // Per candidate i only two sums are needed: W = u1[143] + u2[0] (softbit 0), left in lane 8 i (side_w), and the sync words' edge
+    // term s7 (u1[6] + u1[62]) - i s0 (u2[0] + u2[56]) of the phase sum, formed in lane 8 i + 1 and spread over the octet (side_edge).
+    v2f side_w, side_edge;
     {
-        const v2f a8 = v2f{__shfl(side.x, lane + 8), __shfl(side.y, lane + 8)};     // lane i: u1[143]; lane 8 + i: u1[6]
-        const v2f a16 = v2f{__shfl(side.x, lane + 16), __shfl(side.y, lane + 16)};  // lane 8 + i: u2[56]
-        const v2f a24 = v2f{__shfl(side.x, lane + 24), __shfl(side.y, lane + 24)};  // lane 8 + i: u1[62]
-        const v2f m8 = v2f{__shfl(side.x, lane - 8), __shfl(side.y, lane - 8)};     // lane 8 + i: u2[0]
+        const v2f a1 = v2f{__shfl(side.x, lane + 1), __shfl(side.y, lane + 1)};  // lane 8 i: u1[143]; lane 8 i + 1: u1[6]
+        const v2f a2 = v2f{__shfl(side.x, lane + 2), __shfl(side.y, lane + 2)};  // lane 8 i + 1: u2[56]
+        const v2f a3 = v2f{__shfl(side.x, lane + 3), __shfl(side.y, lane + 3)};  // lane 8 i + 1: u1[62]
+        const v2f m1 = v2f{__shfl(side.x, lane - 1), __shfl(side.y, lane - 1)};  // lane 8 i + 1: u2[0]
         constexpr float s0 = static_cast<float>(kSync8Pm[0]), s7 = static_cast<float>(kSync8Pm[7]);
-        const v2f edge = v2f{s7 * (a8.x + a24.x) + s0 * (m8.y + a16.y), s7 * (a8.y + a24.y) - s0 * (m8.x + a16.x)};
-        side = lane < 8 ? a8 + side : edge;
+        const v2f edge = v2f{s7 * (a1.x + a3.x) + s0 * (m1.y + a2.y), s7 * (a1.y + a3.y) - s0 * (m1.x + a2.x)};
+        side_w = a1 + side;
+        side_edge = v2f{__shfl(edge.x, (lane & ~7) + 1), __shfl(edge.y, (lane & ~7) + 1)};
     }
 
     // ---- P build: thread t filters outputs n = 11 t .. 11 t + 10 of the ring from x[n + 1 .. n + 11] (softbits_kernel.cuh:157-180
@@ -329,24 +339,101 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         same_frames = __ballot(lane < ncand && r == mine);
     }
 
+    // ---- sync pass: the 16 sync softbits, the carrier phase and nbadsync of all this wave's candidates at once ----
+    // Lane 8 i + j folds two plane entries of candidate i over its pattern's frames (order m = 0..5, the adds of fold_plane: the same
+    // bits part two folds later): F(j - 1) for softbit j (lane j = 0: softbit 0 is the wrap sum W instead) and F(55 + j) for softbit
+    // 56 + j.  The 8 lanes of an octet read consecutive entries of one sub-ring; octets may meet in a bank.
     // Phase estimate = sum over the two sync words of folded sample x conj(template) (softbits_kernel.cuh:88-137).  Inside a group
     // the template is one half of the half-sine pulse on each rail, signed by a sync bit (msk_context.cuh:188-196: I carries bits
     // 1,1,3,3,5,5,7 and Q bits 0,2,2,4,4,6,6 over the seven groups), so the sum over the first sync word is
     //     s1 F(0) + s3 F(2) + s5 F(4) + s7 u1[6] - i (s0 u2[0] + s2 F(1) + s4 F(3) + s6 F(5))
-    // and the second the same at groups 56..62.  F(u-1) sits in lane u: lanes 1..6 and 57..62 take it with their own sync bit,
-    // on the real part in odd lanes (k_x) and as -i F in even ones (k_y); the four edge values are added after the lane sum.
-    const int sync_lane = (lane >= 1 && lane < 7) ? lane : (lane >= kSecondSyncBit + 1 && lane < kSecondSyncBit + 7) ? lane - kSecondSyncBit : -1;
-    float k_x = 0.0f, k_y = 0.0f;  // pr = k_x F.x + k_y F.y, pi = k_x F.y - k_y F.x
-#pragma unroll
-    for(int k = 1; k < 7; k++)
+    // and the second the same at groups 56..62.  Lanes j = 1..6 take both their F with their own sync bit, on the real part for odd j
+    // (k_x) and as -i F for even j (k_y); lanes 0 and 7 add nothing: their bits sit in the edge term, added after the octet sum.
+#ifdef MSK144_PHASE_STAMPS
+    const uint64_t st_s0 = (stamp_row_ && tid < 64) ? stamp_now() : 0;
+#endif
+    float cr_v = 1.0f, ci_v = 0.0f;  // lane 8 i + j: unit phasor of candidate i
+    uint64_t keep;                   // bit 8 i: candidate i goes through part two
     {
-        if(sync_lane == k)
+        const uint32_t q = cpos / kGroup;
+        const uint32_t ga8 = static_cast<uint32_t>(oct_j > 0 ? oct_j - 1 : 0) * 8u;  // lane j = 0 re-reads group 0; W replaces it
+        const uint32_t gb8 = static_cast<uint32_t>(kSecondSyncBit - 1 + oct_j) * 8u;
+        const uint32_t a0 = (cpos - q * kGroup) * (kPlaneStride * 8u) + q * 8u + ga8;  // sub-ring pos mod 6, per lane: byte offset of read A, frame 0
+        const uint32_t a_to_b = gb8 - ga8;
+        // every frame is read (the address is inside the sub-ring whatever the pattern), all twelve loads in flight; a lane adds the
+        // frames of its own pattern only
+        v2f va[kPatternBits], vb[kPatternBits];
+#pragma unroll
+        for(int m = 0; m < kPatternBits; m++)
         {
-            if(k % 2 == 1) k_x = static_cast<float>(kSync8Pm[k]);
-            else k_y = static_cast<float>(kSync8Pm[k]);
+            // base (q + 144 m) mod 864, as a byte offset from frame 0's
+            uint32_t oa = a0 + static_cast<uint32_t>(kGroups * m) * 8u;
+            if(m > 0 && q >= static_cast<uint32_t>(kPlaneRing - kGroups * m)) oa -= kPlaneRing * 8u;
+            va[m] = *(lds_v2f_ptr)(xbytes + oa);
+            vb[m] = *(lds_v2f_ptr)(xbytes + (oa + a_to_b));
         }
+        v2f fa = va[0], fb = vb[0];  // frame 0 is in every pattern
+#pragma unroll
+        for(int m = 1; m < kPatternBits; m++)
+        {
+            const bool in = ((cmask >> m) & 1u) != 0u;  // per lane
+            const v2f ta = fa + va[m], tb = fb + vb[m];
+            fa = in ? ta : fa;
+            fb = in ? tb : fb;
+        }
+
+        constexpr uint32_t kSyncBits = []() { uint32_t b = 0; for(int k = 0; k < 8; k++) b |= static_cast<uint32_t>(kSync8[k]) << k; return b; }();
+        const int sync_pm = static_cast<int>((kSyncBits >> oct_j) & 1u) * 2 - 1;  // sync bit j as +-1
+        // pr = k_x F.x + k_y F.y, pi = k_x F.y - k_y F.x: the lane's sync bit on one of the two, j = 1..6 only
+        const bool inner = static_cast<uint32_t>(oct_j - 1) < 6u;
+        const float k_x = inner && (oct_j & 1) ? static_cast<float>(sync_pm) : 0.0f;
+        const float k_y = inner && !(oct_j & 1) ? static_cast<float>(sync_pm) : 0.0f;
+        // carrier phase from the two sync words (softbits_kernel.cuh:88-137): sum c3[k]*conj(cb[k])
+        float pr = f32_add(fmaf(k_y, fa.y, k_x * fa.x), fmaf(k_y, fb.y, k_x * fb.x));
+        float pi = f32_add(fmaf(-k_y, fa.x, k_x * fa.y), fmaf(-k_y, fb.x, k_x * fb.y));
+        oct_sum2_f32(pr, pi);
+        const float sre = pr + side_edge.x;
+        const float sim = pi + side_edge.y;
+        // cfac = conj(exp(i*atan2(im,re))) = (re, -im)/|s|
+        {
+            const float m2 = fmaf(sre, sre, sim * sim);
+            if(m2 > 0.0f)
+            {
+                const float inv = __builtin_amdgcn_rsqf(m2);  // 1 ulp: the unit phasor only needs ~1e-7
+                cr_v = sre * inv;
+                ci_v = -sim * inv;
+            }
+            else if(!(m2 == 0.0f))
+            {
+                cr_v = m2;  // NaN propagates like the reference's atan2f/sincosf chain
+                ci_v = m2;
+            }
+        }
+
+        // de-rotate (softbits_kernel.cuh:146-153): softbit u = Re(rot F) for odd u (I bit), Im(rot F) for even u (Q bit), rot = cr + i ci;
+        // u = j and u = 56 + j have the parity of j.  The same expression as part two's, so the same bits.
+        const bool odd = (oct_j & 1) != 0;
+        const float b_r = odd ? cr_v : ci_v, b_i = odd ? -ci_v : cr_v;
+        const v2f f0 = oct_j == 0 ? side_w : fa;  // softbit 0: group 143 of the folded frame wraps into group 0
+        const float soft_a = fmaf(f0.y, b_i, f0.x * b_r);
+        const float soft_b = fmaf(fb.y, b_i, fb.x * b_r);
+
+        // ---- sync-word disagreements (softbits_kernel.cuh:214-241): bits 0..7 and 56..63; byte i of each ballot is candidate i's ----
+        const uint64_t bad_a = __ballot(((soft_a < 0.0f) ? -1 : 1) != sync_pm);
+        const uint64_t bad_b = __ballot(((soft_b < 0.0f) ? -1 : 1) != sync_pm);
+        const int nbad = __popc(static_cast<uint32_t>(bad_a >> (8 * oct_i)) & 0xffu) + __popc(static_cast<uint32_t>(bad_b >> (8 * oct_i)) & 0xffu);
+
+        // Slots that fold the same frames as a lower slot of their (frequency, pattern) group: that slot does the work, this one names it
+        uint32_t lower = 0u;
+        if(kHandOver) lower = static_cast<uint32_t>(same_frames >> (kSlotsPerPattern * oct_i)) & ((1u << wave) - 1u);
+        const bool owner = oct_j == 0 && oct_i < D;
+        if(owner) a.st.nbadsync[item0 + wave + kSbWaves * oct_i] = lower != 0u ? -1 - __builtin_ctz(lower) : nbad;
+        // the gate is wave-uniform per candidate: the index stage drops a candidate with nbadsync > threshold
+        keep = __ballot(owner && lower == 0u && !(kGateEarly && nbad > a.st.nbadsync_threshold));
     }
-    const bool odd = (lane & 1) != 0;
+#ifdef MSK144_PHASE_STAMPS
+    if(stamp_row_ && tid < 64) st_sync = stamp_now() - st_s0;
+#endif
 
     // byte offset inside a sub-ring of the group this lane reads per slot: softbit u = lane + 64 s needs F(u - 1).  Lane 0 of slot 0
     // (softbit 0 wraps: it takes the side values) and lanes >= 16 of slot 2 (no softbit) re-read a neighbouring group so the reads
@@ -359,62 +446,25 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
         g = g < 0 ? 0 : g > kPlanePad ? kPlanePad : g;
         lane_g8[s] = static_cast<uint32_t>(g) * 8u;
     }
-    // sync bit this lane checks (softbits 0..7 and 56..63), as +-1; 0 = none
-    int sync_pm = 0;
-#pragma unroll
-    for(int k = 0; k < 8; k++)
-        if(lane == k || lane == kSecondSyncBit + k) sync_pm = kSync8Pm[k];
+    const bool odd = (lane & 1) != 0;
 
+    // ---- part two, per kept candidate: all three slots and the rest of the demodulation ----
     for(int i = 0; i < D; i++)
     {
+        if(!((keep >> (kSlotsPerPattern * i)) & 1u)) continue;  // handed over, or gated: wave-uniform
         const int p = i, slot = wave;  // wave w owns slot w of every pattern
         const int c = slot + kSbWaves * p;
         const size_t item = item0 + c;
-        uint32_t pos = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(pos_of_lane), c));
-        if(pos >= static_cast<uint32_t>(kWindowSamples)) pos -= kWindowSamples;  // scanned positions reach 5375
-        if(kHandOver)
-        {
-            // a lower slot of this (frequency, pattern) group folds the same frames: it does the work, this slot names it
-            const uint32_t lower = static_cast<uint32_t>(same_frames >> (kSlotsPerPattern * p)) & ((1u << slot) - 1u);
-            if(lower != 0u)
-            {
-                if(lane == 0) a.st.nbadsync[item] = -1 - __builtin_ctz(lower);
-                continue;
-            }
-        }
 #ifdef MSK144_PHASE_STAMPS
-        const uint64_t st_t0 = (stamp_row_ && tid < 64) ? stamp_now() : 0;
+        const uint64_t st_t1 = (stamp_row_ && tid < 64) ? stamp_now() : 0;
 #endif
-
-        // ---- part 1: slot 0 (softbits 0..63, both sync words), the carrier phase and the sync check.  Slots 1 and 2 wait. ----
+        const uint32_t pos = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cpos), kSlotsPerPattern * i));
         const uint32_t q = pos / kGroup;
         const char* pbytes = xbytes + (pos - q * kGroup) * (kPlaneStride * 8u);  // sub-ring pos mod 6
         v2f f[kSlots];
-        fold_plane<0b001>(f, pbytes, lane_g8, q, p);
-        const v2f wrap = readlane2(side, p), edge = readlane2(side, kSbWaves + p);  // this candidate's side sums
-
-        // carrier phase from the two sync words (softbits_kernel.cuh:88-137): sum c3[k]*conj(cb[k])
-        float pr = fmaf(k_y, f[0].y, k_x * f[0].x);
-        float pi = fmaf(-k_y, f[0].x, k_x * f[0].y);
-        wave_sum2_f32(pr, pi);
-        const float sre = pr + edge.x;
-        const float sim = pi + edge.y;
-        // cfac = conj(exp(i*atan2(im,re))) = (re, -im)/|s|
-        float cr = 1.0f, ci = 0.0f;
-        {
-            const float m2 = fmaf(sre, sre, sim * sim);
-            if(m2 > 0.0f)
-            {
-                const float inv = __builtin_amdgcn_rsqf(m2);  // 1 ulp: the unit phasor only needs ~1e-7
-                cr = sre * inv;
-                ci = -sim * inv;
-            }
-            else if(!(m2 == 0.0f))
-            {
-                cr = m2;  // NaN propagates like the reference's atan2f/sincosf chain
-                ci = m2;
-            }
-        }
+        fold_plane<0b111>(f, pbytes, lane_g8, q, p);
+        const float cr = readlane_f32(cr_v, kSlotsPerPattern * i), ci = readlane_f32(ci_v, kSlotsPerPattern * i);
+        const v2f wrap = readlane2(side_w, kSlotsPerPattern * i);
 
         // de-rotate (softbits_kernel.cuh:146-153): softbit u = Re(rot F) for odd u (I bit), Im(rot F) for even u (Q bit), rot = cr + i ci.
         // re = fr*cr - fi*ci, im = fr*ci + fi*cr: pick the coefficient pair per lane once instead of selecting per value.
@@ -424,20 +474,6 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
             const v2f f0 = lane == 0 ? wrap : f[0];  // softbit 0: group 143 of the folded frame wraps into group 0
             soft[0] = fmaf(f0.y, b_i, f0.x * b_r);
         }
-
-        // ---- sync-word disagreements (softbits_kernel.cuh:214-241): bits 0..7 and 56..63 ----
-        const int hard = (soft[0] < 0.0f) ? -1 : 1;
-        const bool disagree = sync_pm != 0 && hard != sync_pm;
-        const int nbad = __popcll(__ballot(disagree));
-        if(lane == 0) a.st.nbadsync[item] = nbad;
-#ifdef MSK144_PHASE_STAMPS
-        const uint64_t st_t1 = (stamp_row_ && tid < 64) ? stamp_now() : 0;
-        st_part1 += st_t1 - st_t0;
-#endif
-        if(kGateEarly && nbad > a.st.nbadsync_threshold) continue;  // wave-uniform: the index stage drops this candidate
-
-        // ---- part 2: slots 1 and 2 and the rest of the demodulation ----
-        fold_plane<0b110>(f, pbytes, lane_g8, q, p);
         soft[1] = fmaf(f[1].y, b_i, f[1].x * b_r);
         soft[2] = lane < kGroups - 64 * (kSlots - 1) ? fmaf(f[2].y, b_i, f[2].x * b_r) : 0.0f;
 
@@ -481,7 +517,7 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
 #ifdef MSK144_PHASE_STAMPS
     if(stamp_row_ && tid == 0)
     {
-        stamp_row_[3] = st_part1;
+        stamp_row_[3] = st_sync;
         stamp_row_[4] = st_part2;
         stamp_row_[5] = st_n2;
     }

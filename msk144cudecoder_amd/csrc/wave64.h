@@ -131,6 +131,27 @@ __device__ __forceinline__ void oct_max2_f32(float& a, float& b)
     b = rb;
 }
 
+// sum over each aligned group of 8 lanes for two independent values at once, result in all 8: ((v0 + v1) + (v2 + v3)) + ((v7 + v6) +
+// (v5 + v4)) up to the order of each add's operands, so the eight lanes hold the same bits.  Interleaved like oct_max2_f32.
+__device__ __forceinline__ void oct_sum2_f32(float& a, float& b)
+{
+    float ra, rb;
+    asm volatile("s_nop 4\n\t"
+                 "v_add_f32_dpp %0, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_f32_dpp %1, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 0\n\t"
+                 "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 0\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                 "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1"
+                 : "=&v"(ra), "=&v"(rb)
+                 : "v"(a), "v"(b));
+    a = ra;
+    b = rb;
+}
+
 // v + (its quad/row partners): after the four steps every lane of a 16-lane row holds the row sum, added
 // in the order lane^1, lane^2, other quad pair, other half - the reference's shuffle-tree association.
 __device__ __forceinline__ float row_sum_f32(float v)

@@ -94,6 +94,7 @@ def main():
     ap.add_argument("--listing", action="store_true", help="only compile and price the listings (no GPU)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--channels", type=int, default=1024)
+    ap.add_argument("--lib", default=None, help="a stamps library built beforehand (build.build_stamps_library) instead of building it here")
     a = ap.parse_args()
 
     scan_seg = segments(listing("scan.hip", "scan_kernelILi6E"))
@@ -118,7 +119,7 @@ def main():
     import bench
     from msk144cudecoder_amd import build as b
     from msk144cudecoder_amd import hipdecoder as hd
-    lib = b.build_stamps_library()
+    lib = a.lib or b.build_stamps_library()
     hd._lib = hd.load_library(lib)
     L = hd._lib
     L.msk144_debug_read_stamps.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -194,26 +195,29 @@ def main():
     P(f"softbits_kernel<true, true>: {len(s)} sampled workgroups; stamp cost {self_cost}; median workgroup lifetime {median(life.tolist())} cycles; wave 0 ends at "
       f"{median((s[:, 16] - s[:, 0]).tolist())}, the last wave at {median(life.tolist())}, the first at {median((s[:, 16:24].min(axis=1) - s[:, 0]).tolist())}")
     n2 = s[:, 5]
-    # listing order of softbits stamps: 0, 11, 1, 2, 7, [loop: t0, t1, t2], 6, wave-end
+    # listing order of softbits stamps: 0, 11, 1, 2, 7, sync pass [s0, s1], [loop: t1, t2 per kept candidate], 6, wave-end.  The compiler
+    # unrolls the candidate loop per pattern: the part-two bodies are the segments after the pass that hold the three LLR stores.
     sb_names = ["before stamp 0", "stamp pair", "mix (global loads, sincos, LDS store)", "barrier after mix",
-                "side values + filtered plane (x reads, 11 outputs, 2 barriers, P writes)", "candidate loop set-up",
-                "part one: fold slot 0 of the plane, phase, sync check", "gate + part two: fold slots 1+2, normalise, LLR row", "loop tail -> end"]
+                "side values + filtered plane (x reads, 11 outputs, 2 barriers, P writes)", "same-frames ballot",
+                "sync pass: 16 sync softbits, phase and nbadsync of the wave's 6 candidates", "part two: fold three slots, normalise, LLR row"]
+    bodies = [g for g in sb_seg[7:] if g["vmem"] >= 3]
+    p2_seg = dict(cycles=median([g["cycles"] for g in bodies]), ds=median([g["ds"] for g in bodies]), vmem=3)
     mix = median((s[:, 1] - s[:, 11]).tolist()) - self_cost
     bar = median((s[:, 2] - s[:, 1]).tolist()) - self_cost
     plane = median((s[:, 7] - s[:, 2]).tolist()) - self_cost
-    p1 = median((s[:, 3] // 6).tolist()) - self_cost
+    sync = median(s[:, 3].tolist()) - self_cost
     p2 = median((s[:, 4] // np.maximum(n2, 1))[n2 > 0].tolist()) - self_cost
     kept = float(n2.mean()) / 6.0
     total = median((s[:, 6] - s[:, 11]).tolist())
-    P(f"  candidates per wave: 6; part two ran for {100 * kept:.1f} % of them (nbadsync <= 3)")
-    P(f"  {'phase (wave 0)':60s} {'measured':>9s} {'priced':>8s}  measured/priced")
-    for nm, meas, seg, mult in ((sb_names[2], mix, sb_seg[2], 1), (sb_names[3], bar, sb_seg[3], 1), (sb_names[4], plane, sb_seg[4], 1),
-                                (sb_names[6] + " (per candidate)", p1, sb_seg[6], 1), (sb_names[7] + " (per kept candidate)", p2, sb_seg[7], 1)):
+    P(f"  candidates per wave: 6; part two ran for {100 * kept:.1f} % of them (not handed over, nbadsync <= 3)")
+    P(f"  {'phase (wave 0)':76s} {'measured':>9s} {'priced':>8s}  measured/priced")
+    for nm, meas, seg in ((sb_names[2], mix, sb_seg[2]), (sb_names[3], bar, sb_seg[3]), (sb_names[4], plane, sb_seg[4]), (sb_names[6] + " (once)", sync, sb_seg[6]),
+                          (sb_names[7] + " (per kept candidate; priced: median pattern)", p2, p2_seg)):
         ratio = f"{meas / seg['cycles']:5.2f}" if seg["cycles"] > 50 else "    -"
-        P(f"  {nm:60s} {meas:9d} {seg['cycles']:8.0f}  {ratio}    ({seg['ds']} LDS, {seg['vmem']} VMEM instr)")
-    est = mix + bar + plane + 6 * p1 + 6 * kept * p2
-    pr = sb_seg[2]["cycles"] + sb_seg[4]["cycles"] + 6 * sb_seg[6]["cycles"] + 6 * kept * sb_seg[7]["cycles"]
-    P(f"  {'wave 0 total = mix + barrier + plane + 6 part one + 6 x kept x part two':60s} {int(est):9d} {pr:8.0f}  {est / pr:5.2f}    (entry -> end measured: {total})")
+        P(f"  {nm:76s} {meas:9d} {seg['cycles']:8.0f}  {ratio}    ({seg['ds']} LDS, {seg['vmem']} VMEM instr)")
+    est = mix + bar + plane + sync + 6 * kept * p2
+    pr = sb_seg[2]["cycles"] + sb_seg[4]["cycles"] + sb_seg[6]["cycles"] + 6 * kept * p2_seg["cycles"]
+    P(f"  {'wave 0 total = mix + barrier + plane + sync pass + 6 x kept x part two':76s} {int(est):9d} {pr:8.0f}  {est / pr:5.2f}    (entry -> end measured: {total})")
     text = "\n".join(report)
     print(text)
     if a.out:
