@@ -39,6 +39,8 @@
  *   msk144_set_wideband_blanker, the noise blanker every SDR receiver chain has ahead of its channel filter, where an impulse is still a
  *   msk144_wideband_blanker_stats, few samples wide: on the device, ahead of the channeliser and the bank (no reference counterpart)
  *   msk144_dump_wideband_blanked
+ *   msk144_set_wideband_spectrum, the spectrum display every SDR front end has: the power spectrum of each push's input samples at
+ *   msk144_wideband_spectrum the input rate, on the device (no reference counterpart)
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -494,6 +496,48 @@ int msk144_wideband_blanker_stats(msk144_handle* h, msk144_wideband_blanker_coun
 /* test and debug, like msk144_dump_wideband_hop: the N new samples of the last push as the channeliser (or the bank) saw them, cs16 I,Q
  * pairs.  MSK144_ESTATE as above */
 int msk144_dump_wideband_blanked(msk144_handle* h, int16_t* out);
+
+/* ---- Power spectrum of the input stream (no reference counterpart) ----
+ *
+ * Where in the band the energy lies - the tuner's ppm error against the grid, the birdie that drives one channel's AGC down, the
+ * distance of the noise floor from full scale, what the blanker did to the floor - is what every SDR front end shows as a spectrum.
+ * The whole stream is on the device at Fs, so the spectrum of a push is computed there, from one more read of its samples.
+ *
+ *   Input:      the N new samples x[0..N) of a push (N = 5184 Fs/12000 for a first push, else 2592 Fs/12000) exactly as the
+ *               channeliser (or stage 1 at a bank rate) reads them: the blanked stream when the running stream has a blanker, else
+ *               the raw one; cu8 (u - 127.5)/128, cs8 s/128, cs16 s/32768, so full scale is 1.0.  The filter history is no part of it.
+ *   Segments:   S = floor(N / B) segments of B = bins samples, not overlapped: segment s is x[sB .. sB + B - 1]; the last N mod B
+ *               samples are not used, and nothing is carried from push to push: a push's spectrum is a pure function of its samples.
+ *   Output:     X_s[k] = sum_i w[i] x[sB + i] e^{-j 2 pi i k / B},  P[k] = sum_s |X_s[k]|^2,  in ascending frequency: power[j] is bin
+ *               k = (j - B/2) mod B, at (j - B/2) Fs / B Hz from the centre; *segments = S.  A full-scale complex tone on a bin centre
+ *               reads S (sum w)^2: that is 0 dBFS, dBFS[j] = 10 log10(power[j] / (S (sum w)^2)).
+ *   Window:     w[0..B) real and finite; NULL selects the periodic Hann window 0.5 - 0.5 cos(2 pi i / B)
+ *               (msk144host_wideband_spectrum_window).  Formed in double, stored f32, as the taps are.
+ *   Arithmetic: the transform and |X|^2 in f32, the sum over the segments in double.  Segments are assigned to workgroups and the
+ *               partial sums added in a fixed order, without atomics: the same stream pushed twice gives the same bytes.
+ *   Error:      against the exact P of the f32 window and samples, with T = sum_k P[k]:
+ *                   |power[k] - P[k]| <= 2 u sqrt(P[k] T) + u^2 T + v P[k],   v = 4 x 2^-24 (the rounding of re^2 + im^2),
+ *               u = MSK144_SPECTRUM_U the relative l2 error of one f32 transform (|dX_s[k]| <= ||dX_s||_2 <= u ||X_s||_2, then
+ *               Cauchy-Schwarz over the segments): 4 x the largest value any bin needed on an MI355X against a float64 model over
+ *               B = 256..8192 and the three formats (3.9e-8), rounded up; far below the textbook ceiling 8 x 2^-24 x log2 B.
+ *   Parameters: bins a power of two, 256 <= bins <= 8192, and bins <= 2592 Fs/12000, so that every push has a segment.
+ *   Order:      msk144_set_wideband_spectrum(h, &p) takes effect from the next push and allocates everything it needs - a push
+ *               allocates nothing; (h, NULL) switches the spectrum off, as msk144_set_wideband does.  msk144_wideband_spectrum reports
+ *               the last push and synchronises like msk144_wideband_levels.  With none of these entries called, every hop, clip
+ *               count, level, blanker statistic and decode is byte for byte what it is without them.
+ *   Refused:    MSK144_EINVAL outside wideband mode, for bins not a power of two, out of range or longer than a later push, and for a
+ *               window value that is not finite; MSK144_ESTATE from msk144_wideband_spectrum before any push made with the spectrum on. */
+#define MSK144_SPECTRUM_U 2e-7
+/* (a typedef and a function share C's one name space, so the structure cannot be called msk144_wideband_spectrum as well) */
+typedef struct msk144_wideband_spectrum_params
+{
+    int32_t bins;          /* B (1024 is what the program and the Python view default to) */
+    const double* window;  /* [bins], or NULL: periodic Hann */
+} msk144_wideband_spectrum_params;
+
+/* NULL: off */
+int msk144_set_wideband_spectrum(msk144_handle* h, const msk144_wideband_spectrum_params* p);
+int msk144_wideband_spectrum(msk144_handle* h, double* power /*[bins]*/, int64_t* segments);
 
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */

@@ -29,6 +29,7 @@ SOURCES = [
     ("channelise.hip", []),
     ("bank.hip", []),
     ("blanker.hip", []),
+    ("spectrum.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]

@@ -16,6 +16,7 @@
 // IQ outputs bit-identical to the CPU oracle.  Cost: ~15 us of one lane per channel, hidden behind
 // the other channels' workgroups.
 #include "msk144_kernels.h"
+#include "fft_reg.h"
 #include "wave64.h"
 
 namespace msk144
@@ -195,53 +196,6 @@ __global__ __launch_bounds__(kFeThreads) void frontend_fir_kernel(const DeviceSt
 // conflict-free (one pad cell per 32: the radix-32 columns are 33 cells apart), twiddles from the 4096-entry table.
 constexpr int kFftCells = kFftSize + kFftSize / 32;  // padded: cell(i) = i + i / 32
 
-__device__ __forceinline__ int fft_cell(int i)
-{
-    return i + (i >> 5);
-}
-
-// cos(k pi / 16), k = 0..16: after full unrolling k is a constant and the switch folds to a literal
-__device__ __forceinline__ float cos_pi16(int k)
-{
-    switch(k)
-    {
-    case 0: return 1.0f;
-    case 1: return 0.980785280403230449f;
-    case 2: return 0.923879532511286756f;
-    case 3: return 0.831469612302545237f;
-    case 4: return 0.707106781186547524f;
-    case 5: return 0.555570233019602225f;
-    case 6: return 0.382683432365089772f;
-    case 7: return 0.195090322016128268f;
-    case 8: return 0.0f;
-    case 9: return -0.195090322016128268f;
-    case 10: return -0.382683432365089772f;
-    case 11: return -0.555570233019602225f;
-    case 12: return -0.707106781186547524f;
-    case 13: return -0.831469612302545237f;
-    case 14: return -0.923879532511286756f;
-    case 15: return -0.980785280403230449f;
-    default: return -1.0f;
-    }
-}
-
-// x . W32^k (forward) or x . conj(W32^k) (inverse), k = 0..15 a compile-time constant after unrolling
-template<bool kInverse>
-__device__ __forceinline__ float2 mul_w32(float2 x, int k)
-{
-    if(k == 0) return x;
-    if(k == 8) return kInverse ? make_float2(-x.y, x.x) : make_float2(x.y, -x.x);
-    const float c = cos_pi16(k);
-    const float sn = cos_pi16(k < 8 ? 8 - k : k - 8);  // sin(k pi / 16) = cos(|8 - k| pi / 16) > 0
-    const float s = kInverse ? sn : -sn;
-    return make_float2(fmaf(x.x, c, -(x.y * s)), fmaf(x.x, s, x.y * c));
-}
-
-__device__ __forceinline__ float2 cmul_fma(float2 x, float2 w)
-{
-    return make_float2(fmaf(x.x, w.x, -(x.y * w.y)), fmaf(x.x, w.y, x.y * w.x));
-}
-
 // W^m (forward) or conj(W^m) (inverse), 0 <= m < 8192, from the table tw[j] = exp(-2 pi i j / 8192), j < 4096
 template<bool kInverse>
 __device__ __forceinline__ float2 twiddle(const float2* __restrict__ tw, int m)
@@ -250,43 +204,6 @@ __device__ __forceinline__ float2 twiddle(const float2* __restrict__ tw, int m)
     if(m & (kFftSize / 2)) w = make_float2(-w.x, -w.y);
     if(kInverse) w.y = -w.y;
     return w;
-}
-
-// R-point DFT (R = 16 or 32) of a register array, natural order in and out: log2(R) radix-2 decimation-in-frequency stages and
-// the bit reversal, all indices compile-time constants
-template<int R, bool kInverse>
-__device__ __forceinline__ void fft_reg(float2 (&a)[R])
-{
-    constexpr int kLog = R == 32 ? 5 : 4;
-#pragma unroll
-    for(int stage = 0; stage < kLog; stage++)
-    {
-        const int len = R >> stage, half = len >> 1;
-#pragma unroll
-        for(int b = 0; b < R; b += len)
-        {
-#pragma unroll
-            for(int j = 0; j < half; j++)
-            {
-                const float2 u = a[b + j], v = a[b + j + half];
-                a[b + j] = make_float2(u.x + v.x, u.y + v.y);
-                a[b + j + half] = mul_w32<kInverse>(make_float2(u.x - v.x, u.y - v.y), j * (32 / len));
-            }
-        }
-    }
-#pragma unroll
-    for(int i = 0; i < R; i++)
-    {
-        int r = 0;
-#pragma unroll
-        for(int bit = 0; bit < kLog; bit++) r |= ((i >> bit) & 1) << (kLog - 1 - bit);
-        if(i < r)
-        {
-            const float2 t = a[i];
-            a[i] = a[r];
-            a[r] = t;
-        }
-    }
 }
 
 __global__ __launch_bounds__(kFeThreads) void frontend_fft_kernel(const DeviceStore st, const int16_t* __restrict__ d_in,

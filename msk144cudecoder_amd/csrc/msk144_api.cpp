@@ -155,6 +155,17 @@ struct msk144_handle
         BlankerCounters* d_blanker = nullptr;
         long long blanker_pushes = 0;   // of the running stream: its parity picks the carry word
         long long blanker_samples = 0;  // input samples since the first push
+        // power spectrum of the input stream (msk144_set_wideband_spectrum): applies from the next push; `set` allocates - tables and
+        // result for the largest B once, the partial sums for the largest B set so far (spectrum_rows_bins).  spectrum_pushed: the last
+        // push left a spectrum of spectrum_last_bins bins
+        int spectrum_bins = 0;          // B of the next push; 0: off
+        int spectrum_last_bins = 0;
+        int spectrum_rows_bins = 0;
+        bool spectrum_pushed = false;
+        float* d_spec_window = nullptr;     // [B]
+        float2* d_spec_tw = nullptr;        // [B] e^{-j2pi m/B}
+        double* d_spec_partials = nullptr;  // [kSpectrumMaxGroups][spectrum_rows_bins]
+        double* d_spec_out = nullptr;       // [B] ascending frequency
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -1453,6 +1464,9 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         w.blanker_pushes++;
         w.blanker_samples += new_samples;
     }
+    if(w.spectrum_bins) launch_spectrum(raw + hist_bytes, dev_format, new_samples, w.spectrum_bins, w.d_spec_window, w.d_spec_tw, w.d_spec_partials, w.d_spec_out, h->stream);
+    w.spectrum_pushed = w.spectrum_bins != 0;
+    w.spectrum_last_bins = w.spectrum_bins;
     const void* in = raw;
     int format = dev_format;
     WidebandBands bands;
@@ -1619,6 +1633,54 @@ int msk144_dump_wideband_blanked(msk144_handle* h, int16_t* out)
     const size_t cs16 = static_cast<size_t>(msk144wb::sample_bytes(msk144wb::kCs16));
     const size_t n = static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin;
     HIP_TRY(h, hipMemcpy(out, w.d_blanked + static_cast<size_t>(w.raw_hist) * cs16, n * cs16, hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_spectrum(msk144_handle* h, const msk144_wideband_spectrum_params* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_spectrum");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(!p)
+    {
+        w.spectrum_bins = 0;
+        return MSK144_OK;
+    }
+    const int B = p->bins;
+    const std::string why = msk144wb::check_spectrum(B, p->window, static_cast<int64_t>(kHopSamples) / w.Qin * w.Pin);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    // never in a push
+    constexpr size_t kMax = msk144wb::kSpectrumMaxBins;
+    if(!w.d_spec_window && (rc = dev_alloc(h, w.mem, &w.d_spec_window, kMax)) != MSK144_OK) return rc;
+    if(!w.d_spec_tw && (rc = dev_alloc(h, w.mem, &w.d_spec_tw, kMax)) != MSK144_OK) return rc;
+    if(B > w.spectrum_rows_bins)
+    {
+        // a larger B than any before: new rows (the old ones stay with the configuration's owner until it is released)
+        if((rc = dev_alloc(h, w.mem, &w.d_spec_partials, static_cast<size_t>(B) * kSpectrumMaxGroups)) != MSK144_OK) return rc;
+        w.spectrum_rows_bins = B;
+    }
+    if(!w.d_spec_out && (rc = dev_alloc(h, w.mem, &w.d_spec_out, kMax)) != MSK144_OK) return rc;
+    // window and twiddles: formed in double, stored f32
+    const std::vector<double> hann = p->window ? std::vector<double>() : msk144wb::spectrum_window(B);
+    const double* win = p->window ? p->window : hann.data();
+    const std::vector<float> wf(win, win + B);
+    const std::vector<float2> tw = unit_circle(B, -1.0);
+    HIP_TRY(h, hipMemcpy(w.d_spec_window, wf.data(), sizeof(float) * wf.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(w.d_spec_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+    w.spectrum_bins = B;
+    return MSK144_OK;
+}
+
+int msk144_wideband_spectrum(msk144_handle* h, double* power, int64_t* segments)
+{
+    if(!h || !power || !segments) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, "msk144_wideband_spectrum needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !w.spectrum_pushed) return fail(h, MSK144_ESTATE, w.started ? "the last wideband push was made without a spectrum" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(power, w.d_spec_out, sizeof(double) * static_cast<size_t>(w.spectrum_last_bins), hipMemcpyDeviceToHost));
+    *segments = static_cast<int64_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin / w.spectrum_last_bins;
     return MSK144_OK;
 }
 

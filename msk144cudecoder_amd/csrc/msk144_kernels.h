@@ -128,6 +128,13 @@ struct BlankerCounters
 // carry[parity] receives what this one owes.
 void launch_blanker(const void* raw, int format, short2* out, int N, const msk144wb::BlankerParams& p, int parity, BlankerCounters* counters, hipStream_t stream);
 
+// the power spectrum of a push's input samples (spectrum.hip; contract in include/msk144hip.h): raw = the N new samples of a push
+// (format 0 cu8, 1 cs8, 2 cs16; 16-byte loads when it is 16-byte aligned), B = the bins, a power of two within 256..8192 and <= N;
+// window[B] f32; twiddles[m] = e^{-j2pi m/B}, m < B.  Workgroup g of G <= kSpectrumMaxGroups (a function of floor(N / B) alone) leaves
+// its segments' sums in partials[g][B]; out[j] = their sum in row order, bin (j - B/2) mod B: ascending frequency.
+constexpr int kSpectrumMaxGroups = 512;   // two workgroups on each of 256 CUs
+void launch_spectrum(const void* raw, int format, int N, int B, const float* window, const float2* twiddles, double* partials, double* out, hipStream_t stream);
+
 // the analysis bank in front of the channeliser above 6.144 Msps (bank.hip): raw = the L1-1 history samples then 32 x frames new
 // ones (format 0 cu8, 1 cs8, 2 cs16); h1 = the L1 = 64 K1 bank taps (f32); bands[j] = the occupied band k mod 64 of stream j;
 // tw[t] = e^{+j2pi t/64}.  Writes s_{bands[j]}[n_base + f] of frames f < frames to sub[j * stride + off + f] (complex f32).

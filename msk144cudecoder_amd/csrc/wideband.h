@@ -240,6 +240,31 @@ inline std::string check_blanker(const BlankerParams& p)
     return std::string();
 }
 
+// ---- power spectrum of the input stream (msk144_set_wideband_spectrum, msk144_wideband_spectrum) ----
+
+constexpr int kSpectrumMinBins = 256;   // B, a power of two
+constexpr int kSpectrumMaxBins = 8192;
+constexpr int kSpectrumDefaultBins = 1024;
+
+// the default window, periodic Hann: w[i] = 0.5 - 0.5 cos(2 pi i / B)
+inline std::vector<double> spectrum_window(int B)
+{
+    std::vector<double> w(static_cast<size_t>(B));
+    for(int i = 0; i < B; i++) w[static_cast<size_t>(i)] = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / B);
+    return w;
+}
+
+// The rules of msk144_set_wideband_spectrum: B a power of two within 256..8192 and no longer than a later push of hop_samples
+// input samples, every window value finite (window NULL: the default).  Empty string = valid.
+inline std::string check_spectrum(int B, const double* window, int64_t hop_samples)
+{
+    if(B < kSpectrumMinBins || B > kSpectrumMaxBins || (B & (B - 1)) != 0) return "spectrum bins must be a power of two within 256..8192";
+    if(B > hop_samples) return "spectrum bins exceed the " + std::to_string(hop_samples) + " input samples of a push at this rate";
+    for(int i = 0; window && i < B; i++)
+        if(!std::isfinite(window[i])) return "spectrum window value " + std::to_string(i) + " is not finite";
+    return std::string();
+}
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {

@@ -34,6 +34,11 @@ class WidebandAgc(C.Structure):
     _fields_ = [("lo_sq", C.c_int32), ("hi_sq", C.c_int32), ("clip_ppm", C.c_int32), ("hold", C.c_int32), ("min_exp", C.c_int32), ("max_exp", C.c_int32)]
 
 
+class WidebandSpectrum(C.Structure):
+    """msk144_wideband_spectrum_params: bins and the window (NULL: periodic Hann)."""
+    _fields_ = [("bins", C.c_int32), ("window", C.POINTER(C.c_double))]
+
+
 class WidebandBlanker(C.Structure):
     """msk144_wideband_blanker; BLANKER_DEFAULTS holds the defaults of include/msk144hip.h."""
     _fields_ = [("threshold_q4", C.c_int32), ("pre", C.c_int32), ("post", C.c_int32)]
@@ -109,6 +114,8 @@ PROTOTYPES = {
     "msk144_set_wideband_blanker": ([_vp, _P(WidebandBlanker)], C.c_int),
     "msk144_wideband_blanker_stats": ([_vp, _P(WidebandBlankerCounts)], C.c_int),
     "msk144_dump_wideband_blanked": ([_vp, _vp], C.c_int),
+    "msk144_set_wideband_spectrum": ([_vp, _P(WidebandSpectrum)], C.c_int),
+    "msk144_wideband_spectrum": ([_vp, _P(C.c_double), _P(C.c_int64)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -184,6 +191,7 @@ class HipDecoder:
         self.F, self.D, self.K = f.value, d.value, k.value
         self.channels = channels
         self.read_mode = read_mode
+        self._wb_spectrum_bins = self._wb_spectrum_last = 0   # bins of the next wideband push and of the last one; 0: no spectrum
         b = C.c_int32()
         self._chk(self.L.msk144_llr_block_channels(self.h, C.byref(b)))
         self.llr_block = b.value            # channels per softbits -> index -> LDPC block (the library's choice when llr_block_channels = 0)
@@ -348,6 +356,7 @@ class HipDecoder:
         self._wb_P, self._wb_Q = P, Q
         self._wb_bank_ratio = (P2, Q2)
         self._wb_bank_taps = None if bank_taps is None else np.ascontiguousarray(bank_taps, dtype=np.float64)
+        self._wb_spectrum_bins = self._wb_spectrum_last = 0   # a new configuration has no spectrum
         wp = WidebandParams(int(rate_hz), WB_FORMATS[fmt], int(taps_per_phase), float(gain), len(self._wb_taps),
                             self._wb_taps.ctypes.data_as(C.POINTER(C.c_double)), self._wb_offsets.ctypes.data_as(C.POINTER(C.c_int32)),
                             len(self._wb_offsets))
@@ -375,6 +384,7 @@ class HipDecoder:
             buf[:want] = a
         self._chk(self.L.msk144_push_wideband(self.h, slot, 1 if first else 0))
         self._wb_last_first = bool(first)
+        self._wb_spectrum_last = self._wb_spectrum_bins
 
     def dump_wideband_hop(self, channel: int) -> np.ndarray:
         """int8 [n][2] I/Q of the channel's last push (n = 5184 after a first push, else 2592)."""
@@ -447,6 +457,28 @@ class HipDecoder:
         out = np.empty(((5184 if getattr(self, "_wb_last_first", True) else 2592) // self._wb_Q * self._wb_P, 2), dtype=np.int16)
         self._chk(self.L.msk144_dump_wideband_blanked(self.h, _ptr(out)))
         return out
+
+    def set_wideband_spectrum(self, bins=1024, window=None):
+        """The power spectrum of every push's input samples from the next push on (include/msk144hip.h): bins a power of two within
+        256..8192 and no longer than a later push, window `bins` finite values (None: periodic Hann).
+        set_wideband_spectrum(None) switches it off."""
+        if bins is None:
+            self._chk(self.L.msk144_set_wideband_spectrum(self.h, None))
+            self._wb_spectrum_bins = 0
+            return
+        w = None if window is None else np.ascontiguousarray(window, dtype=np.float64)
+        if w is not None and w.shape != (int(bins),):
+            raise ValueError("the window must hold `bins` values")
+        p = WidebandSpectrum(int(bins), None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk(self.L.msk144_set_wideband_spectrum(self.h, C.byref(p)))
+        self._wb_spectrum_bins = int(bins)
+
+    def wideband_spectrum(self):
+        """(float64 [bins] in ascending frequency - power[j] at (j - bins/2) Fs / bins -, segments) of the last push."""
+        out = np.zeros(max(self._wb_spectrum_last, 1), dtype=np.float64)   # no spectrum in the last push: the library writes nothing
+        seg = C.c_int64()
+        self._chk(self.L.msk144_wideband_spectrum(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(seg)))
+        return out, int(seg.value)
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

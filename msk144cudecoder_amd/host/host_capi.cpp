@@ -80,6 +80,16 @@ int64_t msk144host_wideband_blanker_threshold(int64_t S, int64_t N, int32_t thre
     return static_cast<int64_t>(msk144wb::blanker_threshold(static_cast<uint64_t>(S), static_cast<uint64_t>(N), static_cast<uint32_t>(threshold_q4)));
 }
 
+// The default spectrum window of msk144_set_wideband_spectrum (csrc/wideband.h spectrum_window), periodic Hann: B values into out;
+// returns B, or -1 for a B that is not a power of two within 256..8192.
+int msk144host_wideband_spectrum_window(int B, double* out)
+{
+    if(B < msk144wb::kSpectrumMinBins || B > msk144wb::kSpectrumMaxBins || (B & (B - 1)) != 0) return -1;
+    const std::vector<double> w = msk144wb::spectrum_window(B);
+    if(out) std::memcpy(out, w.data(), sizeof(double) * w.size());
+    return B;
+}
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

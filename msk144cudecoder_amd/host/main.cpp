@@ -72,6 +72,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-gain=auto[:G0]   Stepped AGC per channel, on the GPU, one hop behind the levels: 6 dB down at once when more than 0.1 % of a hop's components clip or its level exceeds 32 LSB rms, 6 dB up after 4 hops below 8 LSB rms, within G0 x 2^-20 .. G0 x 2^20. G0 default=100. A step lands on a hop boundary." << std::endl;
     std::cout << "                   --wideband-levels           With --wideband-rate: at the end, on stderr, one line per channel - rms level in LSB over the run, clipped components, last gain, lowest and highest AGC step - and the three most clipped and three quietest channels." << std::endl;
     std::cout << "                   --wideband-blanker[=RATIO[:PRE[:POST]]]  With --wideband-rate: impulse-noise blanker on the input stream, on the GPU, ahead of the channel filters: a sample whose power exceeds RATIO x the mean power of its hop is zeroed together with PRE samples before and POST after it (0..4096 each). RATIO 1..4095.9, default=16; PRE default=2, POST default=8. At the end, on stderr, one line with the hits and the blanked samples." << std::endl;
+    std::cout << "                   --wideband-spectrum=FILE[:BINS[:HOPS]]  With --wideband-rate: the power spectrum of the input stream at the input rate, on the GPU (of the blanked stream with --wideband-blanker): BINS-point transforms (a power of two, 256..8192, default=1024) of the hop's samples under a Hann window, summed over HOPS hops (default=5), appended to FILE as one line 'hop= rate= bins= segments= dbfs=v0,v1,...' in ascending frequency, 0 dBFS = a full-scale tone. At the end, on stderr, one line with the median bin (the floor) and the highest bin." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -185,6 +186,7 @@ int main(int argc, char* const argv[])
                                            {"taps-per-phase", required_argument, 0, 0},
                                            {"wideband-levels", no_argument, 0, 0},
                                            {"wideband-blanker", optional_argument, 0, 0},
+                                           {"wideband-spectrum", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -235,6 +237,7 @@ int main(int argc, char* const argv[])
         case 27:
         case 28:
         case 29:
+        case 30:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -246,6 +249,7 @@ int main(int argc, char* const argv[])
             else if(idx == 26) good = parse_wideband_gain(optarg, wbo);
             else if(idx == 28) wbo.levels = true;
             else if(idx == 29) good = parse_wideband_blanker(optarg, wbo);
+            else if(idx == 30) good = parse_wideband_spectrum(optarg, wbo);
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
@@ -300,11 +304,19 @@ int main(int argc, char* const argv[])
     if(wideband)
     {
         std::string err;
-        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)))
+        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
+           (wbo.spectrum && !wb_api.load_spectrum(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
         }
+    }
+    // --wideband-spectrum: its file is opened once its entries are known to exist, and still before any library call
+    FILE* spectrum_file = nullptr;
+    if(wbo.spectrum && !(spectrum_file = fopen(wbo.spectrum_file.c_str(), "a")))
+    {
+        std::cerr << "--wideband-spectrum: cannot open '" << wbo.spectrum_file << "': " << strerror(errno) << std::endl;
+        return 2;
     }
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
     const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
@@ -441,6 +453,15 @@ int main(int argc, char* const argv[])
                 return 2;
             }
         }
+        if(wbo.spectrum)
+        {
+            const msk144_wideband_spectrum_params sp{wbo.spectrum_bins, nullptr};
+            if(wb_api.set_spectrum(dec.handle(), &sp) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
         if(wbo.blanker)
         {
             const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
@@ -522,6 +543,7 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
+        if(wbo.spectrum) loops[i]->use_wideband_spectrum(spectrum_file, wbo.spectrum_bins, wbo.spectrum_hops, wbo.rate_hz);
         if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
@@ -630,6 +652,13 @@ int main(int argc, char* const argv[])
                     wbo.blanker_params.threshold_q4 / 16.0, wbo.blanker_params.pre, wbo.blanker_params.post, static_cast<long long>(bc.total_hits),
                     static_cast<long long>(bc.total_blanked), static_cast<long long>(bc.total_samples),
                     bc.total_samples ? 100.0 * static_cast<double>(bc.total_blanked) / static_cast<double>(bc.total_samples) : 0.0);
+        if(wbo.spectrum)
+        {
+            const DeviceLoop::SpectrumSummary sm = loops[0]->wideband_spectrum_summary();
+            if(sm.segments)
+                fprintf(stderr, "msk144hipdecoder: wideband spectrum: %d bins of %.1f Hz over %lld segments, floor (median bin) %.2f dBFS, highest bin %.2f dBFS at %+.0f Hz\n",
+                        wbo.spectrum_bins, static_cast<double>(wbo.rate_hz) / wbo.spectrum_bins, sm.segments, sm.median_dbfs, sm.peak_dbfs, sm.peak_hz);
+        }
         if(wbo.levels)
         {
             const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();
@@ -684,6 +713,7 @@ int main(int argc, char* const argv[])
                         dev[MSK144_T_H2D], dev[MSK144_T_FRONTEND], dev[MSK144_T_SCAN], dev[MSK144_T_SOFTBITS], dev[MSK144_T_INDEX], dev[MSK144_T_LDPC], dev[MSK144_T_COLLECT], dev[MSK144_T_D2H]);
         }
     }
+    if(spectrum_file) fclose(spectrum_file);
     std::cout << "Done" << std::endl;
     return 0;
 }

@@ -210,9 +210,11 @@ int DeviceLoop::join()
         int64_t clipped = 0;
         if(wb_->clip(dec_.handle(), &clipped) == MSK144_OK) wb_clipped_ += clipped;
         if(wb_read_levels_) read_wideband_levels();
+        if(wb_spec_file_) read_wideband_spectrum();
         wb_components_ += wb_pending_components_;
         wb_pending_components_ = 0;
     }
+    if(wb_spec_file_ && wb_spec_group_pushes_) write_spectrum_line();  // the last, shorter group
     return failed ? 2 : 0;
 }
 
@@ -238,7 +240,7 @@ bool DeviceLoop::submit_wideband(Batch& b)
         }
         wb_clipped_ += clipped;
         wb_components_ += wb_pending_components_;
-        if(wb_read_levels_ && !read_wideband_levels())
+        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()))
         {
             fail(msk144_last_error(dec_.handle()));
             return false;
@@ -286,6 +288,72 @@ bool DeviceLoop::read_wideband_levels()
         a.max_exp = fresh ? v.exponent : std::max(a.max_exp, static_cast<int>(v.exponent));
     }
     return true;
+}
+
+void DeviceLoop::use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz)
+{
+    wb_spec_file_ = file;
+    wb_spec_hops_ = hops;
+    wb_spec_rate_ = rate_hz;
+    // 0 dBFS is S (sum w)^2 of the window the device holds: the default one, rounded to f32
+    double sum = 0.0;
+    for(double v : msk144wb::spectrum_window(bins)) sum += static_cast<double>(static_cast<float>(v));
+    wb_spec_full_ = sum * sum;
+    wb_spec_buf_.assign(static_cast<size_t>(bins), 0.0);
+    wb_spec_group_ = wb_spec_run_ = wb_spec_buf_;
+}
+
+namespace
+{
+double spectrum_dbfs(double power, double full)
+{
+    const double db = power > 0.0 && full > 0.0 ? 10.0 * std::log10(power / full) : -200.0;
+    return db < -200.0 ? -200.0 : std::round(db * 100.0) / 100.0 + 0.0;  // two decimals, and no "-0.00"
+}
+}  // namespace
+
+// --wideband-spectrum: the spectrum of the push just made (read where its clip count is read), added to the open group and the run
+bool DeviceLoop::read_wideband_spectrum()
+{
+    int64_t segments = 0;
+    if(wb_->spectrum(dec_.handle(), wb_spec_buf_.data(), &segments) != MSK144_OK) return false;
+    for(size_t j = 0; j < wb_spec_buf_.size(); j++)
+    {
+        wb_spec_group_[j] += wb_spec_buf_[j];
+        wb_spec_run_[j] += wb_spec_buf_[j];
+    }
+    wb_spec_group_segments_ += segments;
+    wb_spec_run_segments_ += segments;
+    wb_spec_group_pushes_++;
+    wb_spec_pushes_++;
+    if(wb_spec_group_pushes_ == wb_spec_hops_) write_spectrum_line();
+    return true;
+}
+
+void DeviceLoop::write_spectrum_line()
+{
+    fprintf(wb_spec_file_, "hop=%lld rate=%lld bins=%zu segments=%lld dbfs=", wb_spec_pushes_ - 1, wb_spec_rate_, wb_spec_group_.size(), wb_spec_group_segments_);
+    const double full = static_cast<double>(wb_spec_group_segments_) * wb_spec_full_;
+    for(size_t j = 0; j < wb_spec_group_.size(); j++) fprintf(wb_spec_file_, j ? ",%.2f" : "%.2f", spectrum_dbfs(wb_spec_group_[j], full));
+    fputc('\n', wb_spec_file_);
+    fflush(wb_spec_file_);
+    std::fill(wb_spec_group_.begin(), wb_spec_group_.end(), 0.0);
+    wb_spec_group_segments_ = wb_spec_group_pushes_ = 0;
+}
+
+DeviceLoop::SpectrumSummary DeviceLoop::wideband_spectrum_summary() const
+{
+    SpectrumSummary r;
+    if(!wb_spec_run_segments_) return r;
+    r.segments = wb_spec_run_segments_;
+    const double full = static_cast<double>(wb_spec_run_segments_) * wb_spec_full_;
+    const size_t B = wb_spec_run_.size(), top = static_cast<size_t>(std::max_element(wb_spec_run_.begin(), wb_spec_run_.end()) - wb_spec_run_.begin());
+    std::vector<double> sorted = wb_spec_run_;
+    std::nth_element(sorted.begin(), sorted.begin() + B / 2, sorted.end());
+    r.median_dbfs = spectrum_dbfs(sorted[B / 2], full);
+    r.peak_dbfs = spectrum_dbfs(wb_spec_run_[top], full);
+    r.peak_hz = (static_cast<double>(top) - static_cast<double>(B / 2)) * static_cast<double>(wb_spec_rate_) / static_cast<double>(B);
+    return r;
 }
 
 DeviceLoop::StreamReport DeviceLoop::stream_report(int local) const

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -101,6 +102,19 @@ public:
         wb_read_levels_ = levels;
     }
 
+    // --wideband-spectrum: msk144_wideband_spectrum is read once per push, where its clip count is read, and summed in double; after
+    // every `hops` pushes (and for a last, shorter group in join()) one line goes to `file`:
+    // hop=<index of the last push> rate=<Fs> bins=<B> segments=<sum> dbfs=<v0>,<v1>,...  in ascending frequency, two decimals,
+    // 0 dBFS = a full-scale tone on a bin centre (include/msk144hip.h), floored at -200
+    void use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz);
+    // over the run: the median bin (the floor) and the highest bin with its frequency from the centre; segments 0: no push was read
+    struct SpectrumSummary
+    {
+        long long segments = 0;
+        double median_dbfs = 0.0, peak_dbfs = 0.0, peak_hz = 0.0;
+    };
+    SpectrumSummary wideband_spectrum_summary() const;
+
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
     // window afterwards).  Blocks while two blocks are already queued (back-pressure into the reader).  false once the loop failed.
@@ -166,6 +180,8 @@ private:
     bool enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream);
     bool submit_wideband(Batch& b);
     bool read_wideband_levels();
+    bool read_wideband_spectrum();
+    void write_spectrum_line();
 
     WindowDecoder dec_;
     const int nch_, base_, device_;
@@ -180,6 +196,12 @@ private:
     bool wb_read_levels_ = false;
     std::vector<ChannelLevel> wb_levels_;
     std::vector<msk144_wideband_level> wb_level_buf_;
+    FILE* wb_spec_file_ = nullptr;
+    int wb_spec_hops_ = 0;
+    long long wb_spec_rate_ = 0, wb_spec_pushes_ = 0;  // pushes read so far
+    double wb_spec_full_ = 0.0;                        // (sum w)^2 of the default window
+    std::vector<double> wb_spec_buf_, wb_spec_group_, wb_spec_run_;  // the last push, the open group, the run
+    long long wb_spec_group_segments_ = 0, wb_spec_group_pushes_ = 0, wb_spec_run_segments_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;
     std::vector<Stream> st_;

@@ -51,6 +51,20 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-spectrum: resolved only when it is given (load_spectrum)
+    int (*set_spectrum)(msk144_handle*, const msk144_wideband_spectrum_params*) = nullptr;
+    int (*spectrum)(msk144_handle*, double*, int64_t*) = nullptr;
+
+    bool load_spectrum(std::string& err)
+    {
+        set_spectrum = reinterpret_cast<decltype(set_spectrum)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_spectrum"));
+        spectrum = reinterpret_cast<decltype(spectrum)>(dlsym(RTLD_DEFAULT, "msk144_wideband_spectrum"));
+        if(set_spectrum && spectrum) return true;
+        err = std::string("the loaded libmsk144hip has no input spectrum (") + (set_spectrum ? "msk144_wideband_spectrum" : "msk144_set_wideband_spectrum") +
+              "): --wideband-spectrum needs it";
+        return false;
+    }
+
     bool load(std::string& err)
     {
         set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
@@ -73,6 +87,10 @@ struct WidebandOptions
     bool levels = false;  // --wideband-levels: the per-channel table in the summary
     bool blanker = false; // --wideband-blanker[=RATIO[:PRE[:POST]]]: the impulse-noise blanker on the input stream
     msk144wb::BlankerParams blanker_params;
+    bool spectrum = false; // --wideband-spectrum=FILE[:BINS[:HOPS]]: the input spectrum, one line per HOPS pushes appended to FILE
+    std::string spectrum_file;
+    int spectrum_bins = msk144wb::kSpectrumDefaultBins;
+    int spectrum_hops = 5;
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -135,6 +153,29 @@ inline bool parse_wideband_blanker(const char* arg, WidebandOptions& w)
     return msk144wb::check_blanker(w.blanker_params).empty();
 }
 
+// "FILE[:BINS[:HOPS]]": BINS a power of two within 256..8192 (whether a push is long enough needs the rate: check_wideband_options),
+// HOPS >= 1 pushes per line
+inline bool parse_wideband_spectrum(const std::string& s, WidebandOptions& w)
+{
+    w.spectrum = true;
+    const size_t a = s.find(':');
+    const size_t b = a == std::string::npos ? a : s.find(':', a + 1);
+    w.spectrum_file = s.substr(0, a);
+    if(w.spectrum_file.empty() || (b != std::string::npos && s.find(':', b + 1) != std::string::npos)) return false;
+    long long v = 0;
+    if(a != std::string::npos)
+    {
+        if(!parse_int(s.substr(a + 1, b == std::string::npos ? b : b - a - 1), v) || v < msk144wb::kSpectrumMinBins || v > msk144wb::kSpectrumMaxBins || (v & (v - 1)) != 0) return false;
+        w.spectrum_bins = static_cast<int>(v);
+    }
+    if(b != std::string::npos)
+    {
+        if(!parse_int(s.substr(b + 1), v) || v < 1 || v > 1000000) return false;
+        w.spectrum_hops = static_cast<int>(v);
+    }
+    return true;
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -183,6 +224,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
 {
     if(!w.parse_error.empty()) return w.parse_error;
     if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
+    if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
@@ -190,6 +232,11 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     const std::string why = msk144wb::check_config(w.rate_hz, w.format, w.taps_per_phase, w.gain, w.offsets.data(), static_cast<int>(w.offsets.size()));
     if(why.empty() && w.agc && !msk144wb::gain_ok(w.gain, msk144wb::AgcParams().max_exp))
         return "--wideband-gain=auto:G0 needs 128 x G0 x 2^20 finite (the top of the AGC's ladder)";
+    if(why.empty() && w.spectrum)
+    {
+        const std::string bad = msk144wb::check_spectrum(w.spectrum_bins, nullptr, 2592 * w.rate_hz / msk144wb::kOutRate);
+        if(!bad.empty()) return "--wideband-spectrum: " + bad;
+    }
     return why;
 }
 

@@ -311,6 +311,55 @@ class Blanker:
         return out.reshape(-1), st
 
 
+# ---- the power spectrum of the input stream (msk144_set_wideband_spectrum) ----
+
+SPECTRUM_MIN_BINS, SPECTRUM_MAX_BINS, SPECTRUM_DEFAULT_BINS = 256, 8192, 1024
+SPECTRUM_FLOOR_DBFS = -200.0
+
+
+def spectrum_window(bins: int) -> np.ndarray:
+    """The default window of the contract, periodic Hann: w[i] = 0.5 - 0.5 cos(2 pi i / B), float64 (the library's own is
+    msk144host_wideband_spectrum_window)."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(bins), dtype=np.float64) / int(bins))
+
+
+def spectrum_dbfs(power, segments: int, window) -> np.ndarray:
+    """10 log10(P / (S (sum w)^2)), floored at -200: a full-scale complex tone on a bin centre reads 0 dBFS."""
+    full = float(segments) * float(np.sum(np.asarray(window, dtype=np.float64))) ** 2
+    p = np.asarray(power, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        db = 10.0 * np.log10(p / full) if full > 0.0 else np.full(p.shape, SPECTRUM_FLOOR_DBFS)
+    return np.maximum(np.nan_to_num(db, nan=SPECTRUM_FLOOR_DBFS, neginf=SPECTRUM_FLOOR_DBFS), SPECTRUM_FLOOR_DBFS)
+
+
+class Spectrum:
+    """The power spectrum of the contract (include/msk144hip.h), push by push and in float64 throughout: S = floor(N / B) segments of
+    the push's own samples, not overlapped, P[k] = sum_s |FFT(w x_s)[k]|^2, returned in ascending frequency (power[j] is bin
+    (j - B/2) mod B).  The window is the f32 the device stores, as float64.  fmt is the format the samples arrive in: a raw format, or
+    "cs16" for the output of the Blanker model.  Nothing is carried from push to push."""
+
+    def __init__(self, fmt: str, bins: int = SPECTRUM_DEFAULT_BINS, window=None):
+        if fmt not in FORMATS:
+            raise ValueError(f"format must be one of {FORMATS}")
+        bins = int(bins)
+        if not SPECTRUM_MIN_BINS <= bins <= SPECTRUM_MAX_BINS or bins & (bins - 1):
+            raise ValueError("bins must be a power of two within 256..8192")
+        w = spectrum_window(bins) if window is None else np.asarray(window, dtype=np.float64)
+        if w.shape != (bins,) or not np.all(np.isfinite(w)):
+            raise ValueError("the window must hold `bins` finite values")
+        self.fmt, self.bins = fmt, bins
+        self.window = w.astype(np.float32).astype(np.float64)
+
+    def push(self, raw):
+        """(power float64 [bins] in ascending frequency, segments) of one push's raw samples."""
+        x = read_samples(raw, self.fmt)
+        S = len(x) // self.bins
+        if S < 1:
+            raise ValueError("a push must hold at least one segment")
+        X = np.fft.fft(x[:S * self.bins].reshape(S, self.bins) * self.window[None, :], axis=1)
+        return np.fft.fftshift(np.sum(X.real ** 2 + X.imag ** 2, axis=0)), S
+
+
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 
