@@ -539,6 +539,70 @@ typedef struct msk144_wideband_spectrum_params
 int msk144_set_wideband_spectrum(msk144_handle* h, const msk144_wideband_spectrum_params* p);
 int msk144_wideband_spectrum(msk144_handle* h, double* power /*[bins]*/, int64_t* segments);
 
+/* ---- Per-channel ping detection (no reference counterpart) ----
+ *
+ * What a meteor-scatter operator looks for first is whether, when and where something burst out of the noise; a decode line appears
+ * only when a ping was long and strong enough to decode.  Every channel's int8 hop sits on the device right behind the channeliser,
+ * so a short-time energy profile per channel and an integer detection rule are evaluated there, and the program turns the reports
+ * into an event log.  The detector only reads the staged hops.  Everything below is per channel and per push, in integers.
+ *
+ *   Input:      the int8 I/Q values of the channel's push exactly as stored, what msk144_dump_wideband_hop returns: M = 5184 after a
+ *               first push, else 2592.
+ *   Blocks:     one block is B = 96 samples, 8 ms (a 72 ms MSK144 frame is 9 blocks); nb = M / 96 is 54 or 27.
+ *               E[b] = sum of I*I + Q*Q over samples 96b .. 96b + 95, at most 96 . 2 . 128^2 = 3145728 < 2^22.
+ *   Quiet:      q = the value at rank floor(nb / 4), counted from 0, of E sorted in ascending order (rank 6 of 27, rank 13 of 54): a
+ *               lower quartile, which a ping of up to about 3/4 of a push does not move.
+ *   Reference:  R = max(min(q, the q of the last h earlier pushes of this stream), min_ref), h = min(memory, pushes since the history
+ *               last restarted).  The history restarts at a first push, at the first push after msk144_set_wideband_pings, and at any
+ *               push whose quantiser scale differs from the previous push's - the f32 `gain` msk144_wideband_levels reports for the
+ *               push, compared for equality - so that an AGC step or new gains restart the memory instead of rescaling it.
+ *   Up:         block b is up iff E[b] . 16 > R . ratio_q4, strictly, in 64-bit arithmetic (csrc/wideband.h ping_up).
+ *   Parameters: 16 <= ratio_q4 <= 65535 (default 32: 2.0 x the reference), 0 <= memory <= 16 pushes (default 8, about 1.7 s of hops),
+ *               1 <= min_ref <= 2^22 (default 96: a mean of 1 LSB^2 per sample; below it the channel is under-driven and R is held
+ *               there).  The defaults are design parameters, not measurements.
+ *   Sensitivity: this is a strong-ping detector, less sensitive than the decoder.  A ping at S dB in 2500 Hz lifts a 12 kHz channel by
+ *               1 + 10^(S/10) . 2500/12000, so the defaults see pings from roughly +7 dB up.  In a CPU simulation of the model (no
+ *               GPU measurement stands behind these figures) white int8 noise at 3 and at 20 LSB rms, 1.66 M blocks each with memory
+ *               8, put 0 blocks up at ratio 2.0, 2-3 at 1.75 and about 2600 at 1.5; in a 240 ksps scene with noise at about 20 LSB rms
+ *               every block wholly inside a +10 dB ping was up, most at +7 dB, almost none at +4 dB.
+ *   Events:     the program (and wideband.PingEvents) joins up blocks into events: with g = (blocks of all earlier pushes) + b, an
+ *               event is a maximal run of consecutive up blocks in g; a run that reaches a push's last block stays open into the
+ *               next push, a history restart does not close it, the end of the stream does (csrc/wideband.h PingTracker).
+ *   Order:      msk144_set_wideband_pings(h, &p) switches the detector on from the next push and allocates everything it needs - a
+ *               push allocates nothing; (h, NULL) switches it off, as msk144_set_wideband does.  msk144_wideband_pings reports the last
+ *               push and synchronises like msk144_wideband_levels.  The same stream pushed twice gives the same bytes: a first push
+ *               clears the history.  Whether the detector is on or off, every hop, clip count, level, AGC step, blanker statistic,
+ *               spectrum and decode is byte for byte the same.
+ *   Refused:    MSK144_EINVAL outside wideband mode and for parameters out of range; MSK144_ESTATE from either read entry before a
+ *               push made with the detector on. */
+typedef struct msk144_wideband_ping
+{
+    uint64_t up_mask;   /* bit b is set iff block b is up */
+    int32_t blocks;     /* nb */
+    int32_t history;    /* h, the number of earlier pushes R drew on */
+    int32_t quiet;      /* q */
+    int32_t reference;  /* R */
+    int32_t peak;       /* max E */
+    int32_t peak_block; /* the lowest b at the maximum */
+} msk144_wideband_ping;
+
+typedef struct msk144_wideband_pings_params
+{
+    int32_t ratio_q4; /* 16 x the ratio to the reference (32) */
+    int32_t memory;   /* earlier pushes whose quiet level bounds the reference (8) */
+    int32_t min_ref;  /* floor of the reference (96) */
+} msk144_wideband_pings_params;
+
+#define MSK144_PING_MAX_BLOCKS 54
+
+/* NULL: off */
+int msk144_set_wideband_pings(msk144_handle* h, const msk144_wideband_pings_params* p);
+/* out[channels]: the last push */
+int msk144_wideband_pings(msk144_handle* h, msk144_wideband_ping* out);
+/* test and debug, like msk144_dump_wideband_hop: E of the channel's last push in energies[0 .. *n), energies[54]; the rest is 0.
+ * channel = -1: every channel's, energies[channels][54] (what the program's event log reads, in one copy) */
+int msk144_wideband_ping_blocks(msk144_handle* h, int32_t channel, int32_t* energies, int32_t* n);
+
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
 int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);

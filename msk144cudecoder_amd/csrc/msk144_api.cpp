@@ -166,6 +166,13 @@ struct msk144_handle
         float2* d_spec_tw = nullptr;        // [B] e^{-j2pi m/B}
         double* d_spec_partials = nullptr;  // [kSpectrumMaxGroups][spectrum_rows_bins]
         double* d_spec_out = nullptr;       // [B] ascending frequency
+        // ping detection (msk144_set_wideband_pings): applies from the next push; `set` allocates.  ping_restart: the next push is
+        // the first since `set`; ping_pushed: the last push left records
+        bool pings = false, ping_restart = false, ping_pushed = false;
+        msk144wb::PingParams ping_params;
+        msk144wb::PingHistory* d_ping_state = nullptr;   // [channels]
+        msk144wb::PingRecord* d_ping_records = nullptr;  // [channels]
+        int32_t* d_ping_energies = nullptr;              // [channels][54]
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -589,6 +596,17 @@ int wb_quiesce(msk144_handle* h, const char* who)
 {
     if(!h) return fail(h, MSK144_EINVAL, "null argument");
     if(!h->wb.configured) return fail(h, MSK144_EINVAL, std::string(who) + " needs wideband mode (msk144_set_wideband)");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MSK144_OK;
+}
+
+// the read entries of the ping detector: wideband mode, and the last push made with the detector on; waits for that push
+int wb_ping_ready(msk144_handle* h, const char* who)
+{
+    const auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, std::string(who) + " needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !w.ping_pushed) return fail(h, MSK144_ESTATE, w.started ? "the last wideband push was made without the ping detector" : "no wideband push has been made");
     HIP_TRY(h, hipSetDevice(h->params.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MSK144_OK;
@@ -1482,6 +1500,13 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
                       w.P, w.Q, w.hist, M, first ? 1 : 0, w.m_next, w.d_scale, w.d_levels, h->stream, bands);
     if(w.agc)
         launch_agc_step(w.d_levels, w.bank ? w.d_slot_channel : nullptr, w.d_gains, w.d_exp, w.d_quiet, w.d_used_exp, w.d_scale, w.slots, M, w.agc_params, h->stream);
+    if(w.pings)
+    {
+        launch_pings(reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), first ? 1 : 0, C, w.d_gains, w.agc ? w.d_used_exp : nullptr, w.ping_params,
+                     first || w.ping_restart ? 1 : 0, w.d_ping_state, w.d_ping_records, w.d_ping_energies, h->stream);
+        w.ping_restart = false;
+    }
+    w.ping_pushed = w.pings;
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     w.push_gains = w.gains;
@@ -1681,6 +1706,56 @@ int msk144_wideband_spectrum(msk144_handle* h, double* power, int64_t* segments)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(power, w.d_spec_out, sizeof(double) * static_cast<size_t>(w.spectrum_last_bins), hipMemcpyDeviceToHost));
     *segments = static_cast<int64_t>(w.last_first ? kWindowSamples : kHopSamples) / w.Qin * w.Pin / w.spectrum_last_bins;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_pings(msk144_handle* h, const msk144_wideband_pings_params* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_pings");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(!p)
+    {
+        w.pings = false;
+        return MSK144_OK;
+    }
+    const msk144wb::PingParams pp{p->ratio_q4, p->memory, p->min_ref};
+    const std::string why = msk144wb::check_pings(pp);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    // never in a push
+    const size_t C = w.gains.size();
+    if(!w.d_ping_state && (rc = dev_alloc(h, w.mem, &w.d_ping_state, C)) != MSK144_OK) return rc;
+    if(!w.d_ping_records && (rc = dev_alloc(h, w.mem, &w.d_ping_records, C)) != MSK144_OK) return rc;
+    if(!w.d_ping_energies && (rc = dev_alloc(h, w.mem, &w.d_ping_energies, C * msk144wb::kPingMaxBlocks)) != MSK144_OK) return rc;
+    HIP_TRY(h, hipMemset(w.d_ping_state, 0, sizeof(msk144wb::PingHistory) * C));
+    w.ping_params = pp;
+    w.pings = true;
+    w.ping_restart = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_pings(msk144_handle* h, msk144_wideband_ping* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    const int rc = wb_ping_ready(h, "msk144_wideband_pings");
+    if(rc != MSK144_OK) return rc;
+    static_assert(sizeof(msk144_wideband_ping) == sizeof(msk144wb::PingRecord) && offsetof(msk144_wideband_ping, peak_block) == offsetof(msk144wb::PingRecord, peak_block),
+                  "the kernel writes msk144_wideband_ping");
+    HIP_TRY(h, hipMemcpy(out, h->wb.d_ping_records, sizeof(msk144_wideband_ping) * h->wb.gains.size(), hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_wideband_ping_blocks(msk144_handle* h, int32_t channel, int32_t* energies, int32_t* n)
+{
+    if(!h || !energies || !n) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(w.configured && (channel < -1 || channel >= h->params.channels)) return fail(h, MSK144_EINVAL, "channel out of range");
+    const int rc = wb_ping_ready(h, "msk144_wideband_ping_blocks");
+    if(rc != MSK144_OK) return rc;
+    const size_t row = msk144wb::kPingMaxBlocks;
+    if(channel < 0) HIP_TRY(h, hipMemcpy(energies, w.d_ping_energies, sizeof(int32_t) * row * w.gains.size(), hipMemcpyDeviceToHost));
+    else HIP_TRY(h, hipMemcpy(energies, w.d_ping_energies + row * static_cast<size_t>(channel), sizeof(int32_t) * row, hipMemcpyDeviceToHost));
+    *n = (w.last_first ? kWindowSamples : kHopSamples) / msk144wb::kPingBlock;
     return MSK144_OK;
 }
 

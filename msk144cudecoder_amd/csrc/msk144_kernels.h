@@ -113,6 +113,14 @@ void launch_channelise(const void* raw, int format, const float2* G, const Wideb
 void launch_agc_step(const unsigned long long* levels, const int32_t* slot_channel, const float* gains, int32_t* exps, int32_t* quiet, int32_t* used_exps, float* scale,
                      int slots, int samples, const msk144wb::AgcParams& p, hipStream_t stream);
 
+// ping detection on the staged hops of a push (pings.hip; contract in include/msk144hip.h), behind the channeliser and the AGC step:
+// first_halves and hops are the hop ring's staging, [channels][5184] bytes each (with first != 0 a channel's push is its row of
+// first_halves followed by its row of hops).  gains[channels] and used_exps[channels] (NULL without the AGC: exponent 0) give the
+// scale each channel's push was quantised with; restart != 0 restarts every channel's history.  Writes records[channels] and
+// energies[channels][54] (0 past the push's blocks) and moves state[channels].
+void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float* gains, const int32_t* used_exps, const msk144wb::PingParams& p,
+                  int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, hipStream_t stream);
+
 // what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
 // before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push
 struct BlankerCounters

@@ -3,8 +3,10 @@
 // Header-only, plain C++ (no HIP), so that every one of those builds gets the same taps and the same checks.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <numeric>
 #include <string>
@@ -263,6 +265,195 @@ inline std::string check_spectrum(int B, const double* window, int64_t hop_sampl
     for(int i = 0; window && i < B; i++)
         if(!std::isfinite(window[i])) return "spectrum window value " + std::to_string(i) + " is not finite";
     return std::string();
+}
+
+// ---- per-channel ping detection (msk144_set_wideband_pings, msk144_wideband_pings) ----
+
+constexpr int kPingBlock = 96;        // B: samples per block, 8 ms; a 72 ms frame is 9 blocks
+constexpr int kPingMaxBlocks = 54;    // nb of a first push (5184 / 96); a later push has 27
+constexpr int kPingEnergyBits = 22;   // E <= 96 x 2 x 128^2 = 3145728 < 2^22
+constexpr int kPingMaxMemory = 16;
+constexpr int kPingMinRatioQ4 = 16;   // 1 x the reference
+constexpr int kPingMaxRatioQ4 = 65535;
+constexpr int kPingMaxMinRef = 1 << kPingEnergyBits;
+constexpr int kPingDefaultMinBlocks = 2;  // the event rule's, a parameter of the program and the model
+constexpr int kPingMaxMinBlocks = 64;
+
+// msk144_wideband_pings_params, field for field.  The defaults are design parameters, not measurements: 2.0 x the reference, the
+// quiet levels of 8 earlier pushes (about 1.7 s), and a floor of 1 LSB^2 per sample under the reference.
+struct PingParams
+{
+    int32_t ratio_q4 = 32;
+    int32_t memory = 8;
+    int32_t min_ref = 96;
+};
+
+// msk144_wideband_ping, field for field: what the kernel writes
+struct PingRecord
+{
+    uint64_t up_mask;
+    int32_t blocks, history, quiet, reference, peak, peak_block;
+};
+static_assert(sizeof(PingRecord) == 32, "msk144_wideband_ping is 32 bytes");
+
+// A channel's memory on the device: the quiet levels of its last pushes (a ring of 16, the next one goes to q[pos]), how many of
+// them belong to the running history (at most 16), and the scale the last push was quantised with.
+struct PingHistory
+{
+    int32_t q[kPingMaxMemory];
+    int32_t count, pos;
+    float scale;
+    int32_t reserved;
+};
+
+// the rank, counted from 0 in ascending order, of the quiet level among the nb block energies of a push: a lower quartile
+MSK144WB_HD inline int ping_rank(int nb) { return nb / 4; }
+
+// The history rule, once.  `restart`: a first push, or the first one after msk144_set_wideband_pings; a scale other than the last
+// push's restarts the history as well.  Returns the minimum of q and the quiet levels of the h earlier pushes that count.
+MSK144WB_HD inline int32_t ping_history_min(const PingHistory& s, bool restart, float scale, int32_t memory, int32_t q, int32_t& h)
+{
+    const int32_t n = restart || s.scale != scale ? 0 : s.count;
+    h = n < memory ? n : memory;
+    int32_t m = q;
+    for(int32_t i = 1; i <= h; i++)
+    {
+        const int32_t v = s.q[(s.pos - i) & (kPingMaxMemory - 1)];
+        m = v < m ? v : m;
+    }
+    return m;
+}
+
+// ... and the push's own quiet level joins the history behind it
+MSK144WB_HD inline void ping_history_put(PingHistory& s, bool restart, float scale, int32_t q)
+{
+    if(restart || s.scale != scale) s.count = s.pos = 0;
+    s.q[s.pos] = q;
+    s.pos = (s.pos + 1) & (kPingMaxMemory - 1);
+    s.count = s.count < kPingMaxMemory ? s.count + 1 : kPingMaxMemory;
+    s.scale = scale;
+}
+
+// R = max(min(q, history), min_ref), and the up rule: E x 16 > R x ratio_q4, strictly, in 64 bits
+MSK144WB_HD inline int32_t ping_reference(int32_t history_min, int32_t min_ref) { return history_min > min_ref ? history_min : min_ref; }
+MSK144WB_HD inline bool ping_up(int32_t E, int32_t R, int32_t ratio_q4) { return static_cast<int64_t>(E) * 16 > static_cast<int64_t>(R) * ratio_q4; }
+
+// The rules of msk144_set_wideband_pings that need no handle.  Empty string = valid.
+inline std::string check_pings(const PingParams& p)
+{
+    if(p.ratio_q4 < kPingMinRatioQ4 || p.ratio_q4 > kPingMaxRatioQ4) return "ping ratio_q4 must lie within 16..65535 (1 .. 4095.94 x the reference)";
+    if(p.memory < 0 || p.memory > kPingMaxMemory) return "ping memory must lie within 0..16 pushes";
+    if(p.min_ref < 1 || p.min_ref > kPingMaxMinRef) return "ping min_ref must lie within 1..4194304";
+    return std::string();
+}
+
+// One push of one channel on the host, from its nb block energies: the record the kernel writes (the radix select there and the
+// sort here pick the same value).  What libmsk144host.so holds the Python model to.
+inline PingRecord ping_record(const PingParams& p, PingHistory& s, bool restart, float scale, const int32_t* E, int nb)
+{
+    std::vector<int32_t> sorted(E, E + nb);
+    std::sort(sorted.begin(), sorted.end());
+    PingRecord r{};
+    r.blocks = nb;
+    r.quiet = sorted[static_cast<size_t>(ping_rank(nb))];
+    r.reference = ping_reference(ping_history_min(s, restart, scale, p.memory, r.quiet, r.history), p.min_ref);
+    ping_history_put(s, restart, scale, r.quiet);
+    r.peak = E[0];
+    for(int b = 0; b < nb; b++)
+    {
+        if(ping_up(E[b], r.reference, p.ratio_q4)) r.up_mask |= 1ull << b;
+        if(E[b] > r.peak) r.peak = E[b], r.peak_block = b;
+    }
+    return r;
+}
+
+// An event: a maximal run of consecutive up blocks of one channel in g = (blocks of all earlier pushes) + b
+struct PingEvent
+{
+    int32_t channel;
+    int64_t start, blocks;  // in blocks of 8 ms
+    int32_t peak;           // the largest E of the run (at its lowest g on a tie) ...
+    int32_t reference;      // ... and the R of the push that block lay in
+};
+
+// The event rule, once.  A run that reaches a push's last block stays open into the next push; a history restart does not close
+// it; close() (the end of the stream) does.  An event is reported when it closes, if it has at least min_blocks blocks: by push,
+// then by channel, then by start.  Host only: the program's log and, through libmsk144host.so, the yardstick of the Python model.
+class PingTracker
+{
+public:
+    PingTracker(int channels, int min_blocks) : min_blocks_(min_blocks), open_(static_cast<size_t>(channels)), count_(static_cast<size_t>(channels), 0), up_(static_cast<size_t>(channels), 0) {}
+
+    // records[channels] of one push and its block energies [channels][kPingMaxBlocks]
+    void push(const PingRecord* records, const int32_t* energies, std::vector<PingEvent>& out)
+    {
+        int nb = 0;
+        for(size_t c = 0; c < open_.size(); c++)
+        {
+            const PingRecord& r = records[c];
+            const int32_t* E = energies + c * kPingMaxBlocks;
+            Run& o = open_[c];
+            nb = r.blocks;
+            for(int b = 0; b < r.blocks; b++)
+            {
+                if((r.up_mask >> b) & 1)
+                {
+                    if(!o.blocks) o = Run{base_ + b, 0, E[b], r.reference};
+                    else if(E[b] > o.peak) o.peak = E[b], o.reference = r.reference;
+                    o.blocks++;
+                    up_[c]++;
+                }
+                else finish(static_cast<int32_t>(c), out);
+            }
+            total_ += r.blocks;
+        }
+        base_ += nb;
+    }
+
+    void close(std::vector<PingEvent>& out)
+    {
+        for(size_t c = 0; c < open_.size(); c++) finish(static_cast<int32_t>(c), out);
+    }
+
+    int64_t events() const { return events_; }
+    int64_t up_blocks() const { return std::accumulate(up_.begin(), up_.end(), static_cast<int64_t>(0)); }
+    int64_t total_blocks() const { return total_; }
+    const std::vector<int64_t>& channel_events() const { return count_; }  // reported events per channel
+    const std::vector<int64_t>& channel_up_blocks() const { return up_; }
+
+private:
+    struct Run
+    {
+        int64_t start = 0, blocks = 0;
+        int32_t peak = 0, reference = 0;
+    };
+
+    void finish(int32_t c, std::vector<PingEvent>& out)
+    {
+        Run& o = open_[static_cast<size_t>(c)];
+        if(o.blocks >= min_blocks_)
+        {
+            out.push_back(PingEvent{c, o.start, o.blocks, o.peak, o.reference});
+            count_[static_cast<size_t>(c)]++;
+            events_++;
+        }
+        o.blocks = 0;
+    }
+
+    int64_t min_blocks_;
+    int64_t base_ = 0, total_ = 0, events_ = 0;
+    std::vector<Run> open_;
+    std::vector<int64_t> count_, up_;
+};
+
+// One line of the event log (--wideband-pings=FILE).  start and dur are block counts x 8 ms, exact in three decimals.
+inline std::string ping_event_line(const PingEvent& e, int32_t offset_hz)
+{
+    char buf[256];
+    const long long s = static_cast<long long>(e.start) * 8, d = static_cast<long long>(e.blocks) * 8;
+    snprintf(buf, sizeof(buf), "ping ch=%d offset=%d start=%lld.%03lld dur=%lld.%03lld blocks=%lld peak=%d ref=%d peak_db=%.1f", e.channel, offset_hz, s / 1000, s % 1000,
+             d / 1000, d % 1000, static_cast<long long>(e.blocks), e.peak, e.reference, 10.0 * std::log10(static_cast<double>(e.peak) / static_cast<double>(e.reference)));
+    return buf;
 }
 
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.

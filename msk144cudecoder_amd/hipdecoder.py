@@ -14,6 +14,7 @@ import numpy as np
 
 from .protocol import ITEM_BYTES
 from .wideband import AGC_DEFAULTS, BLANKER_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc and _blanker; msk144_wideband_level
+from .wideband import PING_DTYPE, PING_MAX_BLOCKS, PINGS_DEFAULTS    # msk144_wideband_ping; the defaults of msk144_wideband_pings_params
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmsk144hip.so")
@@ -43,6 +44,19 @@ class WidebandBlanker(C.Structure):
     """msk144_wideband_blanker; BLANKER_DEFAULTS holds the defaults of include/msk144hip.h."""
     _fields_ = [("threshold_q4", C.c_int32), ("pre", C.c_int32), ("post", C.c_int32)]
 
+
+class WidebandPing(C.Structure):
+    """msk144_wideband_ping; wideband.PING_DTYPE is the same record for numpy."""
+    _fields_ = [("up_mask", C.c_uint64), ("blocks", C.c_int32), ("history", C.c_int32), ("quiet", C.c_int32), ("reference", C.c_int32), ("peak", C.c_int32),
+                ("peak_block", C.c_int32)]
+
+
+class WidebandPingsParams(C.Structure):
+    """msk144_wideband_pings_params; PINGS_DEFAULTS holds the defaults of include/msk144hip.h."""
+    _fields_ = [("ratio_q4", C.c_int32), ("memory", C.c_int32), ("min_ref", C.c_int32)]
+
+
+assert C.sizeof(WidebandPing) == PING_DTYPE.itemsize == 32
 
 BLANKER_STATS = ("samples", "sum_power", "threshold", "hits", "blanked", "carry_out", "total_samples", "total_hits", "total_blanked")
 
@@ -116,6 +130,9 @@ PROTOTYPES = {
     "msk144_dump_wideband_blanked": ([_vp, _vp], C.c_int),
     "msk144_set_wideband_spectrum": ([_vp, _P(WidebandSpectrum)], C.c_int),
     "msk144_wideband_spectrum": ([_vp, _P(C.c_double), _P(C.c_int64)], C.c_int),
+    "msk144_set_wideband_pings": ([_vp, _P(WidebandPingsParams)], C.c_int),
+    "msk144_wideband_pings": ([_vp, _P(WidebandPing)], C.c_int),
+    "msk144_wideband_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -479,6 +496,33 @@ class HipDecoder:
         seg = C.c_int64()
         self._chk(self.L.msk144_wideband_spectrum(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(seg)))
         return out, int(seg.value)
+
+    def set_wideband_pings(self, params=True, **kw):
+        """The ping detector from the next push on (include/msk144hip.h): set_wideband_pings() takes the defaults (PINGS_DEFAULTS),
+        keywords replace single ones (ratio_q4, memory, min_ref); set_wideband_pings(None) switches it off."""
+        if params is None:
+            self._chk(self.L.msk144_set_wideband_pings(self.h, None))
+            return
+        p = dict(PINGS_DEFAULTS)
+        if isinstance(params, dict):
+            p.update(params)
+        p.update(kw)
+        a = WidebandPingsParams(**{k: int(v) for k, v in p.items()})
+        self._chk(self.L.msk144_set_wideband_pings(self.h, C.byref(a)))
+
+    def wideband_pings(self) -> np.ndarray:
+        """PING_DTYPE [channels]: up mask, blocks, history, quiet level, reference, peak and peak block of the last push."""
+        out = np.zeros(self.channels, dtype=PING_DTYPE)
+        self._chk(self.L.msk144_wideband_pings(self.h, out.ctypes.data_as(C.POINTER(WidebandPing))))
+        return out
+
+    def wideband_ping_blocks(self, channel: Optional[int] = None) -> np.ndarray:
+        """int32 [nb] block energies of the channel's last push (nb = 54 after a first push, else 27); channel None: every channel's,
+        int32 [channels][nb]."""
+        out = np.zeros((self.channels if channel is None else 1, PING_MAX_BLOCKS), dtype=np.int32)
+        n = C.c_int32()
+        self._chk(self.L.msk144_wideband_ping_blocks(self.h, -1 if channel is None else int(channel), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return out[:, :n.value].copy() if channel is None else out[0, :n.value].copy()
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

@@ -1,4 +1,5 @@
 // C entry points of the GPU-independent host logic, for the CPU test-suite (libmsk144host.so).
+#include "wideband_cli.h"
 #include "window_decoder.h"
 
 #include "../csrc/msk144_tables.h"
@@ -88,6 +89,90 @@ int msk144host_wideband_spectrum_window(int B, double* out)
     const std::vector<double> w = msk144wb::spectrum_window(B);
     if(out) std::memcpy(out, w.data(), sizeof(double) * w.size());
     return B;
+}
+
+// ---- ping detection (csrc/wideband.h: the rule the device runs, and the event tracker the program runs) ----
+
+namespace
+{
+int copy_why(const std::string& s, char* why, int why_len)
+{
+    if(why && why_len > 0)
+    {
+        std::strncpy(why, s.c_str(), static_cast<size_t>(why_len) - 1);
+        why[why_len - 1] = 0;
+    }
+    return s.empty() ? 0 : -1;
+}
+
+struct PingModel
+{
+    msk144wb::PingParams p;
+    std::vector<msk144wb::PingHistory> state;
+};
+}  // namespace
+
+// p = {ratio_q4, memory, min_ref}: 0 when msk144_set_wideband_pings takes them, else -1 with the refusal text in why
+int msk144host_wideband_ping_check(const int32_t* p, char* why, int why_len) { return copy_why(msk144wb::check_pings(msk144wb::PingParams{p[0], p[1], p[2]}), why, why_len); }
+int msk144host_wideband_ping_rank(int nb) { return msk144wb::ping_rank(nb); }
+int msk144host_wideband_ping_up(int32_t E, int32_t R, int32_t ratio_q4) { return msk144wb::ping_up(E, R, ratio_q4) ? 1 : 0; }
+
+// the detector of `channels` channels with their histories (NULL for parameters the library refuses) ...
+void* msk144host_wideband_ping_new(int channels, const int32_t* p)
+{
+    const msk144wb::PingParams pp{p[0], p[1], p[2]};
+    if(channels < 1 || !msk144wb::check_pings(pp).empty()) return nullptr;
+    return new PingModel{pp, std::vector<msk144wb::PingHistory>(static_cast<size_t>(channels))};
+}
+void msk144host_wideband_ping_free(void* m) { delete static_cast<PingModel*>(m); }
+// ... and one push of it: energies[channels][54] with nb blocks each, scales[channels], restart as the library passes it (a first
+// push, or the first push after `set`); out[channels] msk144_wideband_ping records
+void msk144host_wideband_ping_push(void* m, int restart, const float* scales, const int32_t* energies, int nb, msk144wb::PingRecord* out)
+{
+    PingModel& pm = *static_cast<PingModel*>(m);
+    for(size_t c = 0; c < pm.state.size(); c++) out[c] = msk144wb::ping_record(pm.p, pm.state[c], restart != 0, scales[c], energies + c * msk144wb::kPingMaxBlocks, nb);
+}
+
+// the event tracker: push and close write at most cap events {channel, start, blocks, peak, reference} and return their number
+void* msk144host_wideband_ping_tracker_new(int channels, int min_blocks)
+{
+    if(channels < 1 || min_blocks < 1 || min_blocks > msk144wb::kPingMaxMinBlocks) return nullptr;
+    return new msk144wb::PingTracker(channels, min_blocks);
+}
+void msk144host_wideband_ping_tracker_free(void* t) { delete static_cast<msk144wb::PingTracker*>(t); }
+int msk144host_wideband_ping_tracker_push(void* t, const msk144wb::PingRecord* records, const int32_t* energies, msk144wb::PingEvent* out, int cap)
+{
+    std::vector<msk144wb::PingEvent> ev;
+    static_cast<msk144wb::PingTracker*>(t)->push(records, energies, ev);
+    for(int i = 0; i < static_cast<int>(ev.size()) && i < cap; i++) out[i] = ev[static_cast<size_t>(i)];
+    return static_cast<int>(ev.size());
+}
+int msk144host_wideband_ping_tracker_close(void* t, msk144wb::PingEvent* out, int cap)
+{
+    std::vector<msk144wb::PingEvent> ev;
+    static_cast<msk144wb::PingTracker*>(t)->close(ev);
+    for(int i = 0; i < static_cast<int>(ev.size()) && i < cap; i++) out[i] = ev[static_cast<size_t>(i)];
+    return static_cast<int>(ev.size());
+}
+// {events, up blocks, total blocks} of the tracker so far
+void msk144host_wideband_ping_tracker_counts(void* t, int64_t* out3)
+{
+    const msk144wb::PingTracker& tr = *static_cast<msk144wb::PingTracker*>(t);
+    out3[0] = tr.events(), out3[1] = tr.up_blocks(), out3[2] = tr.total_blocks();
+}
+// the event's line of the log (--wideband-pings=FILE), NUL-terminated in out
+void msk144host_wideband_ping_line(const msk144wb::PingEvent* e, int32_t offset_hz, char* out, int cap)
+{
+    std::strncpy(out, msk144wb::ping_event_line(*e, offset_hz).c_str(), static_cast<size_t>(cap) - 1);
+    out[cap - 1] = 0;
+}
+// "FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]" as the program parses it: 0 and out4 = {ratio_q4, min_blocks, memory, length of FILE}, else -1
+int msk144host_wideband_pings_parse(const char* arg, int32_t* out4)
+{
+    WidebandOptions w;
+    if(!parse_wideband_pings(arg, w)) return -1;
+    out4[0] = w.ping_params.ratio_q4, out4[1] = w.ping_min_blocks, out4[2] = w.ping_params.memory, out4[3] = static_cast<int32_t>(w.pings_file.size());
+    return 0;
 }
 
 void* msk144host_table_new(){ return new CallHashTable(); }

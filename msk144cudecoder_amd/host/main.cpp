@@ -73,6 +73,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-levels           With --wideband-rate: at the end, on stderr, one line per channel - rms level in LSB over the run, clipped components, last gain, lowest and highest AGC step - and the three most clipped and three quietest channels." << std::endl;
     std::cout << "                   --wideband-blanker[=RATIO[:PRE[:POST]]]  With --wideband-rate: impulse-noise blanker on the input stream, on the GPU, ahead of the channel filters: a sample whose power exceeds RATIO x the mean power of its hop is zeroed together with PRE samples before and POST after it (0..4096 each). RATIO 1..4095.9, default=16; PRE default=2, POST default=8. At the end, on stderr, one line with the hits and the blanked samples." << std::endl;
     std::cout << "                   --wideband-spectrum=FILE[:BINS[:HOPS]]  With --wideband-rate: the power spectrum of the input stream at the input rate, on the GPU (of the blanked stream with --wideband-blanker): BINS-point transforms (a power of two, 256..8192, default=1024) of the hop's samples under a Hann window, summed over HOPS hops (default=5), appended to FILE as one line 'hop= rate= bins= segments= dbfs=v0,v1,...' in ascending frequency, 0 dBFS = a full-scale tone. At the end, on stderr, one line with the median bin (the floor) and the highest bin." << std::endl;
+    std::cout << "                   --wideband-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]  With --wideband-rate: ping detection per channel, on the GPU, on each channel's int8 I/Q: the energy of every 8 ms block (96 samples) is compared with RATIO x the channel's quiet level (the lower quartile of a hop's blocks, the lowest of this hop and the MEMORY hops before it, 0..16; default=8). RATIO 1..4095.9, default=2. A run of at least MIN_BLOCKS (1..64, default=2) consecutive blocks above it is an event, appended to FILE when it ends as one line 'ping ch= offset= start= dur= blocks= peak= ref= peak_db='. A strong-ping detector (from about +7 dB in 2500 Hz), less sensitive than the decoder. At the end, on stderr, one line with the events and the most active channels." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -187,6 +188,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-levels", no_argument, 0, 0},
                                            {"wideband-blanker", optional_argument, 0, 0},
                                            {"wideband-spectrum", required_argument, 0, 0},
+                                           {"wideband-pings", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -238,6 +240,7 @@ int main(int argc, char* const argv[])
         case 28:
         case 29:
         case 30:
+        case 31:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -250,6 +253,7 @@ int main(int argc, char* const argv[])
             else if(idx == 28) wbo.levels = true;
             else if(idx == 29) good = parse_wideband_blanker(optarg, wbo);
             else if(idx == 30) good = parse_wideband_spectrum(optarg, wbo);
+            else if(idx == 31) good = parse_wideband_pings(optarg, wbo);
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
@@ -305,7 +309,7 @@ int main(int argc, char* const argv[])
     {
         std::string err;
         if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
-           (wbo.spectrum && !wb_api.load_spectrum(err)))
+           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
@@ -316,6 +320,13 @@ int main(int argc, char* const argv[])
     if(wbo.spectrum && !(spectrum_file = fopen(wbo.spectrum_file.c_str(), "a")))
     {
         std::cerr << "--wideband-spectrum: cannot open '" << wbo.spectrum_file << "': " << strerror(errno) << std::endl;
+        return 2;
+    }
+    // --wideband-pings: likewise
+    FILE* pings_file = nullptr;
+    if(wbo.pings && !(pings_file = fopen(wbo.pings_file.c_str(), "a")))
+    {
+        std::cerr << "--wideband-pings: cannot open '" << wbo.pings_file << "': " << strerror(errno) << std::endl;
         return 2;
     }
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
@@ -462,6 +473,15 @@ int main(int argc, char* const argv[])
                 return 2;
             }
         }
+        if(wbo.pings)
+        {
+            const msk144_wideband_pings_params pp{wbo.ping_params.ratio_q4, wbo.ping_params.memory, wbo.ping_params.min_ref};
+            if(wb_api.set_pings(dec.handle(), &pp) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
         if(wbo.blanker)
         {
             const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
@@ -544,6 +564,7 @@ int main(int argc, char* const argv[])
     for(size_t i = 0; i < loops.size(); i++)
     {
         if(wbo.spectrum) loops[i]->use_wideband_spectrum(spectrum_file, wbo.spectrum_bins, wbo.spectrum_hops, wbo.rate_hz);
+        if(wbo.pings) loops[i]->use_wideband_pings(pings_file, wbo.ping_min_blocks, wbo.offsets);
         if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
@@ -659,6 +680,28 @@ int main(int argc, char* const argv[])
                 fprintf(stderr, "msk144hipdecoder: wideband spectrum: %d bins of %.1f Hz over %lld segments, floor (median bin) %.2f dBFS, highest bin %.2f dBFS at %+.0f Hz\n",
                         wbo.spectrum_bins, static_cast<double>(wbo.rate_hz) / wbo.spectrum_bins, sm.segments, sm.median_dbfs, sm.peak_dbfs, sm.peak_hz);
         }
+        if(wbo.pings)
+        {
+            const msk144wb::PingTracker& tr = loops[0]->wideband_ping_tracker();
+            const std::vector<int64_t>& ev = tr.channel_events();
+            const std::vector<int64_t>& up = tr.channel_up_blocks();
+            std::vector<int> active;
+            for(int c = 0; c < static_cast<int>(ev.size()); c++)
+                if(ev[static_cast<size_t>(c)]) active.push_back(c);
+            const int with_events = static_cast<int>(active.size());
+            std::stable_sort(active.begin(), active.end(), [&](int a, int b) {
+                return ev[static_cast<size_t>(a)] != ev[static_cast<size_t>(b)] ? ev[static_cast<size_t>(a)] > ev[static_cast<size_t>(b)] : up[static_cast<size_t>(a)] > up[static_cast<size_t>(b)];
+            });
+            std::string line = "msk144hipdecoder: wideband pings: " + std::to_string(tr.events()) + " events on " + std::to_string(with_events) + " of " + std::to_string(ev.size()) +
+                               " channels, " + std::to_string(tr.up_blocks()) + " of " + std::to_string(tr.total_blocks()) + " blocks up";
+            char buf[96];
+            for(size_t i = 0; i < 3 && i < active.size(); i++)
+            {
+                snprintf(buf, sizeof(buf), "%s ch=%d (%lld)", i ? "" : "; most active", active[i], static_cast<long long>(ev[static_cast<size_t>(active[i])]));
+                line += buf;
+            }
+            std::cerr << line << std::endl;
+        }
         if(wbo.levels)
         {
             const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();
@@ -714,6 +757,7 @@ int main(int argc, char* const argv[])
         }
     }
     if(spectrum_file) fclose(spectrum_file);
+    if(pings_file) fclose(pings_file);
     std::cout << "Done" << std::endl;
     return 0;
 }

@@ -211,10 +211,16 @@ int DeviceLoop::join()
         if(wb_->clip(dec_.handle(), &clipped) == MSK144_OK) wb_clipped_ += clipped;
         if(wb_read_levels_) read_wideband_levels();
         if(wb_spec_file_) read_wideband_spectrum();
+        if(wb_ping_file_) read_wideband_pings();
         wb_components_ += wb_pending_components_;
         wb_pending_components_ = 0;
     }
     if(wb_spec_file_ && wb_spec_group_pushes_) write_spectrum_line();  // the last, shorter group
+    if(wb_ping_file_)
+    {
+        wb_ping_tracker_->close(wb_ping_events_);  // the end of the stream closes every open run
+        write_ping_events();
+    }
     return failed ? 2 : 0;
 }
 
@@ -240,7 +246,7 @@ bool DeviceLoop::submit_wideband(Batch& b)
         }
         wb_clipped_ += clipped;
         wb_components_ += wb_pending_components_;
-        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()))
+        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ && !read_wideband_pings()))
         {
             fail(msk144_last_error(dec_.handle()));
             return false;
@@ -288,6 +294,33 @@ bool DeviceLoop::read_wideband_levels()
         a.max_exp = fresh ? v.exponent : std::max(a.max_exp, static_cast<int>(v.exponent));
     }
     return true;
+}
+
+void DeviceLoop::use_wideband_pings(FILE* file, int min_blocks, const std::vector<int32_t>& offsets)
+{
+    wb_ping_file_ = file;
+    wb_ping_offsets_ = offsets;
+    wb_ping_tracker_.reset(new msk144wb::PingTracker(static_cast<int>(offsets.size()), min_blocks));
+    wb_ping_buf_.resize(offsets.size());
+    wb_ping_energies_.resize(offsets.size() * msk144wb::kPingMaxBlocks);
+}
+
+// --wideband-pings: the records and block energies of the push just made (read where its clip count is read) to the event tracker
+bool DeviceLoop::read_wideband_pings()
+{
+    static_assert(sizeof(msk144_wideband_ping) == sizeof(msk144wb::PingRecord), "the tracker reads msk144_wideband_ping");
+    int32_t nb = 0;
+    if(wb_->pings(dec_.handle(), wb_ping_buf_.data()) != MSK144_OK || wb_->ping_blocks(dec_.handle(), -1, wb_ping_energies_.data(), &nb) != MSK144_OK) return false;
+    wb_ping_tracker_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_ping_energies_.data(), wb_ping_events_);
+    write_ping_events();
+    return true;
+}
+
+void DeviceLoop::write_ping_events()
+{
+    for(const msk144wb::PingEvent& e : wb_ping_events_) fprintf(wb_ping_file_, "%s\n", msk144wb::ping_event_line(e, wb_ping_offsets_[static_cast<size_t>(e.channel)]).c_str());
+    if(!wb_ping_events_.empty()) fflush(wb_ping_file_);
+    wb_ping_events_.clear();
 }
 
 void DeviceLoop::use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz)

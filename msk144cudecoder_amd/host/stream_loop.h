@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -108,6 +109,11 @@ public:
     // 0 dBFS = a full-scale tone on a bin centre (include/msk144hip.h), floored at -200
     void use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz);
     // over the run: the median bin (the floor) and the highest bin with its frequency from the centre; segments 0: no push was read
+    // --wideband-pings: msk144_wideband_pings and the block energies are read once per push, where its clip count is read; every
+    // event that closes (csrc/wideband.h PingTracker) is appended to `file` as one line and flushed, the open ones when the stream ends
+    void use_wideband_pings(FILE* file, int min_blocks, const std::vector<int32_t>& offsets);
+    const msk144wb::PingTracker& wideband_ping_tracker() const { return *wb_ping_tracker_; }
+
     struct SpectrumSummary
     {
         long long segments = 0;
@@ -181,6 +187,8 @@ private:
     bool submit_wideband(Batch& b);
     bool read_wideband_levels();
     bool read_wideband_spectrum();
+    bool read_wideband_pings();
+    void write_ping_events();
     void write_spectrum_line();
 
     WindowDecoder dec_;
@@ -201,6 +209,11 @@ private:
     long long wb_spec_rate_ = 0, wb_spec_pushes_ = 0;  // pushes read so far
     double wb_spec_full_ = 0.0;                        // (sum w)^2 of the default window
     std::vector<double> wb_spec_buf_, wb_spec_group_, wb_spec_run_;  // the last push, the open group, the run
+    FILE* wb_ping_file_ = nullptr;
+    std::unique_ptr<msk144wb::PingTracker> wb_ping_tracker_;
+    std::vector<int32_t> wb_ping_offsets_, wb_ping_energies_;
+    std::vector<msk144_wideband_ping> wb_ping_buf_;
+    std::vector<msk144wb::PingEvent> wb_ping_events_;
     long long wb_spec_group_segments_ = 0, wb_spec_group_pushes_ = 0, wb_spec_run_segments_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;

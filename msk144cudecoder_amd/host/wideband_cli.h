@@ -65,6 +65,22 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-pings: resolved only when it is given (load_pings)
+    int (*set_pings)(msk144_handle*, const msk144_wideband_pings_params*) = nullptr;
+    int (*pings)(msk144_handle*, msk144_wideband_ping*) = nullptr;
+    int (*ping_blocks)(msk144_handle*, int32_t, int32_t*, int32_t*) = nullptr;
+
+    bool load_pings(std::string& err)
+    {
+        set_pings = reinterpret_cast<decltype(set_pings)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_pings"));
+        pings = reinterpret_cast<decltype(pings)>(dlsym(RTLD_DEFAULT, "msk144_wideband_pings"));
+        ping_blocks = reinterpret_cast<decltype(ping_blocks)>(dlsym(RTLD_DEFAULT, "msk144_wideband_ping_blocks"));
+        if(set_pings && pings && ping_blocks) return true;
+        err = std::string("the loaded libmsk144hip has no ping detector (") + (!set_pings ? "msk144_set_wideband_pings" : !pings ? "msk144_wideband_pings" : "msk144_wideband_ping_blocks") +
+              "): --wideband-pings needs it";
+        return false;
+    }
+
     bool load(std::string& err)
     {
         set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
@@ -91,6 +107,10 @@ struct WidebandOptions
     std::string spectrum_file;
     int spectrum_bins = msk144wb::kSpectrumDefaultBins;
     int spectrum_hops = 5;
+    bool pings = false;    // --wideband-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]: the ping detector, one line per closed event appended to FILE
+    std::string pings_file;
+    msk144wb::PingParams ping_params;
+    int ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -176,6 +196,45 @@ inline bool parse_wideband_spectrum(const std::string& s, WidebandOptions& w)
     return true;
 }
 
+// "FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]": RATIO a decimal ratio to the reference, kept as rint(16 x RATIO) within 16..65535;
+// MIN_BLOCKS 1..64 blocks of 8 ms an event must have; MEMORY 0..16 earlier pushes
+inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
+{
+    w.pings = true;
+    w.ping_params = msk144wb::PingParams();
+    w.ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
+    std::vector<std::string> f;
+    size_t a = 0;
+    while(true)
+    {
+        const size_t b = s.find(':', a);
+        f.push_back(s.substr(a, b == std::string::npos ? b : b - a));
+        if(b == std::string::npos) break;
+        a = b + 1;
+    }
+    w.pings_file = f[0];
+    if(f[0].empty() || f.size() > 4) return false;
+    long long v = 0;
+    if(f.size() > 1)
+    {
+        char* end = nullptr;
+        const double r = std::strtod(f[1].c_str(), &end);
+        if(f[1].empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
+        w.ping_params.ratio_q4 = static_cast<int32_t>(std::lrint(16.0 * r));
+    }
+    if(f.size() > 2)
+    {
+        if(!parse_int(f[2], v) || v < 1 || v > msk144wb::kPingMaxMinBlocks) return false;
+        w.ping_min_blocks = static_cast<int>(v);
+    }
+    if(f.size() > 3)
+    {
+        if(!parse_int(f[3], v) || v < INT32_MIN || v > INT32_MAX) return false;
+        w.ping_params.memory = static_cast<int32_t>(v);
+    }
+    return msk144wb::check_pings(w.ping_params).empty();
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -225,6 +284,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     if(!w.parse_error.empty()) return w.parse_error;
     if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
+    if(w.rate_hz <= 0 && w.pings) return "--wideband-pings needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";

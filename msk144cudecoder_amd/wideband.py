@@ -360,6 +360,139 @@ class Spectrum:
         return np.fft.fftshift(np.sum(X.real ** 2 + X.imag ** 2, axis=0)), S
 
 
+# ---- per-channel ping detection (msk144_set_wideband_pings) ----
+
+# msk144_wideband_ping (include/msk144hip.h); HipDecoder.wideband_pings() returns the same records
+PING_DTYPE = np.dtype([("up_mask", "<u8"), ("blocks", "<i4"), ("history", "<i4"), ("quiet", "<i4"), ("reference", "<i4"), ("peak", "<i4"), ("peak_block", "<i4")])
+assert PING_DTYPE.itemsize == 32
+PING_BLOCK = 96           # samples per block: 8 ms
+PING_MAX_BLOCKS = 54      # blocks of a first push; a later push has 27
+PING_MAX_MEMORY = 16
+# the defaults of msk144_wideband_pings_params (csrc/wideband.h PingParams): design parameters, not measurements
+PINGS_DEFAULTS = dict(ratio_q4=32, memory=8, min_ref=96)
+PING_MIN_BLOCKS = 2       # the event rule's default
+
+
+def ping_blocks(q) -> np.ndarray:
+    """int64 [channel][nb]: E[b] = the sum of I*I + Q*Q over samples 96b .. 96b+95 of the int8 hops q [channel][M][2]."""
+    q = np.asarray(q)
+    C_, M = q.shape[0], q.shape[1]
+    if M % PING_BLOCK or q.shape[2:] != (2,):
+        raise ValueError("hops must be [channel][M][2] with M a multiple of 96")
+    return np.sum(q.astype(np.int64).reshape(C_, M // PING_BLOCK, 2 * PING_BLOCK) ** 2, axis=2)
+
+
+class Pings:
+    """The ping detector of the contract (include/msk144hip.h) in Python integers, push by push: per channel the quiet levels of the
+    pushes since its history last restarted, and the scale of its last push.  reset() stands for a first push and for
+    msk144_set_wideband_pings: the next push restarts every history.  `energies` holds the last push's E, int64 [channel][nb]."""
+
+    def __init__(self, channels: int, **params):
+        p = dict(PINGS_DEFAULTS)
+        unknown = set(params) - set(p)
+        if unknown:
+            raise TypeError(f"unknown ping parameters {sorted(unknown)}")
+        p.update({k: int(v) for k, v in params.items()})
+        if not 16 <= p["ratio_q4"] <= 65535:
+            raise ValueError("ratio_q4 must lie within 16..65535")
+        if not 0 <= p["memory"] <= PING_MAX_MEMORY:
+            raise ValueError("memory must lie within 0..16 pushes")
+        if not 1 <= p["min_ref"] <= 1 << 22:
+            raise ValueError("min_ref must lie within 1..2^22")
+        self.p, self.channels = p, int(channels)
+        self.energies = None
+        self.reset()
+
+    def reset(self):
+        self.quiet = [[] for _ in range(self.channels)]   # the q of the pushes since the restart, oldest first
+        self.scale = [None] * self.channels
+
+    def push(self, q, scales) -> np.ndarray:
+        """PING_DTYPE [channel] from the int8 hops q [channel][M][2] of one push and the f32 scale each channel was quantised with
+        (wideband_levels()["gain"]); a scale other than the channel's last restarts its history."""
+        E = ping_blocks(q)
+        if E.shape[0] != self.channels:
+            raise ValueError(f"{self.channels} channels, got {E.shape[0]}")
+        sc = np.broadcast_to(np.asarray(scales, dtype=np.float32), (self.channels,))
+        nb = E.shape[1]
+        out = np.zeros(self.channels, dtype=PING_DTYPE)
+        for c in range(self.channels):
+            e = [int(v) for v in E[c]]
+            if self.scale[c] is None or self.scale[c] != sc[c]:
+                self.quiet[c] = []
+            self.scale[c] = sc[c]
+            quiet = sorted(e)[nb // 4]
+            h = min(self.p["memory"], len(self.quiet[c]))
+            R = max(min([quiet] + self.quiet[c][len(self.quiet[c]) - h:]), self.p["min_ref"])
+            self.quiet[c] = (self.quiet[c] + [quiet])[-PING_MAX_MEMORY:]
+            mask = 0
+            for b in range(nb):
+                if e[b] * 16 > R * self.p["ratio_q4"]:
+                    mask |= 1 << b
+            peak = max(e)
+            out[c] = (mask, nb, h, quiet, R, peak, e.index(peak))
+        self.energies = E
+        return out
+
+
+class PingEvents:
+    """The event rule of the contract: with g = (blocks of all earlier pushes) + b an event is a maximal run of consecutive up blocks
+    of a channel.  A run that reaches a push's last block stays open into the next push; close() - the end of the stream - closes
+    every open run.  An event is reported when it closes, if it has at least min_blocks blocks, as a dict with channel, start and
+    blocks (in blocks of 8 ms), peak (the largest E of the run, at its lowest g on a tie) and reference (the R of the push that block
+    lay in): by push, then by channel, then by start."""
+
+    def __init__(self, min_blocks: int = PING_MIN_BLOCKS):
+        if not 1 <= int(min_blocks) <= 64:
+            raise ValueError("min_blocks must lie within 1..64")
+        self.min_blocks = int(min_blocks)
+        self.base = 0
+        self.open = {}
+        self.up_blocks = self.total_blocks = 0
+
+    def _finish(self, c, out):
+        run = self.open.pop(c, None)
+        if run is not None and run["blocks"] >= self.min_blocks:
+            out.append(run)
+
+    def push(self, records, energies) -> list:
+        """records: PING_DTYPE [channel] of one push; energies: its E [channel][nb] (Pings.energies, or
+        HipDecoder.wideband_ping_blocks()).  Returns the events that closed in this push."""
+        out = []
+        nb = 0
+        for c in range(len(records)):
+            mask, nb, R = int(records["up_mask"][c]), int(records["blocks"][c]), int(records["reference"][c])
+            for b in range(nb):
+                if (mask >> b) & 1:
+                    e = int(energies[c][b])
+                    run = self.open.get(c)
+                    if run is None:
+                        self.open[c] = dict(channel=c, start=self.base + b, blocks=1, peak=e, reference=R)
+                    else:
+                        run["blocks"] += 1
+                        if e > run["peak"]:
+                            run["peak"], run["reference"] = e, R
+                    self.up_blocks += 1
+                else:
+                    self._finish(c, out)
+            self.total_blocks += nb
+        self.base += nb
+        return out
+
+    def close(self) -> list:
+        out = []
+        for c in sorted(self.open):
+            self._finish(c, out)
+        return out
+
+
+def ping_event_line(event: dict, offset_hz: int) -> str:
+    """One line of the event log of msk144hipdecoder --wideband-pings=FILE; start and dur are block counts x 0.008 s."""
+    s, d = event["start"] * 8, event["blocks"] * 8
+    return (f"ping ch={event['channel']} offset={int(offset_hz)} start={s // 1000}.{s % 1000:03d} dur={d // 1000}.{d % 1000:03d} blocks={event['blocks']} "
+            f"peak={event['peak']} ref={event['reference']} peak_db={10.0 * math.log10(event['peak'] / event['reference']):.1f}")
+
+
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 
