@@ -41,6 +41,9 @@
  *   msk144_dump_wideband_blanked
  *   msk144_set_wideband_spectrum, the spectrum display every SDR front end has: the power spectrum of each push's input samples at
  *   msk144_wideband_spectrum the input rate, on the device (no reference counterpart)
+ *   msk144_set_wideband_waterfall, the fast graph every MSK144 operator knows, for every channel at once: a 96-point spectrum per
+ *   msk144_wideband_waterfall, 8 ms block of each channel's int8 hop, on the device (no reference counterpart)
+ *   msk144_wideband_waterfall_sums
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -602,6 +605,55 @@ int msk144_wideband_pings(msk144_handle* h, msk144_wideband_ping* out);
 /* test and debug, like msk144_dump_wideband_hop: E of the channel's last push in energies[0 .. *n), energies[54]; the rest is 0.
  * channel = -1: every channel's, energies[channels][54] (what the program's event log reads, in one copy) */
 int msk144_wideband_ping_blocks(msk144_handle* h, int32_t channel, int32_t* energies, int32_t* n);
+
+/* ---- Per-channel waterfall (no reference counterpart) ----
+ *
+ * Levels, the input spectrum and the ping detector do not show what is inside a 12 kHz channel: where in the channel a ping sat,
+ * whether a steady carrier sits in the passband, what a ping looked like in time x frequency.  At bank rates a bin of the input
+ * spectrum is wider than that.  Every channel's int8 hop sits on the device behind the channeliser, so the short-time spectra of
+ * all channels are one more read of the staged hops and one small transform per 8 ms block.  The waterfall only reads the hops: it is
+ * a display and a per-event frequency estimate at 125 Hz resolution from 8 ms blocks, and does not feed the decoder.
+ *
+ *   Input:      the int8 I/Q values of the channel's push exactly as stored, what msk144_dump_wideband_hop returns, taken as
+ *               integers x = I + jQ in LSB: M = 5184 after a first push, else 2592.
+ *   Rows:       one row per block of the ping detector: B = 96 samples, nb = M / 96 = 54 or 27, row b covers samples 96b .. 96b + 95
+ *               (block b of msk144_wideband_ping is row b).  Nothing is carried from push to push: a push's rows are a pure
+ *               function of its hops.
+ *   Output:     X_b[k] = sum_{i<96} w[i] x[96b + i] e^{-j 2 pi i k / 96},  P_b[k] = |X_b[k]|^2, in ascending frequency: rows[b][j] is
+ *               bin k = (j - 48) mod 96, at (j - 48) x 125 Hz from the channel's offset.
+ *   Window:     w[0..96) real and finite; NULL selects the periodic Hann window 0.5 - 0.5 cos(2 pi i / 96)
+ *               (msk144host_wideband_waterfall_window).  Formed in double, stored f32, as the spectrum's window and the taps are.
+ *   Scale:      a tone of amplitude A LSB on a bin centre reads (A sum w)^2; the program's 0 dB is A = 1:
+ *               dB = 10 log10(max(P / (sum w)^2, 1e-10)), the sum taken over the f32 window.
+ *   Sums:       sums[c][j] = sum_b (double) rows[c][b][j] over the f32 values actually stored, b ascending, added one after another
+ *               in double.
+ *   Arithmetic: the transform and |X|^2 in f32; no atomics and a fixed order everywhere: the same stream pushed twice gives the
+ *               same bytes in rows and sums.
+ *   Error:      per row, against the exact P_b of the f32 window and the integer samples, with T_b = sum_k P_b[k]:
+ *                   |rows[b][j] - P_b[k]| <= 2 u sqrt(P_b[k] T_b) + u^2 T_b + v P_b[k],   v = 4 x 2^-24 (the rounding of re^2 + im^2),
+ *               u = MSK144_WATERFALL_U: 4 x the largest value any row needed on an MI355X against a float64 model over 1 .. 130
+ *               channels, cu8 and cs16, the Hann, an all-ones and a random window, silence and all-clipped hops (6.9e-7),
+ *               rounded up to one significant digit; below the worst case of a 96-term f32 sum with rounded twiddles and window,
+ *               98 x 2^-24 = 5.8e-6.
+ *   Order:      msk144_set_wideband_waterfall(h, &p) takes effect from the next push and allocates everything a push needs - a push
+ *               allocates nothing; (h, NULL) switches it off, as msk144_set_wideband does.  The read entries report the last push and
+ *               synchronise like msk144_wideband_levels.  Whether the waterfall is on or off, every hop, clip count, level, AGC
+ *               step, blanker statistic, spectrum, ping record and decode is byte for byte the same.
+ *   Refused:    MSK144_EINVAL outside wideband mode, for a window value that is not finite and for a channel outside
+ *               -1 .. channels - 1; MSK144_ESTATE from the read entries before a push made with the waterfall on. */
+#define MSK144_WATERFALL_BINS 96
+#define MSK144_WATERFALL_U 3e-6 /* largest needed: 6.9e-7 */
+typedef struct msk144_wideband_waterfall_params
+{
+    const double* window; /* [96], or NULL: periodic Hann */
+} msk144_wideband_waterfall_params;
+
+/* NULL: off */
+int msk144_set_wideband_waterfall(msk144_handle* h, const msk144_wideband_waterfall_params* p);
+/* rows[54][96] of the channel's last push, *n = nb of them, the rows past *n are 0; channel = -1: every channel's, rows[channels][54][96] */
+int msk144_wideband_waterfall(msk144_handle* h, int32_t channel, float* rows, int32_t* n);
+/* sums[channels][96] of the last push */
+int msk144_wideband_waterfall_sums(msk144_handle* h, double* sums);
 
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */

@@ -31,6 +31,7 @@ SOURCES = [
     ("blanker.hip", []),
     ("spectrum.hip", []),
     ("pings.hip", []),
+    ("waterfall.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]

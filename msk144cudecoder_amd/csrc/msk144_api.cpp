@@ -173,6 +173,12 @@ struct msk144_handle
         msk144wb::PingHistory* d_ping_state = nullptr;   // [channels]
         msk144wb::PingRecord* d_ping_records = nullptr;  // [channels]
         int32_t* d_ping_energies = nullptr;              // [channels][54]
+        // per-channel waterfall (msk144_set_wideband_waterfall): applies from the next push; `set` allocates.  waterfall_pushed: the
+        // last push left rows and sums
+        bool waterfall = false, waterfall_pushed = false;
+        float2* d_wf_dft = nullptr;   // [3][96][32] the windowed DFT matrix in the kernel's order
+        float* d_wf_rows = nullptr;   // [channels][54][96]
+        double* d_wf_sums = nullptr;  // [channels][96]
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -607,6 +613,17 @@ int wb_ping_ready(msk144_handle* h, const char* who)
     const auto& w = h->wb;
     if(!w.configured) return fail(h, MSK144_EINVAL, std::string(who) + " needs wideband mode (msk144_set_wideband)");
     if(!w.started || !w.ping_pushed) return fail(h, MSK144_ESTATE, w.started ? "the last wideband push was made without the ping detector" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MSK144_OK;
+}
+
+// the read entries of the waterfall: wideband mode, and the last push made with the waterfall on; waits for that push
+int wb_waterfall_ready(msk144_handle* h, const char* who)
+{
+    const auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, std::string(who) + " needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !w.waterfall_pushed) return fail(h, MSK144_ESTATE, w.started ? "the last wideband push was made without the waterfall" : "no wideband push has been made");
     HIP_TRY(h, hipSetDevice(h->params.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MSK144_OK;
@@ -1507,6 +1524,9 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         w.ping_restart = false;
     }
     w.ping_pushed = w.pings;
+    if(w.waterfall)
+        launch_waterfall(reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), first ? 1 : 0, C, w.d_wf_dft, w.d_wf_rows, w.d_wf_sums, h->stream);
+    w.waterfall_pushed = w.waterfall;
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     w.push_gains = w.gains;
@@ -1756,6 +1776,72 @@ int msk144_wideband_ping_blocks(msk144_handle* h, int32_t channel, int32_t* ener
     if(channel < 0) HIP_TRY(h, hipMemcpy(energies, w.d_ping_energies, sizeof(int32_t) * row * w.gains.size(), hipMemcpyDeviceToHost));
     else HIP_TRY(h, hipMemcpy(energies, w.d_ping_energies + row * static_cast<size_t>(channel), sizeof(int32_t) * row, hipMemcpyDeviceToHost));
     *n = (w.last_first ? kWindowSamples : kHopSamples) / msk144wb::kPingBlock;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_waterfall(msk144_handle* h, const msk144_wideband_waterfall_params* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_waterfall");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(!p)
+    {
+        w.waterfall = false;
+        return MSK144_OK;
+    }
+    const std::string why = msk144wb::check_waterfall(p->window);
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    // never in a push
+    constexpr int B = msk144wb::kWaterfallBins;
+    const size_t C = w.gains.size();
+    if(!w.d_wf_dft && (rc = dev_alloc(h, w.mem, &w.d_wf_dft, kWaterfallDftSize)) != MSK144_OK) return rc;
+    if(!w.d_wf_rows && (rc = dev_alloc(h, w.mem, &w.d_wf_rows, C * msk144wb::kWaterfallRows * B)) != MSK144_OK) return rc;
+    if(!w.d_wf_sums && (rc = dev_alloc(h, w.mem, &w.d_wf_sums, C * B)) != MSK144_OK) return rc;
+    // the matrix: the window rounded to f32, times the twiddle in double, stored f32; slot j = 32 t + c is bin (j - 48) mod 96
+    const std::vector<double> hann = p->window ? std::vector<double>() : msk144wb::waterfall_window();
+    const double* win = p->window ? p->window : hann.data();
+    std::vector<float2> dft(kWaterfallDftSize);
+    for(int j = 0; j < B; j++)
+        for(int i = 0; i < B; i++)
+        {
+            const double wi = static_cast<double>(static_cast<float>(win[i]));
+            const double a = -2.0 * M_PI * static_cast<double>((i * ((j + B / 2) % B)) % B) / B;
+            dft[(static_cast<size_t>(j / 32) * B + static_cast<size_t>(i)) * 32 + static_cast<size_t>(j % 32)] =
+                make_float2(static_cast<float>(wi * std::cos(a)), static_cast<float>(wi * std::sin(a)));
+        }
+    HIP_TRY(h, hipMemcpy(w.d_wf_dft, dft.data(), sizeof(float2) * dft.size(), hipMemcpyHostToDevice));
+    w.waterfall = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_waterfall(msk144_handle* h, int32_t channel, float* rows, int32_t* n)
+{
+    if(!h || !rows || !n) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(w.configured && (channel < -1 || channel >= h->params.channels)) return fail(h, MSK144_EINVAL, "channel out of range");
+    const int rc = wb_waterfall_ready(h, "msk144_wideband_waterfall");
+    if(rc != MSK144_OK) return rc;
+    constexpr size_t B = msk144wb::kWaterfallBins, R = msk144wb::kWaterfallRows;
+    const size_t nb = static_cast<size_t>(w.last_first ? kWindowSamples : kHopSamples) / B;
+    const size_t count = channel < 0 ? w.gains.size() : 1;
+    // the device holds the rows of the push's blocks; what lies past them (an earlier first push's) is not part of this push
+    if(nb == R) HIP_TRY(h, hipMemcpy(rows, w.d_wf_rows + (channel < 0 ? 0 : R * B * static_cast<size_t>(channel)), sizeof(float) * R * B * count, hipMemcpyDeviceToHost));
+    else
+    {
+        HIP_TRY(h, hipMemcpy2D(rows, sizeof(float) * R * B, w.d_wf_rows + (channel < 0 ? 0 : R * B * static_cast<size_t>(channel)), sizeof(float) * R * B, sizeof(float) * nb * B, count,
+                               hipMemcpyDeviceToHost));
+        for(size_t c = 0; c < count; c++) std::fill(rows + (c * R + nb) * B, rows + (c + 1) * R * B, 0.0f);
+    }
+    *n = static_cast<int32_t>(nb);
+    return MSK144_OK;
+}
+
+int msk144_wideband_waterfall_sums(msk144_handle* h, double* sums)
+{
+    if(!h || !sums) return fail(h, MSK144_EINVAL, "null argument");
+    const int rc = wb_waterfall_ready(h, "msk144_wideband_waterfall_sums");
+    if(rc != MSK144_OK) return rc;
+    HIP_TRY(h, hipMemcpy(sums, h->wb.d_wf_sums, sizeof(double) * msk144wb::kWaterfallBins * h->wb.gains.size(), hipMemcpyDeviceToHost));
     return MSK144_OK;
 }
 

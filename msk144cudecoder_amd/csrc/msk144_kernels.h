@@ -121,6 +121,13 @@ void launch_agc_step(const unsigned long long* levels, const int32_t* slot_chann
 void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float* gains, const int32_t* used_exps, const msk144wb::PingParams& p,
                   int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, hipStream_t stream);
 
+// the per-channel waterfall of a push (waterfall.hip; contract in include/msk144hip.h), on the staged hops like launch_pings:
+// dft[t][i][c] = w[i] e^{-j2pi i k/96} of slot j = 32 t + c, k = (j - 48) mod 96, f32 (kWaterfallDftSize values).  Writes
+// rows[channels][54][96] - only the rows of the push's blocks, 27 or with first != 0 54 - and sums[channels][96], the sum of a
+// channel's rows in ascending block order in double.
+constexpr size_t kWaterfallDftSize = static_cast<size_t>(msk144wb::kWaterfallBins) * msk144wb::kWaterfallBins;
+void launch_waterfall(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float2* dft, float* rows, double* sums, hipStream_t stream);
+
 // what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
 // before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push
 struct BlankerCounters

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -454,6 +455,127 @@ inline std::string ping_event_line(const PingEvent& e, int32_t offset_hz)
     snprintf(buf, sizeof(buf), "ping ch=%d offset=%d start=%lld.%03lld dur=%lld.%03lld blocks=%lld peak=%d ref=%d peak_db=%.1f", e.channel, offset_hz, s / 1000, s % 1000,
              d / 1000, d % 1000, static_cast<long long>(e.blocks), e.peak, e.reference, 10.0 * std::log10(static_cast<double>(e.peak) / static_cast<double>(e.reference)));
     return buf;
+}
+
+// ---- per-channel waterfall (msk144_set_wideband_waterfall, msk144_wideband_waterfall, msk144_wideband_waterfall_sums) ----
+
+constexpr int kWaterfallBins = kPingBlock;   // one 96-point transform per block of the ping detector: 125 Hz per bin
+constexpr int kWaterfallRows = kPingMaxBlocks;
+constexpr double kWaterfallFloor = 1e-10;    // -100 dB under a tone of 1 LSB on a bin centre
+constexpr double kWaterfallCarrierDb = 10.0; // the summary's carrier rule; a design parameter, not a measurement
+constexpr int kWaterfallMaxListed = 16;      // channels of --wideband-waterfall=FILE:c0,c1,...
+constexpr int kWaterfallHandful = 4;         // up to this many channels are read one by one, more in one copy of all
+
+// the default window, periodic Hann: w[i] = 0.5 - 0.5 cos(2 pi i / 96)
+inline std::vector<double> waterfall_window()
+{
+    std::vector<double> w(static_cast<size_t>(kWaterfallBins));
+    for(int i = 0; i < kWaterfallBins; i++) w[static_cast<size_t>(i)] = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / kWaterfallBins);
+    return w;
+}
+
+// The rule of msk144_set_wideband_waterfall that needs no handle: every window value finite (NULL: the default).  Empty string = valid.
+inline std::string check_waterfall(const double* window)
+{
+    for(int i = 0; window && i < kWaterfallBins; i++)
+        if(!std::isfinite(window[i])) return "waterfall window value " + std::to_string(i) + " is not finite";
+    return std::string();
+}
+
+// 0 dB of the program's output: (sum w)^2 of the window the device holds, rounded to f32 (NULL: the default)
+inline double waterfall_full(const double* window)
+{
+    const std::vector<double> hann = window ? std::vector<double>() : waterfall_window();
+    const double* w = window ? window : hann.data();
+    double sum = 0.0;
+    for(int i = 0; i < kWaterfallBins; i++) sum += static_cast<double>(static_cast<float>(w[i]));
+    return sum * sum;
+}
+
+// 10 log10(max(P / (sum w)^2, floor)): 0 dB is a tone of 1 LSB on a bin centre, the floor -100 dB
+inline double waterfall_db(double power, double full)
+{
+    const double r = power / full;
+    return r > kWaterfallFloor ? 10.0 * std::log10(r) : 10.0 * std::log10(kWaterfallFloor);
+}
+
+// (j - 48) x 125 Hz: slot j of a row from the channel's offset
+inline int32_t waterfall_hz(int j) { return (j - kWaterfallBins / 2) * (12000 / kWaterfallBins); }
+
+// One line of the waterfall log (--wideband-waterfall=FILE): row `row`[96] of global block g, t = 0.008 g exact in three decimals,
+// two decimals per bin and no "-0.00"
+inline std::string waterfall_line(int32_t channel, int32_t offset_hz, int64_t g, const float* row, double full)
+{
+    char buf[128];
+    const long long ms = static_cast<long long>(g) * 8;
+    snprintf(buf, sizeof(buf), "wf ch=%d offset=%d block=%lld t=%lld.%03lld db=", channel, offset_hz, static_cast<long long>(g), ms / 1000, ms % 1000);
+    std::string line = buf;
+    for(int j = 0; j < kWaterfallBins; j++)
+    {
+        snprintf(buf, sizeof(buf), "%.2f", waterfall_db(static_cast<double>(row[j]), full));
+        if(j) line += ',';
+        line += std::strcmp(buf, "-0.00") ? buf : "0.00";
+    }
+    return line;
+}
+
+// The frequency of a ping event, once: one double accumulator [96] per channel.  Blocks are taken in stream order; a block that is
+// up adds its row, a block that is not up clears the accumulator, so that when PingTracker closes an event the accumulator holds
+// exactly that event's rows.  push and close append one frequency - (j* - 48) x 125 Hz, j* the lowest j at the maximum - per event
+// PingTracker reports from the same records (runs of at least min_blocks blocks), in its order.  Host only.
+class PingSpectra
+{
+public:
+    PingSpectra(int channels, int min_blocks) : min_blocks_(min_blocks), acc_(static_cast<size_t>(channels) * kWaterfallBins, 0.0), blocks_(static_cast<size_t>(channels), 0) {}
+
+    // records[channels] of one push and its rows [channels][54][96]; only the rows of up blocks are read
+    void push(const PingRecord* records, const float* rows, std::vector<int32_t>& out)
+    {
+        for(size_t c = 0; c < blocks_.size(); c++)
+        {
+            const PingRecord& r = records[c];
+            double* a = &acc_[c * kWaterfallBins];
+            for(int b = 0; b < r.blocks; b++)
+            {
+                if((r.up_mask >> b) & 1)
+                {
+                    const float* row = rows + (c * kWaterfallRows + static_cast<size_t>(b)) * kWaterfallBins;
+                    for(int j = 0; j < kWaterfallBins; j++) a[j] += static_cast<double>(row[j]);
+                    blocks_[c]++;
+                }
+                else finish(c, out);
+            }
+        }
+    }
+
+    void close(std::vector<int32_t>& out)
+    {
+        for(size_t c = 0; c < blocks_.size(); c++) finish(c, out);
+    }
+
+private:
+    void finish(size_t c, std::vector<int32_t>& out)
+    {
+        double* a = &acc_[c * kWaterfallBins];
+        if(blocks_[c] >= min_blocks_) out.push_back(waterfall_hz(static_cast<int>(std::max_element(a, a + kWaterfallBins) - a)));
+        if(blocks_[c]) std::fill(a, a + kWaterfallBins, 0.0);
+        blocks_[c] = 0;
+    }
+
+    int64_t min_blocks_;
+    std::vector<double> acc_;
+    std::vector<int64_t> blocks_;
+};
+
+// The summary's carrier rule on a channel's run-summed spectrum [96]: the excess in dB of its highest bin (the lowest j at the
+// maximum, in j_top) over its median bin (rank 48 in ascending order); 0 when the median bin is not positive
+inline double waterfall_excess_db(const double* sum, int& j_top)
+{
+    std::vector<double> sorted(sum, sum + kWaterfallBins);
+    std::nth_element(sorted.begin(), sorted.begin() + kWaterfallBins / 2, sorted.end());
+    j_top = static_cast<int>(std::max_element(sum, sum + kWaterfallBins) - sum);
+    const double median = sorted[kWaterfallBins / 2];
+    return median > 0.0 ? 10.0 * std::log10(sum[j_top] / median) : 0.0;
 }
 
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.

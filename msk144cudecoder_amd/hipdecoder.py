@@ -15,6 +15,7 @@ import numpy as np
 from .protocol import ITEM_BYTES
 from .wideband import AGC_DEFAULTS, BLANKER_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc and _blanker; msk144_wideband_level
 from .wideband import PING_DTYPE, PING_MAX_BLOCKS, PINGS_DEFAULTS    # msk144_wideband_ping; the defaults of msk144_wideband_pings_params
+from .wideband import WATERFALL_BINS, WATERFALL_ROWS                 # the shape of msk144_wideband_waterfall's rows
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmsk144hip.so")
@@ -38,6 +39,11 @@ class WidebandAgc(C.Structure):
 class WidebandSpectrum(C.Structure):
     """msk144_wideband_spectrum_params: bins and the window (NULL: periodic Hann)."""
     _fields_ = [("bins", C.c_int32), ("window", C.POINTER(C.c_double))]
+
+
+class WidebandWaterfall(C.Structure):
+    """msk144_wideband_waterfall_params: the window (NULL: periodic Hann)."""
+    _fields_ = [("window", C.POINTER(C.c_double))]
 
 
 class WidebandBlanker(C.Structure):
@@ -133,6 +139,9 @@ PROTOTYPES = {
     "msk144_set_wideband_pings": ([_vp, _P(WidebandPingsParams)], C.c_int),
     "msk144_wideband_pings": ([_vp, _P(WidebandPing)], C.c_int),
     "msk144_wideband_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
+    "msk144_set_wideband_waterfall": ([_vp, _P(WidebandWaterfall)], C.c_int),
+    "msk144_wideband_waterfall": ([_vp, _i32, _P(C.c_float), _P(_i32)], C.c_int),
+    "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -523,6 +532,32 @@ class HipDecoder:
         n = C.c_int32()
         self._chk(self.L.msk144_wideband_ping_blocks(self.h, -1 if channel is None else int(channel), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
         return out[:, :n.value].copy() if channel is None else out[0, :n.value].copy()
+
+    def set_wideband_waterfall(self, window="hann"):
+        """The per-channel waterfall from the next push on (include/msk144hip.h): set_wideband_waterfall() takes the periodic Hann
+        window, set_wideband_waterfall(w) 96 finite values; set_wideband_waterfall(None) switches it off."""
+        if window is None:
+            self._chk(self.L.msk144_set_wideband_waterfall(self.h, None))
+            return
+        w = None if isinstance(window, str) and window == "hann" else np.ascontiguousarray(window, dtype=np.float64)
+        if w is not None and w.shape != (WATERFALL_BINS,):
+            raise ValueError("the window must hold 96 values")
+        p = WidebandWaterfall(None if w is None else w.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk(self.L.msk144_set_wideband_waterfall(self.h, C.byref(p)))
+
+    def wideband_waterfall(self, channel: Optional[int] = None) -> np.ndarray:
+        """float32 [nb][96] of the channel's last push - rows[b][j] the power of block b at (j - 48) x 125 Hz from the channel's
+        offset, nb = 54 after a first push, else 27; channel None: every channel's, float32 [channels][nb][96]."""
+        out = np.zeros((self.channels if channel is None else 1, WATERFALL_ROWS, WATERFALL_BINS), dtype=np.float32)
+        n = C.c_int32()
+        self._chk(self.L.msk144_wideband_waterfall(self.h, -1 if channel is None else int(channel), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        return out[:, :n.value].copy() if channel is None else out[0, :n.value].copy()
+
+    def wideband_waterfall_sums(self) -> np.ndarray:
+        """float64 [channels][96]: every channel's rows of the last push added in double, block by block."""
+        out = np.zeros((self.channels, WATERFALL_BINS), dtype=np.float64)
+        self._chk(self.L.msk144_wideband_waterfall_sums(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

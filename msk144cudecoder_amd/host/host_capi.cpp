@@ -175,6 +175,59 @@ int msk144host_wideband_pings_parse(const char* arg, int32_t* out4)
     return 0;
 }
 
+// ---- the per-channel waterfall (csrc/wideband.h: the window, the check, the dB scale, the line, the frequency rule of a ping event) ----
+
+// the default window of msk144_set_wideband_waterfall (periodic Hann) in out[96]; returns 96
+int msk144host_wideband_waterfall_window(double* out)
+{
+    const std::vector<double> w = msk144wb::waterfall_window();
+    std::copy(w.begin(), w.end(), out);
+    return msk144wb::kWaterfallBins;
+}
+// 0 when msk144_set_wideband_waterfall takes the window [96] (NULL: the default), else -1 with the refusal text in why
+int msk144host_wideband_waterfall_check(const double* window, char* why, int why_len) { return copy_why(msk144wb::check_waterfall(window), why, why_len); }
+// (sum w)^2 over the f32 window (NULL: the default), and the dB of a power against it
+double msk144host_wideband_waterfall_full(const double* window) { return msk144wb::waterfall_full(window); }
+double msk144host_wideband_waterfall_db(double power, double full) { return msk144wb::waterfall_db(power, full); }
+// the row's line of the log (--wideband-waterfall=FILE), NUL-terminated in out
+void msk144host_wideband_waterfall_line(int32_t channel, int32_t offset_hz, int64_t block, const float* row, double full, char* out, int cap)
+{
+    std::strncpy(out, msk144wb::waterfall_line(channel, offset_hz, block, row, full).c_str(), static_cast<size_t>(cap) - 1);
+    out[cap - 1] = 0;
+}
+// "FILE[:CHANNELS]" as the program parses it: 0 and out = {1 for `pings` else 0, listed channels, length of FILE, the channels ...}
+// (19 values), else -1
+int msk144host_wideband_waterfall_parse(const char* arg, int32_t* out)
+{
+    WidebandOptions w;
+    if(!parse_wideband_waterfall(arg, w)) return -1;
+    out[0] = w.waterfall_by_pings ? 1 : 0, out[1] = static_cast<int32_t>(w.waterfall_channels.size()), out[2] = static_cast<int32_t>(w.waterfall_file.size());
+    for(size_t i = 0; i < w.waterfall_channels.size(); i++) out[3 + i] = w.waterfall_channels[i];
+    return 0;
+}
+// the frequency rule: push and close write at most cap frequencies in Hz, one per reported event, and return their number
+void* msk144host_wideband_ping_spectra_new(int channels, int min_blocks)
+{
+    if(channels < 1 || min_blocks < 1 || min_blocks > msk144wb::kPingMaxMinBlocks) return nullptr;
+    return new msk144wb::PingSpectra(channels, min_blocks);
+}
+void msk144host_wideband_ping_spectra_free(void* s) { delete static_cast<msk144wb::PingSpectra*>(s); }
+// records[channels], rows[channels][54][96]
+int msk144host_wideband_ping_spectra_push(void* s, const msk144wb::PingRecord* records, const float* rows, int32_t* out, int cap)
+{
+    std::vector<int32_t> f;
+    static_cast<msk144wb::PingSpectra*>(s)->push(records, rows, f);
+    for(int i = 0; i < static_cast<int>(f.size()) && i < cap; i++) out[i] = f[static_cast<size_t>(i)];
+    return static_cast<int>(f.size());
+}
+int msk144host_wideband_ping_spectra_close(void* s, int32_t* out, int cap)
+{
+    std::vector<int32_t> f;
+    static_cast<msk144wb::PingSpectra*>(s)->close(f);
+    for(int i = 0; i < static_cast<int>(f.size()) && i < cap; i++) out[i] = f[static_cast<size_t>(i)];
+    return static_cast<int>(f.size());
+}
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

@@ -74,6 +74,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-blanker[=RATIO[:PRE[:POST]]]  With --wideband-rate: impulse-noise blanker on the input stream, on the GPU, ahead of the channel filters: a sample whose power exceeds RATIO x the mean power of its hop is zeroed together with PRE samples before and POST after it (0..4096 each). RATIO 1..4095.9, default=16; PRE default=2, POST default=8. At the end, on stderr, one line with the hits and the blanked samples." << std::endl;
     std::cout << "                   --wideband-spectrum=FILE[:BINS[:HOPS]]  With --wideband-rate: the power spectrum of the input stream at the input rate, on the GPU (of the blanked stream with --wideband-blanker): BINS-point transforms (a power of two, 256..8192, default=1024) of the hop's samples under a Hann window, summed over HOPS hops (default=5), appended to FILE as one line 'hop= rate= bins= segments= dbfs=v0,v1,...' in ascending frequency, 0 dBFS = a full-scale tone. At the end, on stderr, one line with the median bin (the floor) and the highest bin." << std::endl;
     std::cout << "                   --wideband-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]  With --wideband-rate: ping detection per channel, on the GPU, on each channel's int8 I/Q: the energy of every 8 ms block (96 samples) is compared with RATIO x the channel's quiet level (the lower quartile of a hop's blocks, the lowest of this hop and the MEMORY hops before it, 0..16; default=8). RATIO 1..4095.9, default=2. A run of at least MIN_BLOCKS (1..64, default=2) consecutive blocks above it is an event, appended to FILE when it ends as one line 'ping ch= offset= start= dur= blocks= peak= ref= peak_db='. A strong-ping detector (from about +7 dB in 2500 Hz), less sensitive than the decoder. At the end, on stderr, one line with the events and the most active channels." << std::endl;
+    std::cout << "                   --wideband-waterfall=FILE[:CHANNELS]  With --wideband-rate: a waterfall per channel, on the GPU, on each channel's int8 I/Q: one 96-point spectrum (125 Hz per bin, Hann window) per 8 ms block, the blocks of --wideband-pings. CHANNELS is a list of up to 16 channel indices c0,c1,... (every block of these is written) or 'pings' (every block above the threshold of every channel; the default with --wideband-pings, without it a list is required). After every push one line per selected row is appended to FILE: 'wf ch= offset= block= t= db=v0,...,v95' in ascending frequency from -6000 Hz, 0 dB = a tone of 1 LSB, floor -100 dB. With --wideband-pings every ping line gains ' freq=<Hz>', the strongest bin of the event's blocks. At the end, on stderr, one line with the rows written and up to three channels whose spectrum summed over the run has a bin at least 10 dB (a design parameter) over the channel's median bin: a steady carrier in the passband. A display and a frequency estimate; it does not feed the decoder." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -189,6 +190,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-blanker", optional_argument, 0, 0},
                                            {"wideband-spectrum", required_argument, 0, 0},
                                            {"wideband-pings", required_argument, 0, 0},
+                                           {"wideband-waterfall", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -241,6 +243,7 @@ int main(int argc, char* const argv[])
         case 29:
         case 30:
         case 31:
+        case 32:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -254,6 +257,7 @@ int main(int argc, char* const argv[])
             else if(idx == 29) good = parse_wideband_blanker(optarg, wbo);
             else if(idx == 30) good = parse_wideband_spectrum(optarg, wbo);
             else if(idx == 31) good = parse_wideband_pings(optarg, wbo);
+            else if(idx == 32) good = parse_wideband_waterfall(optarg, wbo);
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
@@ -309,7 +313,8 @@ int main(int argc, char* const argv[])
     {
         std::string err;
         if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
-           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)))
+           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)) ||
+           (wbo.waterfall && !wb_api.load_waterfall(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
@@ -327,6 +332,13 @@ int main(int argc, char* const argv[])
     if(wbo.pings && !(pings_file = fopen(wbo.pings_file.c_str(), "a")))
     {
         std::cerr << "--wideband-pings: cannot open '" << wbo.pings_file << "': " << strerror(errno) << std::endl;
+        return 2;
+    }
+    // --wideband-waterfall: likewise
+    FILE* waterfall_file = nullptr;
+    if(wbo.waterfall && !(waterfall_file = fopen(wbo.waterfall_file.c_str(), "a")))
+    {
+        std::cerr << "--wideband-waterfall: cannot open '" << wbo.waterfall_file << "': " << strerror(errno) << std::endl;
         return 2;
     }
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
@@ -482,6 +494,15 @@ int main(int argc, char* const argv[])
                 return 2;
             }
         }
+        if(wbo.waterfall)
+        {
+            const msk144_wideband_waterfall_params wp{nullptr};
+            if(wb_api.set_waterfall(dec.handle(), &wp) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
         if(wbo.blanker)
         {
             const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
@@ -565,6 +586,7 @@ int main(int argc, char* const argv[])
     {
         if(wbo.spectrum) loops[i]->use_wideband_spectrum(spectrum_file, wbo.spectrum_bins, wbo.spectrum_hops, wbo.rate_hz);
         if(wbo.pings) loops[i]->use_wideband_pings(pings_file, wbo.ping_min_blocks, wbo.offsets);
+        if(wbo.waterfall) loops[i]->use_wideband_waterfall(waterfall_file, wbo.waterfall_by_pings, wbo.waterfall_channels, wbo.offsets, wbo.ping_min_blocks);
         if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
@@ -702,6 +724,19 @@ int main(int argc, char* const argv[])
             }
             std::cerr << line << std::endl;
         }
+        if(wbo.waterfall)
+        {
+            std::string line = "msk144hipdecoder: wideband waterfall: " + std::to_string(loops[0]->wideband_waterfall_rows()) + " rows written";
+            const std::vector<DeviceLoop::WaterfallCarrier> carriers = loops[0]->wideband_waterfall_carriers();
+            line += carriers.empty() ? "; no channel has a bin 10 dB over its median bin" : "; a bin 10 dB or more over the channel's median bin:";
+            char buf[96];
+            for(const DeviceLoop::WaterfallCarrier& c : carriers)
+            {
+                snprintf(buf, sizeof(buf), " ch=%d %+d Hz (+%.1f dB)", c.channel, c.hz, c.excess_db);
+                line += buf;
+            }
+            std::cerr << line << std::endl;
+        }
         if(wbo.levels)
         {
             const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();
@@ -758,6 +793,7 @@ int main(int argc, char* const argv[])
     }
     if(spectrum_file) fclose(spectrum_file);
     if(pings_file) fclose(pings_file);
+    if(waterfall_file) fclose(waterfall_file);
     std::cout << "Done" << std::endl;
     return 0;
 }

@@ -212,6 +212,7 @@ int DeviceLoop::join()
         if(wb_read_levels_) read_wideband_levels();
         if(wb_spec_file_) read_wideband_spectrum();
         if(wb_ping_file_) read_wideband_pings();
+        else if(wb_wf_file_) read_wideband_waterfall();
         wb_components_ += wb_pending_components_;
         wb_pending_components_ = 0;
     }
@@ -219,7 +220,8 @@ int DeviceLoop::join()
     if(wb_ping_file_)
     {
         wb_ping_tracker_->close(wb_ping_events_);  // the end of the stream closes every open run
-        write_ping_events();
+        if(wb_wf_spectra_) wb_wf_spectra_->close(wb_ping_freqs_);
+        if(!write_ping_events()) failed = true;
     }
     return failed ? 2 : 0;
 }
@@ -246,7 +248,7 @@ bool DeviceLoop::submit_wideband(Batch& b)
         }
         wb_clipped_ += clipped;
         wb_components_ += wb_pending_components_;
-        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ && !read_wideband_pings()))
+        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ ? !read_wideband_pings() : (wb_wf_file_ && !read_wideband_waterfall())))
         {
             fail(msk144_last_error(dec_.handle()));
             return false;
@@ -312,15 +314,98 @@ bool DeviceLoop::read_wideband_pings()
     int32_t nb = 0;
     if(wb_->pings(dec_.handle(), wb_ping_buf_.data()) != MSK144_OK || wb_->ping_blocks(dec_.handle(), -1, wb_ping_energies_.data(), &nb) != MSK144_OK) return false;
     wb_ping_tracker_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_ping_energies_.data(), wb_ping_events_);
-    write_ping_events();
+    if(wb_wf_file_ && !read_wideband_waterfall()) return false;  // the same push's rows: the frequencies of the events that closed
+    return write_ping_events();
+}
+
+// with --wideband-waterfall event k of the tracker has frequency k of PingSpectra, which follows the same records; the two rules
+// disagreeing on the events of a push is a defect of the program: it ends the run instead of writing lines without the field
+bool DeviceLoop::write_ping_events()
+{
+    if(wb_wf_spectra_ && wb_ping_freqs_.size() != wb_ping_events_.size())
+    {
+        fail("ping events and their frequencies disagree: " + std::to_string(wb_ping_events_.size()) + " events, " + std::to_string(wb_ping_freqs_.size()) + " frequencies");
+        return false;
+    }
+    for(size_t k = 0; k < wb_ping_events_.size(); k++)
+    {
+        const msk144wb::PingEvent& e = wb_ping_events_[k];
+        std::string line = msk144wb::ping_event_line(e, wb_ping_offsets_[static_cast<size_t>(e.channel)]);
+        if(wb_wf_spectra_) line += " freq=" + std::to_string(wb_ping_freqs_[k]);
+        fprintf(wb_ping_file_, "%s\n", line.c_str());
+    }
+    if(!wb_ping_events_.empty()) fflush(wb_ping_file_);
+    wb_ping_events_.clear();
+    wb_ping_freqs_.clear();
     return true;
 }
 
-void DeviceLoop::write_ping_events()
+void DeviceLoop::use_wideband_waterfall(FILE* file, bool by_pings, const std::vector<int32_t>& channels, const std::vector<int32_t>& offsets, int min_blocks)
 {
-    for(const msk144wb::PingEvent& e : wb_ping_events_) fprintf(wb_ping_file_, "%s\n", msk144wb::ping_event_line(e, wb_ping_offsets_[static_cast<size_t>(e.channel)]).c_str());
-    if(!wb_ping_events_.empty()) fflush(wb_ping_file_);
-    wb_ping_events_.clear();
+    wb_wf_file_ = file;
+    wb_wf_by_pings_ = by_pings;
+    wb_wf_channels_ = channels;
+    wb_wf_offsets_ = offsets;
+    if(wb_ping_file_) wb_wf_spectra_.reset(new msk144wb::PingSpectra(static_cast<int>(offsets.size()), min_blocks));
+    wb_wf_full_ = msk144wb::waterfall_full(nullptr);
+    wb_wf_rows_.assign(offsets.size() * msk144wb::kWaterfallRows * msk144wb::kWaterfallBins, 0.0f);
+    wb_wf_sums_.assign(offsets.size() * msk144wb::kWaterfallBins, 0.0);
+    wb_wf_run_ = wb_wf_sums_;
+}
+
+// --wideband-waterfall: the rows and sums of the push just made (read where its clip count is read, behind its ping records)
+bool DeviceLoop::read_wideband_waterfall()
+{
+    constexpr size_t B = msk144wb::kWaterfallBins, R = msk144wb::kWaterfallRows;
+    const size_t C = wb_wf_offsets_.size();
+    const int nb = static_cast<int>(wb_wf_pushes_ ? R / 2 : R);  // a first push, then hops
+    // the channels whose rows are needed: the listed ones, and with the ping detector those with an up block
+    std::vector<int32_t> need = wb_wf_channels_;
+    for(size_t c = 0; wb_wf_spectra_ && c < C; c++)
+        if(wb_ping_buf_[c].up_mask && std::find(need.begin(), need.end(), static_cast<int32_t>(c)) == need.end()) need.push_back(static_cast<int32_t>(c));
+    int32_t n = nb;
+    if(need.size() > static_cast<size_t>(msk144wb::kWaterfallHandful))
+    {
+        if(wb_->waterfall(dec_.handle(), -1, wb_wf_rows_.data(), &n) != MSK144_OK) return false;
+    }
+    else
+        for(int32_t c : need)
+            if(wb_->waterfall(dec_.handle(), c, wb_wf_rows_.data() + static_cast<size_t>(c) * R * B, &n) != MSK144_OK) return false;
+    if(n != nb || wb_->waterfall_sums(dec_.handle(), wb_wf_sums_.data()) != MSK144_OK) return false;
+    for(size_t k = 0; k < wb_wf_sums_.size(); k++) wb_wf_run_[k] += wb_wf_sums_[k];
+
+    const auto write = [&](size_t c, int b) {
+        fprintf(wb_wf_file_, "%s\n",
+                msk144wb::waterfall_line(static_cast<int32_t>(c), wb_wf_offsets_[c], wb_wf_base_ + b, wb_wf_rows_.data() + (c * R + static_cast<size_t>(b)) * B, wb_wf_full_).c_str());
+        wb_wf_written_++;
+    };
+    const long long before = wb_wf_written_;
+    if(!wb_wf_by_pings_)
+        for(int32_t c : wb_wf_channels_)
+            for(int b = 0; b < nb; b++) write(static_cast<size_t>(c), b);
+    else
+        for(size_t c = 0; c < C; c++)
+            for(int b = 0; b < nb; b++)
+                if((wb_ping_buf_[c].up_mask >> b) & 1) write(c, b);
+    if(wb_wf_written_ != before) fflush(wb_wf_file_);
+    if(wb_wf_spectra_) wb_wf_spectra_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_wf_rows_.data(), wb_ping_freqs_);
+    wb_wf_base_ += nb;
+    wb_wf_pushes_++;
+    return true;
+}
+
+std::vector<DeviceLoop::WaterfallCarrier> DeviceLoop::wideband_waterfall_carriers() const
+{
+    std::vector<WaterfallCarrier> out;
+    for(size_t c = 0; c < wb_wf_offsets_.size(); c++)
+    {
+        int j = 0;
+        const double excess = msk144wb::waterfall_excess_db(&wb_wf_run_[c * msk144wb::kWaterfallBins], j);
+        if(excess >= msk144wb::kWaterfallCarrierDb) out.push_back(WaterfallCarrier{static_cast<int>(c), msk144wb::waterfall_hz(j), excess});
+    }
+    std::stable_sort(out.begin(), out.end(), [](const WaterfallCarrier& a, const WaterfallCarrier& b) { return a.excess_db > b.excess_db; });
+    if(out.size() > 3) out.resize(3);
+    return out;
 }
 
 void DeviceLoop::use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz)

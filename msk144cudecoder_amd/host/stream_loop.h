@@ -113,6 +113,22 @@ public:
     // event that closes (csrc/wideband.h PingTracker) is appended to `file` as one line and flushed, the open ones when the stream ends
     void use_wideband_pings(FILE* file, int min_blocks, const std::vector<int32_t>& offsets);
     const msk144wb::PingTracker& wideband_ping_tracker() const { return *wb_ping_tracker_; }
+    // --wideband-waterfall: after every push one line per selected row is appended to `file` (csrc/wideband.h waterfall_line) - every
+    // block of the listed channels, or with by_pings every up block of every channel (needs use_wideband_pings) - and the sums are
+    // added to the run's.  Rows are read only for the channels that need them: the listed ones and, with the ping detector, those
+    // with an up block; more than a handful in one copy of all.  With the ping detector every event line gains ` freq=<Hz>`
+    // (csrc/wideband.h PingSpectra).  Call it after use_wideband_pings.
+    void use_wideband_waterfall(FILE* file, bool by_pings, const std::vector<int32_t>& channels, const std::vector<int32_t>& offsets, int min_blocks);
+    // over the run: the rows written and up to three channels whose summed spectrum has a bin at least 10 dB
+    // (msk144wb::kWaterfallCarrierDb) over the channel's median bin, the largest excess first
+    struct WaterfallCarrier
+    {
+        int channel = 0;
+        int32_t hz = 0;
+        double excess_db = 0.0;
+    };
+    long long wideband_waterfall_rows() const { return wb_wf_written_; }
+    std::vector<WaterfallCarrier> wideband_waterfall_carriers() const;
 
     struct SpectrumSummary
     {
@@ -188,7 +204,8 @@ private:
     bool read_wideband_levels();
     bool read_wideband_spectrum();
     bool read_wideband_pings();
-    void write_ping_events();
+    bool read_wideband_waterfall();
+    bool write_ping_events();
     void write_spectrum_line();
 
     WindowDecoder dec_;
@@ -214,6 +231,14 @@ private:
     std::vector<int32_t> wb_ping_offsets_, wb_ping_energies_;
     std::vector<msk144_wideband_ping> wb_ping_buf_;
     std::vector<msk144wb::PingEvent> wb_ping_events_;
+    FILE* wb_wf_file_ = nullptr;
+    bool wb_wf_by_pings_ = false;
+    std::vector<int32_t> wb_wf_channels_, wb_wf_offsets_, wb_ping_freqs_;
+    std::unique_ptr<msk144wb::PingSpectra> wb_wf_spectra_;
+    std::vector<float> wb_wf_rows_;                 // [channels][54][96], the rows of the channels read
+    std::vector<double> wb_wf_sums_, wb_wf_run_;    // [channels][96]: the last push, the run
+    double wb_wf_full_ = 1.0;                       // (sum w)^2 of the default window
+    long long wb_wf_pushes_ = 0, wb_wf_base_ = 0, wb_wf_written_ = 0;  // pushes read, blocks of all earlier pushes, rows written
     long long wb_spec_group_segments_ = 0, wb_spec_group_pushes_ = 0, wb_spec_run_segments_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;

@@ -81,6 +81,22 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-waterfall: resolved only when it is given (load_waterfall)
+    int (*set_waterfall)(msk144_handle*, const msk144_wideband_waterfall_params*) = nullptr;
+    int (*waterfall)(msk144_handle*, int32_t, float*, int32_t*) = nullptr;
+    int (*waterfall_sums)(msk144_handle*, double*) = nullptr;
+
+    bool load_waterfall(std::string& err)
+    {
+        set_waterfall = reinterpret_cast<decltype(set_waterfall)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_waterfall"));
+        waterfall = reinterpret_cast<decltype(waterfall)>(dlsym(RTLD_DEFAULT, "msk144_wideband_waterfall"));
+        waterfall_sums = reinterpret_cast<decltype(waterfall_sums)>(dlsym(RTLD_DEFAULT, "msk144_wideband_waterfall_sums"));
+        if(set_waterfall && waterfall && waterfall_sums) return true;
+        err = std::string("the loaded libmsk144hip has no waterfall (") +
+              (!set_waterfall ? "msk144_set_wideband_waterfall" : !waterfall ? "msk144_wideband_waterfall" : "msk144_wideband_waterfall_sums") + "): --wideband-waterfall needs it";
+        return false;
+    }
+
     bool load(std::string& err)
     {
         set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
@@ -111,6 +127,10 @@ struct WidebandOptions
     std::string pings_file;
     msk144wb::PingParams ping_params;
     int ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
+    bool waterfall = false;       // --wideband-waterfall=FILE[:CHANNELS]: the per-channel waterfall, one line per selected row appended to FILE
+    std::string waterfall_file;
+    bool waterfall_by_pings = true;            // CHANNELS is `pings` (the default; needs --wideband-pings): every up block of every channel
+    std::vector<int32_t> waterfall_channels;   // ... or a list of up to 16 channel indices: every block of these
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -235,6 +255,35 @@ inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
     return msk144wb::check_pings(w.ping_params).empty();
 }
 
+// "FILE[:CHANNELS]": CHANNELS `pings`, or up to 16 different channel indices c0,c1,... (whether they exist and whether `pings` has a
+// detector to follow needs the other options: check_wideband_options)
+inline bool parse_wideband_waterfall(const std::string& s, WidebandOptions& w)
+{
+    w.waterfall = true;
+    w.waterfall_by_pings = true;
+    w.waterfall_channels.clear();
+    const size_t a = s.find(':');
+    w.waterfall_file = s.substr(0, a);
+    if(w.waterfall_file.empty()) return false;
+    if(a == std::string::npos) return true;
+    const std::string list = s.substr(a + 1);
+    if(list == "pings") return true;
+    w.waterfall_by_pings = false;
+    size_t p = 0;
+    while(true)
+    {
+        const size_t q = list.find(',', p);
+        long long v = 0;
+        if(!parse_int(list.substr(p, q == std::string::npos ? q : q - p), v) || v < 0 || v > INT32_MAX) return false;
+        if(std::find(w.waterfall_channels.begin(), w.waterfall_channels.end(), static_cast<int32_t>(v)) != w.waterfall_channels.end()) return false;
+        w.waterfall_channels.push_back(static_cast<int32_t>(v));
+        if(w.waterfall_channels.size() > static_cast<size_t>(msk144wb::kWaterfallMaxListed)) return false;
+        if(q == std::string::npos) break;
+        p = q + 1;
+    }
+    return true;
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -285,6 +334,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.pings) return "--wideband-pings needs --wideband-rate=HZ";
+    if(w.rate_hz <= 0 && w.waterfall) return "--wideband-waterfall needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
@@ -297,6 +347,10 @@ inline std::string check_wideband_options(const WidebandOptions& w)
         const std::string bad = msk144wb::check_spectrum(w.spectrum_bins, nullptr, 2592 * w.rate_hz / msk144wb::kOutRate);
         if(!bad.empty()) return "--wideband-spectrum: " + bad;
     }
+    if(why.empty() && w.waterfall && w.waterfall_by_pings && !w.pings) return "--wideband-waterfall=FILE needs a channel list (FILE:c0,c1,...) without --wideband-pings";
+    for(size_t i = 0; why.empty() && w.waterfall && i < w.waterfall_channels.size(); i++)
+        if(static_cast<size_t>(w.waterfall_channels[i]) >= w.offsets.size())
+            return "--wideband-waterfall: channel " + std::to_string(w.waterfall_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
     return why;
 }
 

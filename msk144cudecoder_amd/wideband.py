@@ -493,6 +493,123 @@ def ping_event_line(event: dict, offset_hz: int) -> str:
             f"peak={event['peak']} ref={event['reference']} peak_db={10.0 * math.log10(event['peak'] / event['reference']):.1f}")
 
 
+# ---- per-channel waterfall (msk144_set_wideband_waterfall) ----
+
+WATERFALL_BINS = PING_BLOCK          # one 96-point transform per block of the ping detector: 125 Hz per bin
+WATERFALL_ROWS = PING_MAX_BLOCKS
+WATERFALL_FLOOR = 1e-10              # -100 dB under a tone of 1 LSB on a bin centre
+WATERFALL_CARRIER_DB = 10.0          # the carrier rule of the program's summary: a design parameter
+
+
+def waterfall_window() -> np.ndarray:
+    """The default window of the contract, periodic Hann: w[i] = 0.5 - 0.5 cos(2 pi i / 96), float64 (the library's own is
+    msk144host_wideband_waterfall_window)."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(WATERFALL_BINS, dtype=np.float64) / WATERFALL_BINS)
+
+
+def waterfall_full(window=None) -> float:
+    """(sum w)^2 over the f32 window the device holds: what a tone of 1 LSB on a bin centre reads, 0 dB of the program's output."""
+    w = waterfall_window() if window is None else np.asarray(window, dtype=np.float64)
+    s = 0.0
+    for v in w.astype(np.float32):
+        s += float(v)
+    return s * s
+
+
+def waterfall_hz(j: int) -> int:
+    """(j - 48) x 125 Hz: slot j of a row from the channel's offset."""
+    return (int(j) - WATERFALL_BINS // 2) * (12000 // WATERFALL_BINS)
+
+
+def waterfall_db(power, full: float) -> np.ndarray:
+    """10 log10(max(P / (sum w)^2, 1e-10)), value by value with math.log10 as the program does."""
+    p = np.asarray(power, dtype=np.float64)
+    out = np.empty(p.shape, dtype=np.float64)
+    flat = out.reshape(-1)
+    for n, v in enumerate(p.reshape(-1)):
+        r = float(v) / full
+        flat[n] = 10.0 * math.log10(r) if r > WATERFALL_FLOOR else 10.0 * math.log10(WATERFALL_FLOOR)
+    return out
+
+
+def waterfall_line(channel: int, offset_hz: int, block: int, row, full: float) -> str:
+    """One line of msk144hipdecoder --wideband-waterfall=FILE: row [96] of global block g, t = 0.008 g, two decimals per bin."""
+    ms = int(block) * 8
+    db = ",".join("0.00" if s == "-0.00" else s for s in ("%.2f" % v for v in waterfall_db(row, full)))
+    return f"wf ch={int(channel)} offset={int(offset_hz)} block={int(block)} t={ms // 1000}.{ms % 1000:03d} db={db}"
+
+
+class Waterfall:
+    """The waterfall of the contract (include/msk144hip.h) in float64, fed hops: P_b[k] = |sum_i w[i] x[96b + i] e^{-j2pi ik/96}|^2 of
+    the int8 hops x = I + jQ, by a direct product with the exact 96 x 96 matrix (the angle reduced mod 96 in integers), returned in
+    ascending frequency: rows[c][b][j] is bin (j - 48) mod 96.  The window is the f32 the device stores, as float64.  Nothing is
+    carried from push to push."""
+
+    def __init__(self, window=None):
+        w = waterfall_window() if window is None else np.asarray(window, dtype=np.float64)
+        if w.shape != (WATERFALL_BINS,) or not np.all(np.isfinite(w)):
+            raise ValueError("the window must hold 96 finite values")
+        self.window = w.astype(np.float32).astype(np.float64)
+        i = np.arange(WATERFALL_BINS, dtype=np.int64)
+        k = (i - WATERFALL_BINS // 2) % WATERFALL_BINS
+        self.matrix = self.window[:, None] * np.exp(-2j * np.pi * ((i[:, None] * k[None, :]) % WATERFALL_BINS) / WATERFALL_BINS)   # [i][j]
+
+    def push(self, q) -> np.ndarray:
+        """float64 [channel][nb][96] from the int8 hops q [channel][M][2] of one push."""
+        q = np.asarray(q)
+        if q.ndim != 3 or q.shape[1] % WATERFALL_BINS or q.shape[2] != 2:
+            raise ValueError("hops must be [channel][M][2] with M a multiple of 96")
+        x = q[..., 0].astype(np.float64) + 1j * q[..., 1].astype(np.float64)
+        X = x.reshape(q.shape[0], -1, WATERFALL_BINS) @ self.matrix
+        return X.real ** 2 + X.imag ** 2
+
+
+def waterfall_sums(rows) -> np.ndarray:
+    """float64 [channel][96]: the f32 rows [channel][nb][96] added one after another in double, b ascending."""
+    r = np.asarray(rows, dtype=np.float32)
+    out = np.zeros((r.shape[0], r.shape[2]), dtype=np.float64)
+    for b in range(r.shape[1]):
+        out += r[:, b, :].astype(np.float64)
+    return out
+
+
+class PingSpectra:
+    """The frequency of a ping event (csrc/wideband.h PingSpectra, the rule the program runs): one float64 accumulator [96] per channel;
+    blocks are taken in stream order, a block that is up adds its row, a block that is not up clears it.  push and close return one
+    frequency in Hz - (j* - 48) x 125, j* the lowest j at the maximum - per event PingEvents reports from the same records (runs of
+    at least min_blocks blocks), in its order."""
+
+    def __init__(self, channels: int, min_blocks: int = PING_MIN_BLOCKS):
+        self.min_blocks = int(min_blocks)
+        self.acc = np.zeros((int(channels), WATERFALL_BINS), dtype=np.float64)
+        self.blocks = [0] * int(channels)
+
+    def _finish(self, c, out):
+        if self.blocks[c] >= self.min_blocks:
+            out.append(waterfall_hz(int(np.argmax(self.acc[c]))))
+        self.acc[c] = 0.0
+        self.blocks[c] = 0
+
+    def push(self, records, rows) -> list:
+        """records: PING_DTYPE [channel] of one push; rows: its waterfall [channel][nb][96] (HipDecoder.wideband_waterfall())."""
+        out = []
+        for c in range(len(records)):
+            mask, nb = int(records["up_mask"][c]), int(records["blocks"][c])
+            for b in range(nb):
+                if (mask >> b) & 1:
+                    self.acc[c] += np.asarray(rows[c][b], dtype=np.float32).astype(np.float64)
+                    self.blocks[c] += 1
+                else:
+                    self._finish(c, out)
+        return out
+
+    def close(self) -> list:
+        out = []
+        for c in range(len(self.blocks)):
+            self._finish(c, out)
+        return out
+
+
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 

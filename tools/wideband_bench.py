@@ -10,14 +10,16 @@ the defaults), so the time includes its step kernel after every push.  --blanker
 blanker_bytes is what they move per push (the raw push read twice, its cs16 form written once).  --spectrum[=BINS]: the input
 spectrum is on (msk144_set_wideband_spectrum, BINS default 1024, the default window), so the time includes its two kernels ahead of the
 channeliser; spectrum_bytes is the push they read once.  --pings: the ping detector is on (msk144_set_wideband_pings with the
-defaults), so the time includes its kernel behind the channeliser; pings_bytes is the staged hops it reads once.
+defaults), so the time includes its kernel behind the channeliser; pings_bytes is the staged hops it reads once.  --waterfall: the
+per-channel waterfall is on (msk144_set_wideband_waterfall, the default window), so the time includes its two kernels behind the
+channeliser; waterfall_mfma is the f32 MFMA instructions of a push (576 per channel) and waterfall_bytes the rows it writes.
 
 Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --program-rate, default 1.92 Msps, the program's
 default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
 samples at 12 kHz).
 
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
-                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings]
+                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--waterfall]
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from msk144cudecoder_amd import hipdecoder, wideband  # noqa: E402
 FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
 
-def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False) -> dict:
+def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False, waterfall: bool = False) -> dict:
     D = rate // 12000
     rng = np.random.default_rng(C + D)
     g = math.gcd(rate, 12000)
@@ -57,6 +59,8 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
             d.set_wideband_spectrum(spectrum)
         if pings:
             d.set_wideband_pings()
+        if waterfall:
+            d.set_wideband_waterfall()
         for s in range(2):
             d.wideband_slot(s)[:] = rng.integers(120, 136, size=d.wideband_slot(s).size, dtype=np.uint8)
         d.push_wideband(0, first=True)
@@ -96,6 +100,10 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
     if pings:
         ratio["pings"] = True
         ratio["pings_bytes"] = C * 2592 * 2   # every channel's int8 hop read once
+    if waterfall:
+        ratio["waterfall"] = True
+        ratio["waterfall_mfma"] = C * 576               # 3 waves x 96 steps x 2 per channel and hop
+        ratio["waterfall_bytes"] = C * 27 * 96 * 4      # the rows of a hop, written once
     return dict(channels=C, **ratio, K=K, agc=agc, blanker=blanker, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
                 channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
                 tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
@@ -143,11 +151,12 @@ def main():
     ap.add_argument("--blanker", action="store_true", help="measure with the impulse-noise blanker on")
     ap.add_argument("--spectrum", type=int, nargs="?", const=1024, default=0, metavar="BINS", help="measure with the input spectrum on (BINS default 1024)")
     ap.add_argument("--pings", action="store_true", help="measure with the ping detector on")
+    ap.add_argument("--waterfall", action="store_true", help="measure with the per-channel waterfall on")
     a = ap.parse_args()
     rates = [int(v) * 12000 for v in a.decimations.split(",") if v] + [int(v) for v in a.rates.split(",") if v]
     for C in [int(v) for v in a.channels.split(",")]:
         for rate in rates:
-            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings)), flush=True)
+            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall)), flush=True)
     if a.program_hops:
         print(json.dumps(program_run(a.program_hops, rate=a.program_rate)), flush=True)
 
