@@ -655,6 +655,68 @@ int msk144_wideband_waterfall(msk144_handle* h, int32_t channel, float* rows, in
 /* sums[channels][96] of the last push */
 int msk144_wideband_waterfall_sums(msk144_handle* h, double* sums);
 
+/* ---- Per-ping capture of a channel's hops, for replay (no reference counterpart) ----
+ *
+ * A ping that did not decode is gone 216 ms later, when the hop ring advances.  Every channel's 12 ksps int8 I/Q stream - exactly
+ * what a read_mode 2 handle, or msk144hipdecoder --read-mode=2, reads - sits on the device behind the channeliser, and the ring
+ * also holds the hop before the newest one.  The capture picks the few (channel, hop) pairs worth keeping, packs them densely on the
+ * device and hands the host only those bytes: a quiet band costs a 16-byte header, a busy one 5184 bytes per kept hop.  The
+ * capture only reads the ping records and the ring.
+ *
+ *   Input:      per channel c, the ping record of every push (msk144_wideband_pings; all zero while the detector is off) and the
+ *               channel's ring window behind the push.  A stream's hops are numbered k = 0, 1, 2, ...: the first push carries hops
+ *               0 and 1, the p-th later push hop p + 1.  One hop is 2592 int8 I/Q pairs, 5184 bytes: one unit.
+ *   Rule:       a(k) = 1 iff the record of the push that carried hop k has an up block among hop k's 27 (first push: bits 0..26 are
+ *               hop 0, bits 27..53 hop 1; later push: bits 0..26).  L = c is in the list.
+ *               W(k) = L, or a(j) = 1 for some max(0, k - post) <= j <= k: active, within `post` hops after activity, or listed.
+ *               P(k) = pre = 1 and not W(k) and a(k + 1) = 1: the one hop of pre-roll the ring holds.
+ *               Hop k is emitted in the push that carries k if W(k), in the push that carries k + 1 if P(k) (for k = 0 both are the
+ *               first push), otherwise never; no hop is emitted twice.  csrc/wideband.h capture_step is the rule for device and host.
+ *   Parameters: pre 0 or 1 (default 1), 0 <= post <= 16 hops (default 1), 1 <= max_units <= 16384, up to 16 listed channels.  The
+ *               defaults are design parameters, not measurements.
+ *   Order:      a push's units come by channel ascending, then by hop ascending.  Of `total` units the first min(total, max_units)
+ *               are stored, the rest dropped and only counted; the rule never depends on what was dropped.  The state is per
+ *               channel - hops since the last active one, saturating, and whether the newest hop was emitted.  A first push clears
+ *               it: the same stream pushed twice gives the same bytes.  msk144_set_wideband_capture(h, &p) takes effect from the
+ *               next push, allocates everything - a push allocates nothing - and clears the state as well: activity before it counts
+ *               as none, and the pre-roll hop is used when the stream already has one.  (h, NULL) switches capture off, as
+ *               msk144_set_wideband does.  With capture off a push issues the calls it issues without it; on or off, every hop,
+ *               clip count, level, AGC step, blanker statistic, spectrum, ping record, waterfall row and decode is byte for byte the
+ *               same.
+ *   Output:     msk144_wideband_capture reports the last push and synchronises like msk144_wideband_levels: *count descriptors in
+ *               units[], *count rows of 5184 bytes in data[] (nothing past them is written), *total = all units of the push.
+ *               *count <= the max_units that push was made with, which is the last one set: every call of
+ *               msk144_set_wideband_capture that is accepted, (h, NULL) too, ends the last push's units, and the read entry answers
+ *               MSK144_ESTATE until the next push made with capture on.  So buffers for the max_units last set always suffice.
+ *               A larger max_units than any set before frees the device rows and allocates larger ones; a smaller one keeps them.
+ *               A unit's bytes are the bytes msk144_dump_wideband_hop returned for that hop in the push that carried it.
+ *               flags: bit 0 a(k); bit 1 L; bit 2 emitted as P(k), one push late; bit 3 tail: not active, but within `post` hops
+ *               after activity.
+ *   Refused:    MSK144_EINVAL outside wideband mode, for parameters out of range and for a listed channel that is out of range or
+ *               repeated (a refused call changes nothing); MSK144_ESTATE from msk144_wideband_capture before a push made with capture
+ *               on, and between an accepted msk144_set_wideband_capture and the next such push. */
+#define MSK144_CAPTURE_UNIT_BYTES 5184
+typedef struct msk144_wideband_capture_params
+{
+    int32_t pre;        /* hops of pre-roll, 0 or 1 (1) */
+    int32_t post;       /* hops kept after the last active one (1) */
+    int32_t max_units;  /* units stored per push; the program takes min(2 x channels, 512) */
+    int32_t num_listed; /* channels captured whether active or not */
+    int32_t listed[16];
+} msk144_wideband_capture_params;
+
+typedef struct msk144_wideband_capture_unit
+{
+    int32_t channel;
+    int32_t flags; /* bit 0 active, 1 listed, 2 pre-roll, 3 tail */
+    int64_t hop;   /* k */
+} msk144_wideband_capture_unit;
+
+/* NULL: off */
+int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_params* p);
+/* units[max_units], data[max_units][5184], max_units as last set: the last push, made since then */
+int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* units, int8_t* data /*[max_units][5184]*/, int32_t* count, int32_t* total);
+
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
 int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);

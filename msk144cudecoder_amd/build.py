@@ -32,6 +32,7 @@ SOURCES = [
     ("spectrum.hip", []),
     ("pings.hip", []),
     ("waterfall.hip", []),
+    ("capture.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstddef>
@@ -179,6 +180,17 @@ struct msk144_handle
         float2* d_wf_dft = nullptr;   // [3][96][32] the windowed DFT matrix in the kernel's order
         float* d_wf_rows = nullptr;   // [channels][54][96]
         double* d_wf_sums = nullptr;  // [channels][96]
+        // per-ping capture (msk144_set_wideband_capture): applies from the next push; `set` allocates - the descriptors and rows for
+        // the largest max_units set so far (capture_rows; a larger one frees them and allocates anew).  capture_restart: the next
+        // push is the first since `set`; capture_pushed: the last push left a header and no `set` has come since
+        bool capture = false, capture_restart = false, capture_pushed = false;
+        msk144wb::CaptureParams capture_params;
+        int capture_rows = 0;
+        uint8_t* d_cap_listed = nullptr;                  // [channels]
+        msk144wb::CaptureState* d_cap_state = nullptr;    // [channels]
+        msk144wb::CaptureHeader* d_cap_header = nullptr;  // [1]
+        msk144wb::CaptureUnit* d_cap_units = nullptr;     // [capture_rows]
+        uint8_t* d_cap_data = nullptr;                    // [capture_rows][5184]
         // Fs = 12000 Pin/Qin, the input rate (= P/Q without the bank); raw history samples kept between pushes
         int Pin = 0, Qin = 0, raw_hist = 0;
         // two-stage bank (rates above 6.144 Msps): P/Q, K, L, hist above are those of the channeliser at Fs/32
@@ -245,6 +257,19 @@ template<typename T>
 int dev_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
 {
     return alloc(h, owner, false, p, count);
+}
+
+// frees one buffer that dev_alloc registered with `owner` ahead of the rest; *p = nullptr
+template<typename T>
+void dev_free(Buffers& owner, T** p)
+{
+    const auto it = std::find(owner.device.begin(), owner.device.end(), static_cast<void*>(*p));
+    if(it != owner.device.end())
+    {
+        (void)hipFree(*it);
+        owner.device.erase(it);
+    }
+    *p = nullptr;
 }
 
 template<typename T>
@@ -1537,6 +1562,17 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     w.started = true;
     w.last_first = first != 0;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, C, h->stream);
+    if(w.capture)
+    {
+        // behind the ring kernel: the ring now holds the push's newest hop, number m_next / 2592 - 1, and the one before it
+        ev_begin(h);
+        launch_capture(h->d_ring, w.pings ? w.d_ping_records : nullptr, w.d_cap_listed, w.d_cap_state, C, first ? 1 : 0, first || w.capture_restart ? 1 : 0, w.capture_params,
+                       w.m_next / kHopSamples - 1, w.d_cap_header, w.d_cap_units, w.d_cap_data, h->stream);
+        ev_end(h, MSK144_T_FRONTEND);
+        w.capture_restart = false;
+        HIP_TRY(h, hipGetLastError());
+    }
+    w.capture_pushed = w.capture;
     return run_frontend(h, h->d_input);
 }
 
@@ -1842,6 +1878,74 @@ int msk144_wideband_waterfall_sums(msk144_handle* h, double* sums)
     const int rc = wb_waterfall_ready(h, "msk144_wideband_waterfall_sums");
     if(rc != MSK144_OK) return rc;
     HIP_TRY(h, hipMemcpy(sums, h->wb.d_wf_sums, sizeof(double) * msk144wb::kWaterfallBins * h->wb.gains.size(), hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_params* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_capture");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    if(!p)
+    {
+        w.capture = w.capture_pushed = false;
+        return MSK144_OK;
+    }
+    static_assert(sizeof(p->listed) / sizeof(p->listed[0]) == msk144wb::kCaptureMaxListed, "the list holds 16 channels");
+    const msk144wb::CaptureParams cp{p->pre, p->post, p->max_units};
+    const size_t C = w.gains.size();
+    const std::string why = msk144wb::check_capture(cp, p->listed, p->num_listed, static_cast<int>(C));
+    if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+    // An accepted `set` ends the last push's units: the read entry answers MSK144_ESTATE until the next push made with capture on.
+    // So it never meets a count above the caller's max_units, nor rows that no push has written.
+    w.capture = w.capture_pushed = false;
+    // never in a push
+    if(!w.d_cap_listed && (rc = dev_alloc(h, w.mem, &w.d_cap_listed, C)) != MSK144_OK) return rc;
+    if(!w.d_cap_state && (rc = dev_alloc(h, w.mem, &w.d_cap_state, C)) != MSK144_OK) return rc;
+    if(!w.d_cap_header && (rc = dev_alloc(h, w.mem, &w.d_cap_header, 1)) != MSK144_OK) return rc;
+    if(cp.max_units > w.capture_rows)
+    {
+        // more units than any set before: the old rows, which nothing reads any more, are freed and larger ones take their place
+        // (wb_quiesce has waited for the kernels that wrote them).  If that fails capture stays off, with no rows.
+        w.capture_rows = 0;
+        dev_free(w.mem, &w.d_cap_units);
+        dev_free(w.mem, &w.d_cap_data);
+        if((rc = dev_alloc(h, w.mem, &w.d_cap_units, static_cast<size_t>(cp.max_units))) != MSK144_OK) return rc;
+        if((rc = dev_alloc(h, w.mem, &w.d_cap_data, static_cast<size_t>(cp.max_units) * msk144wb::kCaptureUnitBytes)) != MSK144_OK) return rc;
+        w.capture_rows = cp.max_units;
+    }
+    std::vector<uint8_t> listed(C, 0);
+    for(int i = 0; i < p->num_listed; i++) listed[static_cast<size_t>(p->listed[i])] = 1;
+    HIP_TRY(h, hipMemcpy(w.d_cap_listed, listed.data(), C, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(w.d_cap_state, 0, sizeof(msk144wb::CaptureState) * C));
+    w.capture_params = cp;
+    w.capture = true;
+    w.capture_restart = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* units, int8_t* data, int32_t* count, int32_t* total)
+{
+    if(!h || !units || !data || !count || !total) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    if(!w.configured) return fail(h, MSK144_EINVAL, "msk144_wideband_capture needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !w.capture_pushed) return fail(h, MSK144_ESTATE, w.started ? "no wideband push has been made with capture on since it was last set" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    static_assert(sizeof(msk144_wideband_capture_unit) == sizeof(msk144wb::CaptureUnit) && offsetof(msk144_wideband_capture_unit, hop) == offsetof(msk144wb::CaptureUnit, hop),
+                  "the kernel writes msk144_wideband_capture_unit");
+    msk144wb::CaptureHeader head{};
+    HIP_TRY(h, hipMemcpy(&head, w.d_cap_header, sizeof(head), hipMemcpyDeviceToHost));
+    // the push that left the header was made with capture_params (`set` ends the units of the push before it)
+    if(head.count < 0 || head.count > w.capture_params.max_units || head.count > w.capture_rows) return fail(h, MSK144_EHIP, "msk144_wideband_capture: the device left a header out of range");
+    // a quiet band costs the header alone
+    if(head.count)
+    {
+        HIP_TRY(h, hipMemcpy(units, w.d_cap_units, sizeof(msk144wb::CaptureUnit) * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(data, w.d_cap_data, static_cast<size_t>(msk144wb::kCaptureUnitBytes) * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
+    }
+    *count = head.count;
+    *total = head.total;
     return MSK144_OK;
 }
 

@@ -128,6 +128,13 @@ void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int
 constexpr size_t kWaterfallDftSize = static_cast<size_t>(msk144wb::kWaterfallBins) * msk144wb::kWaterfallBins;
 void launch_waterfall(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float2* dft, float* rows, double* sums, hipStream_t stream);
 
+// the capture of a push (capture.hip; contract in include/msk144hip.h), behind launch_hop_ring: ring[channels] the 10368-byte
+// windows, records[channels] the push's ping records or nullptr (the detector was off), listed[channels] the list flags.  `newest`
+// is the newest hop of the push; `clear`: a first push or the first one after msk144_set_wideband_capture.  Moves state[channels]
+// and writes the header, the first min(total, max_units) descriptors and their rows data[.][5184].
+void launch_capture(const void* ring, const msk144wb::PingRecord* records, const uint8_t* listed, msk144wb::CaptureState* state, int channels, int first, int clear,
+                    const msk144wb::CaptureParams& p, long long newest, msk144wb::CaptureHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream);
+
 // what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
 // before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push
 struct BlankerCounters

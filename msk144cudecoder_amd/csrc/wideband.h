@@ -578,6 +578,249 @@ inline double waterfall_excess_db(const double* sum, int& j_top)
     return median > 0.0 ? 10.0 * std::log10(sum[j_top] / median) : 0.0;
 }
 
+// ---- per-ping capture of a channel's hops (msk144_set_wideband_capture, msk144_wideband_capture) ----
+
+constexpr int kCaptureUnitBytes = 5184;                   // one hop of one channel: 2592 int8 I/Q pairs, what --read-mode=2 reads
+constexpr int kCaptureHopBlocks = 27;                     // a hop is 27 blocks of the ping detector
+constexpr int kCaptureMaxPost = 16;
+constexpr int kCaptureQuiet = kCaptureMaxPost + 1;        // `since` saturates here: no activity that any `post` still reaches
+constexpr int kCaptureMaxUnits = 16384;
+constexpr int kCaptureMaxListed = kWaterfallMaxListed;
+constexpr int kCaptureDefaultMaxUnits = 512;              // the program's and the Python view's: min(2 x channels, 512)
+static_assert(kCaptureUnitBytes % 16 == 0 && kCaptureHopBlocks * kPingBlock * 2 == kCaptureUnitBytes && 2 * kCaptureHopBlocks == kPingMaxBlocks, "a unit is a hop");
+
+enum CaptureFlags
+{
+    kCaptureActive = 1,   // a(k): an up block among the hop's 27
+    kCaptureListed = 2,   // L
+    kCapturePre = 4,      // emitted as P(k), one push late
+    kCaptureTail = 8      // not active, but active within `post` hops before
+};
+
+// msk144_wideband_capture_params without the list.  The defaults are design parameters, not measurements.
+struct CaptureParams
+{
+    int32_t pre = 1, post = 1, max_units = kCaptureDefaultMaxUnits;
+};
+
+// msk144_wideband_capture_unit, field for field: what the plan kernel writes
+struct CaptureUnit
+{
+    int32_t channel, flags;
+    int64_t hop;
+};
+static_assert(sizeof(CaptureUnit) == 16, "msk144_wideband_capture_unit is 16 bytes");
+
+// what a push leaves in front of the descriptors: the stored units, all units, and the newest hop of the push
+struct CaptureHeader
+{
+    int32_t count, total;
+    int64_t hop;
+};
+static_assert(sizeof(CaptureHeader) == 16, "the capture header is 16 bytes");
+
+// a channel's memory: hops since the last active one (kCaptureQuiet: none that counts), and whether its newest hop was emitted
+struct CaptureState
+{
+    int32_t since, emitted;
+};
+
+// The capture rule, once, for one channel and one push.  `first`: the push carries hops 0 and 1 (up_mask bits 0..26 and 27..53),
+// else the newest hop alone (bits 0..26); up_mask is 0 when the detector was off.  `clear`: a first push, or the first push after
+// msk144_set_wideband_capture: earlier activity counts as none and the previous hop as not emitted.  Returns the channel's units of
+// this push, 0 .. 2 in ascending hop order: half[i] is the half of the channel's ring window the unit lies in (0: the hop before
+// the newest, 1: the newest), flags[i] its CaptureFlags.
+//   W(k) = listed, or a(j) for some k - post <= j <= k   -> hop k is emitted in its own push
+//   P(k) = pre and not W(k) and a(k + 1)                 -> hop k is emitted in the next push (for k = 0 that is the same push)
+MSK144WB_HD inline int capture_step(CaptureState& s, bool first, bool clear, uint64_t up_mask, bool listed, int32_t pre, int32_t post, int32_t flags[2], int32_t half[2])
+{
+    int32_t since = clear ? kCaptureQuiet : s.since;
+    bool emitted = clear ? false : s.emitted != 0;
+    int n = 0;
+    for(int i = first ? 0 : 1; i < 2; i++)
+    {
+        const bool a = ((up_mask >> (first ? kCaptureHopBlocks * i : 0)) & ((1ull << kCaptureHopBlocks) - 1)) != 0;
+        since = a ? 0 : since < kCaptureQuiet ? since + 1 : kCaptureQuiet;
+        const bool w = listed || since <= post;
+        // the hop before this one: in the ring since the push before, or hop 0 of this first push
+        if(i == 1 && pre && a && !emitted)
+        {
+            flags[n] = kCapturePre;
+            half[n++] = 0;
+        }
+        if(w)
+        {
+            flags[n] = (a ? kCaptureActive : 0) | (listed ? kCaptureListed : 0) | (!a && since <= post ? kCaptureTail : 0);
+            half[n++] = i;
+        }
+        emitted = w;
+    }
+    s.since = since;
+    s.emitted = emitted ? 1 : 0;
+    return n;
+}
+
+// The rules of msk144_set_wideband_capture.  Empty string = valid.
+inline std::string check_capture(const CaptureParams& p, const int32_t* listed, int num_listed, int channels)
+{
+    if(p.pre != 0 && p.pre != 1) return "capture pre must be 0 or 1 (the ring holds one hop of pre-roll)";
+    if(p.post < 0 || p.post > kCaptureMaxPost) return "capture post must lie within 0..16 hops";
+    if(p.max_units < 1 || p.max_units > kCaptureMaxUnits) return "capture max_units must lie within 1..16384";
+    if(num_listed < 0 || num_listed > kCaptureMaxListed) return "capture lists at most 16 channels";
+    for(int i = 0; i < num_listed; i++)
+    {
+        if(listed[i] < 0 || listed[i] >= channels) return "capture channel " + std::to_string(listed[i]) + " is out of range";
+        for(int j = 0; j < i; j++)
+            if(listed[j] == listed[i]) return "capture channel " + std::to_string(listed[i]) + " is listed twice";
+    }
+    return std::string();
+}
+
+// The rule over all channels of a stream on the host: what the plan kernel computes, and through libmsk144host.so the yardstick of
+// wideband.Capture.  Units come by channel, then by hop; the first max_units of a push are stored, the rest only counted - the
+// state moves the same either way.
+class Capture
+{
+public:
+    Capture(int channels, const CaptureParams& p, const int32_t* listed, int num_listed) : p_(p), state_(static_cast<size_t>(channels)), listed_(static_cast<size_t>(channels), 0)
+    {
+        for(int i = 0; i < num_listed; i++) listed_[static_cast<size_t>(listed[i])] = 1;
+    }
+
+    // as msk144_set_wideband_capture in mid-stream: the state cleared, the hop count kept
+    void restart() { clear_ = true; }
+    // the newest hop of the last push, for a rule that joins a stream in mid-stream
+    void set_hop(int64_t hop) { hop_ = hop; }
+    int64_t hop() const { return hop_; }
+
+    // records[channels] of one push, or nullptr: the detector was off.  Appends the stored units and returns the total.
+    int32_t push(const PingRecord* records, bool first, std::vector<CaptureUnit>& out)
+    {
+        hop_ = first ? 1 : hop_ + 1;
+        int32_t total = 0;
+        for(size_t c = 0; c < state_.size(); c++)
+        {
+            int32_t flags[2], half[2];
+            const int n = capture_step(state_[c], first, first || clear_, records ? records[c].up_mask : 0, listed_[c] != 0, p_.pre, p_.post, flags, half);
+            for(int i = 0; i < n; i++, total++)
+                if(total < p_.max_units) out.push_back(CaptureUnit{static_cast<int32_t>(c), flags[i], hop_ - 1 + half[i]});
+        }
+        clear_ = false;
+        return total;
+    }
+
+private:
+    CaptureParams p_;
+    std::vector<CaptureState> state_;
+    std::vector<uint8_t> listed_;
+    bool clear_ = true;
+    int64_t hop_ = 0;
+};
+
+// The file rule of --wideband-capture=DIR, once.  A channel's unit continues the channel's open segment iff its hop is the segment's
+// last hop + 1; otherwise the open segment ends and DIR/ch<c>_hop<k0>.cs8 begins.  Every write is open-append-close.  A segment
+// that ends - when the channel's next unit does not continue it, or at close() - appends one line to DIR/capture.log.  The last
+// segments of every channel are remembered, so that a ping line can name the file and the sample its event starts at.  A segment's
+// first write truncates a file of that name, while the log is only ever appended to: whoever writes a second stream into the same
+// DIR starts capture.log afresh first, as the program does, or its old lines name files whose content is no longer theirs.  Host only.
+class CaptureSegments
+{
+public:
+    CaptureSegments(const std::string& dir, const std::vector<int32_t>& offsets) : dir_(dir), offsets_(offsets), chan_(offsets.size()) {}
+
+    static std::string segment_name(int32_t channel, int64_t hop)
+    {
+        return "ch" + std::to_string(channel) + "_hop" + std::to_string(hop) + ".cs8";
+    }
+
+    // `count` units of one push and their rows data[count][5184]; false when a file could not be written
+    bool push(const CaptureUnit* units, const int8_t* data, int count)
+    {
+        for(int u = 0; u < count; u++)
+        {
+            const CaptureUnit& x = units[u];
+            Chan& ch = chan_[static_cast<size_t>(x.channel)];
+            if(ch.hops && x.hop != ch.k0 + ch.hops && !finish(x.channel)) return false;
+            if(!ch.hops)
+            {
+                ch.k0 = x.hop;
+                segments_++;
+            }
+            FILE* f = fopen((dir_ + "/" + segment_name(x.channel, ch.k0)).c_str(), ch.hops ? "ab" : "wb");
+            if(!f) return false;
+            const bool ok = fwrite(data + static_cast<size_t>(u) * kCaptureUnitBytes, 1, kCaptureUnitBytes, f) == kCaptureUnitBytes;
+            if(fclose(f) != 0 || !ok) return false;
+            ch.hops++;
+            hops_++;
+        }
+        return true;
+    }
+
+    // the end of the stream: every open segment ends, in channel order
+    bool close()
+    {
+        for(size_t c = 0; c < chan_.size(); c++)
+            if(chan_[c].hops && !finish(static_cast<int32_t>(c))) return false;
+        return true;
+    }
+
+    // What a ping line gains for an event of `channel` that starts at global block g: " file=<name> at=<sample offset of that block
+    // in the file>", or " file=-" when the hop the block lies in is in none of the channel's remembered segments (it was dropped).
+    std::string locate(int32_t channel, int64_t g) const
+    {
+        const Chan& ch = chan_[static_cast<size_t>(channel)];
+        const int64_t k = g / kCaptureHopBlocks;
+        int64_t k0 = -1;
+        if(ch.hops && k >= ch.k0 && k < ch.k0 + ch.hops) k0 = ch.k0;
+        for(int i = 0; k0 < 0 && i < kRemembered; i++)
+            if(ch.past_hops[i] && k >= ch.past_k0[i] && k < ch.past_k0[i] + ch.past_hops[i]) k0 = ch.past_k0[i];
+        if(k0 < 0) return " file=-";
+        return " file=" + segment_name(channel, k0) + " at=" + std::to_string((k - k0) * (kCaptureUnitBytes / 2) + (g % kCaptureHopBlocks) * kPingBlock);
+    }
+
+    int64_t segments() const { return segments_; }
+    int64_t hops() const { return hops_; }
+    int64_t bytes() const { return hops_ * kCaptureUnitBytes; }
+
+    // one line of DIR/capture.log; t = 0.216 k0 exact in three decimals
+    static std::string log_line(int32_t channel, int32_t offset_hz, int64_t k0, int64_t hops)
+    {
+        char buf[256];
+        const long long ms = static_cast<long long>(k0) * 216;
+        snprintf(buf, sizeof(buf), "capture ch=%d offset=%d hop=%lld t=%lld.%03lld hops=%lld file=%s", channel, offset_hz, static_cast<long long>(k0), ms / 1000, ms % 1000,
+                 static_cast<long long>(hops), segment_name(channel, k0).c_str());
+        return buf;
+    }
+
+private:
+    static constexpr int kRemembered = 4;
+    struct Chan
+    {
+        int64_t k0 = 0, hops = 0;  // the open segment; hops = 0: none
+        int64_t past_k0[kRemembered] = {0, 0, 0, 0}, past_hops[kRemembered] = {0, 0, 0, 0};
+        int next = 0;
+    };
+
+    bool finish(int32_t c)
+    {
+        Chan& ch = chan_[static_cast<size_t>(c)];
+        FILE* f = fopen((dir_ + "/capture.log").c_str(), "a");
+        if(!f) return false;
+        const bool ok = fprintf(f, "%s\n", log_line(c, offsets_[static_cast<size_t>(c)], ch.k0, ch.hops).c_str()) > 0;
+        if(fclose(f) != 0 || !ok) return false;
+        ch.past_k0[ch.next] = ch.k0;
+        ch.past_hops[ch.next] = ch.hops;
+        ch.next = (ch.next + 1) % kRemembered;
+        ch.hops = 0;
+        return true;
+    }
+
+    std::string dir_;
+    std::vector<int32_t> offsets_;
+    std::vector<Chan> chan_;
+    int64_t segments_ = 0, hops_ = 0;
+};
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {

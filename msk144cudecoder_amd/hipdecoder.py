@@ -15,6 +15,7 @@ import numpy as np
 from .protocol import ITEM_BYTES
 from .wideband import AGC_DEFAULTS, BLANKER_DEFAULTS, LEVEL_DTYPE    # the defaults of msk144_wideband_agc and _blanker; msk144_wideband_level
 from .wideband import PING_DTYPE, PING_MAX_BLOCKS, PINGS_DEFAULTS    # msk144_wideband_ping; the defaults of msk144_wideband_pings_params
+from .wideband import CAPTURE_DTYPE, CAPTURE_UNIT_BYTES, capture_default_max_units   # msk144_wideband_capture_unit
 from .wideband import WATERFALL_BINS, WATERFALL_ROWS                 # the shape of msk144_wideband_waterfall's rows
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -62,7 +63,18 @@ class WidebandPingsParams(C.Structure):
     _fields_ = [("ratio_q4", C.c_int32), ("memory", C.c_int32), ("min_ref", C.c_int32)]
 
 
+class WidebandCaptureParams(C.Structure):
+    """msk144_wideband_capture_params."""
+    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_units", C.c_int32), ("num_listed", C.c_int32), ("listed", C.c_int32 * 16)]
+
+
+class WidebandCaptureUnit(C.Structure):
+    """msk144_wideband_capture_unit; wideband.CAPTURE_DTYPE is the same record for numpy."""
+    _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("hop", C.c_int64)]
+
+
 assert C.sizeof(WidebandPing) == PING_DTYPE.itemsize == 32
+assert C.sizeof(WidebandCaptureUnit) == CAPTURE_DTYPE.itemsize == 16
 
 BLANKER_STATS = ("samples", "sum_power", "threshold", "hits", "blanked", "carry_out", "total_samples", "total_hits", "total_blanked")
 
@@ -142,6 +154,8 @@ PROTOTYPES = {
     "msk144_set_wideband_waterfall": ([_vp, _P(WidebandWaterfall)], C.c_int),
     "msk144_wideband_waterfall": ([_vp, _i32, _P(C.c_float), _P(_i32)], C.c_int),
     "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
+    "msk144_set_wideband_capture": ([_vp, _P(WidebandCaptureParams)], C.c_int),
+    "msk144_wideband_capture": ([_vp, _P(WidebandCaptureUnit), _P(C.c_int8), _P(_i32), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -558,6 +572,34 @@ class HipDecoder:
         out = np.zeros((self.channels, WATERFALL_BINS), dtype=np.float64)
         self._chk(self.L.msk144_wideband_waterfall_sums(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def set_wideband_capture(self, pre=1, post=1, max_units=None, channels=()):
+        """The per-ping capture from the next push on (include/msk144hip.h): `pre` 0 or 1 hops of pre-roll, `post` hops kept after the
+        last active one, at most `max_units` units stored per push (None: min(2 x channels, 512)), `channels` up to 16 listed channels
+        that are kept whether active or not; set_wideband_capture(None) switches it off.  Either ends the last push's units:
+        wideband_capture() raises (MSK144_ESTATE) until the next push made with capture on."""
+        if pre is None:
+            self._chk(self.L.msk144_set_wideband_capture(self.h, None))
+            return
+        listed = [int(c) for c in channels]
+        if len(listed) > 16:
+            raise ValueError("capture lists at most 16 channels")
+        n = capture_default_max_units(self.channels) if max_units is None else int(max_units)
+        p = WidebandCaptureParams(int(pre), int(post), n, len(listed), (C.c_int32 * 16)(*listed))
+        self._chk(self.L.msk144_set_wideband_capture(self.h, C.byref(p)))
+        self._capture_units = n   # what a push made from now on stores at the most; `set` ends the units of the push before it
+
+    def wideband_capture(self):
+        """(units, data, total) of the last push: CAPTURE_DTYPE [count] by channel then by hop, their int8 I/Q [count][2592][2] - the
+        bytes dump_wideband_hop returned for that hop in the push that carried it - and the number of units the push had, of which
+        total - count were dropped."""
+        cap = max(getattr(self, "_capture_units", 0), 1)
+        units = np.zeros(cap, dtype=CAPTURE_DTYPE)
+        data = np.zeros((cap, CAPTURE_UNIT_BYTES // 2, 2), dtype=np.int8)
+        count, total = C.c_int32(), C.c_int32()
+        self._chk(self.L.msk144_wideband_capture(self.h, units.ctypes.data_as(C.POINTER(WidebandCaptureUnit)), data.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(count),
+                                                 C.byref(total)))
+        return units[:count.value].copy(), data[:count.value].copy(), total.value
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

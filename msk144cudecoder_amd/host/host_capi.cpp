@@ -228,6 +228,56 @@ int msk144host_wideband_ping_spectra_close(void* s, int32_t* out, int cap)
     return static_cast<int>(f.size());
 }
 
+// "DIR[:CHANNELS[:POST[:PRE]]]" as the program parses it: out[0] = by pings, out[1] = post, out[2] = pre, out[3] = the length of
+// DIR, out[4] = listed channels, then the channels (5 + 16 = 21 values at most); -1: refused
+int msk144host_wideband_capture_parse(const char* arg, int32_t* out)
+{
+    WidebandOptions w;
+    if(!parse_wideband_capture(arg, w)) return -1;
+    out[0] = w.capture_by_pings ? 1 : 0, out[1] = w.capture_params.post, out[2] = w.capture_params.pre, out[3] = static_cast<int32_t>(w.capture_dir.size());
+    out[4] = static_cast<int32_t>(w.capture_channels.size());
+    for(size_t i = 0; i < w.capture_channels.size(); i++) out[5 + i] = w.capture_channels[i];
+    return 0;
+}
+int msk144host_wideband_capture_default_max_units(int channels) { return capture_default_max_units(static_cast<size_t>(channels)); }
+// the capture rule: nullptr for parameters msk144_set_wideband_capture refuses
+void* msk144host_wideband_capture_new(int channels, int pre, int post, int max_units, const int32_t* listed, int num_listed)
+{
+    const msk144wb::CaptureParams p{pre, post, max_units};
+    if(channels < 1 || !msk144wb::check_capture(p, listed, num_listed, channels).empty()) return nullptr;
+    return new msk144wb::Capture(channels, p, listed, num_listed);
+}
+void msk144host_wideband_capture_free(void* s) { delete static_cast<msk144wb::Capture*>(s); }
+void msk144host_wideband_capture_restart(void* s) { static_cast<msk144wb::Capture*>(s)->restart(); }
+void msk144host_wideband_capture_set_hop(void* s, int64_t hop) { static_cast<msk144wb::Capture*>(s)->set_hop(hop); }
+// records[channels] or NULL (the detector off): writes at most cap units, *count = the stored ones, and returns the total
+int msk144host_wideband_capture_push(void* s, const msk144wb::PingRecord* records, int first, msk144wb::CaptureUnit* out, int cap, int32_t* count)
+{
+    std::vector<msk144wb::CaptureUnit> u;
+    const int32_t total = static_cast<msk144wb::Capture*>(s)->push(records, first != 0, u);
+    for(int i = 0; i < static_cast<int>(u.size()) && i < cap; i++) out[i] = u[static_cast<size_t>(i)];
+    *count = static_cast<int32_t>(u.size());
+    return total;
+}
+// the file rule: offsets[channels]
+void* msk144host_wideband_capture_segments_new(const char* dir, const int32_t* offsets, int channels)
+{
+    return new msk144wb::CaptureSegments(dir, std::vector<int32_t>(offsets, offsets + channels));
+}
+void msk144host_wideband_capture_segments_free(void* s) { delete static_cast<msk144wb::CaptureSegments*>(s); }
+int msk144host_wideband_capture_segments_push(void* s, const msk144wb::CaptureUnit* units, const int8_t* data, int count)
+{
+    return static_cast<msk144wb::CaptureSegments*>(s)->push(units, data, count) ? 0 : -1;
+}
+int msk144host_wideband_capture_segments_close(void* s) { return static_cast<msk144wb::CaptureSegments*>(s)->close() ? 0 : -1; }
+// out: at least 96 bytes
+void msk144host_wideband_capture_segments_locate(void* s, int channel, int64_t block, char* out)
+{
+    const std::string f = static_cast<msk144wb::CaptureSegments*>(s)->locate(channel, block);
+    std::strncpy(out, f.c_str(), 95);
+    out[95] = 0;
+}
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

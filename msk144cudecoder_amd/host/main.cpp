@@ -12,6 +12,7 @@
 #include <poll.h>
 #include <signal.h>
 #include <sys/resource.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cerrno>
@@ -75,6 +76,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-spectrum=FILE[:BINS[:HOPS]]  With --wideband-rate: the power spectrum of the input stream at the input rate, on the GPU (of the blanked stream with --wideband-blanker): BINS-point transforms (a power of two, 256..8192, default=1024) of the hop's samples under a Hann window, summed over HOPS hops (default=5), appended to FILE as one line 'hop= rate= bins= segments= dbfs=v0,v1,...' in ascending frequency, 0 dBFS = a full-scale tone. At the end, on stderr, one line with the median bin (the floor) and the highest bin." << std::endl;
     std::cout << "                   --wideband-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]  With --wideband-rate: ping detection per channel, on the GPU, on each channel's int8 I/Q: the energy of every 8 ms block (96 samples) is compared with RATIO x the channel's quiet level (the lower quartile of a hop's blocks, the lowest of this hop and the MEMORY hops before it, 0..16; default=8). RATIO 1..4095.9, default=2. A run of at least MIN_BLOCKS (1..64, default=2) consecutive blocks above it is an event, appended to FILE when it ends as one line 'ping ch= offset= start= dur= blocks= peak= ref= peak_db='. A strong-ping detector (from about +7 dB in 2500 Hz), less sensitive than the decoder. At the end, on stderr, one line with the events and the most active channels." << std::endl;
     std::cout << "                   --wideband-waterfall=FILE[:CHANNELS]  With --wideband-rate: a waterfall per channel, on the GPU, on each channel's int8 I/Q: one 96-point spectrum (125 Hz per bin, Hann window) per 8 ms block, the blocks of --wideband-pings. CHANNELS is a list of up to 16 channel indices c0,c1,... (every block of these is written) or 'pings' (every block above the threshold of every channel; the default with --wideband-pings, without it a list is required). After every push one line per selected row is appended to FILE: 'wf ch= offset= block= t= db=v0,...,v95' in ascending frequency from -6000 Hz, 0 dB = a tone of 1 LSB, floor -100 dB. With --wideband-pings every ping line gains ' freq=<Hz>', the strongest bin of the event's blocks. At the end, on stderr, one line with the rows written and up to three channels whose spectrum summed over the run has a bin at least 10 dB (a design parameter) over the channel's median bin: a steady carrier in the passband. A display and a frequency estimate; it does not feed the decoder." << std::endl;
+    std::cout << "                   --wideband-capture=DIR[:CHANNELS[:POST[:PRE]]]  With --wideband-rate: keep each ping's channel I/Q for replay. On the GPU, after every push, the hops worth keeping are picked per channel and packed; only those bytes come to the host. CHANNELS is 'pings' (a hop is kept when the channel has a block above the threshold in it, for POST hops after that (0..16, default 1) and, with PRE = 1 (the default; 0 or 1), the one hop before it; the default with --wideband-pings, without it a list is required) or a list of up to 16 channel indices c0,c1,... that are kept whether active or not. At most min(2 x channels, 512) hops are kept per push; more are dropped and counted. Consecutive hops of a channel are appended to DIR/ch<c>_hop<k0>.cs8: int8 I/Q at 12000 samples per second, what --read-mode=2 reads. When a segment ends one line is appended to DIR/capture.log: 'capture ch= offset= hop= t= hops= file='. Every run starts capture.log afresh and overwrites segments of the same name. With --wideband-pings every ping line gains ' file=<name> at=<sample offset of the event's first block in that file>' (' file=-' when that hop was dropped). At the end, on stderr, one line with segments, hops written, bytes and dropped units." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     // clang-format on
 }
@@ -191,6 +193,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-spectrum", required_argument, 0, 0},
                                            {"wideband-pings", required_argument, 0, 0},
                                            {"wideband-waterfall", required_argument, 0, 0},
+                                           {"wideband-capture", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -244,6 +247,7 @@ int main(int argc, char* const argv[])
         case 30:
         case 31:
         case 32:
+        case 33:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -258,6 +262,7 @@ int main(int argc, char* const argv[])
             else if(idx == 30) good = parse_wideband_spectrum(optarg, wbo);
             else if(idx == 31) good = parse_wideband_pings(optarg, wbo);
             else if(idx == 32) good = parse_wideband_waterfall(optarg, wbo);
+            else if(idx == 33) good = parse_wideband_capture(optarg, wbo);
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
@@ -314,7 +319,7 @@ int main(int argc, char* const argv[])
         std::string err;
         if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
            (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)) ||
-           (wbo.waterfall && !wb_api.load_waterfall(err)))
+           (wbo.waterfall && !wb_api.load_waterfall(err)) || (wbo.capture && !wb_api.load_capture(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
             return 2;
@@ -340,6 +345,20 @@ int main(int argc, char* const argv[])
     {
         std::cerr << "--wideband-waterfall: cannot open '" << wbo.waterfall_file << "': " << strerror(errno) << std::endl;
         return 2;
+    }
+    // --wideband-capture: its directory is made if it is not there, and capture.log must be writable in it.  A run starts the log
+    // afresh: a segment's first write truncates a file of the same name that an earlier run left, so that run's lines would name
+    // files whose content is no longer theirs.
+    if(wbo.capture)
+    {
+        FILE* log = nullptr;
+        if((mkdir(wbo.capture_dir.c_str(), 0777) != 0 && errno != EEXIST) || !(log = fopen((wbo.capture_dir + "/capture.log").c_str(), "w")))
+        {
+            std::cerr << "--wideband-capture: cannot write under '" << wbo.capture_dir << "': " << strerror(errno) << std::endl;
+            return 2;
+        }
+        fclose(log);
+        wbo.capture_params.max_units = capture_default_max_units(wbo.offsets.size());
     }
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
     const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
@@ -503,6 +522,20 @@ int main(int argc, char* const argv[])
                 return 2;
             }
         }
+        if(wbo.capture)
+        {
+            msk144_wideband_capture_params cp{};
+            cp.pre = wbo.capture_params.pre;
+            cp.post = wbo.capture_params.post;
+            cp.max_units = wbo.capture_params.max_units;
+            cp.num_listed = static_cast<int32_t>(wbo.capture_channels.size());
+            std::copy(wbo.capture_channels.begin(), wbo.capture_channels.end(), cp.listed);
+            if(wb_api.set_capture(dec.handle(), &cp) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
         if(wbo.blanker)
         {
             const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
@@ -587,6 +620,7 @@ int main(int argc, char* const argv[])
         if(wbo.spectrum) loops[i]->use_wideband_spectrum(spectrum_file, wbo.spectrum_bins, wbo.spectrum_hops, wbo.rate_hz);
         if(wbo.pings) loops[i]->use_wideband_pings(pings_file, wbo.ping_min_blocks, wbo.offsets);
         if(wbo.waterfall) loops[i]->use_wideband_waterfall(waterfall_file, wbo.waterfall_by_pings, wbo.waterfall_channels, wbo.offsets, wbo.ping_min_blocks);
+        if(wbo.capture) loops[i]->use_wideband_capture(wbo.capture_dir, wbo.offsets, wbo.capture_params.max_units);
         if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
@@ -736,6 +770,12 @@ int main(int argc, char* const argv[])
                 line += buf;
             }
             std::cerr << line << std::endl;
+        }
+        if(wbo.capture)
+        {
+            const msk144wb::CaptureSegments& cs = loops[0]->wideband_capture_segments();
+            fprintf(stderr, "msk144hipdecoder: wideband capture: %lld segments, %lld hops written, %lld bytes, %lld units dropped\n", static_cast<long long>(cs.segments()),
+                    static_cast<long long>(cs.hops()), static_cast<long long>(cs.bytes()), loops[0]->wideband_capture_dropped());
         }
         if(wbo.levels)
         {

@@ -212,7 +212,11 @@ int DeviceLoop::join()
         if(wb_read_levels_) read_wideband_levels();
         if(wb_spec_file_) read_wideband_spectrum();
         if(wb_ping_file_) read_wideband_pings();
-        else if(wb_wf_file_) read_wideband_waterfall();
+        else
+        {
+            if(wb_wf_file_) read_wideband_waterfall();
+            if(wb_cap_segments_ && !read_wideband_capture()) failed = true;
+        }
         wb_components_ += wb_pending_components_;
         wb_pending_components_ = 0;
     }
@@ -222,6 +226,11 @@ int DeviceLoop::join()
         wb_ping_tracker_->close(wb_ping_events_);  // the end of the stream closes every open run
         if(wb_wf_spectra_) wb_wf_spectra_->close(wb_ping_freqs_);
         if(!write_ping_events()) failed = true;
+    }
+    if(wb_cap_segments_ && !wb_cap_segments_->close())  // ... and every open segment
+    {
+        fail("--wideband-capture: cannot write capture.log: " + std::string(strerror(errno)));
+        failed = true;
     }
     return failed ? 2 : 0;
 }
@@ -248,9 +257,15 @@ bool DeviceLoop::submit_wideband(Batch& b)
         }
         wb_clipped_ += clipped;
         wb_components_ += wb_pending_components_;
-        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ ? !read_wideband_pings() : (wb_wf_file_ && !read_wideband_waterfall())))
+        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ ? !read_wideband_pings() : ((wb_wf_file_ && !read_wideband_waterfall()) || (wb_cap_segments_ && !read_wideband_capture()))))
         {
-            fail(msk144_last_error(dec_.handle()));
+            // a reader that could not write its file has said why itself; the library's last error is then not the cause
+            bool said;
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                said = failed_;
+            }
+            if(!said) fail(msk144_last_error(dec_.handle()));
             return false;
         }
     }
@@ -315,6 +330,7 @@ bool DeviceLoop::read_wideband_pings()
     if(wb_->pings(dec_.handle(), wb_ping_buf_.data()) != MSK144_OK || wb_->ping_blocks(dec_.handle(), -1, wb_ping_energies_.data(), &nb) != MSK144_OK) return false;
     wb_ping_tracker_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_ping_energies_.data(), wb_ping_events_);
     if(wb_wf_file_ && !read_wideband_waterfall()) return false;  // the same push's rows: the frequencies of the events that closed
+    if(wb_cap_segments_ && !read_wideband_capture()) return false;  // the same push's units: the files of the events that closed
     return write_ping_events();
 }
 
@@ -332,12 +348,32 @@ bool DeviceLoop::write_ping_events()
         const msk144wb::PingEvent& e = wb_ping_events_[k];
         std::string line = msk144wb::ping_event_line(e, wb_ping_offsets_[static_cast<size_t>(e.channel)]);
         if(wb_wf_spectra_) line += " freq=" + std::to_string(wb_ping_freqs_[k]);
+        if(wb_cap_segments_) line += wb_cap_segments_->locate(e.channel, e.start);
         fprintf(wb_ping_file_, "%s\n", line.c_str());
     }
     if(!wb_ping_events_.empty()) fflush(wb_ping_file_);
     wb_ping_events_.clear();
     wb_ping_freqs_.clear();
     return true;
+}
+
+void DeviceLoop::use_wideband_capture(const std::string& dir, const std::vector<int32_t>& offsets, int max_units)
+{
+    wb_cap_segments_.reset(new msk144wb::CaptureSegments(dir, offsets));
+    wb_cap_units_.resize(static_cast<size_t>(max_units));
+    wb_cap_data_.resize(static_cast<size_t>(max_units) * msk144wb::kCaptureUnitBytes);
+}
+
+// --wideband-capture: the units of the push just made (read where its ping records are read) to their segment files
+bool DeviceLoop::read_wideband_capture()
+{
+    static_assert(sizeof(msk144_wideband_capture_unit) == sizeof(msk144wb::CaptureUnit), "the segments read msk144_wideband_capture_unit");
+    int32_t count = 0, total = 0;
+    if(wb_->capture(dec_.handle(), wb_cap_units_.data(), wb_cap_data_.data(), &count, &total) != MSK144_OK) return false;
+    wb_cap_dropped_ += total - count;
+    if(wb_cap_segments_->push(reinterpret_cast<const msk144wb::CaptureUnit*>(wb_cap_units_.data()), wb_cap_data_.data(), count)) return true;
+    fail("--wideband-capture: cannot write a segment: " + std::string(strerror(errno)));
+    return false;
 }
 
 void DeviceLoop::use_wideband_waterfall(FILE* file, bool by_pings, const std::vector<int32_t>& channels, const std::vector<int32_t>& offsets, int min_blocks)

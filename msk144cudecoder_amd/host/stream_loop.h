@@ -130,6 +130,13 @@ public:
     long long wideband_waterfall_rows() const { return wb_wf_written_; }
     std::vector<WaterfallCarrier> wideband_waterfall_carriers() const;
 
+    // --wideband-capture: msk144_wideband_capture is read once per push, where its ping records are read, and the units go to
+    // segment files under `dir` (csrc/wideband.h CaptureSegments).  With the ping detector every event line gains
+    // ` file=<name> at=<sample>` (` file=-`: the hop was dropped).  Call it after use_wideband_pings.
+    void use_wideband_capture(const std::string& dir, const std::vector<int32_t>& offsets, int max_units);
+    const msk144wb::CaptureSegments& wideband_capture_segments() const { return *wb_cap_segments_; }
+    long long wideband_capture_dropped() const { return wb_cap_dropped_; }
+
     struct SpectrumSummary
     {
         long long segments = 0;
@@ -205,6 +212,7 @@ private:
     bool read_wideband_spectrum();
     bool read_wideband_pings();
     bool read_wideband_waterfall();
+    bool read_wideband_capture();
     bool write_ping_events();
     void write_spectrum_line();
 
@@ -239,6 +247,10 @@ private:
     std::vector<double> wb_wf_sums_, wb_wf_run_;    // [channels][96]: the last push, the run
     double wb_wf_full_ = 1.0;                       // (sum w)^2 of the default window
     long long wb_wf_pushes_ = 0, wb_wf_base_ = 0, wb_wf_written_ = 0;  // pushes read, blocks of all earlier pushes, rows written
+    std::unique_ptr<msk144wb::CaptureSegments> wb_cap_segments_;
+    std::vector<msk144_wideband_capture_unit> wb_cap_units_;  // [max_units]
+    std::vector<int8_t> wb_cap_data_;                         // [max_units][5184]
+    long long wb_cap_dropped_ = 0;
     long long wb_spec_group_segments_ = 0, wb_spec_group_pushes_ = 0, wb_spec_run_segments_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;

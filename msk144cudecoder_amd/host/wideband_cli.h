@@ -97,6 +97,19 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-capture: resolved only when it is given (load_capture)
+    int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
+    int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
+
+    bool load_capture(std::string& err)
+    {
+        set_capture = reinterpret_cast<decltype(set_capture)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_capture"));
+        capture = reinterpret_cast<decltype(capture)>(dlsym(RTLD_DEFAULT, "msk144_wideband_capture"));
+        if(set_capture && capture) return true;
+        err = std::string("the loaded libmsk144hip has no capture (") + (!set_capture ? "msk144_set_wideband_capture" : "msk144_wideband_capture") + "): --wideband-capture needs it";
+        return false;
+    }
+
     bool load(std::string& err)
     {
         set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
@@ -131,6 +144,11 @@ struct WidebandOptions
     std::string waterfall_file;
     bool waterfall_by_pings = true;            // CHANNELS is `pings` (the default; needs --wideband-pings): every up block of every channel
     std::vector<int32_t> waterfall_channels;   // ... or a list of up to 16 channel indices: every block of these
+    bool capture = false;         // --wideband-capture=DIR[:CHANNELS[:POST[:PRE]]]: every kept hop of a channel appended to a segment file under DIR
+    std::string capture_dir;
+    bool capture_by_pings = true;              // CHANNELS is `pings` (the default; needs --wideband-pings): what the rule keeps around activity
+    std::vector<int32_t> capture_channels;     // ... or a list of up to 16 channel indices, kept whether active or not
+    msk144wb::CaptureParams capture_params;    // max_units is set once the channels are known: min(2 x channels, 512)
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -284,6 +302,54 @@ inline bool parse_wideband_waterfall(const std::string& s, WidebandOptions& w)
     return true;
 }
 
+// "DIR[:CHANNELS[:POST[:PRE]]]": CHANNELS `pings`, or up to 16 different channel indices c0,c1,...; POST 0..16 hops, PRE 0 or 1
+// (whether the channels exist and whether `pings` has a detector to follow needs the other options: check_wideband_options)
+inline bool parse_wideband_capture(const std::string& s, WidebandOptions& w)
+{
+    w.capture = true;
+    w.capture_by_pings = true;
+    w.capture_channels.clear();
+    w.capture_params = msk144wb::CaptureParams();
+    std::vector<std::string> f;
+    size_t a = 0;
+    while(true)
+    {
+        const size_t b = s.find(':', a);
+        f.push_back(s.substr(a, b == std::string::npos ? b : b - a));
+        if(b == std::string::npos) break;
+        a = b + 1;
+    }
+    w.capture_dir = f[0];
+    if(f[0].empty() || f.size() > 4) return false;
+    long long v = 0;
+    if(f.size() > 1 && f[1] != "pings")
+    {
+        w.capture_by_pings = false;
+        size_t p = 0;
+        while(true)
+        {
+            const size_t q = f[1].find(',', p);
+            if(!parse_int(f[1].substr(p, q == std::string::npos ? q : q - p), v) || v < 0 || v > INT32_MAX) return false;
+            if(std::find(w.capture_channels.begin(), w.capture_channels.end(), static_cast<int32_t>(v)) != w.capture_channels.end()) return false;
+            w.capture_channels.push_back(static_cast<int32_t>(v));
+            if(w.capture_channels.size() > static_cast<size_t>(msk144wb::kCaptureMaxListed)) return false;
+            if(q == std::string::npos) break;
+            p = q + 1;
+        }
+    }
+    if(f.size() > 2)
+    {
+        if(!parse_int(f[2], v) || v < 0 || v > msk144wb::kCaptureMaxPost) return false;
+        w.capture_params.post = static_cast<int32_t>(v);
+    }
+    if(f.size() > 3)
+    {
+        if(!parse_int(f[3], v) || v < 0 || v > 1) return false;
+        w.capture_params.pre = static_cast<int32_t>(v);
+    }
+    return true;
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -335,6 +401,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.pings) return "--wideband-pings needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.waterfall) return "--wideband-waterfall needs --wideband-rate=HZ";
+    if(w.rate_hz <= 0 && w.capture) return "--wideband-capture needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
@@ -351,7 +418,17 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     for(size_t i = 0; why.empty() && w.waterfall && i < w.waterfall_channels.size(); i++)
         if(static_cast<size_t>(w.waterfall_channels[i]) >= w.offsets.size())
             return "--wideband-waterfall: channel " + std::to_string(w.waterfall_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
+    if(why.empty() && w.capture && w.capture_by_pings && !w.pings) return "--wideband-capture=DIR needs a channel list (DIR:c0,c1,...) without --wideband-pings";
+    for(size_t i = 0; why.empty() && w.capture && i < w.capture_channels.size(); i++)
+        if(static_cast<size_t>(w.capture_channels[i]) >= w.offsets.size())
+            return "--wideband-capture: channel " + std::to_string(w.capture_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
     return why;
+}
+
+// the program's max_units: min(2 x channels, 512)
+inline int32_t capture_default_max_units(size_t channels)
+{
+    return static_cast<int32_t>(std::min<size_t>(2 * channels, static_cast<size_t>(msk144wb::kCaptureDefaultMaxUnits)));
 }
 
 }  // namespace msk144host

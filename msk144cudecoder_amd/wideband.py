@@ -610,6 +610,142 @@ class PingSpectra:
         return out
 
 
+# ---- per-ping capture of a channel's hops (msk144_set_wideband_capture) ----
+
+# msk144_wideband_capture_unit (include/msk144hip.h); HipDecoder.wideband_capture() returns the same records
+CAPTURE_DTYPE = np.dtype([("channel", "<i4"), ("flags", "<i4"), ("hop", "<i8")])
+assert CAPTURE_DTYPE.itemsize == 16
+CAPTURE_UNIT_BYTES = 2 * HOP_OUT     # one hop of one channel: 2592 int8 I/Q pairs
+CAPTURE_HOP_BLOCKS = HOP_OUT // PING_BLOCK   # 27
+CAPTURE_MAX_POST = 16
+CAPTURE_MAX_UNITS = 16384
+CAPTURE_MAX_LISTED = 16
+CAPTURE_ACTIVE, CAPTURE_LISTED, CAPTURE_PRE, CAPTURE_TAIL = 1, 2, 4, 8   # the bits of `flags`
+# the defaults of msk144_wideband_capture_params (csrc/wideband.h CaptureParams): design parameters, not measurements
+CAPTURE_DEFAULTS = dict(pre=1, post=1)
+
+
+def capture_default_max_units(channels: int) -> int:
+    """What the program and HipDecoder.set_wideband_capture take: min(2 x channels, 512)."""
+    return min(2 * int(channels), 512)
+
+
+class Capture:
+    """The capture rule of the contract (include/msk144hip.h) in Python integers, push by push.  Per channel: the hops since the last
+    active one (None: none that counts) and whether the newest hop was emitted.  push() takes the ping records of one push
+    (PING_DTYPE [channel], or None: the detector was off) and returns (units, total): the stored units as CAPTURE_DTYPE, by channel
+    then by hop, and the number of units the push had.  restart() stands for msk144_set_wideband_capture in mid-stream: the state is
+    cleared, the hop count stays.  `hop` is the newest hop of the last push; a model that joins a stream in mid-stream sets it."""
+
+    def __init__(self, channels: int, pre: int = 1, post: int = 1, max_units=None, listed=()):
+        max_units = capture_default_max_units(channels) if max_units is None else int(max_units)
+        listed = [int(c) for c in listed]
+        if pre not in (0, 1):
+            raise ValueError("pre must be 0 or 1")
+        if not 0 <= int(post) <= CAPTURE_MAX_POST:
+            raise ValueError("post must lie within 0..16 hops")
+        if not 1 <= max_units <= CAPTURE_MAX_UNITS:
+            raise ValueError("max_units must lie within 1..16384")
+        if len(listed) > CAPTURE_MAX_LISTED or len(set(listed)) != len(listed) or any(not 0 <= c < channels for c in listed):
+            raise ValueError("up to 16 different listed channels within the channels")
+        self.channels, self.pre, self.post, self.max_units, self.listed = int(channels), int(pre), int(post), max_units, frozenset(listed)
+        self.hop = 0
+        self.restart()
+
+    def restart(self):
+        self.since = [None] * self.channels
+        self.emitted = [False] * self.channels
+
+    def push(self, records, first: bool):
+        if first:
+            self.restart()
+        self.hop = 1 if first else self.hop + 1
+        hop_mask = (1 << CAPTURE_HOP_BLOCKS) - 1
+        units = []
+        for c in range(self.channels):
+            mask = 0 if records is None else int(records["up_mask"][c])
+            listed = c in self.listed
+            # the hops of this push and the activity of each: hops 0 and 1 of a first push, else the newest
+            hops = [(0, mask & hop_mask), (1, (mask >> CAPTURE_HOP_BLOCKS) & hop_mask)] if first else [(self.hop, mask & hop_mask)]
+            for k, active in hops:
+                if active:
+                    self.since[c] = 0
+                elif self.since[c] is not None:
+                    self.since[c] = self.since[c] + 1 if self.since[c] < CAPTURE_MAX_POST else None
+                near = self.since[c] is not None and self.since[c] <= self.post
+                if k > 0 and self.pre and active and not self.emitted[c]:
+                    units.append((c, CAPTURE_PRE, k - 1))
+                if listed or near:
+                    units.append((c, (CAPTURE_ACTIVE if active else 0) | (CAPTURE_LISTED if listed else 0) | (CAPTURE_TAIL if near and not active else 0), k))
+                self.emitted[c] = listed or near
+        return np.array(units[:self.max_units], dtype=CAPTURE_DTYPE), len(units)
+
+
+def capture_segment_name(channel: int, hop: int) -> str:
+    return f"ch{int(channel)}_hop{int(hop)}.cs8"
+
+
+def capture_log_line(channel: int, offset_hz: int, hop: int, hops: int) -> str:
+    """One line of DIR/capture.log of msk144hipdecoder --wideband-capture=DIR; t = 0.216 x hop."""
+    ms = int(hop) * 216
+    return f"capture ch={int(channel)} offset={int(offset_hz)} hop={int(hop)} t={ms // 1000}.{ms % 1000:03d} hops={int(hops)} file={capture_segment_name(channel, hop)}"
+
+
+class CaptureSegments:
+    """The file rule of --wideband-capture=DIR (csrc/wideband.h CaptureSegments): a channel's unit continues the channel's open segment
+    iff its hop is the segment's last hop + 1, otherwise the open segment ends and DIR/ch<c>_hop<k0>.cs8 begins.  Every write is
+    open-append-close.  A segment that ends - when the channel's next unit does not continue it, or at close() - appends one line to
+    DIR/capture.log.  The last four ended segments of a channel and its open one are remembered for locate().  A segment's first
+    write truncates a file of that name and the log is only appended to: the program starts capture.log afresh with every run."""
+
+    REMEMBERED = 4
+
+    def __init__(self, directory: str, offsets_hz: Sequence[int]):
+        self.dir, self.offsets = str(directory), [int(f) for f in offsets_hz]
+        self.open = {}   # channel -> [k0, hops]
+        self.past = {}   # channel -> the last ended (k0, hops), oldest first
+        self.segments = self.hops = 0
+
+    @property
+    def bytes(self) -> int:
+        return self.hops * CAPTURE_UNIT_BYTES
+
+    def _finish(self, c):
+        k0, n = self.open.pop(c)
+        with open(os.path.join(self.dir, "capture.log"), "a") as f:
+            f.write(capture_log_line(c, self.offsets[c], k0, n) + "\n")
+        self.past[c] = (self.past.get(c, []) + [(k0, n)])[-self.REMEMBERED:]
+
+    def push(self, units, data):
+        """units: CAPTURE_DTYPE [count] of one push; data: their int8 rows, [count][2592][2] or [count][5184]."""
+        data = np.ascontiguousarray(data, dtype=np.int8).reshape(len(units), CAPTURE_UNIT_BYTES)
+        for u in range(len(units)):
+            c, k = int(units["channel"][u]), int(units["hop"][u])
+            if c in self.open and k != sum(self.open[c]):
+                self._finish(c)
+            if c not in self.open:
+                self.open[c] = [k, 0]
+                self.segments += 1
+            with open(os.path.join(self.dir, capture_segment_name(c, self.open[c][0])), "ab" if self.open[c][1] else "wb") as f:
+                f.write(data[u].tobytes())
+            self.open[c][1] += 1
+            self.hops += 1
+
+    def close(self):
+        for c in sorted(self.open):
+            self._finish(c)
+
+    def locate(self, channel: int, block: int) -> str:
+        """What a ping line gains for an event of `channel` that starts at global block `block`: ' file=<name> at=<sample offset of
+        that block in the file>', or ' file=-' when the hop it lies in is in none of the remembered segments."""
+        k = int(block) // CAPTURE_HOP_BLOCKS
+        spans = ([tuple(self.open[channel])] if channel in self.open else []) + self.past.get(channel, [])
+        for k0, n in spans:
+            if k0 <= k < k0 + n:
+                return f" file={capture_segment_name(channel, k0)} at={(k - k0) * HOP_OUT + int(block) % CAPTURE_HOP_BLOCKS * PING_BLOCK}"
+        return " file=-"
+
+
 class Channeliser:
     """The contract, push by push: keeps the history input samples and the output index m like the device does.
 

@@ -13,13 +13,16 @@ channeliser; spectrum_bytes is the push they read once.  --pings: the ping detec
 defaults), so the time includes its kernel behind the channeliser; pings_bytes is the staged hops it reads once.  --waterfall: the
 per-channel waterfall is on (msk144_set_wideband_waterfall, the default window), so the time includes its two kernels behind the
 channeliser; waterfall_mfma is the f32 MFMA instructions of a push (576 per channel) and waterfall_bytes the rows it writes.
+--capture: the capture is on (msk144_set_wideband_capture with the defaults) with every 8th channel listed, up to the 16 the list
+holds, so that the units are non-trivial without a detector; the time includes its two kernels behind the hop ring, capture_units is
+the units of a push and capture_bytes what the copy kernel moves for them.
 
 Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --program-rate, default 1.92 Msps, the program's
 default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
 samples at 12 kHz).
 
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
-                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--waterfall]
+                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--waterfall] [--capture]
 """
 from __future__ import annotations
 
@@ -42,7 +45,8 @@ from msk144cudecoder_amd import hipdecoder, wideband  # noqa: E402
 FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
 
-def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False, waterfall: bool = False) -> dict:
+def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False, waterfall: bool = False,
+            capture: bool = False) -> dict:
     D = rate // 12000
     rng = np.random.default_rng(C + D)
     g = math.gcd(rate, 12000)
@@ -61,6 +65,9 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
             d.set_wideband_pings()
         if waterfall:
             d.set_wideband_waterfall()
+        listed = list(range(0, C, 8))[:wideband.CAPTURE_MAX_LISTED]
+        if capture:
+            d.set_wideband_capture(channels=listed)
         for s in range(2):
             d.wideband_slot(s)[:] = rng.integers(120, 136, size=d.wideband_slot(s).size, dtype=np.uint8)
         d.push_wideband(0, first=True)
@@ -104,6 +111,10 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
         ratio["waterfall"] = True
         ratio["waterfall_mfma"] = C * 576               # 3 waves x 96 steps x 2 per channel and hop
         ratio["waterfall_bytes"] = C * 27 * 96 * 4      # the rows of a hop, written once
+    if capture:
+        ratio["capture"] = True
+        ratio["capture_units"] = len(listed)
+        ratio["capture_bytes"] = len(listed) * wideband.CAPTURE_UNIT_BYTES
     return dict(channels=C, **ratio, K=K, agc=agc, blanker=blanker, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
                 channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
                 tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
@@ -152,11 +163,12 @@ def main():
     ap.add_argument("--spectrum", type=int, nargs="?", const=1024, default=0, metavar="BINS", help="measure with the input spectrum on (BINS default 1024)")
     ap.add_argument("--pings", action="store_true", help="measure with the ping detector on")
     ap.add_argument("--waterfall", action="store_true", help="measure with the per-channel waterfall on")
+    ap.add_argument("--capture", action="store_true", help="measure with the capture on, every 8th channel (up to 16) listed")
     a = ap.parse_args()
     rates = [int(v) * 12000 for v in a.decimations.split(",") if v] + [int(v) for v in a.rates.split(",") if v]
     for C in [int(v) for v in a.channels.split(",")]:
         for rate in rates:
-            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall)), flush=True)
+            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall, capture=a.capture)), flush=True)
     if a.program_hops:
         print(json.dumps(program_run(a.program_hops, rate=a.program_rate)), flush=True)
 
