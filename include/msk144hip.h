@@ -567,7 +567,8 @@ int msk144_wideband_spectrum(msk144_handle* h, double* power /*[bins]*/, int64_t
  *               1 + 10^(S/10) . 2500/12000, so the defaults see pings from roughly +7 dB up.  In a CPU simulation of the model (no
  *               GPU measurement stands behind these figures) white int8 noise at 3 and at 20 LSB rms, 1.66 M blocks each with memory
  *               8, put 0 blocks up at ratio 2.0, 2-3 at 1.75 and about 2600 at 1.5; in a 240 ksps scene with noise at about 20 LSB rms
- *               every block wholly inside a +10 dB ping was up, most at +7 dB, almost none at +4 dB.
+ *               every block wholly inside a +10 dB ping was up, most at +7 dB, almost none at +4 dB.  The ping band below
+ *               (msk144_set_wideband_ping_band) compares in-band energy instead and sees pings some 2.5 to 3 dB weaker.
  *   Events:     the program (and wideband.PingEvents) joins up blocks into events: with g = (blocks of all earlier pushes) + b, an
  *               event is a maximal run of consecutive up blocks in g; a run that reaches a push's last block stays open into the
  *               next push, a history restart does not close it, the end of the stream does (csrc/wideband.h PingTracker).
@@ -605,6 +606,62 @@ int msk144_wideband_pings(msk144_handle* h, msk144_wideband_ping* out);
 /* test and debug, like msk144_dump_wideband_hop: E of the channel's last push in energies[0 .. *n), energies[54]; the rest is 0.
  * channel = -1: every channel's, energies[channels][54] (what the program's event log reads, in one copy) */
 int msk144_wideband_ping_blocks(msk144_handle* h, int32_t channel, int32_t* energies, int32_t* n);
+
+/* ---- The ping band: an in-band filter ahead of the ping detector's block energies (no reference counterpart) ----
+ *
+ * E above is the energy of a whole 12 kHz channel; an MSK144 signal fills about 2.4 kHz of it.  With the band on, a 64-tap complex
+ * band-pass runs on the stored int8 values ahead of the block energies, and the detector - quiet level, reference, up mask, peak -
+ * runs unchanged on the in-band energies Ef.  Exact integer arithmetic throughout (csrc/pingband.hip; the same rule on the host is
+ * csrc/wideband.h ping_band_energies).  Per channel, with x[n] = I + jQ the stored int8 values as integers:
+ *
+ *   Taps:       64 complex int8 taps b[k] = (br[k], bi[k]), k = 0..63; any int8 values are valid, a shorter filter is zero-padded.
+ *   Filter:     z[n] = sum over k < 64 of b[k] . x[n - k], a complex integer product; |Re z| and |Im z| are at most
+ *               128 . 64 . 2 . 128 = 2^21, so int32 is exact.
+ *   Tail:       x[n - k] reaches into the channel's previous 63 stored samples, which the filter keeps per channel on the device.
+ *               The tail is all zero whenever the ping history restarts by order of the library: at a first push, and at the first
+ *               push after msk144_set_wideband_pings or msk144_set_wideband_ping_band.  A change of quantiser scale (an AGC step, new
+ *               gains) restarts the reference history but not the tail: it holds the stored values as they are.  The tail advances
+ *               only on pushes made with the detector and the band both on.
+ *   Energy:     Ef[b] = min((sum over samples 96b .. 96b + 95 of Re z^2 + Im z^2) >> shift, 2^22 - 1), 0 <= shift <= 40.  The sum is
+ *               below 2^50; the clamp keeps Ef inside the 22 bits of E.
+ *   Use:        with the band on, Ef stands for E everywhere in the ping contract above: msk144_wideband_ping_blocks returns Ef,
+ *               msk144_wideband_ping keeps its layout (quiet, reference and peak are then in-band), the events, the frequency of a
+ *               ping, the waterfall's `pings` mode and the capture follow the same up masks.
+ *   Default design (msk144host_wideband_ping_band_design in libmsk144host.so, csrc/wideband.h ping_band_design; the program and the
+ *               Python side both take it from there): integer centre_hz and 500 <= halfwidth_hz <= 3000 with
+ *               |centre_hz| + halfwidth_hz <= 6000.  In double: a Hamming-windowed sinc low-pass with cutoff halfwidth_hz centred on
+ *               k = 31.5, turned by e^{+j 2 pi centre (k - 31.5) / 12000}, scaled so that the largest |component| is 127, rounded
+ *               with rint.  shift = rint(log2 |B(centre)|^2), B the response of the rounded taps, so that a signal inside the band
+ *               comes out near the level it went in with and min_ref keeps its meaning.
+ *   Ratio:      Ef has about a quarter of E's degrees of freedom per block, so noise alone swings it further and the ratio must rise
+ *               with the band on.  In a CPU simulation of the model (tools/pingband_sim.py; no GPU measurement stands behind these
+ *               figures), set up as the one above - white int8 noise at 3 and at 20 LSB rms, 1.66 M blocks each, memory 8 - and with
+ *               the default band, the blocks up were 14375 and 13813 at ratio 2.0, 232 and 206 at 2.5, 17 and 18 at 2.75, 2 and 0 at
+ *               3.0, 0 and 0 at 3.25 and above.  MSK144_PING_BAND_RATIO_Q4 = 52, ratio 3.25, the smallest multiple of 0.25 with no
+ *               block up in either, is the default the program uses with the band on.
+ *   Sensitivity: CPU simulation again, the 240 ksps scene of the ping detector's paragraph with synthesised MSK144 pings through the
+ *               float64 channeliser model, eight seeds, 552 blocks wholly inside a ping.  Share of them up, whole channel at ratio
+ *               2.0 / default band at 3.25: +10 dB 100 / 100 %, +7 dB 86.1 / 100 %, +4 dB 2.2 / 74.1 %, +2 dB 0 / 14.1 %, 0 dB 0 / 1.1 %
+ *               (+6 dB 42.9 / 99.8 %, +5 dB 12.9 / 94.9 %, +3 dB 0 / 37.9 %); no block away from a ping was up in either.  Half the
+ *               blocks are up at about +6.2 dB without and +3.4 dB with the band: a gain of 2.5 to 3 dB, less than the 6 dB of the
+ *               bandwidth ratio because of the higher ratio.
+ *   Order:      msk144_set_wideband_ping_band(h, &p) takes effect from the next push, allocates everything it needs - a push
+ *               allocates nothing - and restarts the ping history; (h, NULL) switches the band off, likewise from the next push and
+ *               with a restart, as msk144_set_wideband does.  It is valid in wideband mode whether or not the detector is on and acts
+ *               only on pushes made with the detector on; msk144_set_wideband_pings(h, NULL) leaves it configured.  No atomics: the
+ *               same stream pushed twice gives the same bytes.  Whether the band is on or off, every hop, clip count, level, AGC
+ *               step, blanker statistic, spectrum, waterfall row of a listed channel and decode is byte for byte the same.
+ *   Refused:    MSK144_EINVAL outside wideband mode and for shift outside 0..40. */
+typedef struct msk144_wideband_ping_band_params
+{
+    int8_t taps[64][2]; /* (br, bi) of b[0] .. b[63] */
+    int32_t shift;
+} msk144_wideband_ping_band_params;
+
+#define MSK144_PING_BAND_RATIO_Q4 52
+
+/* NULL: off */
+int msk144_set_wideband_ping_band(msk144_handle* h, const msk144_wideband_ping_band_params* p);
 
 /* ---- Per-channel waterfall (no reference counterpart) ----
  *

@@ -33,6 +33,7 @@ SOURCES = [
     ("pings.hip", []),
     ("waterfall.hip", []),
     ("capture.hip", []),
+    ("pingband.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]

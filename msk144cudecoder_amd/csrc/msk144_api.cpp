@@ -174,6 +174,11 @@ struct msk144_handle
         msk144wb::PingHistory* d_ping_state = nullptr;   // [channels]
         msk144wb::PingRecord* d_ping_records = nullptr;  // [channels]
         int32_t* d_ping_energies = nullptr;              // [channels][54]
+        // the ping band (msk144_set_wideband_ping_band): applies from the next push made with the detector on; `set` allocates
+        bool ping_band = false;
+        int32_t ping_band_shift = 0;
+        int8_t* d_ping_band_taps = nullptr;    // [64][2]
+        uint8_t* d_ping_band_tails = nullptr;  // [channels][128]: two zero bytes, then the 63 stored samples before the next push
         // per-channel waterfall (msk144_set_wideband_waterfall): applies from the next push; `set` allocates.  waterfall_pushed: the
         // last push left rows and sums
         bool waterfall = false, waterfall_pushed = false;
@@ -1544,8 +1549,11 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
         launch_agc_step(w.d_levels, w.bank ? w.d_slot_channel : nullptr, w.d_gains, w.d_exp, w.d_quiet, w.d_used_exp, w.d_scale, w.slots, M, w.agc_params, h->stream);
     if(w.pings)
     {
+        if(w.ping_band)
+            launch_pingband(reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), first ? 1 : 0, C, w.d_ping_band_taps, w.ping_band_shift,
+                            first || w.ping_restart ? 1 : 0, w.d_ping_band_tails, w.d_ping_energies, h->stream);
         launch_pings(reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), first ? 1 : 0, C, w.d_gains, w.agc ? w.d_used_exp : nullptr, w.ping_params,
-                     first || w.ping_restart ? 1 : 0, w.d_ping_state, w.d_ping_records, w.d_ping_energies, h->stream);
+                     first || w.ping_restart ? 1 : 0, w.d_ping_state, w.d_ping_records, w.d_ping_energies, w.ping_band, h->stream);
         w.ping_restart = false;
     }
     w.ping_pushed = w.pings;
@@ -1786,6 +1794,34 @@ int msk144_set_wideband_pings(msk144_handle* h, const msk144_wideband_pings_para
     HIP_TRY(h, hipMemset(w.d_ping_state, 0, sizeof(msk144wb::PingHistory) * C));
     w.ping_params = pp;
     w.pings = true;
+    w.ping_restart = true;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_ping_band(msk144_handle* h, const msk144_wideband_ping_band_params* p)
+{
+    int rc = wb_quiesce(h, "msk144_set_wideband_ping_band");
+    if(rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    static_assert(sizeof(msk144_wideband_ping_band_params) == sizeof(msk144wb::PingBandParams) && offsetof(msk144_wideband_ping_band_params, shift) == offsetof(msk144wb::PingBandParams, shift),
+                  "msk144wb::PingBandParams is msk144_wideband_ping_band_params");
+    if(p)
+    {
+        msk144wb::PingBandParams bp;
+        std::memcpy(&bp, p, sizeof(bp));
+        const std::string why = msk144wb::check_ping_band(bp);
+        if(!why.empty()) return fail(h, MSK144_EINVAL, why);
+        // never in a push; the energies are the detector's, whichever `set` comes first
+        const size_t C = w.gains.size();
+        if(!w.d_ping_band_taps && (rc = dev_alloc(h, w.mem, &w.d_ping_band_taps, sizeof(bp.taps))) != MSK144_OK) return rc;
+        if(!w.d_ping_band_tails && (rc = dev_alloc(h, w.mem, &w.d_ping_band_tails, C * 2 * msk144wb::kPingBandTaps)) != MSK144_OK) return rc;
+        if(!w.d_ping_energies && (rc = dev_alloc(h, w.mem, &w.d_ping_energies, C * msk144wb::kPingMaxBlocks)) != MSK144_OK) return rc;
+        HIP_TRY(h, hipMemcpy(w.d_ping_band_taps, bp.taps, sizeof(bp.taps), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemset(w.d_ping_band_tails, 0, C * 2 * msk144wb::kPingBandTaps));
+        w.ping_band_shift = bp.shift;
+    }
+    w.ping_band = p != nullptr;
+    // E and Ef do not share a history: the next push with the detector on restarts it, and finds the tail all zero
     w.ping_restart = true;
     return MSK144_OK;
 }

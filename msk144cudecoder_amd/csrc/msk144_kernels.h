@@ -117,9 +117,17 @@ void launch_agc_step(const unsigned long long* levels, const int32_t* slot_chann
 // first_halves and hops are the hop ring's staging, [channels][5184] bytes each (with first != 0 a channel's push is its row of
 // first_halves followed by its row of hops).  gains[channels] and used_exps[channels] (NULL without the AGC: exponent 0) give the
 // scale each channel's push was quantised with; restart != 0 restarts every channel's history.  Writes records[channels] and
-// energies[channels][54] (0 past the push's blocks) and moves state[channels].
+// energies[channels][54] (0 past the push's blocks) and moves state[channels].  band: the push's energies are taken from `energies`
+// as launch_pingband left them, not summed from the hops.
 void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float* gains, const int32_t* used_exps, const msk144wb::PingParams& p,
-                  int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, hipStream_t stream);
+                  int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, bool band, hipStream_t stream);
+
+// the ping band of a push (pingband.hip; contract in include/msk144hip.h), ahead of launch_pings on the same stream and on the same
+// staged hops: taps[64][2] int8 on the device; tails[channels][128] bytes, a channel's 63 stored samples before the push behind two
+// zero bytes, read unless restart != 0 (then all zero) and moved on to the push's last 63.  Writes energies[channels][b] for the
+// push's blocks, 27 or with first != 0 54.
+void launch_pingband(const int8_t* first_halves, const int8_t* hops, int first, int channels, const int8_t* taps, int shift, int restart, uint8_t* tails, int32_t* energies,
+                     hipStream_t stream);
 
 // the per-channel waterfall of a push (waterfall.hip; contract in include/msk144hip.h), on the staged hops like launch_pings:
 // dft[t][i][c] = w[i] e^{-j2pi i k/96} of slot j = 32 t + c, k = (j - 48) mod 96, f32 (kWaterfallDftSize values).  Writes

@@ -10,6 +10,9 @@
 //   up mask       one ballot of msk144wb::ping_up;
 //   peak          one wave max (wave64.h) of (E << 6) | (63 - b): the largest E, and the lowest b that has it.
 //
+// With the ping band on (msk144_set_wideband_ping_band) pingband.hip has left the in-band energies Ef of the push in the debug array,
+// and the second instantiation of the kernel takes its E from there instead of the hops; everything behind that is the same code.
+//
 // Lane 0 then moves the history (msk144wb::ping_history_put) and writes the record; every lane writes its E (0 past nb) to the
 // channel's row of the debug array.  No atomics and no order between waves: the same hops give the same bytes.
 //
@@ -49,7 +52,10 @@ __device__ __forceinline__ int32_t dot4_sq(uint32_t a, int32_t acc)
 #endif
 }
 
-// first_halves, hops: [channels][5184] bytes, the hop ring's staging; records[channels]; energies[channels][54]; state[channels]
+// first_halves, hops: [channels][5184] bytes, the hop ring's staging; records[channels]; energies[channels][54]; state[channels].
+// kBand: the energies of the push are already in `energies` (pingband.hip wrote the in-band Ef there, ahead on the same stream) and
+// the hops are not read; every other step is the same code.
+template<bool kBand>
 __global__ __launch_bounds__(kWaves * 64) void pings_kernel(const int8_t* __restrict__ first_halves, const int8_t* __restrict__ hops, int first, int channels,
                                                             const float* __restrict__ gains, const int32_t* __restrict__ used_exps, msk144wb::PingParams p, int restart,
                                                             msk144wb::PingHistory* __restrict__ state, msk144wb::PingRecord* __restrict__ records,
@@ -61,7 +67,11 @@ __global__ __launch_bounds__(kWaves * 64) void pings_kernel(const int8_t* __rest
     const int nb = first ? 2 * kHopBlocks : kHopBlocks;
 
     int32_t E = 0;
-    if(lane < nb)
+    if constexpr(kBand)
+    {
+        if(lane < nb) E = energies[static_cast<size_t>(ch) * msk144wb::kPingMaxBlocks + lane];
+    }
+    else if(lane < nb)
     {
         const bool head = first && lane < kHopBlocks;
         const int8_t* row = (head ? first_halves : hops) + static_cast<size_t>(ch) * kRowBytes;
@@ -124,9 +134,9 @@ __global__ __launch_bounds__(kWaves * 64) void pings_kernel(const int8_t* __rest
 }  // namespace
 
 void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float* gains, const int32_t* used_exps, const msk144wb::PingParams& p,
-                  int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, hipStream_t stream)
+                  int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, bool band, hipStream_t stream)
 {
-    hipLaunchKernelGGL(pings_kernel, dim3((channels + kWaves - 1) / kWaves), dim3(kWaves * 64), 0, stream, first_halves, hops, first, channels, gains, used_exps, p, restart,
+    hipLaunchKernelGGL(band ? pings_kernel<true> : pings_kernel<false>, dim3((channels + kWaves - 1) / kWaves), dim3(kWaves * 64), 0, stream, first_halves, hops, first, channels, gains, used_exps, p, restart,
                        state, records, energies);
 }
 

@@ -368,6 +368,112 @@ inline PingRecord ping_record(const PingParams& p, PingHistory& s, bool restart,
     return r;
 }
 
+// ---- the ping band: an in-band filter ahead of the block energies (msk144_set_wideband_ping_band) ----
+
+constexpr int kPingBandTaps = 64;
+constexpr int kPingBandTail = kPingBandTaps - 1;   // stored samples a channel keeps between pushes
+constexpr int kPingBandMaxShift = 40;
+constexpr int32_t kPingBandMaxEnergy = (1 << kPingEnergyBits) - 1;
+constexpr int kPingBandMinHalfwidthHz = 500;
+constexpr int kPingBandMaxHalfwidthHz = 3000;
+constexpr int kPingBandDefaultHalfwidthHz = 1500;
+// The detector's default ratio with the default band on, in sixteenths: the smallest multiple of 0.25 with no noise block up in
+// the CPU simulation that include/msk144hip.h tabulates
+constexpr int kPingBandDefaultRatioQ4 = 52;
+
+// msk144_wideband_ping_band_params, field for field
+struct PingBandParams
+{
+    int8_t taps[kPingBandTaps][2];
+    int32_t shift;
+};
+static_assert(sizeof(PingBandParams) == 132, "msk144_wideband_ping_band_params is 132 bytes");
+
+// The rules of msk144_set_wideband_ping_band that need no handle: any int8 taps.  Empty string = valid.
+inline std::string check_ping_band(const PingBandParams& p)
+{
+    if(p.shift < 0 || p.shift > kPingBandMaxShift) return "ping band shift must lie within 0..40";
+    return std::string();
+}
+
+// The rules of the default design.  Empty string = valid.
+inline std::string check_ping_band_design(int centre_hz, int halfwidth_hz)
+{
+    if(halfwidth_hz < kPingBandMinHalfwidthHz || halfwidth_hz > kPingBandMaxHalfwidthHz) return "ping band half-width must lie within 500..3000 Hz";
+    if(std::abs(static_cast<long long>(centre_hz)) + halfwidth_hz > kOutRate / 2) return "ping band must lie within +-6000 Hz: |centre| + half-width <= 6000";
+    return std::string();
+}
+
+// |B(f)|^2 of the integer taps, B(f) = sum b[k] e^{-j 2 pi f k / 12000}
+inline double ping_band_response(const PingBandParams& p, double f_hz)
+{
+    double re = 0.0, im = 0.0;
+    for(int k = 0; k < kPingBandTaps; k++)
+    {
+        const double a = -2.0 * M_PI * f_hz * k / kOutRate, c = std::cos(a), s = std::sin(a);
+        re += p.taps[k][0] * c - p.taps[k][1] * s;
+        im += p.taps[k][0] * s + p.taps[k][1] * c;
+    }
+    return re * re + im * im;
+}
+
+// The default design, in double: a Hamming-windowed sinc low-pass with cutoff halfwidth_hz centred on k = 31.5, turned to centre_hz,
+// scaled so that the largest |component| is 127 and rounded; shift = rint(log2 |B(centre)|^2) of the rounded taps, so that a signal
+// inside the band comes out at about the level it went in with.  The caller has checked the arguments.
+inline PingBandParams ping_band_design(int centre_hz, int halfwidth_hz)
+{
+    double re[kPingBandTaps], im[kPingBandTaps], top = 0.0;
+    for(int k = 0; k < kPingBandTaps; k++)
+    {
+        const double t = k - 0.5 * (kPingBandTaps - 1);
+        const double arg = 2.0 * halfwidth_hz * t / kOutRate;
+        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
+        const double h = sinc * (0.54 - 0.46 * std::cos(2.0 * M_PI * k / (kPingBandTaps - 1)));
+        const double a = 2.0 * M_PI * centre_hz * t / kOutRate;
+        re[k] = h * std::cos(a);
+        im[k] = h * std::sin(a);
+        top = std::max(top, std::max(std::fabs(re[k]), std::fabs(im[k])));
+    }
+    PingBandParams p{};
+    for(int k = 0; k < kPingBandTaps; k++)
+    {
+        p.taps[k][0] = static_cast<int8_t>(std::rint(re[k] * 127.0 / top));
+        p.taps[k][1] = static_cast<int8_t>(std::rint(im[k] * 127.0 / top));
+    }
+    p.shift = static_cast<int32_t>(std::rint(std::log2(ping_band_response(p, centre_hz))));
+    return p;
+}
+
+// The filter and its energies on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push (n a multiple
+// of 96), tail[63][2] the channel's 63 stored samples before them, oldest first (all zero where the ping kernel restarts); writes
+// Ef[n / 96] and moves the tail on to the last 63 samples of x.  z[m] = sum_k b[k] x[m - k] in int32 (|Re z|, |Im z| <= 2^21),
+// Ef[b] = min((sum over the block of Re z^2 + Im z^2) >> shift, 2^22 - 1) in 64 bits.  What libmsk144host.so holds the Python model
+// and the kernel (pingband.hip) to.
+inline void ping_band_energies(const PingBandParams& p, const int8_t* x, int n, int8_t* tail, int32_t* Ef)
+{
+    std::vector<int8_t> s(static_cast<size_t>(2 * (kPingBandTail + n)));
+    std::memcpy(s.data(), tail, 2 * kPingBandTail);
+    std::memcpy(s.data() + 2 * kPingBandTail, x, static_cast<size_t>(2 * n));
+    for(int b = 0; b < n / kPingBlock; b++)
+    {
+        uint64_t sum = 0;
+        for(int m = b * kPingBlock; m < (b + 1) * kPingBlock; m++)
+        {
+            int32_t zr = 0, zi = 0;
+            for(int k = 0; k < kPingBandTaps; k++)
+            {
+                const int32_t xr = s[static_cast<size_t>(2 * (kPingBandTail + m - k))], xi = s[static_cast<size_t>(2 * (kPingBandTail + m - k) + 1)];
+                zr += p.taps[k][0] * xr - p.taps[k][1] * xi;
+                zi += p.taps[k][0] * xi + p.taps[k][1] * xr;
+            }
+            sum += static_cast<uint64_t>(static_cast<int64_t>(zr) * zr) + static_cast<uint64_t>(static_cast<int64_t>(zi) * zi);
+        }
+        sum >>= p.shift;
+        Ef[b] = sum > static_cast<uint64_t>(kPingBandMaxEnergy) ? kPingBandMaxEnergy : static_cast<int32_t>(sum);
+    }
+    std::memcpy(tail, s.data() + static_cast<size_t>(2 * n), 2 * kPingBandTail);
+}
+
 // An event: a maximal run of consecutive up blocks of one channel in g = (blocks of all earlier pushes) + b
 struct PingEvent
 {

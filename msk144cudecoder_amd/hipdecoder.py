@@ -63,6 +63,11 @@ class WidebandPingsParams(C.Structure):
     _fields_ = [("ratio_q4", C.c_int32), ("memory", C.c_int32), ("min_ref", C.c_int32)]
 
 
+class WidebandPingBandParams(C.Structure):
+    """msk144_wideband_ping_band_params."""
+    _fields_ = [("taps", (C.c_int8 * 2) * 64), ("shift", C.c_int32)]
+
+
 class WidebandCaptureParams(C.Structure):
     """msk144_wideband_capture_params."""
     _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_units", C.c_int32), ("num_listed", C.c_int32), ("listed", C.c_int32 * 16)]
@@ -151,6 +156,7 @@ PROTOTYPES = {
     "msk144_set_wideband_pings": ([_vp, _P(WidebandPingsParams)], C.c_int),
     "msk144_wideband_pings": ([_vp, _P(WidebandPing)], C.c_int),
     "msk144_wideband_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
+    "msk144_set_wideband_ping_band": ([_vp, _P(WidebandPingBandParams)], C.c_int),
     "msk144_set_wideband_waterfall": ([_vp, _P(WidebandWaterfall)], C.c_int),
     "msk144_wideband_waterfall": ([_vp, _i32, _P(C.c_float), _P(_i32)], C.c_int),
     "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
@@ -532,6 +538,30 @@ class HipDecoder:
         p.update(kw)
         a = WidebandPingsParams(**{k: int(v) for k, v in p.items()})
         self._chk(self.L.msk144_set_wideband_pings(self.h, C.byref(a)))
+
+    def set_wideband_ping_band(self, centre_hz=0, halfwidth_hz: int = 1500, taps=None, shift: Optional[int] = None):
+        """The ping band from the next push on (include/msk144hip.h): the detector then runs on in-band energies.
+        set_wideband_ping_band() takes the default design around centre_hz +- halfwidth_hz (wideband.ping_band_taps);
+        taps (int8 [k][2], k <= 64) and shift give a filter of one's own; set_wideband_ping_band(None) switches it off."""
+        if centre_hz is None:
+            self._chk(self.L.msk144_set_wideband_ping_band(self.h, None))
+            return
+        if taps is None:
+            from .wideband import ping_band_taps
+            t, s = ping_band_taps(centre_hz, halfwidth_hz)
+            shift = s if shift is None else shift
+        else:
+            if shift is None:
+                raise ValueError("taps need a shift")
+            t = np.asarray(taps)
+            if t.ndim != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= 64 or np.any(t != t.astype(np.int8)):
+                raise ValueError("taps must be int8 [k][2] with 1 <= k <= 64")
+        a = WidebandPingBandParams()
+        full = np.zeros((64, 2), dtype=np.int8)
+        full[:t.shape[0]] = t
+        C.memmove(a.taps, full.ctypes.data, full.nbytes)
+        a.shift = int(shift)
+        self._chk(self.L.msk144_set_wideband_ping_band(self.h, C.byref(a)))
 
     def wideband_pings(self) -> np.ndarray:
         """PING_DTYPE [channels]: up mask, blocks, history, quiet level, reference, peak and peak block of the last push."""

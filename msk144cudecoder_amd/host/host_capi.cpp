@@ -175,6 +175,48 @@ int msk144host_wideband_pings_parse(const char* arg, int32_t* out4)
     return 0;
 }
 
+// ---- the ping band (csrc/wideband.h: the default design, the check, the filter and its energies) ----
+
+// The default design of msk144_set_wideband_ping_band: taps[64][2] int8 and the shift; -1 with the refusal text for a band the design
+// does not take.  The taps the program and msk144cudecoder_amd.wideband.ping_band_taps hand to the library.
+int msk144host_wideband_ping_band_design(int32_t centre_hz, int32_t halfwidth_hz, int8_t* taps, int32_t* shift, char* why, int why_len)
+{
+    const std::string s = msk144wb::check_ping_band_design(centre_hz, halfwidth_hz);
+    if(!s.empty()) return copy_why(s, why, why_len);
+    const msk144wb::PingBandParams p = msk144wb::ping_band_design(centre_hz, halfwidth_hz);
+    std::memcpy(taps, p.taps, sizeof(p.taps));
+    *shift = p.shift;
+    return copy_why(s, why, why_len);
+}
+// 0 when msk144_set_wideband_ping_band takes the shift (any int8 taps are valid), else -1 with the refusal text
+int msk144host_wideband_ping_band_check(int32_t shift, char* why, int why_len)
+{
+    msk144wb::PingBandParams p{};
+    p.shift = shift;
+    return copy_why(msk144wb::check_ping_band(p), why, why_len);
+}
+// One push of `channels` channels: x[channels][n][2] stored int8 samples (n a multiple of 96), tails[channels][63][2] in and out,
+// Ef[channels][n / 96].  -1 for a shift or an n out of range.
+int msk144host_wideband_ping_band_energies(const int8_t* taps, int32_t shift, int channels, const int8_t* x, int n, int8_t* tails, int32_t* Ef)
+{
+    msk144wb::PingBandParams p{};
+    std::memcpy(p.taps, taps, sizeof(p.taps));
+    p.shift = shift;
+    if(!msk144wb::check_ping_band(p).empty() || channels < 1 || n < 0 || n % msk144wb::kPingBlock != 0) return -1;
+    for(int c = 0; c < channels; c++)
+        msk144wb::ping_band_energies(p, x + static_cast<size_t>(c) * 2 * n, n, tails + static_cast<size_t>(c) * 2 * msk144wb::kPingBandTail, Ef + static_cast<size_t>(c) * (n / msk144wb::kPingBlock));
+    return 0;
+}
+// "[HALFWIDTH[:CENTRE]]" as the program parses the value of --wideband-pings-band (centre_default: --center-frequency): 0 and
+// out2 = {halfwidth, centre}, else -1
+int msk144host_wideband_ping_band_parse(const char* arg, int32_t centre_default, int32_t* out2)
+{
+    WidebandOptions w;
+    if(!parse_wideband_ping_band(arg, centre_default, w)) return -1;
+    out2[0] = w.ping_band_halfwidth, out2[1] = w.ping_band_centre;
+    return 0;
+}
+
 // ---- the per-channel waterfall (csrc/wideband.h: the window, the check, the dB scale, the line, the frequency rule of a ping event) ----
 
 // the default window of msk144_set_wideband_waterfall (periodic Hann) in out[96]; returns 96

@@ -75,6 +75,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-blanker[=RATIO[:PRE[:POST]]]  With --wideband-rate: impulse-noise blanker on the input stream, on the GPU, ahead of the channel filters: a sample whose power exceeds RATIO x the mean power of its hop is zeroed together with PRE samples before and POST after it (0..4096 each). RATIO 1..4095.9, default=16; PRE default=2, POST default=8. At the end, on stderr, one line with the hits and the blanked samples." << std::endl;
     std::cout << "                   --wideband-spectrum=FILE[:BINS[:HOPS]]  With --wideband-rate: the power spectrum of the input stream at the input rate, on the GPU (of the blanked stream with --wideband-blanker): BINS-point transforms (a power of two, 256..8192, default=1024) of the hop's samples under a Hann window, summed over HOPS hops (default=5), appended to FILE as one line 'hop= rate= bins= segments= dbfs=v0,v1,...' in ascending frequency, 0 dBFS = a full-scale tone. At the end, on stderr, one line with the median bin (the floor) and the highest bin." << std::endl;
     std::cout << "                   --wideband-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]  With --wideband-rate: ping detection per channel, on the GPU, on each channel's int8 I/Q: the energy of every 8 ms block (96 samples) is compared with RATIO x the channel's quiet level (the lower quartile of a hop's blocks, the lowest of this hop and the MEMORY hops before it, 0..16; default=8). RATIO 1..4095.9, default=2. A run of at least MIN_BLOCKS (1..64, default=2) consecutive blocks above it is an event, appended to FILE when it ends as one line 'ping ch= offset= start= dur= blocks= peak= ref= peak_db='. A strong-ping detector (from about +7 dB in 2500 Hz), less sensitive than the decoder. At the end, on stderr, one line with the events and the most active channels." << std::endl;
+    std::cout << "                   --wideband-pings-band[=HALFWIDTH[:CENTRE]]  With --wideband-pings: a 64-tap complex band-pass of CENTRE +- HALFWIDTH Hz, on the GPU, ahead of the detector's block energies, so that it compares the energy inside the signal's band and not that of the whole 12 kHz channel. HALFWIDTH 500..3000, default=1500; CENTRE an integer with |CENTRE| + HALFWIDTH <= 6000, default=the value of --center-frequency. The in-band energy of a block swings further on noise alone, so without a RATIO in --wideband-pings RATIO defaults to 3.25. The ping lines keep their format; peak and ref are then in-band. The detector's summary line adds 'band <CENTRE> +-<HALFWIDTH> Hz shift <s>'." << std::endl;
     std::cout << "                   --wideband-waterfall=FILE[:CHANNELS]  With --wideband-rate: a waterfall per channel, on the GPU, on each channel's int8 I/Q: one 96-point spectrum (125 Hz per bin, Hann window) per 8 ms block, the blocks of --wideband-pings. CHANNELS is a list of up to 16 channel indices c0,c1,... (every block of these is written) or 'pings' (every block above the threshold of every channel; the default with --wideband-pings, without it a list is required). After every push one line per selected row is appended to FILE: 'wf ch= offset= block= t= db=v0,...,v95' in ascending frequency from -6000 Hz, 0 dB = a tone of 1 LSB, floor -100 dB. With --wideband-pings every ping line gains ' freq=<Hz>', the strongest bin of the event's blocks. At the end, on stderr, one line with the rows written and up to three channels whose spectrum summed over the run has a bin at least 10 dB (a design parameter) over the channel's median bin: a steady carrier in the passband. A display and a frequency estimate; it does not feed the decoder." << std::endl;
     std::cout << "                   --wideband-capture=DIR[:CHANNELS[:POST[:PRE]]]  With --wideband-rate: keep each ping's channel I/Q for replay. On the GPU, after every push, the hops worth keeping are picked per channel and packed; only those bytes come to the host. CHANNELS is 'pings' (a hop is kept when the channel has a block above the threshold in it, for POST hops after that (0..16, default 1) and, with PRE = 1 (the default; 0 or 1), the one hop before it; the default with --wideband-pings, without it a list is required) or a list of up to 16 channel indices c0,c1,... that are kept whether active or not. At most min(2 x channels, 512) hops are kept per push; more are dropped and counted. Consecutive hops of a channel are appended to DIR/ch<c>_hop<k0>.cs8: int8 I/Q at 12000 samples per second, what --read-mode=2 reads. When a segment ends one line is appended to DIR/capture.log: 'capture ch= offset= hop= t= hops= file='. Every run starts capture.log afresh and overwrites segments of the same name. With --wideband-pings every ping line gains ' file=<name> at=<sample offset of the event's first block in that file>' (' file=-' when that hop was dropped). At the end, on stderr, one line with segments, hops written, bytes and dropped units." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
@@ -194,6 +195,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-pings", required_argument, 0, 0},
                                            {"wideband-waterfall", required_argument, 0, 0},
                                            {"wideband-capture", required_argument, 0, 0},
+                                           {"wideband-pings-band", optional_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -248,6 +250,7 @@ int main(int argc, char* const argv[])
         case 31:
         case 32:
         case 33:
+        case 34:
         {
             wbo.any_option = true;
             long long v = 0;
@@ -263,6 +266,7 @@ int main(int argc, char* const argv[])
             else if(idx == 31) good = parse_wideband_pings(optarg, wbo);
             else if(idx == 32) good = parse_wideband_waterfall(optarg, wbo);
             else if(idx == 33) good = parse_wideband_capture(optarg, wbo);
+            else if(idx == 34) wbo.ping_band = true, wbo.ping_band_arg = optarg ? optarg : "";
             else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
             if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
             break;
@@ -270,6 +274,10 @@ int main(int argc, char* const argv[])
         default: show_help(argv[0]); return 0;
         }
     }
+
+    // --wideband-pings-band: its CENTRE defaults to --center-frequency, wherever on the line that stood
+    if(wbo.ping_band && !parse_wideband_ping_band(wbo.ping_band_arg, center_set ? static_cast<int>(std::lrint(opt.center_hz)) : 0, wbo) && wbo.parse_error.empty())
+        wbo.parse_error = "bad value for --wideband-pings-band: '" + wbo.ping_band_arg + "'";
 
     // --wideband-rate: checked in full before anything touches the library
     const bool wideband = wbo.any_option;
@@ -314,11 +322,12 @@ int main(int argc, char* const argv[])
         return 2;
     }
     WidebandApi wb_api;
+    int ping_band_shift = 0;  // of --wideband-pings-band's design, for the summary
     if(wideband)
     {
         std::string err;
         if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
-           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)) ||
+           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)) || (wbo.ping_band && !wb_api.load_ping_band(err)) ||
            (wbo.waterfall && !wb_api.load_waterfall(err)) || (wbo.capture && !wb_api.load_capture(err)))
         {
             std::cerr << "msk144hip: " << err << std::endl;
@@ -499,6 +508,19 @@ int main(int argc, char* const argv[])
         {
             const msk144_wideband_spectrum_params sp{wbo.spectrum_bins, nullptr};
             if(wb_api.set_spectrum(dec.handle(), &sp) != MSK144_OK)
+            {
+                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
+                return 2;
+            }
+        }
+        if(wbo.ping_band)
+        {
+            const msk144wb::PingBandParams d = msk144wb::ping_band_design(wbo.ping_band_centre, wbo.ping_band_halfwidth);
+            msk144_wideband_ping_band_params bp;
+            static_assert(sizeof(bp) == sizeof(d), "msk144wb::PingBandParams is msk144_wideband_ping_band_params");
+            std::memcpy(&bp, &d, sizeof(bp));
+            ping_band_shift = bp.shift;
+            if(wb_api.set_ping_band(dec.handle(), &bp) != MSK144_OK)
             {
                 std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
                 return 2;
@@ -751,6 +773,11 @@ int main(int argc, char* const argv[])
             std::string line = "msk144hipdecoder: wideband pings: " + std::to_string(tr.events()) + " events on " + std::to_string(with_events) + " of " + std::to_string(ev.size()) +
                                " channels, " + std::to_string(tr.up_blocks()) + " of " + std::to_string(tr.total_blocks()) + " blocks up";
             char buf[96];
+            if(wbo.ping_band)
+            {
+                snprintf(buf, sizeof(buf), ", band %d +-%d Hz shift %d", wbo.ping_band_centre, wbo.ping_band_halfwidth, ping_band_shift);
+                line += buf;
+            }
             for(size_t i = 0; i < 3 && i < active.size(); i++)
             {
                 snprintf(buf, sizeof(buf), "%s ch=%d (%lld)", i ? "" : "; most active", active[i], static_cast<long long>(ev[static_cast<size_t>(active[i])]));

@@ -81,6 +81,17 @@ struct WidebandApi
         return false;
     }
 
+    // --wideband-pings-band: resolved only when it is given (load_ping_band)
+    int (*set_ping_band)(msk144_handle*, const msk144_wideband_ping_band_params*) = nullptr;
+
+    bool load_ping_band(std::string& err)
+    {
+        set_ping_band = reinterpret_cast<decltype(set_ping_band)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_ping_band"));
+        if(set_ping_band) return true;
+        err = "the loaded libmsk144hip has no ping band (msk144_set_wideband_ping_band): --wideband-pings-band needs it";
+        return false;
+    }
+
     // --wideband-waterfall: resolved only when it is given (load_waterfall)
     int (*set_waterfall)(msk144_handle*, const msk144_wideband_waterfall_params*) = nullptr;
     int (*waterfall)(msk144_handle*, int32_t, float*, int32_t*) = nullptr;
@@ -140,6 +151,11 @@ struct WidebandOptions
     std::string pings_file;
     msk144wb::PingParams ping_params;
     int ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
+    bool ping_ratio_given = false;  // --wideband-pings carried a RATIO
+    bool ping_band = false;         // --wideband-pings-band[=HALFWIDTH[:CENTRE]]: the in-band filter ahead of the detector's energies
+    std::string ping_band_arg;      // its value, parsed once --center-frequency is known (parse_wideband_ping_band)
+    int ping_band_halfwidth = msk144wb::kPingBandDefaultHalfwidthHz;
+    int ping_band_centre = 0;
     bool waterfall = false;       // --wideband-waterfall=FILE[:CHANNELS]: the per-channel waterfall, one line per selected row appended to FILE
     std::string waterfall_file;
     bool waterfall_by_pings = true;            // CHANNELS is `pings` (the default; needs --wideband-pings): every up block of every channel
@@ -241,6 +257,7 @@ inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
     w.pings = true;
     w.ping_params = msk144wb::PingParams();
     w.ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
+    w.ping_ratio_given = false;
     std::vector<std::string> f;
     size_t a = 0;
     while(true)
@@ -259,6 +276,7 @@ inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
         const double r = std::strtod(f[1].c_str(), &end);
         if(f[1].empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
         w.ping_params.ratio_q4 = static_cast<int32_t>(std::lrint(16.0 * r));
+        w.ping_ratio_given = true;
     }
     if(f.size() > 2)
     {
@@ -271,6 +289,30 @@ inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
         w.ping_params.memory = static_cast<int32_t>(v);
     }
     return msk144wb::check_pings(w.ping_params).empty();
+}
+
+// "[HALFWIDTH[:CENTRE]]", behind every other option: HALFWIDTH 500..3000 Hz (1500), CENTRE an integer (centre_default, the value of
+// --center-frequency) with |CENTRE| + HALFWIDTH <= 6000.  Without a RATIO in --wideband-pings the detector's ratio becomes the
+// band's default.  (Whether there is a detector needs the other options: check_wideband_options.)
+inline bool parse_wideband_ping_band(const std::string& s, int centre_default, WidebandOptions& w)
+{
+    w.ping_band = true;
+    w.ping_band_halfwidth = msk144wb::kPingBandDefaultHalfwidthHz;
+    w.ping_band_centre = centre_default;
+    if(!w.ping_ratio_given) w.ping_params.ratio_q4 = msk144wb::kPingBandDefaultRatioQ4;
+    long long v = 0;
+    if(!s.empty())
+    {
+        const size_t a = s.find(':');
+        if(!parse_int(s.substr(0, a), v) || v < INT32_MIN || v > INT32_MAX) return false;
+        w.ping_band_halfwidth = static_cast<int>(v);
+        if(a != std::string::npos)
+        {
+            if(!parse_int(s.substr(a + 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
+            w.ping_band_centre = static_cast<int>(v);
+        }
+    }
+    return msk144wb::check_ping_band_design(w.ping_band_centre, w.ping_band_halfwidth).empty();
 }
 
 // "FILE[:CHANNELS]": CHANNELS `pings`, or up to 16 different channel indices c0,c1,... (whether they exist and whether `pings` has a
@@ -400,6 +442,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.pings) return "--wideband-pings needs --wideband-rate=HZ";
+    if(w.rate_hz <= 0 && w.ping_band) return "--wideband-pings-band needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.waterfall) return "--wideband-waterfall needs --wideband-rate=HZ";
     if(w.rate_hz <= 0 && w.capture) return "--wideband-capture needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
@@ -414,6 +457,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
         const std::string bad = msk144wb::check_spectrum(w.spectrum_bins, nullptr, 2592 * w.rate_hz / msk144wb::kOutRate);
         if(!bad.empty()) return "--wideband-spectrum: " + bad;
     }
+    if(why.empty() && w.ping_band && !w.pings) return "--wideband-pings-band needs --wideband-pings=FILE";
     if(why.empty() && w.waterfall && w.waterfall_by_pings && !w.pings) return "--wideband-waterfall=FILE needs a channel list (FILE:c0,c1,...) without --wideband-pings";
     for(size_t i = 0; why.empty() && w.waterfall && i < w.waterfall_channels.size(); i++)
         if(static_cast<size_t>(w.waterfall_channels[i]) >= w.offsets.size())

@@ -407,10 +407,11 @@ class Pings:
         self.quiet = [[] for _ in range(self.channels)]   # the q of the pushes since the restart, oldest first
         self.scale = [None] * self.channels
 
-    def push(self, q, scales) -> np.ndarray:
+    def push(self, q, scales, energies=None) -> np.ndarray:
         """PING_DTYPE [channel] from the int8 hops q [channel][M][2] of one push and the f32 scale each channel was quantised with
-        (wideband_levels()["gain"]); a scale other than the channel's last restarts its history."""
-        E = ping_blocks(q)
+        (wideband_levels()["gain"]); a scale other than the channel's last restarts its history.  `energies`: the rule runs on
+        these [channel][nb] in place of the E of q (the in-band Ef of PingBand.push; q is then not read and may be None)."""
+        E = ping_blocks(q) if energies is None else np.asarray(energies, dtype=np.int64)
         if E.shape[0] != self.channels:
             raise ValueError(f"{self.channels} channels, got {E.shape[0]}")
         sc = np.broadcast_to(np.asarray(scales, dtype=np.float32), (self.channels,))
@@ -433,6 +434,73 @@ class Pings:
             out[c] = (mask, nb, h, quiet, R, peak, e.index(peak))
         self.energies = E
         return out
+
+
+# ---- the ping band: an in-band filter ahead of the block energies (msk144_set_wideband_ping_band) ----
+
+PING_BAND_TAPS = 64
+PING_BAND_MAX_SHIFT = 40
+PING_BAND_MAX_ENERGY = (1 << 22) - 1
+PING_BAND_RATIO_Q4 = 52   # MSK144_PING_BAND_RATIO_Q4: the detector's default ratio with the default band on
+
+
+def ping_band_taps(centre_hz: int = 0, halfwidth_hz: int = 1500) -> Tuple[np.ndarray, int]:
+    """The default design of the contract, from libmsk144host.so (csrc/wideband.h ping_band_design), exactly what the program hands
+    to the library: (int8 [64][2] taps (br, bi), shift)."""
+    L = _host_lib()
+    taps = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
+    shift = C.c_int32(0)
+    why = C.create_string_buffer(256)
+    L.msk144host_wideband_ping_band_design.restype = C.c_int
+    rc = L.msk144host_wideband_ping_band_design(C.c_int32(int(centre_hz)), C.c_int32(int(halfwidth_hz)), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why, len(why))
+    if rc != 0:
+        raise ValueError(why.value.decode())
+    return taps, int(shift.value)
+
+
+class PingBand:
+    """The ping band of the contract (include/msk144hip.h) in int64 numpy, push by push: z[n] = sum b[k] x[n - k] on the stored int8
+    values, Ef[b] = min((sum over the block of |z|^2) >> shift, 2^22 - 1), and per channel the 63 stored samples before the next
+    push.  reset() stands for every push at which the library restarts the ping history (a first push, the first push after
+    msk144_set_wideband_pings or msk144_set_wideband_ping_band): the tail is all zero there.  A change of scale does not reset."""
+
+    def __init__(self, channels: int, taps, shift: int):
+        t = np.asarray(taps)
+        if t.ndim != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= PING_BAND_TAPS:
+            raise ValueError("taps must be [k][2] with 1 <= k <= 64")
+        if np.any(t != t.astype(np.int8)):
+            raise ValueError("taps must be int8 values")
+        if not 0 <= int(shift) <= PING_BAND_MAX_SHIFT:
+            raise ValueError("shift must lie within 0..40")
+        self.taps = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
+        self.taps[:t.shape[0]] = t
+        self.shift, self.channels = int(shift), int(channels)
+        self.reset()
+
+    def reset(self):
+        self.tail = np.zeros((self.channels, PING_BAND_TAPS - 1, 2), dtype=np.int8)
+
+    def push(self, q) -> np.ndarray:
+        """int64 [channel][nb]: Ef of the int8 hops q [channel][M][2] of one push, M a multiple of 96; the tail moves on."""
+        q = np.asarray(q)
+        if q.ndim != 3 or q.shape[0] != self.channels or q.shape[1] % PING_BLOCK or q.shape[2] != 2:
+            raise ValueError(f"hops must be [{self.channels}][M][2] with M a multiple of 96")
+        M = q.shape[1]
+        s = np.concatenate([self.tail, q.astype(np.int8)], axis=1).astype(np.int64)
+        xr, xi = s[:, :, 0], s[:, :, 1]
+        zr = np.zeros((self.channels, M), dtype=np.int64)
+        zi = np.zeros((self.channels, M), dtype=np.int64)
+        T = PING_BAND_TAPS - 1
+        for k in range(PING_BAND_TAPS):
+            br, bi = int(self.taps[k, 0]), int(self.taps[k, 1])
+            if br == 0 and bi == 0:
+                continue
+            a, b = xr[:, T - k:T - k + M], xi[:, T - k:T - k + M]
+            zr += br * a - bi * b
+            zi += br * b + bi * a
+        S = np.sum((zr * zr + zi * zi).reshape(self.channels, M // PING_BLOCK, PING_BLOCK), axis=2)   # < 2^50
+        self.tail = s[:, M:, :].astype(np.int8)
+        return np.minimum(S >> self.shift, PING_BAND_MAX_ENERGY)
 
 
 class PingEvents:

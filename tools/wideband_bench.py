@@ -10,7 +10,9 @@ the defaults), so the time includes its step kernel after every push.  --blanker
 blanker_bytes is what they move per push (the raw push read twice, its cs16 form written once).  --spectrum[=BINS]: the input
 spectrum is on (msk144_set_wideband_spectrum, BINS default 1024, the default window), so the time includes its two kernels ahead of the
 channeliser; spectrum_bytes is the push they read once.  --pings: the ping detector is on (msk144_set_wideband_pings with the
-defaults), so the time includes its kernel behind the channeliser; pings_bytes is the staged hops it reads once.  --waterfall: the
+defaults), so the time includes its kernel behind the channeliser; pings_bytes is the staged hops it reads once.  --pings-band: the
+ping band is on as well (msk144_set_wideband_ping_band with the default design; implies --pings), so the time includes its kernel
+ahead of the detector's; pings_band_dot4 is the int8 dot products of a push (channels x 2592 x 99).  --waterfall: the
 per-channel waterfall is on (msk144_set_wideband_waterfall, the default window), so the time includes its two kernels behind the
 channeliser; waterfall_mfma is the f32 MFMA instructions of a push (576 per channel) and waterfall_bytes the rows it writes.
 --capture: the capture is on (msk144_set_wideband_capture with the defaults) with every 8th channel listed, up to the 16 the list
@@ -22,7 +24,7 @@ default decode configuration): hops per second of the whole program against the 
 samples at 12 kHz).
 
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
-                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--waterfall] [--capture]
+                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--pings-band] [--waterfall] [--capture]
 """
 from __future__ import annotations
 
@@ -46,7 +48,7 @@ FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
 
 def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False, waterfall: bool = False,
-            capture: bool = False) -> dict:
+            capture: bool = False, pings_band: bool = False) -> dict:
     D = rate // 12000
     rng = np.random.default_rng(C + D)
     g = math.gcd(rate, 12000)
@@ -61,8 +63,10 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
             d.set_wideband_blanker()
         if spectrum:
             d.set_wideband_spectrum(spectrum)
-        if pings:
+        if pings or pings_band:
             d.set_wideband_pings()
+        if pings_band:
+            d.set_wideband_ping_band()
         if waterfall:
             d.set_wideband_waterfall()
         listed = list(range(0, C, 8))[:wideband.CAPTURE_MAX_LISTED]
@@ -104,7 +108,10 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
     if spectrum:
         ratio["spectrum_bins"] = spectrum
         ratio["spectrum_bytes"] = 2592 * P // Q * (4 if blanker else 2)   # the push read once: cu8, or the blanker's cs16
-    if pings:
+    if pings_band:
+        ratio["pings_band"] = True
+        ratio["pings_band_dot4"] = C * 2592 * 99   # 33 tap dwords x 3 sums per output
+    if pings or pings_band:
         ratio["pings"] = True
         ratio["pings_bytes"] = C * 2592 * 2   # every channel's int8 hop read once
     if waterfall:
@@ -162,13 +169,15 @@ def main():
     ap.add_argument("--blanker", action="store_true", help="measure with the impulse-noise blanker on")
     ap.add_argument("--spectrum", type=int, nargs="?", const=1024, default=0, metavar="BINS", help="measure with the input spectrum on (BINS default 1024)")
     ap.add_argument("--pings", action="store_true", help="measure with the ping detector on")
+    ap.add_argument("--pings-band", action="store_true", help="measure with the ping detector and its in-band filter on")
     ap.add_argument("--waterfall", action="store_true", help="measure with the per-channel waterfall on")
     ap.add_argument("--capture", action="store_true", help="measure with the capture on, every 8th channel (up to 16) listed")
     a = ap.parse_args()
     rates = [int(v) * 12000 for v in a.decimations.split(",") if v] + [int(v) for v in a.rates.split(",") if v]
     for C in [int(v) for v in a.channels.split(",")]:
         for rate in rates:
-            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall, capture=a.capture)), flush=True)
+            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall, capture=a.capture,
+                                     pings_band=a.pings_band)), flush=True)
     if a.program_hops:
         print(json.dumps(program_run(a.program_hops, rate=a.program_rate)), flush=True)
 
