@@ -35,6 +35,7 @@ SOURCES = [
     ("capture.hip", []),
     ("pingband.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
+    ("msk144_wideband_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]
 

@@ -1,0 +1,314 @@
+// The handle behind the C ABI of libmsk144hip.so, and what its two host files share: msk144_api.cpp (handle lifetime, the narrowband
+// entries, the decode) and msk144_wideband_api.cpp (every msk144_*wideband* entry).  Host code only: nothing here launches a kernel.
+#pragma once
+
+#include "../../include/msk144hip.h"
+
+#include "msk144_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+// Device and pinned host buffers that are freed together (dev_alloc, host_alloc register them)
+struct Buffers
+{
+    std::vector<void*> device, pinned;
+
+    void release()
+    {
+        for(void* p : device) (void)hipFree(p);
+        for(void* p : pinned) (void)hipHostFree(p);
+        device.clear();
+        pinned.clear();
+    }
+};
+
+// Channel slots: without the bank slot c is channel c; with it, the channels of each occupied band (k mod 64, ascending) one after
+// another, each band's group padded to whole waves, at the residual offset f_c - k Fs/64
+struct WbSlots
+{
+    std::vector<int32_t> slot_channel;   // the channel of slot c; -1: padding
+    std::vector<long long> slot_offset;  // its offset at the channeliser's rate
+    std::vector<int32_t> wave_band;      // bank: the sub-band stream of each wave of 32 slots
+    std::vector<int32_t> band_list;      // bank: the occupied band k mod 64 of stream j
+};
+
+// The shape of one push: 5184 output samples per channel for a first push, 2592 for a later one
+struct WbPush
+{
+    bool first = false;
+    int M = 0;        // output samples per channel
+    int samples = 0;  // input samples: M Pin/Qin
+    int frames = 0;   // the channeliser's input samples, M P/Q: with the bank, its frames of 32 input samples
+};
+
+// The wideband configuration of a handle (msk144_set_wideband): one block per option.  In every block `on` is what the next push
+// does (set by the option's msk144_set_wideband_* entry), `pushed` whether the last push left the option's results (what its read
+// entries test, wb_read_ready; set by the push), `restart` that the next push with the option on is its first since `set`; d_* are
+// device buffers, allocated by `set` once per configuration (wb_ensure) and never in a push.  The exceptions are written at their
+// block: bank.on is the rate's, no option; blanker; spectrum.pushed; capture.pushed.  Value-initialised is "not configured, all off".
+struct Wideband
+{
+    Buffers mem;
+    bool configured = false, started = false;  // started: a first push has been made since the configuration
+    int channels = 0;      // the handle's
+    WbPush last;           // the last push
+    WbSlots layout;
+    // the channeliser: Fs = 12000 P/Q in lowest terms at its input (Q = 1: decimation by D = P), 12000 Pin/Qin at the handle's
+    struct Core
+    {
+        int P = 0, Q = 0, Pin = 0, Qin = 0, format = 0;
+        int hist = 0, raw_hist = 0;  // samples kept between pushes: the channeliser's ceil(L/Q) - 1, the raw input's (the same without the bank)
+        long long m_next = 0;        // output sample index of the next push
+        size_t slot_bytes = 0;       // pinned bytes per slot: 5184 Pin/Qin samples
+        uint8_t* pinned[MSK144_SLOTS] = {};
+        uint8_t* d_raw = nullptr;    // history samples + the samples of one push, raw format
+        uint8_t* d_in = nullptr;     // the running stream's input and its format there: d_raw in `format`, or d_blanked in cs16.  Derived
+        int in_format = 0;           // from blanker.pushed alone, where a first push latches that (msk144_push_wideband); nothing else writes them
+        float2* d_G = nullptr;       // one block per branch (WidebandBranch); Q = 1: the one block [ceil(slots/32)][D][K][32]
+        msk144::WidebandBranch* d_branches = nullptr;  // [Q]
+        int32_t* d_fmod = nullptr;
+        float2* d_rot = nullptr;     // [12000]
+        unsigned long long* d_clip = nullptr;
+    } core;
+    // two-stage bank (rates above 6.144 Msps): the channeliser runs at Fs/32 on the sub-band streams, one per layout.band_list
+    struct Bank
+    {
+        bool on = false;
+        int K1 = 0;
+        long long stride = 0;  // float2 per sub-band stream: hist + 5184 P/Q frames
+        long long n_next = 0;  // bank frame index of the next push
+        float* d_h1 = nullptr;
+        int32_t* d_bands = nullptr;
+        float2* d_tw = nullptr;   // [64]
+        float2* d_sub = nullptr;  // [bands][stride]
+        int32_t* d_wave_band = nullptr;
+        int32_t* d_slot_channel = nullptr;
+    } bank;
+    // per-channel levels (taken at every push), gains and the stepped AGC (msk144_set_wideband_agc), whose on / pushed these are
+    struct Agc
+    {
+        bool on = false, pushed = false;
+        msk144wb::AgcParams params;
+        float gain = 0.0f;                       // the configured default, which msk144_set_wideband_gains(h, NULL) restores
+        std::vector<float> gains, push_gains;    // base gain of every channel: of the next push, of the last one
+        unsigned long long* d_levels = nullptr;  // [channels] msk144wb::pack_level of the last push
+        float* d_scale = nullptr;                // [slots] what the next push is quantised with: 128 x gain x 2^exponent
+        float* d_base_scale = nullptr;           // [slots] the same at exponent 0
+        float* d_gains = nullptr;                // [channels]
+        int32_t* d_exp = nullptr;                // [channels] AGC exponent of the next push
+        int32_t* d_quiet = nullptr;              // [channels] pushes in a row below the window
+        int32_t* d_used_exp = nullptr;           // [channels] AGC exponent of the last push
+    } agc;
+    // impulse-noise blanker (msk144_set_wideband_blanker).  Two-phase: on / next are what is set; a first push latches them into
+    // pushed / params, the running stream's.  A blanked stream is cs16 in d_blanked (history + one push, as d_raw), made from d_stage
+    struct Blanker
+    {
+        bool on = false, pushed = false;
+        msk144wb::BlankerParams next, params;
+        uint8_t *d_stage = nullptr, *d_blanked = nullptr;
+        msk144::BlankerCounters* d_counters = nullptr;
+        long long pushes = 0;   // of the running stream: its parity picks the carry word
+        long long samples = 0;  // input samples since the first push
+    } blanker;
+    // power spectrum of the input stream (msk144_set_wideband_spectrum): tables and result for the largest B, allocated once
+    struct Spectrum
+    {
+        int bins = 0;       // B of the next push; on: bins != 0
+        int pushed = 0;     // B of the spectrum the last push left; 0: none
+        int rows_bins = 0;  // the largest B set so far, which the partial sums hold
+        float* d_window = nullptr;     // [B]
+        float2* d_tw = nullptr;        // [B] e^{-j2pi m/B}
+        double* d_partials = nullptr;  // [kSpectrumMaxGroups][rows_bins]
+        double* d_out = nullptr;       // [B] ascending frequency
+    } spectrum;
+    // ping detection (msk144_set_wideband_pings)
+    struct Pings
+    {
+        bool on = false, pushed = false, restart = false;
+        msk144wb::PingParams params;
+        msk144wb::PingHistory* d_state = nullptr;   // [channels]
+        msk144wb::PingRecord* d_records = nullptr;  // [channels]
+        int32_t* d_energies = nullptr;              // [channels][54]; the ping band's too, allocated by whichever `set` comes first
+    } pings;
+    // the ping band (msk144_set_wideband_ping_band): acts in a push made with the detector on, and restarts through pings.restart
+    struct PingBand
+    {
+        bool on = false;
+        int32_t shift = 0;
+        int8_t* d_taps = nullptr;    // [64][2]
+        uint8_t* d_tails = nullptr;  // [channels][128]: two zero bytes, then the 63 stored samples before the next push
+    } ping_band;
+    // per-channel waterfall (msk144_set_wideband_waterfall)
+    struct Waterfall
+    {
+        bool on = false, pushed = false;
+        float2* d_dft = nullptr;   // [3][96][32] the windowed DFT matrix in the kernel's order
+        float* d_rows = nullptr;   // [channels][54][96]
+        double* d_sums = nullptr;  // [channels][96]
+    } waterfall;
+    // per-ping capture (msk144_set_wideband_capture): descriptors and rows for the largest max_units set so far (`rows`; a larger
+    // one frees them and allocates anew).  pushed: the last push left a header and no `set` has come since
+    struct Capture
+    {
+        bool on = false, pushed = false, restart = false;
+        msk144wb::CaptureParams params;
+        int rows = 0;
+        uint8_t* d_listed = nullptr;                  // [channels]
+        msk144wb::CaptureState* d_state = nullptr;    // [channels]
+        msk144wb::CaptureHeader* d_header = nullptr;  // [1]
+        msk144wb::CaptureUnit* d_units = nullptr;     // [rows]
+        uint8_t* d_data = nullptr;                    // [rows][5184]
+    } capture;
+};
+
+struct msk144_handle
+{
+    msk144_params params{};
+    msk144::DeviceStore st{};
+    msk144::SyncTemplate tpl{};
+    std::vector<float> freq_host;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+
+    // every buffer of the handle except those of its wideband configuration
+    Buffers mem;
+    float* d_freq = nullptr;
+    float2* d_cb42 = nullptr;
+    uint8_t* d_input = nullptr;  // staging for host-submitted windows
+    float2* d_twiddle = nullptr;
+    float* d_fft_mask = nullptr;
+
+    int llr_block = 1;  // channels per softbits->index->LDPC block
+    bool retained = true;  // every LLR row of a decode stays readable (one block covers all channels and msk144_set_llr_retention was not switched off)
+    bool rows_valid = true;  // the LLR store holds every row of the last softbits run (false after a decode without retention, until the next retained one)
+    int active = 1;     // channels the current hop covers (msk144_submit_slot_n: the first n of the slot); <= st.channels
+    bool have_window = false;
+    bool decoded = false;
+    bool profiling = false;
+    // HIP-event pairs recorded around each stage; a pool so that many steps can be in flight
+    // before the times are harvested at the next synchronisation point
+    struct Span
+    {
+        int stage;
+        int call;  // spans of one decode/submit call are summed into one sample
+        hipEvent_t e0, e1;
+    };
+    int call_id = 0;
+    int last_call[MSK144_T_COUNT];
+    std::vector<Span> spans_pending;
+    std::vector<hipEvent_t> ev_free;
+    hipEvent_t ev_open = nullptr;
+    double t_sum[MSK144_T_COUNT]{};
+    int t_cnt[MSK144_T_COUNT]{};
+
+    // Pinned staging slots (msk144_input_slot .. msk144_fetch_wait), allocated on first use.  Slot 0's device record list is
+    // st.results of the plain calls; slot 1 has its own, so the list of one slot survives the decode of the other.
+    struct Slot
+    {
+        uint8_t* in = nullptr;              // pinned windows, input_bytes()
+        msk144_result* d_records = nullptr; // device record list this slot's decode writes
+        msk144_result* out = nullptr;       // pinned records, max_results
+        int32_t* out_count = nullptr;       // pinned
+        float* out_seg = nullptr;           // pinned [channels][8]
+        int32_t copied = 0;                 // records covered by the asynchronous copy
+        hipEvent_t done = nullptr;
+        bool pending = false;
+        // hop-ring inputs (msk144_hop_slot), pinned, allocated on first use
+        uint8_t* hops = nullptr;          // [channels][half window]
+        uint8_t* first_halves = nullptr;  // [channels][half window]
+        int32_t* streams = nullptr;    // [channels]
+        uint8_t* is_first = nullptr;   // [channels]
+    };
+    Slot slots[MSK144_SLOTS];
+    bool slots_ready = false;
+    int cur_slot = 0;                        // the slot whose record list the next decode writes
+    std::atomic<int32_t> last_total{0};      // record count of the last fetched hop: sizes the next asynchronous copy
+    hipStream_t copy_stream = nullptr;       // remainder copies of msk144_fetch_wait (may run on a second thread)
+    // device side of the hop ring: every stream's current window, and the staging of one batch of hops
+    uint8_t* d_ring = nullptr;
+    uint8_t* d_hops = nullptr;
+    uint8_t* d_first = nullptr;
+    int32_t* d_streams = nullptr;
+    uint8_t* d_isfirst = nullptr;
+    bool ring_ready = false;
+    // msk144_clock_probe: its own stream, so that the probe wave runs beside the decode kernels
+    hipStream_t probe_stream = nullptr;
+    uint64_t* d_probe = nullptr;
+
+    // wideband channeliser (msk144_set_wideband); its buffers have their own owner, as a new configuration replaces them
+    Wideband wb;
+
+    std::string error;
+};
+
+// internal to the library: none of this is exported
+#pragma GCC visibility push(hidden)
+
+// defined in msk144_api.cpp
+int fail(msk144_handle* h, int code, const std::string& msg);  // sets the handle's (h == nullptr: the thread's creation) error text; returns code
+void ev_begin(msk144_handle* h);
+void ev_end(msk144_handle* h, int stage);
+int ensure_ring(msk144_handle* h);
+int check_hop_slot(msk144_handle* h, int32_t slot);
+int begin_hop(msk144_handle* h, int32_t slot, int32_t n);
+int run_frontend(msk144_handle* h, const void* d_in);
+// defined in msk144_wideband_api.cpp: back to no wideband configuration, its buffers freed, every field reset
+void wb_release(msk144_handle* h);
+
+#define HIP_TRY(h, expr)                                                                                   \
+    do                                                                                                     \
+    {                                                                                                      \
+        hipError_t e_ = (expr);                                                                            \
+        if(e_ != hipSuccess) return fail(h, MSK144_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while(0)
+
+// count elements of device (hipMalloc) or pinned host (hipHostMalloc) memory, registered with the owner that frees them
+template<typename T>
+int alloc(msk144_handle* h, Buffers& owner, bool pinned, T** p, size_t count)
+{
+    void* q = nullptr;
+    const size_t bytes = count * sizeof(T);
+    hipError_t e = pinned ? hipHostMalloc(&q, bytes ? bytes : 1, hipHostMallocDefault) : hipMalloc(&q, bytes ? bytes : 1);
+    if(e != hipSuccess)
+    {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s(%zu bytes): %s", pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+        return fail(h, MSK144_ENOMEM, buf);
+    }
+    (pinned ? owner.pinned : owner.device).push_back(q);
+    *p = static_cast<T*>(q);
+    return MSK144_OK;
+}
+
+template<typename T>
+int dev_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
+{
+    return alloc(h, owner, false, p, count);
+}
+
+// frees one buffer that dev_alloc registered with `owner` ahead of the rest; *p = nullptr
+template<typename T>
+void dev_free(Buffers& owner, T** p)
+{
+    const auto it = std::find(owner.device.begin(), owner.device.end(), static_cast<void*>(*p));
+    if(it != owner.device.end())
+    {
+        (void)hipFree(*it);
+        owner.device.erase(it);
+    }
+    *p = nullptr;
+}
+
+template<typename T>
+int host_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
+{
+    return alloc(h, owner, true, p, count);
+}
+
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI host code (msk144_api.cpp) and the gfx950 kernels.
+// Internal interface between the C-ABI host code (msk144_api.cpp, msk144_wideband_api.cpp) and the gfx950 kernels.
 // One launcher per reference kernel; every launcher only enqueues work on `stream`.
 #pragma once
 

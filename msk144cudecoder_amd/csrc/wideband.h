@@ -1,4 +1,4 @@
-// Wideband channeliser contract shared by the library (msk144_api.cpp, channelise.hip), the stream program (main.cpp) and the
+// Wideband channeliser contract shared by the library (msk144_wideband_api.cpp, channelise.hip), the stream program (main.cpp) and the
 // host test library (host_capi.cpp): the rules a wideband configuration must meet and the default prototype filter.
 // Header-only, plain C++ (no HIP), so that every one of those builds gets the same taps and the same checks.
 #pragma once

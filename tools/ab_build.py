@@ -3,6 +3,11 @@
 
     python tools/ab_build.py <rev> <name> file.hip [file2.hip ...]   ->  tools/ab/libmsk144hip_<name>.so
 
+The sources are those of msk144cudecoder_amd/build.py SOURCES, swapped by name: the host side of the C ABI is two of them,
+msk144_api.cpp and msk144_wideband_api.cpp (the wideband entries; both include api_handle.h, which is taken from the tree).  A
+revision from before that split has no msk144_wideband_api.cpp and cannot be mixed in file by file: build it from a checkout of its
+own (`git worktree add`, then `python -m msk144cudecoder_amd.build` there) and pass the library to the A/B tools.
+
 tools/ab_bench.sh then alternates bench.py between the tree's library and that one on ONE box (boxes of the pool differ by +-4 %)."""
 import os
 import subprocess

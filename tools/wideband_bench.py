@@ -4,8 +4,10 @@ For every (channels, rate) the handle is pushed `--pushes` later pushes of rando
 time covers the channeliser and the IQ front end; the same handle is then fed the same number of plain msk144_push_hops calls,
 whose front-end time is the IQ front end alone, and the difference is the channeliser.  FLOP count: channels x 2592 x K x
 (Fs/12000) x 8 (= channels x 2592 x K*D x 8 at Fs = D x 12000); above 6.144 Msps (the two-stage bank) the bank's work per push
-plus the channeliser's at Fs/32.  One JSON line per configuration on stdout.  --agc: the stepped AGC is on (msk144_set_wideband_agc with
-the defaults), so the time includes its step kernel after every push.  --blanker: the impulse-noise blanker is on
+plus the channeliser's at Fs/32.  push_host_us is the median host time of one msk144_push_wideband call (the call returns before
+the device has run it; profiling is on, so the HIP events of the stage times are part of it).  One JSON line per configuration on
+stdout.  --agc: the stepped AGC is on (msk144_set_wideband_agc with the defaults), so the time includes its step kernel after
+every push.  --blanker: the impulse-noise blanker is on
 (msk144_set_wideband_blanker with the defaults), so the time includes its two kernels ahead of the channeliser, which then reads cs16;
 blanker_bytes is what they move per push (the raw push read twice, its cs16 form written once).  --spectrum[=BINS]: the input
 spectrum is on (msk144_set_wideband_spectrum, BINS default 1024, the default window), so the time includes its two kernels ahead of the
@@ -78,8 +80,11 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
         d.synchronize()
         d.set_profiling(True)
         d.stage_times(reset=True)
+        host = []
         for i in range(pushes):
+            t0 = time.perf_counter()
             d.push_wideband(i % 2, first=False)
+            host.append(time.perf_counter() - t0)
         wide = d.stage_times(reset=True)
         for s in range(2):
             hops, _, streams, is_first = d.hop_slot(s)
@@ -123,7 +128,7 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
         ratio["capture_units"] = len(listed)
         ratio["capture_bytes"] = len(listed) * wideband.CAPTURE_UNIT_BYTES
     return dict(channels=C, **ratio, K=K, agc=agc, blanker=blanker, pushes=pushes, push_frontend_ms=round(wide["frontend"][0], 4), iq_frontend_ms=round(plain["frontend"][0], 4),
-                channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), gflop=round(flop / 1e9, 2),
+                channeliser_ms=round(ms, 4), h2d_ms=round(wide["h2d"][0], 4), push_host_us=round(float(np.median(host)) * 1e6, 1), gflop=round(flop / 1e9, 2),
                 tflops=round(flop / (ms * 1e-3) / 1e12, 1) if ms > 0 else None,
                 fraction_of_fp32_peak=round(flop / (ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 3) if ms > 0 else None,
                 target_ms=target)
