@@ -7,18 +7,19 @@
 // submits hop n+1 while the GPU decodes hop n and a second thread turns the records of hop n-1 into text.  --devices=0,1,... runs
 // one such loop per GPU, each on its contiguous share of the streams (the reference binds to one device, main.cu:115).
 #include "stream_loop.h"
+#include "wideband_run.h"
 
 #include <getopt.h>
 #include <poll.h>
 #include <signal.h>
 #include <sys/resource.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cerrno>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -91,15 +92,8 @@ const char* mode_name(int mode)
 
 void split_list(const std::string& list, std::vector<std::string>& out)
 {
-    size_t a = 0;
-    while(a <= list.size())
-    {
-        const size_t b = list.find(',', a);
-        const std::string item = list.substr(a, b == std::string::npos ? std::string::npos : b - a);
+    for(const std::string& item : split_fields(list, ','))
         if(!item.empty()) out.push_back(item);
-        if(b == std::string::npos) break;
-        a = b + 1;
-    }
 }
 
 void warn_if_late(long long ms)
@@ -203,6 +197,7 @@ int main(int argc, char* const argv[])
         const int c = getopt_long(argc, argv, "", long_options, &idx);
         if(c == -1) break;
         if(c != 0) continue;  // unknown option: getopt has printed its own message, carry on like the reference
+        if(take_wideband_option(long_options[idx].name, optarg, wbo)) continue;
         switch(idx)
         {
         case 0: show_help(argv[0]); return 0;
@@ -238,39 +233,6 @@ int main(int argc, char* const argv[])
         case 19: split_list(optarg, device_list); break;
         case 20: opt.max_results = atoi(optarg); break;
         case 21: opt.every_slot = true; break;
-        case 22:
-        case 23:
-        case 24:
-        case 25:
-        case 26:
-        case 27:
-        case 28:
-        case 29:
-        case 30:
-        case 31:
-        case 32:
-        case 33:
-        case 34:
-        {
-            wbo.any_option = true;
-            long long v = 0;
-            bool good = true;
-            if(idx == 22) good = parse_int(optarg, v) && (wbo.rate_hz = v) > 0;
-            else if(idx == 23) good = parse_wideband_format(optarg, wbo.format);
-            else if(idx == 24) good = parse_offset_list(optarg, wbo.offsets), wbo.offset_sources++;
-            else if(idx == 25) good = parse_offset_grid(optarg, wbo.offsets), wbo.offset_sources++;
-            else if(idx == 26) good = parse_wideband_gain(optarg, wbo);
-            else if(idx == 28) wbo.levels = true;
-            else if(idx == 29) good = parse_wideband_blanker(optarg, wbo);
-            else if(idx == 30) good = parse_wideband_spectrum(optarg, wbo);
-            else if(idx == 31) good = parse_wideband_pings(optarg, wbo);
-            else if(idx == 32) good = parse_wideband_waterfall(optarg, wbo);
-            else if(idx == 33) good = parse_wideband_capture(optarg, wbo);
-            else if(idx == 34) wbo.ping_band = true, wbo.ping_band_arg = optarg ? optarg : "";
-            else good = parse_int(optarg, v) && v >= 1 && v <= msk144wb::kMaxTapsPerPhase && ((wbo.taps_per_phase = static_cast<int>(v)), true);
-            if(!good && wbo.parse_error.empty()) wbo.parse_error = std::string("bad value for --") + long_options[idx].name + ": '" + (optarg ? optarg : "") + "'";
-            break;
-        }
         default: show_help(argv[0]); return 0;
         }
     }
@@ -321,54 +283,9 @@ int main(int argc, char* const argv[])
         std::cerr << "--interleaved=N takes N >= 1 streams from stdin and excludes --inputs" << std::endl;
         return 2;
     }
-    WidebandApi wb_api;
-    int ping_band_shift = 0;  // of --wideband-pings-band's design, for the summary
-    if(wideband)
-    {
-        std::string err;
-        if(!wb_api.load(err) || ((wbo.agc || wbo.levels) && !wb_api.load_levels(err)) || (wbo.blanker && !wb_api.load_blanker(err)) ||
-           (wbo.spectrum && !wb_api.load_spectrum(err)) || (wbo.pings && !wb_api.load_pings(err)) || (wbo.ping_band && !wb_api.load_ping_band(err)) ||
-           (wbo.waterfall && !wb_api.load_waterfall(err)) || (wbo.capture && !wb_api.load_capture(err)))
-        {
-            std::cerr << "msk144hip: " << err << std::endl;
-            return 2;
-        }
-    }
-    // --wideband-spectrum: its file is opened once its entries are known to exist, and still before any library call
-    FILE* spectrum_file = nullptr;
-    if(wbo.spectrum && !(spectrum_file = fopen(wbo.spectrum_file.c_str(), "a")))
-    {
-        std::cerr << "--wideband-spectrum: cannot open '" << wbo.spectrum_file << "': " << strerror(errno) << std::endl;
-        return 2;
-    }
-    // --wideband-pings: likewise
-    FILE* pings_file = nullptr;
-    if(wbo.pings && !(pings_file = fopen(wbo.pings_file.c_str(), "a")))
-    {
-        std::cerr << "--wideband-pings: cannot open '" << wbo.pings_file << "': " << strerror(errno) << std::endl;
-        return 2;
-    }
-    // --wideband-waterfall: likewise
-    FILE* waterfall_file = nullptr;
-    if(wbo.waterfall && !(waterfall_file = fopen(wbo.waterfall_file.c_str(), "a")))
-    {
-        std::cerr << "--wideband-waterfall: cannot open '" << wbo.waterfall_file << "': " << strerror(errno) << std::endl;
-        return 2;
-    }
-    // --wideband-capture: its directory is made if it is not there, and capture.log must be writable in it.  A run starts the log
-    // afresh: a segment's first write truncates a file of the same name that an earlier run left, so that run's lines would name
-    // files whose content is no longer theirs.
-    if(wbo.capture)
-    {
-        FILE* log = nullptr;
-        if((mkdir(wbo.capture_dir.c_str(), 0777) != 0 && errno != EEXIST) || !(log = fopen((wbo.capture_dir + "/capture.log").c_str(), "w")))
-        {
-            std::cerr << "--wideband-capture: cannot write under '" << wbo.capture_dir << "': " << strerror(errno) << std::endl;
-            return 2;
-        }
-        fclose(log);
-        wbo.capture_params.max_units = capture_default_max_units(wbo.offsets.size());
-    }
+    // --wideband-rate: the entries resolved and the files opened before anything touches the library (wideband_run.h)
+    WidebandRun wideband_run(wbo);
+    if(wideband && !wideband_run.prepare()) return 2;
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
     const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
     opt.profile = timing && batched;
@@ -459,115 +376,7 @@ int main(int argc, char* const argv[])
     std::cerr << "msk144hipdecoder: " << F << " frequency hypotheses x " << D << " patterns x 8 = " << F * D * 8 << " candidates per window; HIP workgroups per window: scan "
               << F << " x 512, softbits " << F << " x 512, LDPC one wave per gated candidate" << std::endl;
     if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
-    if(wideband)
-    {
-        const int64_t rate2 = msk144wb::stage2_rate(wbo.rate_hz);  // the channeliser's rate: Fs, or Fs/32 behind the bank
-        const msk144wb::RateRatio rr = msk144wb::rate_ratio(rate2);
-        static const char* fmt_names[] = {"cu8", "cs8", "cs16"};
-        std::cerr << "msk144hipdecoder: wideband input " << wbo.rate_hz << " sps " << fmt_names[wbo.format] << " on stdin, ";
-        if(rate2 != wbo.rate_hz)
-        {
-            std::vector<int> bands;
-            for(int32_t f : wbo.offsets)
-            {
-                const int b = msk144wb::bank_band(wbo.rate_hz, f) & (msk144wb::kBankBands - 1);
-                if(std::find(bands.begin(), bands.end(), b) == bands.end()) bands.push_back(b);
-            }
-            std::cerr << "stage 1: " << msk144wb::kBankBands << "-band analysis bank, " << bands.size() << " bands occupied, sub-band rate " << rate2 << " sps, filter "
-                      << msk144wb::kDefaultBankTapsPerBand << " x " << msk144wb::kBankBands << " taps; stage 2: ";
-        }
-        std::cerr << (rr.Q == 1 ? "decimation " + std::to_string(rr.P) : "resampling " + std::to_string(rr.P) + "/" + std::to_string(rr.Q)) << ", filter "
-                  << wbo.taps_per_phase << " x " << rr.P << " taps, gain " << wbo.gain << (wbo.agc ? " x 2^e (AGC, e within +-20)" : "") << ", " << nch << " channels as one GPU batch per hop:" << std::endl;
-        for(int c = 0; c < nch; c++) std::cerr << "msk144hipdecoder: ch=" << c << " offset " << wbo.offsets[static_cast<size_t>(c)] << " Hz" << std::endl;
-        const std::vector<double> taps = msk144wb::design_taps_rate(rate2, wbo.taps_per_phase);
-        msk144_wideband_params wp{};
-        wp.rate_hz = wbo.rate_hz;
-        wp.format = wbo.format;
-        wp.taps_per_phase = wbo.taps_per_phase;
-        wp.gain = wbo.gain;
-        wp.num_taps = static_cast<int32_t>(taps.size());
-        wp.taps = taps.data();
-        wp.offsets_hz = wbo.offsets.data();
-        wp.num_offsets = nch;
-        if(wb_api.set(dec.handle(), &wp) != MSK144_OK)
-        {
-            std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-            return 2;
-        }
-        if(wbo.agc)
-        {
-            const msk144wb::AgcParams d;
-            const msk144_wideband_agc agc{d.lo_sq, d.hi_sq, d.clip_ppm, d.hold, d.min_exp, d.max_exp};
-            if(wb_api.set_agc(dec.handle(), &agc) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.spectrum)
-        {
-            const msk144_wideband_spectrum_params sp{wbo.spectrum_bins, nullptr};
-            if(wb_api.set_spectrum(dec.handle(), &sp) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.ping_band)
-        {
-            const msk144wb::PingBandParams d = msk144wb::ping_band_design(wbo.ping_band_centre, wbo.ping_band_halfwidth);
-            msk144_wideband_ping_band_params bp;
-            static_assert(sizeof(bp) == sizeof(d), "msk144wb::PingBandParams is msk144_wideband_ping_band_params");
-            std::memcpy(&bp, &d, sizeof(bp));
-            ping_band_shift = bp.shift;
-            if(wb_api.set_ping_band(dec.handle(), &bp) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.pings)
-        {
-            const msk144_wideband_pings_params pp{wbo.ping_params.ratio_q4, wbo.ping_params.memory, wbo.ping_params.min_ref};
-            if(wb_api.set_pings(dec.handle(), &pp) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.waterfall)
-        {
-            const msk144_wideband_waterfall_params wp{nullptr};
-            if(wb_api.set_waterfall(dec.handle(), &wp) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.capture)
-        {
-            msk144_wideband_capture_params cp{};
-            cp.pre = wbo.capture_params.pre;
-            cp.post = wbo.capture_params.post;
-            cp.max_units = wbo.capture_params.max_units;
-            cp.num_listed = static_cast<int32_t>(wbo.capture_channels.size());
-            std::copy(wbo.capture_channels.begin(), wbo.capture_channels.end(), cp.listed);
-            if(wb_api.set_capture(dec.handle(), &cp) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-        if(wbo.blanker)
-        {
-            const msk144_wideband_blanker bl{wbo.blanker_params.threshold_q4, wbo.blanker_params.pre, wbo.blanker_params.post};
-            if(wb_api.set_blanker(dec.handle(), &bl) != MSK144_OK)
-            {
-                std::cerr << "msk144hip: " << msk144_last_error(dec.handle()) << std::endl;
-                return 2;
-            }
-        }
-    }
+    if(wideband && !wideband_run.configure(dec.handle())) return 2;
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
@@ -639,11 +448,7 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
-        if(wbo.spectrum) loops[i]->use_wideband_spectrum(spectrum_file, wbo.spectrum_bins, wbo.spectrum_hops, wbo.rate_hz);
-        if(wbo.pings) loops[i]->use_wideband_pings(pings_file, wbo.ping_min_blocks, wbo.offsets);
-        if(wbo.waterfall) loops[i]->use_wideband_waterfall(waterfall_file, wbo.waterfall_by_pings, wbo.waterfall_channels, wbo.offsets, wbo.ping_min_blocks);
-        if(wbo.capture) loops[i]->use_wideband_capture(wbo.capture_dir, wbo.offsets, wbo.capture_params.max_units);
-        if(wideband) loops[i]->use_wideband(&wb_api, wbo.levels);
+        if(wideband) loops[i]->use_wideband(&wideband_run);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
         {
@@ -739,101 +544,7 @@ int main(int argc, char* const argv[])
                       << ls.hops << " stream hops, " << ls.late << " late, worst latency " << ls.worst_ms << " ms" << std::endl;
     }
     std::cerr << "msk144hipdecoder: " << batches << " batches, " << total_hops << " stream hops, " << total_late << " late, worst latency " << worst << " ms" << std::endl;
-    if(wideband)
-    {
-        const long long clipped = loops[0]->wideband_clipped(), all = loops[0]->wideband_components();
-        std::cerr << "msk144hipdecoder: wideband: " << clipped << " of " << all << " channel I/Q components clipped to int8";
-        if(all) std::cerr << " (" << 100.0 * static_cast<double>(clipped) / static_cast<double>(all) << " %)";
-        std::cerr << (clipped && !wbo.agc ? "; lower --wideband-gain" : "") << std::endl;
-        msk144_wideband_blanker_counts bc{};
-        if(wbo.blanker && wb_api.blanker_stats(loops[0]->decoder().handle(), &bc) == MSK144_OK)  // MSK144_ESTATE: no push was made
-            fprintf(stderr, "msk144hipdecoder: wideband blanker: threshold %g x mean power, guard %d+%d samples, %lld hits, %lld of %lld samples blanked (%.4f %%)\n",
-                    wbo.blanker_params.threshold_q4 / 16.0, wbo.blanker_params.pre, wbo.blanker_params.post, static_cast<long long>(bc.total_hits),
-                    static_cast<long long>(bc.total_blanked), static_cast<long long>(bc.total_samples),
-                    bc.total_samples ? 100.0 * static_cast<double>(bc.total_blanked) / static_cast<double>(bc.total_samples) : 0.0);
-        if(wbo.spectrum)
-        {
-            const DeviceLoop::SpectrumSummary sm = loops[0]->wideband_spectrum_summary();
-            if(sm.segments)
-                fprintf(stderr, "msk144hipdecoder: wideband spectrum: %d bins of %.1f Hz over %lld segments, floor (median bin) %.2f dBFS, highest bin %.2f dBFS at %+.0f Hz\n",
-                        wbo.spectrum_bins, static_cast<double>(wbo.rate_hz) / wbo.spectrum_bins, sm.segments, sm.median_dbfs, sm.peak_dbfs, sm.peak_hz);
-        }
-        if(wbo.pings)
-        {
-            const msk144wb::PingTracker& tr = loops[0]->wideband_ping_tracker();
-            const std::vector<int64_t>& ev = tr.channel_events();
-            const std::vector<int64_t>& up = tr.channel_up_blocks();
-            std::vector<int> active;
-            for(int c = 0; c < static_cast<int>(ev.size()); c++)
-                if(ev[static_cast<size_t>(c)]) active.push_back(c);
-            const int with_events = static_cast<int>(active.size());
-            std::stable_sort(active.begin(), active.end(), [&](int a, int b) {
-                return ev[static_cast<size_t>(a)] != ev[static_cast<size_t>(b)] ? ev[static_cast<size_t>(a)] > ev[static_cast<size_t>(b)] : up[static_cast<size_t>(a)] > up[static_cast<size_t>(b)];
-            });
-            std::string line = "msk144hipdecoder: wideband pings: " + std::to_string(tr.events()) + " events on " + std::to_string(with_events) + " of " + std::to_string(ev.size()) +
-                               " channels, " + std::to_string(tr.up_blocks()) + " of " + std::to_string(tr.total_blocks()) + " blocks up";
-            char buf[96];
-            if(wbo.ping_band)
-            {
-                snprintf(buf, sizeof(buf), ", band %d +-%d Hz shift %d", wbo.ping_band_centre, wbo.ping_band_halfwidth, ping_band_shift);
-                line += buf;
-            }
-            for(size_t i = 0; i < 3 && i < active.size(); i++)
-            {
-                snprintf(buf, sizeof(buf), "%s ch=%d (%lld)", i ? "" : "; most active", active[i], static_cast<long long>(ev[static_cast<size_t>(active[i])]));
-                line += buf;
-            }
-            std::cerr << line << std::endl;
-        }
-        if(wbo.waterfall)
-        {
-            std::string line = "msk144hipdecoder: wideband waterfall: " + std::to_string(loops[0]->wideband_waterfall_rows()) + " rows written";
-            const std::vector<DeviceLoop::WaterfallCarrier> carriers = loops[0]->wideband_waterfall_carriers();
-            line += carriers.empty() ? "; no channel has a bin 10 dB over its median bin" : "; a bin 10 dB or more over the channel's median bin:";
-            char buf[96];
-            for(const DeviceLoop::WaterfallCarrier& c : carriers)
-            {
-                snprintf(buf, sizeof(buf), " ch=%d %+d Hz (+%.1f dB)", c.channel, c.hz, c.excess_db);
-                line += buf;
-            }
-            std::cerr << line << std::endl;
-        }
-        if(wbo.capture)
-        {
-            const msk144wb::CaptureSegments& cs = loops[0]->wideband_capture_segments();
-            fprintf(stderr, "msk144hipdecoder: wideband capture: %lld segments, %lld hops written, %lld bytes, %lld units dropped\n", static_cast<long long>(cs.segments()),
-                    static_cast<long long>(cs.hops()), static_cast<long long>(cs.bytes()), loops[0]->wideband_capture_dropped());
-        }
-        if(wbo.levels)
-        {
-            const std::vector<DeviceLoop::ChannelLevel>& lv = loops[0]->wideband_levels();
-            std::vector<int> by_clip, by_rms;
-            for(int c = 0; c < static_cast<int>(lv.size()); c++)
-            {
-                fprintf(stderr, "msk144hipdecoder: wideband level ch=%d offset=%d Hz rms=%.2f LSB clipped=%lld gain=%g exp=%d..%d\n", c, wbo.offsets[static_cast<size_t>(c)],
-                        lv[static_cast<size_t>(c)].rms(), lv[static_cast<size_t>(c)].clipped, static_cast<double>(lv[static_cast<size_t>(c)].gain),
-                        lv[static_cast<size_t>(c)].min_exp, lv[static_cast<size_t>(c)].max_exp);
-                by_clip.push_back(c);
-                by_rms.push_back(c);
-            }
-            std::stable_sort(by_clip.begin(), by_clip.end(), [&](int a, int b) { return lv[static_cast<size_t>(a)].clipped > lv[static_cast<size_t>(b)].clipped; });
-            std::stable_sort(by_rms.begin(), by_rms.end(), [&](int a, int b) { return lv[static_cast<size_t>(a)].rms() < lv[static_cast<size_t>(b)].rms(); });
-            std::string line = "msk144hipdecoder: wideband levels: most clipped";
-            char buf[96];
-            for(size_t i = 0; i < 3 && i < by_clip.size(); i++)
-            {
-                snprintf(buf, sizeof(buf), " ch=%d (%lld)", by_clip[i], lv[static_cast<size_t>(by_clip[i])].clipped);
-                line += buf;
-            }
-            line += "; quietest";
-            for(size_t i = 0; i < 3 && i < by_rms.size(); i++)
-            {
-                snprintf(buf, sizeof(buf), " ch=%d (%.2f LSB)", by_rms[i], lv[static_cast<size_t>(by_rms[i])].rms());
-                line += buf;
-            }
-            std::cerr << line << std::endl;
-        }
-    }
+    if(wideband) wideband_run.print_summary(loops[0]->decoder().handle());
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {
@@ -858,9 +569,6 @@ int main(int argc, char* const argv[])
                         dev[MSK144_T_H2D], dev[MSK144_T_FRONTEND], dev[MSK144_T_SCAN], dev[MSK144_T_SOFTBITS], dev[MSK144_T_INDEX], dev[MSK144_T_LDPC], dev[MSK144_T_COLLECT], dev[MSK144_T_D2H]);
         }
     }
-    if(spectrum_file) fclose(spectrum_file);
-    if(pings_file) fclose(pings_file);
-    if(waterfall_file) fclose(waterfall_file);
     std::cout << "Done" << std::endl;
     return 0;
 }

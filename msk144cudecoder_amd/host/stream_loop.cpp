@@ -1,5 +1,7 @@
 #include "stream_loop.h"
 
+#include "wideband_run.h"
+
 #include <fcntl.h>
 #include <poll.h>
 #include <sys/stat.h>
@@ -205,73 +207,41 @@ int DeviceLoop::join()
         if(s.worst_ms > stats_.worst_ms) stats_.worst_ms = s.worst_ms;
     }
     if(!failed && dec_.ok()) stats_.have_device_ms = dec_.stage_times(stats_.device_ms);
-    if(!failed && wb_ && wb_pending_components_)
+    // --wideband-rate: what the last push left, then the end of the stream (both threads have ended: this thread may touch wb_)
+    if(wb_ && !failed && !wb_->read_push(dec_.handle()))
     {
-        int64_t clipped = 0;
-        if(wb_->clip(dec_.handle(), &clipped) == MSK144_OK) wb_clipped_ += clipped;
-        if(wb_read_levels_) read_wideband_levels();
-        if(wb_spec_file_) read_wideband_spectrum();
-        if(wb_ping_file_) read_wideband_pings();
-        else
-        {
-            if(wb_wf_file_) read_wideband_waterfall();
-            if(wb_cap_segments_ && !read_wideband_capture()) failed = true;
-        }
-        wb_components_ += wb_pending_components_;
-        wb_pending_components_ = 0;
+        fail(wb_->error());
+        failed = true;
     }
-    if(wb_spec_file_ && wb_spec_group_pushes_) write_spectrum_line();  // the last, shorter group
-    if(wb_ping_file_)
+    if(wb_ && !wb_->finish())
     {
-        wb_ping_tracker_->close(wb_ping_events_);  // the end of the stream closes every open run
-        if(wb_wf_spectra_) wb_wf_spectra_->close(wb_ping_freqs_);
-        if(!write_ping_events()) failed = true;
-    }
-    if(wb_cap_segments_ && !wb_cap_segments_->close())  // ... and every open segment
-    {
-        fail("--wideband-capture: cannot write capture.log: " + std::string(strerror(errno)));
+        fail(wb_->error());
         failed = true;
     }
     return failed ? 2 : 0;
 }
 
-// --wideband-rate: copy the push into the slot's pinned wideband buffer and run channeliser + decode on it.  The clip count of the
-// previous push is read first (it waits for that push's kernels; the GPU runs the hops one after another anyway).
+// --wideband-rate: copy the push into the slot's pinned wideband buffer and run channeliser + decode on it.  What the
+// previous push left is read first (WidebandRun::read_push; it waits for that push's kernels; the GPU runs the hops one after
+// another anyway).
 bool DeviceLoop::submit_wideband(Batch& b)
 {
     const auto a0 = Clock::now();
     void* buf = nullptr;
     size_t cap = 0;
-    if(wb_->slot(dec_.handle(), b.slot, &buf, &cap) != MSK144_OK || wb_block_.size() > cap)
+    if(wb_->api().slot(dec_.handle(), b.slot, &buf, &cap) != MSK144_OK || wb_block_.size() > cap)
     {
         fail(wb_block_.size() > cap ? std::string("wideband push larger than the slot") : std::string(msk144_last_error(dec_.handle())));
         return false;
     }
-    if(wb_pending_components_)
+    if(!wb_->read_push(dec_.handle()))
     {
-        int64_t clipped = 0;
-        if(wb_->clip(dec_.handle(), &clipped) != MSK144_OK)
-        {
-            fail(msk144_last_error(dec_.handle()));
-            return false;
-        }
-        wb_clipped_ += clipped;
-        wb_components_ += wb_pending_components_;
-        if((wb_read_levels_ && !read_wideband_levels()) || (wb_spec_file_ && !read_wideband_spectrum()) || (wb_ping_file_ ? !read_wideband_pings() : ((wb_wf_file_ && !read_wideband_waterfall()) || (wb_cap_segments_ && !read_wideband_capture()))))
-        {
-            // a reader that could not write its file has said why itself; the library's last error is then not the cause
-            bool said;
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                said = failed_;
-            }
-            if(!said) fail(msk144_last_error(dec_.handle()));
-            return false;
-        }
+        fail(wb_->error());
+        return false;
     }
     memcpy(buf, wb_block_.data(), wb_block_.size());
     const bool first = wb_first_;
-    wb_pending_components_ = 2ll * nch_ * (first ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES);
+    wb_->pushed(first);
     for(int c = 0; c < nch_; c++)
     {
         Stream& s = st_[c];
@@ -281,7 +251,7 @@ bool DeviceLoop::submit_wideband(Batch& b)
         s.ready = false;
     }
     const auto a1 = Clock::now();
-    if(!dec_.submit_wideband(b.slot, first, wb_->push))
+    if(!dec_.submit_wideband(b.slot, first, wb_->api().push))
     {
         fail(dec_.error());
         return false;
@@ -290,224 +260,6 @@ bool DeviceLoop::submit_wideband(Batch& b)
     b.assemble_ms = ms_between(a0, a1);
     b.submit_ms = ms_between(a1, Clock::now());
     return true;
-}
-
-// --wideband-levels: the levels of the push just made (read where its clip count is read), summed per channel
-bool DeviceLoop::read_wideband_levels()
-{
-    wb_level_buf_.resize(static_cast<size_t>(nch_));
-    if(wb_->levels(dec_.handle(), wb_level_buf_.data()) != MSK144_OK) return false;
-    const bool fresh = wb_levels_.empty();
-    wb_levels_.resize(static_cast<size_t>(nch_));
-    for(int c = 0; c < nch_; c++)
-    {
-        const msk144_wideband_level& v = wb_level_buf_[static_cast<size_t>(c)];
-        ChannelLevel& a = wb_levels_[static_cast<size_t>(c)];
-        a.samples += v.samples;
-        a.sum_sq += v.sum_sq;
-        a.clipped += v.clipped;
-        a.gain = v.gain;
-        a.min_exp = fresh ? v.exponent : std::min(a.min_exp, static_cast<int>(v.exponent));
-        a.max_exp = fresh ? v.exponent : std::max(a.max_exp, static_cast<int>(v.exponent));
-    }
-    return true;
-}
-
-void DeviceLoop::use_wideband_pings(FILE* file, int min_blocks, const std::vector<int32_t>& offsets)
-{
-    wb_ping_file_ = file;
-    wb_ping_offsets_ = offsets;
-    wb_ping_tracker_.reset(new msk144wb::PingTracker(static_cast<int>(offsets.size()), min_blocks));
-    wb_ping_buf_.resize(offsets.size());
-    wb_ping_energies_.resize(offsets.size() * msk144wb::kPingMaxBlocks);
-}
-
-// --wideband-pings: the records and block energies of the push just made (read where its clip count is read) to the event tracker
-bool DeviceLoop::read_wideband_pings()
-{
-    static_assert(sizeof(msk144_wideband_ping) == sizeof(msk144wb::PingRecord), "the tracker reads msk144_wideband_ping");
-    int32_t nb = 0;
-    if(wb_->pings(dec_.handle(), wb_ping_buf_.data()) != MSK144_OK || wb_->ping_blocks(dec_.handle(), -1, wb_ping_energies_.data(), &nb) != MSK144_OK) return false;
-    wb_ping_tracker_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_ping_energies_.data(), wb_ping_events_);
-    if(wb_wf_file_ && !read_wideband_waterfall()) return false;  // the same push's rows: the frequencies of the events that closed
-    if(wb_cap_segments_ && !read_wideband_capture()) return false;  // the same push's units: the files of the events that closed
-    return write_ping_events();
-}
-
-// with --wideband-waterfall event k of the tracker has frequency k of PingSpectra, which follows the same records; the two rules
-// disagreeing on the events of a push is a defect of the program: it ends the run instead of writing lines without the field
-bool DeviceLoop::write_ping_events()
-{
-    if(wb_wf_spectra_ && wb_ping_freqs_.size() != wb_ping_events_.size())
-    {
-        fail("ping events and their frequencies disagree: " + std::to_string(wb_ping_events_.size()) + " events, " + std::to_string(wb_ping_freqs_.size()) + " frequencies");
-        return false;
-    }
-    for(size_t k = 0; k < wb_ping_events_.size(); k++)
-    {
-        const msk144wb::PingEvent& e = wb_ping_events_[k];
-        std::string line = msk144wb::ping_event_line(e, wb_ping_offsets_[static_cast<size_t>(e.channel)]);
-        if(wb_wf_spectra_) line += " freq=" + std::to_string(wb_ping_freqs_[k]);
-        if(wb_cap_segments_) line += wb_cap_segments_->locate(e.channel, e.start);
-        fprintf(wb_ping_file_, "%s\n", line.c_str());
-    }
-    if(!wb_ping_events_.empty()) fflush(wb_ping_file_);
-    wb_ping_events_.clear();
-    wb_ping_freqs_.clear();
-    return true;
-}
-
-void DeviceLoop::use_wideband_capture(const std::string& dir, const std::vector<int32_t>& offsets, int max_units)
-{
-    wb_cap_segments_.reset(new msk144wb::CaptureSegments(dir, offsets));
-    wb_cap_units_.resize(static_cast<size_t>(max_units));
-    wb_cap_data_.resize(static_cast<size_t>(max_units) * msk144wb::kCaptureUnitBytes);
-}
-
-// --wideband-capture: the units of the push just made (read where its ping records are read) to their segment files
-bool DeviceLoop::read_wideband_capture()
-{
-    static_assert(sizeof(msk144_wideband_capture_unit) == sizeof(msk144wb::CaptureUnit), "the segments read msk144_wideband_capture_unit");
-    int32_t count = 0, total = 0;
-    if(wb_->capture(dec_.handle(), wb_cap_units_.data(), wb_cap_data_.data(), &count, &total) != MSK144_OK) return false;
-    wb_cap_dropped_ += total - count;
-    if(wb_cap_segments_->push(reinterpret_cast<const msk144wb::CaptureUnit*>(wb_cap_units_.data()), wb_cap_data_.data(), count)) return true;
-    fail("--wideband-capture: cannot write a segment: " + std::string(strerror(errno)));
-    return false;
-}
-
-void DeviceLoop::use_wideband_waterfall(FILE* file, bool by_pings, const std::vector<int32_t>& channels, const std::vector<int32_t>& offsets, int min_blocks)
-{
-    wb_wf_file_ = file;
-    wb_wf_by_pings_ = by_pings;
-    wb_wf_channels_ = channels;
-    wb_wf_offsets_ = offsets;
-    if(wb_ping_file_) wb_wf_spectra_.reset(new msk144wb::PingSpectra(static_cast<int>(offsets.size()), min_blocks));
-    wb_wf_full_ = msk144wb::waterfall_full(nullptr);
-    wb_wf_rows_.assign(offsets.size() * msk144wb::kWaterfallRows * msk144wb::kWaterfallBins, 0.0f);
-    wb_wf_sums_.assign(offsets.size() * msk144wb::kWaterfallBins, 0.0);
-    wb_wf_run_ = wb_wf_sums_;
-}
-
-// --wideband-waterfall: the rows and sums of the push just made (read where its clip count is read, behind its ping records)
-bool DeviceLoop::read_wideband_waterfall()
-{
-    constexpr size_t B = msk144wb::kWaterfallBins, R = msk144wb::kWaterfallRows;
-    const size_t C = wb_wf_offsets_.size();
-    const int nb = static_cast<int>(wb_wf_pushes_ ? R / 2 : R);  // a first push, then hops
-    // the channels whose rows are needed: the listed ones, and with the ping detector those with an up block
-    std::vector<int32_t> need = wb_wf_channels_;
-    for(size_t c = 0; wb_wf_spectra_ && c < C; c++)
-        if(wb_ping_buf_[c].up_mask && std::find(need.begin(), need.end(), static_cast<int32_t>(c)) == need.end()) need.push_back(static_cast<int32_t>(c));
-    int32_t n = nb;
-    if(need.size() > static_cast<size_t>(msk144wb::kWaterfallHandful))
-    {
-        if(wb_->waterfall(dec_.handle(), -1, wb_wf_rows_.data(), &n) != MSK144_OK) return false;
-    }
-    else
-        for(int32_t c : need)
-            if(wb_->waterfall(dec_.handle(), c, wb_wf_rows_.data() + static_cast<size_t>(c) * R * B, &n) != MSK144_OK) return false;
-    if(n != nb || wb_->waterfall_sums(dec_.handle(), wb_wf_sums_.data()) != MSK144_OK) return false;
-    for(size_t k = 0; k < wb_wf_sums_.size(); k++) wb_wf_run_[k] += wb_wf_sums_[k];
-
-    const auto write = [&](size_t c, int b) {
-        fprintf(wb_wf_file_, "%s\n",
-                msk144wb::waterfall_line(static_cast<int32_t>(c), wb_wf_offsets_[c], wb_wf_base_ + b, wb_wf_rows_.data() + (c * R + static_cast<size_t>(b)) * B, wb_wf_full_).c_str());
-        wb_wf_written_++;
-    };
-    const long long before = wb_wf_written_;
-    if(!wb_wf_by_pings_)
-        for(int32_t c : wb_wf_channels_)
-            for(int b = 0; b < nb; b++) write(static_cast<size_t>(c), b);
-    else
-        for(size_t c = 0; c < C; c++)
-            for(int b = 0; b < nb; b++)
-                if((wb_ping_buf_[c].up_mask >> b) & 1) write(c, b);
-    if(wb_wf_written_ != before) fflush(wb_wf_file_);
-    if(wb_wf_spectra_) wb_wf_spectra_->push(reinterpret_cast<const msk144wb::PingRecord*>(wb_ping_buf_.data()), wb_wf_rows_.data(), wb_ping_freqs_);
-    wb_wf_base_ += nb;
-    wb_wf_pushes_++;
-    return true;
-}
-
-std::vector<DeviceLoop::WaterfallCarrier> DeviceLoop::wideband_waterfall_carriers() const
-{
-    std::vector<WaterfallCarrier> out;
-    for(size_t c = 0; c < wb_wf_offsets_.size(); c++)
-    {
-        int j = 0;
-        const double excess = msk144wb::waterfall_excess_db(&wb_wf_run_[c * msk144wb::kWaterfallBins], j);
-        if(excess >= msk144wb::kWaterfallCarrierDb) out.push_back(WaterfallCarrier{static_cast<int>(c), msk144wb::waterfall_hz(j), excess});
-    }
-    std::stable_sort(out.begin(), out.end(), [](const WaterfallCarrier& a, const WaterfallCarrier& b) { return a.excess_db > b.excess_db; });
-    if(out.size() > 3) out.resize(3);
-    return out;
-}
-
-void DeviceLoop::use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz)
-{
-    wb_spec_file_ = file;
-    wb_spec_hops_ = hops;
-    wb_spec_rate_ = rate_hz;
-    // 0 dBFS is S (sum w)^2 of the window the device holds: the default one, rounded to f32
-    double sum = 0.0;
-    for(double v : msk144wb::spectrum_window(bins)) sum += static_cast<double>(static_cast<float>(v));
-    wb_spec_full_ = sum * sum;
-    wb_spec_buf_.assign(static_cast<size_t>(bins), 0.0);
-    wb_spec_group_ = wb_spec_run_ = wb_spec_buf_;
-}
-
-namespace
-{
-double spectrum_dbfs(double power, double full)
-{
-    const double db = power > 0.0 && full > 0.0 ? 10.0 * std::log10(power / full) : -200.0;
-    return db < -200.0 ? -200.0 : std::round(db * 100.0) / 100.0 + 0.0;  // two decimals, and no "-0.00"
-}
-}  // namespace
-
-// --wideband-spectrum: the spectrum of the push just made (read where its clip count is read), added to the open group and the run
-bool DeviceLoop::read_wideband_spectrum()
-{
-    int64_t segments = 0;
-    if(wb_->spectrum(dec_.handle(), wb_spec_buf_.data(), &segments) != MSK144_OK) return false;
-    for(size_t j = 0; j < wb_spec_buf_.size(); j++)
-    {
-        wb_spec_group_[j] += wb_spec_buf_[j];
-        wb_spec_run_[j] += wb_spec_buf_[j];
-    }
-    wb_spec_group_segments_ += segments;
-    wb_spec_run_segments_ += segments;
-    wb_spec_group_pushes_++;
-    wb_spec_pushes_++;
-    if(wb_spec_group_pushes_ == wb_spec_hops_) write_spectrum_line();
-    return true;
-}
-
-void DeviceLoop::write_spectrum_line()
-{
-    fprintf(wb_spec_file_, "hop=%lld rate=%lld bins=%zu segments=%lld dbfs=", wb_spec_pushes_ - 1, wb_spec_rate_, wb_spec_group_.size(), wb_spec_group_segments_);
-    const double full = static_cast<double>(wb_spec_group_segments_) * wb_spec_full_;
-    for(size_t j = 0; j < wb_spec_group_.size(); j++) fprintf(wb_spec_file_, j ? ",%.2f" : "%.2f", spectrum_dbfs(wb_spec_group_[j], full));
-    fputc('\n', wb_spec_file_);
-    fflush(wb_spec_file_);
-    std::fill(wb_spec_group_.begin(), wb_spec_group_.end(), 0.0);
-    wb_spec_group_segments_ = wb_spec_group_pushes_ = 0;
-}
-
-DeviceLoop::SpectrumSummary DeviceLoop::wideband_spectrum_summary() const
-{
-    SpectrumSummary r;
-    if(!wb_spec_run_segments_) return r;
-    r.segments = wb_spec_run_segments_;
-    const double full = static_cast<double>(wb_spec_run_segments_) * wb_spec_full_;
-    const size_t B = wb_spec_run_.size(), top = static_cast<size_t>(std::max_element(wb_spec_run_.begin(), wb_spec_run_.end()) - wb_spec_run_.begin());
-    std::vector<double> sorted = wb_spec_run_;
-    std::nth_element(sorted.begin(), sorted.begin() + B / 2, sorted.end());
-    r.median_dbfs = spectrum_dbfs(sorted[B / 2], full);
-    r.peak_dbfs = spectrum_dbfs(wb_spec_run_[top], full);
-    r.peak_hz = (static_cast<double>(top) - static_cast<double>(B / 2)) * static_cast<double>(wb_spec_rate_) / static_cast<double>(B);
-    return r;
 }
 
 DeviceLoop::StreamReport DeviceLoop::stream_report(int local) const

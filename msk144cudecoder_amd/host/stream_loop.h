@@ -9,16 +9,12 @@
 // local index.
 #pragma once
 
-#include "wideband_cli.h"
 #include "window_decoder.h"
 
 #include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstdio>
 #include <condition_variable>
 #include <deque>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -28,6 +24,7 @@ namespace msk144host
 {
 
 using Clock = std::chrono::steady_clock;
+class WidebandRun;
 
 struct LoopOptions
 {
@@ -94,55 +91,13 @@ public:
     // --interleaved: the hops arrive through feed() instead (one reader thread splits stdin between the loops)
     void use_feed() { fed_ = true; }
     // --wideband-rate: the blocks arrive through feed_raw() and are wideband samples - one push of the channeliser, which writes
-    // the hop of every stream of this loop on the device (msk144_set_wideband has been called on decoder().handle())
-    // levels: msk144_wideband_levels is read once per push and accumulated per channel (--wideband-levels)
-    void use_wideband(const WidebandApi* api, bool levels = false)
+    // the hop of every stream of this loop on the device.  `run` (wideband_run.h) has configured decoder().handle(); the loop reads
+    // what a push left through it before it stages the next one, and once more in join(), which also finishes it.
+    void use_wideband(WidebandRun* run)
     {
         fed_ = true;
-        wb_ = api;
-        wb_read_levels_ = levels;
+        wb_ = run;
     }
-
-    // --wideband-spectrum: msk144_wideband_spectrum is read once per push, where its clip count is read, and summed in double; after
-    // every `hops` pushes (and for a last, shorter group in join()) one line goes to `file`:
-    // hop=<index of the last push> rate=<Fs> bins=<B> segments=<sum> dbfs=<v0>,<v1>,...  in ascending frequency, two decimals,
-    // 0 dBFS = a full-scale tone on a bin centre (include/msk144hip.h), floored at -200
-    void use_wideband_spectrum(FILE* file, int bins, int hops, long long rate_hz);
-    // over the run: the median bin (the floor) and the highest bin with its frequency from the centre; segments 0: no push was read
-    // --wideband-pings: msk144_wideband_pings and the block energies are read once per push, where its clip count is read; every
-    // event that closes (csrc/wideband.h PingTracker) is appended to `file` as one line and flushed, the open ones when the stream ends
-    void use_wideband_pings(FILE* file, int min_blocks, const std::vector<int32_t>& offsets);
-    const msk144wb::PingTracker& wideband_ping_tracker() const { return *wb_ping_tracker_; }
-    // --wideband-waterfall: after every push one line per selected row is appended to `file` (csrc/wideband.h waterfall_line) - every
-    // block of the listed channels, or with by_pings every up block of every channel (needs use_wideband_pings) - and the sums are
-    // added to the run's.  Rows are read only for the channels that need them: the listed ones and, with the ping detector, those
-    // with an up block; more than a handful in one copy of all.  With the ping detector every event line gains ` freq=<Hz>`
-    // (csrc/wideband.h PingSpectra).  Call it after use_wideband_pings.
-    void use_wideband_waterfall(FILE* file, bool by_pings, const std::vector<int32_t>& channels, const std::vector<int32_t>& offsets, int min_blocks);
-    // over the run: the rows written and up to three channels whose summed spectrum has a bin at least 10 dB
-    // (msk144wb::kWaterfallCarrierDb) over the channel's median bin, the largest excess first
-    struct WaterfallCarrier
-    {
-        int channel = 0;
-        int32_t hz = 0;
-        double excess_db = 0.0;
-    };
-    long long wideband_waterfall_rows() const { return wb_wf_written_; }
-    std::vector<WaterfallCarrier> wideband_waterfall_carriers() const;
-
-    // --wideband-capture: msk144_wideband_capture is read once per push, where its ping records are read, and the units go to
-    // segment files under `dir` (csrc/wideband.h CaptureSegments).  With the ping detector every event line gains
-    // ` file=<name> at=<sample>` (` file=-`: the hop was dropped).  Call it after use_wideband_pings.
-    void use_wideband_capture(const std::string& dir, const std::vector<int32_t>& offsets, int max_units);
-    const msk144wb::CaptureSegments& wideband_capture_segments() const { return *wb_cap_segments_; }
-    long long wideband_capture_dropped() const { return wb_cap_dropped_; }
-
-    struct SpectrumSummary
-    {
-        long long segments = 0;
-        double median_dbfs = 0.0, peak_dbfs = 0.0, peak_hz = 0.0;
-    };
-    SpectrumSummary wideband_spectrum_summary() const;
 
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
@@ -151,18 +106,6 @@ public:
     void feed_end();
     // --wideband-rate: one push of raw wideband samples (5184 x P/Q the first time, 2592 x P/Q afterwards; P/Q = D for an integer rate)
     bool feed_raw(const unsigned char* data, size_t bytes);
-    // clipped I/Q components of the channeliser output over the run, and all components written (valid after join())
-    long long wideband_clipped() const { return wb_clipped_; }
-    long long wideband_components() const { return wb_components_; }
-    // --wideband-levels: every channel's statistics summed over the run, the gain of its last push, the AGC exponents it saw
-    struct ChannelLevel
-    {
-        long long samples = 0, sum_sq = 0, clipped = 0;
-        float gain = 0.0f;
-        int min_exp = 0, max_exp = 0;
-        double rms() const { return samples ? std::sqrt(static_cast<double>(sum_sq) / (2.0 * static_cast<double>(samples))) : 0.0; }
-    };
-    const std::vector<ChannelLevel>& wideband_levels() const { return wb_levels_; }
     int join();  // 0, or 2 after a library failure (already logged)
 
     const LoopStats& stats() const { return stats_; }
@@ -208,13 +151,6 @@ private:
     void fail(const std::string& what);
     bool enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream);
     bool submit_wideband(Batch& b);
-    bool read_wideband_levels();
-    bool read_wideband_spectrum();
-    bool read_wideband_pings();
-    bool read_wideband_waterfall();
-    bool read_wideband_capture();
-    bool write_ping_events();
-    void write_spectrum_line();
 
     WindowDecoder dec_;
     const int nch_, base_, device_;
@@ -222,36 +158,9 @@ private:
     LinePrinter& out_;
     std::string error_;
     bool fed_ = false;
-    const WidebandApi* wb_ = nullptr;
+    WidebandRun* wb_ = nullptr;
     std::vector<unsigned char> wb_block_;  // the push the ingest thread has taken from the queue
     bool wb_first_ = true;
-    long long wb_clipped_ = 0, wb_components_ = 0, wb_pending_components_ = 0;
-    bool wb_read_levels_ = false;
-    std::vector<ChannelLevel> wb_levels_;
-    std::vector<msk144_wideband_level> wb_level_buf_;
-    FILE* wb_spec_file_ = nullptr;
-    int wb_spec_hops_ = 0;
-    long long wb_spec_rate_ = 0, wb_spec_pushes_ = 0;  // pushes read so far
-    double wb_spec_full_ = 0.0;                        // (sum w)^2 of the default window
-    std::vector<double> wb_spec_buf_, wb_spec_group_, wb_spec_run_;  // the last push, the open group, the run
-    FILE* wb_ping_file_ = nullptr;
-    std::unique_ptr<msk144wb::PingTracker> wb_ping_tracker_;
-    std::vector<int32_t> wb_ping_offsets_, wb_ping_energies_;
-    std::vector<msk144_wideband_ping> wb_ping_buf_;
-    std::vector<msk144wb::PingEvent> wb_ping_events_;
-    FILE* wb_wf_file_ = nullptr;
-    bool wb_wf_by_pings_ = false;
-    std::vector<int32_t> wb_wf_channels_, wb_wf_offsets_, wb_ping_freqs_;
-    std::unique_ptr<msk144wb::PingSpectra> wb_wf_spectra_;
-    std::vector<float> wb_wf_rows_;                 // [channels][54][96], the rows of the channels read
-    std::vector<double> wb_wf_sums_, wb_wf_run_;    // [channels][96]: the last push, the run
-    double wb_wf_full_ = 1.0;                       // (sum w)^2 of the default window
-    long long wb_wf_pushes_ = 0, wb_wf_base_ = 0, wb_wf_written_ = 0;  // pushes read, blocks of all earlier pushes, rows written
-    std::unique_ptr<msk144wb::CaptureSegments> wb_cap_segments_;
-    std::vector<msk144_wideband_capture_unit> wb_cap_units_;  // [max_units]
-    std::vector<int8_t> wb_cap_data_;                         // [max_units][5184]
-    long long wb_cap_dropped_ = 0;
-    long long wb_spec_group_segments_ = 0, wb_spec_group_pushes_ = 0, wb_spec_run_segments_ = 0;
 
     size_t win_bytes_ = 0, half_ = 0, unit_ = 0;
     std::vector<Stream> st_;

@@ -8,130 +8,16 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
 namespace msk144host
 {
-
-struct WidebandApi
-{
-    int (*set)(msk144_handle*, const msk144_wideband_params*) = nullptr;
-    int (*slot)(msk144_handle*, int32_t, void**, size_t*) = nullptr;
-    int (*push)(msk144_handle*, int32_t, int32_t) = nullptr;
-    int (*clip)(msk144_handle*, int64_t*) = nullptr;
-    // --wideband-gain=auto, --wideband-levels: resolved only when one of them is given (load_levels)
-    int (*levels)(msk144_handle*, msk144_wideband_level*) = nullptr;
-    int (*set_gains)(msk144_handle*, const float*) = nullptr;
-    int (*set_agc)(msk144_handle*, const msk144_wideband_agc*) = nullptr;
-
-    bool load_levels(std::string& err)
-    {
-        levels = reinterpret_cast<decltype(levels)>(dlsym(RTLD_DEFAULT, "msk144_wideband_levels"));
-        set_gains = reinterpret_cast<decltype(set_gains)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_gains"));
-        set_agc = reinterpret_cast<decltype(set_agc)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_agc"));
-        if(levels && set_gains && set_agc) return true;
-        err = "the loaded libmsk144hip has no per-channel levels or AGC (msk144_wideband_levels): --wideband-gain=auto and --wideband-levels need them";
-        return false;
-    }
-
-    // --wideband-blanker: resolved only when it is given (load_blanker)
-    int (*set_blanker)(msk144_handle*, const msk144_wideband_blanker*) = nullptr;
-    int (*blanker_stats)(msk144_handle*, msk144_wideband_blanker_counts*) = nullptr;
-
-    bool load_blanker(std::string& err)
-    {
-        set_blanker = reinterpret_cast<decltype(set_blanker)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_blanker"));
-        blanker_stats = reinterpret_cast<decltype(blanker_stats)>(dlsym(RTLD_DEFAULT, "msk144_wideband_blanker_stats"));
-        if(set_blanker && blanker_stats) return true;
-        err = std::string("the loaded libmsk144hip has no impulse-noise blanker (") + (set_blanker ? "msk144_wideband_blanker_stats" : "msk144_set_wideband_blanker") +
-              "): --wideband-blanker needs it";
-        return false;
-    }
-
-    // --wideband-spectrum: resolved only when it is given (load_spectrum)
-    int (*set_spectrum)(msk144_handle*, const msk144_wideband_spectrum_params*) = nullptr;
-    int (*spectrum)(msk144_handle*, double*, int64_t*) = nullptr;
-
-    bool load_spectrum(std::string& err)
-    {
-        set_spectrum = reinterpret_cast<decltype(set_spectrum)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_spectrum"));
-        spectrum = reinterpret_cast<decltype(spectrum)>(dlsym(RTLD_DEFAULT, "msk144_wideband_spectrum"));
-        if(set_spectrum && spectrum) return true;
-        err = std::string("the loaded libmsk144hip has no input spectrum (") + (set_spectrum ? "msk144_wideband_spectrum" : "msk144_set_wideband_spectrum") +
-              "): --wideband-spectrum needs it";
-        return false;
-    }
-
-    // --wideband-pings: resolved only when it is given (load_pings)
-    int (*set_pings)(msk144_handle*, const msk144_wideband_pings_params*) = nullptr;
-    int (*pings)(msk144_handle*, msk144_wideband_ping*) = nullptr;
-    int (*ping_blocks)(msk144_handle*, int32_t, int32_t*, int32_t*) = nullptr;
-
-    bool load_pings(std::string& err)
-    {
-        set_pings = reinterpret_cast<decltype(set_pings)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_pings"));
-        pings = reinterpret_cast<decltype(pings)>(dlsym(RTLD_DEFAULT, "msk144_wideband_pings"));
-        ping_blocks = reinterpret_cast<decltype(ping_blocks)>(dlsym(RTLD_DEFAULT, "msk144_wideband_ping_blocks"));
-        if(set_pings && pings && ping_blocks) return true;
-        err = std::string("the loaded libmsk144hip has no ping detector (") + (!set_pings ? "msk144_set_wideband_pings" : !pings ? "msk144_wideband_pings" : "msk144_wideband_ping_blocks") +
-              "): --wideband-pings needs it";
-        return false;
-    }
-
-    // --wideband-pings-band: resolved only when it is given (load_ping_band)
-    int (*set_ping_band)(msk144_handle*, const msk144_wideband_ping_band_params*) = nullptr;
-
-    bool load_ping_band(std::string& err)
-    {
-        set_ping_band = reinterpret_cast<decltype(set_ping_band)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_ping_band"));
-        if(set_ping_band) return true;
-        err = "the loaded libmsk144hip has no ping band (msk144_set_wideband_ping_band): --wideband-pings-band needs it";
-        return false;
-    }
-
-    // --wideband-waterfall: resolved only when it is given (load_waterfall)
-    int (*set_waterfall)(msk144_handle*, const msk144_wideband_waterfall_params*) = nullptr;
-    int (*waterfall)(msk144_handle*, int32_t, float*, int32_t*) = nullptr;
-    int (*waterfall_sums)(msk144_handle*, double*) = nullptr;
-
-    bool load_waterfall(std::string& err)
-    {
-        set_waterfall = reinterpret_cast<decltype(set_waterfall)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_waterfall"));
-        waterfall = reinterpret_cast<decltype(waterfall)>(dlsym(RTLD_DEFAULT, "msk144_wideband_waterfall"));
-        waterfall_sums = reinterpret_cast<decltype(waterfall_sums)>(dlsym(RTLD_DEFAULT, "msk144_wideband_waterfall_sums"));
-        if(set_waterfall && waterfall && waterfall_sums) return true;
-        err = std::string("the loaded libmsk144hip has no waterfall (") +
-              (!set_waterfall ? "msk144_set_wideband_waterfall" : !waterfall ? "msk144_wideband_waterfall" : "msk144_wideband_waterfall_sums") + "): --wideband-waterfall needs it";
-        return false;
-    }
-
-    // --wideband-capture: resolved only when it is given (load_capture)
-    int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
-    int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
-
-    bool load_capture(std::string& err)
-    {
-        set_capture = reinterpret_cast<decltype(set_capture)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband_capture"));
-        capture = reinterpret_cast<decltype(capture)>(dlsym(RTLD_DEFAULT, "msk144_wideband_capture"));
-        if(set_capture && capture) return true;
-        err = std::string("the loaded libmsk144hip has no capture (") + (!set_capture ? "msk144_set_wideband_capture" : "msk144_wideband_capture") + "): --wideband-capture needs it";
-        return false;
-    }
-
-    bool load(std::string& err)
-    {
-        set = reinterpret_cast<decltype(set)>(dlsym(RTLD_DEFAULT, "msk144_set_wideband"));
-        slot = reinterpret_cast<decltype(slot)>(dlsym(RTLD_DEFAULT, "msk144_wideband_slot"));
-        push = reinterpret_cast<decltype(push)>(dlsym(RTLD_DEFAULT, "msk144_push_wideband"));
-        clip = reinterpret_cast<decltype(clip)>(dlsym(RTLD_DEFAULT, "msk144_wideband_clip_count"));
-        if(set && slot && push && clip) return true;
-        err = "the loaded libmsk144hip has no wideband channeliser (msk144_set_wideband)";
-        return false;
-    }
-};
 
 struct WidebandOptions
 {
@@ -171,6 +57,84 @@ struct WidebandOptions
     std::string parse_error;  // first malformed value
 };
 
+// The library entries of wideband mode.  The four of the channeliser are always resolved, those of an option only when it is given.
+struct WidebandApi
+{
+    int (*set)(msk144_handle*, const msk144_wideband_params*) = nullptr;
+    int (*slot)(msk144_handle*, int32_t, void**, size_t*) = nullptr;
+    int (*push)(msk144_handle*, int32_t, int32_t) = nullptr;
+    int (*clip)(msk144_handle*, int64_t*) = nullptr;
+    // --wideband-gain=auto, --wideband-levels
+    int (*levels)(msk144_handle*, msk144_wideband_level*) = nullptr;
+    int (*set_gains)(msk144_handle*, const float*) = nullptr;
+    int (*set_agc)(msk144_handle*, const msk144_wideband_agc*) = nullptr;
+    // --wideband-blanker
+    int (*set_blanker)(msk144_handle*, const msk144_wideband_blanker*) = nullptr;
+    int (*blanker_stats)(msk144_handle*, msk144_wideband_blanker_counts*) = nullptr;
+    // --wideband-spectrum
+    int (*set_spectrum)(msk144_handle*, const msk144_wideband_spectrum_params*) = nullptr;
+    int (*spectrum)(msk144_handle*, double*, int64_t*) = nullptr;
+    // --wideband-pings
+    int (*set_pings)(msk144_handle*, const msk144_wideband_pings_params*) = nullptr;
+    int (*pings)(msk144_handle*, msk144_wideband_ping*) = nullptr;
+    int (*ping_blocks)(msk144_handle*, int32_t, int32_t*, int32_t*) = nullptr;
+    // --wideband-pings-band
+    int (*set_ping_band)(msk144_handle*, const msk144_wideband_ping_band_params*) = nullptr;
+    // --wideband-waterfall
+    int (*set_waterfall)(msk144_handle*, const msk144_wideband_waterfall_params*) = nullptr;
+    int (*waterfall)(msk144_handle*, int32_t, float*, int32_t*) = nullptr;
+    int (*waterfall_sums)(msk144_handle*, double*) = nullptr;
+    // --wideband-capture
+    int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
+    int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
+
+    // Resolves the channeliser's entries and those of every option of `w`, group after group; false with the first group that lacks
+    // one: "the loaded libmsk144hip has no <feature> (<first missing symbol>)[: <who> need(s) it]".
+    bool resolve(const WidebandOptions& w, std::string& err)
+    {
+        struct Entry
+        {
+            const char* name;
+            void* pointer;  // the member that receives it
+        };
+        struct Group
+        {
+            bool wanted;
+            const char *feature, *needs;
+            std::vector<Entry> entries;
+        };
+        const Group groups[] = {
+            {true, "wideband channeliser", "", {{"msk144_set_wideband", &set}, {"msk144_wideband_slot", &slot}, {"msk144_push_wideband", &push}, {"msk144_wideband_clip_count", &clip}}},
+            {w.agc || w.levels, "per-channel levels or AGC", ": --wideband-gain=auto and --wideband-levels need them",
+             {{"msk144_wideband_levels", &levels}, {"msk144_set_wideband_gains", &set_gains}, {"msk144_set_wideband_agc", &set_agc}}},
+            {w.blanker, "impulse-noise blanker", ": --wideband-blanker needs it", {{"msk144_set_wideband_blanker", &set_blanker}, {"msk144_wideband_blanker_stats", &blanker_stats}}},
+            {w.spectrum, "input spectrum", ": --wideband-spectrum needs it", {{"msk144_set_wideband_spectrum", &set_spectrum}, {"msk144_wideband_spectrum", &spectrum}}},
+            {w.pings, "ping detector", ": --wideband-pings needs it", {{"msk144_set_wideband_pings", &set_pings}, {"msk144_wideband_pings", &pings}, {"msk144_wideband_ping_blocks", &ping_blocks}}},
+            {w.ping_band, "ping band", ": --wideband-pings-band needs it", {{"msk144_set_wideband_ping_band", &set_ping_band}}},
+            {w.waterfall, "waterfall", ": --wideband-waterfall needs it",
+             {{"msk144_set_wideband_waterfall", &set_waterfall}, {"msk144_wideband_waterfall", &waterfall}, {"msk144_wideband_waterfall_sums", &waterfall_sums}}},
+            {w.capture, "capture", ": --wideband-capture needs it", {{"msk144_set_wideband_capture", &set_capture}, {"msk144_wideband_capture", &capture}}},
+        };
+        for(const Group& g : groups)
+        {
+            if(!g.wanted) continue;
+            const char* missing = nullptr;
+            for(const Entry& e : g.entries)
+            {
+                void* p = dlsym(RTLD_DEFAULT, e.name);
+                std::memcpy(e.pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
+                if(!p && !missing) missing = e.name;
+            }
+            if(!missing) continue;
+            err = std::string("the loaded libmsk144hip has no ") + g.feature + " (" + missing + ")" + g.needs;
+            return false;
+        }
+        return true;
+    }
+};
+
+// ---- the shared parse helpers ----
+
 inline bool parse_int(const std::string& s, long long& v)
 {
     if(s.empty()) return false;
@@ -179,6 +143,55 @@ inline bool parse_int(const std::string& s, long long& v)
     v = std::strtoll(s.c_str(), &end, 10);
     return errno == 0 && end && *end == 0;
 }
+
+// an integer within lo..hi into `out`
+template <class T>
+inline bool parse_int_in(const std::string& s, long long lo, long long hi, T& out)
+{
+    long long v = 0;
+    if(!parse_int(s, v) || v < lo || v > hi) return false;
+    out = static_cast<T>(v);
+    return true;
+}
+
+// the fields of "a<sep>b<sep>...", empty ones kept: at least one
+inline std::vector<std::string> split_fields(const std::string& s, char sep)
+{
+    std::vector<std::string> f;
+    size_t a = 0;
+    while(true)
+    {
+        const size_t b = s.find(sep, a);
+        f.push_back(s.substr(a, b == std::string::npos ? b : b - a));
+        if(b == std::string::npos) return f;
+        a = b + 1;
+    }
+}
+
+// "c0,c1,...": up to `max` different non-negative channel indices
+inline bool parse_channel_list(const std::string& list, int max, std::vector<int32_t>& out)
+{
+    for(const std::string& item : split_fields(list, ','))
+    {
+        int32_t c = 0;
+        if(!parse_int_in(item, 0, INT32_MAX, c) || std::find(out.begin(), out.end(), c) != out.end()) return false;
+        out.push_back(c);
+        if(out.size() > static_cast<size_t>(max)) return false;
+    }
+    return true;
+}
+
+// RATIO, a decimal ratio within 0..1e6, kept as rint(16 x RATIO) (whether the library takes it is the option's own check)
+inline bool parse_ratio_q4(const std::string& s, int32_t& q4)
+{
+    char* end = nullptr;
+    const double r = std::strtod(s.c_str(), &end);
+    if(s.empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
+    q4 = static_cast<int32_t>(std::lrint(16.0 * r));
+    return true;
+}
+
+// ---- the options ----
 
 // "G" or "auto[:G0]"
 inline bool parse_wideband_gain(const std::string& s, WidebandOptions& w)
@@ -198,32 +211,17 @@ inline bool parse_wideband_gain(const std::string& s, WidebandOptions& w)
     return !g.empty() && end && *end == 0;
 }
 
-// "RATIO[:PRE[:POST]]": RATIO a decimal power ratio to the push's mean power, kept as rint(16 x RATIO); PRE, POST in samples.
-// NULL (the bare option): the defaults.
+// "RATIO[:PRE[:POST]]": RATIO a decimal power ratio to the push's mean power; PRE, POST in samples.  NULL (the bare option): the
+// defaults.
 inline bool parse_wideband_blanker(const char* arg, WidebandOptions& w)
 {
     w.blanker = true;
     w.blanker_params = msk144wb::BlankerParams();
     if(!arg) return true;
-    const std::string s = arg;
-    const size_t a = s.find(':');
-    const size_t b = a == std::string::npos ? a : s.find(':', a + 1);
-    const std::string ratio = s.substr(0, a);
-    char* end = nullptr;
-    const double r = std::strtod(ratio.c_str(), &end);
-    if(ratio.empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
-    w.blanker_params.threshold_q4 = static_cast<int32_t>(std::lrint(16.0 * r));
-    long long v = 0;
-    if(a != std::string::npos)
-    {
-        if(!parse_int(s.substr(a + 1, b == std::string::npos ? b : b - a - 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
-        w.blanker_params.pre = static_cast<int32_t>(v);
-    }
-    if(b != std::string::npos)
-    {
-        if(!parse_int(s.substr(b + 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
-        w.blanker_params.post = static_cast<int32_t>(v);
-    }
+    const std::vector<std::string> f = split_fields(arg, ':');
+    if(f.size() > 3 || !parse_ratio_q4(f[0], w.blanker_params.threshold_q4)) return false;
+    if(f.size() > 1 && !parse_int_in(f[1], INT32_MIN, INT32_MAX, w.blanker_params.pre)) return false;
+    if(f.size() > 2 && !parse_int_in(f[2], INT32_MIN, INT32_MAX, w.blanker_params.post)) return false;
     return msk144wb::check_blanker(w.blanker_params).empty();
 }
 
@@ -232,62 +230,27 @@ inline bool parse_wideband_blanker(const char* arg, WidebandOptions& w)
 inline bool parse_wideband_spectrum(const std::string& s, WidebandOptions& w)
 {
     w.spectrum = true;
-    const size_t a = s.find(':');
-    const size_t b = a == std::string::npos ? a : s.find(':', a + 1);
-    w.spectrum_file = s.substr(0, a);
-    if(w.spectrum_file.empty() || (b != std::string::npos && s.find(':', b + 1) != std::string::npos)) return false;
-    long long v = 0;
-    if(a != std::string::npos)
-    {
-        if(!parse_int(s.substr(a + 1, b == std::string::npos ? b : b - a - 1), v) || v < msk144wb::kSpectrumMinBins || v > msk144wb::kSpectrumMaxBins || (v & (v - 1)) != 0) return false;
-        w.spectrum_bins = static_cast<int>(v);
-    }
-    if(b != std::string::npos)
-    {
-        if(!parse_int(s.substr(b + 1), v) || v < 1 || v > 1000000) return false;
-        w.spectrum_hops = static_cast<int>(v);
-    }
-    return true;
+    const std::vector<std::string> f = split_fields(s, ':');
+    w.spectrum_file = f[0];
+    if(f[0].empty() || f.size() > 3) return false;
+    if(f.size() > 1 && (!parse_int_in(f[1], msk144wb::kSpectrumMinBins, msk144wb::kSpectrumMaxBins, w.spectrum_bins) || (w.spectrum_bins & (w.spectrum_bins - 1)) != 0)) return false;
+    return f.size() < 3 || parse_int_in(f[2], 1, 1000000, w.spectrum_hops);
 }
 
-// "FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]": RATIO a decimal ratio to the reference, kept as rint(16 x RATIO) within 16..65535;
-// MIN_BLOCKS 1..64 blocks of 8 ms an event must have; MEMORY 0..16 earlier pushes
+// "FILE[:RATIO[:MIN_BLOCKS[:MEMORY]]]": RATIO a decimal ratio to the reference, within 16..65535 as q4; MIN_BLOCKS 1..64 blocks of
+// 8 ms an event must have; MEMORY 0..16 earlier pushes
 inline bool parse_wideband_pings(const std::string& s, WidebandOptions& w)
 {
     w.pings = true;
     w.ping_params = msk144wb::PingParams();
     w.ping_min_blocks = msk144wb::kPingDefaultMinBlocks;
-    w.ping_ratio_given = false;
-    std::vector<std::string> f;
-    size_t a = 0;
-    while(true)
-    {
-        const size_t b = s.find(':', a);
-        f.push_back(s.substr(a, b == std::string::npos ? b : b - a));
-        if(b == std::string::npos) break;
-        a = b + 1;
-    }
+    const std::vector<std::string> f = split_fields(s, ':');
     w.pings_file = f[0];
+    w.ping_ratio_given = f.size() > 1;
     if(f[0].empty() || f.size() > 4) return false;
-    long long v = 0;
-    if(f.size() > 1)
-    {
-        char* end = nullptr;
-        const double r = std::strtod(f[1].c_str(), &end);
-        if(f[1].empty() || !end || *end != 0 || !(r >= 0.0 && r <= 1e6)) return false;
-        w.ping_params.ratio_q4 = static_cast<int32_t>(std::lrint(16.0 * r));
-        w.ping_ratio_given = true;
-    }
-    if(f.size() > 2)
-    {
-        if(!parse_int(f[2], v) || v < 1 || v > msk144wb::kPingMaxMinBlocks) return false;
-        w.ping_min_blocks = static_cast<int>(v);
-    }
-    if(f.size() > 3)
-    {
-        if(!parse_int(f[3], v) || v < INT32_MIN || v > INT32_MAX) return false;
-        w.ping_params.memory = static_cast<int32_t>(v);
-    }
+    if(f.size() > 1 && !parse_ratio_q4(f[1], w.ping_params.ratio_q4)) return false;
+    if(f.size() > 2 && !parse_int_in(f[2], 1, msk144wb::kPingMaxMinBlocks, w.ping_min_blocks)) return false;
+    if(f.size() > 3 && !parse_int_in(f[3], INT32_MIN, INT32_MAX, w.ping_params.memory)) return false;
     return msk144wb::check_pings(w.ping_params).empty();
 }
 
@@ -300,17 +263,11 @@ inline bool parse_wideband_ping_band(const std::string& s, int centre_default, W
     w.ping_band_halfwidth = msk144wb::kPingBandDefaultHalfwidthHz;
     w.ping_band_centre = centre_default;
     if(!w.ping_ratio_given) w.ping_params.ratio_q4 = msk144wb::kPingBandDefaultRatioQ4;
-    long long v = 0;
     if(!s.empty())
     {
-        const size_t a = s.find(':');
-        if(!parse_int(s.substr(0, a), v) || v < INT32_MIN || v > INT32_MAX) return false;
-        w.ping_band_halfwidth = static_cast<int>(v);
-        if(a != std::string::npos)
-        {
-            if(!parse_int(s.substr(a + 1), v) || v < INT32_MIN || v > INT32_MAX) return false;
-            w.ping_band_centre = static_cast<int>(v);
-        }
+        const std::vector<std::string> f = split_fields(s, ':');
+        if(f.size() > 2 || !parse_int_in(f[0], INT32_MIN, INT32_MAX, w.ping_band_halfwidth)) return false;
+        if(f.size() > 1 && !parse_int_in(f[1], INT32_MIN, INT32_MAX, w.ping_band_centre)) return false;
     }
     return msk144wb::check_ping_band_design(w.ping_band_centre, w.ping_band_halfwidth).empty();
 }
@@ -320,28 +277,12 @@ inline bool parse_wideband_ping_band(const std::string& s, int centre_default, W
 inline bool parse_wideband_waterfall(const std::string& s, WidebandOptions& w)
 {
     w.waterfall = true;
-    w.waterfall_by_pings = true;
     w.waterfall_channels.clear();
-    const size_t a = s.find(':');
-    w.waterfall_file = s.substr(0, a);
-    if(w.waterfall_file.empty()) return false;
-    if(a == std::string::npos) return true;
-    const std::string list = s.substr(a + 1);
-    if(list == "pings") return true;
-    w.waterfall_by_pings = false;
-    size_t p = 0;
-    while(true)
-    {
-        const size_t q = list.find(',', p);
-        long long v = 0;
-        if(!parse_int(list.substr(p, q == std::string::npos ? q : q - p), v) || v < 0 || v > INT32_MAX) return false;
-        if(std::find(w.waterfall_channels.begin(), w.waterfall_channels.end(), static_cast<int32_t>(v)) != w.waterfall_channels.end()) return false;
-        w.waterfall_channels.push_back(static_cast<int32_t>(v));
-        if(w.waterfall_channels.size() > static_cast<size_t>(msk144wb::kWaterfallMaxListed)) return false;
-        if(q == std::string::npos) break;
-        p = q + 1;
-    }
-    return true;
+    const std::vector<std::string> f = split_fields(s, ':');
+    w.waterfall_file = f[0];
+    w.waterfall_by_pings = f.size() == 1 || (f.size() == 2 && f[1] == "pings");
+    if(f[0].empty() || f.size() > 2) return false;
+    return w.waterfall_by_pings || parse_channel_list(f[1], msk144wb::kWaterfallMaxListed, w.waterfall_channels);
 }
 
 // "DIR[:CHANNELS[:POST[:PRE]]]": CHANNELS `pings`, or up to 16 different channel indices c0,c1,...; POST 0..16 hops, PRE 0 or 1
@@ -349,47 +290,15 @@ inline bool parse_wideband_waterfall(const std::string& s, WidebandOptions& w)
 inline bool parse_wideband_capture(const std::string& s, WidebandOptions& w)
 {
     w.capture = true;
-    w.capture_by_pings = true;
     w.capture_channels.clear();
     w.capture_params = msk144wb::CaptureParams();
-    std::vector<std::string> f;
-    size_t a = 0;
-    while(true)
-    {
-        const size_t b = s.find(':', a);
-        f.push_back(s.substr(a, b == std::string::npos ? b : b - a));
-        if(b == std::string::npos) break;
-        a = b + 1;
-    }
+    const std::vector<std::string> f = split_fields(s, ':');
     w.capture_dir = f[0];
+    w.capture_by_pings = f.size() == 1 || f[1] == "pings";
     if(f[0].empty() || f.size() > 4) return false;
-    long long v = 0;
-    if(f.size() > 1 && f[1] != "pings")
-    {
-        w.capture_by_pings = false;
-        size_t p = 0;
-        while(true)
-        {
-            const size_t q = f[1].find(',', p);
-            if(!parse_int(f[1].substr(p, q == std::string::npos ? q : q - p), v) || v < 0 || v > INT32_MAX) return false;
-            if(std::find(w.capture_channels.begin(), w.capture_channels.end(), static_cast<int32_t>(v)) != w.capture_channels.end()) return false;
-            w.capture_channels.push_back(static_cast<int32_t>(v));
-            if(w.capture_channels.size() > static_cast<size_t>(msk144wb::kCaptureMaxListed)) return false;
-            if(q == std::string::npos) break;
-            p = q + 1;
-        }
-    }
-    if(f.size() > 2)
-    {
-        if(!parse_int(f[2], v) || v < 0 || v > msk144wb::kCaptureMaxPost) return false;
-        w.capture_params.post = static_cast<int32_t>(v);
-    }
-    if(f.size() > 3)
-    {
-        if(!parse_int(f[3], v) || v < 0 || v > 1) return false;
-        w.capture_params.pre = static_cast<int32_t>(v);
-    }
-    return true;
+    if(!w.capture_by_pings && !parse_channel_list(f[1], msk144wb::kCaptureMaxListed, w.capture_channels)) return false;
+    if(f.size() > 2 && !parse_int_in(f[2], 0, msk144wb::kCaptureMaxPost, w.capture_params.post)) return false;
+    return f.size() < 4 || parse_int_in(f[3], 0, 1, w.capture_params.pre);
 }
 
 inline bool parse_wideband_format(const std::string& s, int& fmt)
@@ -404,34 +313,54 @@ inline bool parse_wideband_format(const std::string& s, int& fmt)
 // "f1,f2,..." in integer Hz
 inline bool parse_offset_list(const std::string& list, std::vector<int32_t>& out)
 {
-    size_t a = 0;
-    while(a <= list.size())
+    for(const std::string& item : split_fields(list, ','))
     {
-        const size_t b = list.find(',', a);
-        long long v = 0;
-        if(!parse_int(list.substr(a, b == std::string::npos ? std::string::npos : b - a), v) || v < INT32_MIN || v > INT32_MAX) return false;
-        out.push_back(static_cast<int32_t>(v));
-        if(b == std::string::npos) break;
-        a = b + 1;
+        int32_t f = 0;
+        if(!parse_int_in(item, INT32_MIN, INT32_MAX, f)) return false;
+        out.push_back(f);
     }
-    return !out.empty();
+    return true;
 }
 
 // "first:step:count" -> first, first+step, ... (count >= 1)
 inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out)
 {
-    const size_t a = spec.find(':');
-    const size_t b = a == std::string::npos ? a : spec.find(':', a + 1);
+    const std::vector<std::string> f = split_fields(spec, ':');
     long long first = 0, step = 0, count = 0;
-    if(b == std::string::npos || !parse_int(spec.substr(0, a), first) || !parse_int(spec.substr(a + 1, b - a - 1), step) || !parse_int(spec.substr(b + 1), count))
-        return false;
-    if(count < 1 || count > 1000000) return false;
+    if(f.size() != 3 || !parse_int(f[0], first) || !parse_int(f[1], step) || !parse_int_in(f[2], 1, 1000000, count)) return false;
     for(long long i = 0; i < count; i++)
     {
-        const long long f = first + i * step;
-        if(f < INT32_MIN || f > INT32_MAX) return false;
-        out.push_back(static_cast<int32_t>(f));
+        const long long hz = first + i * step;
+        if(hz < INT32_MIN || hz > INT32_MAX) return false;
+        out.push_back(static_cast<int32_t>(hz));
     }
+    return true;
+}
+
+// One option of the command line by its name: false when `name` is no wideband option, else it is taken into `w` - a malformed value
+// as the first parse error, which check_wideband_options reports.  --wideband-pings-band keeps its value for parse_wideband_ping_band,
+// behind the whole line.
+inline bool take_wideband_option(const std::string& name, const char* arg, WidebandOptions& w)
+{
+    const std::string value = arg ? arg : "";
+    long long v = 0;
+    bool good = true;
+    if(name == "wideband-rate") good = parse_int(value, v) && (w.rate_hz = v) > 0;
+    else if(name == "wideband-format") good = parse_wideband_format(value, w.format);
+    else if(name == "channel-offsets") good = parse_offset_list(value, w.offsets), w.offset_sources++;
+    else if(name == "channel-grid") good = parse_offset_grid(value, w.offsets), w.offset_sources++;
+    else if(name == "wideband-gain") good = parse_wideband_gain(value, w);
+    else if(name == "taps-per-phase") good = parse_int_in(value, 1, msk144wb::kMaxTapsPerPhase, w.taps_per_phase);
+    else if(name == "wideband-levels") w.levels = true;
+    else if(name == "wideband-blanker") good = parse_wideband_blanker(arg, w);
+    else if(name == "wideband-spectrum") good = parse_wideband_spectrum(value, w);
+    else if(name == "wideband-pings") good = parse_wideband_pings(value, w);
+    else if(name == "wideband-waterfall") good = parse_wideband_waterfall(value, w);
+    else if(name == "wideband-capture") good = parse_wideband_capture(value, w);
+    else if(name == "wideband-pings-band") w.ping_band = true, w.ping_band_arg = value;
+    else return false;
+    w.any_option = true;
+    if(!good && w.parse_error.empty()) w.parse_error = "bad value for --" + name + ": '" + value + "'";
     return true;
 }
 
@@ -439,34 +368,34 @@ inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out
 inline std::string check_wideband_options(const WidebandOptions& w)
 {
     if(!w.parse_error.empty()) return w.parse_error;
-    if(w.rate_hz <= 0 && w.blanker) return "--wideband-blanker needs --wideband-rate=HZ";
-    if(w.rate_hz <= 0 && w.spectrum) return "--wideband-spectrum needs --wideband-rate=HZ";
-    if(w.rate_hz <= 0 && w.pings) return "--wideband-pings needs --wideband-rate=HZ";
-    if(w.rate_hz <= 0 && w.ping_band) return "--wideband-pings-band needs --wideband-rate=HZ";
-    if(w.rate_hz <= 0 && w.waterfall) return "--wideband-waterfall needs --wideband-rate=HZ";
-    if(w.rate_hz <= 0 && w.capture) return "--wideband-capture needs --wideband-rate=HZ";
     if(w.rate_hz <= 0)
+    {
+        const std::pair<bool, const char*> own_line[] = {{w.blanker, "--wideband-blanker"},      {w.spectrum, "--wideband-spectrum"},   {w.pings, "--wideband-pings"},
+                                                         {w.ping_band, "--wideband-pings-band"}, {w.waterfall, "--wideband-waterfall"}, {w.capture, "--wideband-capture"}};
+        for(const auto& o : own_line)
+            if(o.first) return std::string(o.second) + " needs --wideband-rate=HZ";
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
                         : "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain and --taps-per-phase need --wideband-rate=HZ";
+    }
     if(w.offset_sources != 1) return "--wideband-rate needs exactly one of --channel-offsets=f1,f2,... or --channel-grid=first:step:count";
     const std::string why = msk144wb::check_config(w.rate_hz, w.format, w.taps_per_phase, w.gain, w.offsets.data(), static_cast<int>(w.offsets.size()));
-    if(why.empty() && w.agc && !msk144wb::gain_ok(w.gain, msk144wb::AgcParams().max_exp))
-        return "--wideband-gain=auto:G0 needs 128 x G0 x 2^20 finite (the top of the AGC's ladder)";
-    if(why.empty() && w.spectrum)
+    if(!why.empty()) return why;
+    if(w.agc && !msk144wb::gain_ok(w.gain, msk144wb::AgcParams().max_exp)) return "--wideband-gain=auto:G0 needs 128 x G0 x 2^20 finite (the top of the AGC's ladder)";
+    if(w.spectrum)
     {
         const std::string bad = msk144wb::check_spectrum(w.spectrum_bins, nullptr, 2592 * w.rate_hz / msk144wb::kOutRate);
         if(!bad.empty()) return "--wideband-spectrum: " + bad;
     }
-    if(why.empty() && w.ping_band && !w.pings) return "--wideband-pings-band needs --wideband-pings=FILE";
-    if(why.empty() && w.waterfall && w.waterfall_by_pings && !w.pings) return "--wideband-waterfall=FILE needs a channel list (FILE:c0,c1,...) without --wideband-pings";
-    for(size_t i = 0; why.empty() && w.waterfall && i < w.waterfall_channels.size(); i++)
+    if(w.ping_band && !w.pings) return "--wideband-pings-band needs --wideband-pings=FILE";
+    if(w.waterfall && w.waterfall_by_pings && !w.pings) return "--wideband-waterfall=FILE needs a channel list (FILE:c0,c1,...) without --wideband-pings";
+    for(size_t i = 0; w.waterfall && i < w.waterfall_channels.size(); i++)
         if(static_cast<size_t>(w.waterfall_channels[i]) >= w.offsets.size())
             return "--wideband-waterfall: channel " + std::to_string(w.waterfall_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
-    if(why.empty() && w.capture && w.capture_by_pings && !w.pings) return "--wideband-capture=DIR needs a channel list (DIR:c0,c1,...) without --wideband-pings";
-    for(size_t i = 0; why.empty() && w.capture && i < w.capture_channels.size(); i++)
+    if(w.capture && w.capture_by_pings && !w.pings) return "--wideband-capture=DIR needs a channel list (DIR:c0,c1,...) without --wideband-pings";
+    for(size_t i = 0; w.capture && i < w.capture_channels.size(); i++)
         if(static_cast<size_t>(w.capture_channels[i]) >= w.offsets.size())
             return "--wideband-capture: channel " + std::to_string(w.capture_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
-    return why;
+    return "";
 }
 
 // the program's max_units: min(2 x channels, 512)

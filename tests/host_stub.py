@@ -16,6 +16,21 @@ HOST = os.path.join(ROOT, "msk144cudecoder_amd", "host")
 PROGRAM_SOURCES = ("snr_tracker.cpp", "result_filter.cpp", "unpack77.cpp", "postprocess.cpp", "window_decoder.cpp", "stream_loop.cpp", "main.cpp")
 
 
+# every wideband entry the stand-in has, and the one command line that switches every wideband option on (five channels, PUSHES pushes)
+WIDEBAND_STUBS = ("msk144hip_stub.cpp", "wideband_stub.cpp", "wideband_levels_stub.cpp", "wideband_blanker_stub.cpp", "wideband_spectrum_stub.cpp", "wideband_pings_stub.cpp",
+                  "wideband_pingband_stub.cpp", "wideband_waterfall_stub.cpp", "wideband_capture_stub.cpp")
+WIDEBAND_RATE, WIDEBAND_OFFSETS, WIDEBAND_PUSHES = 240000, (-24000, 0, 12000, 36000, 48000), 4
+WIDEBAND_DATA = bytes((5184 + (WIDEBAND_PUSHES - 1) * 2592) * WIDEBAND_RATE // 12000 * 2)
+
+
+def wideband_all_options(dir):
+    """The arguments; the spectrum, ping and waterfall files and the capture directory lie under `dir`."""
+    d = str(dir)
+    return [f"--wideband-rate={WIDEBAND_RATE}", "--wideband-format=cs8", "--channel-offsets=" + ",".join(map(str, WIDEBAND_OFFSETS)), "--wideband-gain=auto", "--wideband-levels",
+            "--wideband-blanker", f"--wideband-spectrum={d}/spectrum.txt:256:2", f"--wideband-pings={d}/pings.txt", "--wideband-pings-band", f"--wideband-waterfall={d}/waterfall.txt",
+            f"--wideband-capture={d}/capture"]
+
+
 def build_program(dir, stubs=("msk144hip_stub.cpp",), flags=("-O1",)):
     """Compile the stand-in library from `stubs` and the program against it, both in `dir`; returns the program's path."""
     d = str(dir)

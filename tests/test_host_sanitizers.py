@@ -1,5 +1,7 @@
 """The pipelined multi-stream loop of msk144hipdecoder (ingest thread + post-processing thread over two staging slots) under
-ThreadSanitizer and AddressSanitizer/UBSan - CPU build against tests/stub_hip (GPU sanitizers are not available on the pool)."""
+ThreadSanitizer and AddressSanitizer/UBSan - CPU build against tests/stub_hip (GPU sanitizers are not available on the pool).  And
+the wideband mode with every option on: its state (host/wideband_run.h) is touched by the main thread before the loop's threads
+start and after they are joined, by the ingest thread in between, and by no lock."""
 import os
 import platform
 import shutil
@@ -9,13 +11,13 @@ import sys
 import numpy as np
 import pytest
 
-from host_stub import HOST, PROGRAM_SOURCES, ROOT, marked_stream, windows_seen
+from host_stub import HOST, PROGRAM_SOURCES, ROOT, WIDEBAND_DATA, WIDEBAND_STUBS, marked_stream, wideband_all_options, windows_seen
 
 
-def _build(tmp, flag):
+def _build(tmp, flag, stubs=("msk144hip_stub.cpp",)):
     d = str(tmp)
     common = ["g++", "-O1", "-g", f"-fsanitize={flag}", "-std=c++17", "-pthread"]
-    r = subprocess.run(common + ["-fPIC", "-shared", "-o", os.path.join(d, "libmsk144hip.so"), os.path.join(ROOT, "tests", "stub_hip", "msk144hip_stub.cpp")],
+    r = subprocess.run(common + ["-fPIC", "-shared", "-o", os.path.join(d, "libmsk144hip.so")] + [os.path.join(ROOT, "tests", "stub_hip", s) for s in stubs],
                        capture_output=True, text=True)
     if r.returncode != 0:
         pytest.skip(f"-fsanitize={flag} not usable with this toolchain: {r.stderr[-200:]}")
@@ -71,3 +73,13 @@ def test_multi_stream_loop_under_sanitizers(tmp_path, flag):
     err = r.stderr.decode()
     assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, err[-3000:]
     assert windows_seen(r.stdout.decode(), n)[3] == [(30 + k, 31 + k) for k in range(h + 1)]
+
+
+@pytest.mark.parametrize("flag", ["thread", "address,undefined"])
+def test_wideband_run_with_every_option_under_sanitizers(tmp_path, flag):
+    exe = _build(tmp_path, flag, WIDEBAND_STUBS)
+    env = dict(os.environ, MSK144_STUB_DECODE_MS="4", TSAN_OPTIONS="halt_on_error=1 exitcode=66", ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run(_no_aslr_prefix(flag) + [exe] + wideband_all_options(tmp_path), input=WIDEBAND_DATA, capture_output=True, timeout=300, env=env)
+    err = r.stderr.decode()
+    assert r.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, err[-3000:]
+    assert r.stdout.decode().strip().endswith("Done")
