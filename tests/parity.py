@@ -212,18 +212,28 @@ def bp_outcome(orc_mod, llr):
     return (bool(ok), int(it) if ok else -1, int(nh) if ok else -1, bytes(np.asarray(msg, dtype=np.uint8)) if ok else b"")
 
 
-def verify_marginal_bp(orc_mod, llr, gpu_outcome, seed, trials=48):
+def perturbed_llr(llr, scale, rng, absolute=False):
+    """llr (1 + s u), and with `absolute` + s rms(llr) u' on top (u, u' uniform in [-1, 1]): a relative perturbation cannot
+    move an LLR that is exactly 0."""
+    p = llr * (1.0 + scale * rng.uniform(-1.0, 1.0, size=llr.shape))
+    if absolute:
+        p = p + scale * float(np.sqrt(np.mean(np.square(llr.astype(np.float64))))) * rng.uniform(-1.0, 1.0, size=llr.shape)
+    return p.astype(np.float32)
+
+
+def verify_marginal_bp(orc_mod, llr, gpu_outcome, seed, trials=48, absolute=False):
     """A BP accept/iteration difference between the HIP kernel and the oracle is tolerated ONLY if the oracle's own decision
     is unstable at that input: re-running the oracle's BP on the same LLRs perturbed by a relative 1e-6 .. 1e-4 (the kernel's
     tanh/atanh differ from libm by ~1e-7) must reproduce the kernel's (accept, iteration) outcome in some trial AND the
-    oracle's in another.  Returns the smallest scale at which that happens; raises AssertionError for a stable difference."""
+    oracle's in another.  Returns the smallest scale at which that happens; raises AssertionError for a stable difference.
+    absolute=True (rows with exact zeros, tests/ldpc_rows.py) adds a term of the same scale times the row's rms."""
     llr = np.ascontiguousarray(llr, dtype=np.float32)
     rng = np.random.default_rng(seed)
     base = bp_outcome(orc_mod, llr)[:2]
     for scale in BP_PERTURBATION_SCALES:
         seen = {base}
         for _ in range(trials):
-            pert = (llr * (1.0 + scale * rng.uniform(-1.0, 1.0, size=llr.shape))).astype(np.float32)
+            pert = perturbed_llr(llr, scale, rng, absolute)
             seen.add(bp_outcome(orc_mod, pert)[:2])
             if tuple(gpu_outcome[:2]) in seen and len(seen) > 1:
                 return scale
