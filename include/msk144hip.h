@@ -712,6 +712,66 @@ int msk144_wideband_waterfall(msk144_handle* h, int32_t channel, float* rows, in
 /* sums[channels][96] of the last push */
 int msk144_wideband_waterfall_sums(msk144_handle* h, double* sums);
 
+/* ---- The notch: steady carriers taken out of a channel (no reference counterpart) ----
+ *
+ * A spur of the SDR, a birdie or a beacon inside a channel's 2.4 kHz band goes straight into the decoder's int8 I/Q and costs
+ * decodes.  With a notch on a channel, a 64-tap complex band-pass estimates the carriers from the stored int8 values and the stage
+ * takes the estimate from the delayed input.  Exact integer arithmetic throughout (csrc/notch.hip; the same rule on the host is
+ * csrc/wideband.h notch_filter).  Per notched channel, with x[n] = I + jQ the stored int8 values as integers, in stream order:
+ *
+ *   Taps:       64 complex int8 taps b[k] = (br[k], bi[k]), k = 0..63, and a shift s, 0 <= s <= 15; any int8 values are valid.
+ *   Filter:     z[n] = sum over k < 64 of b[k] . x[n - k], in int32 as the ping band's z;
+ *               y[n] = sat8(((x[n - 31] << s) - z[n] + r) >> s) per component, r = s ? 1 << (s - 1) : 0, the shift right an
+ *               arithmetic shift of int32, sat8 a clamp to -128..127.  y replaces x in the staged rows.
+ *   Delay:      the output is the input delayed by 31 samples (2.6 ms) minus the band-passed estimate of the carriers.  The delay
+ *               is part of the contract: a notched channel's pings, waterfall rows and decode times lie 31 samples late.
+ *   Tail:       x[n - k] reaches into the channel's previous 63 raw (pre-notch) stored samples, which the stage keeps per channel
+ *               on the device.  x before the channel's first filtered sample is 0: the tail is all zero at a first push, and on
+ *               the next push of a channel whose entry is new or differs from the one it had.  A channel whose entry is unchanged
+ *               by a new table keeps its tail.
+ *   Place:      directly behind the channeliser and the AGC step, ahead of everything that reads the staged hops.  So
+ *               msk144_dump_wideband_hop, the ping band, the pings, the waterfall, the hop ring, the capture and the decode all
+ *               see the notched channel; msk144_wideband_levels and the clip count stay the channeliser's own, so that the AGC
+ *               keeps acting on the level with the carrier in it.  The channels not in the table are not touched.
+ *   Default design (msk144host_wideband_notch_design in libmsk144host.so, csrc/wideband.h notch_design; the Python side takes it
+ *               from there): 1 or 2 integer frequencies per channel, relative to the channel's offset, 50 <= halfwidth_hz <= 500
+ *               (default 100), |f| + halfwidth_hz <= 6000, two frequencies at least 1000 Hz apart (closer ones over-subtract in a
+ *               CPU check, because the two pass bands add).  In double: a 63-tap Hamming-windowed sinc low-pass with cutoff
+ *               halfwidth_hz centred on k = 31, scaled to unit DC gain, turned by e^{+j 2 pi f (k - 31) / 12000} to each frequency
+ *               and summed; s = min(15, floor(log2(127 / largest |component|))), taps rint(value x 2^s), tap 63 = 0.  In a CPU
+ *               check of the rounded default design (W = 100) a component 62 Hz from the notch comes out 23.0 dB down, one 400 Hz
+ *               away 0.1 dB down.
+ *   Cost:       CPU simulation with the reference decoder on synthetic int8 windows (no GPU measurement stands behind these
+ *               figures; DESIGN 4.4 has the table): the notch recovers nearly every decode a carrier takes away (+6 dB pings, two
+ *               tones of 50 LSB: 5 of 24 decoded without, 24 of 24 with), and costs sensitivity on a weak ping where there is no
+ *               carrier (0 dB, no carrier: 24 of 24 without, 21 of 24 with).  Hence per channel, and only where a carrier sits.
+ *   Order:      msk144_set_wideband_notch(h, channels, count, params) replaces the whole table from the next push on and allocates
+ *               everything it needs - a push allocates nothing; count = 0 or channels = NULL switches the notch off, as
+ *               msk144_set_wideband does.  With no channel notched a push launches nothing.  No atomics: the same stream pushed
+ *               twice gives the same bytes.  msk144_wideband_notch_stats reports the last push - on[c] and the components of it
+ *               that sat8 clamped - and synchronises like msk144_wideband_levels.
+ *   Refused:    MSK144_EINVAL outside wideband mode, for a channel listed twice or out of range, for count outside 0..channels,
+ *               for a missing params and for a shift outside 0..15; MSK144_ESTATE from msk144_wideband_notch_stats before a push
+ *               made with the notch on since the table was last set. */
+typedef struct msk144_wideband_notch_params
+{
+    int8_t taps[64][2]; /* (br, bi) of b[0] .. b[63] */
+    int32_t shift;
+} msk144_wideband_notch_params;
+
+typedef struct msk144_wideband_notch_count
+{
+    int32_t on;      /* 1: the channel was notched in the last push */
+    int32_t clipped; /* components of the last push that sat8 clamped */
+} msk144_wideband_notch_count;
+
+#define MSK144_NOTCH_DELAY 31
+
+/* params[count], one per listed channel; count = 0 or channels = NULL: off */
+int msk144_set_wideband_notch(msk144_handle* h, const int32_t* channels, int32_t count, const msk144_wideband_notch_params* params);
+/* out[channels]: the last push */
+int msk144_wideband_notch_stats(msk144_handle* h, msk144_wideband_notch_count* out);
+
 /* ---- Per-ping capture of a channel's hops, for replay (no reference counterpart) ----
  *
  * A ping that did not decode is gone 216 ms later, when the hop ring advances.  Every channel's 12 ksps int8 I/Q stream - exactly

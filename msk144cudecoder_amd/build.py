@@ -34,6 +34,7 @@ SOURCES = [
     ("waterfall.hip", []),
     ("capture.hip", []),
     ("pingband.hip", []),
+    ("notch.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("msk144_wideband_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]

@@ -144,6 +144,19 @@ struct Wideband
         int8_t* d_taps = nullptr;    // [64][2]
         uint8_t* d_tails = nullptr;  // [channels][128]: two zero bytes, then the 63 stored samples before the next push
     } ping_band;
+    // the notch (msk144_set_wideband_notch): on = the table lists a channel.  pushed: the last push ran it and no `set` has come since
+    struct Notch
+    {
+        bool on = false, pushed = false;
+        int count = 0;                             // channels in the table = entries of d_list
+        std::vector<uint8_t> listed;               // [channels] the channel is in the table, with ...
+        std::vector<msk144wb::NotchParams> table;  // [channels] ... this entry
+        int32_t* d_list = nullptr;     // [channels] the table's channels, ascending; the first `count` are read
+        int8_t* d_taps = nullptr;      // [channels][64][2]
+        int32_t* d_shifts = nullptr;   // [channels]
+        uint8_t* d_tails = nullptr;    // [channels][128]: two zero bytes, then the 63 raw stored samples before the next push
+        int32_t* d_clipped = nullptr;  // [channels] of the last push; 0 for a channel not in the table
+    } notch;
     // per-channel waterfall (msk144_set_wideband_waterfall)
     struct Waterfall
     {

@@ -113,6 +113,13 @@ void launch_channelise(const void* raw, int format, const float2* G, const Wideb
 void launch_agc_step(const unsigned long long* levels, const int32_t* slot_channel, const float* gains, int32_t* exps, int32_t* quiet, int32_t* used_exps, float* scale,
                      int slots, int samples, const msk144wb::AgcParams& p, hipStream_t stream);
 
+// the notch of a push (notch.hip; contract in include/msk144hip.h), behind the channeliser and the AGC step on the same stream and
+// ahead of every reader of the staged hops, which it rewrites in place: list[count] the notched channels, count >= 1;
+// taps[channels][64][2] int8 and shifts[channels], read for the listed channels; tails[channels][128] bytes, a channel's 63 raw stored
+// samples before the push behind two zero bytes, moved on to the push's last 63 raw ones.  Writes clipped[c] for the listed channels.
+void launch_notch(int8_t* first_halves, int8_t* hops, int first, const int32_t* list, int count, const int8_t* taps, const int32_t* shifts, uint8_t* tails, int32_t* clipped,
+                  hipStream_t stream);
+
 // ping detection on the staged hops of a push (pings.hip; contract in include/msk144hip.h), behind the channeliser and the AGC step:
 // first_halves and hops are the hop ring's staging, [channels][5184] bytes each (with first != 0 a channel's push is its row of
 // first_halves followed by its row of hops).  gains[channels] and used_exps[channels] (NULL without the AGC: exponent 0) give the

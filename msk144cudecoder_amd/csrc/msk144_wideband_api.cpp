@@ -276,11 +276,14 @@ int wb_stage_input(msk144_handle* h, int32_t slot, const WbPush& p)
         if(e == hipSuccess) e = hipMemsetAsync(w.agc.d_exp, 0, sizeof(int32_t) * C, h->stream);
         if(e == hipSuccess) e = hipMemsetAsync(w.agc.d_quiet, 0, sizeof(int32_t) * C, h->stream);
     }
+    // the notch starts from silence with a stream: x before the first filtered sample is 0
+    if(w.notch.on && p.first && e == hipSuccess) e = hipMemsetAsync(w.notch.d_tails, 0, static_cast<size_t>(C) * 2 * msk144wb::kNotchTaps, h->stream);
     ev_end(h, MSK144_T_H2D);
     return e == hipSuccess ? MSK144_OK : fail(h, MSK144_EHIP, std::string("msk144_push_wideband: ") + hipGetErrorString(e));
 }
 
-// The front end: blanker and spectrum on the input, the bank, the channeliser into the staged hops, the AGC's step
+// The front end: blanker and spectrum on the input, the bank, the channeliser into the staged hops, the AGC's step, the notch on
+// the staged hops of the table's channels
 void wb_launch_frontend(msk144_handle* h, const WbPush& p)
 {
     auto& w = h->wb;
@@ -305,6 +308,10 @@ void wb_launch_frontend(msk144_handle* h, const WbPush& p)
     launch_channelise(b.on ? static_cast<const void*>(b.d_sub) : k.d_in, b.on ? kSubbandFormat : k.in_format, k.d_G, k.d_branches, k.d_fmod, k.d_rot, reinterpret_cast<int8_t*>(h->d_first),
                       reinterpret_cast<int8_t*>(h->d_hops), k.d_clip, slots, k.P, k.Q, k.hist, p.M, p.first ? 1 : 0, k.m_next, a.d_scale, a.d_levels, h->stream, bands);
     if(a.on) launch_agc_step(a.d_levels, b.on ? b.d_slot_channel : nullptr, a.d_gains, a.d_exp, a.d_quiet, a.d_used_exp, a.d_scale, slots, p.M, a.params, h->stream);
+    auto& n = w.notch;
+    if(n.on)
+        launch_notch(reinterpret_cast<int8_t*>(h->d_first), reinterpret_cast<int8_t*>(h->d_hops), p.first ? 1 : 0, n.d_list, n.count, n.d_taps, n.d_shifts, n.d_tails, n.d_clipped, h->stream);
+    n.pushed = n.on;
 }
 
 // The observers of the staged hops: the ping band ahead of the detector, the waterfall
@@ -621,6 +628,73 @@ int msk144_set_wideband_ping_band(msk144_handle* h, const msk144_wideband_ping_b
     pb.on = p != nullptr;
     // E and Ef do not share a history: the next push with the detector on restarts it, and finds the tail all zero
     h->wb.pings.restart = true;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_notch(msk144_handle* h, const int32_t* channels, int32_t count, const msk144_wideband_notch_params* params)
+{
+    if(const int rc = wb_quiesce(h, "msk144_set_wideband_notch"); rc != MSK144_OK) return rc;
+    auto& n = h->wb.notch;
+    static_assert(sizeof(msk144_wideband_notch_params) == sizeof(msk144wb::NotchParams) && offsetof(msk144_wideband_notch_params, shift) == offsetof(msk144wb::NotchParams, shift),
+                  "msk144wb::NotchParams is msk144_wideband_notch_params");
+    const int C = h->wb.channels;
+    if(!channels) count = 0;
+    if(count < 0 || count > C) return fail(h, MSK144_EINVAL, "the notch table holds 0.." + std::to_string(C) + " channels");
+    if(count && !params) return fail(h, MSK144_EINVAL, "null argument");
+    std::vector<uint8_t> listed(static_cast<size_t>(C), 0);
+    std::vector<msk144wb::NotchParams> table(static_cast<size_t>(C));
+    for(int i = 0; i < count; i++)
+    {
+        const int32_t c = channels[i];
+        if(c < 0 || c >= C) return fail(h, MSK144_EINVAL, "notch channel " + std::to_string(c) + " is out of range");
+        if(listed[static_cast<size_t>(c)]) return fail(h, MSK144_EINVAL, "notch channel " + std::to_string(c) + " is listed twice");
+        listed[static_cast<size_t>(c)] = 1;
+        std::memcpy(&table[static_cast<size_t>(c)], &params[i], sizeof(msk144wb::NotchParams));
+        if(const std::string why = msk144wb::check_notch(table[static_cast<size_t>(c)].shift); !why.empty()) return fail(h, MSK144_EINVAL, why);
+    }
+    n.pushed = false;
+    if(count)
+    {
+        const size_t Cs = static_cast<size_t>(C), row = 2 * msk144wb::kNotchTaps;
+        if(wb_ensure(h, &n.d_list, Cs) || wb_ensure(h, &n.d_taps, Cs * row) || wb_ensure(h, &n.d_shifts, Cs) || wb_ensure(h, &n.d_clipped, Cs)) return MSK144_ENOMEM;
+        if(!n.d_tails)
+        {
+            if(wb_ensure(h, &n.d_tails, Cs * row)) return MSK144_ENOMEM;
+            HIP_TRY(h, hipMemset(n.d_tails, 0, Cs * row));
+        }
+        if(n.listed.empty()) n.listed.assign(Cs, 0), n.table.assign(Cs, msk144wb::NotchParams{});
+        std::vector<int32_t> list, shifts(Cs, 0);
+        std::vector<int8_t> taps(Cs * row, 0);
+        for(size_t c = 0; c < Cs; c++)
+        {
+            if(!listed[c]) continue;
+            list.push_back(static_cast<int32_t>(c));
+            shifts[c] = table[c].shift;
+            std::memcpy(&taps[c * row], table[c].taps, row);
+            // a new or a changed entry starts from silence; an unchanged one keeps its tail
+            if(!n.listed[c] || std::memcmp(&n.table[c], &table[c], sizeof(msk144wb::NotchParams)) != 0) HIP_TRY(h, hipMemset(n.d_tails + c * row, 0, row));
+        }
+        HIP_TRY(h, hipMemcpy(n.d_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(n.d_taps, taps.data(), taps.size(), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(n.d_shifts, shifts.data(), sizeof(int32_t) * Cs, hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemset(n.d_clipped, 0, sizeof(int32_t) * Cs));
+    }
+    n.listed = count ? listed : std::vector<uint8_t>();
+    n.table = count ? table : std::vector<msk144wb::NotchParams>();
+    n.count = count;
+    n.on = count > 0;
+    return MSK144_OK;
+}
+
+int msk144_wideband_notch_stats(msk144_handle* h, msk144_wideband_notch_count* out)
+{
+    if(!h || !out) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& n = h->wb.notch;
+    if(const int rc = wb_read_ready(h, "msk144_wideband_notch_stats", n.pushed, "no wideband push has been made with the notch on since it was last set"); rc != MSK144_OK) return rc;
+    const size_t C = static_cast<size_t>(h->wb.channels);
+    std::vector<int32_t> clipped(C);
+    HIP_TRY(h, hipMemcpy(clipped.data(), n.d_clipped, sizeof(int32_t) * C, hipMemcpyDeviceToHost));
+    for(size_t c = 0; c < C; c++) out[c] = msk144_wideband_notch_count{n.listed[c], clipped[c]};
     return MSK144_OK;
 }
 

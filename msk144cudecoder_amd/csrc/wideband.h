@@ -927,6 +927,244 @@ private:
     int64_t segments_ = 0, hops_ = 0;
 };
 
+// ---- the notch: steady carriers taken out of a channel's stored samples (msk144_set_wideband_notch, msk144_wideband_notch_stats) ----
+
+constexpr int kNotchTaps = 64;
+constexpr int kNotchTail = kNotchTaps - 1;   // raw (pre-notch) stored samples a channel keeps between pushes
+constexpr int kNotchDelay = 31;              // the output is the input delayed by this many samples, minus the estimate
+constexpr int kNotchMaxShift = 15;
+constexpr int kNotchMaxFreqs = 2;            // carriers of one channel's default design
+constexpr int kNotchMinHalfwidthHz = 50;
+constexpr int kNotchMaxHalfwidthHz = 500;
+constexpr int kNotchDefaultHalfwidthHz = 100;
+constexpr int kNotchMinSpacingHz = 1000;     // closer carriers over-subtract: the two pass bands of the estimate add
+
+// msk144_wideband_notch_params, field for field
+struct NotchParams
+{
+    int8_t taps[kNotchTaps][2];
+    int32_t shift;
+};
+static_assert(sizeof(NotchParams) == 132, "msk144_wideband_notch_params is 132 bytes");
+
+// The rule of msk144_set_wideband_notch that needs no handle: any int8 taps.  Empty string = valid.
+inline std::string check_notch(int32_t shift)
+{
+    if(shift < 0 || shift > kNotchMaxShift) return "notch shift must lie within 0..15";
+    return std::string();
+}
+
+// The rules of the default design.  Empty string = valid.
+inline std::string check_notch_design(const int32_t* freqs_hz, int n, int halfwidth_hz)
+{
+    if(n < 1 || n > kNotchMaxFreqs || !freqs_hz) return "a notch takes 1 or 2 frequencies";
+    if(halfwidth_hz < kNotchMinHalfwidthHz || halfwidth_hz > kNotchMaxHalfwidthHz) return "notch half-width must lie within 50..500 Hz";
+    for(int i = 0; i < n; i++)
+        if(std::abs(static_cast<long long>(freqs_hz[i])) + halfwidth_hz > kOutRate / 2) return "notch must lie within +-6000 Hz: |frequency| + half-width <= 6000";
+    if(n == 2 && std::abs(static_cast<long long>(freqs_hz[0]) - freqs_hz[1]) < kNotchMinSpacingHz) return "two notches of a channel must lie at least 1000 Hz apart";
+    return std::string();
+}
+
+// |H(f)|^2 of the whole stage, H(f) = e^{-j 2 pi f 31 / 12000} - B(f) / 2^shift with B(f) = sum b[k] e^{-j 2 pi f k / 12000}: what a
+// component at f_hz keeps of its power (without the rounding of the output)
+inline double notch_response(const NotchParams& p, double f_hz)
+{
+    const double scale = std::ldexp(1.0, -p.shift), d = -2.0 * M_PI * f_hz * kNotchDelay / kOutRate;
+    double re = std::cos(d), im = std::sin(d);
+    for(int k = 0; k < kNotchTaps; k++)
+    {
+        const double a = -2.0 * M_PI * f_hz * k / kOutRate, c = std::cos(a), s = std::sin(a);
+        re -= scale * (p.taps[k][0] * c - p.taps[k][1] * s);
+        im -= scale * (p.taps[k][0] * s + p.taps[k][1] * c);
+    }
+    return re * re + im * im;
+}
+
+// The default design, in double: a 63-tap Hamming-windowed sinc low-pass with cutoff halfwidth_hz centred on k = 31 and scaled to unit
+// DC gain, turned to each frequency by e^{+j 2 pi f (k - 31) / 12000} and summed: the estimate of the carriers, which the stage takes
+// from the input delayed by 31 samples.  shift = min(15, floor(log2(127 / largest |component|))), taps rint(value x 2^shift), tap 63 = 0.
+// The caller has checked the arguments.
+inline NotchParams notch_design(const int32_t* freqs_hz, int n, int halfwidth_hz)
+{
+    constexpr int N = kNotchTaps - 1;
+    double h[N], re[N] = {}, im[N] = {}, sum = 0.0, top = 0.0;
+    for(int k = 0; k < N; k++)
+    {
+        const double arg = 2.0 * halfwidth_hz * (k - kNotchDelay) / kOutRate;
+        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
+        h[k] = sinc * (0.54 - 0.46 * std::cos(2.0 * M_PI * k / (N - 1)));
+        sum += h[k];
+    }
+    for(int k = 0; k < N; k++)
+    {
+        for(int i = 0; i < n; i++)
+        {
+            const double a = 2.0 * M_PI * freqs_hz[i] * (k - kNotchDelay) / kOutRate;
+            re[k] += h[k] / sum * std::cos(a);
+            im[k] += h[k] / sum * std::sin(a);
+        }
+        top = std::max(top, std::max(std::fabs(re[k]), std::fabs(im[k])));
+    }
+    NotchParams p{};
+    p.shift = std::min(kNotchMaxShift, static_cast<int>(std::floor(std::log2(127.0 / top))));
+    for(int k = 0; k < N; k++)
+    {
+        p.taps[k][0] = static_cast<int8_t>(std::rint(std::ldexp(re[k], p.shift)));
+        p.taps[k][1] = static_cast<int8_t>(std::rint(std::ldexp(im[k], p.shift)));
+    }
+    return p;
+}
+
+MSK144WB_HD inline int32_t notch_sat8(int32_t v) { return v < -128 ? -128 : v > 127 ? 127 : v; }
+
+// One component of the stage: x the component of x[n - 31], z that of z[n].  The shift right is arithmetic.
+MSK144WB_HD inline int32_t notch_out(int32_t x, int32_t z, int32_t shift) { return (x * (1 << shift) - z + (shift ? 1 << (shift - 1) : 0)) >> shift; }
+
+// The stage on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push, tail[63][2] the channel's 63 raw
+// (pre-notch) stored samples before them, oldest first (all zero where the channel's filter starts); writes y[n][2] (y may be x),
+// adds the components that sat8 clamped to *clipped and moves the tail on to the last 63 samples of x.  z[m] = sum_k b[k] x[m - k]
+// in int32 as the ping band's, y[m] = sat8(((x[m - 31] << shift) - z[m] + r) >> shift).  What libmsk144host.so holds the Python model
+// and the kernel (notch.hip) to.
+inline void notch_filter(const NotchParams& p, const int8_t* x, int n, int8_t* tail, int8_t* y, int32_t* clipped)
+{
+    std::vector<int8_t> s(static_cast<size_t>(2 * (kNotchTail + n)));
+    std::memcpy(s.data(), tail, 2 * kNotchTail);
+    std::memcpy(s.data() + 2 * kNotchTail, x, static_cast<size_t>(2 * n));
+    for(int m = 0; m < n; m++)
+    {
+        int32_t zr = 0, zi = 0;
+        for(int k = 0; k < kNotchTaps; k++)
+        {
+            const int32_t xr = s[static_cast<size_t>(2 * (kNotchTail + m - k))], xi = s[static_cast<size_t>(2 * (kNotchTail + m - k) + 1)];
+            zr += p.taps[k][0] * xr - p.taps[k][1] * xi;
+            zi += p.taps[k][0] * xi + p.taps[k][1] * xr;
+        }
+        const size_t d = static_cast<size_t>(2 * (kNotchTail + m - kNotchDelay));
+        const int32_t vr = notch_out(s[d], zr, p.shift), vi = notch_out(s[d + 1], zi, p.shift);
+        const int32_t yr = notch_sat8(vr), yi = notch_sat8(vi);
+        *clipped += (yr != vr) + (yi != vi);
+        y[2 * m] = static_cast<int8_t>(yr);
+        y[2 * m + 1] = static_cast<int8_t>(yi);
+    }
+    std::memcpy(tail, s.data() + static_cast<size_t>(2 * n), 2 * kNotchTail);
+}
+
+// The host rule of --wideband-notch=auto: which carriers get a notch, from every push's msk144_wideband_waterfall_sums.  Host only,
+// with a Python twin (wideband.NotchPlanner).  db, period and persist are design parameters, not measurements.
+struct NotchPlan
+{
+    double db = kWaterfallCarrierDb;  // a bin is hot when it lies at least this far over the period's median bin
+    int32_t period = 23;              // pushes whose sums are added, about 5 s
+    int32_t persist = 2;              // consecutive periods the same bin, +-1, must be hot in
+};
+constexpr int kNotchPlanGuardBins = 3;     // bins either side of a channel's notches that the search leaves out
+constexpr int kNotchPlanMaxPeriod = 100000;
+constexpr int kNotchPlanMaxPersist = 1000;
+
+inline std::string check_notch_plan(const NotchPlan& p)
+{
+    if(!(p.db >= 1.0 && p.db <= 100.0)) return "notch auto DB must lie within 1..100 dB";
+    if(p.period < 1 || p.period > kNotchPlanMaxPeriod) return "notch auto PERIOD must lie within 1..100000 pushes";
+    if(p.persist < 1 || p.persist > kNotchPlanMaxPersist) return "notch auto PERSIST must lie within 1..1000 periods";
+    return std::string();
+}
+
+// a notch the planner added: at hz from the channel's offset, for a bin excess_db over the period's median bin
+struct NotchAdded
+{
+    int32_t channel, hz;
+    double excess_db;
+};
+
+// Per channel the planner adds the sums of `period` pushes.  At the end of a period it takes the highest bin j (the lowest at the
+// maximum) that is not within 3 bins of one of the channel's notches; the bin is hot when it lies at least db over the period's
+// median bin (rank 48 of all 96 in ascending order, which must be positive).  The same bin, +-1 from the period before, hot in
+// `persist` consecutive periods adds a notch at rint(125 (j - 48 + d)) Hz if the channel has fewer than 2 and check_notch_design
+// takes the new list (the spacing rule); d is the vertex of the parabola through 10 log10 of bins j - 1, j, j + 1, clamped to +-0.5,
+// and 0 at j = 0 or 95, where a neighbour is not positive or where the three do not form a peak.  Notches are only ever added
+// during a run: the notch is ahead of the waterfall, so a released notch could not be told from a carrier that left.
+class NotchPlanner
+{
+public:
+    NotchPlanner(int channels, const NotchPlan& plan, int halfwidth_hz)
+        : plan_(plan), halfwidth_(halfwidth_hz), acc_(static_cast<size_t>(channels) * kWaterfallBins, 0.0), chan_(static_cast<size_t>(channels))
+    {
+    }
+
+    // sums[channels][96] of one push; appends what this push added, by channel
+    void push(const double* sums, std::vector<NotchAdded>& out)
+    {
+        for(size_t k = 0; k < acc_.size(); k++) acc_[k] += sums[k];
+        if(++pushes_ < plan_.period) return;
+        pushes_ = 0;
+        for(size_t c = 0; c < chan_.size(); c++) end_period(static_cast<int32_t>(c), &acc_[c * kWaterfallBins], out);
+        std::fill(acc_.begin(), acc_.end(), 0.0);
+    }
+
+    const std::vector<int32_t>& notches(int channel) const { return chan_[static_cast<size_t>(channel)].hz; }
+
+    static double vertex(const double* a, int j)
+    {
+        if(j <= 0 || j >= kWaterfallBins - 1 || !(a[j - 1] > 0.0) || !(a[j + 1] > 0.0) || !(a[j] > 0.0)) return 0.0;
+        const double lm = 10.0 * std::log10(a[j - 1]), l0 = 10.0 * std::log10(a[j]), lp = 10.0 * std::log10(a[j + 1]);
+        const double den = lm - 2.0 * l0 + lp;
+        if(!(den < 0.0)) return 0.0;
+        const double d = 0.5 * (lm - lp) / den;
+        return d < -0.5 ? -0.5 : d > 0.5 ? 0.5 : d;
+    }
+
+private:
+    struct Chan
+    {
+        std::vector<int32_t> hz;  // the channel's notches
+        int32_t bin = -1, run = 0;  // the hot bin of the last period and the periods in a row it has been hot
+    };
+
+    void end_period(int32_t c, const double* a, std::vector<NotchAdded>& out)
+    {
+        Chan& s = chan_[static_cast<size_t>(c)];
+        int j = -1;
+        for(int i = 0; i < kWaterfallBins; i++)
+        {
+            bool guarded = false;
+            for(int32_t f : s.hz) guarded = guarded || std::abs(i - (static_cast<int>(std::lrint(f / 125.0)) + kWaterfallBins / 2)) <= kNotchPlanGuardBins;
+            if(!guarded && (j < 0 || a[i] > a[j])) j = i;
+        }
+        std::vector<double> sorted(a, a + kWaterfallBins);
+        std::nth_element(sorted.begin(), sorted.begin() + kWaterfallBins / 2, sorted.end());
+        const double median = sorted[kWaterfallBins / 2];
+        const double excess = j >= 0 && median > 0.0 && a[j] > 0.0 ? 10.0 * std::log10(a[j] / median) : 0.0;
+        if(!(j >= 0 && median > 0.0 && excess >= plan_.db))
+        {
+            s.bin = -1, s.run = 0;
+            return;
+        }
+        s.run = s.bin >= 0 && std::abs(j - s.bin) <= 1 ? s.run + 1 : 1;
+        s.bin = j;
+        if(s.run < plan_.persist || s.hz.size() >= static_cast<size_t>(kNotchMaxFreqs)) return;
+        std::vector<int32_t> next = s.hz;
+        next.push_back(static_cast<int32_t>(std::lrint(125.0 * (j - kWaterfallBins / 2 + vertex(a, j)))));
+        if(!check_notch_design(next.data(), static_cast<int>(next.size()), halfwidth_).empty()) return;
+        s.hz = next;
+        s.bin = -1, s.run = 0;
+        out.push_back(NotchAdded{c, next.back(), excess});
+    }
+
+    NotchPlan plan_;
+    int halfwidth_;
+    int32_t pushes_ = 0;
+    std::vector<double> acc_;
+    std::vector<Chan> chan_;
+};
+
+// The stderr line of a notch the planner added at hop k
+inline std::string notch_added_line(const NotchAdded& n, int32_t offset_hz, long long hop)
+{
+    char buf[192];
+    snprintf(buf, sizeof(buf), "msk144hipdecoder: wideband notch: ch=%d offset=%d notch=%d excess=%.1f at hop %lld", n.channel, offset_hz, n.hz, n.excess_db, hop);
+    return buf;
+}
+
 // Every rule of the contract (include/msk144hip.h) except the ones that need a handle.  Empty string = valid.
 inline std::string check_config(int64_t rate_hz, int format, int K, float gain, const int32_t* offsets, int count)
 {

@@ -68,6 +68,20 @@ class WidebandPingBandParams(C.Structure):
     _fields_ = [("taps", (C.c_int8 * 2) * 64), ("shift", C.c_int32)]
 
 
+class WidebandNotchParams(C.Structure):
+    """msk144_wideband_notch_params."""
+    _fields_ = [("taps", (C.c_int8 * 2) * 64), ("shift", C.c_int32)]
+
+
+class WidebandNotchCount(C.Structure):
+    """msk144_wideband_notch_count; NOTCH_COUNT_DTYPE is the same record for numpy."""
+    _fields_ = [("on", C.c_int32), ("clipped", C.c_int32)]
+
+
+NOTCH_COUNT_DTYPE = np.dtype([("on", "<i4"), ("clipped", "<i4")])
+assert C.sizeof(WidebandNotchParams) == 132 and C.sizeof(WidebandNotchCount) == NOTCH_COUNT_DTYPE.itemsize == 8
+
+
 class WidebandCaptureParams(C.Structure):
     """msk144_wideband_capture_params."""
     _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("max_units", C.c_int32), ("num_listed", C.c_int32), ("listed", C.c_int32 * 16)]
@@ -157,6 +171,8 @@ PROTOTYPES = {
     "msk144_wideband_pings": ([_vp, _P(WidebandPing)], C.c_int),
     "msk144_wideband_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
     "msk144_set_wideband_ping_band": ([_vp, _P(WidebandPingBandParams)], C.c_int),
+    "msk144_set_wideband_notch": ([_vp, _P(_i32), _i32, _P(WidebandNotchParams)], C.c_int),
+    "msk144_wideband_notch_stats": ([_vp, _P(WidebandNotchCount)], C.c_int),
     "msk144_set_wideband_waterfall": ([_vp, _P(WidebandWaterfall)], C.c_int),
     "msk144_wideband_waterfall": ([_vp, _i32, _P(C.c_float), _P(_i32)], C.c_int),
     "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
@@ -576,6 +592,31 @@ class HipDecoder:
         n = C.c_int32()
         self._chk(self.L.msk144_wideband_ping_blocks(self.h, -1 if channel is None else int(channel), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
         return out[:, :n.value].copy() if channel is None else out[0, :n.value].copy()
+
+    def set_wideband_notch(self, table=None):
+        """The notch table from the next push on (include/msk144hip.h): {channel: [f_hz, ...]} takes the default design for 1 or 2
+        frequencies relative to the channel's offset (wideband.notch_taps, halfwidth_hz = 100), {channel: (taps, shift)} a filter of
+        one's own (taps int8 [k][2], k <= 64).  The table replaces the one before it: a channel whose entry is unchanged keeps its
+        tail, a new or changed one starts from silence.  set_wideband_notch(None), or an empty table, switches the notch off."""
+        if not table:
+            self._chk(self.L.msk144_set_wideband_notch(self.h, None, 0, None))
+            return
+        from .wideband import notch_entry
+        chans = sorted(int(c) for c in table)
+        if len(set(chans)) != len(table):
+            raise ValueError("a channel is listed twice")
+        arr = (WidebandNotchParams * len(chans))()
+        for a, c in zip(arr, chans):
+            t, s = notch_entry(table[c])
+            C.memmove(a.taps, t.ctypes.data, t.nbytes)
+            a.shift = int(s)
+        self._chk(self.L.msk144_set_wideband_notch(self.h, (C.c_int32 * len(chans))(*chans), len(chans), arr))
+
+    def wideband_notch_stats(self) -> np.ndarray:
+        """NOTCH_COUNT_DTYPE [channels]: whether the channel was notched in the last push, and the components of it that sat8 clamped."""
+        out = np.zeros(self.channels, dtype=NOTCH_COUNT_DTYPE)
+        self._chk(self.L.msk144_wideband_notch_stats(self.h, out.ctypes.data_as(C.POINTER(WidebandNotchCount))))
+        return out
 
     def set_wideband_waterfall(self, window="hann"):
         """The per-channel waterfall from the next push on (include/msk144hip.h): set_wideband_waterfall() takes the periodic Hann

@@ -217,6 +217,88 @@ int msk144host_wideband_ping_band_parse(const char* arg, int32_t centre_default,
     return 0;
 }
 
+// ---- the notch (csrc/wideband.h: the default design, the checks, the response, the filter) ----
+
+// The default design of a channel's notch: taps[64][2] int8 and the shift for n frequencies; -1 with the refusal text for what the
+// design does not take.  The taps msk144cudecoder_amd.wideband.notch_taps hands to the library.
+int msk144host_wideband_notch_design(const int32_t* freqs_hz, int32_t n, int32_t halfwidth_hz, int8_t* taps, int32_t* shift, char* why, int why_len)
+{
+    const std::string s = msk144wb::check_notch_design(freqs_hz, n, halfwidth_hz);
+    if(!s.empty()) return copy_why(s, why, why_len);
+    const msk144wb::NotchParams p = msk144wb::notch_design(freqs_hz, n, halfwidth_hz);
+    std::memcpy(taps, p.taps, sizeof(p.taps));
+    *shift = p.shift;
+    return copy_why(s, why, why_len);
+}
+// 0 when msk144_set_wideband_notch takes the shift (any int8 taps are valid), else -1 with the refusal text
+int msk144host_wideband_notch_check(int32_t shift, char* why, int why_len) { return copy_why(msk144wb::check_notch(shift), why, why_len); }
+// |H(f)|^2 of the stage with these taps and shift (csrc/wideband.h notch_response)
+double msk144host_wideband_notch_response(const int8_t* taps, int32_t shift, double f_hz)
+{
+    msk144wb::NotchParams p{};
+    std::memcpy(p.taps, taps, sizeof(p.taps));
+    p.shift = shift;
+    return msk144wb::notch_response(p, f_hz);
+}
+// One push of `channels` channels, each with its own entry: taps[channels][64][2], shifts[channels], x[channels][n][2] stored int8
+// samples, tails[channels][63][2] raw samples in and out, y[channels][n][2], clipped[channels] (set, not added to).  -1 for a shift
+// or an n out of range.
+int msk144host_wideband_notch_filter(const int8_t* taps, const int32_t* shifts, int channels, const int8_t* x, int n, int8_t* tails, int8_t* y, int32_t* clipped)
+{
+    if(channels < 1 || n < 0) return -1;
+    for(int c = 0; c < channels; c++)
+        if(!msk144wb::check_notch(shifts[c]).empty()) return -1;
+    for(int c = 0; c < channels; c++)
+    {
+        msk144wb::NotchParams p{};
+        std::memcpy(p.taps, taps + static_cast<size_t>(c) * sizeof(p.taps), sizeof(p.taps));
+        p.shift = shifts[c];
+        clipped[c] = 0;
+        msk144wb::notch_filter(p, x + static_cast<size_t>(c) * 2 * n, n, tails + static_cast<size_t>(c) * 2 * msk144wb::kNotchTail, y + static_cast<size_t>(c) * 2 * n, &clipped[c]);
+    }
+    return 0;
+}
+
+// "SPEC[/HALFWIDTH]" as the program parses the value of --wideband-notch: -1 when it refuses it; else the number of table entries
+// (0 with auto) and out = {auto, halfwidth, period, persist, then per entry: channel, n, f0, f1}, *db the rule's DB; cap counts int32
+int msk144host_wideband_notch_parse(const char* arg, int32_t* out, int cap, double* db)
+{
+    WidebandOptions w;
+    if(!parse_wideband_notch(arg, w) || static_cast<size_t>(cap) < 4 + 4 * w.notch_table.size()) return -1;
+    out[0] = w.notch_auto ? 1 : 0, out[1] = w.notch_halfwidth, out[2] = w.notch_plan.period, out[3] = w.notch_plan.persist;
+    *db = w.notch_plan.db;
+    for(size_t i = 0; i < w.notch_table.size(); i++)
+    {
+        const std::vector<int32_t>& f = w.notch_table[i].second;
+        int32_t* e = out + 4 + 4 * i;
+        e[0] = w.notch_table[i].first, e[1] = static_cast<int32_t>(f.size()), e[2] = f[0], e[3] = f.size() > 1 ? f[1] : 0;
+    }
+    return static_cast<int>(w.notch_table.size());
+}
+// The planner of --wideband-notch=auto (csrc/wideband.h NotchPlanner); nullptr for a plan check_notch_plan refuses
+void* msk144host_wideband_notch_planner_new(int channels, double db, int32_t period, int32_t persist, int32_t halfwidth_hz)
+{
+    msk144wb::NotchPlan plan;
+    plan.db = db, plan.period = period, plan.persist = persist;
+    if(channels < 1 || !msk144wb::check_notch_plan(plan).empty()) return nullptr;
+    return new msk144wb::NotchPlanner(channels, plan, halfwidth_hz);
+}
+void msk144host_wideband_notch_planner_free(void* p) { delete static_cast<msk144wb::NotchPlanner*>(p); }
+// sums[channels][96] of one push; what it added into out_channel, out_hz, out_excess (at most cap; the count is returned)
+int msk144host_wideband_notch_planner_push(void* p, const double* sums, int32_t* out_channel, int32_t* out_hz, double* out_excess, int cap)
+{
+    std::vector<msk144wb::NotchAdded> added;
+    static_cast<msk144wb::NotchPlanner*>(p)->push(sums, added);
+    for(size_t i = 0; i < added.size() && i < static_cast<size_t>(cap); i++) out_channel[i] = added[i].channel, out_hz[i] = added[i].hz, out_excess[i] = added[i].excess_db;
+    return static_cast<int>(added.size());
+}
+// the stderr line of an added notch
+void msk144host_wideband_notch_line(int32_t channel, int32_t hz, double excess_db, int32_t offset_hz, int64_t hop, char* out, int cap)
+{
+    std::strncpy(out, msk144wb::notch_added_line(msk144wb::NotchAdded{channel, hz, excess_db}, offset_hz, hop).c_str(), static_cast<size_t>(cap) - 1);
+    out[cap - 1] = 0;
+}
+
 // ---- the per-channel waterfall (csrc/wideband.h: the window, the check, the dB scale, the line, the frequency rule of a ping event) ----
 
 // the default window of msk144_set_wideband_waterfall (periodic Hann) in out[96]; returns 96

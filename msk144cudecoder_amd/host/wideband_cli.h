@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace msk144host
@@ -51,6 +52,11 @@ struct WidebandOptions
     bool capture_by_pings = true;              // CHANNELS is `pings` (the default; needs --wideband-pings): what the rule keeps around activity
     std::vector<int32_t> capture_channels;     // ... or a list of up to 16 channel indices, kept whether active or not
     msk144wb::CaptureParams capture_params;    // max_units is set once the channels are known: min(2 x channels, 512)
+    bool notch = false;           // --wideband-notch=SPEC[/HALFWIDTH]: steady carriers taken out of single channels
+    bool notch_auto = false;                   // SPEC is auto[:DB[:PERIOD[:PERSIST]]]: the host rule msk144wb::NotchPlanner on the waterfall sums
+    msk144wb::NotchPlan notch_plan;
+    int notch_halfwidth = msk144wb::kNotchDefaultHalfwidthHz;
+    std::vector<std::pair<int32_t, std::vector<int32_t>>> notch_table;  // ... or ch:Hz[+Hz],...: (channel, its frequencies from the channel's offset)
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -84,6 +90,9 @@ struct WidebandApi
     int (*set_waterfall)(msk144_handle*, const msk144_wideband_waterfall_params*) = nullptr;
     int (*waterfall)(msk144_handle*, int32_t, float*, int32_t*) = nullptr;
     int (*waterfall_sums)(msk144_handle*, double*) = nullptr;
+    // --wideband-notch
+    int (*set_notch)(msk144_handle*, const int32_t*, int32_t, const msk144_wideband_notch_params*) = nullptr;
+    int (*notch_stats)(msk144_handle*, msk144_wideband_notch_count*) = nullptr;
     // --wideband-capture
     int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
     int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
@@ -113,6 +122,8 @@ struct WidebandApi
             {w.ping_band, "ping band", ": --wideband-pings-band needs it", {{"msk144_set_wideband_ping_band", &set_ping_band}}},
             {w.waterfall, "waterfall", ": --wideband-waterfall needs it",
              {{"msk144_set_wideband_waterfall", &set_waterfall}, {"msk144_wideband_waterfall", &waterfall}, {"msk144_wideband_waterfall_sums", &waterfall_sums}}},
+            {w.notch, "notch", ": --wideband-notch needs it", {{"msk144_set_wideband_notch", &set_notch}, {"msk144_wideband_notch_stats", &notch_stats}}},
+            {w.notch && w.notch_auto, "waterfall", ": --wideband-notch=auto needs it", {{"msk144_set_wideband_waterfall", &set_waterfall}, {"msk144_wideband_waterfall_sums", &waterfall_sums}}},
             {w.capture, "capture", ": --wideband-capture needs it", {{"msk144_set_wideband_capture", &set_capture}, {"msk144_wideband_capture", &capture}}},
         };
         for(const Group& g : groups)
@@ -301,6 +312,56 @@ inline bool parse_wideband_capture(const std::string& s, WidebandOptions& w)
     return f.size() < 4 || parse_int_in(f[3], 0, 1, w.capture_params.pre);
 }
 
+// "SPEC[/HALFWIDTH]": HALFWIDTH 50..500 Hz (100); SPEC "auto[:DB[:PERIOD[:PERSIST]]]" - DB a decimal within 1..100, PERIOD 1..100000
+// pushes, PERSIST 1..1000 periods - or "ch:Hz[+Hz],ch:Hz,...": different channels, each with one or two integer frequencies that
+// msk144wb::check_notch_design takes (whether the channels exist needs the other options: check_wideband_options)
+inline bool parse_wideband_notch(const std::string& s, WidebandOptions& w)
+{
+    w.notch = true;
+    w.notch_auto = false;
+    w.notch_plan = msk144wb::NotchPlan();
+    w.notch_halfwidth = msk144wb::kNotchDefaultHalfwidthHz;
+    w.notch_table.clear();
+    const std::vector<std::string> parts = split_fields(s, '/');
+    if(parts.size() > 2 || parts[0].empty()) return false;
+    if(parts.size() > 1 && !parse_int_in(parts[1], msk144wb::kNotchMinHalfwidthHz, msk144wb::kNotchMaxHalfwidthHz, w.notch_halfwidth)) return false;
+    if(parts[0].compare(0, 4, "auto") == 0)
+    {
+        const std::vector<std::string> f = split_fields(parts[0], ':');
+        w.notch_auto = true;
+        if(f[0] != "auto" || f.size() > 4) return false;
+        if(f.size() > 1)
+        {
+            char* end = nullptr;
+            w.notch_plan.db = std::strtod(f[1].c_str(), &end);
+            if(f[1].empty() || !end || *end != 0) return false;
+        }
+        if(f.size() > 2 && !parse_int_in(f[2], 1, msk144wb::kNotchPlanMaxPeriod, w.notch_plan.period)) return false;
+        if(f.size() > 3 && !parse_int_in(f[3], 1, msk144wb::kNotchPlanMaxPersist, w.notch_plan.persist)) return false;
+        return msk144wb::check_notch_plan(w.notch_plan).empty();
+    }
+    for(const std::string& item : split_fields(parts[0], ','))
+    {
+        const size_t colon = item.find(':');
+        int32_t c = 0;
+        if(colon == std::string::npos || !parse_int_in(item.substr(0, colon), 0, INT32_MAX, c)) return false;
+        for(const auto& e : w.notch_table)
+            if(e.first == c) return false;
+        std::string list = item.substr(colon + 1);
+        if(!list.empty() && list[0] == '+') list.erase(0, 1);  // "+300" is 300
+        std::vector<int32_t> freqs;
+        for(const std::string& hz : split_fields(list, '+'))
+        {
+            int32_t f = 0;
+            if(!parse_int_in(hz, INT32_MIN, INT32_MAX, f)) return false;
+            freqs.push_back(f);
+        }
+        if(!msk144wb::check_notch_design(freqs.data(), static_cast<int>(freqs.size()), w.notch_halfwidth).empty()) return false;
+        w.notch_table.emplace_back(c, freqs);
+    }
+    return true;
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -358,6 +419,7 @@ inline bool take_wideband_option(const std::string& name, const char* arg, Wideb
     else if(name == "wideband-waterfall") good = parse_wideband_waterfall(value, w);
     else if(name == "wideband-capture") good = parse_wideband_capture(value, w);
     else if(name == "wideband-pings-band") w.ping_band = true, w.ping_band_arg = value;
+    else if(name == "wideband-notch") good = parse_wideband_notch(value, w);
     else return false;
     w.any_option = true;
     if(!good && w.parse_error.empty()) w.parse_error = "bad value for --" + name + ": '" + value + "'";
@@ -371,7 +433,8 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     if(w.rate_hz <= 0)
     {
         const std::pair<bool, const char*> own_line[] = {{w.blanker, "--wideband-blanker"},      {w.spectrum, "--wideband-spectrum"},   {w.pings, "--wideband-pings"},
-                                                         {w.ping_band, "--wideband-pings-band"}, {w.waterfall, "--wideband-waterfall"}, {w.capture, "--wideband-capture"}};
+                                                         {w.ping_band, "--wideband-pings-band"}, {w.waterfall, "--wideband-waterfall"}, {w.capture, "--wideband-capture"},
+                                                         {w.notch, "--wideband-notch"}};
         for(const auto& o : own_line)
             if(o.first) return std::string(o.second) + " needs --wideband-rate=HZ";
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
@@ -395,6 +458,9 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     for(size_t i = 0; w.capture && i < w.capture_channels.size(); i++)
         if(static_cast<size_t>(w.capture_channels[i]) >= w.offsets.size())
             return "--wideband-capture: channel " + std::to_string(w.capture_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
+    for(const auto& e : w.notch_table)
+        if(static_cast<size_t>(e.first) >= w.offsets.size())
+            return "--wideband-notch: channel " + std::to_string(e.first) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
     return "";
 }
 

@@ -6,6 +6,7 @@
 // Threads: no lock, by this rule.  prepare(), configure(), finish() and print_summary() run on the main thread, the first two before
 // the DeviceLoop that holds this object starts its threads, the last two after it has joined them.  pushed() and read_push() run on
 // the loop's ingest thread while it lives, read_push() once more on the main thread (DeviceLoop::join) after it has ended.
+// With --wideband-notch=auto read_push() is also where a new notch table goes to the library, on the thread that makes the next push.
 #pragma once
 
 #include "wideband_cli.h"
@@ -40,7 +41,7 @@ public:
     void pushed(bool first) { pending_components_ = 2ll * channels() * (first ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES); }
     // Reads what the last push left, if one is unread, into the state blocks and the files: the clip count (which waits for the
     // push's kernels), levels, spectrum, then the ping records with - behind them, for the events they close - the waterfall rows and
-    // the capture units.  false: error() says why.
+    // the capture units, last the notch counts and, with auto, the planner's step and the new table for the next push.  false: error() says why.
     bool read_push(msk144_handle* h);
     // The end of the stream: the last, shorter spectrum group, the ping events still open, the open capture segments.  false: error().
     bool finish();
@@ -58,6 +59,8 @@ private:
     bool read_pings(msk144_handle* h);
     bool read_waterfall(msk144_handle* h);
     bool read_capture(msk144_handle* h);
+    bool read_notch(msk144_handle* h);
+    bool set_notch_table(msk144_handle* h);
     bool write_ping_events();
     void write_spectrum_line();
 
@@ -111,6 +114,15 @@ private:
         std::vector<int8_t> data;                         // [max_units][5184]
         long long dropped = 0;
     } capture_;
+    struct Notch  // --wideband-notch: the table the library holds, a fixed one or what the planner has added so far
+    {
+        std::unique_ptr<msk144wb::NotchPlanner> planner;  // with auto only
+        std::vector<std::vector<int32_t>> table;          // [channels] the channel's frequencies; empty: not notched
+        std::vector<msk144_wideband_notch_count> counts;  // [channels] of the last push
+        std::vector<double> sums;                         // [channels][96] of the last push, when --wideband-waterfall does not read them
+        long long pushes = 0, clamped = 0;                // pushes read, components clamped over the run
+        bool set = false;                                 // the library holds a table: the last push was made with it
+    } notch_;
 };
 
 }  // namespace msk144host

@@ -98,6 +98,14 @@ inline bool WidebandRun::prepare()
         waterfall_.sums.assign(C * msk144wb::kWaterfallBins, 0.0);
         waterfall_.run = waterfall_.sums;
     }
+    if(opt_.notch)
+    {
+        notch_.table.assign(C, std::vector<int32_t>());
+        notch_.counts.resize(C);
+        for(const auto& e : opt_.notch_table) notch_.table[static_cast<size_t>(e.first)] = e.second;
+        if(opt_.notch_auto) notch_.planner.reset(new msk144wb::NotchPlanner(static_cast<int>(C), opt_.notch_plan, opt_.notch_halfwidth));
+        if(opt_.notch_auto && !opt_.waterfall) notch_.sums.assign(C * msk144wb::kWaterfallBins, 0.0);
+    }
     if(opt_.capture)
     {
         capture_.segments.reset(new msk144wb::CaptureSegments(opt_.capture_dir, opt_.offsets));
@@ -165,7 +173,7 @@ inline bool WidebandRun::configure(msk144_handle* h)
         const msk144_wideband_pings_params pp{opt_.ping_params.ratio_q4, opt_.ping_params.memory, opt_.ping_params.min_ref};
         if(api_.set_pings(h, &pp) != MSK144_OK) return set_failed(h);
     }
-    if(opt_.waterfall)
+    if(opt_.waterfall || (opt_.notch && opt_.notch_auto))  // auto reads the sums of every push; without --wideband-waterfall no file is written
     {
         const msk144_wideband_waterfall_params fp{nullptr};
         if(api_.set_waterfall(h, &fp) != MSK144_OK) return set_failed(h);
@@ -180,6 +188,7 @@ inline bool WidebandRun::configure(msk144_handle* h)
         std::copy(opt_.capture_channels.begin(), opt_.capture_channels.end(), cp.listed);
         if(api_.set_capture(h, &cp) != MSK144_OK) return set_failed(h);
     }
+    if(opt_.notch && !opt_.notch_auto && !set_notch_table(h)) return false;
     if(opt_.blanker)
     {
         const msk144_wideband_blanker bl{opt_.blanker_params.threshold_q4, opt_.blanker_params.pre, opt_.blanker_params.post};
@@ -203,7 +212,7 @@ inline bool WidebandRun::read_push(msk144_handle* h)
         pending_components_ = 0;
     }
     ok = ok && (!opt_.levels || read_levels(h)) && (!opt_.spectrum || read_spectrum(h)) && (!opt_.pings || read_pings(h)) && (!opt_.waterfall || read_waterfall(h)) &&
-         (!opt_.capture || read_capture(h)) && (!opt_.pings || write_ping_events());
+         (!opt_.capture || read_capture(h)) && (!opt_.pings || write_ping_events()) && (!opt_.notch || read_notch(h));
     if(!ok && error_.empty()) error_ = msk144_last_error(h);
     return ok;
 }
@@ -370,6 +379,52 @@ inline bool WidebandRun::read_capture(msk144_handle* h)
     return false;
 }
 
+// the whole table to the library: the default design of every notched channel; from the next push on
+inline bool WidebandRun::set_notch_table(msk144_handle* h)
+{
+    std::vector<int32_t> channels;
+    std::vector<msk144_wideband_notch_params> params;
+    for(size_t c = 0; c < notch_.table.size(); c++)
+    {
+        const std::vector<int32_t>& f = notch_.table[c];
+        if(f.empty()) continue;
+        const msk144wb::NotchParams d = msk144wb::notch_design(f.data(), static_cast<int>(f.size()), opt_.notch_halfwidth);
+        msk144_wideband_notch_params np;
+        static_assert(sizeof(np) == sizeof(d), "msk144wb::NotchParams is msk144_wideband_notch_params");
+        std::memcpy(&np, &d, sizeof(np));
+        channels.push_back(static_cast<int32_t>(c));
+        params.push_back(np);
+    }
+    if(api_.set_notch(h, channels.data(), static_cast<int32_t>(channels.size()), params.data()) != MSK144_OK) return set_failed(h);
+    notch_.set = !channels.empty();
+    return true;
+}
+
+// The clamped components of the push, then with auto the planner's step on the push's waterfall sums: every notch it adds is one
+// line on stderr, and the new table goes to the library for the next push (a hop boundary, as an AGC step).
+inline bool WidebandRun::read_notch(msk144_handle* h)
+{
+    Notch& n = notch_;
+    const long long hop = ++n.pushes;  // the newest hop of the push: a first push carries hops 0 and 1
+    if(n.set)
+    {
+        if(api_.notch_stats(h, n.counts.data()) != MSK144_OK) return false;
+        for(const msk144_wideband_notch_count& c : n.counts) n.clamped += c.clipped;
+    }
+    if(!n.planner) return true;
+    if(!opt_.waterfall && api_.waterfall_sums(h, n.sums.data()) != MSK144_OK) return false;
+    std::vector<msk144wb::NotchAdded> added;
+    n.planner->push(opt_.waterfall ? waterfall_.sums.data() : n.sums.data(), added);
+    for(const msk144wb::NotchAdded& a : added)
+    {
+        n.table[static_cast<size_t>(a.channel)] = n.planner->notches(a.channel);
+        std::cerr << msk144wb::notch_added_line(a, opt_.offsets[static_cast<size_t>(a.channel)], hop) << std::endl;
+    }
+    if(added.empty() || set_notch_table(h)) return true;
+    error_ = msk144_last_error(h);
+    return false;
+}
+
 inline void WidebandRun::print_summary(msk144_handle* h) const
 {
     char buf[96];
@@ -447,6 +502,28 @@ inline void WidebandRun::print_summary(msk144_handle* h) const
             line += buf;
         }
         std::cerr << line << std::endl;
+    }
+    if(opt_.notch)
+    {
+        // channels notched, notches, clamped components over the run, and up to three channels with their frequencies
+        int channels = 0, notches = 0;
+        std::string which;
+        for(size_t c = 0; c < notch_.table.size(); c++)
+        {
+            const std::vector<int32_t>& f = notch_.table[c];
+            if(f.empty()) continue;
+            notches += static_cast<int>(f.size());
+            if(++channels > 3) continue;
+            which += (channels == 1 ? "; ch=" : " ch=") + std::to_string(c);
+            for(size_t i = 0; i < f.size(); i++)
+            {
+                snprintf(buf, sizeof(buf), "%s%+d", i ? "," : " ", f[i]);
+                which += buf;
+            }
+            which += " Hz";
+        }
+        std::cerr << "msk144hipdecoder: wideband notch: " << channels << " of " << notch_.table.size() << " channels notched, " << notches << " notches of +-" << opt_.notch_halfwidth
+                  << " Hz, " << notch_.clamped << " components clamped" << which << std::endl;
     }
     if(opt_.capture)
     {

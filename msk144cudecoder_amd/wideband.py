@@ -503,6 +503,176 @@ class PingBand:
         return np.minimum(S >> self.shift, PING_BAND_MAX_ENERGY)
 
 
+# ---- the notch: steady carriers taken out of a channel's stored samples (msk144_set_wideband_notch) ----
+
+NOTCH_TAPS = 64
+NOTCH_DELAY = 31        # MSK144_NOTCH_DELAY: the output is the input delayed by 31 samples, minus the estimate of the carriers
+NOTCH_MAX_SHIFT = 15
+NOTCH_HALFWIDTH_HZ = 100
+
+
+def notch_taps(freqs, halfwidth_hz: int = NOTCH_HALFWIDTH_HZ) -> Tuple[np.ndarray, int]:
+    """The default design of the contract for 1 or 2 frequencies (Hz from the channel's offset), from libmsk144host.so
+    (csrc/wideband.h notch_design): (int8 [64][2] taps (br, bi), shift)."""
+    L = _host_lib()
+    f = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.int32)
+    if f.ndim != 1 or np.any(f != np.atleast_1d(freqs)):
+        raise ValueError("notch frequencies must be integers")
+    taps = np.zeros((NOTCH_TAPS, 2), dtype=np.int8)
+    shift = C.c_int32(0)
+    why = C.create_string_buffer(256)
+    L.msk144host_wideband_notch_design.restype = C.c_int
+    rc = L.msk144host_wideband_notch_design(f.ctypes.data_as(C.c_void_p), C.c_int32(len(f)), C.c_int32(int(halfwidth_hz)), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why,
+                                            len(why))
+    if rc != 0:
+        raise ValueError(why.value.decode())
+    return taps, int(shift.value)
+
+
+def notch_entry(entry) -> Tuple[np.ndarray, int]:
+    """One entry of a notch table as (int8 [64][2] taps, shift): a list of frequencies takes the default design, (taps, shift) is
+    checked and zero-padded."""
+    if isinstance(entry, tuple) and len(entry) == 2 and np.ndim(entry[0]) == 2:
+        t, shift = np.asarray(entry[0]), int(entry[1])
+        if t.shape[1] != 2 or not 1 <= t.shape[0] <= NOTCH_TAPS or np.any(t != t.astype(np.int8)):
+            raise ValueError("taps must be int8 [k][2] with 1 <= k <= 64")
+        full = np.zeros((NOTCH_TAPS, 2), dtype=np.int8)
+        full[:t.shape[0]] = t
+        return full, shift
+    return notch_taps(list(entry))
+
+
+class Notch:
+    """The notch of the contract (include/msk144hip.h) in int64 numpy, push by push: per channel of the table z[n] = sum b[k] x[n - k]
+    on the stored int8 values, y[n] = sat8(((x[n - 31] << s) - z[n] + r) >> s), and the 63 raw stored samples before the next push.
+    set(table) takes what HipDecoder.set_wideband_notch takes and, as the library, zeroes the tail of a channel whose entry is new or
+    changed and keeps that of an unchanged one; reset() stands for a first push: every tail is zero."""
+
+    def __init__(self, channels: int, table=None):
+        self.channels = int(channels)
+        self.table = {}
+        self.reset()
+        self.set(table)
+
+    def reset(self):
+        self.tail = np.zeros((self.channels, NOTCH_TAPS - 1, 2), dtype=np.int8)
+
+    def set(self, table):
+        new = {}
+        for c, entry in (table or {}).items():
+            c = int(c)
+            if not 0 <= c < self.channels or c in new:
+                raise ValueError(f"channel {c} is out of range or listed twice")
+            t, s = notch_entry(entry)
+            if not 0 <= s <= NOTCH_MAX_SHIFT:
+                raise ValueError("shift must lie within 0..15")
+            new[c] = (t, s)
+            old = self.table.get(c)
+            if old is None or old[1] != s or not np.array_equal(old[0], t):
+                self.tail[c] = 0
+        self.table = new
+
+    def push(self, q):
+        """(int8 [channel][M][2] the notched hops, int64 [channel] clamped components) from the int8 hops q [channel][M][2] of one
+        push; the channels not in the table pass unchanged; the tails of those in it move on."""
+        q = np.asarray(q)
+        if q.ndim != 3 or q.shape[0] != self.channels or q.shape[2] != 2:
+            raise ValueError(f"hops must be [{self.channels}][M][2]")
+        M, T = q.shape[1], NOTCH_TAPS - 1
+        out = q.astype(np.int8).copy()
+        clipped = np.zeros(self.channels, dtype=np.int64)
+        for c, (taps, s) in self.table.items():
+            x = np.concatenate([self.tail[c], q[c].astype(np.int8)]).astype(np.int64)
+            z = np.zeros((M, 2), dtype=np.int64)
+            for k in range(NOTCH_TAPS):
+                br, bi = int(taps[k, 0]), int(taps[k, 1])
+                if br == 0 and bi == 0:
+                    continue
+                a, b = x[T - k:T - k + M, 0], x[T - k:T - k + M, 1]
+                z[:, 0] += br * a - bi * b
+                z[:, 1] += br * b + bi * a
+            v = ((x[T - NOTCH_DELAY:T - NOTCH_DELAY + M] << s) - z + ((1 << (s - 1)) if s else 0)) >> s
+            y = np.clip(v, -128, 127)
+            clipped[c] = int(np.count_nonzero(y != v))
+            out[c] = y.astype(np.int8)
+            self.tail[c] = x[M:].astype(np.int8)
+        return out, clipped
+
+
+NOTCH_PLAN_DEFAULTS = dict(db=10.0, period=23, persist=2)   # msk144wb::NotchPlan: design parameters, not measurements
+NOTCH_PLAN_GUARD_BINS = 3
+
+
+def notch_design_refused(freqs, halfwidth_hz: int) -> bool:
+    """The rules of the default design (csrc/wideband.h check_notch_design)."""
+    f = [int(v) for v in freqs]
+    return (not 1 <= len(f) <= 2 or not 50 <= halfwidth_hz <= 500 or any(abs(v) + halfwidth_hz > OUT_RATE // 2 for v in f)
+            or (len(f) == 2 and abs(f[0] - f[1]) < 1000))
+
+
+class NotchPlanner:
+    """The host rule of msk144hipdecoder --wideband-notch=auto (csrc/wideband.h NotchPlanner), operation for operation: fed every
+    push's waterfall sums [channel][96], it adds them over `period` pushes; at the end of a period the highest bin j of a channel
+    that is not within 3 bins of one of its notches is hot when it lies at least `db` over the period's median bin; the same bin, +-1,
+    hot in `persist` consecutive periods adds a notch at rint(125 (j - 48 + d)) Hz, d the vertex of the parabola through 10 log10 of
+    bins j - 1, j, j + 1 clamped to +-0.5, if the channel has fewer than 2 and the spacing rule holds.  Notches are only ever added."""
+
+    def __init__(self, channels: int, db: float = 10.0, period: int = 23, persist: int = 2, halfwidth_hz: int = NOTCH_HALFWIDTH_HZ):
+        if not 1.0 <= db <= 100.0 or not 1 <= period <= 100000 or not 1 <= persist <= 1000:
+            raise ValueError("db must lie within 1..100, period within 1..100000, persist within 1..1000")
+        self.channels, self.db, self.period, self.persist, self.halfwidth = int(channels), float(db), int(period), int(persist), int(halfwidth_hz)
+        self.acc = np.zeros((self.channels, WATERFALL_BINS), dtype=np.float64)
+        self.pushes = 0
+        self.notches = [[] for _ in range(self.channels)]
+        self.state = [(-1, 0)] * self.channels     # (the hot bin of the last period, the periods in a row it has been hot)
+
+    @staticmethod
+    def vertex(a, j: int) -> float:
+        if j <= 0 or j >= WATERFALL_BINS - 1 or not a[j - 1] > 0.0 or not a[j + 1] > 0.0 or not a[j] > 0.0:
+            return 0.0
+        lm, l0, lp = (10.0 * math.log10(float(a[i])) for i in (j - 1, j, j + 1))
+        den = lm - 2.0 * l0 + lp
+        if not den < 0.0:
+            return 0.0
+        return min(max(0.5 * (lm - lp) / den, -0.5), 0.5)
+
+    def push(self, sums) -> list:
+        """[(channel, hz, excess_db)] added by this push, by channel."""
+        s = np.asarray(sums, dtype=np.float64).reshape(self.channels, WATERFALL_BINS)
+        self.acc += s
+        self.pushes += 1
+        if self.pushes < self.period:
+            return []
+        self.pushes = 0
+        out = []
+        for c in range(self.channels):
+            a = self.acc[c]
+            j = -1
+            for i in range(WATERFALL_BINS):
+                if any(abs(i - (round(f / 125.0) + WATERFALL_BINS // 2)) <= NOTCH_PLAN_GUARD_BINS for f in self.notches[c]):
+                    continue
+                if j < 0 or a[i] > a[j]:
+                    j = i
+            median = float(np.sort(a)[WATERFALL_BINS // 2])
+            excess = 10.0 * math.log10(float(a[j]) / median) if j >= 0 and median > 0.0 and a[j] > 0.0 else 0.0
+            if not (j >= 0 and median > 0.0 and excess >= self.db):
+                self.state[c] = (-1, 0)
+                continue
+            last, run = self.state[c]
+            run = run + 1 if last >= 0 and abs(j - last) <= 1 else 1
+            self.state[c] = (j, run)
+            if run < self.persist or len(self.notches[c]) >= 2:
+                continue
+            nxt = self.notches[c] + [int(round(125.0 * (j - WATERFALL_BINS // 2 + self.vertex(a, j))))]
+            if notch_design_refused(nxt, self.halfwidth):
+                continue
+            self.notches[c] = nxt
+            self.state[c] = (-1, 0)
+            out.append((c, nxt[-1], excess))
+        self.acc[:] = 0.0
+        return out
+
+
 class PingEvents:
     """The event rule of the contract: with g = (blocks of all earlier pushes) + b an event is a maximal run of consecutive up blocks
     of a channel.  A run that reaches a push's last block stays open into the next push; close() - the end of the stream - closes

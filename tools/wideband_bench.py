@@ -19,14 +19,17 @@ per-channel waterfall is on (msk144_set_wideband_waterfall, the default window),
 channeliser; waterfall_mfma is the f32 MFMA instructions of a push (576 per channel) and waterfall_bytes the rows it writes.
 --capture: the capture is on (msk144_set_wideband_capture with the defaults) with every 8th channel listed, up to the 16 the list
 holds, so that the units are non-trivial without a detector; the time includes its two kernels behind the hop ring, capture_units is
-the units of a push and capture_bytes what the copy kernel moves for them.
+the units of a push and capture_bytes what the copy kernel moves for them.  --notch N: the first N channels are notched
+(msk144_set_wideband_notch with the default design at +300 Hz), so the time includes the notch kernel behind the channeliser, one
+workgroup per notched channel; notch_dot4 is its int8 dot products of a push (N x 2592 x 99).  Every line of such a run is also
+appended to profiles/wideband_bench_notch.jsonl; run it with --notch 0 as well, on the same box, and compare the two.
 
 Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --program-rate, default 1.92 Msps, the program's
 default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
 samples at 12 kHz).
 
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
-                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--pings-band] [--waterfall] [--capture]
+                                   [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--pings-band] [--waterfall] [--capture] [--notch N]
 """
 from __future__ import annotations
 
@@ -50,7 +53,7 @@ FP32_PEAK_TFLOPS = 157.3   # MI355X, vector and f32-input MFMA (spec)
 
 
 def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blanker: bool = False, spectrum: int = 0, pings: bool = False, waterfall: bool = False,
-            capture: bool = False, pings_band: bool = False) -> dict:
+            capture: bool = False, pings_band: bool = False, notch: int = None) -> dict:
     D = rate // 12000
     rng = np.random.default_rng(C + D)
     g = math.gcd(rate, 12000)
@@ -69,6 +72,8 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
             d.set_wideband_pings()
         if pings_band:
             d.set_wideband_ping_band()
+        if notch:
+            d.set_wideband_notch({c: [300] for c in range(min(notch, C))})
         if waterfall:
             d.set_wideband_waterfall()
         listed = list(range(0, C, 8))[:wideband.CAPTURE_MAX_LISTED]
@@ -119,6 +124,9 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
     if pings or pings_band:
         ratio["pings"] = True
         ratio["pings_bytes"] = C * 2592 * 2   # every channel's int8 hop read once
+    if notch is not None:
+        ratio["notch_channels"] = min(notch, C)
+        ratio["notch_dot4"] = min(notch, C) * 2592 * 99   # 33 tap dwords x 3 sums per output
     if waterfall:
         ratio["waterfall"] = True
         ratio["waterfall_mfma"] = C * 576               # 3 waves x 96 steps x 2 per channel and hop
@@ -177,12 +185,20 @@ def main():
     ap.add_argument("--pings-band", action="store_true", help="measure with the ping detector and its in-band filter on")
     ap.add_argument("--waterfall", action="store_true", help="measure with the per-channel waterfall on")
     ap.add_argument("--capture", action="store_true", help="measure with the capture on, every 8th channel (up to 16) listed")
+    ap.add_argument("--notch", type=int, default=None, metavar="N", help="measure with the first N channels notched (0: none, for the comparison); appends to profiles/wideband_bench_notch.jsonl")
     a = ap.parse_args()
+    log = None
+    if a.notch is not None:
+        log = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wideband_bench_notch.jsonl"), "a")
     rates = [int(v) * 12000 for v in a.decimations.split(",") if v] + [int(v) for v in a.rates.split(",") if v]
     for C in [int(v) for v in a.channels.split(",")]:
         for rate in rates:
-            print(json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall, capture=a.capture,
-                                     pings_band=a.pings_band)), flush=True)
+            line = json.dumps(measure(C, rate, a.pushes, agc=a.agc, blanker=a.blanker, spectrum=a.spectrum, pings=a.pings, waterfall=a.waterfall, capture=a.capture,
+                                      pings_band=a.pings_band, notch=a.notch))
+            print(line, flush=True)
+            if log:
+                log.write(line + "\n")
+                log.flush()
     if a.program_hops:
         print(json.dumps(program_run(a.program_hops, rate=a.program_rate)), flush=True)
 
