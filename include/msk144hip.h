@@ -834,6 +834,53 @@ int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_
 /* units[max_units], data[max_units][5184], max_units as last set: the last push, made since then */
 int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* units, int8_t* data /*[max_units][5184]*/, int32_t* count, int32_t* total);
 
+/* ---- The gate: only the channels with activity are decoded (no reference counterpart) ----
+ *
+ * A meteor-scatter channel is noise for minutes and carries a ping for a fraction of a second, yet every channel's window goes
+ * through scan, softbits and LDPC on every push.  With the gate on, the ping detector's up masks pick the channels whose window is
+ * decoded, on the device; the decode then runs on those alone.  The channeliser, AGC, notch, ping detector, waterfall, hop ring,
+ * capture and the IQ front end run for every channel as without it, so levels, ping records, captures and the eight segment
+ * powers of every channel are those of an ungated push.  The detector is less sensitive than the decoder: a ping
+ * the detector does not see is not decoded.  An opt-in extra; with the gate off every byte is what it is without this entry.
+ *
+ *   Rule:       per channel `since`, the hops since the last active one, saturating at 17.  A push carries one hop (up_mask bits
+ *               0..26), a first push hops 0 and 1 (bits 0..26 and 27..53), walked in that order.  A hop is active iff at least
+ *               min_up of its 27 blocks are up; since = active ? 0 : min(since + 1, 17).  After the walk the channel's window is
+ *               decoded iff always[c] or since <= hold.  A first push, and the first push after msk144_set_wideband_gate, start
+ *               from since = 17.  up_mask is 0 while the detector is off: then only the `always` channels are decoded.  The window
+ *               of push k covers hops k - 1 and k, so with hold >= 1 every window that contains an active hop is decoded, and no
+ *               window is decoded because of activity more than `hold` hops old; hold = 0 decodes only windows whose newest hop is
+ *               active.  csrc/wideband.h gate_step is the rule for device and host.
+ *   Parameters: 0 <= hold <= 16 hops (default 1), 1 <= min_up <= 27 blocks (default 1), 1 <= max_channels <= channels or 0 = all,
+ *               and an `always` flag per channel, any subset.  The defaults are design parameters, not measurements.
+ *   Order:      the qualifying channels in ascending order.  Of `total` the first min(total, max_channels) are listed and decoded,
+ *               the rest dropped and only counted; `since` moves the same for every channel either way.  On the stream: the plan
+ *               behind the ping detector, its header and list to pinned memory, an event; then the hop ring, the capture and the
+ *               front end; then the gather of the listed channels' analytic windows into a store of the gate's own.
+ *               msk144_set_wideband_gate(h, &p, always) takes effect from the next push and allocates everything - a push
+ *               allocates nothing; (h, NULL, NULL) switches the gate off, as msk144_set_wideband does.
+ *   Decode:     msk144_decode_stages on a push made with the gate on waits for that event - the one host wait the gate adds: the
+ *               decode's launches are sized by the count, and the hot kernels are given neither an indirection nor an early exit -
+ *               and runs scan .. collect on `count` channels.  count = 0 launches nothing and leaves 0 records.  A record's channel
+ *               is the position j in the list, as after msk144_push_hops; msk144_copy_count and the dumps are by position too.
+ *               msk144_fetch_wait returns seg_power[channels][8] by channel, for all channels.
+ *   Output:     msk144_wideband_gate reports the last push: channels_out[0 .. *count) the listed channels, *total all that
+ *               qualified.  It waits for the gate's event only, not for the stream.
+ *   Refused:    MSK144_EINVAL outside wideband mode and for parameters out of range (a refused call changes nothing);
+ *               MSK144_ESTATE from msk144_wideband_gate before a push made with the gate on, and between an accepted
+ *               msk144_set_wideband_gate and the next such push. */
+typedef struct msk144_wideband_gate_params
+{
+    int32_t hold;          /* hops a channel stays in after its last active one (1) */
+    int32_t min_up;        /* up blocks that make a hop active (1) */
+    int32_t max_channels;  /* channels decoded per push; 0: all */
+} msk144_wideband_gate_params;
+
+/* params NULL: off.  always[channels], nonzero = decoded on every push, or NULL: none */
+int msk144_set_wideband_gate(msk144_handle* h, const msk144_wideband_gate_params* params, const uint8_t* always);
+/* channels_out[max_channels as last set; channels when 0]: the last push, made since then */
+int msk144_wideband_gate(msk144_handle* h, int32_t* channels_out, int32_t* count, int32_t* total);
+
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
 int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);

@@ -35,6 +35,7 @@ SOURCES = [
     ("capture.hip", []),
     ("pingband.hip", []),
     ("notch.hip", []),
+    ("gate.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("msk144_wideband_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
 ]

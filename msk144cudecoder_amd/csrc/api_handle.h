@@ -178,6 +178,20 @@ struct Wideband
         msk144wb::CaptureUnit* d_units = nullptr;     // [rows]
         uint8_t* d_data = nullptr;                    // [rows][5184]
     } capture;
+    // the gate (msk144_set_wideband_gate).  pushed: the last push left a header and no `set` has come since.  `planned` is recorded
+    // behind the copy of the header to `header`: what msk144_decode_stages and msk144_wideband_gate wait for, not the stream
+    struct Gate
+    {
+        bool on = false, pushed = false, restart = false;
+        msk144wb::GateParams params;
+        uint8_t* d_always = nullptr;                // [channels]
+        int32_t* d_since = nullptr;                 // [channels]
+        msk144wb::GateHeader* d_header = nullptr;   // [1]
+        int32_t* d_list = nullptr;                  // [channels]
+        float2* d_analytic = nullptr;               // [channels][5184]: row j is the window of channel list[j]
+        msk144wb::GateHeader* header = nullptr;     // pinned: the header, and behind it the list, int32 [channels]
+        hipEvent_t planned = nullptr;
+    } gate;
 };
 
 struct msk144_handle
@@ -203,6 +217,8 @@ struct msk144_handle
     int active = 1;     // channels the current hop covers (msk144_submit_slot_n: the first n of the slot); <= st.channels
     bool have_window = false;
     bool decoded = false;
+    bool gated = false;  // the current hop is a wideband push made with the gate on (Wideband::Gate): the decode covers the listed channels ...
+    int gated_n = 0;     // ... this many, which the last decode read from the gate's header
     bool profiling = false;
     // HIP-event pairs recorded around each stage; a pool so that many steps can be in flight
     // before the times are harvested at the next synchronisation point

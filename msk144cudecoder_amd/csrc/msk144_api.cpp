@@ -227,6 +227,7 @@ int begin_hop(msk144_handle* h, int32_t slot, int32_t n)
     h->call_id++;
     h->cur_slot = slot;
     h->active = n;
+    h->gated = false;
     return MSK144_OK;
 }
 
@@ -469,6 +470,7 @@ int msk144_submit_analytic(msk144_handle* h, const float* windows)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->cur_slot = 0;
     h->active = h->st.channels;
+    h->gated = false;
     h->have_window = true;
     h->decoded = false;
     return MSK144_OK;
@@ -485,7 +487,26 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
     HIP_TRY(h, hipSetDevice(h->params.device));
     h->call_id++;
     if(h->profiling) harvest_finished(h);
-    const DeviceStore cur = active_store(h);
+    DeviceStore cur = active_store(h);
+    if(h->gated)
+    {
+        // The one host wait the gate adds (include/msk144hip.h): the launches below are sized by the number of listed channels, and
+        // the hot kernels are given neither an indirection nor an early exit.  It waits for the plan's event, not for the stream
+        const auto& g = h->wb.gate;
+        HIP_TRY(h, hipEventSynchronize(g.planned));
+        const int n = g.header->count;
+        if(n < 0 || n > h->st.channels) return fail(h, MSK144_EHIP, "msk144_decode_stages: the device left a gate header out of range");
+        h->gated_n = n;
+        if(n == 0)
+        {
+            // nothing to decode: no launch (a grid of 0 workgroups is an error), and a record list of 0
+            if(stages & MSK144_STAGE_COLLECT) HIP_TRY(h, hipMemsetAsync(h->st.result_count, 0, sizeof(int32_t), h->stream));
+            h->decoded = true;
+            return MSK144_OK;
+        }
+        cur.channels = cur.nch = n;
+        cur.analytic = g.d_analytic;
+    }
     if(stages & MSK144_STAGE_SCAN)
     {
         ev_begin(h);
@@ -628,7 +649,7 @@ int msk144_copy_count(msk144_handle* h, int64_t* slots)
     if(!h->decoded) return fail(h, MSK144_ESTATE, "no decode has been run");
     int rc = msk144_synchronize(h);
     if(rc != MSK144_OK) return rc;
-    std::vector<int32_t> per_channel(static_cast<size_t>(h->active));
+    std::vector<int32_t> per_channel(static_cast<size_t>(h->gated ? h->gated_n : h->active));
     HIP_TRY(h, hipMemcpy(per_channel.data(), h->st.copy_count, sizeof(int32_t) * per_channel.size(), hipMemcpyDeviceToHost));
     int64_t total = 0;
     for(int32_t c : per_channel) total += c;
@@ -767,7 +788,7 @@ int msk144_dump_analytic(msk144_handle* h, int32_t channel, float* out)
     if(!h || !out || channel < 0 || channel >= h->st.channels) return fail(h, MSK144_EINVAL, "bad argument");
     int rc = msk144_synchronize(h);
     if(rc != MSK144_OK) return rc;
-    HIP_TRY(h, hipMemcpy(out, h->st.analytic + static_cast<size_t>(channel) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out, (h->gated ? h->wb.gate.d_analytic : h->st.analytic) + static_cast<size_t>(channel) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
     return MSK144_OK;
 }
 

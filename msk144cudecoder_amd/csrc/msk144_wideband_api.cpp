@@ -12,6 +12,10 @@ using namespace msk144;
 
 void wb_release(msk144_handle* h)
 {
+    // the gate's event and store go with the configuration: a window pushed through them can no longer be decoded
+    if(h->wb.gate.planned) (void)hipEventDestroy(h->wb.gate.planned);
+    if(h->gated) h->have_window = false;
+    h->gated = false;
     h->wb.mem.release();
     h->wb = {};
 }
@@ -348,6 +352,40 @@ int wb_capture(msk144_handle* h, const WbPush& p)
     return MSK144_OK;
 }
 
+// The gate's plan, behind the ping detector: the list of the channels whose window this push decodes, its header to the pinned
+// copy, and the event the decode waits for.  The ring, the capture and the front end follow it on the stream
+int wb_gate_plan(msk144_handle* h, const WbPush& p)
+{
+    auto& g = h->wb.gate;
+    g.pushed = g.on;
+    if(!g.on) return MSK144_OK;
+    const int C = h->wb.channels;
+    ev_begin(h);
+    launch_gate_plan(h->wb.pings.on ? h->wb.pings.d_records : nullptr, g.d_always, g.d_since, C, p.first ? 1 : 0, p.first || g.restart ? 1 : 0, g.params,
+                     (h->wb.core.m_next + p.M) / kHopSamples - 1, g.d_header, g.d_list, h->stream);
+    ev_end(h, MSK144_T_FRONTEND);
+    g.restart = false;
+    HIP_TRY(h, hipGetLastError());
+    // header and list in one pinned block: a quiet band reads 16 bytes of it, a busy one the listed channels behind them
+    HIP_TRY(h, hipMemcpyAsync(g.header, g.d_header, sizeof(msk144wb::GateHeader), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(g.header + 1, g.d_list, sizeof(int32_t) * static_cast<size_t>(C), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipEventRecord(g.planned, h->stream));
+    return MSK144_OK;
+}
+
+// ... and its gather, behind the IQ front end: the listed channels' analytic windows, densely, for the decode
+int wb_gate_gather(msk144_handle* h)
+{
+    auto& g = h->wb.gate;
+    h->gated = g.on;
+    if(!g.on) return MSK144_OK;
+    ev_begin(h);
+    launch_gate_gather(h->st.analytic, g.d_header, g.d_list, h->wb.channels, g.d_analytic, h->stream);
+    ev_end(h, MSK144_T_FRONTEND);
+    HIP_TRY(h, hipGetLastError());
+    return MSK144_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -429,6 +467,7 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     wb_launch_observers(h, p);
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
+    if((rc = wb_gate_plan(h, p)) != MSK144_OK) return rc;
     w.agc.push_gains = w.agc.gains;
     w.agc.pushed = w.agc.on;
     w.core.m_next += p.M;
@@ -437,7 +476,8 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     w.last = p;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, w.channels, h->stream);
     if((rc = wb_capture(h, p)) != MSK144_OK) return rc;
-    return run_frontend(h, h->d_input);
+    if((rc = run_frontend(h, h->d_input)) != MSK144_OK) return rc;
+    return wb_gate_gather(h);
 }
 
 int msk144_dump_wideband_hop(msk144_handle* h, int32_t channel, int8_t* out)
@@ -833,6 +873,59 @@ int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* unit
         HIP_TRY(h, hipMemcpy(units, c.d_units, sizeof(msk144wb::CaptureUnit) * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
         HIP_TRY(h, hipMemcpy(data, c.d_data, static_cast<size_t>(msk144wb::kCaptureUnitBytes) * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
     }
+    *count = head.count;
+    *total = head.total;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_gate(msk144_handle* h, const msk144_wideband_gate_params* p, const uint8_t* always)
+{
+    if(const int rc = wb_quiesce(h, "msk144_set_wideband_gate"); rc != MSK144_OK) return rc;
+    auto& w = h->wb;
+    auto& g = w.gate;
+    if(!p)
+    {
+        g.on = g.pushed = false;
+        return MSK144_OK;
+    }
+    const msk144wb::GateParams gp{p->hold, p->min_up, p->max_channels};
+    const size_t C = static_cast<size_t>(w.channels);
+    if(const std::string why = msk144wb::check_gate(gp, w.channels); !why.empty()) return fail(h, MSK144_EINVAL, why);
+    // an accepted `set` ends the last push's list: the read entry answers MSK144_ESTATE until the next push made with the gate on
+    g.on = g.pushed = false;
+    if(wb_ensure(h, &g.d_always, C) || wb_ensure(h, &g.d_since, C) || wb_ensure(h, &g.d_header, 1) || wb_ensure(h, &g.d_list, C) || wb_ensure(h, &g.d_analytic, C * kWindowSamples))
+        return MSK144_ENOMEM;
+    if(!g.header)
+    {
+        // the pinned header with the list behind it: 16 bytes are four int32
+        int32_t* block = nullptr;
+        if(const int rc = host_alloc(h, w.mem, &block, sizeof(msk144wb::GateHeader) / sizeof(int32_t) + C); rc != MSK144_OK) return rc;
+        g.header = reinterpret_cast<msk144wb::GateHeader*>(block);
+    }
+    if(!g.planned) HIP_TRY(h, hipEventCreateWithFlags(&g.planned, hipEventBlockingSync | hipEventDisableTiming));
+    std::vector<uint8_t> flags(C, 0);
+    for(size_t c = 0; always && c < C; c++) flags[c] = always[c] != 0;
+    HIP_TRY(h, hipMemcpy(g.d_always, flags.data(), C, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(g.d_since, 0, sizeof(int32_t) * C));
+    g.params = gp;
+    g.on = true;
+    g.restart = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_gate(msk144_handle* h, int32_t* channels_out, int32_t* count, int32_t* total)
+{
+    if(!h || !channels_out || !count || !total) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& w = h->wb;
+    const auto& g = w.gate;
+    // as wb_read_ready, but it waits for the gate's event alone: the list is ready long before the push's front end is
+    if(!w.configured) return fail(h, MSK144_EINVAL, "msk144_wideband_gate needs wideband mode (msk144_set_wideband)");
+    if(!w.started || !g.pushed) return fail(h, MSK144_ESTATE, w.started ? "no wideband push has been made with the gate on since it was last set" : "no wideband push has been made");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    HIP_TRY(h, hipEventSynchronize(g.planned));
+    const msk144wb::GateHeader head = *g.header;
+    if(head.count < 0 || head.count > w.channels) return fail(h, MSK144_EHIP, "msk144_wideband_gate: the device left a header out of range");
+    std::memcpy(channels_out, g.header + 1, sizeof(int32_t) * static_cast<size_t>(head.count));
     *count = head.count;
     *total = head.total;
     return MSK144_OK;

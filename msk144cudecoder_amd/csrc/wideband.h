@@ -927,6 +927,93 @@ private:
     int64_t segments_ = 0, hops_ = 0;
 };
 
+// ---- the gate: only the channels with activity are decoded (msk144_set_wideband_gate, msk144_wideband_gate) ----
+
+constexpr int kGateMaxHold = 16;
+constexpr int kGateQuiet = kGateMaxHold + 1;   // `since` saturates here: no activity that any `hold` still reaches
+constexpr int kGateHopBlocks = kCaptureHopBlocks;
+
+// msk144_wideband_gate_params, field for field.  The defaults are design parameters, not measurements.
+struct GateParams
+{
+    int32_t hold = 1, min_up = 1, max_channels = 0;   // max_channels 0: every channel
+};
+
+// what a push leaves in front of the list: the listed channels, all channels that qualified, and the newest hop of the push
+struct GateHeader
+{
+    int32_t count, total;
+    int64_t hop;
+};
+static_assert(sizeof(GateHeader) == 16, "the gate header is 16 bytes");
+
+// The gate rule, once, for one channel and one push.  `since`: hops since the channel's last active one, saturating at kGateQuiet.
+// `first`: the push carries hops 0 and 1 (up_mask bits 0..26 and 27..53), walked in that order, else the newest hop alone (bits
+// 0..26); up_mask is 0 when the detector was off.  `clear`: a first push, or the first push after msk144_set_wideband_gate: earlier
+// activity counts as none.  A hop is active iff at least min_up of its 27 blocks are up.  Returns whether the channel's window of
+// this push is decoded: always, or since <= hold after the walk.
+//   The window of push k covers hops k - 1 and k.  With hold >= 1 every window that contains an active hop is decoded: an active
+//   hop k gives since = 0 in push k and since <= 1 in push k + 1.  No window is decoded because of activity more than `hold` hops
+//   old.  hold = 0 decodes only the windows whose newest hop is active.
+MSK144WB_HD inline bool gate_step(int32_t& since, bool first, bool clear, uint64_t up_mask, bool always, int32_t hold, int32_t min_up)
+{
+    int32_t s = clear ? kGateQuiet : since;
+    for(int i = first ? 0 : 1; i < 2; i++)
+    {
+        const uint64_t bits = (up_mask >> (first ? kGateHopBlocks * i : 0)) & ((1ull << kGateHopBlocks) - 1);
+        int32_t up = 0;
+        for(uint64_t b = bits; b; b &= b - 1) up++;
+        s = up >= min_up ? 0 : s < kGateQuiet ? s + 1 : kGateQuiet;
+    }
+    since = s;
+    return always || s <= hold;
+}
+
+// max_channels as the rule uses it: 0 stands for every channel
+inline int32_t gate_max_channels(const GateParams& p, int channels) { return p.max_channels ? p.max_channels : channels; }
+
+// The rules of msk144_set_wideband_gate.  Empty string = valid.
+inline std::string check_gate(const GateParams& p, int channels)
+{
+    if(p.hold < 0 || p.hold > kGateMaxHold) return "gate hold must lie within 0..16 hops";
+    if(p.min_up < 1 || p.min_up > kGateHopBlocks) return "gate min_up must lie within 1..27 blocks";
+    if(p.max_channels < 0 || p.max_channels > channels) return "gate max_channels must lie within 1.." + std::to_string(channels) + ", or be 0 for all";
+    return std::string();
+}
+
+// The rule over all channels of a stream on the host: what the plan kernel computes, and through libmsk144host.so the yardstick of
+// wideband.Gate.  Channels come in ascending order; the first max_channels that qualify are listed, the rest only counted - the
+// state moves the same either way.
+class Gate
+{
+public:
+    Gate(int channels, const GateParams& p, const uint8_t* always) : p_(p), since_(static_cast<size_t>(channels), kGateQuiet), always_(static_cast<size_t>(channels), 0)
+    {
+        for(int c = 0; always && c < channels; c++) always_[static_cast<size_t>(c)] = always[c] != 0;
+    }
+
+    // as msk144_set_wideband_gate in mid-stream: the state cleared
+    void restart() { clear_ = true; }
+
+    // records[channels] of one push, or nullptr: the detector was off.  Appends the listed channels and returns the total.
+    int32_t push(const PingRecord* records, bool first, std::vector<int32_t>& out)
+    {
+        const int32_t cap = gate_max_channels(p_, static_cast<int>(since_.size()));
+        int32_t total = 0;
+        for(size_t c = 0; c < since_.size(); c++)
+            if(gate_step(since_[c], first, first || clear_, records ? records[c].up_mask : 0, always_[c] != 0, p_.hold, p_.min_up) && total++ < cap)
+                out.push_back(static_cast<int32_t>(c));
+        clear_ = false;
+        return total;
+    }
+
+private:
+    GateParams p_;
+    std::vector<int32_t> since_;
+    std::vector<uint8_t> always_;
+    bool clear_ = true;
+};
+
 // ---- the notch: steady carriers taken out of a channel's stored samples (msk144_set_wideband_notch, msk144_wideband_notch_stats) ----
 
 constexpr int kNotchTaps = 64;

@@ -92,6 +92,11 @@ class WidebandCaptureUnit(C.Structure):
     _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("hop", C.c_int64)]
 
 
+class WidebandGateParams(C.Structure):
+    """msk144_wideband_gate_params."""
+    _fields_ = [("hold", C.c_int32), ("min_up", C.c_int32), ("max_channels", C.c_int32)]
+
+
 assert C.sizeof(WidebandPing) == PING_DTYPE.itemsize == 32
 assert C.sizeof(WidebandCaptureUnit) == CAPTURE_DTYPE.itemsize == 16
 
@@ -178,6 +183,8 @@ PROTOTYPES = {
     "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
     "msk144_set_wideband_capture": ([_vp, _P(WidebandCaptureParams)], C.c_int),
     "msk144_wideband_capture": ([_vp, _P(WidebandCaptureUnit), _P(C.c_int8), _P(_i32), _P(_i32)], C.c_int),
+    "msk144_set_wideband_gate": ([_vp, _P(WidebandGateParams), _P(C.c_uint8)], C.c_int),
+    "msk144_wideband_gate": ([_vp, _P(_i32), _P(_i32), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -671,6 +678,30 @@ class HipDecoder:
         self._chk(self.L.msk144_wideband_capture(self.h, units.ctypes.data_as(C.POINTER(WidebandCaptureUnit)), data.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(count),
                                                  C.byref(total)))
         return units[:count.value].copy(), data[:count.value].copy(), total.value
+
+    def set_wideband_gate(self, hold=1, min_up=1, max_channels=None, always=()):
+        """The gate from the next push on (include/msk144hip.h): a channel's window is decoded while the channel had a hop with at
+        least `min_up` up blocks within the last `hold` hops, or is one of the `always` channels; at most `max_channels` per push
+        (None: all).  set_wideband_gate(None) switches it off.  Either ends the last push's list: wideband_gate() raises
+        (MSK144_ESTATE) until the next push made with the gate on.  Records of a gated decode carry list positions as channel."""
+        if hold is None:
+            self._chk(self.L.msk144_set_wideband_gate(self.h, None, None))
+            return
+        flags = np.zeros(self.channels, dtype=np.uint8)
+        for c in always:
+            if not 0 <= int(c) < self.channels:
+                raise ValueError(f"always channel {c} is out of range")
+            flags[int(c)] = 1
+        p = WidebandGateParams(int(hold), int(min_up), 0 if max_channels is None else int(max_channels))
+        self._chk(self.L.msk144_set_wideband_gate(self.h, C.byref(p), flags.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def wideband_gate(self):
+        """(list, total) of the last push: the int32 channels whose window it decodes, ascending - position j of the list is what
+        the decode's records carry as channel - and the number of channels that qualified, of which total - len(list) were dropped."""
+        out = np.zeros(self.channels, dtype=np.int32)
+        count, total = C.c_int32(), C.c_int32()
+        self._chk(self.L.msk144_wideband_gate(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(count), C.byref(total)))
+        return out[:count.value].copy(), total.value
 
     # ---- parity / debug ----
     def dump_analytic(self, channel=0) -> np.ndarray:

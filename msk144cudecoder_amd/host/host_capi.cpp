@@ -402,6 +402,42 @@ void msk144host_wideband_capture_segments_locate(void* s, int channel, int64_t b
     out[95] = 0;
 }
 
+// "[HOLD[:MIN_UP[:MAX[:ALWAYS]]]]" as the program parses it (NULL: the bare option): out[0] = hold, out[1] = min_up, out[2] = max
+// channels, out[3] = always channels, then the first cap - 4 of them; -1: refused
+int msk144host_wideband_gate_parse(const char* arg, int32_t* out, int cap)
+{
+    WidebandOptions w;
+    if(!parse_wideband_gate(arg, w)) return -1;
+    out[0] = w.gate_params.hold, out[1] = w.gate_params.min_up, out[2] = w.gate_params.max_channels, out[3] = static_cast<int32_t>(w.gate_always.size());
+    for(size_t i = 0; i < w.gate_always.size() && 4 + i < static_cast<size_t>(cap); i++) out[4 + i] = w.gate_always[i];
+    return 0;
+}
+// the gate rule: nullptr for parameters msk144_set_wideband_gate refuses; always[channels] or NULL
+void* msk144host_wideband_gate_new(int channels, int hold, int min_up, int max_channels, const uint8_t* always)
+{
+    const msk144wb::GateParams p{hold, min_up, max_channels};
+    if(channels < 1 || !msk144wb::check_gate(p, channels).empty()) return nullptr;
+    return new msk144wb::Gate(channels, p, always);
+}
+void msk144host_wideband_gate_free(void* s) { delete static_cast<msk144wb::Gate*>(s); }
+void msk144host_wideband_gate_restart(void* s) { static_cast<msk144wb::Gate*>(s)->restart(); }
+// records[channels] or NULL (the detector off): writes at most cap channels, *count = the listed ones, and returns the total
+int msk144host_wideband_gate_push(void* s, const msk144wb::PingRecord* records, int first, int32_t* out, int cap, int32_t* count)
+{
+    std::vector<int32_t> list;
+    const int32_t total = static_cast<msk144wb::Gate*>(s)->push(records, first != 0, list);
+    for(int i = 0; i < static_cast<int>(list.size()) && i < cap; i++) out[i] = list[static_cast<size_t>(i)];
+    *count = static_cast<int32_t>(list.size());
+    return total;
+}
+// out: at least 128 bytes; the text msk144_set_wideband_gate refuses the parameters with, empty when it takes them
+void msk144host_wideband_gate_check(int channels, int hold, int min_up, int max_channels, char* out)
+{
+    const std::string why = msk144wb::check_gate(msk144wb::GateParams{hold, min_up, max_channels}, channels);
+    std::strncpy(out, why.c_str(), 127);
+    out[127] = 0;
+}
+
 void* msk144host_table_new(){ return new CallHashTable(); }
 void msk144host_table_free(void* t) { delete static_cast<CallHashTable*>(t); }
 void msk144host_table_clear(void* t) { static_cast<CallHashTable*>(t)->clear(); }

@@ -251,7 +251,7 @@ bool DeviceLoop::submit_wideband(Batch& b)
         s.ready = false;
     }
     const auto a1 = Clock::now();
-    if(!dec_.submit_wideband(b.slot, first, wb_->api().push))
+    if(!dec_.submit_wideband(b.slot, first, wb_->api().push, wb_->api().gate))
     {
         fail(dec_.error());
         return false;

@@ -57,6 +57,9 @@ struct WidebandOptions
     msk144wb::NotchPlan notch_plan;
     int notch_halfwidth = msk144wb::kNotchDefaultHalfwidthHz;
     std::vector<std::pair<int32_t, std::vector<int32_t>>> notch_table;  // ... or ch:Hz[+Hz],...: (channel, its frequencies from the channel's offset)
+    bool gate = false;            // --wideband-gate[=HOLD[:MIN_UP[:MAX[:ALWAYS]]]]: only the channels with activity are decoded
+    msk144wb::GateParams gate_params;          // max_channels 0: every channel
+    std::vector<int32_t> gate_always;          // channel indices decoded on every push
     std::vector<int32_t> offsets;
     bool any_option = false;  // some wideband option was given (they all need --wideband-rate)
     int offset_sources = 0;   // --channel-offsets and --channel-grid given (exactly one is needed)
@@ -96,6 +99,9 @@ struct WidebandApi
     // --wideband-capture
     int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
     int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
+    // --wideband-gate
+    int (*set_gate)(msk144_handle*, const msk144_wideband_gate_params*, const uint8_t*) = nullptr;
+    int (*gate)(msk144_handle*, int32_t*, int32_t*, int32_t*) = nullptr;
 
     // Resolves the channeliser's entries and those of every option of `w`, group after group; false with the first group that lacks
     // one: "the loaded libmsk144hip has no <feature> (<first missing symbol>)[: <who> need(s) it]".
@@ -125,6 +131,7 @@ struct WidebandApi
             {w.notch, "notch", ": --wideband-notch needs it", {{"msk144_set_wideband_notch", &set_notch}, {"msk144_wideband_notch_stats", &notch_stats}}},
             {w.notch && w.notch_auto, "waterfall", ": --wideband-notch=auto needs it", {{"msk144_set_wideband_waterfall", &set_waterfall}, {"msk144_wideband_waterfall_sums", &waterfall_sums}}},
             {w.capture, "capture", ": --wideband-capture needs it", {{"msk144_set_wideband_capture", &set_capture}, {"msk144_wideband_capture", &capture}}},
+            {w.gate, "gate", ": --wideband-gate needs it", {{"msk144_set_wideband_gate", &set_gate}, {"msk144_wideband_gate", &gate}}},
         };
         for(const Group& g : groups)
         {
@@ -362,6 +369,23 @@ inline bool parse_wideband_notch(const std::string& s, WidebandOptions& w)
     return true;
 }
 
+// "[HOLD[:MIN_UP[:MAX[:ALWAYS]]]]": HOLD 0..16 hops, MIN_UP 1..27 blocks, MAX channels decoded per push (0: all), ALWAYS different
+// channel indices c0,c1,... decoded on every push; an empty field keeps its default.  NULL (the bare option): the defaults.
+// (Whether MAX and the channels fit, and whether there is a detector to follow, needs the other options: check_wideband_options.)
+inline bool parse_wideband_gate(const char* arg, WidebandOptions& w)
+{
+    w.gate = true;
+    w.gate_params = msk144wb::GateParams();
+    w.gate_always.clear();
+    if(!arg) return true;
+    const std::vector<std::string> f = split_fields(arg, ':');
+    if(f.size() > 4) return false;
+    if(!f[0].empty() && !parse_int_in(f[0], 0, msk144wb::kGateMaxHold, w.gate_params.hold)) return false;
+    if(f.size() > 1 && !f[1].empty() && !parse_int_in(f[1], 1, msk144wb::kGateHopBlocks, w.gate_params.min_up)) return false;
+    if(f.size() > 2 && !f[2].empty() && !parse_int_in(f[2], 0, INT32_MAX, w.gate_params.max_channels)) return false;
+    return f.size() < 4 || f[3].empty() || parse_channel_list(f[3], INT32_MAX - 1, w.gate_always);
+}
+
 inline bool parse_wideband_format(const std::string& s, int& fmt)
 {
     if(s == "cu8") fmt = msk144wb::kCu8;
@@ -420,6 +444,7 @@ inline bool take_wideband_option(const std::string& name, const char* arg, Wideb
     else if(name == "wideband-capture") good = parse_wideband_capture(value, w);
     else if(name == "wideband-pings-band") w.ping_band = true, w.ping_band_arg = value;
     else if(name == "wideband-notch") good = parse_wideband_notch(value, w);
+    else if(name == "wideband-gate") good = parse_wideband_gate(arg, w);
     else return false;
     w.any_option = true;
     if(!good && w.parse_error.empty()) w.parse_error = "bad value for --" + name + ": '" + value + "'";
@@ -434,7 +459,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     {
         const std::pair<bool, const char*> own_line[] = {{w.blanker, "--wideband-blanker"},      {w.spectrum, "--wideband-spectrum"},   {w.pings, "--wideband-pings"},
                                                          {w.ping_band, "--wideband-pings-band"}, {w.waterfall, "--wideband-waterfall"}, {w.capture, "--wideband-capture"},
-                                                         {w.notch, "--wideband-notch"}};
+                                                         {w.notch, "--wideband-notch"},          {w.gate, "--wideband-gate"}};
         for(const auto& o : own_line)
             if(o.first) return std::string(o.second) + " needs --wideband-rate=HZ";
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
@@ -461,6 +486,15 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     for(const auto& e : w.notch_table)
         if(static_cast<size_t>(e.first) >= w.offsets.size())
             return "--wideband-notch: channel " + std::to_string(e.first) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
+    if(w.gate)
+    {
+        if(!w.pings && w.gate_always.empty()) return "--wideband-gate needs --wideband-pings=FILE, or a list of channels that are always decoded (HOLD:MIN_UP:MAX:c0,c1,...)";
+        const std::string bad = msk144wb::check_gate(w.gate_params, static_cast<int>(w.offsets.size()));
+        if(!bad.empty()) return "--wideband-gate: " + bad;
+        for(int32_t c : w.gate_always)
+            if(static_cast<size_t>(c) >= w.offsets.size())
+                return "--wideband-gate: channel " + std::to_string(c) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
+    }
     return "";
 }
 

@@ -41,7 +41,8 @@ public:
     void pushed(bool first) { pending_components_ = 2ll * channels() * (first ? MSK144_WINDOW_SAMPLES : MSK144_HOP_SAMPLES); }
     // Reads what the last push left, if one is unread, into the state blocks and the files: the clip count (which waits for the
     // push's kernels), levels, spectrum, then the ping records with - behind them, for the events they close - the waterfall rows and
-    // the capture units, last the notch counts and, with auto, the planner's step and the new table for the next push.  false: error() says why.
+    // the capture units, then the notch counts and, with auto, the planner's step and the new table for the next push, last the gate's
+    // counts.  false: error() says why.
     bool read_push(msk144_handle* h);
     // The end of the stream: the last, shorter spectrum group, the ping events still open, the open capture segments.  false: error().
     bool finish();
@@ -60,6 +61,7 @@ private:
     bool read_waterfall(msk144_handle* h);
     bool read_capture(msk144_handle* h);
     bool read_notch(msk144_handle* h);
+    bool read_gate(msk144_handle* h);
     bool set_notch_table(msk144_handle* h);
     bool write_ping_events();
     void write_spectrum_line();
@@ -123,6 +125,12 @@ private:
         long long pushes = 0, clamped = 0;                // pushes read, components clamped over the run
         bool set = false;                                 // the library holds a table: the last push was made with it
     } notch_;
+    struct Gate  // --wideband-gate: the channel windows the decode covered, over the run
+    {
+        std::vector<int32_t> list;                        // [channels] of the last push
+        long long decoded = 0, windows = 0, dropped = 0;  // listed channels, channels x pushes, qualified but over the budget
+        int busiest = 0;                                  // the largest list of a push
+    } gate_;
 };
 
 }  // namespace msk144host

@@ -106,6 +106,7 @@ inline bool WidebandRun::prepare()
         if(opt_.notch_auto) notch_.planner.reset(new msk144wb::NotchPlanner(static_cast<int>(C), opt_.notch_plan, opt_.notch_halfwidth));
         if(opt_.notch_auto && !opt_.waterfall) notch_.sums.assign(C * msk144wb::kWaterfallBins, 0.0);
     }
+    if(opt_.gate) gate_.list.resize(C);
     if(opt_.capture)
     {
         capture_.segments.reset(new msk144wb::CaptureSegments(opt_.capture_dir, opt_.offsets));
@@ -189,6 +190,13 @@ inline bool WidebandRun::configure(msk144_handle* h)
         if(api_.set_capture(h, &cp) != MSK144_OK) return set_failed(h);
     }
     if(opt_.notch && !opt_.notch_auto && !set_notch_table(h)) return false;
+    if(opt_.gate)
+    {
+        const msk144_wideband_gate_params gp{opt_.gate_params.hold, opt_.gate_params.min_up, opt_.gate_params.max_channels};
+        std::vector<uint8_t> always(opt_.offsets.size(), 0);
+        for(int32_t c : opt_.gate_always) always[static_cast<size_t>(c)] = 1;
+        if(api_.set_gate(h, &gp, always.data()) != MSK144_OK) return set_failed(h);
+    }
     if(opt_.blanker)
     {
         const msk144_wideband_blanker bl{opt_.blanker_params.threshold_q4, opt_.blanker_params.pre, opt_.blanker_params.post};
@@ -212,7 +220,7 @@ inline bool WidebandRun::read_push(msk144_handle* h)
         pending_components_ = 0;
     }
     ok = ok && (!opt_.levels || read_levels(h)) && (!opt_.spectrum || read_spectrum(h)) && (!opt_.pings || read_pings(h)) && (!opt_.waterfall || read_waterfall(h)) &&
-         (!opt_.capture || read_capture(h)) && (!opt_.pings || write_ping_events()) && (!opt_.notch || read_notch(h));
+         (!opt_.capture || read_capture(h)) && (!opt_.pings || write_ping_events()) && (!opt_.notch || read_notch(h)) && (!opt_.gate || read_gate(h));
     if(!ok && error_.empty()) error_ = msk144_last_error(h);
     return ok;
 }
@@ -425,6 +433,18 @@ inline bool WidebandRun::read_notch(msk144_handle* h)
     return false;
 }
 
+// the gate's list of the push, counted: the decoder has mapped its records through the same list (WindowDecoder::submit_wideband)
+inline bool WidebandRun::read_gate(msk144_handle* h)
+{
+    int32_t count = 0, total = 0;
+    if(api_.gate(h, gate_.list.data(), &count, &total) != MSK144_OK) return false;
+    gate_.decoded += count;
+    gate_.windows += channels();
+    gate_.dropped += total - count;
+    gate_.busiest = std::max(gate_.busiest, static_cast<int>(count));
+    return true;
+}
+
 inline void WidebandRun::print_summary(msk144_handle* h) const
 {
     char buf[96];
@@ -531,6 +551,10 @@ inline void WidebandRun::print_summary(msk144_handle* h) const
         fprintf(stderr, "msk144hipdecoder: wideband capture: %lld segments, %lld hops written, %lld bytes, %lld units dropped\n", static_cast<long long>(cs.segments()),
                 static_cast<long long>(cs.hops()), static_cast<long long>(cs.bytes()), capture_.dropped);
     }
+    if(opt_.gate)
+        fprintf(stderr, "msk144hipdecoder: wideband gate: %lld of %lld channel windows decoded (%.1f %%), hold %d, min up %d, at most %d per push, %lld dropped, busiest push %d channels\n",
+                gate_.decoded, gate_.windows, gate_.windows ? 100.0 * static_cast<double>(gate_.decoded) / static_cast<double>(gate_.windows) : 0.0, opt_.gate_params.hold,
+                opt_.gate_params.min_up, msk144wb::gate_max_channels(opt_.gate_params, channels()), gate_.dropped, gate_.busiest);
     if(opt_.levels)
     {
         const std::vector<Levels::Channel>& lv = levels_.run;

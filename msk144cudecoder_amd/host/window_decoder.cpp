@@ -121,6 +121,7 @@ bool WindowDecoder::submit_hops(int slot, int n)
     HopStage hs;
     if(!hop_stage(slot, hs)) return false;
     streams_[slot].assign(hs.streams, hs.streams + n);
+    gated_[slot] = false;
     int rc = msk144_push_hops(handle_, slot, n);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
@@ -132,12 +133,21 @@ bool WindowDecoder::submit_hops(int slot, int n)
     return true;
 }
 
-bool WindowDecoder::submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t))
+bool WindowDecoder::submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t), int (*gate)(msk144_handle*, int32_t*, int32_t*, int32_t*))
 {
     streams_[slot].resize(static_cast<size_t>(opt_.channels));
     for(int c = 0; c < opt_.channels; c++) streams_[slot][static_cast<size_t>(c)] = c;
+    gated_[slot] = gate != nullptr;
     int rc = push(handle_, slot, first ? 1 : 0);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
+    if(rc == MSK144_OK && gate)
+    {
+        // the decode has waited for the gate's event: the list is there, and the records carry positions in it
+        int32_t count = 0, total = 0;
+        static_assert(sizeof(int) == sizeof(int32_t), "the list is read into the slot's streams");
+        rc = gate(handle_, streams_[slot].data(), &count, &total);
+        if(rc == MSK144_OK) streams_[slot].resize(static_cast<size_t>(count));
+    }
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
     if(rc != MSK144_OK)
     {
@@ -150,6 +160,7 @@ bool WindowDecoder::submit_wideband(int slot, bool first, int (*push)(msk144_han
 bool WindowDecoder::submit(int slot, const std::vector<int>& streams)
 {
     streams_[slot] = streams;
+    gated_[slot] = false;
     int rc = msk144_submit_slot_n(handle_, slot, static_cast<int32_t>(streams.size()));
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
@@ -187,12 +198,16 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
     const size_t n_results = static_cast<size_t>(n);
 
     // results arrive ordered by (position in the slot, item): walk them position by position
-    size_t r = 0;
-    for(size_t j = 0; j < streams.size(); j++)
+    // A gated wideband push: every stream takes part - its segment powers come by stream - and has records only where the gate
+    // listed it, at position j of the list; the others are post-processed with no candidates, as a window that decoded nothing
+    const bool gated = gated_[slot];
+    size_t r = 0, j = 0;
+    for(size_t u = 0; u < (gated ? static_cast<size_t>(nch) : streams.size()); u++)
     {
-        const int c = streams[j];
+        const bool listed = !gated || (j < streams.size() && streams[j] == static_cast<int>(u));
+        const int c = gated ? static_cast<int>(u) : streams[u];
         std::vector<AcceptedCandidate> accepted;
-        for(; r < n_results && results[r].channel == static_cast<int32_t>(j); r++)
+        for(; listed && r < n_results && results[r].channel == static_cast<int32_t>(j); r++)
         {
             const msk144_result& res = results[r];
             AcceptedCandidate a;
@@ -203,7 +218,8 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
             unpack_bits(res.message, a.bits);
             accepted.push_back(a);
         }
-        snr_[c].update(&seg[j * 8]);  // main.cu:388
+        snr_[c].update(&seg[(gated ? u : j) * 8]);  // main.cu:388
+        if(listed) j++;
         lines[c] = postprocess_window(accepted, snr_[c].snr_int(), opt_.reference_cache_quirk, calls_[c], filter_[c]);
         if(opt_.print_bits)
         {

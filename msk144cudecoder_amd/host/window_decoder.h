@@ -112,8 +112,10 @@ public:
     bool hop_stage(int slot, HopStage& out);
     bool submit_hops(int slot, int n);  // the first n entries of the slot's hop stage
     // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
-    // it at run time): every stream, in order
-    bool submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t));
+    // it at run time): every stream, in order.  `gate` (msk144_wideband_gate, with --wideband-gate): the decode covers the channels
+    // of the gate's list, which is taken behind it; collect() then gives every stream its SNR update and its post-processing, the
+    // streams that were not decoded with no candidates
+    bool submit_wideband(int slot, bool first, int (*push)(msk144_handle*, int32_t, int32_t), int (*gate)(msk144_handle*, int32_t*, int32_t*, int32_t*) = nullptr);
     msk144_handle* handle() const { return handle_; }
     void* stage(int slot);
     bool submit(int slot, const std::vector<int>& streams);
@@ -134,6 +136,7 @@ private:
     std::vector<ResultFilter> filter_;
     std::vector<CallHashTable> calls_;
     std::vector<int> streams_[kSlots];  // streams of the hop in flight on each slot, by position
+    bool gated_[kSlots] = {};           // the slot's hop is a gated wideband push: segment powers come by stream, for every stream
     size_t window_bytes_ = 0;           // of one stream
     bool last_overflow_ = false;
 };

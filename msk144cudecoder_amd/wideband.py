@@ -919,6 +919,53 @@ class Capture:
         return np.array(units[:self.max_units], dtype=CAPTURE_DTYPE), len(units)
 
 
+# ---- the gate: only the channels with activity are decoded (msk144_set_wideband_gate) ----
+
+GATE_MAX_HOLD = 16
+GATE_QUIET = GATE_MAX_HOLD + 1      # `since` saturates here
+GATE_HOP_BLOCKS = CAPTURE_HOP_BLOCKS
+# the defaults of msk144_wideband_gate_params (csrc/wideband.h GateParams): design parameters, not measurements
+GATE_DEFAULTS = dict(hold=1, min_up=1)
+
+
+class Gate:
+    """The gate rule of the contract (include/msk144hip.h) in Python integers, push by push.  Per channel `since`: the hops since
+    the last active one, saturating at GATE_QUIET.  push() takes the ping records of one push (PING_DTYPE [channel], or None: the
+    detector was off) and returns (list, total): the channels whose window the push decodes as int32, ascending, at most
+    max_channels of them, and the number that qualified.  restart() stands for msk144_set_wideband_gate in mid-stream."""
+
+    def __init__(self, channels: int, hold: int = 1, min_up: int = 1, max_channels=None, always=()):
+        channels = int(channels)
+        max_channels = channels if not max_channels else int(max_channels)
+        always = [int(c) for c in always]
+        if not 0 <= int(hold) <= GATE_MAX_HOLD:
+            raise ValueError("hold must lie within 0..16 hops")
+        if not 1 <= int(min_up) <= GATE_HOP_BLOCKS:
+            raise ValueError("min_up must lie within 1..27 blocks")
+        if not 1 <= max_channels <= channels:
+            raise ValueError("max_channels must lie within 1..channels")
+        if any(not 0 <= c < channels for c in always):
+            raise ValueError("an always channel is out of range")
+        self.channels, self.hold, self.min_up, self.max_channels, self.always = channels, int(hold), int(min_up), max_channels, frozenset(always)
+        self.restart()
+
+    def restart(self):
+        self.since = [GATE_QUIET] * self.channels
+
+    def push(self, records, first: bool):
+        if first:
+            self.restart()
+        hop_mask = (1 << GATE_HOP_BLOCKS) - 1
+        chosen = []
+        for c in range(self.channels):
+            mask = 0 if records is None else int(records["up_mask"][c])
+            for bits in ([mask & hop_mask, (mask >> GATE_HOP_BLOCKS) & hop_mask] if first else [mask & hop_mask]):
+                self.since[c] = 0 if bin(bits).count("1") >= self.min_up else min(self.since[c] + 1, GATE_QUIET)
+            if c in self.always or self.since[c] <= self.hold:
+                chosen.append(c)
+        return np.array(chosen[:self.max_channels], dtype=np.int32), len(chosen)
+
+
 def capture_segment_name(channel: int, hop: int) -> str:
     return f"ch{int(channel)}_hop{int(hop)}.cs8"
 

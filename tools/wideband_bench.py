@@ -28,6 +28,12 @@ Then one msk144hipdecoder run over a pre-written cu8 file (1024 channels at --pr
 default decode configuration): hops per second of the whole program against the real-time rate of 4.63 hops/s (one hop = 2592
 samples at 12 kHz).
 
+--gate SHARES is a leg of its own: 1024 channels at D = 160 and the deep options (width 500, step 1, depth 6), the detector off,
+and for each share an always list (msk144_set_wideband_gate) of round(share x 1024) evenly spread channels.  It measures the host
+milliseconds of push + decode + fetch per share, and the same for an ungated handle in the same run, then runs the program three
+times with the detector on - ungated, with every channel always decoded, and with the bare --wideband-gate - and appends every line
+to profiles/wideband_bench_gate.jsonl.  Nothing is asserted on these times.
+
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
                                    [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--pings-band] [--waterfall] [--capture] [--notch N]
 """
@@ -142,8 +148,59 @@ def measure(C: int, rate: int, pushes: int, K: int = 16, agc: bool = False, blan
                 target_ms=target)
 
 
-def program_run(hops: int, C: int = 1024, rate: int = 1920000) -> dict:
-    """Wall time of one msk144hipdecoder run over a file of 1 first + (hops - 1) later pushes of cu8 noise."""
+GATE_CFG = dict(center=0.0, width=500.0, step=1.0, depth=6, nbadsync_threshold=1, read_mode=2)   # the deep options
+
+
+def gate_channels(share: float, C: int) -> list:
+    """round(share x C) channels spread evenly over the C, so that the share is exact."""
+    n = int(round(share * C))
+    return sorted({i * C // n for i in range(n)}) if n else []
+
+
+def step_ms(d, pushes: int, warmup: int = 3) -> list:
+    """Host milliseconds of push + decode + fetch, one value per later push, behind `warmup` unmeasured ones."""
+    out = []
+    for i in range(warmup + pushes):
+        s = i % 2
+        t0 = time.perf_counter()
+        d.push_wideband(s, first=False)
+        d.decode()
+        d.fetch_async(s)
+        d.fetch_wait(s)
+        if i >= warmup:
+            out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def measure_gate(shares, pushes: int, C: int = 1024, rate: int = 1920000) -> list:
+    """--gate: ms per push + decode + fetch at the deep options with the detector off and an always list of each share of the
+    channels, and the same for an ungated handle in the same run.  Nothing is asserted."""
+    lim = rate // 2 - 6000
+    offsets = np.linspace(-lim, lim, C).astype(np.int32)
+    rng = np.random.default_rng(C)
+    out = []
+    with hipdecoder.HipDecoder(channels=C, **GATE_CFG) as plain, hipdecoder.HipDecoder(channels=C, **GATE_CFG) as gated:
+        for d in (plain, gated):
+            d.set_wideband(rate, offsets, "cu8")
+            for s in range(2):
+                d.wideband_slot(s)[:] = rng.integers(120, 136, size=d.wideband_slot(s).size, dtype=np.uint8)
+            d.push_wideband(0, first=True)
+            d.synchronize()
+        for share in shares:
+            listed = gate_channels(share, C)
+            gated.set_wideband_gate(always=listed)
+            a, b = step_ms(plain, pushes), step_ms(gated, pushes)
+            lst, total = gated.wideband_gate()
+            assert list(lst) == listed and total == len(listed)
+            out.append(dict(gate_share=share, channels=C, D=rate // 12000, config="width 500 step 1 depth 6", detector=False, listed=len(listed), pushes=pushes,
+                            gated_ms_median=round(float(np.median(b)), 3), gated_ms_mean=round(float(np.mean(b)), 3), ungated_ms_median=round(float(np.median(a)), 3),
+                            ungated_ms_mean=round(float(np.mean(a)), 3), gather_bytes=len(listed) * 5184 * 8 * 2))
+    return out
+
+
+def program_run(hops: int, C: int = 1024, rate: int = 1920000, gate: str = None, pings: bool = False) -> dict:
+    """Wall time of one msk144hipdecoder run over a file of 1 first + (hops - 1) later pushes of cu8 noise.  gate: the value of
+    --wideband-gate ("" the bare option, "all": every channel always decoded); pings: with --wideband-pings (the events to /dev/null)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = os.path.join(root, "msk144cudecoder_amd", "msk144hipdecoder")
     g = math.gcd(rate, 12000)
@@ -156,6 +213,10 @@ def program_run(hops: int, C: int = 1024, rate: int = 1920000) -> dict:
         f.write(np.clip(np.rint(127.5 + 6.0 * rng.standard_normal(n)), 0, 255).astype(np.uint8).tobytes())
         f.flush()
         args = [exe, f"--wideband-rate={rate}", "--wideband-format=cu8", "--channel-offsets=" + ",".join(str(int(v)) for v in offsets), "--wideband-gain=20"]
+        if pings:
+            args.append("--wideband-pings=/dev/null")
+        if gate is not None:
+            args.append("--wideband-gate" + ("=1:1:0:" + ",".join(str(c) for c in range(C)) if gate == "all" else "=" + gate if gate else ""))
         with open(f.name, "rb") as src:
             t0 = time.perf_counter()
             p = subprocess.run(args, stdin=src, capture_output=True, timeout=600)
@@ -166,6 +227,11 @@ def program_run(hops: int, C: int = 1024, rate: int = 1920000) -> dict:
     m = re.search(r"msk144hipdecoder: (\d+) batches", err)
     batches = int(m.group(1)) if m else None
     ratio = dict(D=P) if Q == 1 else dict(rate_hz=rate, P=P, Q=Q)
+    if gate is not None:
+        m = re.search(r"wideband gate: (\d+) of (\d+) channel windows decoded", err)
+        ratio.update(gate=gate, gate_windows=[int(m.group(1)), int(m.group(2))] if m else None)
+    if pings:
+        ratio["pings"] = True
     return dict(program="msk144hipdecoder", channels=C, **ratio, hops=batches, wall_s=round(wall, 3), hops_per_s=round(batches / wall, 2) if batches else None,
                 realtime_hops_per_s=4.63, note="wall time of the whole process, handle creation and file reading included")
 
@@ -186,7 +252,20 @@ def main():
     ap.add_argument("--waterfall", action="store_true", help="measure with the per-channel waterfall on")
     ap.add_argument("--capture", action="store_true", help="measure with the capture on, every 8th channel (up to 16) listed")
     ap.add_argument("--notch", type=int, default=None, metavar="N", help="measure with the first N channels notched (0: none, for the comparison); appends to profiles/wideband_bench_notch.jsonl")
+    ap.add_argument("--gate", default=None, metavar="SHARES", help="only the gate leg: ms per push + decode + fetch at 1024 channels, D = 160 and the deep options with each share "
+                    "(e.g. 0,0.1,0.5,1) of the channels always decoded and the detector off, against an ungated handle in the same run; then the program ungated, with every channel "
+                    "always decoded and behind the detector; appends to profiles/wideband_bench_gate.jsonl")
     a = ap.parse_args()
+    if a.gate is not None:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wideband_bench_gate.jsonl"), "a") as log:
+            lines = measure_gate([float(v) for v in a.gate.split(",") if v], a.pushes)
+            if a.program_hops:
+                lines += [program_run(a.program_hops, rate=a.program_rate, pings=True), program_run(a.program_hops, rate=a.program_rate, pings=True, gate="all"),
+                          program_run(a.program_hops, rate=a.program_rate, pings=True, gate="")]
+            for line in lines:
+                print(json.dumps(line), flush=True)
+                log.write(json.dumps(line) + "\n")
+        return
     log = None
     if a.notch is not None:
         log = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wideband_bench_notch.jsonl"), "a")
