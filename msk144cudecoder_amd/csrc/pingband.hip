@@ -1,26 +1,9 @@
 // pingband: the in-band filter ahead of the ping detector's block energies (msk144_set_wideband_ping_band, include/msk144hip.h).
 //
-// One workgroup of four waves per channel.  It stages the channel's 63-sample tail and the push's row (two rows on a first push)
-// in LDS with 16-byte loads, so that stored sample m of the push lies at byte 128 + 2m and the tail in bytes 2..127 in front of it
-// (bytes 0..1, "sample -64", are zero), and packs the 64 complex int8 taps once into 33 dwords per sum for the int8 dot product.
-//
-// A work item is 12 consecutive outputs z[n0] .. z[n0 + 11], n0 = 12 x item, eight items to a block of 96; a lane takes one item
-// per pass (216 items of a later push, 432 of a first one).  A dword of the row holds two samples (I0, Q0, I1, Q1), and the window
-// x[n - 63 .. n] of an odd n starts on a dword, that of an even n two bytes behind one.  So the taps are packed twice:
-//
-//   even n   dword j of the window that starts at sample n - 64 meets taps (64 - 2j, 63 - 2j): 33 dwords, tap 64 and tap -1 are 0;
-//   odd n    the same dword - the window of n - 1 - meets taps (65 - 2j, 64 - 2j): dword 0 is all zero;
-//
-// and a pair of outputs (n, n + 1), n even, runs over the same 33 dwords.  The 38 dwords that an item's six pairs cover are read
-// once, with 8-byte LDS loads, and stay in registers; the tap dwords are the same address in every lane (LDS broadcasts).  Per
-// dword and output there are three dot products: Re z = sum br I - sum bi Q as two of them, with packings (br, 0) and (0, bi) - a
-// single packing (br, -bi) cannot hold bi = -128, and any int8 tap is valid - and Im z as one with (bi, br).  The squares and the
-// block sum are 64-bit integers, summed over an item's 12 outputs in the lane and over a block's eight lanes with three wave
-// shuffles: exact in any order, no atomics, the same hops give the same bytes.
-//
-// The tail is read before the workgroup's barrier and written behind it by the same eight lanes of the same workgroup, the only one
-// that touches the channel: it needs no order between workgroups.
-#include "msk144_kernels.h"
+// The filter, its LDS layout and the tail are fir64.h's.  This file's own is the ending: eight items to a block of 96 outputs, the
+// squares and the block sum in 64-bit integers, summed over an item's 12 outputs in the lane and over a block's eight lanes with
+// three wave shuffles - exact in any order, no atomics, the same hops give the same bytes - then the shift and the clamp to 22 bits.
+#include "fir64.h"
 
 namespace msk144
 {
@@ -28,106 +11,28 @@ namespace msk144
 namespace
 {
 
-constexpr int kThreads = 256;
-constexpr int kRowBytes = 2 * kHopSamples;                          // 5184
-constexpr int kRowVecs = kRowBytes / 16;                            // 324
-constexpr int kTailBytes = 128;                                     // 2 zero bytes + 63 samples
-constexpr int kTailVecs = kTailBytes / 16;
-constexpr int kItemOutputs = 12;
-constexpr int kPairs = kItemOutputs / 2;
-constexpr int kBlockItems = msk144wb::kPingBlock / kItemOutputs;    // 8 lanes to a block
-constexpr int kTapDwords = msk144wb::kPingBandTaps / 2 + 1;         // 33
-constexpr int kWindowDwords = kTapDwords + kPairs - 1;              // 38
-static_assert(kRowBytes % 16 == 0 && msk144wb::kPingBlock % kItemOutputs == 0 && kThreads % kBlockItems == 0 && kWindowDwords % 2 == 0, "whole vectors, whole items");
-static_assert(kTailBytes == 2 * (msk144wb::kPingBandTail + 1), "the tail row is 64 samples, the oldest one zero");
-static_assert(kBlockItems == 8, "three shuffles sum a block");
+using namespace fir64;
 
-__device__ __forceinline__ int32_t dot4(uint32_t a, uint32_t b, int32_t acc)
-{
-#if __has_builtin(__builtin_amdgcn_sdot4)
-    return __builtin_amdgcn_sdot4(static_cast<int>(a), static_cast<int>(b), acc, false);
-#else
-#pragma unroll
-    for(int k = 0; k < 4; k++) acc += static_cast<int32_t>(static_cast<int8_t>(a >> (8 * k))) * static_cast<int32_t>(static_cast<int8_t>(b >> (8 * k)));
-    return acc;
-#endif
-}
+constexpr int kBlockItems = msk144wb::kPingBlock / kItemOutputs;    // 8 lanes to a block
+static_assert(msk144wb::kPingBlock % kItemOutputs == 0 && kThreads % kBlockItems == 0, "whole items to a block, whole blocks to a wave");
+static_assert(kBlockItems == 8, "three shuffles sum a block");
 
 // first_halves, hops: [channels][5184] bytes; taps[64][2]; tails[channels][128] bytes; energies[channels][54]
 __global__ __launch_bounds__(kThreads) void pingband_kernel(const uint4* __restrict__ first_halves, const uint4* __restrict__ hops, int first, const int8_t* __restrict__ taps,
                                                             int shift, int restart, uint4* __restrict__ tails, int32_t* __restrict__ energies)
 {
-    __shared__ uint4 s_x[kTailVecs + 2 * kRowVecs];
-    __shared__ uint4 s_t[kTapDwords][2];  // even n: (br, 0), (0, bi), (bi, br); odd n: the same three; two dwords unused
+    __shared__ Lds s;
     const int tid = threadIdx.x;
     const size_t ch = blockIdx.x;
-    const int nvec = first ? 2 * kRowVecs : kRowVecs;
+    stage(s, first_halves, hops, first, ch, taps, restart, tails);
 
-    if(tid < kTailVecs) s_x[tid] = restart ? uint4{0, 0, 0, 0} : tails[ch * kTailVecs + tid];
-    for(int i = tid; i < nvec; i += kThreads)
+    const int items = first ? 2 * kRowItems : kRowItems;  // nb x 8
+    for(int base = 0; base < items; base += kThreads)    // the same trips in every lane: the shuffles meet whole waves
     {
-        const bool head = first && i < kRowVecs;
-        s_x[kTailVecs + i] = (head ? first_halves : hops)[ch * kRowVecs + (first && !head ? i - kRowVecs : i)];
-    }
-    if(tid < kTapDwords)
-    {
-        // tap k as unsigned bytes, zero outside 0..63
-        auto re = [&](int k) -> uint32_t { return k >= 0 && k < msk144wb::kPingBandTaps ? static_cast<uint8_t>(taps[2 * k]) : 0u; };
-        auto im = [&](int k) -> uint32_t { return k >= 0 && k < msk144wb::kPingBandTaps ? static_cast<uint8_t>(taps[2 * k + 1]) : 0u; };
-        const int e1 = 64 - 2 * tid, e2 = e1 - 1, o1 = e1 + 1, o2 = e1;
-        uint4 a, b;
-        a.x = re(e1) | (re(e2) << 16);
-        a.y = (im(e1) << 8) | (im(e2) << 24);
-        a.z = im(e1) | (re(e1) << 8) | (im(e2) << 16) | (re(e2) << 24);
-        a.w = re(o1) | (re(o2) << 16);
-        b.x = (im(o1) << 8) | (im(o2) << 24);
-        b.y = im(o1) | (re(o1) << 8) | (im(o2) << 16) | (re(o2) << 24);
-        b.z = b.w = 0;
-        s_t[tid][0] = a;
-        s_t[tid][1] = b;
-    }
-    __syncthreads();
-
-    // the last 63 samples of the push, as the next push finds them
-    if(tid < kTailVecs)
-    {
-        uint4 v = s_x[nvec + tid];
-        if(tid == 0) v.x &= 0xffff0000u;
-        tails[ch * kTailVecs + tid] = v;
-    }
-
-    const uint2* xw = reinterpret_cast<const uint2*>(s_x);
-    const int items = nvec * 16 / (2 * kItemOutputs);  // 216 or 432: nb x 8
-    for(int base = 0; base < items; base += kThreads)  // the same trips in every lane: the shuffles meet whole waves
-    {
-        const int item = base + tid;
-        const int it = item < items ? item : items - 1;  // lanes past the end redo the last item and write nothing
-        // the item's window starts at sample 12 it - 64: byte 24 it, dwords 6 it .. 6 it + 37 (the last one of the last item ends the row)
+        const int n = base + tid;
         uint32_t d[kWindowDwords];
-#pragma unroll
-        for(int i = 0; i < kWindowDwords / 2; i++)
-        {
-            const uint2 v = xw[it * (kPairs / 2) + i];
-            d[2 * i] = v.x;
-            d[2 * i + 1] = v.y;
-        }
-        int32_t ra[kItemOutputs] = {}, rb[kItemOutputs] = {}, zi[kItemOutputs] = {};
-#pragma unroll
-        for(int j = 0; j < kTapDwords; j++)
-        {
-            const uint4 t0 = s_t[j][0], t1 = s_t[j][1];
-#pragma unroll
-            for(int p = 0; p < kPairs; p++)
-            {
-                const uint32_t x = d[j + p];
-                ra[2 * p] = dot4(t0.x, x, ra[2 * p]);
-                rb[2 * p] = dot4(t0.y, x, rb[2 * p]);
-                zi[2 * p] = dot4(t0.z, x, zi[2 * p]);
-                ra[2 * p + 1] = dot4(t0.w, x, ra[2 * p + 1]);
-                rb[2 * p + 1] = dot4(t1.x, x, rb[2 * p + 1]);
-                zi[2 * p + 1] = dot4(t1.y, x, zi[2 * p + 1]);
-            }
-        }
+        int32_t ra[kItemOutputs], rb[kItemOutputs], zi[kItemOutputs];
+        item(s, n < items ? n : items - 1, d, ra, rb, zi);  // lanes past the end redo the last item and write nothing
         unsigned long long sum = 0;
 #pragma unroll
         for(int o = 0; o < kItemOutputs; o++)
@@ -138,10 +43,10 @@ __global__ __launch_bounds__(kThreads) void pingband_kernel(const uint4* __restr
         sum += __shfl_xor(sum, 1);
         sum += __shfl_xor(sum, 2);
         sum += __shfl_xor(sum, 4);
-        if(item < items && (tid & (kBlockItems - 1)) == 0)
+        if(n < items && (tid & (kBlockItems - 1)) == 0)
         {
             const unsigned long long e = sum >> shift;
-            energies[ch * msk144wb::kPingMaxBlocks + item / kBlockItems] = e > static_cast<unsigned long long>(msk144wb::kPingBandMaxEnergy) ? msk144wb::kPingBandMaxEnergy : static_cast<int32_t>(e);
+            energies[ch * msk144wb::kPingMaxBlocks + n / kBlockItems] = e > static_cast<unsigned long long>(msk144wb::kPingBandMaxEnergy) ? msk144wb::kPingBandMaxEnergy : static_cast<int32_t>(e);
         }
     }
 }

@@ -36,22 +36,6 @@ static_assert(kHopSamples % msk144wb::kPingBlock == 0 && 2 * kHopBlocks == msk14
 static_assert(kBlockBytes % 16 == 0 && kRowBytes % 16 == 0, "16-byte loads");
 static_assert(msk144wb::kPingEnergyBits + 6 <= 28, "the peak key keeps clear of the exponent bits that bias it");
 
-// a . a over four int8 components, added to acc
-__device__ __forceinline__ int32_t dot4_sq(uint32_t a, int32_t acc)
-{
-#if __has_builtin(__builtin_amdgcn_sdot4)
-    return __builtin_amdgcn_sdot4(static_cast<int>(a), static_cast<int>(a), acc, false);
-#else
-#pragma unroll
-    for(int k = 0; k < 4; k++)
-    {
-        const int32_t v = static_cast<int8_t>(a >> (8 * k));
-        acc += v * v;
-    }
-    return acc;
-#endif
-}
-
 // first_halves, hops: [channels][5184] bytes, the hop ring's staging; records[channels]; energies[channels][54]; state[channels].
 // kBand: the energies of the push are already in `energies` (pingband.hip wrote the in-band Ef there, ahead on the same stream) and
 // the hops are not read; every other step is the same code.
@@ -80,10 +64,10 @@ __global__ __launch_bounds__(kWaves * 64) void pings_kernel(const int8_t* __rest
         for(int j = 0; j < kBlockBytes / 16; j++)
         {
             const uint4 v = src[j];
-            E = dot4_sq(v.x, E);
-            E = dot4_sq(v.y, E);
-            E = dot4_sq(v.z, E);
-            E = dot4_sq(v.w, E);
+            E = dot4(v.x, v.x, E);
+            E = dot4(v.y, v.y, E);
+            E = dot4(v.z, v.z, E);
+            E = dot4(v.w, v.w, E);
         }
     }
 

@@ -46,6 +46,18 @@ __device__ __forceinline__ float f32_sqrt(float x)
     return __builtin_sqrtf(x);  // v_sqrt_f32 + FMA refinement, correctly rounded
 }
 
+// a . b over four int8 components each, added to acc (v_dot4_i32_i8)
+__device__ __forceinline__ int32_t dot4(uint32_t a, uint32_t b, int32_t acc)
+{
+#if __has_builtin(__builtin_amdgcn_sdot4)
+    return __builtin_amdgcn_sdot4(static_cast<int>(a), static_cast<int>(b), acc, false);
+#else
+#pragma unroll
+    for(int k = 0; k < 4; k++) acc += static_cast<int32_t>(static_cast<int8_t>(a >> (8 * k))) * static_cast<int32_t>(static_cast<int8_t>(b >> (8 * k)));
+    return acc;
+#endif
+}
+
 __device__ __forceinline__ int lane_id()
 {
     return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));

@@ -368,10 +368,61 @@ inline PingRecord ping_record(const PingParams& p, PingHistory& s, bool restart,
     return r;
 }
 
+// ---- the 64-tap complex int8 FIR on a channel's stored samples, behind the ping band and the notch (the kernels': csrc/fir64.h) ----
+
+constexpr int kFirTaps = 64, kFirTail = kFirTaps - 1;   // the tail: the stored samples a channel keeps between pushes
+
+// 64 complex int8 taps (br, bi) and a shift: msk144_wideband_ping_band_params and msk144_wideband_notch_params, field for field
+struct FirParams
+{
+    int8_t taps[kFirTaps][2];
+    int32_t shift;
+};
+
+// (re, im) += gain x B(f), B(f) = sum b[k] e^{-j 2 pi f k / 12000} of the integer taps, term by term in ascending k
+inline void fir_response_add(const FirParams& p, double f_hz, double gain, double& re, double& im)
+{
+    for(int k = 0; k < kFirTaps; k++)
+    {
+        const double a = -2.0 * M_PI * f_hz * k / kOutRate, c = std::cos(a), s = std::sin(a);
+        re += gain * (p.taps[k][0] * c - p.taps[k][1] * s);
+        im += gain * (p.taps[k][0] * s + p.taps[k][1] * c);
+    }
+}
+
+// h[N]: a Hamming-windowed sinc low-pass with cutoff halfwidth_hz, centred on k = mid, unscaled
+inline void hamming_sinc(int N, double mid, int halfwidth_hz, double* h)
+{
+    for(int k = 0; k < N; k++)
+    {
+        const double arg = 2.0 * halfwidth_hz * (k - mid) / kOutRate;
+        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
+        h[k] = sinc * (0.54 - 0.46 * std::cos(2.0 * M_PI * k / (N - 1)));
+    }
+}
+
+// The filter on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push, tail[63][2] the channel's 63
+// stored samples before them, oldest first.  Leaves the joined stream in s[63 + n][2], so that x[m - k] is s[63 + m - k], returns
+// z[n][2], z[m] = sum_k b[k] x[m - k] in int32 (|Re z|, |Im z| <= 2^21), and moves the tail on to the last 63 samples of x.
+inline std::vector<int32_t> fir_push(const FirParams& p, const int8_t* x, int n, int8_t* tail, std::vector<int8_t>& s)
+{
+    s.assign(tail, tail + 2 * kFirTail);
+    s.insert(s.end(), x, x + 2 * n);
+    std::vector<int32_t> z(static_cast<size_t>(2 * n), 0);
+    for(int m = 0; m < n; m++)
+        for(int k = 0; k < kFirTaps; k++)
+        {
+            const int32_t xr = s[static_cast<size_t>(2 * (kFirTail + m - k))], xi = s[static_cast<size_t>(2 * (kFirTail + m - k) + 1)];
+            z[static_cast<size_t>(2 * m)] += p.taps[k][0] * xr - p.taps[k][1] * xi;
+            z[static_cast<size_t>(2 * m + 1)] += p.taps[k][0] * xi + p.taps[k][1] * xr;
+        }
+    std::copy(s.end() - 2 * kFirTail, s.end(), tail);
+    return z;
+}
+
 // ---- the ping band: an in-band filter ahead of the block energies (msk144_set_wideband_ping_band) ----
 
-constexpr int kPingBandTaps = 64;
-constexpr int kPingBandTail = kPingBandTaps - 1;   // stored samples a channel keeps between pushes
+constexpr int kPingBandTaps = kFirTaps, kPingBandTail = kFirTail;
 constexpr int kPingBandMaxShift = 40;
 constexpr int32_t kPingBandMaxEnergy = (1 << kPingEnergyBits) - 1;
 constexpr int kPingBandMinHalfwidthHz = 500;
@@ -381,12 +432,7 @@ constexpr int kPingBandDefaultHalfwidthHz = 1500;
 // the CPU simulation that include/msk144hip.h tabulates
 constexpr int kPingBandDefaultRatioQ4 = 52;
 
-// msk144_wideband_ping_band_params, field for field
-struct PingBandParams
-{
-    int8_t taps[kPingBandTaps][2];
-    int32_t shift;
-};
+using PingBandParams = FirParams;
 static_assert(sizeof(PingBandParams) == 132, "msk144_wideband_ping_band_params is 132 bytes");
 
 // The rules of msk144_set_wideband_ping_band that need no handle: any int8 taps.  Empty string = valid.
@@ -404,16 +450,11 @@ inline std::string check_ping_band_design(int centre_hz, int halfwidth_hz)
     return std::string();
 }
 
-// |B(f)|^2 of the integer taps, B(f) = sum b[k] e^{-j 2 pi f k / 12000}
+// |B(f)|^2 of the integer taps
 inline double ping_band_response(const PingBandParams& p, double f_hz)
 {
     double re = 0.0, im = 0.0;
-    for(int k = 0; k < kPingBandTaps; k++)
-    {
-        const double a = -2.0 * M_PI * f_hz * k / kOutRate, c = std::cos(a), s = std::sin(a);
-        re += p.taps[k][0] * c - p.taps[k][1] * s;
-        im += p.taps[k][0] * s + p.taps[k][1] * c;
-    }
+    fir_response_add(p, f_hz, 1.0, re, im);
     return re * re + im * im;
 }
 
@@ -422,16 +463,14 @@ inline double ping_band_response(const PingBandParams& p, double f_hz)
 // inside the band comes out at about the level it went in with.  The caller has checked the arguments.
 inline PingBandParams ping_band_design(int centre_hz, int halfwidth_hz)
 {
-    double re[kPingBandTaps], im[kPingBandTaps], top = 0.0;
+    constexpr double mid = 0.5 * (kPingBandTaps - 1);
+    double h[kPingBandTaps], re[kPingBandTaps], im[kPingBandTaps], top = 0.0;
+    hamming_sinc(kPingBandTaps, mid, halfwidth_hz, h);
     for(int k = 0; k < kPingBandTaps; k++)
     {
-        const double t = k - 0.5 * (kPingBandTaps - 1);
-        const double arg = 2.0 * halfwidth_hz * t / kOutRate;
-        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
-        const double h = sinc * (0.54 - 0.46 * std::cos(2.0 * M_PI * k / (kPingBandTaps - 1)));
-        const double a = 2.0 * M_PI * centre_hz * t / kOutRate;
-        re[k] = h * std::cos(a);
-        im[k] = h * std::sin(a);
+        const double a = 2.0 * M_PI * centre_hz * (k - mid) / kOutRate;
+        re[k] = h[k] * std::cos(a);
+        im[k] = h[k] * std::sin(a);
         top = std::max(top, std::max(std::fabs(re[k]), std::fabs(im[k])));
     }
     PingBandParams p{};
@@ -446,32 +485,19 @@ inline PingBandParams ping_band_design(int centre_hz, int halfwidth_hz)
 
 // The filter and its energies on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push (n a multiple
 // of 96), tail[63][2] the channel's 63 stored samples before them, oldest first (all zero where the ping kernel restarts); writes
-// Ef[n / 96] and moves the tail on to the last 63 samples of x.  z[m] = sum_k b[k] x[m - k] in int32 (|Re z|, |Im z| <= 2^21),
-// Ef[b] = min((sum over the block of Re z^2 + Im z^2) >> shift, 2^22 - 1) in 64 bits.  What libmsk144host.so holds the Python model
-// and the kernel (pingband.hip) to.
+// Ef[n / 96] and moves the tail on to the last 63 samples of x.  With fir_push's z, Ef[b] = min((sum over the block of Re z^2 +
+// Im z^2) >> shift, 2^22 - 1) in 64 bits.  What libmsk144host.so holds the Python model and the kernel (pingband.hip) to.
 inline void ping_band_energies(const PingBandParams& p, const int8_t* x, int n, int8_t* tail, int32_t* Ef)
 {
-    std::vector<int8_t> s(static_cast<size_t>(2 * (kPingBandTail + n)));
-    std::memcpy(s.data(), tail, 2 * kPingBandTail);
-    std::memcpy(s.data() + 2 * kPingBandTail, x, static_cast<size_t>(2 * n));
+    std::vector<int8_t> s;
+    const std::vector<int32_t> z = fir_push(p, x, n, tail, s);
     for(int b = 0; b < n / kPingBlock; b++)
     {
         uint64_t sum = 0;
-        for(int m = b * kPingBlock; m < (b + 1) * kPingBlock; m++)
-        {
-            int32_t zr = 0, zi = 0;
-            for(int k = 0; k < kPingBandTaps; k++)
-            {
-                const int32_t xr = s[static_cast<size_t>(2 * (kPingBandTail + m - k))], xi = s[static_cast<size_t>(2 * (kPingBandTail + m - k) + 1)];
-                zr += p.taps[k][0] * xr - p.taps[k][1] * xi;
-                zi += p.taps[k][0] * xi + p.taps[k][1] * xr;
-            }
-            sum += static_cast<uint64_t>(static_cast<int64_t>(zr) * zr) + static_cast<uint64_t>(static_cast<int64_t>(zi) * zi);
-        }
+        for(size_t i = static_cast<size_t>(2 * b * kPingBlock); i < static_cast<size_t>(2 * (b + 1) * kPingBlock); i++) sum += static_cast<uint64_t>(static_cast<int64_t>(z[i]) * z[i]);
         sum >>= p.shift;
         Ef[b] = sum > static_cast<uint64_t>(kPingBandMaxEnergy) ? kPingBandMaxEnergy : static_cast<int32_t>(sum);
     }
-    std::memcpy(tail, s.data() + static_cast<size_t>(2 * n), 2 * kPingBandTail);
 }
 
 // An event: a maximal run of consecutive up blocks of one channel in g = (blocks of all earlier pushes) + b
@@ -1016,8 +1042,7 @@ private:
 
 // ---- the notch: steady carriers taken out of a channel's stored samples (msk144_set_wideband_notch, msk144_wideband_notch_stats) ----
 
-constexpr int kNotchTaps = 64;
-constexpr int kNotchTail = kNotchTaps - 1;   // raw (pre-notch) stored samples a channel keeps between pushes
+constexpr int kNotchTaps = kFirTaps, kNotchTail = kFirTail;   // a tail of raw (pre-notch) samples
 constexpr int kNotchDelay = 31;              // the output is the input delayed by this many samples, minus the estimate
 constexpr int kNotchMaxShift = 15;
 constexpr int kNotchMaxFreqs = 2;            // carriers of one channel's default design
@@ -1026,12 +1051,7 @@ constexpr int kNotchMaxHalfwidthHz = 500;
 constexpr int kNotchDefaultHalfwidthHz = 100;
 constexpr int kNotchMinSpacingHz = 1000;     // closer carriers over-subtract: the two pass bands of the estimate add
 
-// msk144_wideband_notch_params, field for field
-struct NotchParams
-{
-    int8_t taps[kNotchTaps][2];
-    int32_t shift;
-};
+using NotchParams = FirParams;
 static_assert(sizeof(NotchParams) == 132, "msk144_wideband_notch_params is 132 bytes");
 
 // The rule of msk144_set_wideband_notch that needs no handle: any int8 taps.  Empty string = valid.
@@ -1052,18 +1072,13 @@ inline std::string check_notch_design(const int32_t* freqs_hz, int n, int halfwi
     return std::string();
 }
 
-// |H(f)|^2 of the whole stage, H(f) = e^{-j 2 pi f 31 / 12000} - B(f) / 2^shift with B(f) = sum b[k] e^{-j 2 pi f k / 12000}: what a
-// component at f_hz keeps of its power (without the rounding of the output)
+// |H(f)|^2 of the whole stage, H(f) = e^{-j 2 pi f 31 / 12000} - B(f) / 2^shift: what a component at f_hz keeps of its power (without
+// the rounding of the output)
 inline double notch_response(const NotchParams& p, double f_hz)
 {
-    const double scale = std::ldexp(1.0, -p.shift), d = -2.0 * M_PI * f_hz * kNotchDelay / kOutRate;
+    const double d = -2.0 * M_PI * f_hz * kNotchDelay / kOutRate;
     double re = std::cos(d), im = std::sin(d);
-    for(int k = 0; k < kNotchTaps; k++)
-    {
-        const double a = -2.0 * M_PI * f_hz * k / kOutRate, c = std::cos(a), s = std::sin(a);
-        re -= scale * (p.taps[k][0] * c - p.taps[k][1] * s);
-        im -= scale * (p.taps[k][0] * s + p.taps[k][1] * c);
-    }
+    fir_response_add(p, f_hz, -std::ldexp(1.0, -p.shift), re, im);
     return re * re + im * im;
 }
 
@@ -1075,13 +1090,8 @@ inline NotchParams notch_design(const int32_t* freqs_hz, int n, int halfwidth_hz
 {
     constexpr int N = kNotchTaps - 1;
     double h[N], re[N] = {}, im[N] = {}, sum = 0.0, top = 0.0;
-    for(int k = 0; k < N; k++)
-    {
-        const double arg = 2.0 * halfwidth_hz * (k - kNotchDelay) / kOutRate;
-        const double sinc = std::fabs(arg) < 1e-12 ? 1.0 : std::sin(M_PI * arg) / (M_PI * arg);
-        h[k] = sinc * (0.54 - 0.46 * std::cos(2.0 * M_PI * k / (N - 1)));
-        sum += h[k];
-    }
+    hamming_sinc(N, kNotchDelay, halfwidth_hz, h);
+    for(int k = 0; k < N; k++) sum += h[k];
     for(int k = 0; k < N; k++)
     {
         for(int i = 0; i < n; i++)
@@ -1109,31 +1119,18 @@ MSK144WB_HD inline int32_t notch_out(int32_t x, int32_t z, int32_t shift) { retu
 
 // The stage on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push, tail[63][2] the channel's 63 raw
 // (pre-notch) stored samples before them, oldest first (all zero where the channel's filter starts); writes y[n][2] (y may be x),
-// adds the components that sat8 clamped to *clipped and moves the tail on to the last 63 samples of x.  z[m] = sum_k b[k] x[m - k]
-// in int32 as the ping band's, y[m] = sat8(((x[m - 31] << shift) - z[m] + r) >> shift).  What libmsk144host.so holds the Python model
-// and the kernel (notch.hip) to.
+// adds the components that sat8 clamped to *clipped and moves the tail on to the last 63 samples of x.  With fir_push's z,
+// y[m] = sat8(((x[m - 31] << shift) - z[m] + r) >> shift).  What libmsk144host.so holds the Python model and the kernel (notch.hip) to.
 inline void notch_filter(const NotchParams& p, const int8_t* x, int n, int8_t* tail, int8_t* y, int32_t* clipped)
 {
-    std::vector<int8_t> s(static_cast<size_t>(2 * (kNotchTail + n)));
-    std::memcpy(s.data(), tail, 2 * kNotchTail);
-    std::memcpy(s.data() + 2 * kNotchTail, x, static_cast<size_t>(2 * n));
-    for(int m = 0; m < n; m++)
+    std::vector<int8_t> s;
+    const std::vector<int32_t> z = fir_push(p, x, n, tail, s);
+    for(size_t i = 0; i < z.size(); i++)
     {
-        int32_t zr = 0, zi = 0;
-        for(int k = 0; k < kNotchTaps; k++)
-        {
-            const int32_t xr = s[static_cast<size_t>(2 * (kNotchTail + m - k))], xi = s[static_cast<size_t>(2 * (kNotchTail + m - k) + 1)];
-            zr += p.taps[k][0] * xr - p.taps[k][1] * xi;
-            zi += p.taps[k][0] * xi + p.taps[k][1] * xr;
-        }
-        const size_t d = static_cast<size_t>(2 * (kNotchTail + m - kNotchDelay));
-        const int32_t vr = notch_out(s[d], zr, p.shift), vi = notch_out(s[d + 1], zi, p.shift);
-        const int32_t yr = notch_sat8(vr), yi = notch_sat8(vi);
-        *clipped += (yr != vr) + (yi != vi);
-        y[2 * m] = static_cast<int8_t>(yr);
-        y[2 * m + 1] = static_cast<int8_t>(yi);
+        const int32_t v = notch_out(s[2 * (kNotchTail - kNotchDelay) + i], z[i], p.shift), sat = notch_sat8(v);
+        *clipped += sat != v;
+        y[i] = static_cast<int8_t>(sat);
     }
-    std::memcpy(tail, s.data() + static_cast<size_t>(2 * n), 2 * kNotchTail);
 }
 
 // The host rule of --wideband-notch=auto: which carriers get a notch, from every push's msk144_wideband_waterfall_sums.  Host only,

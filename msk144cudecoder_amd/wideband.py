@@ -44,6 +44,10 @@ def _host_lib():
         L.msk144host_wideband_check.restype = C.c_int
         L.msk144host_wideband_bank_taps.argtypes = [C.c_int64, C.c_int, C.c_void_p]
         L.msk144host_wideband_bank_taps.restype = C.c_int
+        L.msk144host_wideband_ping_band_design.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int]
+        L.msk144host_wideband_ping_band_design.restype = C.c_int
+        L.msk144host_wideband_notch_design.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int]
+        L.msk144host_wideband_notch_design.restype = C.c_int
         _host = L
     return _host
 
@@ -444,16 +448,42 @@ PING_BAND_MAX_ENERGY = (1 << 22) - 1
 PING_BAND_RATIO_Q4 = 52   # MSK144_PING_BAND_RATIO_Q4: the detector's default ratio with the default band on
 
 
+def _fir_taps(taps, shape_error: str, value_error: str) -> np.ndarray:
+    """int8 [64][2] from taps [k][2], 1 <= k <= 64, zero-padded; the two refusals are the caller's texts."""
+    t = np.asarray(taps)
+    if t.ndim != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= PING_BAND_TAPS:
+        raise ValueError(shape_error)
+    if np.any(t != t.astype(np.int8)):
+        raise ValueError(value_error)
+    full = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
+    full[:t.shape[0]] = t
+    return full
+
+
+def _fir_push(tail, q, taps) -> Tuple[np.ndarray, np.ndarray]:
+    """The 64-tap FIR behind the ping band and the notch (csrc/wideband.h fir_push): int8 tail [..][63][2], int8 hops q [..][M][2] and
+    taps [64][2] give the joined stream s [..][63 + M][2], so that x[m - k] is s[..., 63 + m - k, :], and z [..][M][2],
+    z[m] = sum b[k] x[m - k], both int64.  The next tail is s[..., M:, :]."""
+    s = np.concatenate([tail, np.asarray(q).astype(np.int8)], axis=-2).astype(np.int64)
+    M, T = s.shape[-2] - (PING_BAND_TAPS - 1), PING_BAND_TAPS - 1
+    z = np.zeros(s.shape[:-2] + (M, 2), dtype=np.int64)
+    for k in range(PING_BAND_TAPS):
+        br, bi = int(taps[k, 0]), int(taps[k, 1])
+        if br == 0 and bi == 0:
+            continue
+        a, b = s[..., T - k:T - k + M, 0], s[..., T - k:T - k + M, 1]
+        z[..., 0] += br * a - bi * b
+        z[..., 1] += br * b + bi * a
+    return s, z
+
+
 def ping_band_taps(centre_hz: int = 0, halfwidth_hz: int = 1500) -> Tuple[np.ndarray, int]:
     """The default design of the contract, from libmsk144host.so (csrc/wideband.h ping_band_design), exactly what the program hands
     to the library: (int8 [64][2] taps (br, bi), shift)."""
-    L = _host_lib()
     taps = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
     shift = C.c_int32(0)
     why = C.create_string_buffer(256)
-    L.msk144host_wideband_ping_band_design.restype = C.c_int
-    rc = L.msk144host_wideband_ping_band_design(C.c_int32(int(centre_hz)), C.c_int32(int(halfwidth_hz)), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why, len(why))
-    if rc != 0:
+    if _host_lib().msk144host_wideband_ping_band_design(int(centre_hz), int(halfwidth_hz), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why, len(why)) != 0:
         raise ValueError(why.value.decode())
     return taps, int(shift.value)
 
@@ -465,15 +495,9 @@ class PingBand:
     msk144_set_wideband_pings or msk144_set_wideband_ping_band): the tail is all zero there.  A change of scale does not reset."""
 
     def __init__(self, channels: int, taps, shift: int):
-        t = np.asarray(taps)
-        if t.ndim != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= PING_BAND_TAPS:
-            raise ValueError("taps must be [k][2] with 1 <= k <= 64")
-        if np.any(t != t.astype(np.int8)):
-            raise ValueError("taps must be int8 values")
+        self.taps = _fir_taps(taps, "taps must be [k][2] with 1 <= k <= 64", "taps must be int8 values")
         if not 0 <= int(shift) <= PING_BAND_MAX_SHIFT:
             raise ValueError("shift must lie within 0..40")
-        self.taps = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
-        self.taps[:t.shape[0]] = t
         self.shift, self.channels = int(shift), int(channels)
         self.reset()
 
@@ -486,19 +510,8 @@ class PingBand:
         if q.ndim != 3 or q.shape[0] != self.channels or q.shape[1] % PING_BLOCK or q.shape[2] != 2:
             raise ValueError(f"hops must be [{self.channels}][M][2] with M a multiple of 96")
         M = q.shape[1]
-        s = np.concatenate([self.tail, q.astype(np.int8)], axis=1).astype(np.int64)
-        xr, xi = s[:, :, 0], s[:, :, 1]
-        zr = np.zeros((self.channels, M), dtype=np.int64)
-        zi = np.zeros((self.channels, M), dtype=np.int64)
-        T = PING_BAND_TAPS - 1
-        for k in range(PING_BAND_TAPS):
-            br, bi = int(self.taps[k, 0]), int(self.taps[k, 1])
-            if br == 0 and bi == 0:
-                continue
-            a, b = xr[:, T - k:T - k + M], xi[:, T - k:T - k + M]
-            zr += br * a - bi * b
-            zi += br * b + bi * a
-        S = np.sum((zr * zr + zi * zi).reshape(self.channels, M // PING_BLOCK, PING_BLOCK), axis=2)   # < 2^50
+        s, z = _fir_push(self.tail, q, self.taps)
+        S = np.sum(np.sum(z * z, axis=2).reshape(self.channels, M // PING_BLOCK, PING_BLOCK), axis=2)   # < 2^50
         self.tail = s[:, M:, :].astype(np.int8)
         return np.minimum(S >> self.shift, PING_BAND_MAX_ENERGY)
 
@@ -514,17 +527,13 @@ NOTCH_HALFWIDTH_HZ = 100
 def notch_taps(freqs, halfwidth_hz: int = NOTCH_HALFWIDTH_HZ) -> Tuple[np.ndarray, int]:
     """The default design of the contract for 1 or 2 frequencies (Hz from the channel's offset), from libmsk144host.so
     (csrc/wideband.h notch_design): (int8 [64][2] taps (br, bi), shift)."""
-    L = _host_lib()
     f = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.int32)
     if f.ndim != 1 or np.any(f != np.atleast_1d(freqs)):
         raise ValueError("notch frequencies must be integers")
     taps = np.zeros((NOTCH_TAPS, 2), dtype=np.int8)
     shift = C.c_int32(0)
     why = C.create_string_buffer(256)
-    L.msk144host_wideband_notch_design.restype = C.c_int
-    rc = L.msk144host_wideband_notch_design(f.ctypes.data_as(C.c_void_p), C.c_int32(len(f)), C.c_int32(int(halfwidth_hz)), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why,
-                                            len(why))
-    if rc != 0:
+    if _host_lib().msk144host_wideband_notch_design(f.ctypes.data_as(C.c_void_p), len(f), int(halfwidth_hz), taps.ctypes.data_as(C.c_void_p), C.byref(shift), why, len(why)) != 0:
         raise ValueError(why.value.decode())
     return taps, int(shift.value)
 
@@ -533,12 +542,8 @@ def notch_entry(entry) -> Tuple[np.ndarray, int]:
     """One entry of a notch table as (int8 [64][2] taps, shift): a list of frequencies takes the default design, (taps, shift) is
     checked and zero-padded."""
     if isinstance(entry, tuple) and len(entry) == 2 and np.ndim(entry[0]) == 2:
-        t, shift = np.asarray(entry[0]), int(entry[1])
-        if t.shape[1] != 2 or not 1 <= t.shape[0] <= NOTCH_TAPS or np.any(t != t.astype(np.int8)):
-            raise ValueError("taps must be int8 [k][2] with 1 <= k <= 64")
-        full = np.zeros((NOTCH_TAPS, 2), dtype=np.int8)
-        full[:t.shape[0]] = t
-        return full, shift
+        shift, why = int(entry[1]), "taps must be int8 [k][2] with 1 <= k <= 64"
+        return _fir_taps(entry[0], why, why), shift
     return notch_taps(list(entry))
 
 
@@ -582,15 +587,7 @@ class Notch:
         out = q.astype(np.int8).copy()
         clipped = np.zeros(self.channels, dtype=np.int64)
         for c, (taps, s) in self.table.items():
-            x = np.concatenate([self.tail[c], q[c].astype(np.int8)]).astype(np.int64)
-            z = np.zeros((M, 2), dtype=np.int64)
-            for k in range(NOTCH_TAPS):
-                br, bi = int(taps[k, 0]), int(taps[k, 1])
-                if br == 0 and bi == 0:
-                    continue
-                a, b = x[T - k:T - k + M, 0], x[T - k:T - k + M, 1]
-                z[:, 0] += br * a - bi * b
-                z[:, 1] += br * b + bi * a
+            x, z = _fir_push(self.tail[c], q[c], taps)
             v = ((x[T - NOTCH_DELAY:T - NOTCH_DELAY + M] << s) - z + ((1 << (s - 1)) if s else 0)) >> s
             y = np.clip(v, -128, 127)
             clipped[c] = int(np.count_nonzero(y != v))
