@@ -20,29 +20,21 @@ import pytest
 import wideband_blanker_check as kc
 import wideband_gpu as wg
 import wideband_levels_check as lc
+import wideband_options as wo
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, ESTATE, code_of
 
 pytestmark = pytest.mark.gpu
 
 RATE = 240000
 OFFSETS = kc.EFFECT_OFFSETS
-EINVAL, ESTATE = -1, -4
 
 
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 def all_hops(d):
@@ -60,12 +52,6 @@ def push_and_compare(d, model, parts, what):
         assert np.array_equal(got.reshape(-1), want), f"{what} push {i}: {np.count_nonzero(got.reshape(-1) != want)} components differ"
         assert d.wideband_blanker_stats() == st, f"{what} push {i}"
     return st
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
 
 
 # ---- 1. stream and statistics ----
@@ -153,13 +139,12 @@ def test_without_a_hit_the_hops_are_those_of_a_plain_handle(handles):
 def test_switching(hip, handles):
     a, b = handles(len(OFFSETS))
     parts = kc.edge_pushes(RATE, "cu8", 3, 2, 8, np.random.default_rng(4))
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_blanker) == EINVAL                         # not in wideband mode
+    wo.refuses_outside_wideband_mode(hip, [hip.HipDecoder.set_wideband_blanker])
     for d in (a, b):
         d.set_wideband(RATE, OFFSETS, "cu8")
     for bad in (dict(threshold_q4=15), dict(threshold_q4=65536), dict(pre=-1), dict(pre=4097), dict(post=-1), dict(post=4097)):
         assert code_of(hip, lambda: a.set_wideband_blanker(**bad)) == EINVAL, bad
-    assert code_of(hip, a.wideband_blanker_stats) == ESTATE                                # before any push
+    wo.unreadable(hip, [a.wideband_blanker_stats])                                         # before any push
 
     # set, then switched off before the first push: a handle that never had one
     a.set_wideband_blanker()
@@ -170,14 +155,14 @@ def test_switching(hip, handles):
             d.push_wideband(i % 2, part, first=i == 0)
         plain.append(all_hops(b))
         assert np.array_equal(all_hops(a), plain[i])
-        assert code_of(hip, a.wideband_blanker_stats) == ESTATE and code_of(hip, a.dump_wideband_blanked) == ESTATE
+        wo.unreadable(hip, [a.wideband_blanker_stats, a.dump_wideband_blanked])
 
     # set in mid-stream: the running stream keeps what it started with
     a.push_wideband(0, parts[0], first=True)
     a.set_wideband_blanker()
     a.push_wideband(1, parts[1], first=False)
     assert np.array_equal(all_hops(a), plain[1])
-    assert code_of(hip, a.wideband_blanker_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_blanker_stats])
 
     # ... and the next first push is blanked; the same stream pushed twice gives the same bytes
     runs = []

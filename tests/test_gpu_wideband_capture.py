@@ -31,12 +31,13 @@ import pytest
 import wideband_capture_check as cc
 import wideband_gpu as wg
 import wideband_levels_check as lc
+import wideband_options as wo
 import wideband_pings_check as pc
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, ESTATE, code_of
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -4
 RATIO_Q4 = 22           # 1.375 x the reference: white noise alone puts a block up now and then
 COUNTS = (1, 63, 64, 65, 255, 256, 257, 513, 769)
 
@@ -44,23 +45,8 @@ COUNTS = (1, 63, 64, 65, 255, 256, 257, 513, 769)
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 class Saved:
@@ -193,22 +179,8 @@ def test_overflow_at_the_count(handles):
 
 def test_an_agc_step_in_mid_stream(handles):
     d, _ = handles(len(pc.SCENE_OFFSETS))
-    rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
-    rng = np.random.default_rng(21)
-    gain = pc.burst_gain(rate)
-    sizes = [k // 2 for k in wb.push_sizes_for_rate(6, rate)]
-    x = (rng.standard_normal(2 * sum(sizes), dtype=np.float32) * np.float32(pc.BURST_SIGMA)).view(np.complex64)
-    # a loud tone on channel 1 through the whole of push 2 (hop 3): far above the AGC's window, so the push behind it is quantised
-    # with a lower gain
-    a0 = sizes[0] + sizes[1]
-    n = np.arange(a0, a0 + sizes[2], dtype=np.int64)
-    x[n] += (120.0 / (128.0 * gain) * np.exp(2j * np.pi * (np.mod(int(offsets[1]) * n, rate).astype(np.float64) / rate))).astype(np.complex64)
-    raw = wb.write_samples(x, "cs16")
-    parts, pos = [], 0
-    for k in sizes:
-        parts.append(raw[2 * pos:2 * (pos + k)])
-        pos += k
-    d.set_wideband(rate, offsets, "cs16", gain=gain)
+    parts, gain = wo.loud_push_stream(6)               # a loud tone on channel 1 through the whole of push 2 (hop 3)
+    d.set_wideband(pc.SCENE_RATE, pc.SCENE_OFFSETS, "cs16", gain=gain)
     d.set_wideband_agc()
     d.set_wideband_pings()
     d.set_wideband_capture(1, 2, None, [4])
@@ -322,16 +294,9 @@ def test_max_units_grown_and_shrunk_between_a_push_and_a_read(hip, handles):
 def test_the_same_stream_twice_gives_the_same_bytes(handles):
     d, _ = handles(len(cc.SCENE_OFFSETS))
     scene_setup(d)
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(cc.scene_parts()):
-            d.push_wideband(i % 2, part, first=i == 0)
-            units, data, total = d.wideband_capture()
-            out.append((units.tobytes(), data.tobytes(), total))
-        runs.append(out)
+    again = wo.same_bytes_twice(d, cc.scene_parts(), type(d).wideband_capture)
     d.synchronize()
-    assert runs[0] == runs[1] and sum(t for _, _, t in runs[0]) >= 30
+    assert sum(t for _, _, t in again) >= 30
 
 
 # ---- 6. refusals and order ----
@@ -339,10 +304,8 @@ def test_the_same_stream_twice_gives_the_same_bytes(handles):
 def test_order_and_refusals(hip, handles):
     a, _ = handles(len(cc.SCENE_OFFSETS))
     parts = cc.scene_parts()
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_capture) == EINVAL                       # not in wideband mode
-        assert code_of(hip, lambda: fresh.set_wideband_capture(None)) == EINVAL
-        assert code_of(hip, fresh.wideband_capture) == EINVAL
+    H = hip.HipDecoder
+    wo.refuses_outside_wideband_mode(hip, [H.set_wideband_capture, lambda f: f.set_wideband_capture(None), H.wideband_capture])
     a.set_wideband(cc.SCENE_RATE, cc.SCENE_OFFSETS, "cs16", gain=cc.SCENE_GAIN)
     C = a.channels
     for bad in (dict(pre=2), dict(pre=-1), dict(post=-1), dict(post=17), dict(max_units=0), dict(max_units=16385), dict(max_units=-4), dict(channels=[C]), dict(channels=[-1]),
@@ -351,9 +314,9 @@ def test_order_and_refusals(hip, handles):
     for good in (dict(pre=0, post=0, max_units=1), dict(post=16), dict(max_units=16384), dict(channels=list(range(C))), dict()):
         a.set_wideband_capture(**good)
     a.set_wideband_capture(None)
-    assert code_of(hip, a.wideband_capture) == ESTATE                                   # before any push
+    wo.unreadable(hip, [a.wideband_capture])                                            # before any push
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_capture) == ESTATE                                   # ... and after one made with capture off
+    wo.unreadable(hip, [a.wideband_capture])                                            # ... and after one made with capture off
     # without the detector only listed channels are kept; `set` takes effect at the next push and not before
     a.set_wideband_capture(1, 1, None, [2])
     assert code_of(hip, a.wideband_capture) == ESTATE
@@ -377,13 +340,13 @@ def test_order_and_refusals(hip, handles):
     assert len(units) == 0 and data.shape == (0, wb.HOP_OUT, 2) and total == 0
     # switched off: there is nothing to read any more, nor after the next push; msk144_set_wideband switches it off as well
     a.set_wideband_capture(None)
-    assert code_of(hip, a.wideband_capture) == ESTATE
+    wo.unreadable(hip, [a.wideband_capture])
     a.push_wideband(0, parts[4], first=False)
-    assert code_of(hip, a.wideband_capture) == ESTATE
+    wo.unreadable(hip, [a.wideband_capture])
     a.set_wideband_capture()
     a.set_wideband(cc.SCENE_RATE, cc.SCENE_OFFSETS, "cs16", gain=cc.SCENE_GAIN)
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_capture) == ESTATE
+    wo.unreadable(hip, [a.wideband_capture])
     a.synchronize()
 
 
@@ -395,12 +358,7 @@ def test_it_changes_nothing(handles, name):
     rate, offsets, K = shape["rate"], shape["offsets"], shape["K"]
     a, b = handles(len(offsets))
     if name == "rat":
-        raw, planted = wg.plant_scene(wb.FIRST_OUT + 2 * wb.HOP_OUT, rate, offsets, [3, 17, 30], np.random.default_rng(55))
-        parts, pos = [], 0
-        for k in wb.push_sizes_for_rate(3, rate):
-            parts.append(raw[pos:pos + k])
-            pos += k
-        fmt, gain = "cu8", 100.0
+        parts, planted, fmt, gain = wo.rat_scene()
     else:
         fmt, gain = "cs16", pc.burst_gain(rate)
         parts = pc.burst_parts(rate, tuple(int(f) for f in offsets), fmt)[:3]
@@ -409,22 +367,13 @@ def test_it_changes_nothing(handles, name):
         d.set_wideband_pings(ratio_q4=RATIO_Q4)
         d.set_wideband_waterfall()
     a.set_wideband_capture(1, 1, None, spread(len(offsets)))
-    seen = []
-    for d in (a, b):
-        out = []
-        for i, part in enumerate(parts):
-            d.push_wideband(i % 2, part, first=i == 0)
-            hops = wg.dump_hops(d, range(d.channels))
-            out.append((hops, d.wideband_clip_count(), d.wideband_levels(), d.wideband_pings(), d.wideband_ping_blocks(), d.wideband_waterfall(), wg._decode(d, i % 2)))
-        seen.append(out)
+    H = type(a)
+    seen = wo.leaves_unchanged(a, b, parts, reads=(H.wideband_pings, H.wideband_ping_blocks, H.wideband_waterfall), decode=True)
     assert a.wideband_capture()[2] > 0
-    for x, y in zip(*seen):
-        assert x[0].any() and np.array_equal(x[0], y[0]) and x[1] == y[1]
-        for u, v in zip(x[2:], y[2:]):
-            assert u.tobytes() == v.tobytes()
-        assert x[3]["up_mask"].any() or x[4].any()
+    for s in seen:
+        assert s["reads"][0]["up_mask"].any() or s["reads"][1].any()
     if name == "rat":
-        assert sum(len(o[6]) for o in seen[0]) > 0 and planted     # the scene decodes to something
+        assert sum(len(s["records"]) for s in seen) > 0 and planted     # the scene decodes to something
     for d in (a, b):
         d.set_wideband_waterfall(None)
         d.set_wideband_pings(None)

@@ -22,13 +22,15 @@ import re
 import numpy as np
 import pytest
 
+import wideband_check as wc
 import wideband_gate_check as gc
 import wideband_gpu as wg
+import wideband_options as wo
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, code_of
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -4
 CFG = dict(center=0.0, width=20.0, step=2.0, depth=3, nbadsync_threshold=1, read_mode=2)
 PROGRAM_ARGS = ["--search-width=20", "--search-step=2", "--scan-depth=3", "--nbadsync-threshold=1"]
 RATIO_Q4 = 21           # 1.3125 x the reference: on white noise alone about half of the hops have an up block
@@ -40,22 +42,8 @@ SCENE_C, SCENE_HOPS = 16, 9
 @pytest.fixture(scope="module")
 def handles(hip):
     """One handle per channel count (two of the scene's), made on first use and kept for the module."""
-    made = {}
-
-    def get(C, k=0):
-        if (C, k) not in made:
-            made[(C, k)] = hip.HipDecoder(channels=C, **CFG)
-        return made[(C, k)]
-
-    yield get
-    for d in made.values():
-        d.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
+    with wo.handle_cache(lambda key: hip.HipDecoder(channels=key[0], **CFG)) as get:
+        yield lambda C, k=0: get((C, k))
 
 
 def noise_offsets(C):
@@ -78,12 +66,7 @@ def noise_parts():
         for f, m0, m1 in ((-111888, 3000, 4500), (0, 7000, 9800), (60032, 12000, 12400)):
             sl = slice(m0 * 20, m1 * 20)
             x[sl] += (40.0 / unit) * np.exp(2j * np.pi * f * n[sl] / NOISE_RATE)
-        raw = wb.write_samples(x, "cs16")
-        out, pos = [], 0
-        for k in wb.push_sizes_for_rate(NOISE_PUSHES, NOISE_RATE):
-            out.append(raw[pos:pos + k])
-            pos += k
-        _noise["parts"] = out
+        _noise["parts"] = wc.split_pushes(wb.write_samples(x, "cs16"), NOISE_RATE, NOISE_PUSHES)
     return _noise["parts"]
 
 
@@ -249,19 +232,17 @@ def test_switching_off_and_refusals(hip, handles):
     assert set(gc.SCENE_ALWAYS) <= set(lst) and len(lst) < SCENE_C and len(before[0]) < SCENE_C
     decode_fetch(a, 1), decode_fetch(b, 1)
     a.set_wideband_gate(None)
-    assert code_of(hip, a.wideband_gate) == ESTATE
+    wo.unreadable(hip, [a.wideband_gate])
     for i, part in enumerate(parts[4:6]):
         for d in (a, b):
             d.push_wideband(i % 2, part, first=False)
-        assert code_of(hip, a.wideband_gate) == ESTATE
+        wo.unreadable(hip, [a.wideband_gate])
         (ra, sa), (rb, sb) = decode_fetch(a, i % 2), decode_fetch(b, i % 2)
         assert ra.tobytes() == rb.tobytes() and sa.tobytes() == sb.tobytes(), f"push {4 + i} after the gate was switched off"
     # set again: the read entry answers ESTATE until the next push made with it
     a.set_wideband_gate()
-    assert code_of(hip, a.wideband_gate) == ESTATE
-    with hip.HipDecoder(channels=1, **CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_gate) == EINVAL
-        assert code_of(hip, fresh.wideband_gate) == EINVAL
+    wo.unreadable(hip, [a.wideband_gate])
+    wo.refuses_outside_wideband_mode(hip, [hip.HipDecoder.set_wideband_gate, hip.HipDecoder.wideband_gate])
 
 
 # ---- 6. the program ----

@@ -25,22 +25,13 @@ import pytest
 import wideband_gpu as wg
 import wideband_levels_check as lc
 import wideband_notch_check as nc
+import wideband_options as wo
 import wideband_pingband_check as bc
 import wideband_pings_check as pc
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, SMALL, Plain, code_of, shape_of
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ESTATE = -1, -4
-SMALL = {
-    "one": dict(rate=240000, K=16, offsets=np.array([12345], dtype=np.int32)),
-    "five": dict(rate=240000, K=16, offsets=pc.SCENE_OFFSETS),
-}
-
-
-def shape_of(name):
-    return lc.SHAPES[name] if name in lc.SHAPES else SMALL[name]
-
 
 def entry(kind: int, c: int):
     """The three kinds of entry: the default design (the bursts sit on the channel's offset: 0 Hz is among its carriers), random
@@ -64,39 +55,14 @@ def tables(C):
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
-
-
-class Plain:
-    """Stands for handle B where its hops are already known: the raw hops of one push."""
-
-    def __init__(self, hops):
-        self.hops, self.channels = hops, hops.shape[0]
-
-    def dump_wideband_hop(self, c):
-        return self.hops[c]
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 # ---- 1. shapes ----
 
 @pytest.mark.parametrize("fmt", ["cu8", "cs16"])
-@pytest.mark.parametrize("name", list(lc.SHAPES) + list(SMALL))
+@pytest.mark.parametrize("name", wo.SHAPE_NAMES)
 def test_shapes_against_the_model(handles, name, fmt):
     shape = shape_of(name)
     rate, offsets = shape["rate"], shape["offsets"]
@@ -141,23 +107,21 @@ def test_pure_delay_and_all_zeros(handles):
     a.set_wideband_notch(table)
     model = wb.Notch(C_, table)
     stream = [np.zeros((C_, 31, 2), dtype=np.int8)]
-    pos = 0
     for i, part in enumerate(parts):
         for d in (a, b):
             d.push_wideband(i % 2, part, first=i == 0)
         got, raw, k = nc.assert_push(a, b, model, f"identities push {i}")
         stream.append(raw)
         whole = np.concatenate(stream, axis=1)
-        M = raw.shape[1]
+        delayed = whole[:, whole.shape[1] - raw.shape[1] - 31:whole.shape[1] - 31]
         assert raw.any() and not k.any()
         for c in range(C_):
             if c == 1:
                 assert np.array_equal(got[c], raw[c])
             elif c % 3:
-                assert np.array_equal(got[c], whole[c, pos:pos + M]), f"push {i} ch={c}: not the input delayed by 31 samples"
+                assert np.array_equal(got[c], delayed[c]), f"push {i} ch={c}: not the input delayed by 31 samples"
             else:
                 assert not got[c].any(), f"push {i} ch={c}: not all zero"
-        pos += M
     a.set_wideband_notch(None)
     a.synchronize()
     b.synchronize()
@@ -255,10 +219,7 @@ def test_order_and_refusals(hip, handles):
         return L.msk144_set_wideband_notch(d.h, ch, len(channels) if count is None else count, params)
 
     good = (hip.WidebandNotchParams * C_)()
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, lambda: fresh.set_wideband_notch({0: [0]})) == EINVAL          # not in wideband mode
-        assert code_of(hip, lambda: fresh.set_wideband_notch(None)) == EINVAL
-        assert code_of(hip, fresh.wideband_notch_stats) == EINVAL
+    wo.refuses_outside_wideband_mode(hip, [lambda f: f.set_wideband_notch({0: [0]}), lambda f: f.set_wideband_notch(None), hip.HipDecoder.wideband_notch_stats])
     for d in (a, b):
         d.set_wideband(rate, offsets, "cs16", gain=gain)
     assert raw_set(a, [0, 0], good) == EINVAL and b"twice" in L.msk144_last_error(a.h)
@@ -270,16 +231,16 @@ def test_order_and_refusals(hip, handles):
     for ok in (0, 15):
         a.set_wideband_notch({2: (np.full((64, 2), -128, dtype=np.int8), ok)})
     # ESTATE: before any push, before a push with the notch on, and again after a new table
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
     a.set_wideband_notch(None)
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
     b.push_wideband(0, parts[0], first=True)
 
     # set in mid-stream: the table's channels start from silence on the next push
     t0 = {0: [300], 3: [0, 1500]}
     a.set_wideband_notch(t0)
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
     model = wb.Notch(C_, t0)
     for d in (a, b):
         d.push_wideband(1, parts[1], first=False)
@@ -288,7 +249,7 @@ def test_order_and_refusals(hip, handles):
     # 0 unchanged: keeps its tail; 3 changed, 1 new: zero tails.  A filter that had cleared channel 0's tail would differ
     t1 = {0: wb.notch_taps([300]), 1: [0], 3: [0, 1600]}
     a.set_wideband_notch(t1)
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
     model.set(t1)
     for d in (a, b):
         d.push_wideband(0, parts[2], first=False)
@@ -300,31 +261,23 @@ def test_order_and_refusals(hip, handles):
     for d in (a, b):
         d.push_wideband(1, parts[3], first=False)
     assert np.array_equal(wg.dump_hops(a, range(C_)), wg.dump_hops(b, range(C_)))
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
 
     # the same stream pushed twice gives the same bytes: a first push zeroes every tail
     a.set_wideband_notch(t1)
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(parts):
-            a.push_wideband(i % 2, part, first=i == 0)
-            out.append((wg.dump_hops(a, range(C_)), a.wideband_notch_stats()))
-        runs.append(out)
-    for (h0, s0), (h1, s1) in zip(*runs):
-        assert h0.tobytes() == h1.tobytes() and s0.tobytes() == s1.tobytes() and h0.any()
+    again = wo.same_bytes_twice(a, parts, lambda d: (wg.dump_hops(d, range(C_)), d.wideband_notch_stats()))
     model = wb.Notch(C_, t1)
     for i, part in enumerate(parts):
         b.push_wideband(i % 2, part, first=i == 0)
         want, _ = model.push(wg.dump_hops(b, range(C_)))
-        assert np.array_equal(want, runs[1][i][0]), f"second run, push {i}"
+        assert np.array_equal(want, again[i][0]), f"second run, push {i}"
 
     # msk144_set_wideband switches it off
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     a.push_wideband(0, parts[0], first=True)
     b.push_wideband(0, parts[0], first=True)
     assert np.array_equal(wg.dump_hops(a, range(C_)), wg.dump_hops(b, range(C_)))
-    assert code_of(hip, a.wideband_notch_stats) == ESTATE
+    wo.unreadable(hip, [a.wideband_notch_stats])
     a.synchronize()
     b.synchronize()
 

@@ -19,18 +19,15 @@ import pytest
 
 import wideband_gpu as wg
 import wideband_levels_check as lc
+import wideband_options as wo
 import wideband_pingband_check as bc
 import wideband_pings_check as pc
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, code_of, shape_of
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -4
 CLAMP = (1 << 22) - 1
-SMALL = {
-    "one": dict(rate=240000, K=16, offsets=np.array([12345], dtype=np.int32)),
-    "five": dict(rate=240000, K=16, offsets=pc.SCENE_OFFSETS),
-}
 
 
 def random_band():
@@ -52,34 +49,15 @@ def delta(k, re=1, im=0):
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
-
-
-def shape_of(name):
-    return lc.SHAPES[name] if name in lc.SHAPES else SMALL[name]
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 # ---- 1. shapes ----
 
 @pytest.mark.parametrize("which", list(BANDS))
 @pytest.mark.parametrize("fmt", ["cu8", "cs16"])
-@pytest.mark.parametrize("name", list(lc.SHAPES) + list(SMALL))
+@pytest.mark.parametrize("name", wo.SHAPE_NAMES)
 def test_shapes_against_the_models(handles, name, fmt, which):
     shape = shape_of(name)
     rate, offsets = shape["rate"], shape["offsets"]
@@ -171,26 +149,17 @@ def test_all_zero_and_all_clipped_hops(handles):
 
 def test_an_agc_step_restarts_the_history_and_keeps_the_tail(handles):
     d, _ = handles(len(pc.SCENE_OFFSETS))
-    rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
-    rng = np.random.default_rng(21)
-    gain = pc.burst_gain(rate)
-    sizes = [k // 2 for k in wb.push_sizes_for_rate(5, rate)]
-    x = (rng.standard_normal(2 * sum(sizes), dtype=np.float32) * np.float32(pc.BURST_SIGMA)).view(np.complex64)
-    a0 = sizes[0] + sizes[1]
-    n = np.arange(a0, a0 + sizes[2], dtype=np.int64)   # a loud tone on channel 1 through the whole of push 2
-    x[n] += (120.0 / (128.0 * gain) * np.exp(2j * np.pi * (np.mod(int(offsets[1]) * n, rate).astype(np.float64) / rate))).astype(np.complex64)
-    raw = wb.write_samples(x, "cs16")
+    parts, gain = wo.loud_push_stream(5)               # a loud tone on channel 1 through the whole of push 2
     taps, shift = wb.ping_band_taps()
-    d.set_wideband(rate, offsets, "cs16", gain=gain)
+    d.set_wideband(pc.SCENE_RATE, pc.SCENE_OFFSETS, "cs16", gain=gain)
     d.set_wideband_agc()
     d.set_wideband_pings()
     d.set_wideband_ping_band()
     band, det = wb.PingBand(d.channels, taps, shift), wb.Pings(d.channels)
-    hist, exps, pos = [], [], 0
-    for i, k in enumerate(sizes):
+    hist, exps = [], []
+    for i, part in enumerate(parts):
         tail = band.tail.copy()
-        d.push_wideband(i % 2, raw[2 * pos:2 * (pos + k)], first=i == 0)
-        pos += k
+        d.push_wideband(i % 2, part, first=i == 0)
         rec, Ef, hops = bc.assert_push(d, band, det, f"AGC push {i}")
         hist.append([int(v) for v in rec["history"]])
         exps.append([int(v) for v in d.wideband_levels()["exponent"]])
@@ -212,30 +181,16 @@ def test_it_changes_nothing(handles):
     shape = lc.SHAPES["rat"]
     rate, offsets, K = shape["rate"], shape["offsets"], shape["K"]
     a, b = handles(len(offsets))
-    raw, planted = wg.plant_scene(wb.FIRST_OUT + 2 * wb.HOP_OUT, rate, offsets, [3, 17, 30], np.random.default_rng(55))
-    parts, pos = [], 0
-    for k in wb.push_sizes_for_rate(3, rate):
-        parts.append(raw[pos:pos + k])
-        pos += k
+    parts, planted, fmt, gain = wo.rat_scene()
     for d in (a, b):
-        d.set_wideband(rate, offsets, "cu8", taps_per_phase=K, gain=100.0)
+        d.set_wideband(rate, offsets, fmt, taps_per_phase=K, gain=gain)
         d.set_wideband_pings()
         d.set_wideband_waterfall()
     a.set_wideband_ping_band()
-    seen = []
-    for d in (a, b):
-        out = []
-        for i, part in enumerate(parts):
-            d.push_wideband(i % 2, part, first=i == 0)
-            hops = wg.dump_hops(d, range(d.channels))
-            rows = d.wideband_waterfall(17)
-            out.append((hops, d.wideband_clip_count(), d.wideband_levels(), rows, wg._decode(d, i % 2)))
-        seen.append(out)
+    seen = wo.leaves_unchanged(a, b, parts, reads=(lambda d: d.wideband_waterfall(17),), decode=True)
     assert not np.array_equal(a.wideband_ping_blocks(), b.wideband_ping_blocks())     # the band was on
-    for (h0, c0, l0, w0, r0), (h1, c1, l1, w1, r1) in zip(*seen):
-        assert h0.any() and np.array_equal(h0, h1) and c0 == c1 and np.array_equal(l0, l1)
-        assert w0.any() and w0.tobytes() == w1.tobytes() and r0.tobytes() == r1.tobytes()
-    assert sum(len(r) for _, _, _, _, r in seen[0]) > 0 and planted     # the scene decodes to something
+    assert all(s["reads"][0].any() for s in seen)
+    assert sum(len(s["records"]) for s in seen) > 0 and planted     # the scene decodes to something
     for d in (a, b):
         d.set_wideband_waterfall(None)
 
@@ -249,9 +204,7 @@ def test_order_and_refusals(hip, handles):
     gain = pc.burst_gain(rate)
     taps, shift = wb.ping_band_taps()
     C_ = len(offsets)
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_ping_band) == EINVAL                       # not in wideband mode
-        assert code_of(hip, lambda: fresh.set_wideband_ping_band(None)) == EINVAL
+    wo.refuses_outside_wideband_mode(hip, [hip.HipDecoder.set_wideband_ping_band, lambda f: f.set_wideband_ping_band(None)])
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     for bad in (-1, 41, 1 << 20, -(1 << 31)):
         assert code_of(hip, lambda: a.set_wideband_ping_band(taps=taps, shift=bad)) == EINVAL, bad
@@ -262,7 +215,7 @@ def test_order_and_refusals(hip, handles):
     # valid with the detector off, and acts only once it is on: the tail has not moved with the first push, and is zero anyway
     a.set_wideband_ping_band()
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_pings) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings])
     a.set_wideband_pings(ratio_q4=wb.PING_BAND_RATIO_Q4)
     band, det = wb.PingBand(C_, taps, shift), wb.Pings(C_, ratio_q4=wb.PING_BAND_RATIO_Q4)
     for i in (1, 2):
@@ -279,7 +232,7 @@ def test_order_and_refusals(hip, handles):
     # msk144_set_wideband_pings(h, NULL) leaves it configured; the detector's return restarts both
     a.set_wideband_pings(None)
     a.push_wideband(0, parts[1], first=False)
-    assert code_of(hip, a.wideband_pings) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings])
     a.set_wideband_pings(ratio_q4=wb.PING_BAND_RATIO_Q4)
     band.reset()
     det.reset()
@@ -295,16 +248,8 @@ def test_order_and_refusals(hip, handles):
 
     # the same stream pushed twice gives the same bytes
     a.set_wideband_ping_band()
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(parts):
-            a.push_wideband(i % 2, part, first=i == 0)
-            out.append((a.wideband_pings(), a.wideband_ping_blocks()))
-        runs.append(out)
-    for (r0, e0), (r1, e1) in zip(*runs):
-        assert r0.tobytes() == r1.tobytes() and np.array_equal(e0, e1) and e0.any()
-    assert [int(r["history"][0]) for r, _ in runs[1]] == [0, 1, 2, 3]
+    again = wo.same_bytes_twice(a, parts, lambda d: (d.wideband_pings(), d.wideband_ping_blocks()))
+    assert [int(r["history"][0]) for r, _ in again] == [0, 1, 2, 3]
 
     # msk144_set_wideband switches it off
     a.set_wideband(rate, offsets, "cs16", gain=gain)

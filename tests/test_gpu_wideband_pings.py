@@ -18,48 +18,25 @@ import pytest
 
 import wideband_gpu as wg
 import wideband_levels_check as lc
+import wideband_options as wo
 import wideband_pings_check as pc
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, ESTATE, code_of, shape_of
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ESTATE = -1, -4
-SMALL = {
-    "one": dict(rate=240000, K=16, offsets=np.array([12345], dtype=np.int32)),
-    "five": dict(rate=240000, K=16, offsets=pc.SCENE_OFFSETS),
-}
 
 
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
-
-
-def shape_of(name):
-    return lc.SHAPES[name] if name in lc.SHAPES else SMALL[name]
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 # ---- 1. shapes ----
 
 @pytest.mark.parametrize("fmt", ["cu8", "cs16"])
-@pytest.mark.parametrize("name", list(lc.SHAPES) + list(SMALL))
+@pytest.mark.parametrize("name", wo.SHAPE_NAMES)
 def test_shapes_against_the_model(handles, name, fmt):
     shape = shape_of(name)
     rate, offsets = shape["rate"], shape["offsets"]
@@ -116,25 +93,14 @@ def test_all_zero_and_all_clipped_hops(handles):
 
 def test_an_agc_step_restarts_the_history(handles):
     d, _ = handles(len(pc.SCENE_OFFSETS))
-    rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
-    P, Q = wb.rate_ratio(rate)
-    rng = np.random.default_rng(21)
-    gain = pc.burst_gain(rate)                         # noise at about 15 LSB rms: inside the AGC's window of 8 .. 32
-    sizes = [k // 2 for k in wb.push_sizes_for_rate(6, rate)]
-    x = (rng.standard_normal(2 * sum(sizes), dtype=np.float32) * np.float32(pc.BURST_SIGMA)).view(np.complex64)
-    # a loud tone on channel 1 through the whole of push 2: some 120 LSB of amplitude, far above the window and clipping
-    a0 = sizes[0] + sizes[1]
-    n = np.arange(a0, a0 + sizes[2], dtype=np.int64)
-    x[n] += (120.0 / (128.0 * gain) * np.exp(2j * np.pi * (np.mod(int(offsets[1]) * n, rate).astype(np.float64) / rate))).astype(np.complex64)
-    raw = wb.write_samples(x, "cs16")
-    d.set_wideband(rate, offsets, "cs16", gain=gain)
+    parts, gain = wo.loud_push_stream(6)               # a loud tone on channel 1 through the whole of push 2
+    d.set_wideband(pc.SCENE_RATE, pc.SCENE_OFFSETS, "cs16", gain=gain)
     d.set_wideband_agc()
     d.set_wideband_pings()
     det = wb.Pings(d.channels)
-    hist, exps, pos = [], [], 0
-    for i, k in enumerate(sizes):
-        d.push_wideband(i % 2, raw[2 * pos:2 * (pos + k)], first=i == 0)
-        pos += k
+    hist, exps = [], []
+    for i, part in enumerate(parts):
+        d.push_wideband(i % 2, part, first=i == 0)
         rec, _ = pc.assert_push(d, det, f"AGC push {i}")
         hist.append([int(v) for v in rec["history"]])
         exps.append([int(v) for v in d.wideband_levels()["exponent"]])
@@ -157,34 +123,17 @@ def test_it_changes_nothing(handles, name):
     rate, offsets, K = shape["rate"], shape["offsets"], shape["K"]
     a, b = handles(len(offsets))
     if name == "rat":
-        raw, planted = wg.plant_scene(wb.FIRST_OUT + 2 * wb.HOP_OUT, rate, offsets, [3, 17, 30], np.random.default_rng(55))
-        parts, pos = [], 0
-        for k in wb.push_sizes_for_rate(3, rate):
-            parts.append(raw[pos:pos + k])
-            pos += k
-        fmt, gain = "cu8", 100.0
+        parts, planted, fmt, gain = wo.rat_scene()
     else:
         fmt, gain = "cs16", pc.burst_gain(rate)
         parts = pc.burst_parts(rate, tuple(int(f) for f in offsets), fmt)[:2]
     for d in (a, b):
         d.set_wideband(rate, offsets, fmt, taps_per_phase=K, gain=gain)
     a.set_wideband_pings()
-    seen = []
-    for d in (a, b):
-        out = []
-        for i, part in enumerate(parts):
-            d.push_wideband(i % 2, part, first=i == 0)
-            hops = wg.dump_hops(d, range(d.channels))
-            rec = wg._decode(d, i % 2) if name == "rat" else None
-            out.append((hops, d.wideband_clip_count(), d.wideband_levels(), rec))
-        seen.append(out)
+    seen = wo.leaves_unchanged(a, b, parts, decode=name == "rat")
     assert list(a.wideband_pings()["blocks"]) == [27] * len(offsets)
-    for (h0, c0, l0, r0), (h1, c1, l1, r1) in zip(*seen):
-        assert h0.any() and np.array_equal(h0, h1) and c0 == c1 and np.array_equal(l0, l1)
-        if name == "rat":
-            assert r0.tobytes() == r1.tobytes()
     if name == "rat":
-        assert sum(len(r) for _, _, _, r in seen[0]) > 0 and planted     # the scene decodes to something
+        assert sum(len(s["records"]) for s in seen) > 0 and planted     # the scene decodes to something
 
 
 # ---- 5. switching ----
@@ -194,22 +143,17 @@ def test_order_and_refusals(hip, handles):
     rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
     parts = pc.burst_parts(rate, tuple(int(f) for f in offsets), "cs16")
     gain = pc.burst_gain(rate)
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_pings) == EINVAL                         # not in wideband mode
-        assert code_of(hip, lambda: fresh.set_wideband_pings(None)) == EINVAL
-        assert code_of(hip, fresh.wideband_pings) == EINVAL
-        assert code_of(hip, lambda: fresh.wideband_ping_blocks(0)) == EINVAL
+    H = hip.HipDecoder
+    wo.refuses_outside_wideband_mode(hip, [H.set_wideband_pings, lambda f: f.set_wideband_pings(None), H.wideband_pings, lambda f: f.wideband_ping_blocks(0)])
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     for bad in (dict(ratio_q4=15), dict(ratio_q4=65536), dict(ratio_q4=-32), dict(memory=-1), dict(memory=17), dict(min_ref=0), dict(min_ref=(1 << 22) + 1), dict(min_ref=-96)):
         assert code_of(hip, lambda: a.set_wideband_pings(**bad)) == EINVAL, bad
     for good in (dict(ratio_q4=16), dict(ratio_q4=65535), dict(memory=0), dict(memory=16), dict(min_ref=1), dict(min_ref=1 << 22)):
         a.set_wideband_pings(**good)
     a.set_wideband_pings(None)
-    assert code_of(hip, a.wideband_pings) == ESTATE                                     # before any push
-    assert code_of(hip, a.wideband_ping_blocks) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings, a.wideband_ping_blocks])                      # before any push
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_pings) == ESTATE                                     # ... and after one made with the detector off
-    assert code_of(hip, lambda: a.wideband_ping_blocks(0)) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings, lambda: a.wideband_ping_blocks(0)])           # ... and after one made with the detector off
 
     # `set` in mid-stream: the next push has records, with history 0; a channel out of range is refused
     a.set_wideband_pings(ratio_q4=24, memory=3)
@@ -230,25 +174,17 @@ def test_order_and_refusals(hip, handles):
     assert list(rec["history"]) == [0] * a.channels
 
     # the same stream pushed twice gives the same bytes: a first push clears the history
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(parts):
-            a.push_wideband(i % 2, part, first=i == 0)
-            out.append((a.wideband_pings(), a.wideband_ping_blocks()))
-        runs.append(out)
-    for (r0, e0), (r1, e1) in zip(*runs):
-        assert r0.tobytes() == r1.tobytes() and np.array_equal(e0, e1) and e0.any()
-    assert [int(r["history"][0]) for r, _ in runs[1]] == [0, 1, 2, 3]
+    again = wo.same_bytes_twice(a, parts, lambda d: (d.wideband_pings(), d.wideband_ping_blocks()))
+    assert [int(r["history"][0]) for r, _ in again] == [0, 1, 2, 3]
 
     # switched off: from the next push on there is nothing to read; msk144_set_wideband switches it off as well
     a.set_wideband_pings(None)
     a.push_wideband(0, parts[1], first=False)
-    assert code_of(hip, a.wideband_pings) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings])
     a.set_wideband_pings()
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_pings) == ESTATE
+    wo.unreadable(hip, [a.wideband_pings])
     a.synchronize()
 
 

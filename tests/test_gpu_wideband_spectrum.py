@@ -23,38 +23,24 @@ of wideband_spectrum_check.py: noise, a full-scale tone on a bin centre, a tone 
 import numpy as np
 import pytest
 
-import wideband_gpu as wg
+import wideband_check as wc
 import wideband_levels_check as lc
+import wideband_options as wo
 import wideband_spectrum_check as sc
 from msk144cudecoder_amd import wideband as wb
+from wideband_options import EINVAL, code_of
 
 pytestmark = pytest.mark.gpu
 
 RATE = 240000
 OFFSETS = np.array([-114000, -30000, 0, 12345, 114000], dtype=np.int32)
-EINVAL, ESTATE = -1, -4
 
 
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 def push_and_compare(d, model, parts, what):
@@ -134,7 +120,7 @@ def blanker_pushes():
     at = np.cumsum([0] + sizes[:-1]) + np.array([(k // 2) // 2048 * 2048 + 1152 for k in sizes])
     x[at] = 1.0 + 1.0j
     raw = wb.write_samples(x, "cu8")
-    return [raw[2 * a:2 * (a + k)] for a, k in zip(np.cumsum([0] + sizes[:-1]), sizes)]
+    return wc.split_pushes(raw, RATE, 3)
 
 
 @pytest.mark.parametrize("B", [256, 2048])
@@ -173,33 +159,16 @@ def test_it_changes_nothing(handles, name):
     rate, offsets, K = shape["rate"], shape["offsets"], shape["K"]
     a, b = handles(len(offsets))
     if name == "rat":
-        raw, planted = wg.plant_scene(wb.FIRST_OUT + 2 * wb.HOP_OUT, rate, offsets, [3, 17, 30], np.random.default_rng(55))
-        parts, pos = [], 0
-        for k in wb.push_sizes_for_rate(3, rate):
-            parts.append(raw[pos:pos + k])
-            pos += k
-        fmt, gain = "cu8", 100.0
+        parts, planted, fmt, gain = wo.rat_scene()
     else:
         parts, fmt, gain = sc.pushes(rate, "cs16", 2), "cs16", 4.0
     for d in (a, b):
         d.set_wideband(rate, offsets, fmt, taps_per_phase=K, gain=gain)
     a.set_wideband_spectrum(1024)
-    seen = []
-    for d in (a, b):
-        out = []
-        for i, part in enumerate(parts):
-            d.push_wideband(i % 2, part, first=i == 0)
-            hops = wg.dump_hops(d, range(d.channels))
-            rec = wg._decode(d, i % 2) if name == "rat" else None
-            out.append((hops, d.wideband_clip_count(), d.wideband_levels(), rec))
-        seen.append(out)
+    seen = wo.leaves_unchanged(a, b, parts, decode=name == "rat")
     assert a.wideband_spectrum()[1] == len(parts[-1]) // 2 // 1024
-    for (h0, c0, l0, r0), (h1, c1, l1, r1) in zip(*seen):
-        assert h0.any() and np.array_equal(h0, h1) and c0 == c1 and np.array_equal(l0, l1)
-        if name == "rat":
-            assert r0.tobytes() == r1.tobytes()
     if name == "rat":
-        assert sum(len(r) for _, _, _, r in seen[0]) > 0 and planted     # the scene decodes to something
+        assert sum(len(s["records"]) for s in seen) > 0 and planted     # the scene decodes to something
 
 
 # ---- 6. order ----
@@ -207,9 +176,7 @@ def test_it_changes_nothing(handles, name):
 def test_order_and_refusals(hip, handles):
     a, _ = handles(len(OFFSETS))
     parts = sc.pushes(RATE, "cs8", 3)
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_spectrum) == EINVAL                      # not in wideband mode
-        assert code_of(hip, fresh.wideband_spectrum) == EINVAL
+    wo.refuses_outside_wideband_mode(hip, [hip.HipDecoder.set_wideband_spectrum, hip.HipDecoder.wideband_spectrum])
     a.set_wideband(RATE, OFFSETS, "cs8")
     for bad in (0, 128, 255, 300, 1000, 16384, -1024):
         assert code_of(hip, lambda: a.set_wideband_spectrum(bad)) == EINVAL, bad
@@ -217,27 +184,19 @@ def test_order_and_refusals(hip, handles):
         w = np.ones(256)
         w[200] = bad
         assert code_of(hip, lambda: a.set_wideband_spectrum(256, w)) == EINVAL, bad
-    assert code_of(hip, a.wideband_spectrum) == ESTATE                                  # before any push
+    wo.unreadable(hip, [a.wideband_spectrum])                                           # before any push
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_spectrum) == ESTATE                                  # ... and after one made without the spectrum
+    wo.unreadable(hip, [a.wideband_spectrum])                                           # ... and after one made without the spectrum
 
     # the same stream pushed twice gives the same bytes
     a.set_wideband_spectrum(512)
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(parts):
-            a.push_wideband(i % 2, part, first=i == 0)
-            out.append(a.wideband_spectrum())
-        runs.append(out)
-    for (p0, s0), (p1, s1) in zip(*runs):
-        assert s0 == s1 and p0.tobytes() == p1.tobytes() and p0.any()
+    last = wo.same_bytes_twice(a, parts, hip.HipDecoder.wideband_spectrum)[2]
 
     # `set` between pushes: the last push's spectrum stays readable, the next push has the new size and window
     window = sc.random_window(2048, 3)
     a.set_wideband_spectrum(2048, window)
     p, s = a.wideband_spectrum()
-    assert s == runs[0][2][1] and p.tobytes() == runs[0][2][0].tobytes()
+    assert s == last[1] and p.tobytes() == last[0].tobytes()
     a.push_wideband(1, parts[1], first=False)
     want, segments = wb.Spectrum("cs8", 2048, window).push(parts[1])
     got, got_segments = a.wideband_spectrum()
@@ -247,7 +206,7 @@ def test_order_and_refusals(hip, handles):
     # switched off: from the next push on there is nothing to read; on again: there is
     a.set_wideband_spectrum(None)
     a.push_wideband(0, parts[2], first=False)
-    assert code_of(hip, a.wideband_spectrum) == ESTATE
+    wo.unreadable(hip, [a.wideband_spectrum])
     a.set_wideband_spectrum(256)
     a.push_wideband(1, parts[2], first=False)
     sc.assert_within(a.wideband_spectrum()[0], wb.Spectrum("cs8", 256).push(parts[2])[0], sc.U, "switched on again")
@@ -255,4 +214,4 @@ def test_order_and_refusals(hip, handles):
     # msk144_set_wideband switches the spectrum off
     a.set_wideband(RATE, OFFSETS, "cs8")
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_spectrum) == ESTATE
+    wo.unreadable(hip, [a.wideband_spectrum])

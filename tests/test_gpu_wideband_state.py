@@ -14,10 +14,9 @@ import pytest
 
 import wideband_check as wc
 import wideband_gpu as wg
+from wideband_options import EINVAL, ESTATE, OK
 
 pytestmark = pytest.mark.gpu
-
-OK, EINVAL, ESTATE = 0, -1, -4
 
 
 # ---- 1. the state table ----
@@ -48,6 +47,8 @@ TABLE = {
     "wideband_waterfall": (_mode("wideband_waterfall"), NO_PUSH, NO_WATERFALL, DONE),
     "wideband_waterfall_sums": (_mode("wideband_waterfall_sums"), NO_PUSH, NO_WATERFALL, DONE),
     "wideband_capture": (_mode("wideband_capture"), NO_PUSH, (ESTATE, "no wideband push has been made with capture on since it was last set"), DONE),
+    "wideband_notch_stats": (_mode("wideband_notch_stats"), NO_PUSH, (ESTATE, "no wideband push has been made with the notch on since it was last set"), DONE),
+    "wideband_gate": (_mode("wideband_gate"), NO_PUSH, (ESTATE, "no wideband push has been made with the gate on since it was last set"), DONE),
 }
 
 
@@ -74,6 +75,8 @@ def _read(hip, d, entry):
         "wideband_waterfall": lambda: L.msk144_wideband_waterfall(h, -1, p(a, C.c_float), C.byref(n)),
         "wideband_waterfall_sums": lambda: L.msk144_wideband_waterfall_sums(h, p(a, C.c_double)),
         "wideband_capture": lambda: L.msk144_wideband_capture(h, p(a, hip.WidebandCaptureUnit), p(b, C.c_int8), C.byref(n), C.byref(m)),
+        "wideband_notch_stats": lambda: L.msk144_wideband_notch_stats(h, p(a, hip.WidebandNotchCount)),
+        "wideband_gate": lambda: L.msk144_wideband_gate(h, p(a, C.c_int32), C.byref(n), C.byref(m)),
     }[entry]()
     return rc, None if rc == OK else (L.msk144_last_error(h) or b"").decode()
 
@@ -98,6 +101,8 @@ def test_read_entries_by_state(hip):
         d.set_wideband_ping_band()
         d.set_wideband_waterfall()
         d.set_wideband_capture(channels=[0])
+        d.set_wideband_notch({0: [0]})
+        d.set_wideband_gate()
         d.push_wideband(1, first, first=True)                           # a first push: the blanker applies from one
         _assert_column(hip, d, 3, "a push with every option on")
         # msk144_set_wideband again: no push yet, and every option back to off, so the next push is one made without each

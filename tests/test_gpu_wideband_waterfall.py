@@ -22,40 +22,23 @@ import pytest
 
 import wideband_gpu as wg
 import wideband_levels_check as lc
+import wideband_options as wo
 import wideband_pings_check as pc
 import wideband_waterfall_check as wc
 from msk144cudecoder_amd import wideband as wb
+from wideband_check import split_pushes
+from wideband_options import EINVAL, ESTATE, code_of, shape_of
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -4
-SMALL = {
-    "one": dict(rate=240000, K=16, offsets=np.array([12345], dtype=np.int32)),
-    "five": dict(rate=240000, K=16, offsets=pc.SCENE_OFFSETS),
-}
 WINDOWS = {"hann": "hann", "ones": np.ones(96), "random": wc.random_window(2)}
 
 
 @pytest.fixture(scope="module")
 def handles(hip):
     """Two handles per channel count, made on first use and kept for the module."""
-    made = {}
-
-    def get(C):
-        if C not in made:
-            made[C] = (hip.HipDecoder(channels=C, **wg.DECODE_CFG), hip.HipDecoder(channels=C, **wg.DECODE_CFG))
-        return made[C]
-
-    yield get
-    for a, b in made.values():
-        a.close()
-        b.close()
-
-
-def code_of(hip, call):
-    with pytest.raises(hip.Msk144Error) as e:
-        call()
-    return e.value.code
+    with wo.handle_cache(wo.decode_pair(hip)) as get:
+        yield get
 
 
 def model_of(window):
@@ -65,9 +48,9 @@ def model_of(window):
 # ---- 1. shapes ----
 
 @pytest.mark.parametrize("fmt", ["cu8", "cs16"])
-@pytest.mark.parametrize("name", list(lc.SHAPES) + list(SMALL))
+@pytest.mark.parametrize("name", wo.SHAPE_NAMES)
 def test_shapes_against_the_model(handles, name, fmt):
-    shape = lc.SHAPES[name] if name in lc.SHAPES else SMALL[name]
+    shape = shape_of(name)
     rate, offsets = shape["rate"], shape["offsets"]
     d, _ = handles(len(offsets))
     d.set_wideband(rate, offsets, fmt, taps_per_phase=shape["K"], gain=pc.burst_gain(rate))
@@ -122,8 +105,7 @@ def test_a_tone_reads_its_slot(handles):
     rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
     d, _ = handles(len(offsets))
     gain = pc.burst_gain(rate)
-    sizes = [k // 2 for k in wb.push_sizes_for_rate(3, rate)]
-    n = np.arange(sum(sizes), dtype=np.int64)
+    n = np.arange(sum(wb.push_sizes_for_rate(3, rate)) // 2, dtype=np.int64)
     rng = np.random.default_rng(31)
     x = (rng.standard_normal(2 * len(n), dtype=np.float32) * np.float32(0.002)).view(np.complex64)
     planted = {1: (1375, 59), 3: (-2500, 28)}
@@ -133,10 +115,8 @@ def test_a_tone_reads_its_slot(handles):
     raw = wb.write_samples(x, "cs16")
     d.set_wideband(rate, offsets, "cs16", gain=gain)
     d.set_wideband_waterfall()
-    pos = 0
-    for i, k in enumerate(sizes):
-        d.push_wideband(i % 2, raw[2 * pos:2 * (pos + k)], first=i == 0)
-        pos += k
+    for i, part in enumerate(split_pushes(raw, rate, 3)):
+        d.push_wideband(i % 2, part, first=i == 0)
         rows = d.wideband_waterfall()
         for c, (df, j) in planted.items():
             assert wb.waterfall_hz(j) == df
@@ -154,12 +134,7 @@ def test_it_changes_nothing(handles, name):
     rate, offsets, K = shape["rate"], shape["offsets"], shape["K"]
     a, b = handles(len(offsets))
     if name == "rat":
-        raw, planted = wg.plant_scene(wb.FIRST_OUT + 2 * wb.HOP_OUT, rate, offsets, [3, 17, 30], np.random.default_rng(55))
-        parts, pos = [], 0
-        for k in wb.push_sizes_for_rate(3, rate):
-            parts.append(raw[pos:pos + k])
-            pos += k
-        fmt, gain = "cu8", 100.0
+        parts, planted, fmt, gain = wo.rat_scene()
     else:
         fmt, gain = "cs16", pc.burst_gain(rate)
         parts = pc.burst_parts(rate, tuple(int(f) for f in offsets), fmt)[:2]
@@ -168,23 +143,11 @@ def test_it_changes_nothing(handles, name):
         d.set_wideband_pings()
         d.set_wideband_spectrum(256)
     a.set_wideband_waterfall()
-    seen = []
-    for d in (a, b):
-        out = []
-        for i, part in enumerate(parts):
-            d.push_wideband(i % 2, part, first=i == 0)
-            hops = wg.dump_hops(d, range(d.channels))
-            rec = wg._decode(d, i % 2) if name == "rat" else None
-            out.append((hops, d.wideband_clip_count(), d.wideband_levels(), d.wideband_pings(), d.wideband_ping_blocks(), d.wideband_spectrum(), rec))
-        seen.append(out)
+    H = type(a)
+    seen = wo.leaves_unchanged(a, b, parts, reads=(H.wideband_pings, H.wideband_ping_blocks, H.wideband_spectrum), decode=name == "rat")
     assert a.wideband_waterfall().shape == (len(offsets), 27, 96) and a.wideband_waterfall().any()
-    for (h0, c0, l0, p0, e0, s0, r0), (h1, c1, l1, p1, e1, s1, r1) in zip(*seen):
-        assert h0.any() and np.array_equal(h0, h1) and c0 == c1 and np.array_equal(l0, l1)
-        assert p0.tobytes() == p1.tobytes() and np.array_equal(e0, e1) and s0[0].tobytes() == s1[0].tobytes() and s0[1] == s1[1]
-        if name == "rat":
-            assert r0.tobytes() == r1.tobytes()
     if name == "rat":
-        assert sum(len(r) for *_, r in seen[0]) > 0 and planted     # the scene decodes to something
+        assert sum(len(s["records"]) for s in seen) > 0 and planted     # the scene decodes to something
     for d in (a, b):
         d.set_wideband_pings(None)
         d.set_wideband_spectrum(None)
@@ -197,12 +160,9 @@ def test_order_and_refusals(hip, handles):
     rate, offsets = pc.SCENE_RATE, pc.SCENE_OFFSETS
     parts = pc.burst_parts(rate, tuple(int(f) for f in offsets), "cs16")
     gain = pc.burst_gain(rate)
-    with hip.HipDecoder(channels=1, **wg.DECODE_CFG) as fresh:
-        assert code_of(hip, fresh.set_wideband_waterfall) == EINVAL                     # not in wideband mode
-        assert code_of(hip, lambda: fresh.set_wideband_waterfall(None)) == EINVAL
-        assert code_of(hip, fresh.wideband_waterfall) == EINVAL
-        assert code_of(hip, lambda: fresh.wideband_waterfall(0)) == EINVAL
-        assert code_of(hip, fresh.wideband_waterfall_sums) == EINVAL
+    H = hip.HipDecoder
+    wo.refuses_outside_wideband_mode(hip, [H.set_wideband_waterfall, lambda f: f.set_wideband_waterfall(None), H.wideband_waterfall, lambda f: f.wideband_waterfall(0),
+                                           H.wideband_waterfall_sums])
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     for bad in (np.nan, np.inf, -np.inf):
         w = np.ones(96)
@@ -210,12 +170,9 @@ def test_order_and_refusals(hip, handles):
         assert code_of(hip, lambda: a.set_wideband_waterfall(w)) == EINVAL, bad
     a.set_wideband_waterfall(-np.ones(96))                                              # real and finite is all a window must be
     a.set_wideband_waterfall(None)
-    assert code_of(hip, a.wideband_waterfall) == ESTATE                                 # before any push
-    assert code_of(hip, a.wideband_waterfall_sums) == ESTATE
+    wo.unreadable(hip, [a.wideband_waterfall, a.wideband_waterfall_sums])               # before any push
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_waterfall) == ESTATE                                 # ... and after one made with the waterfall off
-    assert code_of(hip, lambda: a.wideband_waterfall(0)) == ESTATE
-    assert code_of(hip, a.wideband_waterfall_sums) == ESTATE
+    wo.unreadable(hip, [a.wideband_waterfall, lambda: a.wideband_waterfall(0), a.wideband_waterfall_sums])     # ... and after one made with the waterfall off
 
     # `set` in mid-stream: the next push has rows; a channel out of range is refused
     a.set_wideband_waterfall(WINDOWS["random"])
@@ -234,25 +191,17 @@ def test_order_and_refusals(hip, handles):
     wc.assert_push(a, model_of("hann"), wc.U, "set again")
 
     # the same stream pushed twice gives the same bytes; a hop after a first push leaves no row of the first push behind
-    runs = []
-    for _ in range(2):
-        out = []
-        for i, part in enumerate(parts):
-            a.push_wideband(i % 2, part, first=i == 0)
-            out.append((a.wideband_waterfall(), a.wideband_waterfall_sums(), a.wideband_waterfall(2)))
-        runs.append(out)
-    for (r0, s0, c0), (r1, s1, c1) in zip(*runs):
-        assert r0.tobytes() == r1.tobytes() and s0.tobytes() == s1.tobytes() and c0.tobytes() == c1.tobytes() and r0.any()
-    assert [r.shape[1] for r, _, _ in runs[1]] == [54, 27, 27, 27]
+    again = wo.same_bytes_twice(a, parts, lambda d: (d.wideband_waterfall(), d.wideband_waterfall_sums(), d.wideband_waterfall(2)))
+    assert [r.shape[1] for r, _, _ in again] == [54, 27, 27, 27]
 
     # switched off: from the next push on there is nothing to read; msk144_set_wideband switches it off as well
     a.set_wideband_waterfall(None)
     a.push_wideband(0, parts[1], first=False)
-    assert code_of(hip, a.wideband_waterfall) == ESTATE
+    wo.unreadable(hip, [a.wideband_waterfall])
     a.set_wideband_waterfall()
     a.set_wideband(rate, offsets, "cs16", gain=gain)
     a.push_wideband(0, parts[0], first=True)
-    assert code_of(hip, a.wideband_waterfall) == ESTATE and code_of(hip, a.wideband_waterfall_sums) == ESTATE
+    wo.unreadable(hip, [a.wideband_waterfall, a.wideband_waterfall_sums])
     a.synchronize()
 
 

@@ -29,6 +29,7 @@ from typing import List
 import numpy as np
 
 import pack77
+import wideband_check as wc
 from msk144cudecoder_amd import synth
 from msk144cudecoder_amd import wideband as wb
 
@@ -266,11 +267,7 @@ def scene_parts() -> tuple:
         msg = pack77.pack_standard("CQ", "K%dAZ" % (k % 10), "FN42")
         pings.append((int(SCENE_OFFSETS[c]), synth.Ping(msg, start, frames, float(rng.uniform(-150, 150)), SCENE_SNR_DB, float(rng.uniform(0, 6)))))
     raw = wb.synth_wideband(wb.FIRST_OUT + (SCENE_PUSHES - 1) * wb.HOP_OUT, SCENE_RATE, pings, sigma, rng, "cs16")
-    out, pos = [], 0
-    for n in wb.push_sizes_for_rate(SCENE_PUSHES, SCENE_RATE):
-        out.append(raw[pos:pos + n])
-        pos += n
-    return tuple(out)
+    return tuple(wc.split_pushes(raw, SCENE_RATE, SCENE_PUSHES))
 
 
 def up_matrix(records) -> np.ndarray:

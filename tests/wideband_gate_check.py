@@ -174,6 +174,7 @@ def scene_bursts(hops: int):
 def scene_parts(channels: int = 8, hops: int = 12, snr_db: float = SCENE_SNR_DB, seed: int = SCENE_SEED) -> tuple:
     """Raw cs16 pushes of the scene: hops - 1 of them."""
     import pack77
+    import wideband_check as wc
     from msk144cudecoder_amd import synth
     wb = _wb()
     rng = np.random.default_rng([41, seed])
@@ -185,11 +186,7 @@ def scene_parts(channels: int = 8, hops: int = 12, snr_db: float = SCENE_SNR_DB,
         pings.append((int(offsets[c]), synth.Ping(msg, start, frames, float(rng.uniform(-8, 8)), snr_db, float(rng.uniform(0, 6)))))
     pushes = hops - 1
     raw = wb.synth_wideband(wb.FIRST_OUT + (pushes - 1) * wb.HOP_OUT, SCENE_RATE, pings, sigma, rng, "cs16")
-    out, pos = [], 0
-    for n in wb.push_sizes_for_rate(pushes, SCENE_RATE):
-        out.append(raw[pos:pos + n])
-        pos += n
-    return tuple(out)
+    return tuple(wc.split_pushes(raw, SCENE_RATE, pushes))
 
 
 def scene_model(channels: int = 8, hops: int = 12, snr_db: float = SCENE_SNR_DB, seed: int = SCENE_SEED, pings=None, band=None):

@@ -36,6 +36,7 @@ from typing import Dict, List
 
 import numpy as np
 
+import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
 
 N_PUSHES = 12
@@ -113,11 +114,7 @@ def tone_scene(name: str, n_pushes: int = N_PUSHES) -> np.ndarray:
 
 
 def scene_parts(name: str, n_pushes: int = N_PUSHES) -> List[np.ndarray]:
-    raw, out, pos = tone_scene(name, n_pushes), [], 0
-    for k in wb.push_sizes_for_rate(n_pushes, SHAPES[name]["rate"]):
-        out.append(raw[pos:pos + k])
-        pos += k
-    return out
+    return wc.split_pushes(tone_scene(name, n_pushes), SHAPES[name]["rate"], n_pushes)
 
 
 def make_model(shape: dict, gain=100.0, offsets=None):

@@ -9,6 +9,7 @@ import functools
 
 import numpy as np
 
+import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
 
 
@@ -177,11 +178,7 @@ def decode_scene(seed: int = SCENE_SEED):
 
 
 def scene_parts(seed: int = SCENE_SEED):
-    raw, pos, out = decode_scene(seed)[0], 0, []
-    for k in wb.push_sizes_for_rate(SCENE_PUSHES, SCENE_RATE):
-        out.append(raw[pos:pos + k])
-        pos += k
-    return out
+    return wc.split_pushes(decode_scene(seed)[0], SCENE_RATE, SCENE_PUSHES)
 
 
 def scene_model_hops(seed: int = SCENE_SEED, notched: bool = True):

@@ -21,6 +21,7 @@ from typing import List
 import numpy as np
 
 import pack77
+import wideband_check as wc
 from msk144cudecoder_amd import synth
 from msk144cudecoder_amd import wideband as wb
 
@@ -185,11 +186,7 @@ def scene(snr_db: float = 10.0, seed: int = SCENE_SEED) -> np.ndarray:
 
 
 def scene_parts(snr_db: float = 10.0, seed: int = SCENE_SEED) -> List[np.ndarray]:
-    raw, out, pos = scene(snr_db, seed), [], 0
-    for n in wb.push_sizes_for_rate(SCENE_PUSHES, SCENE_RATE):
-        out.append(raw[pos:pos + n])
-        pos += n
-    return out
+    return wc.split_pushes(scene(snr_db, seed), SCENE_RATE, SCENE_PUSHES)
 
 
 @functools.lru_cache(maxsize=None)
@@ -287,12 +284,7 @@ def _burst_signal(rate: int, offsets: tuple, seed: int) -> np.ndarray:
 @functools.lru_cache(maxsize=None)
 def burst_parts(rate: int, offsets: tuple, fmt: str, seed: int = 3) -> tuple:
     """Raw pushes (a first push and three later ones) of white noise with the two tone bursts of BURSTS at channel offsets."""
-    raw = wb.write_samples(_burst_signal(rate, offsets, seed), fmt)
-    out, pos = [], 0
-    for k in wb.push_sizes_for_rate(BURST_PUSHES, rate):
-        out.append(raw[pos:pos + k])
-        pos += k
-    return tuple(out)
+    return tuple(wc.split_pushes(wb.write_samples(_burst_signal(rate, offsets, seed), fmt), rate, BURST_PUSHES))
 
 
 # ---- a device push against the model ----

@@ -22,6 +22,7 @@ from typing import List
 
 import numpy as np
 
+import wideband_check as wc
 from msk144cudecoder_amd import wideband as wb
 
 V = 4.0 * 2.0 ** -24
@@ -79,13 +80,8 @@ def stream(rate: int, n_pushes: int, seed) -> np.ndarray:
 def pushes(rate: int, fmt: str, n_pushes: int, seed: int = 0) -> tuple:
     """The raw pushes of the test stream in fmt (shared, do not modify)."""
     raw = wb.write_samples(stream(rate, n_pushes, [rate, seed]), fmt)
-    out, pos = [], 0
-    for k in wb.push_sizes_for_rate(n_pushes, rate):
-        part = raw[pos:pos + k]
-        part.setflags(write=False)
-        out.append(part)
-        pos += k
-    return tuple(out)
+    raw.setflags(write=False)
+    return tuple(wc.split_pushes(raw, rate, n_pushes))
 
 
 def random_window(bins: int, seed: int) -> np.ndarray:
