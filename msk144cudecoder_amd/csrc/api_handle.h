@@ -174,7 +174,7 @@ struct Wideband
         int rows = 0;
         uint8_t* d_listed = nullptr;                  // [channels]
         msk144wb::CaptureState* d_state = nullptr;    // [channels]
-        msk144wb::CaptureHeader* d_header = nullptr;  // [1]
+        msk144wb::PlanHeader* d_header = nullptr;     // [1]
         msk144wb::CaptureUnit* d_units = nullptr;     // [rows]
         uint8_t* d_data = nullptr;                    // [rows][5184]
     } capture;
@@ -186,10 +186,10 @@ struct Wideband
         msk144wb::GateParams params;
         uint8_t* d_always = nullptr;                // [channels]
         int32_t* d_since = nullptr;                 // [channels]
-        msk144wb::GateHeader* d_header = nullptr;   // [1]
+        msk144wb::PlanHeader* d_header = nullptr;   // [1]
         int32_t* d_list = nullptr;                  // [channels]
         float2* d_analytic = nullptr;               // [channels][5184]: row j is the window of channel list[j]
-        msk144wb::GateHeader* header = nullptr;     // pinned: the header, and behind it the list, int32 [channels]
+        msk144wb::PlanHeader* header = nullptr;     // pinned: the header, and behind it the list, int32 [channels]
         hipEvent_t planned = nullptr;
     } gate;
 };

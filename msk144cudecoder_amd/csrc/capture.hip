@@ -3,14 +3,13 @@
 // include/msk144hip.h).  Both kernels run behind the hop ring kernel: ring[c] then holds the hop before the newest in its first
 // 5184 bytes and the newest in its second (hops 0 and 1 after a first push), so every unit is one half of a ring window.
 //
-//   plan   one workgroup walks the channels in chunks of kPlanThreads, one channel per lane.  A lane applies msk144wb::capture_step
-//          to its channel - the ping record's up mask, the list flag, the channel's state - and has 0, 1 or 2 units.  Their
-//          exclusive prefix in ascending channel order: within a wave two ballots (at least one unit, two units) and the popcounts
-//          of the lanes below; across the waves their totals through LDS; across chunks a running base every lane keeps.  The first
-//          max_units units get a descriptor, the header gets {count, total, newest hop}.  No atomics, one order.
+//   plan   the walk of plan.h with msk144wb::capture_step as a lane's step: the ping record's up mask, the list flag and the
+//          channel's state give 0, 1 or 2 units.  The first max_units units get a descriptor, the header gets {count, total,
+//          newest hop}.
 //   copy   one wave per unit slot, the grid fixed by max_units: a wave at or past the header's count leaves at once, the others move
 //          their unit's 324 16-byte words from the ring window to row u of the dense buffer.
 #include "msk144_kernels.h"
+#include "plan.h"
 
 namespace msk144
 {
@@ -18,52 +17,29 @@ namespace msk144
 namespace
 {
 
-constexpr int kPlanWaves = 4;
-constexpr int kPlanThreads = kPlanWaves * 64;  // the chunk: one channel per lane
 constexpr int kCopyWaves = 4;
 constexpr int kUnitWords = msk144wb::kCaptureUnitBytes / 16;  // 324
 static_assert(2 * kHopSamples == msk144wb::kCaptureUnitBytes && 2 * kWindowSamples == 2 * msk144wb::kCaptureUnitBytes, "a unit is a hop of int8 I/Q: half a ring window");
 
 __global__ __launch_bounds__(kPlanThreads) void capture_plan_kernel(const msk144wb::PingRecord* __restrict__ records, const uint8_t* __restrict__ listed,
                                                                     msk144wb::CaptureState* __restrict__ state, int channels, int first, int clear,
-                                                                    msk144wb::CaptureParams p, long long newest, msk144wb::CaptureHeader* __restrict__ header,
+                                                                    msk144wb::CaptureParams p, long long newest, msk144wb::PlanHeader* __restrict__ header,
                                                                     msk144wb::CaptureUnit* __restrict__ units)
 {
-    __shared__ int s_total[2][kPlanWaves];  // by chunk parity: a wave writes a chunk's total only after every wave has read the one two before
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int base = 0;
-    for(int c0 = 0, parity = 0; c0 < channels; c0 += kPlanThreads, parity ^= 1)
+    PlanWalk walk;
+    for(int c0 = 0; c0 < channels; c0 += kPlanThreads)
     {
         const int c = c0 + static_cast<int>(threadIdx.x);
         int32_t flags[2] = {0, 0}, half[2] = {0, 0};
-        int n = 0;
-        if(c < channels)
-        {
-            msk144wb::CaptureState s = state[c];
-            n = msk144wb::capture_step(s, first != 0, clear != 0, records ? records[c].up_mask : 0ull, listed[c] != 0, p.pre, p.post, flags, half);
-            state[c] = s;
-        }
-        const unsigned long long one = __ballot(n >= 1), two = __ballot(n == 2);
-        if(lane == 0) s_total[parity][wave] = __popcll(one) + __popcll(two);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for(int w = 0; w < kPlanWaves; w++)
-        {
-            const int t = s_total[parity][w];
-            all += t;
-            before += w < wave ? t : 0;
-        }
-        const int idx = base + before + __popcll(one & below) + __popcll(two & below);
+        const int n = c < channels ? msk144wb::capture_step(state[c], first != 0, clear != 0, records ? records[c].up_mask : 0ull, listed[c] != 0, p.pre, p.post, flags, half) : 0;
+        const int idx = walk.place<2>(n);
         for(int i = 0; i < n; i++)
             if(idx + i < p.max_units) units[idx + i] = msk144wb::CaptureUnit{c, flags[i], newest - 1 + half[i]};
-        base += all;
     }
-    if(threadIdx.x == 0) *header = msk144wb::CaptureHeader{base < p.max_units ? base : p.max_units, base, newest};
+    walk.finish(header, p.max_units, newest);
 }
 
-__global__ __launch_bounds__(kCopyWaves * 64) void capture_copy_kernel(const uint4* __restrict__ ring, const msk144wb::CaptureHeader* __restrict__ header,
+__global__ __launch_bounds__(kCopyWaves * 64) void capture_copy_kernel(const uint4* __restrict__ ring, const msk144wb::PlanHeader* __restrict__ header,
                                                                        const msk144wb::CaptureUnit* __restrict__ units, int max_units, uint4* __restrict__ data)
 {
     const int lane = threadIdx.x & 63;
@@ -79,7 +55,7 @@ __global__ __launch_bounds__(kCopyWaves * 64) void capture_copy_kernel(const uin
 }  // namespace
 
 void launch_capture(const void* ring, const msk144wb::PingRecord* records, const uint8_t* listed, msk144wb::CaptureState* state, int channels, int first, int clear,
-                    const msk144wb::CaptureParams& p, long long newest, msk144wb::CaptureHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream)
+                    const msk144wb::CaptureParams& p, long long newest, msk144wb::PlanHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream)
 {
     hipLaunchKernelGGL(capture_plan_kernel, dim3(1), dim3(kPlanThreads), 0, stream, records, listed, state, channels, first, clear, p, newest, header, units);
     hipLaunchKernelGGL(capture_copy_kernel, dim3((p.max_units + kCopyWaves - 1) / kCopyWaves), dim3(kCopyWaves * 64), 0, stream, static_cast<const uint4*>(ring), header, units,

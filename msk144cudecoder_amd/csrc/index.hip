@@ -20,25 +20,17 @@ constexpr int kIdxThreads = 1024;
 constexpr int kIdxWaves = kIdxThreads / 64;
 
 // Ordered compaction helper: returns this thread's output slot (or -1) for `flag`, advancing `base`
-// (workgroup-uniform running count).  All threads of the workgroup must call it.
+// (workgroup-uniform running count).  All threads of the workgroup must call it.  Across the waves:
+// cross_wave_prefix (wave64.h), which the plan kernels of the capture and the gate use too (plan.h).
 __device__ __forceinline__ int ordered_slot(bool flag, int& base, int* s_wave_count)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
     const unsigned long long m = __ballot(flag);
-    if(lane == 0) s_wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for(int w = 0; w < kIdxWaves; w++)
-    {
-        const int c = s_wave_count[w];
-        if(w < wave) before += c;
-        total += c;
-    }
+    int before, total;
+    cross_wave_prefix<kIdxWaves>(__popcll(m), s_wave_count, before, total);
     const int slot = flag ? base + before + __popcll(m & ((1ull << lane) - 1ull)) : -1;
     base += total;
-    __syncthreads();
+    __syncthreads();  // one row: the next call's store waits for these reads
     return slot;
 }
 

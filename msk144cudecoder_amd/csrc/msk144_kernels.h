@@ -148,7 +148,7 @@ void launch_waterfall(const int8_t* first_halves, const int8_t* hops, int first,
 // is the newest hop of the push; `clear`: a first push or the first one after msk144_set_wideband_capture.  Moves state[channels]
 // and writes the header, the first min(total, max_units) descriptors and their rows data[.][5184].
 void launch_capture(const void* ring, const msk144wb::PingRecord* records, const uint8_t* listed, msk144wb::CaptureState* state, int channels, int first, int clear,
-                    const msk144wb::CaptureParams& p, long long newest, msk144wb::CaptureHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream);
+                    const msk144wb::CaptureParams& p, long long newest, msk144wb::PlanHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream);
 
 // the gate of a push (gate.hip; contract in include/msk144hip.h).  Plan, behind launch_pings: records[channels] the push's ping
 // records or nullptr (the detector was off), always[channels] the always flags; `newest` is the newest hop of the push; `clear`: a
@@ -156,8 +156,8 @@ void launch_capture(const void* ring, const msk144wb::PingRecord* records, const
 // min(total, max_channels) channels of list[channels].  Gather, behind the IQ front end: a grid of `channels` workgroups, of which
 // the first header->count move row list[j] of analytic[channels][5184] to row j of packed[channels][5184].
 void launch_gate_plan(const msk144wb::PingRecord* records, const uint8_t* always, int32_t* since, int channels, int first, int clear, const msk144wb::GateParams& p,
-                      long long newest, msk144wb::GateHeader* header, int32_t* list, hipStream_t stream);
-void launch_gate_gather(const float2* analytic, const msk144wb::GateHeader* header, const int32_t* list, int channels, float2* packed, hipStream_t stream);
+                      long long newest, msk144wb::PlanHeader* header, int32_t* list, hipStream_t stream);
+void launch_gate_gather(const float2* analytic, const msk144wb::PlanHeader* header, const int32_t* list, int channels, float2* packed, hipStream_t stream);
 
 // what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
 // before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push

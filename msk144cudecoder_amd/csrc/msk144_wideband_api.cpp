@@ -337,19 +337,29 @@ void wb_launch_observers(msk144_handle* h, const WbPush& p)
     w.waterfall.pushed = w.waterfall.on;
 }
 
+// The frame of a push's plan (capture, gate), around the option's launch: launch(records, first, clear) gets the ping records of
+// the push (null: the detector is off), whether the push is a first one, and whether the option's state starts afresh - a first
+// push, or the first push after the option's `set`
+template<class Option, class Launch>
+int wb_plan(msk144_handle* h, const WbPush& p, Option& o, Launch launch)
+{
+    o.pushed = o.on;
+    if(!o.on) return MSK144_OK;
+    ev_begin(h);
+    launch(h->wb.pings.on ? h->wb.pings.d_records : nullptr, p.first ? 1 : 0, p.first || o.restart ? 1 : 0);
+    ev_end(h, MSK144_T_FRONTEND);
+    o.restart = false;
+    HIP_TRY(h, hipGetLastError());
+    return MSK144_OK;
+}
+
 // Capture, behind the ring kernel: the ring now holds the push's newest hop, number m_next / 2592 - 1, and the one before it
 int wb_capture(msk144_handle* h, const WbPush& p)
 {
     auto& c = h->wb.capture;
-    c.pushed = c.on;
-    if(!c.on) return MSK144_OK;
-    ev_begin(h);
-    launch_capture(h->d_ring, h->wb.pings.on ? h->wb.pings.d_records : nullptr, c.d_listed, c.d_state, h->wb.channels, p.first ? 1 : 0, p.first || c.restart ? 1 : 0, c.params,
-                   h->wb.core.m_next / kHopSamples - 1, c.d_header, c.d_units, c.d_data, h->stream);
-    ev_end(h, MSK144_T_FRONTEND);
-    c.restart = false;
-    HIP_TRY(h, hipGetLastError());
-    return MSK144_OK;
+    return wb_plan(h, p, c, [&](const msk144wb::PingRecord* records, int first, int clear) {
+        launch_capture(h->d_ring, records, c.d_listed, c.d_state, h->wb.channels, first, clear, c.params, h->wb.core.m_next / kHopSamples - 1, c.d_header, c.d_units, c.d_data, h->stream);
+    });
 }
 
 // The gate's plan, behind the ping detector: the list of the channels whose window this push decodes, its header to the pinned
@@ -357,17 +367,13 @@ int wb_capture(msk144_handle* h, const WbPush& p)
 int wb_gate_plan(msk144_handle* h, const WbPush& p)
 {
     auto& g = h->wb.gate;
-    g.pushed = g.on;
-    if(!g.on) return MSK144_OK;
     const int C = h->wb.channels;
-    ev_begin(h);
-    launch_gate_plan(h->wb.pings.on ? h->wb.pings.d_records : nullptr, g.d_always, g.d_since, C, p.first ? 1 : 0, p.first || g.restart ? 1 : 0, g.params,
-                     (h->wb.core.m_next + p.M) / kHopSamples - 1, g.d_header, g.d_list, h->stream);
-    ev_end(h, MSK144_T_FRONTEND);
-    g.restart = false;
-    HIP_TRY(h, hipGetLastError());
+    const int rc = wb_plan(h, p, g, [&](const msk144wb::PingRecord* records, int first, int clear) {
+        launch_gate_plan(records, g.d_always, g.d_since, C, first, clear, g.params, (h->wb.core.m_next + p.M) / kHopSamples - 1, g.d_header, g.d_list, h->stream);
+    });
+    if(rc != MSK144_OK || !g.on) return rc;
     // header and list in one pinned block: a quiet band reads 16 bytes of it, a busy one the listed channels behind them
-    HIP_TRY(h, hipMemcpyAsync(g.header, g.d_header, sizeof(msk144wb::GateHeader), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(g.header, g.d_header, sizeof(msk144wb::PlanHeader), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(g.header + 1, g.d_list, sizeof(int32_t) * static_cast<size_t>(C), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipEventRecord(g.planned, h->stream));
     return MSK144_OK;
@@ -384,6 +390,24 @@ int wb_gate_gather(msk144_handle* h)
     ev_end(h, MSK144_T_FRONTEND);
     HIP_TRY(h, hipGetLastError());
     return MSK144_OK;
+}
+
+// The end of an accepted `set` of a planning option (capture, gate): its flag per channel on the device, its per-channel state
+// cleared, the option on, and its next push one that starts the state afresh
+template<class Option>
+int wb_plan_on(msk144_handle* h, Option& o, uint8_t* d_flags, const std::vector<uint8_t>& flags, void* d_state, size_t state_bytes)
+{
+    HIP_TRY(h, hipMemcpy(d_flags, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(d_state, 0, state_bytes));
+    o.on = true;
+    o.restart = true;
+    return MSK144_OK;
+}
+
+// the header a plan left, as a read entry takes it: a count within 0..most
+int wb_plan_header(msk144_handle* h, const char* who, const msk144wb::PlanHeader& head, int most)
+{
+    return head.count < 0 || head.count > most ? fail(h, MSK144_EHIP, std::string(who) + ": the device left a header out of range") : MSK144_OK;
 }
 
 }  // namespace
@@ -848,12 +872,8 @@ int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_
     }
     std::vector<uint8_t> listed(C, 0);
     for(int i = 0; i < p->num_listed; i++) listed[static_cast<size_t>(p->listed[i])] = 1;
-    HIP_TRY(h, hipMemcpy(c.d_listed, listed.data(), C, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(c.d_state, 0, sizeof(msk144wb::CaptureState) * C));
     c.params = cp;
-    c.on = true;
-    c.restart = true;
-    return MSK144_OK;
+    return wb_plan_on(h, c, c.d_listed, listed, c.d_state, sizeof(msk144wb::CaptureState) * C);
 }
 
 int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* units, int8_t* data, int32_t* count, int32_t* total)
@@ -863,10 +883,10 @@ int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* unit
     if(const int rc = wb_read_ready(h, "msk144_wideband_capture", c.pushed, "no wideband push has been made with capture on since it was last set"); rc != MSK144_OK) return rc;
     static_assert(sizeof(msk144_wideband_capture_unit) == sizeof(msk144wb::CaptureUnit) && offsetof(msk144_wideband_capture_unit, hop) == offsetof(msk144wb::CaptureUnit, hop),
                   "the kernel writes msk144_wideband_capture_unit");
-    msk144wb::CaptureHeader head{};
+    msk144wb::PlanHeader head{};
     HIP_TRY(h, hipMemcpy(&head, c.d_header, sizeof(head), hipMemcpyDeviceToHost));
     // the push that left the header was made with c.params (`set` ends the units of the push before it)
-    if(head.count < 0 || head.count > c.params.max_units || head.count > c.rows) return fail(h, MSK144_EHIP, "msk144_wideband_capture: the device left a header out of range");
+    if(const int rc = wb_plan_header(h, "msk144_wideband_capture", head, std::min(c.params.max_units, c.rows)); rc != MSK144_OK) return rc;
     // a quiet band costs the header alone
     if(head.count)
     {
@@ -899,18 +919,14 @@ int msk144_set_wideband_gate(msk144_handle* h, const msk144_wideband_gate_params
     {
         // the pinned header with the list behind it: 16 bytes are four int32
         int32_t* block = nullptr;
-        if(const int rc = host_alloc(h, w.mem, &block, sizeof(msk144wb::GateHeader) / sizeof(int32_t) + C); rc != MSK144_OK) return rc;
-        g.header = reinterpret_cast<msk144wb::GateHeader*>(block);
+        if(const int rc = host_alloc(h, w.mem, &block, sizeof(msk144wb::PlanHeader) / sizeof(int32_t) + C); rc != MSK144_OK) return rc;
+        g.header = reinterpret_cast<msk144wb::PlanHeader*>(block);
     }
     if(!g.planned) HIP_TRY(h, hipEventCreateWithFlags(&g.planned, hipEventBlockingSync | hipEventDisableTiming));
     std::vector<uint8_t> flags(C, 0);
     for(size_t c = 0; always && c < C; c++) flags[c] = always[c] != 0;
-    HIP_TRY(h, hipMemcpy(g.d_always, flags.data(), C, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(g.d_since, 0, sizeof(int32_t) * C));
     g.params = gp;
-    g.on = true;
-    g.restart = true;
-    return MSK144_OK;
+    return wb_plan_on(h, g, g.d_always, flags, g.d_since, sizeof(int32_t) * C);
 }
 
 int msk144_wideband_gate(msk144_handle* h, int32_t* channels_out, int32_t* count, int32_t* total)
@@ -923,8 +939,8 @@ int msk144_wideband_gate(msk144_handle* h, int32_t* channels_out, int32_t* count
     if(!w.started || !g.pushed) return fail(h, MSK144_ESTATE, w.started ? "no wideband push has been made with the gate on since it was last set" : "no wideband push has been made");
     HIP_TRY(h, hipSetDevice(h->params.device));
     HIP_TRY(h, hipEventSynchronize(g.planned));
-    const msk144wb::GateHeader head = *g.header;
-    if(head.count < 0 || head.count > w.channels) return fail(h, MSK144_EHIP, "msk144_wideband_gate: the device left a header out of range");
+    const msk144wb::PlanHeader head = *g.header;
+    if(const int rc = wb_plan_header(h, "msk144_wideband_gate", head, w.channels); rc != MSK144_OK) return rc;
     std::memcpy(channels_out, g.header + 1, sizeof(int32_t) * static_cast<size_t>(head.count));
     *count = head.count;
     *total = head.total;

@@ -31,8 +31,8 @@ namespace
 constexpr int kWaves = 4;
 constexpr int kBlockBytes = 2 * msk144wb::kPingBlock;        // 192: a multiple of 16, as the 5184-byte rows are
 constexpr int kRowBytes = 2 * kHopSamples;
-constexpr int kHopBlocks = kHopSamples / msk144wb::kPingBlock;  // 27
-static_assert(kHopSamples % msk144wb::kPingBlock == 0 && 2 * kHopBlocks == msk144wb::kPingMaxBlocks, "a hop is 27 whole blocks");
+using msk144wb::kHopBlocks;
+static_assert(kHopSamples == kHopBlocks * msk144wb::kPingBlock && 2 * kHopBlocks == msk144wb::kPingMaxBlocks, "a hop is 27 whole blocks");
 static_assert(kBlockBytes % 16 == 0 && kRowBytes % 16 == 0, "16-byte loads");
 static_assert(msk144wb::kPingEnergyBits + 6 <= 28, "the peak key keeps clear of the exponent bits that bias it");
 

@@ -244,6 +244,28 @@ __device__ __forceinline__ void wave_sum2_f32(float& a, float& b)
     b = readlane_f32(rb, 63);
 }
 
+// The cross-wave step of an ordered compaction, once: every wave of a kWaves-wave workgroup brings `count`, the entries of its 64
+// lanes (wave-uniform: the popcount of a ballot), and learns `before`, the entries of the waves below it, and `all`, the workgroup's.
+// row[kWaves] is LDS the caller owns; the step holds one barrier, between the store and the reads.  A caller that runs it in a loop
+// keeps the next store from overtaking these reads: a barrier of its own behind the step, or two rows taken in turn - a wave
+// stores to a row only after it has passed the barrier of the step between, which every wave reaches after its reads of that row.
+// All threads of the workgroup call it.
+template<int kWaves>
+__device__ __forceinline__ void cross_wave_prefix(int count, int* row, int& before, int& all)
+{
+    const int wave = threadIdx.x >> 6;
+    if((threadIdx.x & 63) == 0) row[wave] = count;
+    __syncthreads();
+    before = all = 0;
+#pragma unroll
+    for(int w = 0; w < kWaves; w++)
+    {
+        const int t = row[w];
+        all += t;
+        before += w < wave ? t : 0;
+    }
+}
+
 // Sum of a 32-lane half of the wave with the reference's shuffle order (1,2,4,8,16); the result
 // is valid in lanes 0 and 32.  Keeping this order makes 144-term block sums bit-compatible with
 // sum_reduction_two_cycles on 32-lane warps.

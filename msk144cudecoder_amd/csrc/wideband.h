@@ -272,6 +272,7 @@ inline std::string check_spectrum(int B, const double* window, int64_t hop_sampl
 
 constexpr int kPingBlock = 96;        // B: samples per block, 8 ms; a 72 ms frame is 9 blocks
 constexpr int kPingMaxBlocks = 54;    // nb of a first push (5184 / 96); a later push has 27
+constexpr int kHopBlocks = 27;        // a hop is 27 blocks
 constexpr int kPingEnergyBits = 22;   // E <= 96 x 2 x 128^2 = 3145728 < 2^22
 constexpr int kPingMaxMemory = 16;
 constexpr int kPingMinRatioQ4 = 16;   // 1 x the reference
@@ -710,16 +711,35 @@ inline double waterfall_excess_db(const double* sum, int& j_top)
     return median > 0.0 ? 10.0 * std::log10(sum[j_top] / median) : 0.0;
 }
 
+// ---- the hop rule and the plan of a push, which the capture and the gate share ----
+
+// Both read the ping detector's up_mask hop by hop and keep, per channel, `since`: the hops since its last active one.
+constexpr int kSinceQuiet = 17;   // `since` saturates here: no activity that any `post` or `hold` still reaches
+
+// The 27 up bits of hop i of a push.  `first`: the push carries hops 0 and 1 (up_mask bits 0..26 and 27..53), i = 0 and 1 in that
+// order; else the newest hop alone (bits 0..26), i = 1.  up_mask is 0 when the detector was off.
+MSK144WB_HD inline uint64_t hop_up_bits(uint64_t up_mask, bool first, int i) { return (up_mask >> (first ? kHopBlocks * i : 0)) & ((1ull << kHopBlocks) - 1); }
+
+// `since` behind one more hop
+MSK144WB_HD inline int32_t since_next(int32_t since, bool active) { return active ? 0 : since < kSinceQuiet ? since + 1 : kSinceQuiet; }
+
+// What the plan of a push leaves in front of its entries (the capture's units, the gate's channels), which come in ascending
+// channel order: the entries stored, all entries the push had, and the newest hop of the push
+struct PlanHeader
+{
+    int32_t count, total;
+    int64_t hop;
+};
+static_assert(sizeof(PlanHeader) == 16, "the plan header is 16 bytes");
+
 // ---- per-ping capture of a channel's hops (msk144_set_wideband_capture, msk144_wideband_capture) ----
 
 constexpr int kCaptureUnitBytes = 5184;                   // one hop of one channel: 2592 int8 I/Q pairs, what --read-mode=2 reads
-constexpr int kCaptureHopBlocks = 27;                     // a hop is 27 blocks of the ping detector
 constexpr int kCaptureMaxPost = 16;
-constexpr int kCaptureQuiet = kCaptureMaxPost + 1;        // `since` saturates here: no activity that any `post` still reaches
 constexpr int kCaptureMaxUnits = 16384;
 constexpr int kCaptureMaxListed = kWaterfallMaxListed;
 constexpr int kCaptureDefaultMaxUnits = 512;              // the program's and the Python view's: min(2 x channels, 512)
-static_assert(kCaptureUnitBytes % 16 == 0 && kCaptureHopBlocks * kPingBlock * 2 == kCaptureUnitBytes && 2 * kCaptureHopBlocks == kPingMaxBlocks, "a unit is a hop");
+static_assert(kCaptureUnitBytes % 16 == 0 && kHopBlocks * kPingBlock * 2 == kCaptureUnitBytes && 2 * kHopBlocks == kPingMaxBlocks, "a unit is a hop");
 
 enum CaptureFlags
 {
@@ -743,36 +763,27 @@ struct CaptureUnit
 };
 static_assert(sizeof(CaptureUnit) == 16, "msk144_wideband_capture_unit is 16 bytes");
 
-// what a push leaves in front of the descriptors: the stored units, all units, and the newest hop of the push
-struct CaptureHeader
-{
-    int32_t count, total;
-    int64_t hop;
-};
-static_assert(sizeof(CaptureHeader) == 16, "the capture header is 16 bytes");
-
-// a channel's memory: hops since the last active one (kCaptureQuiet: none that counts), and whether its newest hop was emitted
+// a channel's memory: hops since the last active one (kSinceQuiet: none that counts), and whether its newest hop was emitted
 struct CaptureState
 {
     int32_t since, emitted;
 };
 
-// The capture rule, once, for one channel and one push.  `first`: the push carries hops 0 and 1 (up_mask bits 0..26 and 27..53),
-// else the newest hop alone (bits 0..26); up_mask is 0 when the detector was off.  `clear`: a first push, or the first push after
-// msk144_set_wideband_capture: earlier activity counts as none and the previous hop as not emitted.  Returns the channel's units of
-// this push, 0 .. 2 in ascending hop order: half[i] is the half of the channel's ring window the unit lies in (0: the hop before
-// the newest, 1: the newest), flags[i] its CaptureFlags.
+// The capture rule, once, for one channel and one push.  `first` and up_mask: as hop_up_bits takes them; a hop is active iff one of
+// its blocks is up.  `clear`: a first push, or the first push after msk144_set_wideband_capture: earlier activity counts as none
+// and the previous hop as not emitted.  Returns the channel's units of this push, 0 .. 2 in ascending hop order: half[i] is the
+// half of the channel's ring window the unit lies in (0: the hop before the newest, 1: the newest), flags[i] its CaptureFlags.
 //   W(k) = listed, or a(j) for some k - post <= j <= k   -> hop k is emitted in its own push
 //   P(k) = pre and not W(k) and a(k + 1)                 -> hop k is emitted in the next push (for k = 0 that is the same push)
 MSK144WB_HD inline int capture_step(CaptureState& s, bool first, bool clear, uint64_t up_mask, bool listed, int32_t pre, int32_t post, int32_t flags[2], int32_t half[2])
 {
-    int32_t since = clear ? kCaptureQuiet : s.since;
+    int32_t since = clear ? kSinceQuiet : s.since;
     bool emitted = clear ? false : s.emitted != 0;
     int n = 0;
     for(int i = first ? 0 : 1; i < 2; i++)
     {
-        const bool a = ((up_mask >> (first ? kCaptureHopBlocks * i : 0)) & ((1ull << kCaptureHopBlocks) - 1)) != 0;
-        since = a ? 0 : since < kCaptureQuiet ? since + 1 : kCaptureQuiet;
+        const bool a = hop_up_bits(up_mask, first, i) != 0;
+        since = since_next(since, a);
         const bool w = listed || since <= post;
         // the hop before this one: in the ring since the push before, or hop 0 of this first push
         if(i == 1 && pre && a && !emitted)
@@ -901,13 +912,13 @@ public:
     std::string locate(int32_t channel, int64_t g) const
     {
         const Chan& ch = chan_[static_cast<size_t>(channel)];
-        const int64_t k = g / kCaptureHopBlocks;
+        const int64_t k = g / kHopBlocks;
         int64_t k0 = -1;
         if(ch.hops && k >= ch.k0 && k < ch.k0 + ch.hops) k0 = ch.k0;
         for(int i = 0; k0 < 0 && i < kRemembered; i++)
             if(ch.past_hops[i] && k >= ch.past_k0[i] && k < ch.past_k0[i] + ch.past_hops[i]) k0 = ch.past_k0[i];
         if(k0 < 0) return " file=-";
-        return " file=" + segment_name(channel, k0) + " at=" + std::to_string((k - k0) * (kCaptureUnitBytes / 2) + (g % kCaptureHopBlocks) * kPingBlock);
+        return " file=" + segment_name(channel, k0) + " at=" + std::to_string((k - k0) * (kCaptureUnitBytes / 2) + (g % kHopBlocks) * kPingBlock);
     }
 
     int64_t segments() const { return segments_; }
@@ -956,8 +967,7 @@ private:
 // ---- the gate: only the channels with activity are decoded (msk144_set_wideband_gate, msk144_wideband_gate) ----
 
 constexpr int kGateMaxHold = 16;
-constexpr int kGateQuiet = kGateMaxHold + 1;   // `since` saturates here: no activity that any `hold` still reaches
-constexpr int kGateHopBlocks = kCaptureHopBlocks;
+static_assert(kCaptureMaxPost < kSinceQuiet && kGateMaxHold < kSinceQuiet, "a saturated `since` lies beyond every post and hold");
 
 // msk144_wideband_gate_params, field for field.  The defaults are design parameters, not measurements.
 struct GateParams
@@ -965,31 +975,21 @@ struct GateParams
     int32_t hold = 1, min_up = 1, max_channels = 0;   // max_channels 0: every channel
 };
 
-// what a push leaves in front of the list: the listed channels, all channels that qualified, and the newest hop of the push
-struct GateHeader
-{
-    int32_t count, total;
-    int64_t hop;
-};
-static_assert(sizeof(GateHeader) == 16, "the gate header is 16 bytes");
-
-// The gate rule, once, for one channel and one push.  `since`: hops since the channel's last active one, saturating at kGateQuiet.
-// `first`: the push carries hops 0 and 1 (up_mask bits 0..26 and 27..53), walked in that order, else the newest hop alone (bits
-// 0..26); up_mask is 0 when the detector was off.  `clear`: a first push, or the first push after msk144_set_wideband_gate: earlier
-// activity counts as none.  A hop is active iff at least min_up of its 27 blocks are up.  Returns whether the channel's window of
-// this push is decoded: always, or since <= hold after the walk.
+// The gate rule, once, for one channel and one push.  `since`: hops since the channel's last active one, saturating at kSinceQuiet.
+// `first` and up_mask: as hop_up_bits takes them; a hop is active iff at least min_up of its 27 blocks are up.  `clear`: a first
+// push, or the first push after msk144_set_wideband_gate: earlier activity counts as none.  Returns whether the channel's window
+// of this push is decoded: always, or since <= hold after the walk.
 //   The window of push k covers hops k - 1 and k.  With hold >= 1 every window that contains an active hop is decoded: an active
 //   hop k gives since = 0 in push k and since <= 1 in push k + 1.  No window is decoded because of activity more than `hold` hops
 //   old.  hold = 0 decodes only the windows whose newest hop is active.
 MSK144WB_HD inline bool gate_step(int32_t& since, bool first, bool clear, uint64_t up_mask, bool always, int32_t hold, int32_t min_up)
 {
-    int32_t s = clear ? kGateQuiet : since;
+    int32_t s = clear ? kSinceQuiet : since;
     for(int i = first ? 0 : 1; i < 2; i++)
     {
-        const uint64_t bits = (up_mask >> (first ? kGateHopBlocks * i : 0)) & ((1ull << kGateHopBlocks) - 1);
         int32_t up = 0;
-        for(uint64_t b = bits; b; b &= b - 1) up++;
-        s = up >= min_up ? 0 : s < kGateQuiet ? s + 1 : kGateQuiet;
+        for(uint64_t b = hop_up_bits(up_mask, first, i); b; b &= b - 1) up++;
+        s = since_next(s, up >= min_up);
     }
     since = s;
     return always || s <= hold;
@@ -1002,7 +1002,7 @@ inline int32_t gate_max_channels(const GateParams& p, int channels) { return p.m
 inline std::string check_gate(const GateParams& p, int channels)
 {
     if(p.hold < 0 || p.hold > kGateMaxHold) return "gate hold must lie within 0..16 hops";
-    if(p.min_up < 1 || p.min_up > kGateHopBlocks) return "gate min_up must lie within 1..27 blocks";
+    if(p.min_up < 1 || p.min_up > kHopBlocks) return "gate min_up must lie within 1..27 blocks";
     if(p.max_channels < 0 || p.max_channels > channels) return "gate max_channels must lie within 1.." + std::to_string(channels) + ", or be 0 for all";
     return std::string();
 }
@@ -1013,7 +1013,7 @@ inline std::string check_gate(const GateParams& p, int channels)
 class Gate
 {
 public:
-    Gate(int channels, const GateParams& p, const uint8_t* always) : p_(p), since_(static_cast<size_t>(channels), kGateQuiet), always_(static_cast<size_t>(channels), 0)
+    Gate(int channels, const GateParams& p, const uint8_t* always) : p_(p), since_(static_cast<size_t>(channels), kSinceQuiet), always_(static_cast<size_t>(channels), 0)
     {
         for(int c = 0; always && c < channels; c++) always_[static_cast<size_t>(c)] = always[c] != 0;
     }

@@ -381,7 +381,7 @@ inline bool parse_wideband_gate(const char* arg, WidebandOptions& w)
     const std::vector<std::string> f = split_fields(arg, ':');
     if(f.size() > 4) return false;
     if(!f[0].empty() && !parse_int_in(f[0], 0, msk144wb::kGateMaxHold, w.gate_params.hold)) return false;
-    if(f.size() > 1 && !f[1].empty() && !parse_int_in(f[1], 1, msk144wb::kGateHopBlocks, w.gate_params.min_up)) return false;
+    if(f.size() > 1 && !f[1].empty() && !parse_int_in(f[1], 1, msk144wb::kHopBlocks, w.gate_params.min_up)) return false;
     if(f.size() > 2 && !f[2].empty() && !parse_int_in(f[2], 0, INT32_MAX, w.gate_params.max_channels)) return false;
     return f.size() < 4 || f[3].empty() || parse_channel_list(f[3], INT32_MAX - 1, w.gate_always);
 }

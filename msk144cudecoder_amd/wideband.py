@@ -845,13 +845,31 @@ class PingSpectra:
         return out
 
 
+# ---- the hop rule that the capture and the gate share (csrc/wideband.h: hop_up_bits, since_next) ----
+
+HOP_BLOCKS = HOP_OUT // PING_BLOCK   # 27
+SINCE_QUIET = 17                     # a channel's `since`, the hops since its last active one, saturates here
+
+
+def hop_masks(records, c: int, first: bool) -> list:
+    """The 27 up bits of each hop that a push brings channel c, oldest hop first: hops 0 and 1 of a first push, else the newest
+    alone.  records: PING_DTYPE [channel], or None: the detector was off, no block is up."""
+    mask = 0 if records is None else int(records["up_mask"][c])
+    hop_mask = (1 << HOP_BLOCKS) - 1
+    return [mask & hop_mask, (mask >> HOP_BLOCKS) & hop_mask] if first else [mask & hop_mask]
+
+
+def since_next(since: int, active: bool) -> int:
+    return 0 if active else min(since + 1, SINCE_QUIET)
+
+
 # ---- per-ping capture of a channel's hops (msk144_set_wideband_capture) ----
 
 # msk144_wideband_capture_unit (include/msk144hip.h); HipDecoder.wideband_capture() returns the same records
 CAPTURE_DTYPE = np.dtype([("channel", "<i4"), ("flags", "<i4"), ("hop", "<i8")])
 assert CAPTURE_DTYPE.itemsize == 16
 CAPTURE_UNIT_BYTES = 2 * HOP_OUT     # one hop of one channel: 2592 int8 I/Q pairs
-CAPTURE_HOP_BLOCKS = HOP_OUT // PING_BLOCK   # 27
+CAPTURE_HOP_BLOCKS = HOP_BLOCKS
 CAPTURE_MAX_POST = 16
 CAPTURE_MAX_UNITS = 16384
 CAPTURE_MAX_LISTED = 16
@@ -867,7 +885,7 @@ def capture_default_max_units(channels: int) -> int:
 
 class Capture:
     """The capture rule of the contract (include/msk144hip.h) in Python integers, push by push.  Per channel: the hops since the last
-    active one (None: none that counts) and whether the newest hop was emitted.  push() takes the ping records of one push
+    active one (SINCE_QUIET: none that counts) and whether the newest hop was emitted.  push() takes the ping records of one push
     (PING_DTYPE [channel], or None: the detector was off) and returns (units, total): the stored units as CAPTURE_DTYPE, by channel
     then by hop, and the number of units the push had.  restart() stands for msk144_set_wideband_capture in mid-stream: the state is
     cleared, the hop count stays.  `hop` is the newest hop of the last push; a model that joins a stream in mid-stream sets it."""
@@ -888,26 +906,20 @@ class Capture:
         self.restart()
 
     def restart(self):
-        self.since = [None] * self.channels
+        self.since = [SINCE_QUIET] * self.channels
         self.emitted = [False] * self.channels
 
     def push(self, records, first: bool):
         if first:
             self.restart()
         self.hop = 1 if first else self.hop + 1
-        hop_mask = (1 << CAPTURE_HOP_BLOCKS) - 1
         units = []
         for c in range(self.channels):
-            mask = 0 if records is None else int(records["up_mask"][c])
             listed = c in self.listed
-            # the hops of this push and the activity of each: hops 0 and 1 of a first push, else the newest
-            hops = [(0, mask & hop_mask), (1, (mask >> CAPTURE_HOP_BLOCKS) & hop_mask)] if first else [(self.hop, mask & hop_mask)]
-            for k, active in hops:
-                if active:
-                    self.since[c] = 0
-                elif self.since[c] is not None:
-                    self.since[c] = self.since[c] + 1 if self.since[c] < CAPTURE_MAX_POST else None
-                near = self.since[c] is not None and self.since[c] <= self.post
+            masks = hop_masks(records, c, first)
+            for k, active in enumerate(masks, start=self.hop + 1 - len(masks)):   # hops 0 and 1 of a first push, else the newest
+                self.since[c] = since_next(self.since[c], active != 0)
+                near = self.since[c] <= self.post
                 if k > 0 and self.pre and active and not self.emitted[c]:
                     units.append((c, CAPTURE_PRE, k - 1))
                 if listed or near:
@@ -919,15 +931,16 @@ class Capture:
 # ---- the gate: only the channels with activity are decoded (msk144_set_wideband_gate) ----
 
 GATE_MAX_HOLD = 16
-GATE_QUIET = GATE_MAX_HOLD + 1      # `since` saturates here
-GATE_HOP_BLOCKS = CAPTURE_HOP_BLOCKS
+GATE_QUIET = SINCE_QUIET
+GATE_HOP_BLOCKS = HOP_BLOCKS
+assert CAPTURE_MAX_POST < SINCE_QUIET and GATE_MAX_HOLD < SINCE_QUIET
 # the defaults of msk144_wideband_gate_params (csrc/wideband.h GateParams): design parameters, not measurements
 GATE_DEFAULTS = dict(hold=1, min_up=1)
 
 
 class Gate:
     """The gate rule of the contract (include/msk144hip.h) in Python integers, push by push.  Per channel `since`: the hops since
-    the last active one, saturating at GATE_QUIET.  push() takes the ping records of one push (PING_DTYPE [channel], or None: the
+    the last active one, saturating at SINCE_QUIET.  push() takes the ping records of one push (PING_DTYPE [channel], or None: the
     detector was off) and returns (list, total): the channels whose window the push decodes as int32, ascending, at most
     max_channels of them, and the number that qualified.  restart() stands for msk144_set_wideband_gate in mid-stream."""
 
@@ -952,12 +965,10 @@ class Gate:
     def push(self, records, first: bool):
         if first:
             self.restart()
-        hop_mask = (1 << GATE_HOP_BLOCKS) - 1
         chosen = []
         for c in range(self.channels):
-            mask = 0 if records is None else int(records["up_mask"][c])
-            for bits in ([mask & hop_mask, (mask >> GATE_HOP_BLOCKS) & hop_mask] if first else [mask & hop_mask]):
-                self.since[c] = 0 if bin(bits).count("1") >= self.min_up else min(self.since[c] + 1, GATE_QUIET)
+            for bits in hop_masks(records, c, first):
+                self.since[c] = since_next(self.since[c], bin(bits).count("1") >= self.min_up)
             if c in self.always or self.since[c] <= self.hold:
                 chosen.append(c)
         return np.array(chosen[:self.max_channels], dtype=np.int32), len(chosen)

@@ -412,7 +412,10 @@ def test_a_failing_device_loop_stops_its_siblings(exe, tmp_path):
     paths = [str(tmp_path / f"live{c}.fifo") for c in range(n)]
     for p in paths:
         os.mkfifo(p)
-    proc = subprocess.Popen([exe, "--devices=0,1", "--inputs=" + ",".join(paths)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+    # The stub fails device 1's fourth batch, so the counts below hold only while every batch carries both streams of its device:
+    # a batch waits for the second one as long as it takes (the writers deliver within tens of milliseconds, so the wait never
+    # runs out), and device 1's writers go at half the pace, so that device 0 is hops ahead when device 1 fails
+    proc = subprocess.Popen([exe, "--devices=0,1", "--hop-timeout-ms=5000", "--inputs=" + ",".join(paths)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                             env=dict(os.environ, MSK144_STUB_DECODE_MS="5", MSK144_STUB_DEVICES="2", MSK144_STUB_FAIL_DEVICE="1", MSK144_STUB_FAIL_AFTER="3"))
     stop = threading.Event()
 
@@ -423,7 +426,7 @@ def test_a_failing_device_loop_stops_its_siblings(exe, tmp_path):
                 f.write(x[:5184 * 2])
                 off = 5184 * 2
                 while not stop.is_set() and off < len(x):
-                    time.sleep(0.02)
+                    time.sleep(0.02 if c < 2 else 0.04)
                     f.write(x[off:off + 5184])
                     off += 5184
         except BrokenPipeError:

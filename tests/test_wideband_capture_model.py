@@ -7,7 +7,7 @@ through libmsk144host.so - and the file rule, wideband.CaptureSegments against t
 2. Overflow: max_units at the largest push's count exactly, one below it, and 1: the stored units are the first max_units of the
    unbounded run's and the totals are unchanged - decisions do not depend on drops.
 3. Details the random runs may miss: the detector off (records None), restart() in mid-stream with its pre-roll, the documented
-   single-hop segments, parameters out of range.
+   single-hop segments, parameters out of range, and the stop of `since`: post = 16 behind one active hop, with and without restart().
 4. CaptureSegments: names, gaps, capture.log lines and at= offsets, Python and C++ writing the same bytes.
 5. The planned scene through the float64 channeliser model and wideband.Pings: its activity equals the plan and holds every case of
    wideband_capture_check.CASES, so the GPU test's scene is known to be a good one.
@@ -127,6 +127,26 @@ def test_detector_off_restart_and_single_hop_segments():
     c[0, 0], c[0, 3] = False, True
     assert [[int(k) for k in u["hop"]] for u, _ in cc.brute(c, 0, 0)] == [[], [], [3], []]
     assert [[int(k) for k in u["hop"]] for u, _ in cc.brute(c, 1, 0)] == [[], [], [2, 3], []]
+
+
+def test_since_saturates_one_hop_past_the_longest_post():
+    """Hop 0 active alone, 20 silent hops, post = 16: the tail runs through hop 16 and `since` then stays at its stop.  restart()
+    ahead of the push that carries hop 5 ends the tail there: earlier activity counts as none."""
+    a = np.zeros((1, 21), dtype=bool)
+    a[0, 0] = True
+    recs = cc.push_records(a)
+    for pre in (0, 1):
+        whole = cc.brute(a, pre, 16)
+        assert [[int(k) for k in u["hop"]] for u, _ in whole] == [[0, 1]] + [[k] for k in range(2, 17)] + [[]] * 4
+        for restart_at, want in ((None, whole), (4, whole[:4] + cc.brute(np.zeros_like(a), pre, 16)[4:])):
+            py, cpp = wb.Capture(1, pre, 16), cc.HostCapture(1, pre, 16)
+            for i, r in enumerate(recs):
+                if i == restart_at:
+                    py.restart()
+                    cpp.restart()
+                cc.assert_units(py.push(r, i == 0), want[i], f"pre {pre} restart {restart_at} push {i}: wideband.Capture")
+                cc.assert_units(cpp.push(r, i == 0), want[i], f"pre {pre} restart {restart_at} push {i}: the C++ rule")
+            assert restart_at is None or all(t == 0 for _, t in want[4:])
 
 
 def test_parameters_out_of_range_are_refused():

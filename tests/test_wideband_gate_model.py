@@ -7,7 +7,7 @@ libmsk144host.so.
 2. max_channels below the qualifying count: the first max_channels in ascending order, the totals unchanged - `since` moves for
    every channel whatever was dropped.
 3. The first push walks hops 0 and 1 in that order; restart() (msk144_set_wideband_gate in mid-stream) forgets earlier activity; the
-   detector off (records None) leaves the always channels.
+   detector off (records None) leaves the always channels; `since` stops one hop past hold = 16, against the brute force.
 4. The coverage property for hold >= 1: every window that contains an active hop is decoded.  Its converse: no window is decoded
    more than `hold` hops after the last activity.  hold = 0 decodes exactly the windows whose newest hop is active.
 5. check_gate's refusals, and the same parameters refused by wideband.Gate.
@@ -118,6 +118,17 @@ def test_the_first_push_walk_restart_and_the_detector_off():
     rng = np.random.default_rng(12)
     records = gc.random_records(rng, 65, 12, 0.2)
     three_forms(records, 65, 3, 1, (7,), restart_at=5, what="restart at push 5")
+
+
+def test_since_saturates_one_hop_past_the_longest_hold():
+    """Hop 0 active alone, 20 silent hops, hold = 16: the channel is listed through hop 16 and `since` then stays at its stop.
+    restart() ahead of the push that carries hop 5 ends that there: earlier activity counts as none."""
+    records = one_channel([1 << 5] + [0] * 19)
+    lists, a = three_forms(records, 1, 16, 1, what="hold 16")
+    assert a.shape == (1, 21) and a[0].tolist() == [True] + [False] * 20
+    assert [t for _, t in lists] == [1] * 16 + [0] * 4           # push p carries hop p + 1
+    lists, _ = three_forms(records, 1, 16, 1, restart_at=4, what="hold 16, restart at push 4")
+    assert [t for _, t in lists] == [1] * 4 + [0] * 16
 
 
 @pytest.mark.parametrize("hold", [0, 1, 3, 16])

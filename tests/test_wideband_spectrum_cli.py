@@ -114,7 +114,7 @@ def test_no_option_no_new_call(new, old):
         err = r.stderr.decode()
         assert r.returncode == 0
         assert "spectrum" not in err
-        outs.append((r.stdout, re.sub(r"worst latency \d+ ms", "worst latency X ms", re.sub(r"\d+ late", "N late", err))))
+        outs.append((re.sub(rb"date=\d{14}", b"date=X", r.stdout), re.sub(r"worst latency \d+ ms", "worst latency X ms", re.sub(r"\d+ late", "N late", err))))
     assert outs[0] == outs[1]
 
 
