@@ -834,6 +834,66 @@ int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_
 /* units[max_units], data[max_units][5184], max_units as last set: the last push, made since then */
 int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* units, int8_t* data /*[max_units][5184]*/, int32_t* count, int32_t* total);
 
+/* ---- Each captured hop as 12 kHz audio (no reference counterpart) ----
+ *
+ * The capture's units are complex int8 I/Q, which only a read_mode 2 handle reads back.  What the rest of the MSK144 world takes -
+ * WSJT-X's File > Open, the reference's default read mode, this library's own audio front end - is real 16-bit audio at 12000
+ * samples per second with the signal around 1500 Hz.  With the audio on, a 64-tap complex band-pass runs on every channel's stored
+ * int8 values, a 96-entry integer phasor table takes the result to a real tone frequency, and the audio of the capture's units can be
+ * read beside them.  Exact integer arithmetic throughout (csrc/audio.hip; the same rule on the host is csrc/wideband.h audio_push).
+ * Per channel, with x[n] = I + jQ the stored int8 values as integers - what msk144_dump_wideband_hop returns, behind the notch - and
+ * n counted from the stream's first stored sample:
+ *
+ *   Filter:     z[n] = sum over k < 64 of b[k] . x[n - k], the ping band's filter: |Re z|, |Im z| <= 2^21, int32 is exact.
+ *   Mix:        a[n] = Re z[n] . pr[n mod 96] - Im z[n] . pi[n mod 96] in int64, |a| <= 2^37: the real part of z[n] w[n mod 96].
+ *               A hop is 2592 = 27 x 96 samples, so n mod 96 is the index inside the hop mod 96, and there is no phase state.
+ *   Output:     y[n] = clamp((a[n] + 2^(shift - 1)) >> shift, -32768, 32767), 1 <= shift <= 40, the shift right an arithmetic
+ *               shift (floor).  `clamped` counts the samples of a hop that the clamp changed.
+ *   Tail:       x[n - k] reaches into the channel's previous 63 stored samples, kept per channel on the device as the ping band's.
+ *               A first push starts from an all-zero tail and filters hops 0 and 1.  The first push after an accepted
+ *               msk144_set_wideband_audio starts from an all-zero tail as well and filters both hops the ring window then holds,
+ *               the hop before the newest and then the newest, so that every unit a push can emit, the pre-roll unit included, has
+ *               audio.  Every other push filters its newest hop and continues the tail.  A change of gain or an AGC step does not
+ *               touch the tail.
+ *   Ring:       the audio of hop k lies in slot k & 1 of a device ring [channels][2][2592] int16, with its clamp count beside it;
+ *               written on every push made with the audio on, whether or not the capture is on.
+ *   Read:       msk144_wideband_capture_audio reports the last push and synchronises like msk144_wideband_capture.  Row u is the
+ *               audio of unit u of msk144_wideband_capture for that push - the same count, order and drop rule - and clamped[u]
+ *               that hop's count.  Nothing past row *count - 1 is written.
+ *   Delay:      the filter's group delay of 31.5 samples (2.6 ms): the audio lags the unit's I/Q by that much.
+ *   Default design (msk144host_wideband_audio_design in libmsk144host.so, csrc/wideband.h audio_design; the program and the Python
+ *               side both take it from there): the taps of the ping band's design for (centre_hz, halfwidth_hz);
+ *               w[m] = (rint(16384 cos t), rint(16384 sin t)), t = 2 pi (tone_hz - centre_hz) m / 12000;
+ *               shift = rint(log2 |B(centre)| + 6), B the response of the rounded taps.  A tone of amplitude A at f inside the band
+ *               comes out at tone + (f - centre) Hz with amplitude near 256 A: an int8 full scale maps near an int16 full scale.
+ *               The figure 256 is a design parameter, not a measurement.  500 <= halfwidth <= 3000, |centre| + halfwidth <= 6000,
+ *               halfwidth <= tone <= 6000 - halfwidth, and tone - centre a multiple of 125 Hz, because the table has 96 entries.
+ *               Defaults: halfwidth 1250, centre 0, tone 1500 (the program takes --center-frequency as the centre).  The band's
+ *               skirt reaches the stop band about 310 Hz outside the half-width; with halfwidth > tone - 310 part of the skirt
+ *               folds over 0 Hz, which is the caller's choice.  In a CPU check of the integer model (no GPU measurement stands
+ *               behind these figures, nor behind the default half-width) tones inside the band came out within +0.7 .. +2.4 dB of
+ *               256 A, and a tone 700 to 3500 Hz outside the band edge at least 36.1 dB below it (tests/test_wideband_audio_model.py).
+ *   Order:      msk144_set_wideband_audio(h, &p) takes effect from the next push and allocates everything it needs - a push
+ *               allocates nothing; the dense rows follow the capture's max_units, and a larger one reallocates them in whichever
+ *               `set` brings it.  (h, NULL) switches the audio off, as msk144_set_wideband does.  With the audio off a push issues
+ *               the calls it issues without it; on or off, every hop, level, ping record, capture unit and decode is byte for byte
+ *               the same.  No atomics: the same stream pushed twice gives the same bytes.
+ *   Refused:    MSK144_EINVAL outside wideband mode and for a shift outside 1..40 (a refused call changes nothing);
+ *               MSK144_ESTATE from msk144_wideband_capture_audio wherever msk144_wideband_capture answers it, and when the last
+ *               push was made without the audio. */
+#define MSK144_AUDIO_PHASORS 96
+typedef struct msk144_wideband_audio_params
+{
+    int8_t taps[64][2];    /* (br, bi) of b[0] .. b[63]; any int8 values are valid */
+    int16_t phasor[96][2]; /* (pr, pi) of w[0] .. w[95]; any int16 values are valid */
+    int32_t shift;         /* 1..40 */
+} msk144_wideband_audio_params;
+
+/* NULL: off */
+int msk144_set_wideband_audio(msk144_handle* h, const msk144_wideband_audio_params* p);
+/* audio[max_units][2592], clamped[max_units], max_units as last set for the capture: the last push, made since then */
+int msk144_wideband_capture_audio(msk144_handle* h, int16_t* audio /*[max_units][2592]*/, int32_t* clamped /*[max_units]*/, int32_t* count);
+
 /* ---- The gate: only the channels with activity are decoded (no reference counterpart) ----
  *
  * A meteor-scatter channel is noise for minutes and carries a ping for a fraction of a second, yet every channel's window goes

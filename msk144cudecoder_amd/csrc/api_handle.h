@@ -178,6 +178,22 @@ struct Wideband
         msk144wb::CaptureUnit* d_units = nullptr;     // [rows]
         uint8_t* d_data = nullptr;                    // [rows][5184]
     } capture;
+    // the audio (msk144_set_wideband_audio): the ring is written by every push made with it on; the dense rows are the capture's
+    // units' and follow capture.rows (`rows`: what they hold; a larger one frees them and allocates anew, in whichever `set` brings
+    // it).  pushed: the last push wrote the ring and no `set` has come since
+    struct Audio
+    {
+        bool on = false, pushed = false, restart = false;
+        int32_t shift = 0;
+        int rows = 0;
+        int8_t* d_taps = nullptr;          // [64][2]
+        int16_t* d_phasor = nullptr;       // [96][2]
+        uint8_t* d_tails = nullptr;        // [channels][128]: two zero bytes, then the 63 stored samples before the next push
+        int16_t* d_ring = nullptr;         // [channels][2][2592]: the audio of hop k in row k & 1
+        int32_t* d_clamped = nullptr;      // [channels][2]
+        int16_t* d_rows = nullptr;         // [rows][2592]
+        int32_t* d_row_clamped = nullptr;  // [rows]
+    } audio;
     // the gate (msk144_set_wideband_gate).  pushed: the last push left a header and no `set` has come since.  `planned` is recorded
     // behind the copy of the header to `header`: what msk144_decode_stages and msk144_wideband_gate wait for, not the stream
     struct Gate

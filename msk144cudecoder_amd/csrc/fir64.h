@@ -1,5 +1,6 @@
 // fir64: z[n] = sum_k b[k] x[n - k], 64 complex int8 taps over a channel's staged int8 hops, for the kernels that end it their own
-// way (pingband.hip: block energies; notch.hip: x[n - 31] - z, in place).  What msk144wb::fir64_push computes on the host.
+// way (pingband.hip: block energies; notch.hip: x[n - 31] - z, in place; audio.hip: mixed to real int16 audio).  What
+// msk144wb::fir_push computes on the host.
 //
 // One workgroup of four waves per channel.  stage() puts the channel's 63-sample tail and the push's row (two rows on a first push)
 // in LDS with 16-byte loads, so that stored sample m of the push lies at byte 128 + 2m and the tail in bytes 2..127 in front of it
@@ -51,7 +52,10 @@ struct Lds
 
 // Everything up to the new tail.  first_halves, hops: [channels][5184] bytes; taps[64][2]; tails[channels][128] bytes, taken as all
 // zero with `restart`.  The workgroup's barrier is in here: what the caller writes to global memory it writes behind this call.
-__device__ __forceinline__ void stage(Lds& s, const uint4* first_halves, const uint4* hops, int first, size_t ch, const int8_t* taps, int restart, uint4* tails)
+// row_vecs: the 16-byte words from one channel's row to the next in first_halves and in hops - 324 for the staged hops, 648 where
+// the two are the halves of the hop ring's windows (audio.hip).
+__device__ __forceinline__ void stage(Lds& s, const uint4* first_halves, const uint4* hops, int first, size_t ch, const int8_t* taps, int restart, uint4* tails,
+                                      size_t row_vecs = kRowVecs)
 {
     const int tid = threadIdx.x;
     const int nvec = first ? 2 * kRowVecs : kRowVecs;
@@ -60,7 +64,7 @@ __device__ __forceinline__ void stage(Lds& s, const uint4* first_halves, const u
     for(int i = tid; i < nvec; i += kThreads)
     {
         const bool head = first && i < kRowVecs;
-        s.x[kTailVecs + i] = (head ? first_halves : hops)[ch * kRowVecs + (first && !head ? i - kRowVecs : i)];
+        s.x[kTailVecs + i] = (head ? first_halves : hops)[ch * row_vecs + (first && !head ? i - kRowVecs : i)];
     }
     if(tid < kTapDwords)
     {

@@ -150,6 +150,18 @@ void launch_waterfall(const int8_t* first_halves, const int8_t* hops, int first,
 void launch_capture(const void* ring, const msk144wb::PingRecord* records, const uint8_t* listed, msk144wb::CaptureState* state, int channels, int first, int clear,
                     const msk144wb::CaptureParams& p, long long newest, msk144wb::PlanHeader* header, msk144wb::CaptureUnit* units, void* data, hipStream_t stream);
 
+// the audio of a push (audio.hip; contract in include/msk144hip.h), behind launch_hop_ring and ahead of launch_capture: ring[channels]
+// the 10368-byte windows; taps[64][2] int8 and phasor[96][2] int16 on the device; tails[channels][128] bytes as launch_pingband's.
+// `newest` is the newest hop of the push.  With both != 0 - a first push, or the first one after msk144_set_wideband_audio - the tail
+// is taken as all zero and both hops of the window are filtered, else the newest alone.  Writes the audio of hop k to row k & 1 of
+// audio[channels][2][2592] int16 and its clamp count to clamped[channels][2].
+void launch_audio(const void* ring, int channels, int both, long long newest, const int8_t* taps, const int16_t* phasor, int shift, uint8_t* tails, int16_t* audio,
+                  int32_t* clamped, hipStream_t stream);
+// ... and behind launch_capture on the same stream: row u of rows[max_units][2592] and row_clamped[u] for the header's first `count`
+// units, from row (channel, hop & 1) of audio and clamped.
+void launch_audio_copy(const int16_t* audio, const int32_t* clamped, const msk144wb::PlanHeader* header, const msk144wb::CaptureUnit* units, int max_units, int16_t* rows,
+                       int32_t* row_clamped, hipStream_t stream);
+
 // the gate of a push (gate.hip; contract in include/msk144hip.h).  Plan, behind launch_pings: records[channels] the push's ping
 // records or nullptr (the detector was off), always[channels] the always flags; `newest` is the newest hop of the push; `clear`: a
 // first push or the first one after msk144_set_wideband_gate.  Moves since[channels] and writes the header and the first

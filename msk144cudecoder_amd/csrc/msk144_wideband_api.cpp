@@ -353,12 +353,44 @@ int wb_plan(msk144_handle* h, const WbPush& p, Option& o, Launch launch)
     return MSK144_OK;
 }
 
-// Capture, behind the ring kernel: the ring now holds the push's newest hop, number m_next / 2592 - 1, and the one before it
+// The audio, behind the ring kernel: the ring now holds the push's newest hop, number m_next / 2592 - 1, and the one before it.
+// A first push and the first one after msk144_set_wideband_audio filter both from an all-zero tail, every other push the newest
+int wb_audio(msk144_handle* h, const WbPush& p)
+{
+    auto& a = h->wb.audio;
+    a.pushed = a.on;
+    if(!a.on) return MSK144_OK;
+    ev_begin(h);
+    launch_audio(h->d_ring, h->wb.channels, p.first || a.restart ? 1 : 0, h->wb.core.m_next / kHopSamples - 1, a.d_taps, a.d_phasor, a.shift, a.d_tails, a.d_ring, a.d_clamped, h->stream);
+    ev_end(h, MSK144_T_FRONTEND);
+    a.restart = false;
+    HIP_TRY(h, hipGetLastError());
+    return MSK144_OK;
+}
+
+// The dense audio rows follow the capture's: with the audio on and more capture rows than they hold, the old ones, which nothing
+// reads any more, are freed and larger ones take their place (the caller's wb_quiesce has waited for the kernels that wrote them)
+int wb_audio_rows(msk144_handle* h)
+{
+    auto& w = h->wb;
+    auto& a = w.audio;
+    if(!a.on || w.capture.rows <= a.rows) return MSK144_OK;
+    a.rows = 0;
+    dev_free(w.mem, &a.d_rows);
+    dev_free(w.mem, &a.d_row_clamped);
+    if(wb_ensure(h, &a.d_rows, static_cast<size_t>(w.capture.rows) * msk144wb::kAudioHopSamples) || wb_ensure(h, &a.d_row_clamped, static_cast<size_t>(w.capture.rows))) return MSK144_ENOMEM;
+    a.rows = w.capture.rows;
+    return MSK144_OK;
+}
+
+// Capture, behind the ring kernel and the audio: the plan and the copy of the units' I/Q, and with the audio on the copy of their audio
 int wb_capture(msk144_handle* h, const WbPush& p)
 {
     auto& c = h->wb.capture;
+    const auto& a = h->wb.audio;
     return wb_plan(h, p, c, [&](const msk144wb::PingRecord* records, int first, int clear) {
         launch_capture(h->d_ring, records, c.d_listed, c.d_state, h->wb.channels, first, clear, c.params, h->wb.core.m_next / kHopSamples - 1, c.d_header, c.d_units, c.d_data, h->stream);
+        if(a.on) launch_audio_copy(a.d_ring, a.d_clamped, c.d_header, c.d_units, c.params.max_units, a.d_rows, a.d_row_clamped, h->stream);
     });
 }
 
@@ -499,6 +531,7 @@ int msk144_push_wideband(msk144_handle* h, int32_t slot, int32_t first)
     w.started = true;
     w.last = p;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, w.channels, h->stream);
+    if((rc = wb_audio(h, p)) != MSK144_OK) return rc;
     if((rc = wb_capture(h, p)) != MSK144_OK) return rc;
     if((rc = run_frontend(h, h->d_input)) != MSK144_OK) return rc;
     return wb_gate_gather(h);
@@ -870,6 +903,7 @@ int msk144_set_wideband_capture(msk144_handle* h, const msk144_wideband_capture_
         if(wb_ensure(h, &c.d_units, static_cast<size_t>(cp.max_units)) || wb_ensure(h, &c.d_data, static_cast<size_t>(cp.max_units) * msk144wb::kCaptureUnitBytes)) return MSK144_ENOMEM;
         c.rows = cp.max_units;
     }
+    if(const int rc = wb_audio_rows(h); rc != MSK144_OK) return rc;  // capture stays off
     std::vector<uint8_t> listed(C, 0);
     for(int i = 0; i < p->num_listed; i++) listed[static_cast<size_t>(p->listed[i])] = 1;
     c.params = cp;
@@ -895,6 +929,61 @@ int msk144_wideband_capture(msk144_handle* h, msk144_wideband_capture_unit* unit
     }
     *count = head.count;
     *total = head.total;
+    return MSK144_OK;
+}
+
+int msk144_set_wideband_audio(msk144_handle* h, const msk144_wideband_audio_params* p)
+{
+    if(const int rc = wb_quiesce(h, "msk144_set_wideband_audio"); rc != MSK144_OK) return rc;
+    auto& a = h->wb.audio;
+    static_assert(sizeof(msk144_wideband_audio_params) == sizeof(msk144wb::AudioParams) && offsetof(msk144_wideband_audio_params, shift) == offsetof(msk144wb::AudioParams, shift) &&
+                      offsetof(msk144_wideband_audio_params, phasor) == offsetof(msk144wb::AudioParams, phasor),
+                  "msk144wb::AudioParams is msk144_wideband_audio_params");
+    if(!p)
+    {
+        a.on = a.pushed = false;
+        return MSK144_OK;
+    }
+    msk144wb::AudioParams ap;
+    std::memcpy(&ap, p, sizeof(ap));
+    if(const std::string why = msk144wb::check_audio(ap); !why.empty()) return fail(h, MSK144_EINVAL, why);
+    // an accepted `set` ends the last push's rows, as the capture's does: the read entry answers MSK144_ESTATE until the next push
+    a.on = a.pushed = false;
+    const size_t C = static_cast<size_t>(h->wb.channels);
+    if(wb_ensure(h, &a.d_taps, sizeof(ap.taps)) || wb_ensure(h, &a.d_phasor, 2 * static_cast<size_t>(msk144wb::kAudioPhasors)) || wb_ensure(h, &a.d_tails, C * 2 * msk144wb::kFirTaps) ||
+       wb_ensure(h, &a.d_ring, C * 2 * msk144wb::kAudioHopSamples) || wb_ensure(h, &a.d_clamped, C * 2))
+        return MSK144_ENOMEM;
+    HIP_TRY(h, hipMemcpy(a.d_taps, ap.taps, sizeof(ap.taps), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(a.d_phasor, ap.phasor, sizeof(ap.phasor), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(a.d_tails, 0, C * 2 * msk144wb::kFirTaps));
+    HIP_TRY(h, hipMemset(a.d_clamped, 0, sizeof(int32_t) * C * 2));
+    a.shift = ap.shift;
+    a.on = true;
+    if(const int rc = wb_audio_rows(h); rc != MSK144_OK)
+    {
+        a.on = false;
+        return rc;
+    }
+    a.restart = true;
+    return MSK144_OK;
+}
+
+int msk144_wideband_capture_audio(msk144_handle* h, int16_t* audio, int32_t* clamped, int32_t* count)
+{
+    if(!h || !audio || !clamped || !count) return fail(h, MSK144_EINVAL, "null argument");
+    const auto& c = h->wb.capture;
+    const auto& a = h->wb.audio;
+    const char* why = !c.pushed ? "no wideband push has been made with capture on since it was last set" : "the last wideband push was made without the audio";
+    if(const int rc = wb_read_ready(h, "msk144_wideband_capture_audio", c.pushed && a.pushed, why); rc != MSK144_OK) return rc;
+    msk144wb::PlanHeader head{};
+    HIP_TRY(h, hipMemcpy(&head, c.d_header, sizeof(head), hipMemcpyDeviceToHost));
+    if(const int rc = wb_plan_header(h, "msk144_wideband_capture_audio", head, std::min(c.params.max_units, a.rows)); rc != MSK144_OK) return rc;
+    if(head.count)
+    {
+        HIP_TRY(h, hipMemcpy(audio, a.d_rows, sizeof(int16_t) * msk144wb::kAudioHopSamples * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(clamped, a.d_row_clamped, sizeof(int32_t) * static_cast<size_t>(head.count), hipMemcpyDeviceToHost));
+    }
+    *count = head.count;
     return MSK144_OK;
 }
 

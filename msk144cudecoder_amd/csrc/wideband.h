@@ -860,25 +860,139 @@ private:
     int64_t hop_ = 0;
 };
 
+// ---- each captured hop as 12 kHz audio (msk144_set_wideband_audio, msk144_wideband_capture_audio; the kernels': csrc/audio.hip) ----
+
+constexpr int kAudioPhasors = 96;                          // w[n mod 96]: a hop is 27 x 96 samples, so there is no phase state
+constexpr int kAudioHopSamples = kCaptureUnitBytes / 2;    // 2592 int16 per unit
+constexpr int kAudioMinShift = 1, kAudioMaxShift = 40;
+constexpr int kAudioToneStepHz = kOutRate / kAudioPhasors; // 125: tone - centre is a multiple of it
+constexpr int kAudioPhasorScale = 16384;
+constexpr int kAudioLevelBits = 6;                         // shift = log2 |B| + 14 - 8: amplitude A comes out near 256 A
+// the defaults are design parameters, not measurements
+constexpr int kAudioDefaultHalfwidthHz = 1250;
+constexpr int kAudioDefaultToneHz = 1500;
+static_assert(kAudioHopSamples % kAudioPhasors == 0 && kOutRate % kAudioPhasors == 0, "whole turns of the table per hop");
+
+// msk144_wideband_audio_params, field for field
+struct AudioParams
+{
+    int8_t taps[kFirTaps][2];
+    int16_t phasor[kAudioPhasors][2];
+    int32_t shift;
+};
+static_assert(sizeof(AudioParams) == 516, "msk144_wideband_audio_params is 516 bytes");
+
+// One output sample, for device and host: y = clamp((Re z pr - Im z pi + 2^(shift - 1)) >> shift) in int64 (|a| <= 2^37); adds 1 to
+// `clamped` when the clamp changed the value
+MSK144WB_HD inline int32_t audio_out(int32_t zr, int32_t zi, int32_t pr, int32_t pi, int32_t shift, int32_t& clamped)
+{
+    const long long a = static_cast<long long>(zr) * pr - static_cast<long long>(zi) * pi;
+    const long long v = (a + (1ll << (shift - 1))) >> shift;
+    const long long y = v < -32768 ? -32768 : v > 32767 ? 32767 : v;
+    clamped += y != v ? 1 : 0;
+    return static_cast<int32_t>(y);
+}
+
+// The rules of msk144_set_wideband_audio that need no handle: any int8 taps and int16 phasors.  Empty string = valid.
+inline std::string check_audio(const AudioParams& p)
+{
+    if(p.shift < kAudioMinShift || p.shift > kAudioMaxShift) return "audio shift must lie within 1..40";
+    return std::string();
+}
+
+// The rules of the default design.  Empty string = valid.
+inline std::string check_audio_design(int centre_hz, int halfwidth_hz, int tone_hz)
+{
+    if(halfwidth_hz < kPingBandMinHalfwidthHz || halfwidth_hz > kPingBandMaxHalfwidthHz) return "audio half-width must lie within 500..3000 Hz";
+    if(std::abs(static_cast<long long>(centre_hz)) + halfwidth_hz > kOutRate / 2) return "audio band must lie within +-6000 Hz: |centre| + half-width <= 6000";
+    if(tone_hz < halfwidth_hz || tone_hz > kOutRate / 2 - halfwidth_hz) return "audio tone must lie within half-width .. 6000 - half-width Hz";
+    if((static_cast<long long>(tone_hz) - centre_hz) % kAudioToneStepHz != 0) return "audio tone - centre must be a multiple of 125 Hz (the phasor table has 96 entries)";
+    return std::string();
+}
+
+// The default design: the ping band's taps for (centre_hz, halfwidth_hz), w[m] = 16384 e^{j 2 pi (tone - centre) m / 12000} rounded
+// with rint - the angle reduced in integers first, (tone - centre) m mod 12000 - and shift = rint(log2 |B(centre)| + 6), so that a
+// tone of amplitude A inside the band comes out at tone + (f - centre) Hz with amplitude near 256 A.  The caller has checked the
+// arguments.  The band's skirt reaches the stop band about 310 Hz outside the half-width; with halfwidth > tone - 310 part of it
+// folds over 0 Hz.
+inline AudioParams audio_design(int centre_hz, int halfwidth_hz, int tone_hz)
+{
+    const PingBandParams b = ping_band_design(centre_hz, halfwidth_hz);
+    AudioParams p{};
+    std::memcpy(p.taps, b.taps, sizeof(p.taps));
+    for(int m = 0; m < kAudioPhasors; m++)
+    {
+        const long long turn = ((static_cast<long long>(tone_hz) - centre_hz) * m % kOutRate + kOutRate) % kOutRate;
+        const double t = 2.0 * M_PI * static_cast<double>(turn) / kOutRate;
+        p.phasor[m][0] = static_cast<int16_t>(std::rint(kAudioPhasorScale * std::cos(t)));
+        p.phasor[m][1] = static_cast<int16_t>(std::rint(kAudioPhasorScale * std::sin(t)));
+    }
+    p.shift = static_cast<int32_t>(std::rint(0.5 * std::log2(ping_band_response(b, centre_hz)) + kAudioLevelBits));
+    return p;
+}
+
+// The audio on the host, for one channel and one push: x[n][2] the n stored int8 samples of the push (n a multiple of 2592, the
+// first of them the first sample of a hop), tail[63][2] the channel's 63 stored samples before them, oldest first (all zero where
+// the library restarts: a first push, the first push after msk144_set_wideband_audio); writes y[n] and clamped[n / 2592] and moves
+// the tail on to the last 63 samples of x.  What libmsk144host.so holds the Python model and the kernel (audio.hip) to.
+inline void audio_push(const AudioParams& p, const int8_t* x, int n, int8_t* tail, int16_t* y, int32_t* clamped)
+{
+    FirParams f{};
+    std::memcpy(f.taps, p.taps, sizeof(f.taps));
+    std::vector<int8_t> s;
+    const std::vector<int32_t> z = fir_push(f, x, n, tail, s);
+    for(int k = 0; k < n / kAudioHopSamples; k++) clamped[k] = 0;
+    for(int m = 0; m < n; m++)
+        y[m] = static_cast<int16_t>(audio_out(z[static_cast<size_t>(2 * m)], z[static_cast<size_t>(2 * m + 1)], p.phasor[m % kAudioPhasors][0], p.phasor[m % kAudioPhasors][1], p.shift,
+                                              clamped[m / kAudioHopSamples]));
+}
+
+// The 44-byte RIFF/WAVE header of `samples` int16 samples of one channel at 12000 Hz: PCM format 1, block align 2, byte rate 24000
+constexpr int kWavHeaderBytes = 44;
+inline void wav_header(uint8_t* out, uint32_t samples)
+{
+    const uint32_t data = 2 * samples;
+    auto le = [&](int at, uint32_t v, int bytes) {
+        for(int i = 0; i < bytes; i++) out[at + i] = static_cast<uint8_t>(v >> (8 * i));
+    };
+    std::memcpy(out, "RIFF", 4);
+    le(4, data + kWavHeaderBytes - 8, 4);
+    std::memcpy(out + 8, "WAVEfmt ", 8);
+    le(16, 16, 4);
+    le(20, 1, 2);
+    le(22, 1, 2);
+    le(24, kOutRate, 4);
+    le(28, 2 * kOutRate, 4);
+    le(32, 2, 2);
+    le(34, 16, 2);
+    std::memcpy(out + 36, "data", 4);
+    le(40, data, 4);
+}
+
 // The file rule of --wideband-capture=DIR, once.  A channel's unit continues the channel's open segment iff its hop is the segment's
 // last hop + 1; otherwise the open segment ends and DIR/ch<c>_hop<k0>.cs8 begins.  Every write is open-append-close.  A segment
 // that ends - when the channel's next unit does not continue it, or at close() - appends one line to DIR/capture.log.  The last
 // segments of every channel are remembered, so that a ping line can name the file and the sample its event starts at.  A segment's
 // first write truncates a file of that name, while the log is only ever appended to: whoever writes a second stream into the same
 // DIR starts capture.log afresh first, as the program does, or its old lines name files whose content is no longer theirs.  Host only.
+// With audio rows (--wideband-audio) every segment has DIR/ch<c>_hop<k0>.wav beside it: wav_header, then the segment's audio rows as
+// little-endian int16; the header's two sizes are written when the segment ends, and its log line gains " wav=<name>".
 class CaptureSegments
 {
 public:
     CaptureSegments(const std::string& dir, const std::vector<int32_t>& offsets) : dir_(dir), offsets_(offsets), chan_(offsets.size()) {}
 
-    static std::string segment_name(int32_t channel, int64_t hop)
+    static std::string segment_name(int32_t channel, int64_t hop, const char* ext = ".cs8")
     {
-        return "ch" + std::to_string(channel) + "_hop" + std::to_string(hop) + ".cs8";
+        return "ch" + std::to_string(channel) + "_hop" + std::to_string(hop) + ext;
     }
+    static std::string wav_name(int32_t channel, int64_t hop) { return segment_name(channel, hop, ".wav"); }
 
-    // `count` units of one push and their rows data[count][5184]; false when a file could not be written
-    bool push(const CaptureUnit* units, const int8_t* data, int count)
+    // `count` units of one push and their rows data[count][5184], and with the audio on their audio[count][2592] and
+    // clamped[count] (else null); false when a file could not be written
+    bool push(const CaptureUnit* units, const int8_t* data, int count, const int16_t* audio = nullptr, const int32_t* clamped = nullptr)
     {
+        wav_ = wav_ || audio;
         for(int u = 0; u < count; u++)
         {
             const CaptureUnit& x = units[u];
@@ -893,6 +1007,8 @@ public:
             if(!f) return false;
             const bool ok = fwrite(data + static_cast<size_t>(u) * kCaptureUnitBytes, 1, kCaptureUnitBytes, f) == kCaptureUnitBytes;
             if(fclose(f) != 0 || !ok) return false;
+            if(audio && !push_wav(x.channel, ch, audio + static_cast<size_t>(u) * kAudioHopSamples)) return false;
+            if(audio) wav_clamped_ += clamped[u];
             ch.hops++;
             hops_++;
         }
@@ -924,15 +1040,19 @@ public:
     int64_t segments() const { return segments_; }
     int64_t hops() const { return hops_; }
     int64_t bytes() const { return hops_ * kCaptureUnitBytes; }
+    // the audio beside them: one WAV file per segment, a hop's samples per unit, and the samples of them that the clamp changed
+    int64_t wav_files() const { return wav_ ? segments_ : 0; }
+    int64_t wav_samples() const { return wav_ ? hops_ * kAudioHopSamples : 0; }
+    int64_t wav_clamped() const { return wav_clamped_; }
 
     // one line of DIR/capture.log; t = 0.216 k0 exact in three decimals
-    static std::string log_line(int32_t channel, int32_t offset_hz, int64_t k0, int64_t hops)
+    static std::string log_line(int32_t channel, int32_t offset_hz, int64_t k0, int64_t hops, bool wav = false)
     {
         char buf[256];
         const long long ms = static_cast<long long>(k0) * 216;
         snprintf(buf, sizeof(buf), "capture ch=%d offset=%d hop=%lld t=%lld.%03lld hops=%lld file=%s", channel, offset_hz, static_cast<long long>(k0), ms / 1000, ms % 1000,
                  static_cast<long long>(hops), segment_name(channel, k0).c_str());
-        return buf;
+        return wav ? std::string(buf) + " wav=" + wav_name(channel, k0) : std::string(buf);
     }
 
 private:
@@ -944,12 +1064,40 @@ private:
         int next = 0;
     };
 
+    // the segment's WAV file: begun with a header of no samples, or appended to
+    bool push_wav(int32_t c, const Chan& ch, const int16_t* row)
+    {
+        FILE* f = fopen((dir_ + "/" + wav_name(c, ch.k0)).c_str(), ch.hops ? "ab" : "wb");
+        if(!f) return false;
+        uint8_t head[kWavHeaderBytes], bytes[2 * kAudioHopSamples];
+        wav_header(head, 0);
+        for(int i = 0; i < kAudioHopSamples; i++)
+        {
+            bytes[2 * i] = static_cast<uint8_t>(static_cast<uint16_t>(row[i]) & 0xffu);
+            bytes[2 * i + 1] = static_cast<uint8_t>(static_cast<uint16_t>(row[i]) >> 8);
+        }
+        const bool ok = (ch.hops || fwrite(head, 1, sizeof(head), f) == sizeof(head)) && fwrite(bytes, 1, sizeof(bytes), f) == sizeof(bytes);
+        return fclose(f) == 0 && ok;
+    }
+
+    // the two sizes of a finished segment's WAV header
+    bool finish_wav(int32_t c, const Chan& ch)
+    {
+        FILE* f = fopen((dir_ + "/" + wav_name(c, ch.k0)).c_str(), "r+b");
+        if(!f) return false;
+        uint8_t head[kWavHeaderBytes];
+        wav_header(head, static_cast<uint32_t>(ch.hops * kAudioHopSamples));
+        const bool ok = fwrite(head, 1, sizeof(head), f) == sizeof(head);
+        return fclose(f) == 0 && ok;
+    }
+
     bool finish(int32_t c)
     {
         Chan& ch = chan_[static_cast<size_t>(c)];
+        if(wav_ && !finish_wav(c, ch)) return false;
         FILE* f = fopen((dir_ + "/capture.log").c_str(), "a");
         if(!f) return false;
-        const bool ok = fprintf(f, "%s\n", log_line(c, offsets_[static_cast<size_t>(c)], ch.k0, ch.hops).c_str()) > 0;
+        const bool ok = fprintf(f, "%s\n", log_line(c, offsets_[static_cast<size_t>(c)], ch.k0, ch.hops, wav_).c_str()) > 0;
         if(fclose(f) != 0 || !ok) return false;
         ch.past_k0[ch.next] = ch.k0;
         ch.past_hops[ch.next] = ch.hops;
@@ -961,7 +1109,8 @@ private:
     std::string dir_;
     std::vector<int32_t> offsets_;
     std::vector<Chan> chan_;
-    int64_t segments_ = 0, hops_ = 0;
+    int64_t segments_ = 0, hops_ = 0, wav_clamped_ = 0;
+    bool wav_ = false;  // the pushes carry audio rows
 };
 
 // ---- the gate: only the channels with activity are decoded (msk144_set_wideband_gate, msk144_wideband_gate) ----

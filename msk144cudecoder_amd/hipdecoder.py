@@ -92,6 +92,11 @@ class WidebandCaptureUnit(C.Structure):
     _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("hop", C.c_int64)]
 
 
+class WidebandAudioParams(C.Structure):
+    """msk144_wideband_audio_params."""
+    _fields_ = [("taps", (C.c_int8 * 2) * 64), ("phasor", (C.c_int16 * 2) * 96), ("shift", C.c_int32)]
+
+
 class WidebandGateParams(C.Structure):
     """msk144_wideband_gate_params."""
     _fields_ = [("hold", C.c_int32), ("min_up", C.c_int32), ("max_channels", C.c_int32)]
@@ -99,6 +104,7 @@ class WidebandGateParams(C.Structure):
 
 assert C.sizeof(WidebandPing) == PING_DTYPE.itemsize == 32
 assert C.sizeof(WidebandCaptureUnit) == CAPTURE_DTYPE.itemsize == 16
+assert C.sizeof(WidebandAudioParams) == 516
 
 BLANKER_STATS = ("samples", "sum_power", "threshold", "hits", "blanked", "carry_out", "total_samples", "total_hits", "total_blanked")
 
@@ -183,6 +189,8 @@ PROTOTYPES = {
     "msk144_wideband_waterfall_sums": ([_vp, _P(C.c_double)], C.c_int),
     "msk144_set_wideband_capture": ([_vp, _P(WidebandCaptureParams)], C.c_int),
     "msk144_wideband_capture": ([_vp, _P(WidebandCaptureUnit), _P(C.c_int8), _P(_i32), _P(_i32)], C.c_int),
+    "msk144_set_wideband_audio": ([_vp, _P(WidebandAudioParams)], C.c_int),
+    "msk144_wideband_capture_audio": ([_vp, _P(C.c_int16), _P(_i32), _P(_i32)], C.c_int),
     "msk144_set_wideband_gate": ([_vp, _P(WidebandGateParams), _P(C.c_uint8)], C.c_int),
     "msk144_wideband_gate": ([_vp, _P(_i32), _P(_i32), _P(_i32)], C.c_int),
 }
@@ -678,6 +686,46 @@ class HipDecoder:
         self._chk(self.L.msk144_wideband_capture(self.h, units.ctypes.data_as(C.POINTER(WidebandCaptureUnit)), data.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(count),
                                                  C.byref(total)))
         return units[:count.value].copy(), data[:count.value].copy(), total.value
+
+    def set_wideband_audio(self, centre_hz=0, halfwidth_hz: int = 1250, tone_hz: int = 1500, taps=None, phasor=None, shift: Optional[int] = None):
+        """The audio from the next push on (include/msk144hip.h): every channel's hops as real int16 audio at 12000 samples per second.
+        set_wideband_audio() takes the default design - centre_hz +- halfwidth_hz comes out around tone_hz (wideband.audio_design);
+        taps (int8 [k][2], k <= 64), phasor (int16 [96][2]) and shift give a filter and a table of one's own;
+        set_wideband_audio(None) switches it off.  Either ends the last push's rows: wideband_capture_audio() raises (MSK144_ESTATE)
+        until the next push made with the audio and the capture on."""
+        if centre_hz is None:
+            self._chk(self.L.msk144_set_wideband_audio(self.h, None))
+            return
+        if taps is None and phasor is None:
+            from .wideband import audio_design
+            t, w, s = audio_design(centre_hz, halfwidth_hz, tone_hz)
+            shift = s if shift is None else shift
+        else:
+            if taps is None or phasor is None or shift is None:
+                raise ValueError("taps, phasor and shift come together")
+            t, w = np.asarray(taps), np.asarray(phasor)
+            if t.ndim != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= 64 or np.any(t != t.astype(np.int8)):
+                raise ValueError("taps must be int8 [k][2] with 1 <= k <= 64")
+            if w.shape != (96, 2) or np.any(w != w.astype(np.int16)):
+                raise ValueError("phasor must be int16 [96][2]")
+        a = WidebandAudioParams()
+        full = np.zeros((64, 2), dtype=np.int8)
+        full[:t.shape[0]] = t
+        w16 = np.ascontiguousarray(w, dtype=np.int16)
+        C.memmove(a.taps, full.ctypes.data, full.nbytes)
+        C.memmove(a.phasor, w16.ctypes.data, w16.nbytes)
+        a.shift = int(shift)
+        self._chk(self.L.msk144_set_wideband_audio(self.h, C.byref(a)))
+
+    def wideband_capture_audio(self):
+        """(audio, clamped) of the last push: int16 [count][2592], row u the audio of unit u of wideband_capture(), and int32 [count],
+        the samples of that hop that the clamp to int16 changed."""
+        cap = max(getattr(self, "_capture_units", 0), 1)
+        audio = np.zeros((cap, CAPTURE_UNIT_BYTES // 2), dtype=np.int16)
+        clamped = np.zeros(cap, dtype=np.int32)
+        count = C.c_int32()
+        self._chk(self.L.msk144_wideband_capture_audio(self.h, audio.ctypes.data_as(C.POINTER(C.c_int16)), clamped.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(count)))
+        return audio[:count.value].copy(), clamped[:count.value].copy()
 
     def set_wideband_gate(self, hold=1, min_up=1, max_channels=None, always=()):
         """The gate from the next push on (include/msk144hip.h): a channel's window is decoded while the channel had a hop with at

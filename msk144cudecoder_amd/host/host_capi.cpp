@@ -217,6 +217,61 @@ int msk144host_wideband_ping_band_parse(const char* arg, int32_t centre_default,
     return 0;
 }
 
+// ---- the audio (csrc/wideband.h: the default design, the check, the filter and its mix to int16) ----
+
+// The default design of msk144_set_wideband_audio: taps[64][2] int8, phasor[96][2] int16 and the shift; -1 with the refusal text for
+// arguments the design does not take.  What the program and msk144cudecoder_amd.wideband.audio_design hand to the library.
+int msk144host_wideband_audio_design(int32_t centre_hz, int32_t halfwidth_hz, int32_t tone_hz, int8_t* taps, int16_t* phasor, int32_t* shift, char* why, int why_len)
+{
+    const std::string s = msk144wb::check_audio_design(centre_hz, halfwidth_hz, tone_hz);
+    if(!s.empty()) return copy_why(s, why, why_len);
+    const msk144wb::AudioParams p = msk144wb::audio_design(centre_hz, halfwidth_hz, tone_hz);
+    std::memcpy(taps, p.taps, sizeof(p.taps));
+    std::memcpy(phasor, p.phasor, sizeof(p.phasor));
+    *shift = p.shift;
+    return copy_why(s, why, why_len);
+}
+// 0 when msk144_set_wideband_audio takes the shift (any int8 taps and int16 phasors are valid), else -1 with the refusal text
+int msk144host_wideband_audio_check(int32_t shift, char* why, int why_len)
+{
+    msk144wb::AudioParams p{};
+    p.shift = shift;
+    return copy_why(msk144wb::check_audio(p), why, why_len);
+}
+// One push of `channels` channels: x[channels][n][2] stored int8 samples (n a multiple of 2592), tails[channels][63][2] in and out,
+// y[channels][n] and clamped[channels][n / 2592].  -1 for a shift or an n out of range.
+int msk144host_wideband_audio_push(const int8_t* taps, const int16_t* phasor, int32_t shift, int channels, const int8_t* x, int n, int8_t* tails, int16_t* y, int32_t* clamped)
+{
+    msk144wb::AudioParams p{};
+    std::memcpy(p.taps, taps, sizeof(p.taps));
+    std::memcpy(p.phasor, phasor, sizeof(p.phasor));
+    p.shift = shift;
+    if(!msk144wb::check_audio(p).empty() || channels < 1 || n < 0 || n % msk144wb::kAudioHopSamples != 0) return -1;
+    for(int c = 0; c < channels; c++)
+        msk144wb::audio_push(p, x + static_cast<size_t>(c) * 2 * n, n, tails + static_cast<size_t>(c) * 2 * msk144wb::kFirTail, y + static_cast<size_t>(c) * n,
+                             clamped + static_cast<size_t>(c) * (n / msk144wb::kAudioHopSamples));
+    return 0;
+}
+// the 44-byte header of a WAV file of `samples` samples, as --wideband-audio writes it
+void msk144host_wideband_wav_header(uint32_t samples, uint8_t* out44)
+{
+    msk144wb::wav_header(out44, samples);
+}
+// "[HALFWIDTH[:CENTRE[:TONE]]]" as the program parses the value of --wideband-audio (centre_default: --center-frequency): 0 and
+// out3 = {halfwidth, centre, tone}, else -1 with the design's refusal text, or an empty one for a value that does not parse
+int msk144host_wideband_audio_parse(const char* arg, int32_t centre_default, int32_t* out3, char* why, int why_len)
+{
+    WidebandOptions w;
+    std::string text;
+    if(!parse_wideband_audio(arg, centre_default, w, text))
+    {
+        copy_why(text, why, why_len);
+        return -1;
+    }
+    out3[0] = w.audio_halfwidth, out3[1] = w.audio_centre, out3[2] = w.audio_tone;
+    return 0;
+}
+
 // ---- the notch (csrc/wideband.h: the default design, the checks, the response, the filter) ----
 
 // The default design of a channel's notch: taps[64][2] int8 and the shift for n frequencies; -1 with the refusal text for what the

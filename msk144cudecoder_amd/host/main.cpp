@@ -79,6 +79,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-pings-band[=HALFWIDTH[:CENTRE]]  With --wideband-pings: a 64-tap complex band-pass of CENTRE +- HALFWIDTH Hz, on the GPU, ahead of the detector's block energies, so that it compares the energy inside the signal's band and not that of the whole 12 kHz channel. HALFWIDTH 500..3000, default=1500; CENTRE an integer with |CENTRE| + HALFWIDTH <= 6000, default=the value of --center-frequency. The in-band energy of a block swings further on noise alone, so without a RATIO in --wideband-pings RATIO defaults to 3.25. The ping lines keep their format; peak and ref are then in-band. The detector's summary line adds 'band <CENTRE> +-<HALFWIDTH> Hz shift <s>'." << std::endl;
     std::cout << "                   --wideband-waterfall=FILE[:CHANNELS]  With --wideband-rate: a waterfall per channel, on the GPU, on each channel's int8 I/Q: one 96-point spectrum (125 Hz per bin, Hann window) per 8 ms block, the blocks of --wideband-pings. CHANNELS is a list of up to 16 channel indices c0,c1,... (every block of these is written) or 'pings' (every block above the threshold of every channel; the default with --wideband-pings, without it a list is required). After every push one line per selected row is appended to FILE: 'wf ch= offset= block= t= db=v0,...,v95' in ascending frequency from -6000 Hz, 0 dB = a tone of 1 LSB, floor -100 dB. With --wideband-pings every ping line gains ' freq=<Hz>', the strongest bin of the event's blocks. At the end, on stderr, one line with the rows written and up to three channels whose spectrum summed over the run has a bin at least 10 dB (a design parameter) over the channel's median bin: a steady carrier in the passband. A display and a frequency estimate; it does not feed the decoder." << std::endl;
     std::cout << "                   --wideband-capture=DIR[:CHANNELS[:POST[:PRE]]]  With --wideband-rate: keep each ping's channel I/Q for replay. On the GPU, after every push, the hops worth keeping are picked per channel and packed; only those bytes come to the host. CHANNELS is 'pings' (a hop is kept when the channel has a block above the threshold in it, for POST hops after that (0..16, default 1) and, with PRE = 1 (the default; 0 or 1), the one hop before it; the default with --wideband-pings, without it a list is required) or a list of up to 16 channel indices c0,c1,... that are kept whether active or not. At most min(2 x channels, 512) hops are kept per push; more are dropped and counted. Consecutive hops of a channel are appended to DIR/ch<c>_hop<k0>.cs8: int8 I/Q at 12000 samples per second, what --read-mode=2 reads. When a segment ends one line is appended to DIR/capture.log: 'capture ch= offset= hop= t= hops= file='. Every run starts capture.log afresh and overwrites segments of the same name. With --wideband-pings every ping line gains ' file=<name> at=<sample offset of the event's first block in that file>' (' file=-' when that hop was dropped). At the end, on stderr, one line with segments, hops written, bytes and dropped units." << std::endl;
+    std::cout << "                   --wideband-audio[=HALFWIDTH[:CENTRE[:TONE]]]  With --wideband-capture: beside every DIR/ch<c>_hop<k0>.cs8 write DIR/ch<c>_hop<k0>.wav, the same hops as real 16-bit audio at 12000 samples per second (one channel, PCM), what WSJT-X opens in MSK144 mode and what this program reads with --skip-wav-header. On the GPU a 64-tap complex band-pass of CENTRE +- HALFWIDTH Hz runs on every channel's int8 I/Q and an integer phasor table takes CENTRE to TONE Hz. HALFWIDTH 500..3000, default=1250; CENTRE an integer with |CENTRE| + HALFWIDTH <= 6000, default=the value of --center-frequency; TONE within HALFWIDTH..6000 - HALFWIDTH with TONE - CENTRE a multiple of 125, default=1500. An int8 full scale comes out near an int16 full scale (a design parameter); louder samples are clamped and counted. The audio lags the .cs8 samples by the filter's 31.5 samples (2.6 ms). The segment's line in capture.log gains ' wav=<name>'. At the end, on stderr, one line with the WAV files, the samples and the clamped samples." << std::endl;
     std::cout << "                   --wideband-notch=SPEC[/HALFWIDTH]  With --wideband-rate: take steady carriers (a spur, a birdie, a beacon) out of single channels, on the GPU, behind the channel filter and the AGC step and ahead of everything that reads the channel's int8 I/Q: a 64-tap complex band-pass of +-HALFWIDTH Hz (50..500, default=100) around each carrier estimates it and the estimate is taken from the channel delayed by 31 samples (2.6 ms). SPEC is a fixed table 'ch:Hz[+Hz],ch:Hz,...' - one or two frequencies per channel in Hz from the channel's offset, at least 1000 Hz apart - or 'auto[:DB[:PERIOD[:PERSIST]]]': a host rule on the channels' waterfall sums (the GPU waterfall is then on even without --wideband-waterfall) that adds a notch where the highest bin of a channel lies at least DB (default=10) over its median bin in PERSIST (default=2) consecutive sums of PERIOD pushes (default=23, about 5 s), at most two per channel; notches are only added during a run, and each is reported on stderr as 'wideband notch: ch= offset= notch= excess= at hop'. DB, PERIOD and PERSIST are design parameters, not measurements. The notch costs sensitivity on a weak ping where there is no carrier: notch only the channels that have one. At the end, on stderr, one line with the channels notched, the notches and the clamped components." << std::endl;
     std::cout << "                   --wideband-gate[=HOLD[:MIN_UP[:MAX[:ALWAYS]]]]  With --wideband-pings: decode only the channels with activity, picked on the GPU from the detector's blocks. A hop of a channel is active when at least MIN_UP (1..27, default=1) of its 27 blocks are above the threshold; the channel's window is decoded in that push and for HOLD more hops (0..16, default=1; with HOLD >= 1 every window that contains an active hop is decoded). At most MAX channels are decoded per push (default and 0: all); more are dropped in ascending channel order and counted. ALWAYS is a list of channel indices c0,c1,... that are decoded on every push; with it the option needs no --wideband-pings. An empty field keeps its default. Levels, ping events, captures and snr= of every channel stay those of a run without the gate. The detector is less sensitive than the decoder: a ping it does not see is not decoded. At the end, on stderr, one line with the channel windows decoded, the dropped ones and the busiest push." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
@@ -193,6 +194,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-capture", required_argument, 0, 0},
                                            {"wideband-pings-band", optional_argument, 0, 0},
                                            {"wideband-notch", required_argument, 0, 0},
+                                           {"wideband-audio", optional_argument, 0, 0},
                                            {"wideband-gate", optional_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
@@ -244,6 +246,10 @@ int main(int argc, char* const argv[])
     // --wideband-pings-band: its CENTRE defaults to --center-frequency, wherever on the line that stood
     if(wbo.ping_band && !parse_wideband_ping_band(wbo.ping_band_arg, center_set ? static_cast<int>(std::lrint(opt.center_hz)) : 0, wbo) && wbo.parse_error.empty())
         wbo.parse_error = "bad value for --wideband-pings-band: '" + wbo.ping_band_arg + "'";
+
+    // --wideband-audio likewise; a value the design refuses is reported with the design's own text
+    if(std::string why; wbo.audio && !parse_wideband_audio(wbo.audio_arg, center_set ? static_cast<int>(std::lrint(opt.center_hz)) : 0, wbo, why) && wbo.parse_error.empty())
+        wbo.parse_error = why.empty() ? "bad value for --wideband-audio: '" + wbo.audio_arg + "'" : "--wideband-audio: " + why;
 
     // --wideband-rate: checked in full before anything touches the library
     const bool wideband = wbo.any_option;

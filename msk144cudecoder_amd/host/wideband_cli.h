@@ -52,6 +52,11 @@ struct WidebandOptions
     bool capture_by_pings = true;              // CHANNELS is `pings` (the default; needs --wideband-pings): what the rule keeps around activity
     std::vector<int32_t> capture_channels;     // ... or a list of up to 16 channel indices, kept whether active or not
     msk144wb::CaptureParams capture_params;    // max_units is set once the channels are known: min(2 x channels, 512)
+    bool audio = false;           // --wideband-audio[=HALFWIDTH[:CENTRE[:TONE]]]: a 12 kHz int16 WAV file beside every capture segment
+    std::string audio_arg;                     // its value, parsed once --center-frequency is known (parse_wideband_audio)
+    int audio_halfwidth = msk144wb::kAudioDefaultHalfwidthHz;
+    int audio_centre = 0;
+    int audio_tone = msk144wb::kAudioDefaultToneHz;
     bool notch = false;           // --wideband-notch=SPEC[/HALFWIDTH]: steady carriers taken out of single channels
     bool notch_auto = false;                   // SPEC is auto[:DB[:PERIOD[:PERSIST]]]: the host rule msk144wb::NotchPlanner on the waterfall sums
     msk144wb::NotchPlan notch_plan;
@@ -99,6 +104,9 @@ struct WidebandApi
     // --wideband-capture
     int (*set_capture)(msk144_handle*, const msk144_wideband_capture_params*) = nullptr;
     int (*capture)(msk144_handle*, msk144_wideband_capture_unit*, int8_t*, int32_t*, int32_t*) = nullptr;
+    // --wideband-audio
+    int (*set_audio)(msk144_handle*, const msk144_wideband_audio_params*) = nullptr;
+    int (*capture_audio)(msk144_handle*, int16_t*, int32_t*, int32_t*) = nullptr;
     // --wideband-gate
     int (*set_gate)(msk144_handle*, const msk144_wideband_gate_params*, const uint8_t*) = nullptr;
     int (*gate)(msk144_handle*, int32_t*, int32_t*, int32_t*) = nullptr;
@@ -131,6 +139,7 @@ struct WidebandApi
             {w.notch, "notch", ": --wideband-notch needs it", {{"msk144_set_wideband_notch", &set_notch}, {"msk144_wideband_notch_stats", &notch_stats}}},
             {w.notch && w.notch_auto, "waterfall", ": --wideband-notch=auto needs it", {{"msk144_set_wideband_waterfall", &set_waterfall}, {"msk144_wideband_waterfall_sums", &waterfall_sums}}},
             {w.capture, "capture", ": --wideband-capture needs it", {{"msk144_set_wideband_capture", &set_capture}, {"msk144_wideband_capture", &capture}}},
+            {w.audio, "audio", ": --wideband-audio needs it", {{"msk144_set_wideband_audio", &set_audio}, {"msk144_wideband_capture_audio", &capture_audio}}},
             {w.gate, "gate", ": --wideband-gate needs it", {{"msk144_set_wideband_gate", &set_gate}, {"msk144_wideband_gate", &gate}}},
         };
         for(const Group& g : groups)
@@ -319,6 +328,28 @@ inline bool parse_wideband_capture(const std::string& s, WidebandOptions& w)
     return f.size() < 4 || parse_int_in(f[3], 0, 1, w.capture_params.pre);
 }
 
+// "[HALFWIDTH[:CENTRE[:TONE]]]", behind every other option: HALFWIDTH 500..3000 Hz (1250), CENTRE an integer (centre_default, the
+// value of --center-frequency), TONE the audio frequency CENTRE comes out at (1500); what msk144wb::check_audio_design takes, whose
+// refusal text goes to `why` (empty for a value that does not parse).  (Whether there is a capture needs the other options:
+// check_wideband_options.)
+inline bool parse_wideband_audio(const std::string& s, int centre_default, WidebandOptions& w, std::string& why)
+{
+    w.audio = true;
+    w.audio_halfwidth = msk144wb::kAudioDefaultHalfwidthHz;
+    w.audio_centre = centre_default;
+    w.audio_tone = msk144wb::kAudioDefaultToneHz;
+    why.clear();
+    if(!s.empty())
+    {
+        const std::vector<std::string> f = split_fields(s, ':');
+        if(f.size() > 3 || !parse_int_in(f[0], INT32_MIN, INT32_MAX, w.audio_halfwidth)) return false;
+        if(f.size() > 1 && !parse_int_in(f[1], INT32_MIN, INT32_MAX, w.audio_centre)) return false;
+        if(f.size() > 2 && !parse_int_in(f[2], INT32_MIN, INT32_MAX, w.audio_tone)) return false;
+    }
+    why = msk144wb::check_audio_design(w.audio_centre, w.audio_halfwidth, w.audio_tone);
+    return why.empty();
+}
+
 // "SPEC[/HALFWIDTH]": HALFWIDTH 50..500 Hz (100); SPEC "auto[:DB[:PERIOD[:PERSIST]]]" - DB a decimal within 1..100, PERIOD 1..100000
 // pushes, PERSIST 1..1000 periods - or "ch:Hz[+Hz],ch:Hz,...": different channels, each with one or two integer frequencies that
 // msk144wb::check_notch_design takes (whether the channels exist needs the other options: check_wideband_options)
@@ -423,8 +454,8 @@ inline bool parse_offset_grid(const std::string& spec, std::vector<int32_t>& out
 }
 
 // One option of the command line by its name: false when `name` is no wideband option, else it is taken into `w` - a malformed value
-// as the first parse error, which check_wideband_options reports.  --wideband-pings-band keeps its value for parse_wideband_ping_band,
-// behind the whole line.
+// as the first parse error, which check_wideband_options reports.  --wideband-pings-band and --wideband-audio keep their values for
+// parse_wideband_ping_band and parse_wideband_audio, behind the whole line.
 inline bool take_wideband_option(const std::string& name, const char* arg, WidebandOptions& w)
 {
     const std::string value = arg ? arg : "";
@@ -443,6 +474,7 @@ inline bool take_wideband_option(const std::string& name, const char* arg, Wideb
     else if(name == "wideband-waterfall") good = parse_wideband_waterfall(value, w);
     else if(name == "wideband-capture") good = parse_wideband_capture(value, w);
     else if(name == "wideband-pings-band") w.ping_band = true, w.ping_band_arg = value;
+    else if(name == "wideband-audio") w.audio = true, w.audio_arg = value;
     else if(name == "wideband-notch") good = parse_wideband_notch(value, w);
     else if(name == "wideband-gate") good = parse_wideband_gate(arg, w);
     else return false;
@@ -459,7 +491,8 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     {
         const std::pair<bool, const char*> own_line[] = {{w.blanker, "--wideband-blanker"},      {w.spectrum, "--wideband-spectrum"},   {w.pings, "--wideband-pings"},
                                                          {w.ping_band, "--wideband-pings-band"}, {w.waterfall, "--wideband-waterfall"}, {w.capture, "--wideband-capture"},
-                                                         {w.notch, "--wideband-notch"},          {w.gate, "--wideband-gate"}};
+                                                         {w.notch, "--wideband-notch"},          {w.gate, "--wideband-gate"},
+                                                         {w.audio, "--wideband-audio"}};
         for(const auto& o : own_line)
             if(o.first) return std::string(o.second) + " needs --wideband-rate=HZ";
         return w.levels ? "--wideband-format, --channel-offsets, --channel-grid, --wideband-gain, --wideband-levels and --taps-per-phase need --wideband-rate=HZ"
@@ -483,6 +516,7 @@ inline std::string check_wideband_options(const WidebandOptions& w)
     for(size_t i = 0; w.capture && i < w.capture_channels.size(); i++)
         if(static_cast<size_t>(w.capture_channels[i]) >= w.offsets.size())
             return "--wideband-capture: channel " + std::to_string(w.capture_channels[i]) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";
+    if(w.audio && !w.capture) return "--wideband-audio needs --wideband-capture=DIR";
     for(const auto& e : w.notch_table)
         if(static_cast<size_t>(e.first) >= w.offsets.size())
             return "--wideband-notch: channel " + std::to_string(e.first) + " is not one of the " + std::to_string(w.offsets.size()) + " channels";

@@ -116,6 +116,12 @@ private:
         std::vector<int8_t> data;                         // [max_units][5184]
         long long dropped = 0;
     } capture_;
+    struct Audio  // --wideband-audio: the units' audio rows go to the WAV file beside their segment
+    {
+        std::vector<int16_t> rows;                        // [max_units][2592]
+        std::vector<int32_t> clamped;                     // [max_units]
+        msk144wb::AudioParams design{};
+    } audio_;
     struct Notch  // --wideband-notch: the table the library holds, a fixed one or what the planner has added so far
     {
         std::unique_ptr<msk144wb::NotchPlanner> planner;  // with auto only

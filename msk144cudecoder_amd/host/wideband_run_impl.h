@@ -113,6 +113,11 @@ inline bool WidebandRun::prepare()
         capture_.units.resize(static_cast<size_t>(opt_.capture_params.max_units));
         capture_.data.resize(static_cast<size_t>(opt_.capture_params.max_units) * msk144wb::kCaptureUnitBytes);
     }
+    if(opt_.audio)
+    {
+        audio_.rows.resize(static_cast<size_t>(opt_.capture_params.max_units) * msk144wb::kAudioHopSamples);
+        audio_.clamped.resize(static_cast<size_t>(opt_.capture_params.max_units));
+    }
     return true;
 }
 
@@ -188,6 +193,14 @@ inline bool WidebandRun::configure(msk144_handle* h)
         cp.num_listed = static_cast<int32_t>(opt_.capture_channels.size());
         std::copy(opt_.capture_channels.begin(), opt_.capture_channels.end(), cp.listed);
         if(api_.set_capture(h, &cp) != MSK144_OK) return set_failed(h);
+    }
+    if(opt_.audio)
+    {
+        audio_.design = msk144wb::audio_design(opt_.audio_centre, opt_.audio_halfwidth, opt_.audio_tone);
+        msk144_wideband_audio_params ap;
+        static_assert(sizeof(ap) == sizeof(audio_.design), "msk144wb::AudioParams is msk144_wideband_audio_params");
+        std::memcpy(&ap, &audio_.design, sizeof(ap));
+        if(api_.set_audio(h, &ap) != MSK144_OK) return set_failed(h);
     }
     if(opt_.notch && !opt_.notch_auto && !set_notch_table(h)) return false;
     if(opt_.gate)
@@ -382,7 +395,16 @@ inline bool WidebandRun::read_capture(msk144_handle* h)
     int32_t count = 0, total = 0;
     if(api_.capture(h, capture_.units.data(), capture_.data.data(), &count, &total) != MSK144_OK) return false;
     capture_.dropped += total - count;
-    if(capture_.segments->push(reinterpret_cast<const msk144wb::CaptureUnit*>(capture_.units.data()), capture_.data.data(), count)) return true;
+    int32_t rows = count;
+    if(opt_.audio && api_.capture_audio(h, audio_.rows.data(), audio_.clamped.data(), &rows) != MSK144_OK) return false;
+    if(rows != count)
+    {
+        error_ = "--wideband-audio: the audio rows of a push are not its units'";
+        return false;
+    }
+    if(capture_.segments->push(reinterpret_cast<const msk144wb::CaptureUnit*>(capture_.units.data()), capture_.data.data(), count, opt_.audio ? audio_.rows.data() : nullptr,
+                               opt_.audio ? audio_.clamped.data() : nullptr))
+        return true;
     error_ = "--wideband-capture: cannot write a segment: " + std::string(strerror(errno));
     return false;
 }
@@ -550,6 +572,9 @@ inline void WidebandRun::print_summary(msk144_handle* h) const
         const msk144wb::CaptureSegments& cs = *capture_.segments;
         fprintf(stderr, "msk144hipdecoder: wideband capture: %lld segments, %lld hops written, %lld bytes, %lld units dropped\n", static_cast<long long>(cs.segments()),
                 static_cast<long long>(cs.hops()), static_cast<long long>(cs.bytes()), capture_.dropped);
+        if(opt_.audio)
+            fprintf(stderr, "msk144hipdecoder: wideband audio: %lld WAV files, %lld samples, %lld clamped, band %d +-%d Hz at %d Hz, shift %d\n", static_cast<long long>(cs.wav_files()),
+                    static_cast<long long>(cs.wav_samples()), static_cast<long long>(cs.wav_clamped()), opt_.audio_centre, opt_.audio_halfwidth, opt_.audio_tone, audio_.design.shift);
     }
     if(opt_.gate)
         fprintf(stderr, "msk144hipdecoder: wideband gate: %lld of %lld channel windows decoded (%.1f %%), hold %d, min up %d, at most %d per push, %lld dropped, busiest push %d channels\n",

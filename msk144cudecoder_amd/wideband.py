@@ -48,6 +48,8 @@ def _host_lib():
         L.msk144host_wideband_ping_band_design.restype = C.c_int
         L.msk144host_wideband_notch_design.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int]
         L.msk144host_wideband_notch_design.restype = C.c_int
+        L.msk144host_wideband_audio_design.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int]
+        L.msk144host_wideband_audio_design.restype = C.c_int
         _host = L
     return _host
 
@@ -514,6 +516,81 @@ class PingBand:
         S = np.sum(np.sum(z * z, axis=2).reshape(self.channels, M // PING_BLOCK, PING_BLOCK), axis=2)   # < 2^50
         self.tail = s[:, M:, :].astype(np.int8)
         return np.minimum(S >> self.shift, PING_BAND_MAX_ENERGY)
+
+
+# ---- each captured hop as 12 kHz audio (msk144_set_wideband_audio, msk144_wideband_capture_audio) ----
+
+AUDIO_PHASORS = 96
+AUDIO_MIN_SHIFT, AUDIO_MAX_SHIFT = 1, 40
+AUDIO_HALFWIDTH_HZ = 1250     # the defaults are design parameters, not measurements
+AUDIO_TONE_HZ = 1500
+WAV_HEADER_BYTES = 44
+
+
+def audio_design(centre_hz: int = 0, halfwidth_hz: int = AUDIO_HALFWIDTH_HZ, tone_hz: int = AUDIO_TONE_HZ) -> Tuple[np.ndarray, np.ndarray, int]:
+    """The default design of the contract, from libmsk144host.so (csrc/wideband.h audio_design), exactly what the program hands to
+    the library: (int8 [64][2] taps (br, bi), int16 [96][2] phasors (pr, pi), shift)."""
+    taps = np.zeros((PING_BAND_TAPS, 2), dtype=np.int8)
+    phasor = np.zeros((AUDIO_PHASORS, 2), dtype=np.int16)
+    shift = C.c_int32(0)
+    why = C.create_string_buffer(256)
+    if _host_lib().msk144host_wideband_audio_design(int(centre_hz), int(halfwidth_hz), int(tone_hz), taps.ctypes.data_as(C.c_void_p), phasor.ctypes.data_as(C.c_void_p), C.byref(shift), why,
+                                          len(why)) != 0:
+        raise ValueError(why.value.decode())
+    return taps, phasor, int(shift.value)
+
+
+def _audio_phasor(phasor) -> np.ndarray:
+    """int16 [96][2] from phasor [96][2]."""
+    w = np.asarray(phasor)
+    if w.shape != (AUDIO_PHASORS, 2) or np.any(w != w.astype(np.int16)):
+        raise ValueError("phasor must be int16 [96][2]")
+    return w.astype(np.int16)
+
+
+class Audio:
+    """The audio of the contract (include/msk144hip.h) in int64 numpy, push by push: z[n] = sum b[k] x[n - k] on the stored int8
+    values, a[n] = Re z pr[n mod 96] - Im z pi[n mod 96], y[n] = clamp((a + 2^(shift - 1)) >> shift) to int16, and per channel the 63
+    stored samples before the next push.  restart stands for every push at which the library starts from an all-zero tail: a first
+    push, and the first push after msk144_set_wideband_audio, whose rows are then the two hops of the ring window, older first."""
+
+    def __init__(self, channels: int, taps, phasor, shift: int):
+        self.taps = _fir_taps(taps, "taps must be [k][2] with 1 <= k <= 64", "taps must be int8 values")
+        self.phasor = _audio_phasor(phasor).astype(np.int64)
+        if not AUDIO_MIN_SHIFT <= int(shift) <= AUDIO_MAX_SHIFT:
+            raise ValueError("audio shift must lie within 1..40")
+        self.shift, self.channels = int(shift), int(channels)
+        self.tail = np.zeros((self.channels, PING_BAND_TAPS - 1, 2), dtype=np.int8)
+
+    def push(self, rows, restart: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(int16 [channel][M], int64 [channel][M / 2592]): the audio of the int8 hops rows [channel][M][2] of one push, M a multiple
+        of 2592 that starts on a hop, and the samples of each hop that the clamp changed; the tail moves on."""
+        q = np.asarray(rows)
+        if q.ndim != 3 or q.shape[0] != self.channels or q.shape[1] % HOP_OUT or q.shape[2] != 2:
+            raise ValueError(f"hops must be [{self.channels}][M][2] with M a multiple of 2592")
+        if restart:
+            self.tail = np.zeros_like(self.tail)
+        M = q.shape[1]
+        s, z = _fir_push(self.tail, q, self.taps)
+        w = self.phasor[np.arange(M) % AUDIO_PHASORS]
+        a = z[..., 0] * w[:, 0] - z[..., 1] * w[:, 1]                # |a| <= 2^37
+        v = (a + (1 << (self.shift - 1))) >> self.shift              # numpy's >> on int64 is arithmetic: floor
+        y = np.clip(v, -32768, 32767)
+        self.tail = s[:, M:, :].astype(np.int8)
+        return y.astype(np.int16), np.sum((y != v).reshape(self.channels, M // HOP_OUT, HOP_OUT), axis=2)
+
+
+def wav_header(samples: int) -> bytes:
+    """The 44-byte RIFF/WAVE header of --wideband-audio's files: PCM format 1, one channel, 12000 Hz, 16 bits."""
+    import struct
+    data = 2 * int(samples)
+    return struct.pack("<4sI8sIHHIIHH4sI", b"RIFF", data + WAV_HEADER_BYTES - 8, b"WAVEfmt ", 16, 1, 1, OUT_RATE, 2 * OUT_RATE, 2, 16, b"data", data)
+
+
+def wav_bytes(audio) -> bytes:
+    """The file rule of --wideband-audio: the header, then the int16 samples of audio (any shape, row after row), little-endian."""
+    a = np.ascontiguousarray(audio, dtype="<i2").reshape(-1)
+    return wav_header(a.size) + a.tobytes()
 
 
 # ---- the notch: steady carriers taken out of a channel's stored samples (msk144_set_wideband_notch) ----

@@ -34,7 +34,16 @@ milliseconds of push + decode + fetch per share, and the same for an ungated han
 times with the detector on - ungated, with every channel always decoded, and with the bare --wideband-gate - and appends every line
 to profiles/wideband_bench_gate.jsonl.  Nothing is asserted on these times.
 
+--audio is a leg of its own as well: 1024 channels at D = 160 with the capture on (every 8th channel listed, up to 16), once with
+the audio off and once with it on (msk144_set_wideband_audio, the default design), two handles in one run.  It measures the host
+milliseconds of one later push that ends in msk144_synchronize - the whole push: channeliser, hop ring, the audio kernel and its
+copy, the capture, the IQ front end - in `--rounds` rounds of `--pushes` pushes that alternate between the two handles, and gives
+the median of every round, so that the spread from round to round stands beside the difference.  audio_dot4 is the audio kernel's
+int8 dot products of a push (channels x 2592 x 99), audio_bytes the int16 rows it writes (channels x 5184).  The lines are
+appended to profiles/wideband_bench_audio.jsonl.  Nothing is asserted on these times.
+
     python tools/wideband_bench.py [--channels 256,1024,4096] [--decimations 80,160,200] [--rates 2048000,2500000]
+                                   [--audio [--rounds 5]]
                                    [--pushes 20] [--program-hops 40] [--program-rate 1920000] [--agc] [--blanker] [--spectrum[=BINS]] [--pings] [--pings-band] [--waterfall] [--capture] [--notch N]
 """
 from __future__ import annotations
@@ -198,6 +207,51 @@ def measure_gate(shares, pushes: int, C: int = 1024, rate: int = 1920000) -> lis
     return out
 
 
+def push_ms(d, pushes: int) -> list:
+    """Host milliseconds of one later push that ends in a synchronise, one value per push."""
+    out = []
+    for i in range(pushes):
+        t0 = time.perf_counter()
+        d.push_wideband(i % 2, first=False)
+        d.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def measure_audio(pushes: int, rounds: int, C: int = 1024, rate: int = 1920000) -> list:
+    """--audio: ms per push with the audio off and on, the capture on in both, in alternating rounds of one run.  Nothing is asserted."""
+    lim = rate // 2 - 6000
+    offsets = np.linspace(-lim, lim, C).astype(np.int32)
+    rng = np.random.default_rng(C)
+    listed = list(range(0, C, 8))[:wideband.CAPTURE_MAX_LISTED]
+    cfg = dict(center=0.0, width=0.0, step=1.0, depth=1, read_mode=2, channels=C)
+    with hipdecoder.HipDecoder(**cfg) as off, hipdecoder.HipDecoder(**cfg) as on:
+        for d in (off, on):
+            d.set_wideband(rate, offsets, "cu8")
+            d.set_wideband_capture(channels=listed)
+            for s in range(2):
+                d.wideband_slot(s)[:] = rng.integers(120, 136, size=d.wideband_slot(s).size, dtype=np.uint8)
+        on.set_wideband_audio()
+        for d in (off, on):
+            d.push_wideband(0, first=True)
+            push_ms(d, 5)                      # warm-up: every kernel of a later push has run
+        medians = {False: [], True: []}
+        for _ in range(rounds):
+            for audio, d in ((False, off), (True, on)):
+                medians[audio].append(float(np.median(push_ms(d, pushes))))
+        rows, clamped = on.wideband_capture_audio()
+        assert rows.shape == (len(listed), wideband.HOP_OUT)
+    out = []
+    for audio in (False, True):
+        m = medians[audio]
+        line = dict(audio=audio, channels=C, D=rate // 12000, capture_units=len(listed), pushes=pushes, rounds=rounds, push_ms=round(float(np.median(m)), 4),
+                    round_medians_ms=[round(v, 4) for v in m], spread_ms=round(max(m) - min(m), 4), timing="host clock around msk144_push_wideband + msk144_synchronize")
+        if audio:
+            line.update(audio_dot4=C * 2592 * 99, audio_bytes=C * 2 * wideband.HOP_OUT)
+        out.append(line)
+    return out
+
+
 def program_run(hops: int, C: int = 1024, rate: int = 1920000, gate: str = None, pings: bool = False) -> dict:
     """Wall time of one msk144hipdecoder run over a file of 1 first + (hops - 1) later pushes of cu8 noise.  gate: the value of
     --wideband-gate ("" the bare option, "all": every channel always decoded); pings: with --wideband-pings (the events to /dev/null)."""
@@ -255,7 +309,16 @@ def main():
     ap.add_argument("--gate", default=None, metavar="SHARES", help="only the gate leg: ms per push + decode + fetch at 1024 channels, D = 160 and the deep options with each share "
                     "(e.g. 0,0.1,0.5,1) of the channels always decoded and the detector off, against an ungated handle in the same run; then the program ungated, with every channel "
                     "always decoded and behind the detector; appends to profiles/wideband_bench_gate.jsonl")
+    ap.add_argument("--audio", action="store_true", help="only the audio leg: ms per push at 1024 channels and D = 160 with the capture on, the audio off and on, in alternating "
+                    "rounds of one run; appends to profiles/wideband_bench_audio.jsonl")
+    ap.add_argument("--rounds", type=int, default=5, help="--audio: rounds of --pushes pushes per handle")
     a = ap.parse_args()
+    if a.audio:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wideband_bench_audio.jsonl"), "a") as log:
+            for line in measure_audio(a.pushes, a.rounds):
+                print(json.dumps(line), flush=True)
+                log.write(json.dumps(line) + "\n")
+        return
     if a.gate is not None:
         with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wideband_bench_gate.jsonl"), "a") as log:
             lines = measure_gate([float(v) for v in a.gate.split(",") if v], a.pushes)
