@@ -283,6 +283,9 @@ int msk144_fetch_wait(msk144_handle* h, int32_t slot, const msk144_result** reco
 
 /* parity / debug */
 int msk144_dump_analytic(msk144_handle* h, int32_t channel, float* out /*[5184][2]*/);
+/* row block_idx (0 .. num_freqs-1) of the handle's phasor table: (cos, sin) of the float phase by which the scan and softbits kernels
+ * rotate sample n of a window for that frequency hypothesis.  The table is built once, in msk144_create. */
+int msk144_dump_mix_table(msk144_handle* h, int32_t block_idx, float* out /*[5184][2]*/);
 int msk144_dump_candidates(msk144_handle* h, int32_t channel, msk144_candidate* out /*[items_per_channel]*/);
 int msk144_dump_indexes(msk144_handle* h, int32_t channel, int32_t* out /*[items_per_channel]*/, int32_t* n);
 /* overwrite a channel's candidate store (pos, nbadsync, softbits) so later stages can be run on

@@ -55,13 +55,27 @@ __device__ __forceinline__ float mix_phase(float nf, float f0)
     return div_sample_rate(f32_mul(f32_mul(nf, twopi), f0));
 }
 
-__device__ __forceinline__ float2 mix_sample(float2 x, float nf, float f0)
+// The phasor of sample n at hypothesis frequency -f0, (cs, sn) = (cos phi_n, sin phi_n).  It depends on n and on the handle's
+// frequency grid alone, so it is computed once per handle (mix_table_kernel, scan.hip) into the [F][5184] table the scan and
+// softbits kernels read; no kernel computes it per tile.
+__device__ __forceinline__ float2 mix_phasor(float nf, float f0)
 {
     float sn, cs;
     sincos_reduced(mix_phase(nf, f0), sn, cs);
+    return make_float2(cs, sn);
+}
+
+// x * (cs + i sn): per component one rounded product and one FMA.  While the phasor was computed beside it the rotation was the
+// plain expression (cs x.x - sn x.y, cs x.y + sn x.x) and WHICH product the compiler rounded on its own was its choice: the sin
+// product everywhere, except in the imaginary part of a kernel's tail samples (n >= 5120 in the scan, n >= 4608 in softbits), where
+// it fused the sin product and rounded cs x.y.  Candidates sit on near-ties, so the choice is part of the results: it is spelled
+// out here, and each kernel names its tail (kTail), instead of being left to the next compiler.
+template<bool kTail>
+__device__ __forceinline__ float2 rotate(float2 x, float cs, float sn)
+{
     float2 y;
-    y.x = cs * x.x - sn * x.y;
-    y.y = cs * x.y + sn * x.x;
+    y.x = fmaf(cs, x.x, -f32_mul(sn, x.y));
+    y.y = kTail ? fmaf(sn, x.x, f32_mul(cs, x.y)) : fmaf(cs, x.y, f32_mul(sn, x.x));
     return y;
 }
 

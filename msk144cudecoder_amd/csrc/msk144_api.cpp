@@ -268,6 +268,11 @@ int msk144_device_count(int32_t* n)
     return MSK144_OK;
 }
 
+// Besides the candidate store the handle owns the mixers' phasor table, st.mix_table [F][5184] float2 (mix.h): 41.5 KB per
+// hypothesis, whatever the channel count.  It is always built: the kernels have no other source of the phasor.  The store holds
+// 8 D items per channel and hypothesis at 543 B each with its LLR row (31 B without), so the table weighs as much as the store of
+// 9.5 / D channels: 20.8 MB beside 2.3 GB at the benchmark shape (1024 channels, F = 501, D = 6, LLR block 128).  Only a handle of
+// fewer channels than that (9 at depth 1, one at depth 8) holds more table than store.
 int msk144_create(const msk144_params* params, msk144_handle** out)
 {
     if(!params || !out) return fail(nullptr, MSK144_EINVAL, "null argument");
@@ -335,6 +340,7 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
     // a failed dev_alloc has set the message; its code is MSK144_ENOMEM
     bool ok = dev_alloc(h, m, &h->d_freq, F) == MSK144_OK;
     ok = ok && dev_alloc(h, m, &h->d_cb42, kSyncTaps) == MSK144_OK;
+    ok = ok && dev_alloc(h, m, &st.mix_table, static_cast<size_t>(F) * kWindowSamples) == MSK144_OK;
     ok = ok && dev_alloc(h, m, &st.analytic, nch * kWindowSamples) == MSK144_OK;
     ok = ok && dev_alloc(h, m, &st.seg_power, nch * 8) == MSK144_OK;
     ok = ok && dev_alloc(h, m, &st.pos, ck) == MSK144_OK;
@@ -373,6 +379,11 @@ int msk144_create(const msk144_params* params, msk144_handle** out)
     ok = ok && hipMemsetAsync(st.result_count, 0, sizeof(int32_t), s0) == hipSuccess;
     ok = ok && hipMemsetAsync(st.pos, 0, ck * sizeof(uint32_t), s0) == hipSuccess;
     ok = ok && hipMemsetAsync(st.nbadsync, 0, ck * sizeof(int32_t), s0) == hipSuccess;
+    if(ok)
+    {
+        launch_mix_table(h->d_freq, st.mix_table, F, s0);  // d_freq was copied synchronously above
+        ok = hipGetLastError() == hipSuccess;
+    }
     ok = ok && hipStreamSynchronize(s0) == hipSuccess;
 
     if(ok && params->read_mode == 1 && params->analytic_method == 1)
@@ -789,6 +800,15 @@ int msk144_dump_analytic(msk144_handle* h, int32_t channel, float* out)
     int rc = msk144_synchronize(h);
     if(rc != MSK144_OK) return rc;
     HIP_TRY(h, hipMemcpy(out, (h->gated ? h->wb.gate.d_analytic : h->st.analytic) + static_cast<size_t>(channel) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
+    return MSK144_OK;
+}
+
+int msk144_dump_mix_table(msk144_handle* h, int32_t block_idx, float* out)
+{
+    if(!h || !out || block_idx < 0 || block_idx >= h->st.F) return fail(h, MSK144_EINVAL, "bad argument");
+    HIP_TRY(h, hipSetDevice(h->params.device));
+    // written once, before msk144_create returned: nothing to wait for
+    HIP_TRY(h, hipMemcpy(out, h->st.mix_table + static_cast<size_t>(block_idx) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
     return MSK144_OK;
 }
 

@@ -47,6 +47,7 @@ struct DeviceStore
 
     const float* freq;        // [F] Hz, host-computed as msk_context.cuh:135
     const float2* cb42;       // [42] sync template (re, im), for kernels that index it per lane
+    float2* mix_table;        // [F][5184] (cos, sin) of the mixers' phase at (freq[b], sample n): launch_mix_table, once per handle
     float2* analytic;         // [channels][5184] front-end output
     float* seg_power;         // [channels][8]
 
@@ -201,6 +202,9 @@ void launch_bank(const void* raw, int format, const float* h1, const int32_t* ba
 
 // one wave that spins for `ticks` of the 100 MHz counter; out[0] = shader cycles elapsed, out[1] = 100 MHz ticks elapsed (hopring.hip)
 void launch_clock_probe(uint64_t* out, uint32_t ticks, hipStream_t stream);
+
+// the phasor table scan and softbits mix from (scan.hip, mix.h): table[b][n] for the F frequencies of freq, n < 5184
+void launch_mix_table(const float* freq, float2* table, int F, hipStream_t stream);
 
 // hot kernels
 void launch_scan(const DeviceStore& st, const SyncTemplate& tpl, hipStream_t stream);

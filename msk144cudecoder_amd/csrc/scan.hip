@@ -14,7 +14,7 @@
 // accumulated across them.
 //
 // Phases (LDS: one 5184+41 complex buffer, 44 KB per workgroup -> 3 workgroups of 8 waves per CU):
-//  1. mix the window into LDS (custom ~25-instruction sincos, mix.h);
+//  1. mix the window into LDS: each sample rotated by its phasor from the handle's table (mix.h; mix_table_kernel below);
 //  2. C[n] by pulse decomposition (correlate_pulses below): a thread owns eleven outputs spaced by six, which share
 //     seventeen half-pulse sums built from the 102 samples it streams - 187 multiply-adds + 93 adds of complex values per
 //     thread instead of one 42-tap sum per output (847).  After a barrier C overwrites the window in place;
@@ -32,6 +32,7 @@
 #include "msk144_kernels.h"
 #include "mix.h"
 #include "phase_stamps.h"
+#include "tile_map.h"
 #include "wave64.h"
 
 #include <utility>
@@ -64,7 +65,6 @@ struct ScanArgs
     DeviceStore st;
     float pp[12];
     int total_tiles;
-    int tiles_per_xcd;
     MSK144_STAMP_ARG
 };
 
@@ -182,13 +182,10 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     __shared__ float s_oct_v[kScanDepthMax][kScanThreads / 8];     // per (pattern, octet of runs): max |S|^2 ...
     __shared__ uint32_t s_oct_pos[kScanDepthMax][kScanThreads / 8];  // ... and its position
 
-    // XCD-aware tile map: workgroups are dealt round-robin over the 8 XCDs, so give each XCD one
-    // contiguous range of tiles - the F tiles of a channel then share one L2 copy of its window.
-    const int xcd = blockIdx.x & 7;
-    const int tile = xcd * a.tiles_per_xcd + (blockIdx.x >> 3);
-    if((blockIdx.x >> 3) >= a.tiles_per_xcd || tile >= a.total_tiles) return;
-    const int ch_rel = tile / a.st.F;  // channel inside the block [ch0, ch0 + nch) this launch covers
-    const int b = tile - ch_rel * a.st.F;
+    const int tile = tile_index(blockIdx.x, a.total_tiles);  // tile_map.h
+    if(tile < 0) return;
+    const Tile tl = tile_of(tile, a.st.nch, a.st.F);
+    const int ch_rel = tl.ch_rel, b = tl.b;
     const int ch = a.st.ch0 + ch_rel;
 
     const int tid = threadIdx.x;
@@ -199,20 +196,23 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     MSK144_STAMP(11);  // two stamps back to back: the stamp's own cost
 
     // ---- 1. mix down by the hypothesis frequency (scan_kernel.cuh:45-69) ----
-    const float f0 = -1.0f * a.st.freq[b];
     const float2* __restrict__ cdat = a.st.analytic + static_cast<size_t>(ch) * kWindowSamples;
-    float2 xin[kMixPerThread];  // all loads in flight before any arithmetic: one L2 latency per tile, not three
+    const float2* __restrict__ phasor = a.st.mix_table + static_cast<size_t>(b) * kWindowSamples;
+    float2 xin[kMixPerThread], ph[kMixPerThread];  // all loads in flight before any arithmetic: one L2 latency per tile, not three
 #pragma unroll
     for(int i = 0; i < kMixPerThread; i++)
         if((i + 1) * kScanThreads <= kWindowSamples || tid + i * kScanThreads < kWindowSamples) xin[i] = cdat[tid + i * kScanThreads];
-    const float tid_f = static_cast<float>(tid);
+#pragma unroll
+    for(int i = 0; i < kMixPerThread; i++)
+        if((i + 1) * kScanThreads <= kWindowSamples || tid + i * kScanThreads < kWindowSamples) ph[i] = phasor[tid + i * kScanThreads];
 #pragma unroll
     for(int i = 0; i < kMixPerThread; i++)
     {
         const int n = tid + i * kScanThreads;
         if((i + 1) * kScanThreads <= kWindowSamples || n < kWindowSamples)
         {
-            const float2 y = mix_sample(xin[i], tid_f + static_cast<float>(i * kScanThreads), f0);
+            // the tail (mix.h): the eleventh sample, n >= 5120; i is a constant once the loop is unrolled
+            const float2 y = i == kMixPerThread - 1 ? rotate<true>(xin[i], ph[i].x, ph[i].y) : rotate<false>(xin[i], ph[i].x, ph[i].y);
             s_buf[n] = y;
             if(n < kWrapPad) s_buf[kWindowSamples + n] = y;
         }
@@ -471,7 +471,29 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     }
 }
 
+// The handle's phasor table (mix.h), filled once in msk144_create: row b = the 5184 phasors of hypothesis b, each formed from the
+// operands the mixers used when they computed it per tile: nf = float(tid) + float(i * 512), f0 = -1.0f * freq[b].
+__global__ __launch_bounds__(kScanThreads) void mix_table_kernel(const float* __restrict__ freq, float2* __restrict__ table)
+{
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float f0 = -1.0f * freq[b];
+    const float tid_f = static_cast<float>(tid);
+    float2* __restrict__ row = table + static_cast<size_t>(b) * kWindowSamples;
+#pragma unroll
+    for(int i = 0; i < kMixPerThread; i++)
+    {
+        const int n = tid + i * kScanThreads;
+        if(n < kWindowSamples) row[n] = mix_phasor(tid_f + static_cast<float>(i * kScanThreads), f0);
+    }
+}
+
 }  // namespace
+
+void launch_mix_table(const float* freq, float2* table, int F, hipStream_t stream)
+{
+    hipLaunchKernelGGL(mix_table_kernel, dim3(F), dim3(kScanThreads), 0, stream, freq, table);
+}
 
 void launch_scan(const DeviceStore& st, const SyncTemplate& tpl, hipStream_t stream)
 {
@@ -479,11 +501,10 @@ void launch_scan(const DeviceStore& st, const SyncTemplate& tpl, hipStream_t str
     a.st = st;
     for(int i = 0; i < 12; i++) a.pp[i] = tpl.pp[i];
     a.total_tiles = st.nch * st.F;  // the whole batch (ch0 = 0, nch = channels) or one channel block of the overlapped schedule
-    a.tiles_per_xcd = (a.total_tiles + 7) / 8;
 #ifdef MSK144_PHASE_STAMPS
     a.stamps = stamp_buffer(0);
 #endif
-    const dim3 grid(a.tiles_per_xcd * 8), block(kScanThreads);
+    const dim3 grid(tiles_per_xcd(a.total_tiles) * 8), block(kScanThreads);
 #ifdef MSK144_SCAN_LDS_PAD_BYTES
     // occupancy probe only (tools/ab_variants.py, DESIGN.md 4.3: what a fused scan -> softbits tile that keeps the mixed window beside C
     // would cost in resident workgroups): unused dynamic LDS that limits a CU to two (+15 KB) or one (+42 KB) workgroups.  Never in the product build.

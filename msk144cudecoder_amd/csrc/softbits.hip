@@ -36,6 +36,7 @@
 #include "msk144_kernels.h"
 #include "mix.h"
 #include "phase_stamps.h"
+#include "tile_map.h"
 #include "wave64.h"
 
 namespace msk144
@@ -74,7 +75,6 @@ struct SoftbitsArgs
     DeviceStore st;
     SyncTemplate tpl;
     int total_tiles;
-    int tiles_per_xcd;
     MSK144_STAMP_ARG
 };
 
@@ -132,11 +132,10 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
     __shared__ __attribute__((aligned(16))) float2 s_x[kWindowLds];
     static_assert(sizeof(s_x) <= 53248, "three workgroups per CU");
 
-    const int xcd = blockIdx.x & 7;
-    const int tile = xcd * a.tiles_per_xcd + (blockIdx.x >> 3);
-    if((blockIdx.x >> 3) >= a.tiles_per_xcd || tile >= a.total_tiles) return;
-    const int ch_rel = tile / a.st.F;  // channel inside the block [ch0, ch0 + nch)
-    const int b = tile - ch_rel * a.st.F;
+    const int tile = tile_index(blockIdx.x, a.total_tiles);  // tile_map.h
+    if(tile < 0) return;
+    const Tile tl = tile_of(tile, a.st.nch, a.st.F);
+    const int ch_rel = tl.ch_rel, b = tl.b;  // channel inside the block [ch0, ch0 + nch), frequency hypothesis
     const int ch = a.st.ch0 + ch_rel;
 
     const int tid = threadIdx.x;
@@ -154,26 +153,32 @@ __global__ __launch_bounds__(kSbThreads, 6) void softbits_kernel(const SoftbitsA
     const size_t item0 = static_cast<size_t>(ch) * a.st.K + static_cast<size_t>(b) * ncand;
     uint32_t pos_of_lane = 0u;  // lane l: scan position of the tile's candidate l (pattern l / 8, slot l % 8)
     if(lane < ncand) pos_of_lane = a.st.pos[item0 + lane];
-    // ---- mix (softbits_kernel.cuh:27-52) ----
-    const float f0 = -1.0f * a.st.freq[b];
+    // ---- mix (softbits_kernel.cuh:27-52): each sample rotated by its phasor from the handle's table (mix.h) ----
     const float2* __restrict__ cdat = a.st.analytic + static_cast<size_t>(ch) * kWindowSamples;
+    const float2* __restrict__ phasor = a.st.mix_table + static_cast<size_t>(b) * kWindowSamples;
     {
         constexpr int kPerThread = (kWindowSamples + kSbThreads - 1) / kSbThreads;  // 11 (10.125)
-        float2 xin[kPerThread];  // all loads in flight before any arithmetic
+        float2 xin[kPerThread], ph[kPerThread];  // all loads in flight before any arithmetic
 #pragma unroll
         for(int i = 0; i < kPerThread; i++)
         {
             const int n = tid + i * kSbThreads;
             xin[i] = n < kWindowSamples ? cdat[n] : make_float2(0.0f, 0.0f);
         }
-        const float tid_f = static_cast<float>(tid);
+#pragma unroll
+        for(int i = 0; i < kPerThread; i++)
+        {
+            const int n = tid + i * kSbThreads;
+            ph[i] = n < kWindowSamples ? phasor[n] : make_float2(0.0f, 0.0f);
+        }
 #pragma unroll
         for(int i = 0; i < kPerThread; i++)
         {
             const int n = tid + i * kSbThreads;
             if(n < kWindowSamples)
             {
-                const float2 y = mix_sample(xin[i], tid_f + static_cast<float>(i * kSbThreads), f0);
+                // the tail (mix.h): the last two samples, n >= 4608; i is a constant once the loop is unrolled
+                const float2 y = i >= kPerThread - 2 ? rotate<true>(xin[i], ph[i].x, ph[i].y) : rotate<false>(xin[i], ph[i].x, ph[i].y);
                 s_x[n] = y;
                 if(n < kRingPad) s_x[kWindowSamples + n] = y;
             }
@@ -534,11 +539,10 @@ void launch_softbits(const DeviceStore& st, const SyncTemplate& tpl, hipStream_t
     a.st = st;
     a.tpl = tpl;
     a.total_tiles = st.nch * st.F;
-    a.tiles_per_xcd = (a.total_tiles + 7) / 8;
 #ifdef MSK144_PHASE_STAMPS
     a.stamps = stamp_buffer(1);
 #endif
-    const int grid = a.tiles_per_xcd * 8;
+    const int grid = tiles_per_xcd(a.total_tiles) * 8;
     // LLR rows are retained only when one block covers every channel of the handle (msk144_api.cpp: dumps, parity tests)
     if(st.gate_early && st.handover) hipLaunchKernelGGL((softbits_kernel<true, true>), dim3(grid), dim3(kSbThreads), 0, stream, a);
     else if(st.gate_early) hipLaunchKernelGGL((softbits_kernel<true, false>), dim3(grid), dim3(kSbThreads), 0, stream, a);

@@ -144,6 +144,7 @@ PROTOTYPES = {
     "msk144_set_channel_base": ([_vp, _i32], C.c_int),
     "msk144_segment_power": ([_vp, _vp], C.c_int),
     "msk144_dump_analytic": ([_vp, _i32, _vp], C.c_int),
+    "msk144_dump_mix_table": ([_vp, _i32, _vp], C.c_int),
     "msk144_dump_candidates": ([_vp, _i32, _vp], C.c_int),
     "msk144_dump_indexes": ([_vp, _i32, _vp, _P(_i32)], C.c_int),
     "msk144_load_candidates": ([_vp, _i32, _vp], C.c_int),
@@ -755,6 +756,12 @@ class HipDecoder:
     def dump_analytic(self, channel=0) -> np.ndarray:
         out = np.empty(5184, dtype=np.complex64)
         self._chk(self.L.msk144_dump_analytic(self.h, channel, _ptr(out)))
+        return out
+
+    def dump_mix_table(self, b=0) -> np.ndarray:
+        """Row b of the handle's phasor table as float32 [5184][2]: (cos, sin) of the mixers' phase at frequency hypothesis b."""
+        out = np.empty((5184, 2), dtype=np.float32)
+        self._chk(self.L.msk144_dump_mix_table(self.h, b, _ptr(out)))
         return out
 
     def dump_candidates(self, channel=0) -> np.ndarray:
