@@ -44,6 +44,8 @@
  *   msk144_set_wideband_waterfall, the fast graph every MSK144 operator knows, for every channel at once: a 96-point spectrum per
  *   msk144_wideband_waterfall, 8 ms block of each channel's int8 hop, on the device (no reference counterpart)
  *   msk144_wideband_waterfall_sums
+ *   msk144_set_input_rate .. the `ffmpeg -ar 12000` step the reference's README puts in front of --read-mode=1, for every stream of a
+ *   msk144_push_rate_hops    handle at once: an integer polyphase resampler on the device in front of the hop ring (no reference counterpart)
  *   msk144_clock_probe       gpu_timer.h's role for the one figure HIP events cannot give: the shader clock a running batch
  *                            actually gets (s_memtime / s_memrealtime), read beside it on a side stream
  *
@@ -947,6 +949,67 @@ int msk144_wideband_gate(msk144_handle* h, int32_t* channels_out, int32_t* count
 /* bank rates only: band k's (-32..32, a band some channel lies in) complex f32 samples s_k[n] of the last push, re,im interleaved:
  * 5184 x P/Q after a first push, else 2592 x P/Q, with P/Q the ratio of the sub-band rate Fs/32 to 12000 */
 int msk144_dump_wideband_band(msk144_handle* h, int32_t band, float* out);
+
+/* ---- Audio input at 24 to 192 kHz: a resampler in front of the hop ring (no reference counterpart) ----
+ *
+ * The reference reads int16 audio at 12000 samples per second and sends its users through `ffmpeg -ar 12000` first; sound cards
+ * and SDR applications record at 48 kHz.  With an input rate set, a read_mode 1 handle takes every stream's hop at Fs and resamples
+ * it to 12 kHz on the device, in exact integers, into the hop ring's staging - what msk144_push_hops would have been handed.  The hop
+ * ring, the audio front end and the decode run unchanged.
+ *
+ *   Input:   real int16 samples per stream at Fs = 12000 x P/Q (lowest terms), Fs a multiple of 125 Hz, 24000 <= Fs <= 192000: Q
+ *            divides 96, hence 2592.  A stream's first hop is 5184 x P/Q input samples, every later one 2592 x P/Q, whole numbers.
+ *   Filter:  integer taps h[0..L), int16, L = K x P, 1 <= K <= 64, at the upsampled rate 12000 x P, and a shift s, 1 <= s <= 15.
+ *            The default is s = 14 and h[k] = rint(2^14 d[k]), d the channel filter's Kaiser-sinc of msk144host_wideband_taps_rate(Fs, K)
+ *            (it sums to Q), K = 16: msk144host_input_rate_taps(rate, K, out) in libmsk144host.so.  Read as h / 2^14 / Q the K = 16
+ *            taps are flat within 0.1 dB to 4 kHz and at least 60 dB down from 8 kHz (a numpy evaluation of the integer taps, no
+ *            measurement on the air stands behind it).
+ *   Headroom: checked when the taps are set: every polyphase branch has sum_k |h[r + kQ]| <= 65535.  Then |acc| <= 65535 x 32768 =
+ *            2^31 - 32768, the rounding term fits, and a 32-bit accumulator is exact for any int16 input.
+ *   Output:  per stream, m counting output samples from the stream's first sample, n_m = floor(mP/Q), r_m = (mP) mod Q, x[n < 0] = 0:
+ *                acc[m] = sum over k >= 0 with r_m + kQ < L of h[r_m + kQ] . x[n_m - k]            (exact, 32-bit)
+ *                y[m]   = clamp((acc[m] + 2^(s-1)) >> s, -32768, 32767)                             (arithmetic shift: floor)
+ *            - the wideband Q-branch formula at f_c = 0.  A value outside the int16 range is clamped and counted.  y[0..2591] goes
+ *            to the first half and y[2592..5183] to the hop on a first hop, 2592 samples to the hop afterwards.
+ *   Delay:   the filter delays the signal by (L - 1)/(2P) output samples: 8 at K = 16, 0.67 ms.
+ *   State:   the stream's last H = ceil(L/Q) - 1 input samples, kept on the device; H is shorter than a hop.  A first hop starts from
+ *            zero history.  Streams that a push does not list keep window and history.
+ *
+ *     msk144_set_input_rate(h, &p);                 resets every stream's history: each stream's next hop must be a first one, else
+ *                                                   MSK144_ESTATE.  NULL switches the resampler off and frees what it held.
+ *     msk144_rate_hop_slot(h, s, &hops, &first_halves, &streams, &is_first, &row);   the four pinned arrays of msk144_hop_slot with
+ *                                                   rows of row = 2592 x P/Q int16; allocated at the first call after a `set`
+ *     msk144_push_rate_hops(h, s, n);               the rules of msk144_push_hops: n listed streams, ascending.  H2D, resampler,
+ *                                                   history, hop ring and front end on the handle's stream
+ *     msk144_decode / msk144_fetch_async / msk144_fetch_wait   as after msk144_push_hops
+ *
+ * msk144_hop_slot / msk144_push_hops / msk144_submit_* stay what they are on such a handle and advance no history.
+ * Stage times: MSK144_T_FRONTEND includes the resampler, MSK144_T_H2D its copy.
+ * Refused: MSK144_EINVAL for a read_mode 2 handle (its input is complex int8 I/Q) or one in wideband mode, for 12000 Hz, a rate that
+ * is no multiple of 125 Hz (the 44.1 kHz family) or outside 24000..192000, L not K x P with 1 <= K <= 64, a shift outside 1..15 and a
+ * branch sum above 65535. */
+typedef struct msk144_input_rate_params
+{
+    int64_t rate_hz;      /* Fs */
+    int32_t shift;        /* s */
+    int32_t num_taps;     /* L = K x P */
+    const int16_t* taps;  /* h[0 .. num_taps) */
+} msk144_input_rate_params;
+
+/* NULL: off */
+int msk144_set_input_rate(msk144_handle* h, const msk144_input_rate_params* params);
+int msk144_rate_hop_slot(msk144_handle* h, int32_t slot, void** hops /*[channels][row]*/, void** first_halves /*[channels][row]*/, int32_t** streams /*[channels]*/,
+                         uint8_t** is_first /*[channels]*/, int32_t* row_samples);
+int msk144_push_rate_hops(msk144_handle* h, int32_t slot, int32_t n);
+/* test and debug: the resampled samples of position j of the last msk144_push_rate_hops, *n = 5184 (a first hop) or 2592; out[5184].
+ * They are read from the hop ring's staging: call it before the handle's next hop entry.  MSK144_ESTATE before any such push */
+int msk144_dump_rate_hop(msk144_handle* h, int32_t j, int16_t* out, int32_t* n);
+/* clamped outputs of every position of the last msk144_push_rate_hops; waits for it.  MSK144_ESTATE before any such push */
+int msk144_input_rate_clamped(msk144_handle* h, int32_t* clamped /*[n of the last push]*/);
+/* the same for pipelined callers, without a wait: the counts of the slot's last msk144_push_rate_hops, *n of them, in pinned memory the
+ * handle owns.  The copy runs on the handle's stream right behind the resampler, so the counts are there once msk144_fetch_wait of
+ * that hop has returned, and stay until the slot is pushed again.  MSK144_ESTATE before any such push on the slot */
+int msk144_input_rate_slot_clamped(msk144_handle* h, int32_t slot, const int32_t** clamped, int32_t* n);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,11 @@
-// The handle behind the C ABI of libmsk144hip.so, and what its two host files share: msk144_api.cpp (handle lifetime, the narrowband
-// entries, the decode) and msk144_wideband_api.cpp (every msk144_*wideband* entry).  Host code only: nothing here launches a kernel.
+// The handle behind the C ABI of libmsk144hip.so, and what its host files share: msk144_api.cpp (handle lifetime, the narrowband
+// entries, the decode), msk144_wideband_api.cpp (every msk144_*wideband* entry) and msk144_input_rate_api.cpp (the resampler in front
+// of the hop ring).  Host code only: nothing here launches a kernel.
 #pragma once
 
 #include "../../include/msk144hip.h"
 
+#include "input_rate.h"
 #include "msk144_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -210,6 +212,31 @@ struct Wideband
     } gate;
 };
 
+// The input-rate configuration of a handle (msk144_set_input_rate): one block, value-initialised is "off".  Its buffers are registered
+// with the handle's own owner (msk144_handle::mem) and freed ahead of it by a new `set`.  d_* and slot_clamped are allocated by `set`,
+// the pinned rows at the first msk144_rate_hop_slot.
+struct InputRate
+{
+    bool on = false;
+    bool pushed = false;          // a msk144_push_rate_hops has been made since `set`: what the two read entries test
+    int64_t rate_hz = 0;
+    msk144ir::Shape shape;
+    int shift = 0;
+    int hist_stride = 0;          // int16 per stream in d_hist: max(H, 1)
+    std::vector<uint8_t> started; // [channels] the stream has had a first hop since `set`
+    std::vector<uint8_t> last_first;  // [last_n] is_first of the last push
+    int last_n = 0;
+    int16_t* hops[MSK144_SLOTS] = {};          // pinned [channels][row]
+    int16_t* first_halves[MSK144_SLOTS] = {};  // pinned [channels][row]
+    int16_t* d_in_hops = nullptr;   // [channels][row]
+    int16_t* d_in_first = nullptr;  // [channels][row]
+    int16_t* d_hist = nullptr;      // [channels][hist_stride]: each stream's last H inputs, oldest first
+    uint32_t* d_taps = nullptr;     // msk144ir::pack_taps
+    int32_t* d_clamped = nullptr;   // [channels] by position of the last push
+    int32_t* slot_clamped[MSK144_SLOTS] = {};  // pinned [channels]: the counts of the last push of each slot, copied behind its resampler
+    int slot_n[MSK144_SLOTS] = {};             // n of that push; 0: none
+};
+
 struct msk144_handle
 {
     msk144_params params{};
@@ -288,6 +315,8 @@ struct msk144_handle
 
     // wideband channeliser (msk144_set_wideband); its buffers have their own owner, as a new configuration replaces them
     Wideband wb;
+    // resampler in front of the hop ring (msk144_set_input_rate)
+    InputRate ir;
 
     std::string error;
 };
@@ -354,6 +383,19 @@ template<typename T>
 int host_alloc(msk144_handle* h, Buffers& owner, T** p, size_t count)
 {
     return alloc(h, owner, true, p, count);
+}
+
+// the same for one that host_alloc registered
+template<typename T>
+void host_free(Buffers& owner, T** p)
+{
+    const auto it = std::find(owner.pinned.begin(), owner.pinned.end(), static_cast<void*>(*p));
+    if(it != owner.pinned.end())
+    {
+        (void)hipHostFree(*it);
+        owner.pinned.erase(it);
+    }
+    *p = nullptr;
 }
 
 #pragma GCC visibility pop

@@ -77,6 +77,26 @@ void launch_frontend_iq(const DeviceStore& st, const int8_t* d_in, hipStream_t s
 // first_halves[j] + hops[j] when is_first[j]); windows[j] = the stream's new window.  Halves and windows in raw input bytes.
 void launch_hop_ring(void* ring, const void* hops, const void* first_halves, const int32_t* streams, const uint8_t* is_first, void* windows, int n, hipStream_t stream);
 
+// the resampler in front of the hop ring (resample.hip; contract in include/msk144hip.h): position j of a batch of n is stream
+// streams[j]; its inputs are row j of in_hops (and of in_first on a first hop), rows of `row` = 2592 P/Q int16; its 12 kHz samples go
+// to row j of out_hops (and out_first), rows of 2592 int16, what launch_hop_ring reads.  hist[channels][hist_stride] holds each
+// stream's last H inputs; taps is msk144ir::pack_taps.  clamped[j] is added to: zero it ahead of the launch.
+struct ResampleArgs
+{
+    const int16_t* in_first;
+    const int16_t* in_hops;
+    const int32_t* streams;
+    const uint8_t* is_first;
+    const uint32_t* taps;
+    const int16_t* hist;
+    int16_t* out_first;
+    int16_t* out_hops;
+    int32_t* clamped;
+    int P, Q, H, hist_stride, row, dwords, shift;
+};
+// the resampler, then the new history of the n streams.  any_first: some is_first[j] is set (the grid then covers both halves)
+void launch_resample(const ResampleArgs& a, int n, bool any_first, hipStream_t stream);
+
 // Above 6.144 Msps the channeliser reads the analysis bank's sub-band streams (format kSubbandFormat: complex f32, one stream per
 // occupied band, stride float2 apart) and its `channels` are channel slots: slot c belongs to channel slot_channel[c] (-1: a padding
 // slot, written nowhere), and wave w (slots 32w .. 32w+31) reads stream wave_band[w].  Unused at the raw formats.

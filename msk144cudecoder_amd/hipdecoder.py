@@ -114,6 +114,10 @@ class WidebandBlankerCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in BLANKER_STATS]
 
 
+class InputRateParams(C.Structure):
+    _fields_ = [("rate_hz", C.c_int64), ("shift", C.c_int32), ("num_taps", C.c_int32), ("taps", C.POINTER(C.c_int16))]
+
+
 class Params(C.Structure):
     _fields_ = [("center_hz", C.c_float), ("width_hz", C.c_float), ("step_hz", C.c_float), ("scan_depth", C.c_int32),
                 ("nbadsync_threshold", C.c_int32), ("read_mode", C.c_int32), ("analytic_method", C.c_int32), ("channels", C.c_int32),
@@ -194,6 +198,12 @@ PROTOTYPES = {
     "msk144_wideband_capture_audio": ([_vp, _P(C.c_int16), _P(_i32), _P(_i32)], C.c_int),
     "msk144_set_wideband_gate": ([_vp, _P(WidebandGateParams), _P(C.c_uint8)], C.c_int),
     "msk144_wideband_gate": ([_vp, _P(_i32), _P(_i32), _P(_i32)], C.c_int),
+    "msk144_set_input_rate": ([_vp, _P(InputRateParams)], C.c_int),
+    "msk144_rate_hop_slot": ([_vp, _i32, _P(_vp), _P(_vp), _P(_vp), _P(_vp), _P(_i32)], C.c_int),
+    "msk144_push_rate_hops": ([_vp, _i32, _i32], C.c_int),
+    "msk144_dump_rate_hop": ([_vp, _i32, _vp, _P(_i32)], C.c_int),
+    "msk144_input_rate_clamped": ([_vp, _P(_i32)], C.c_int),
+    "msk144_input_rate_slot_clamped": ([_vp, _i32, _P(_vp), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -269,6 +279,7 @@ class HipDecoder:
         self.F, self.D, self.K = f.value, d.value, k.value
         self.channels = channels
         self.read_mode = read_mode
+        self._ir_taps, self._ir_last_n = None, 0   # the resampler's taps (kept alive for the library's call) and n of its last push
         self._wb_spectrum_bins = self._wb_spectrum_last = 0   # bins of the next wideband push and of the last one; 0: no spectrum
         b = C.c_int32()
         self._chk(self.L.msk144_llr_block_channels(self.h, C.byref(b)))
@@ -416,6 +427,62 @@ class HipDecoder:
         records = np.frombuffer((C.c_uint8 * (n.value * RESULT_DTYPE.itemsize)).from_address(rec.value), dtype=RESULT_DTYPE).copy() if n.value else np.zeros(0, dtype=RESULT_DTYPE)
         powers = np.frombuffer((C.c_float * (8 * self.channels)).from_address(seg.value), dtype=np.float32).reshape(self.channels, 8).copy()
         return records, powers
+
+    # ---- audio input at 24 to 192 kHz (read_mode 1 handles) ----
+    def set_input_rate(self, rate_hz, taps=None, taps_per_phase: int = 16, shift: Optional[int] = None):
+        """Resample every stream's hops from rate_hz to 12 kHz on the device (include/msk144hip.h).  taps=None: the default design of
+        libmsk144host.so, input_rate.default_taps(rate_hz, taps_per_phase), with shift 14; otherwise int16 taps, K x P of them, and
+        their shift.  rate_hz None switches the resampler off."""
+        self._ir_last_n = 0
+        if rate_hz is None:
+            self._chk(self.L.msk144_set_input_rate(self.h, None))
+            self._ir_taps = None
+            return
+        from .input_rate import DEFAULT_SHIFT, default_taps
+        if taps is None:
+            taps = default_taps(int(rate_hz), taps_per_phase)
+        t = np.asarray(taps)
+        if t.ndim != 1 or not np.issubdtype(t.dtype, np.integer) or np.any(t < -32768) or np.any(t > 32767):
+            raise ValueError("taps must be a row of int16 values")
+        self._ir_taps = np.ascontiguousarray(t, dtype=np.int16)
+        p = InputRateParams(int(rate_hz), DEFAULT_SHIFT if shift is None else int(shift), len(self._ir_taps), self._ir_taps.ctypes.data_as(C.POINTER(C.c_int16)))
+        self._chk(self.L.msk144_set_input_rate(self.h, C.byref(p)))
+
+    def rate_hop_slot(self, slot: int):
+        """(hops, first_halves, streams, is_first): numpy views of the slot's pinned inputs at the input rate - hops and first_halves as
+        int16 [channels][2592 P/Q], streams int32[channels], is_first uint8[channels]."""
+        p = [C.c_void_p() for _ in range(4)]
+        row = C.c_int32()
+        self._chk(self.L.msk144_rate_hop_slot(self.h, slot, *[C.byref(x) for x in p], C.byref(row)))
+        n = row.value * self.channels
+        hops = np.frombuffer((C.c_int16 * n).from_address(p[0].value), dtype=np.int16).reshape(self.channels, row.value)
+        first = np.frombuffer((C.c_int16 * n).from_address(p[1].value), dtype=np.int16).reshape(self.channels, row.value)
+        streams = np.frombuffer((C.c_int32 * self.channels).from_address(p[2].value), dtype=np.int32)
+        is_first = np.frombuffer((C.c_uint8 * self.channels).from_address(p[3].value), dtype=np.uint8)
+        return hops, first, streams, is_first
+
+    def push_rate_hops(self, slot: int, n: int):
+        self._chk(self.L.msk144_push_rate_hops(self.h, slot, n))
+        self._ir_last_n = int(n)
+
+    def dump_rate_hop(self, j: int) -> np.ndarray:
+        """int16 resampled samples of position j of the last push: 5184 for a first hop, else 2592."""
+        out = np.empty(5184, dtype=np.int16)
+        n = C.c_int32()
+        self._chk(self.L.msk144_dump_rate_hop(self.h, j, _ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def input_rate_clamped(self) -> np.ndarray:
+        """int32 [n of the last push]: clamped output samples by position."""
+        out = np.zeros(max(self._ir_last_n, 1), dtype=np.int32)   # one spare element: before any push the library answers ESTATE
+        self._chk(self.L.msk144_input_rate_clamped(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out[:self._ir_last_n]
+
+    def input_rate_slot_clamped(self, slot: int) -> np.ndarray:
+        """The same for the slot's last push, without a wait: valid once fetch_wait(slot) of that hop has returned."""
+        p, n = C.c_void_p(), C.c_int32()
+        self._chk(self.L.msk144_input_rate_slot_clamped(self.h, slot, C.byref(p), C.byref(n)))
+        return np.frombuffer((C.c_int32 * n.value).from_address(p.value), dtype=np.int32).copy()
 
     # ---- wideband channeliser (read_mode 2 handles) ----
     def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0, bank_taps=None):

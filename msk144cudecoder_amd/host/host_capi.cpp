@@ -2,6 +2,7 @@
 #include "wideband_cli.h"
 #include "window_decoder.h"
 
+#include "../csrc/input_rate.h"
 #include "../csrc/msk144_tables.h"
 #include "../csrc/wideband.h"
 
@@ -603,5 +604,44 @@ int msk144host_fft_band_mask(float* out, int cap)
     for(int i = 0; i < static_cast<int>(w.size()) && i < cap; i++) out[i] = w[i];
     return static_cast<int>(w.size());
 }
+
+// ---- the input-rate contract (csrc/input_rate.h), the functions msk144_set_input_rate and msk144hipdecoder apply ----
+// The default integer taps for Fs = 12000 P/Q, h[k] = rint(2^14 d[k]) with d the channel filter's design, for shift 14: L = K*P taps
+// into out; returns L, or -1 for a rate or K the contract refuses.
+int msk144host_input_rate_taps(int64_t rate_hz, int K, int16_t* out)
+{
+    if(!msk144ir::check_rate(rate_hz).empty() || K < 1 || K > msk144ir::kMaxTapsPerPhase) return -1;
+    const std::vector<int16_t> h = msk144ir::default_taps(rate_hz, K);
+    if(out) std::memcpy(out, h.data(), sizeof(int16_t) * h.size());
+    return static_cast<int>(h.size());
+}
+
+// check_config: returns 0 when valid, else -1 with the refusal text in why
+int msk144host_input_rate_check(int64_t rate_hz, int shift, int num_taps, const int16_t* taps, char* why, int why_len)
+{
+    const std::string s = msk144ir::check_config(rate_hz, shift, num_taps, taps);
+    if(why && why_len > 0)
+    {
+        std::strncpy(why, s.c_str(), static_cast<size_t>(why_len) - 1);
+        why[why_len - 1] = 0;
+    }
+    return s.empty() ? 0 : -1;
+}
+
+// The resampler in the integers of the contract (msk144ir::Resampler), for a configuration msk144host_input_rate_check accepts (NULL
+// otherwise).  push: x holds 2 x 2592 P/Q samples for a first hop, else 2592 P/Q; y gets 5184 or 2592; returns the clamped outputs,
+// or -1 for a later hop before a first one.
+void* msk144host_input_rate_new(int channels, int64_t rate_hz, const int16_t* taps, int num_taps, int shift)
+{
+    if(channels < 1 || !msk144ir::check_config(rate_hz, shift, num_taps, taps).empty()) return nullptr;
+    return new msk144ir::Resampler(channels, rate_hz, taps, num_taps, shift);
+}
+int msk144host_input_rate_push(void* r, int stream, const int16_t* x, int first, int16_t* y)
+{
+    msk144ir::Resampler* p = static_cast<msk144ir::Resampler*>(r);
+    if(!p || stream < 0 || stream >= static_cast<int>(p->started.size())) return -1;
+    return p->push(stream, x, first != 0, y);
+}
+void msk144host_input_rate_free(void* r) { delete static_cast<msk144ir::Resampler*>(r); }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 // multi-stream loop is pipelined over the library's two pinned staging slots (stream_loop.h): an ingest thread reads the streams and
 // submits hop n+1 while the GPU decodes hop n and a second thread turns the records of hop n-1 into text.  --devices=0,1,... runs
 // one such loop per GPU, each on its contiguous share of the streams (the reference binds to one device, main.cu:115).
+#include "input_rate_cli.h"
 #include "stream_loop.h"
 #include "wideband_run.h"
 
@@ -83,6 +84,7 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-notch=SPEC[/HALFWIDTH]  With --wideband-rate: take steady carriers (a spur, a birdie, a beacon) out of single channels, on the GPU, behind the channel filter and the AGC step and ahead of everything that reads the channel's int8 I/Q: a 64-tap complex band-pass of +-HALFWIDTH Hz (50..500, default=100) around each carrier estimates it and the estimate is taken from the channel delayed by 31 samples (2.6 ms). SPEC is a fixed table 'ch:Hz[+Hz],ch:Hz,...' - one or two frequencies per channel in Hz from the channel's offset, at least 1000 Hz apart - or 'auto[:DB[:PERIOD[:PERSIST]]]': a host rule on the channels' waterfall sums (the GPU waterfall is then on even without --wideband-waterfall) that adds a notch where the highest bin of a channel lies at least DB (default=10) over its median bin in PERSIST (default=2) consecutive sums of PERIOD pushes (default=23, about 5 s), at most two per channel; notches are only added during a run, and each is reported on stderr as 'wideband notch: ch= offset= notch= excess= at hop'. DB, PERIOD and PERSIST are design parameters, not measurements. The notch costs sensitivity on a weak ping where there is no carrier: notch only the channels that have one. At the end, on stderr, one line with the channels notched, the notches and the clamped components." << std::endl;
     std::cout << "                   --wideband-gate[=HOLD[:MIN_UP[:MAX[:ALWAYS]]]]  With --wideband-pings: decode only the channels with activity, picked on the GPU from the detector's blocks. A hop of a channel is active when at least MIN_UP (1..27, default=1) of its 27 blocks are above the threshold; the channel's window is decoded in that push and for HOLD more hops (0..16, default=1; with HOLD >= 1 every window that contains an active hop is decoded). At most MAX channels are decoded per push (default and 0: all); more are dropped in ascending channel order and counted. ALWAYS is a list of channel indices c0,c1,... that are decoded on every push; with it the option needs no --wideband-pings. An empty field keeps its default. Levels, ping events, captures and snr= of every channel stay those of a run without the gate. The detector is less sensitive than the decoder: a ping it does not see is not decoded. At the end, on stderr, one line with the channel windows decoded, the dropped ones and the busiest push." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
+    std::cout << "                   --input-rate=HZ|wav         With --read-mode=1: every audio stream (stdin, --inputs, --inputs-file, --interleaved) arrives at HZ samples per second and is resampled to 12000 on the GPU, in exact integers, ahead of the decoder. HZ is a multiple of 125 from 24000 to 192000 (e.g. 48000; the 44.1 kHz family is not supported): HZ = 12000 x P/Q, a hop is then 2592 x P/Q samples per stream and the first one 5184 x P/Q. 12000 is the program without the option. The filter is the channel filter's design, K x P integer taps with K = --taps-per-phase; it delays the signal by 0.67 ms at K = 16. 'wav', for the single stdin stream together with --skip-wav-header, takes HZ from the 44-byte header (PCM, one channel, 16 bits). At the end, on stderr, one line with the rate, P/Q, the taps, the shift and the samples clamped." << std::endl;
     // clang-format on
 }
 
@@ -157,6 +159,9 @@ int main(int argc, char* const argv[])
     std::vector<std::string> device_list;
     bool read_mode_set = false;
     WidebandOptions wbo;
+    InputRate input_rate;
+    std::string input_rate_error, taps_per_phase_arg;
+    int wideband_options = 0, taps_per_phase_options = 0;  // how many options went to take_wideband_option, and how many of them were --taps-per-phase
 
     static struct option long_options[] = {{"help", no_argument, 0, 0},
                                            {"center-frequency", required_argument, 0, 0},
@@ -196,6 +201,7 @@ int main(int argc, char* const argv[])
                                            {"wideband-notch", required_argument, 0, 0},
                                            {"wideband-audio", optional_argument, 0, 0},
                                            {"wideband-gate", optional_argument, 0, 0},
+                                           {"input-rate", required_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -203,7 +209,23 @@ int main(int argc, char* const argv[])
         const int c = getopt_long(argc, argv, "", long_options, &idx);
         if(c == -1) break;
         if(c != 0) continue;  // unknown option: getopt has printed its own message, carry on like the reference
-        if(take_wideband_option(long_options[idx].name, optarg, wbo)) continue;
+        if(!strcmp(long_options[idx].name, "input-rate"))
+        {
+            const std::string why = input_rate.parse(optarg);
+            if(!why.empty() && input_rate_error.empty()) input_rate_error = why;
+            continue;
+        }
+        if(!strcmp(long_options[idx].name, "taps-per-phase"))
+        {
+            // the wideband channeliser's, as ever; with --input-rate and no wideband option it is the resampler's (below)
+            taps_per_phase_arg = optarg;
+            taps_per_phase_options++;
+        }
+        if(take_wideband_option(long_options[idx].name, optarg, wbo))
+        {
+            wideband_options++;
+            continue;
+        }
         switch(idx)
         {
         case 0: show_help(argv[0]); return 0;
@@ -243,6 +265,14 @@ int main(int argc, char* const argv[])
         }
     }
 
+    // --taps-per-phase with --input-rate and nothing else of the wideband options: the resampler's K, and no wideband run
+    if(input_rate.given && taps_per_phase_options > 0 && wideband_options == taps_per_phase_options)
+    {
+        if(!parse_int_in(taps_per_phase_arg, 1, msk144ir::kMaxTapsPerPhase, input_rate.taps_per_phase) && input_rate_error.empty())
+            input_rate_error = "bad value for --taps-per-phase: '" + taps_per_phase_arg + "'";
+        wbo = WidebandOptions();
+    }
+
     // --wideband-pings-band: its CENTRE defaults to --center-frequency, wherever on the line that stood
     if(wbo.ping_band && !parse_wideband_ping_band(wbo.ping_band_arg, center_set ? static_cast<int>(std::lrint(opt.center_hz)) : 0, wbo) && wbo.parse_error.empty())
         wbo.parse_error = "bad value for --wideband-pings-band: '" + wbo.ping_band_arg + "'";
@@ -268,6 +298,33 @@ int main(int argc, char* const argv[])
             return 2;
         }
         opt.read_mode = 2;
+    }
+
+    // --input-rate: checked in full, and the header of --input-rate=wav read, before anything touches the library
+    bool wav_header_read = false;
+    if(input_rate.given)
+    {
+        std::string why = input_rate_error;
+        if(!why.empty()) ;  // the option's own value was bad
+        else if(wideband) why = "--input-rate resamples audio streams: it excludes --wideband-rate (whose rate is the I/Q stream's)";
+        else if(opt.read_mode != 1) why = "--input-rate resamples 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
+        else if(input_rate.from_wav && (!input_paths.empty() || interleaved != 0))
+            why = "--input-rate=wav reads the rate of the single stdin stream: with --inputs, --inputs-file or --interleaved give the rate in Hz";
+        else if(input_rate.from_wav && !skip_wav) why = "--input-rate=wav takes the rate from the stream's WAV header: it needs --skip-wav-header";
+        else if(input_rate.from_wav)
+        {
+            unsigned char hdr[44];
+            int64_t hz = 0;
+            if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) why = "--input-rate=wav: the stream ended inside its 44-byte WAV header";
+            else if((why = wav_header_rate(hdr, hz)).empty()) why = input_rate.set_rate(hz);
+            wav_header_read = true;
+        }
+        if(why.empty()) input_rate.prepare(why);
+        if(!why.empty())
+        {
+            std::cerr << why << std::endl;
+            return 2;
+        }
     }
 
     if(!center_set)
@@ -387,21 +444,75 @@ int main(int argc, char* const argv[])
               << F << " x 512, softbits " << F << " x 512, LDPC one wave per gated candidate" << std::endl;
     if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
     if(wideband && !wideband_run.configure(dec.handle())) return 2;
+    if(input_rate.on)
+    {
+        std::string why;
+        if(!input_rate.configure(dec.handle(), why))
+        {
+            std::cerr << "msk144hip: " << why << std::endl;
+            return 2;
+        }
+    }
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
     const size_t sample_bytes = (opt.read_mode == 1) ? sizeof(int16_t) : 2 * sizeof(int8_t);
-    const size_t win_bytes = MSK144_WINDOW_SAMPLES * sample_bytes;
+    // with --input-rate a hop is 2592 x P/Q samples
+    const size_t win_bytes = input_rate.on ? 2 * input_rate.row_bytes() : MSK144_WINDOW_SAMPLES * sample_bytes;
     const size_t half = win_bytes / 2;
     const size_t unit = (opt.read_mode == 1) ? sizeof(int16_t) : sizeof(int8_t);  // the reference counts items of this size
 
     if(!batched)
     {
         // ---- the reference's loop: one stream on stdin, blocking reads (main.cu:261-422) ----
-        if(skip_wav)
+        if(skip_wav && !wav_header_read)
         {
             unsigned char hdr[44];
             if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) std::cerr << "Incomplete read error. rc=0" << std::endl;
+        }
+        if(input_rate.on)
+        {
+            // the same loop at the input rate: the hop ring is the library's (msk144_push_rate_hops), so a hop carries its new samples only
+            dec.use_input_rate(&input_rate);
+            WindowDecoder::HopStage hs;
+            std::vector<std::vector<FilteredResult>> all;
+            bool first = true;
+            while(true)
+            {
+                if(!dec.hop_stage(0, hs))
+                {
+                    std::cerr << "msk144hip: " << dec.error() << std::endl;
+                    return 2;
+                }
+                const size_t want = (first ? win_bytes : half) / unit;
+                size_t rc = 0;
+                if(first)
+                {
+                    rc = fread(hs.first_halves, unit, half / unit, stdin);
+                    if(rc == half / unit) rc += fread(hs.hops, unit, half / unit, stdin);
+                }
+                else rc = fread(hs.hops, unit, want, stdin);
+                if(rc != want)
+                {
+                    std::cerr << "Incomplete read error. rc=" << rc << std::endl;
+                    break;
+                }
+                hs.streams[0] = 0;
+                hs.is_first[0] = first ? 1 : 0;
+                first = false;
+                const auto t0 = Clock::now();
+                if(!dec.submit_hops(0, 1) || !dec.collect(0, all))
+                {
+                    std::cerr << "msk144hip: " << dec.error() << std::endl;
+                    return 2;
+                }
+                if(dec.last_hop_overflowed()) std::cerr << "msk144hipdecoder: the window held more decodes than the result list (raise --max-results): the list was cut, decoding goes on" << std::endl;
+                warn_if_late(std::chrono::duration_cast<std::chrono::milliseconds>(Clock::now() - t0).count());
+                for(const FilteredResult& l : all[0]) std::cout << l.format_line() << std::endl;
+            }
+            std::cerr << input_rate.summary() << std::endl;
+            std::cout << "Done" << std::endl;
+            return 0;
         }
         std::vector<unsigned char> ring(win_bytes, 0);
         bool first = true;
@@ -458,6 +569,16 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
+        if(input_rate.on)
+        {
+            std::string why;
+            if(i > 0 && !input_rate.configure(loops[i]->decoder().handle(), why))
+            {
+                std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
+                return 2;
+            }
+            loops[i]->use_input_rate(&input_rate);
+        }
         if(wideband) loops[i]->use_wideband(&wideband_run);
         else if(interleaved > 0) loops[i]->use_feed();
         else if(!loops[i]->open_inputs(std::vector<std::string>(input_paths.begin() + shares[i].first, input_paths.begin() + shares[i].first + shares[i].count)))
@@ -555,6 +676,7 @@ int main(int argc, char* const argv[])
     }
     std::cerr << "msk144hipdecoder: " << batches << " batches, " << total_hops << " stream hops, " << total_late << " late, worst latency " << worst << " ms" << std::endl;
     if(wideband) wideband_run.print_summary(loops[0]->decoder().handle());
+    if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {

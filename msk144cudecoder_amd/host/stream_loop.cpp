@@ -1,5 +1,6 @@
 #include "stream_loop.h"
 
+#include "input_rate_cli.h"
 #include "wideband_run.h"
 
 #include <fcntl.h>
@@ -105,6 +106,14 @@ bool DeviceLoop::open_inputs(const std::vector<std::string>& paths)
         st_[c].fifo = fstat(st_[c].fd, &sb) == 0 && S_ISFIFO(sb.st_mode);
     }
     return true;
+}
+
+void DeviceLoop::use_input_rate(InputRate* ir)
+{
+    half_ = ir->row_bytes();
+    win_bytes_ = 2 * half_;
+    for(Stream& s : st_) s.pending.reserve(win_bytes_);
+    dec_.use_input_rate(ir);
 }
 
 void DeviceLoop::fail(const std::string& what)

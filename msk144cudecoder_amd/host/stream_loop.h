@@ -99,6 +99,11 @@ public:
         wb_ = run;
     }
 
+    // --input-rate (input_rate_cli.h): every stream arrives at the option's rate and is resampled on the GPU: a hop is 2592 x P/Q
+    // samples per stream (5184 x P/Q the first time), whether it comes from --inputs or through feed().  `ir` has configured
+    // decoder().handle().  Call it before open_inputs() / start().
+    void use_input_rate(InputRate* ir);
+
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
     // window afterwards).  Blocks while two blocks are already queued (back-pressure into the reader).  false once the loop failed.

@@ -1,5 +1,7 @@
 #include "window_decoder.h"
 
+#include "input_rate_cli.h"
+
 #include <chrono>
 #include <cstring>
 
@@ -106,7 +108,8 @@ void* WindowDecoder::stage(int slot)
 bool WindowDecoder::hop_stage(int slot, HopStage& out)
 {
     void *hops = nullptr, *first = nullptr;
-    if(msk144_hop_slot(handle_, slot, &hops, &first, &out.streams, &out.is_first) != MSK144_OK)
+    int32_t row = 0;
+    if((ir_ ? ir_->api.slot(handle_, slot, &hops, &first, &out.streams, &out.is_first, &row) : msk144_hop_slot(handle_, slot, &hops, &first, &out.streams, &out.is_first)) != MSK144_OK)
     {
         error_ = msk144_last_error(handle_);
         return false;
@@ -122,7 +125,7 @@ bool WindowDecoder::submit_hops(int slot, int n)
     if(!hop_stage(slot, hs)) return false;
     streams_[slot].assign(hs.streams, hs.streams + n);
     gated_[slot] = false;
-    int rc = msk144_push_hops(handle_, slot, n);
+    int rc = ir_ ? ir_->api.push(handle_, slot, n) : msk144_push_hops(handle_, slot, n);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
     if(rc != MSK144_OK)
@@ -193,6 +196,20 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
         return false;
     }
     last_overflow_ = rc == MSK144_EOVERFLOW;
+    if(ir_)
+    {
+        // the slot's hop has arrived, and with it the resampler's clamp counts of that hop
+        const int32_t* counts = nullptr;
+        int32_t positions = 0;
+        if(ir_->api.slot_clamped(handle_, slot, &counts, &positions) != MSK144_OK)
+        {
+            error_ = msk144_last_error(handle_);
+            return false;
+        }
+        long long sum = 0;
+        for(int32_t p = 0; p < positions; p++) sum += counts[p];
+        ir_->clamped += sum;
+    }
     const auto t1 = Clock::now();
     const std::vector<int>& streams = streams_[slot];
     const size_t n_results = static_cast<size_t>(n);

@@ -15,6 +15,8 @@
 namespace msk144host
 {
 
+struct InputRate;
+
 struct DecoderOptions
 {
     float center_hz = 1500.0f;
@@ -111,6 +113,11 @@ public:
     };
     bool hop_stage(int slot, HopStage& out);
     bool submit_hops(int slot, int n);  // the first n entries of the slot's hop stage
+    // --input-rate (input_rate_cli.h; `ir` has configured handle()): hop_stage() then gives the slot's rows at the input rate
+    // (msk144_rate_hop_slot: entry j at j * ir->row_bytes()) and submit_hops() pushes them through the resampler
+    // (msk144_push_rate_hops).  collect() adds the clamped samples of the slot's push to ir->clamped, behind msk144_fetch_wait
+    // (msk144_input_rate_slot_clamped: no wait of its own).
+    void use_input_rate(InputRate* ir) { ir_ = ir; }
     // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
     // it at run time): every stream, in order.  `gate` (msk144_wideband_gate, with --wideband-gate): the decode covers the channels
     // of the gate's list, which is taken behind it; collect() then gives every stream its SNR update and its post-processing, the
@@ -139,6 +146,7 @@ private:
     bool gated_[kSlots] = {};           // the slot's hop is a gated wideband push: segment powers come by stream, for every stream
     size_t window_bytes_ = 0;           // of one stream
     bool last_overflow_ = false;
+    InputRate* ir_ = nullptr;
 };
 
 }  // namespace msk144host
