@@ -1011,6 +1011,73 @@ int msk144_input_rate_clamped(msk144_handle* h, int32_t* clamped /*[n of the las
  * that hop has returned, and stay until the slot is pushed again.  MSK144_ESTATE before any such push on the slot */
 int msk144_input_rate_slot_clamped(msk144_handle* h, int32_t slot, const int32_t** clamped, int32_t* n);
 
+/* ---- Stream levels and pings: per-stream levels and a ping record of the audio hops (no reference counterpart) ----
+ *
+ * For the audio streams of msk144_push_hops and msk144_push_rate_hops the decoder reports decodes and nothing else: not whether a
+ * stream is dead, clipping, far too quiet, or full of pings that did not decode.  With the option on, every push also leaves, per
+ * listed position, the levels of its new samples and the record of the wideband ping detector run on their block energies.  read_mode
+ * 1 handles only.  The arithmetic is csrc/stream_pings.h, the kernel csrc/stream_pings.hip, the Python model
+ * msk144cudecoder_amd/stream_pings.py; all integers, nothing has a tolerance.
+ *
+ *   Input:    per listed position j of a push, for stream s = streams[j], the new 12 kHz int16 samples x of that push as the hop
+ *             ring's staging holds them - behind the resampler when an input rate is set.  A later hop has 2592 samples, nb = 27
+ *             blocks of 96; a first hop (is_first[j]) has 5184, nb = 54: the first-half row, then the hop row.
+ *   Energy:   E[b] = min(2^22 - 1, (sum over n < 96 of x[96b + n]^2) >> shift).  The sum is exact: it reaches 96 x 2^30 and is
+ *             kept in 64 bits.  shift is 0..24; the default 12 follows from the cap: audio of 30 to about 13 000 LSB rms stays inside
+ *             the range, and at 30 LSB the quiet level is still about 17.  Louder audio saturates; the saturated blocks are counted.
+ *   Rule:     the wideband ping detector's, unchanged (above; csrc/wideband.h ping_rank, ping_history_min, ping_reference, ping_up,
+ *             ping_history_put), on E with the scale fixed at 1.0f: quiet level at rank nb/4, R = max(min(quiet, the quiet levels of
+ *             the last `memory` pushes of the stream), min_ref), block b up iff E[b] x 16 > R x ratio_q4.  The record is
+ *             msk144_wideband_ping.  ratio_q4, memory and min_ref have the ranges of msk144_set_wideband_pings; the default ratio
+ *             3.5 x (ratio_q4 = 56) is the smallest multiple of 0.25 at which no block of band-limited noise was up in a run of the
+ *             model (the table in csrc/stream_pings.h; a CPU simulation, nothing measured on the air).
+ *   State:    one history per stream, indexed by stream number.  It restarts on the stream's is_first hop and on its first listed
+ *             hop after msk144_set_stream_pings (msk144_set_input_rate forces first hops already).  Streams that a push does not
+ *             list keep their state.
+ *   Levels:   msk144_stream_level per position, exact integers over the same samples.  With an input rate set these are the
+ *             levels of the resampled stream: clipping of the input at Fs is smeared by the filter, and the resampler's clamp count
+ *             (msk144_input_rate_clamped) is a separate figure.
+ *   Order:    msk144_set_stream_pings(h, &p) takes effect from the next push and allocates everything it needs - a push allocates
+ *             nothing; (h, NULL) switches it off.  Never set, or switched off again, every launch, copy and record of a push is
+ *             what it is without the option.  The kernel runs on the handle's stream behind the staging copy (and the resampler)
+ *             and ahead of the hop ring; it reads the staging, never the ring; one copy on the same stream then takes records,
+ *             levels and energies to pinned memory of the slot.  No atomics: the same hops give the same bytes.
+ *             msk144_submit_* pushes carry whole windows: they leave no records and change no state.
+ *   Refused:  MSK144_EINVAL on a read_mode 2 handle, on a handle in wideband mode and for parameters out of range; MSK144_ESTATE
+ *             from the read entries while the option is off or before a push since the `set`.
+ *   Not covered: read_mode 2 streams, a gate or a capture on these records, levels at the input rate, a band filter. */
+typedef struct msk144_stream_level
+{
+    int64_t sum;               /* sum of x */
+    int64_t sum_sq;            /* sum of x^2 */
+    int32_t peak;              /* max |x|, 0..32768 */
+    int32_t full_scale;        /* samples equal to 32767 or -32768 */
+    int32_t samples;           /* 2592 or 5184 */
+    int32_t saturated_blocks;  /* blocks whose E is the cap 2^22 - 1 */
+} msk144_stream_level;
+
+#define MSK144_STREAM_PINGS_RATIO_Q4 56
+#define MSK144_STREAM_PINGS_SHIFT 12
+
+typedef struct msk144_stream_pings_params
+{
+    int32_t ratio_q4;  /* 16..65535 (56) */
+    int32_t memory;    /* 0..16 pushes (8) */
+    int32_t min_ref;   /* 1..4194304 (96) */
+    int32_t shift;     /* 0..24 (12) */
+} msk144_stream_pings_params;
+
+/* NULL: off */
+int msk144_set_stream_pings(msk144_handle* h, const msk144_stream_pings_params* params);
+/* records[channels], levels[channels]: the first *n, by position, of the last push; waits for it */
+int msk144_stream_pings(msk144_handle* h, msk144_wideband_ping* records, msk144_stream_level* levels, int32_t* n);
+/* out[54]: the block energies of position j of the last push, *nb = 27 or 54 of them, zeros behind; waits for it */
+int msk144_stream_ping_blocks(msk144_handle* h, int32_t j, int32_t* out, int32_t* nb);
+/* for pipelined callers, without a wait: records [*n], levels [*n] and energies [*n][54] of the slot's last push, in pinned memory
+ * the handle owns.  The copy runs on the handle's stream right behind the kernel, so they are there once msk144_fetch_wait of that hop
+ * has returned, and stay until the slot is pushed again.  MSK144_ESTATE before a push on the slot since the `set` */
+int msk144_stream_pings_slot(msk144_handle* h, int32_t slot, const msk144_wideband_ping** records, const msk144_stream_level** levels, const int32_t** energies, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

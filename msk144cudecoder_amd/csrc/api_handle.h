@@ -1,6 +1,6 @@
 // The handle behind the C ABI of libmsk144hip.so, and what its host files share: msk144_api.cpp (handle lifetime, the narrowband
-// entries, the decode), msk144_wideband_api.cpp (every msk144_*wideband* entry) and msk144_input_rate_api.cpp (the resampler in front
-// of the hop ring).  Host code only: nothing here launches a kernel.
+// entries, the decode), msk144_wideband_api.cpp (every msk144_*wideband* entry), msk144_input_rate_api.cpp (the resampler in front
+// of the hop ring) and msk144_stream_pings_api.cpp (levels and pings of the audio hops).  Host code only: nothing here launches a kernel.
 #pragma once
 
 #include "../../include/msk144hip.h"
@@ -237,6 +237,25 @@ struct InputRate
     int slot_n[MSK144_SLOTS] = {};             // n of that push; 0: none
 };
 
+// Per-stream levels and pings on the audio hops (msk144_set_stream_pings): one block, value-initialised is "off".  Everything is
+// allocated by the first `set` that switches it on, registered with the handle's own owner, and kept until the handle goes; a push
+// allocates nothing.  The device results of a push are one block - records [n], levels [n], energies [n][54] - so that one copy takes
+// them to the slot's pinned block of the same layout.
+struct StreamPings
+{
+    bool on = false;              // what the next push does
+    bool pushed = false;          // a push has left results since `set`: what the read entries test
+    msk144sp::Params params;
+    std::vector<uint8_t> seen;    // [channels] the stream has been listed since `set`
+    int last_slot = 0;            // the slot of the last push, ...
+    int slot_n[MSK144_SLOTS] = {};  // ... n of each slot's last push since `set`; 0: none
+    msk144wb::PingHistory* d_state = nullptr;  // [channels] by stream
+    uint8_t* d_restart = nullptr;              // [channels] by position
+    uint8_t* d_out = nullptr;                  // the results of the last push: channels x (32 + 32 + 54 x 4) bytes
+    uint8_t* restart[MSK144_SLOTS] = {};       // pinned [channels]
+    uint8_t* out[MSK144_SLOTS] = {};           // pinned, as d_out
+};
+
 struct msk144_handle
 {
     msk144_params params{};
@@ -317,6 +336,8 @@ struct msk144_handle
     Wideband wb;
     // resampler in front of the hop ring (msk144_set_input_rate)
     InputRate ir;
+    // levels and pings of the audio hops (msk144_set_stream_pings)
+    StreamPings sp;
 
     std::string error;
 };
@@ -334,6 +355,9 @@ int begin_hop(msk144_handle* h, int32_t slot, int32_t n);
 int run_frontend(msk144_handle* h, const void* d_in);
 // defined in msk144_wideband_api.cpp: back to no wideband configuration, its buffers freed, every field reset
 void wb_release(msk144_handle* h);
+// defined in msk144_stream_pings_api.cpp: the levels and pings of a push of n audio hops, on the handle's stream behind the staging
+// copy or the resampler and ahead of the hop ring.  The two push entries call it only while h->sp.on
+int sp_push(msk144_handle* h, int32_t slot, int32_t n);
 
 #define HIP_TRY(h, expr)                                                                                   \
     do                                                                                                     \

@@ -740,6 +740,7 @@ int msk144_push_hops(msk144_handle* h, int32_t slot, int32_t n)
     if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, n, hipMemcpyHostToDevice, h->stream);
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_hops: ") + hipGetErrorString(e));
+    if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
     return run_frontend(h, h->d_input);
 }

@@ -171,6 +171,7 @@ int msk144_push_rate_hops(msk144_handle* h, int32_t slot, int32_t n)
     for(int32_t j = 0; j < n; j++) ir.started[static_cast<size_t>(sl.streams[j])] = 1;
     ir.pushed = true;
     ir.slot_n[slot] = n;
+    if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
     return run_frontend(h, h->d_input);
 }

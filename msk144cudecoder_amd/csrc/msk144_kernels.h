@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "msk144_protocol.h"
+#include "stream_pings.h"
 #include "wideband.h"
 
 namespace msk144
@@ -149,6 +150,12 @@ void launch_notch(int8_t* first_halves, int8_t* hops, int first, const int32_t* 
 // as launch_pingband left them, not summed from the hops.
 void launch_pings(const int8_t* first_halves, const int8_t* hops, int first, int channels, const float* gains, const int32_t* used_exps, const msk144wb::PingParams& p,
                   int restart, msk144wb::PingHistory* state, msk144wb::PingRecord* records, int32_t* energies, bool band, hipStream_t stream);
+
+// per-stream levels and pings of a push of audio hops (stream_pings.hip; contract in include/msk144hip.h and stream_pings.h), on the
+// hop ring's staging behind the copy or the resampler: first_halves, hops [n][2592] int16 by position; streams[n], is_first[n] and
+// restart[n] on the device; state[channels] by stream number; records[n], levels[n] and energies[n][54] by position.
+void launch_stream_pings(const void* first_halves, const void* hops, const int32_t* streams, const uint8_t* is_first, const uint8_t* restart, int n, const msk144sp::Params& p,
+                         msk144wb::PingHistory* state, msk144wb::PingRecord* records, msk144sp::Level* levels, int32_t* energies, hipStream_t stream);
 
 // the ping band of a push (pingband.hip; contract in include/msk144hip.h), ahead of launch_pings on the same stream and on the same
 // staged hops: taps[64][2] int8 on the device; tails[channels][128] bytes, a channel's 63 stored samples before the push behind two

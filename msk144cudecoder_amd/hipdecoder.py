@@ -118,6 +118,11 @@ class InputRateParams(C.Structure):
     _fields_ = [("rate_hz", C.c_int64), ("shift", C.c_int32), ("num_taps", C.c_int32), ("taps", C.POINTER(C.c_int16))]
 
 
+class StreamPingsParams(C.Structure):
+    """msk144_stream_pings_params."""
+    _fields_ = [("ratio_q4", C.c_int32), ("memory", C.c_int32), ("min_ref", C.c_int32), ("shift", C.c_int32)]
+
+
 class Params(C.Structure):
     _fields_ = [("center_hz", C.c_float), ("width_hz", C.c_float), ("step_hz", C.c_float), ("scan_depth", C.c_int32),
                 ("nbadsync_threshold", C.c_int32), ("read_mode", C.c_int32), ("analytic_method", C.c_int32), ("channels", C.c_int32),
@@ -204,6 +209,10 @@ PROTOTYPES = {
     "msk144_dump_rate_hop": ([_vp, _i32, _vp, _P(_i32)], C.c_int),
     "msk144_input_rate_clamped": ([_vp, _P(_i32)], C.c_int),
     "msk144_input_rate_slot_clamped": ([_vp, _i32, _P(_vp), _P(_i32)], C.c_int),
+    "msk144_set_stream_pings": ([_vp, _P(StreamPingsParams)], C.c_int),
+    "msk144_stream_pings": ([_vp, _P(WidebandPing), _vp, _P(_i32)], C.c_int),
+    "msk144_stream_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
+    "msk144_stream_pings_slot": ([_vp, _i32, _P(_vp), _P(_vp), _P(_vp), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -483,6 +492,47 @@ class HipDecoder:
         p, n = C.c_void_p(), C.c_int32()
         self._chk(self.L.msk144_input_rate_slot_clamped(self.h, slot, C.byref(p), C.byref(n)))
         return np.frombuffer((C.c_int32 * n.value).from_address(p.value), dtype=np.int32).copy()
+
+    # ---- per-stream levels and pings of the audio hops (read_mode 1 handles) ----
+    def set_stream_pings(self, params=True, **kw):
+        """Levels and a ping record per listed stream from the next push_hops / push_rate_hops on (include/msk144hip.h):
+        set_stream_pings() takes the defaults (stream_pings.STREAM_PINGS_DEFAULTS), keywords replace single ones (ratio_q4, memory,
+        min_ref, shift); set_stream_pings(None) switches it off."""
+        if params is None:
+            self._chk(self.L.msk144_set_stream_pings(self.h, None))
+            return
+        from .stream_pings import STREAM_PINGS_DEFAULTS
+        p = dict(STREAM_PINGS_DEFAULTS)
+        if isinstance(params, dict):
+            p.update(params)
+        p.update(kw)
+        a = StreamPingsParams(**{k: int(v) for k, v in p.items()})
+        self._chk(self.L.msk144_set_stream_pings(self.h, C.byref(a)))
+
+    def stream_pings(self):
+        """(records PING_DTYPE [n], levels stream_pings.LEVEL_DTYPE [n]) of the last push, by position; waits for it."""
+        from .stream_pings import LEVEL_DTYPE as STREAM_LEVEL_DTYPE
+        rec, lev, n = np.zeros(self.channels, dtype=PING_DTYPE), np.zeros(self.channels, dtype=STREAM_LEVEL_DTYPE), C.c_int32()
+        self._chk(self.L.msk144_stream_pings(self.h, rec.ctypes.data_as(C.POINTER(WidebandPing)), _ptr(lev), C.byref(n)))
+        return rec[:n.value].copy(), lev[:n.value].copy()
+
+    def stream_ping_blocks(self, j: int) -> np.ndarray:
+        """int32 [nb] block energies of position j of the last push: nb = 54 for a first hop, else 27."""
+        out, nb = np.zeros(PING_MAX_BLOCKS, dtype=np.int32), C.c_int32()
+        self._chk(self.L.msk144_stream_ping_blocks(self.h, int(j), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nb)))
+        return out[:nb.value].copy()
+
+    def stream_pings_slot(self, slot: int):
+        """(records [n], levels [n], energies int32 [n][54]) of the slot's last push, without a wait: valid once fetch_wait(slot) of
+        that hop has returned."""
+        from .stream_pings import LEVEL_DTYPE as STREAM_LEVEL_DTYPE
+        r, l, e, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._chk(self.L.msk144_stream_pings_slot(self.h, slot, C.byref(r), C.byref(l), C.byref(e), C.byref(n)))
+        k = n.value
+        rec = np.frombuffer((C.c_uint8 * (k * PING_DTYPE.itemsize)).from_address(r.value), dtype=PING_DTYPE).copy()
+        lev = np.frombuffer((C.c_uint8 * (k * STREAM_LEVEL_DTYPE.itemsize)).from_address(l.value), dtype=STREAM_LEVEL_DTYPE).copy()
+        en = np.frombuffer((C.c_int32 * (k * PING_MAX_BLOCKS)).from_address(e.value), dtype=np.int32).reshape(k, PING_MAX_BLOCKS).copy()
+        return rec, lev, en
 
     # ---- wideband channeliser (read_mode 2 handles) ----
     def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0, bank_taps=None):

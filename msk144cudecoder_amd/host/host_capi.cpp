@@ -1,9 +1,11 @@
 // C entry points of the GPU-independent host logic, for the CPU test-suite (libmsk144host.so).
+#include "stream_pings_cli.h"
 #include "wideband_cli.h"
 #include "window_decoder.h"
 
 #include "../csrc/input_rate.h"
 #include "../csrc/msk144_tables.h"
+#include "../csrc/stream_pings.h"
 #include "../csrc/wideband.h"
 
 #include <cstring>
@@ -643,5 +645,48 @@ int msk144host_input_rate_push(void* r, int stream, const int16_t* x, int first,
     return p->push(stream, x, first != 0, y);
 }
 void msk144host_input_rate_free(void* r) { delete static_cast<msk144ir::Resampler*>(r); }
+
+// ---- per-stream levels and pings (csrc/stream_pings.h: what msk144_set_stream_pings checks and the kernel computes) ----
+// p = {ratio_q4, memory, min_ref, shift}: 0 when msk144_set_stream_pings takes them, else -1 with the refusal text in why
+int msk144host_stream_pings_check(const int32_t* p, char* why, int why_len) { return copy_why(msk144sp::check_params(msk144sp::Params{p[0], p[1], p[2], p[3]}), why, why_len); }
+// the defaults of msk144_stream_pings_params, in the same order
+void msk144host_stream_pings_defaults(int32_t* out4)
+{
+    const msk144sp::Params p;
+    out4[0] = p.ratio_q4, out4[1] = p.memory, out4[2] = p.min_ref, out4[3] = p.shift;
+}
+// the detector of `streams` streams with their histories and seen-bits (NULL for parameters the library refuses) ...
+void* msk144host_stream_pings_new(int streams, const int32_t* p)
+{
+    const msk144sp::Params pp{p[0], p[1], p[2], p[3]};
+    if(streams < 1 || !msk144sp::check_params(pp).empty()) return nullptr;
+    return new msk144sp::Model(streams, pp);
+}
+void msk144host_stream_pings_free(void* m) { delete static_cast<msk144sp::Model*>(m); }
+// ... and one listed position of a push: x holds 5184 samples when first, else 2592; record, level and energies[54] come back.
+// -1 for a stream the model does not have
+int msk144host_stream_pings_push(void* m, int stream, int first, const int16_t* x, msk144wb::PingRecord* record, msk144sp::Level* level, int32_t* energies)
+{
+    msk144sp::Model* pm = static_cast<msk144sp::Model*>(m);
+    if(!pm || stream < 0 || stream >= pm->streams()) return -1;
+    *record = pm->push(stream, first != 0, x, *level, energies);
+    return 0;
+}
+// the event's line of the log (--stream-pings=FILE), NUL-terminated in out
+void msk144host_stream_ping_line(const msk144wb::PingEvent* e, char* out, int cap)
+{
+    std::strncpy(out, msk144sp::event_line(*e).c_str(), static_cast<size_t>(cap) - 1);
+    out[cap - 1] = 0;
+}
+// "FILE[:RATIO[:MIN_BLOCKS[:MEMORY[:SHIFT]]]]" as the program parses it: 0 and out5 = {ratio_q4, min_blocks, memory, shift, length of FILE}, else -1
+int msk144host_stream_pings_parse(const char* arg, int32_t* out5)
+{
+    std::string file;
+    msk144sp::Params p;
+    int min_blocks = 0;
+    if(!parse_stream_pings(arg, file, p, min_blocks)) return -1;
+    out5[0] = p.ratio_q4, out5[1] = min_blocks, out5[2] = p.memory, out5[3] = p.shift, out5[4] = static_cast<int32_t>(file.size());
+    return 0;
+}
 
 }  // extern "C"

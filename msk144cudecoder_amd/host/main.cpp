@@ -7,6 +7,7 @@
 // submits hop n+1 while the GPU decodes hop n and a second thread turns the records of hop n-1 into text.  --devices=0,1,... runs
 // one such loop per GPU, each on its contiguous share of the streams (the reference binds to one device, main.cu:115).
 #include "input_rate_cli.h"
+#include "stream_pings_cli.h"
 #include "stream_loop.h"
 #include "wideband_run.h"
 
@@ -85,6 +86,8 @@ void show_help(const char* prog)
     std::cout << "                   --wideband-gate[=HOLD[:MIN_UP[:MAX[:ALWAYS]]]]  With --wideband-pings: decode only the channels with activity, picked on the GPU from the detector's blocks. A hop of a channel is active when at least MIN_UP (1..27, default=1) of its 27 blocks are above the threshold; the channel's window is decoded in that push and for HOLD more hops (0..16, default=1; with HOLD >= 1 every window that contains an active hop is decoded). At most MAX channels are decoded per push (default and 0: all); more are dropped in ascending channel order and counted. ALWAYS is a list of channel indices c0,c1,... that are decoded on every push; with it the option needs no --wideband-pings. An empty field keeps its default. Levels, ping events, captures and snr= of every channel stay those of a run without the gate. The detector is less sensitive than the decoder: a ping it does not see is not decoded. At the end, on stderr, one line with the channel windows decoded, the dropped ones and the busiest push." << std::endl;
     std::cout << "                   --taps-per-phase=K          Channel filter length K x P taps (1..64; P = D for an integer rate). Default=16." << std::endl;
     std::cout << "                   --input-rate=HZ|wav         With --read-mode=1: every audio stream (stdin, --inputs, --inputs-file, --interleaved) arrives at HZ samples per second and is resampled to 12000 on the GPU, in exact integers, ahead of the decoder. HZ is a multiple of 125 from 24000 to 192000 (e.g. 48000; the 44.1 kHz family is not supported): HZ = 12000 x P/Q, a hop is then 2592 x P/Q samples per stream and the first one 5184 x P/Q. 12000 is the program without the option. The filter is the channel filter's design, K x P integer taps with K = --taps-per-phase; it delays the signal by 0.67 ms at K = 16. 'wav', for the single stdin stream together with --skip-wav-header, takes HZ from the 44-byte header (PCM, one channel, 16 bits). At the end, on stderr, one line with the rate, P/Q, the taps, the shift and the samples clamped." << std::endl;
+    std::cout << "                   --stream-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY[:SHIFT]]]]  With --read-mode=1 (stdin, --inputs, --inputs-file, --interleaved, --devices, --input-rate): a ping detector on every audio stream, on the GPU, on the 12 kHz samples the decoder gets. Each hop is cut into blocks of 96 samples (8 ms) with energy E = min(2^22-1, sum of squares >> SHIFT) (0..24, default=12: audio of 30 to about 13000 LSB rms stays in range); a block is up when E exceeds RATIO (1..4095.9, default=3.5) x the stream's quiet level, the lowest lower-quartile E of this hop and the MEMORY (0..16, default=8) before it. A run of at least MIN_BLOCKS (1..64, default=2) up blocks is an event; when it closes one line is appended to FILE: ping ch=<stream> start=<s> dur=<s> blocks=<n> peak=<E> ref=<R> peak_db=<dB>, start counted from the stream's first sample. An empty field keeps its default. At the end, on stderr, one line with the events, the streams that had any, the blocks up and the three most active streams. A strong-ping detector, less sensitive than the decoder; the default RATIO comes from a CPU simulation on noise. Stdout is unchanged." << std::endl;
+    std::cout << "                   --stream-levels             With --read-mode=1: at the end, on stderr, one line per stream - rms in LSB over the run, peak, full-scale samples, hops and all-zero hops, of the 12 kHz samples the decoder gets (behind the resampler with --input-rate) - and one line with the three streams with the most full-scale samples, the three quietest and every stream whose hops were all zero. Stdout is unchanged." << std::endl;
     // clang-format on
 }
 
@@ -160,7 +163,8 @@ int main(int argc, char* const argv[])
     bool read_mode_set = false;
     WidebandOptions wbo;
     InputRate input_rate;
-    std::string input_rate_error, taps_per_phase_arg;
+    StreamStats stream_stats;
+    std::string input_rate_error, taps_per_phase_arg, stream_stats_error;
     int wideband_options = 0, taps_per_phase_options = 0;  // how many options went to take_wideband_option, and how many of them were --taps-per-phase
 
     static struct option long_options[] = {{"help", no_argument, 0, 0},
@@ -202,6 +206,8 @@ int main(int argc, char* const argv[])
                                            {"wideband-audio", optional_argument, 0, 0},
                                            {"wideband-gate", optional_argument, 0, 0},
                                            {"input-rate", required_argument, 0, 0},
+                                           {"stream-pings", required_argument, 0, 0},
+                                           {"stream-levels", no_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -213,6 +219,17 @@ int main(int argc, char* const argv[])
         {
             const std::string why = input_rate.parse(optarg);
             if(!why.empty() && input_rate_error.empty()) input_rate_error = why;
+            continue;
+        }
+        if(!strcmp(long_options[idx].name, "stream-pings"))
+        {
+            const std::string why = stream_stats.parse_pings(optarg);
+            if(!why.empty() && stream_stats_error.empty()) stream_stats_error = why;
+            continue;
+        }
+        if(!strcmp(long_options[idx].name, "stream-levels"))
+        {
+            stream_stats.levels = true;
             continue;
         }
         if(!strcmp(long_options[idx].name, "taps-per-phase"))
@@ -327,6 +344,21 @@ int main(int argc, char* const argv[])
         }
     }
 
+    // --stream-pings, --stream-levels: checked in full before anything touches the library
+    if(stream_stats.on())
+    {
+        const std::string which = stream_stats.pings ? "--stream-pings" : "--stream-levels";
+        std::string why = stream_stats_error;
+        if(!why.empty()) ;  // the option's own value was bad
+        else if(wideband) why = which + " reads the audio streams' hops: it excludes --wideband-rate (whose channels have --wideband-pings and --wideband-levels)";
+        else if(opt.read_mode != 1) why = which + " reads 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
+        if(!why.empty())
+        {
+            std::cerr << why << std::endl;
+            return 2;
+        }
+    }
+
     if(!center_set)
     {
         if(opt.read_mode == 1) opt.center_hz = 1500.0f;
@@ -356,6 +388,12 @@ int main(int argc, char* const argv[])
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
     const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
     opt.profile = timing && batched;
+    // --stream-pings, --stream-levels: the entries resolved and the log opened before anything touches the library
+    if(std::string why; stream_stats.on() && !stream_stats.prepare(nch, why))
+    {
+        std::cerr << why << std::endl;
+        return 2;
+    }
     {
         // one descriptor per stream plus what the runtime opens: lift the soft limit when the hard limit allows
         rlimit lim{};
@@ -453,6 +491,16 @@ int main(int argc, char* const argv[])
             return 2;
         }
     }
+    if(stream_stats.on())
+    {
+        std::string why;
+        if(!stream_stats.configure(dec.handle(), why))
+        {
+            std::cerr << "msk144hip: " << why << std::endl;
+            return 2;
+        }
+        dec.use_stream_stats(&stream_stats, 0);
+    }
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
@@ -470,10 +518,11 @@ int main(int argc, char* const argv[])
             unsigned char hdr[44];
             if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) std::cerr << "Incomplete read error. rc=0" << std::endl;
         }
-        if(input_rate.on)
+        if(input_rate.on || stream_stats.on())
         {
-            // the same loop at the input rate: the hop ring is the library's (msk144_push_rate_hops), so a hop carries its new samples only
-            dec.use_input_rate(&input_rate);
+            // the same loop over the library's hop ring (msk144_push_rate_hops at the input rate, msk144_push_hops for the levels and
+            // pings of a 12 kHz stream, which a whole-window submit does not produce): a hop carries its new samples only
+            if(input_rate.on) dec.use_input_rate(&input_rate);
             WindowDecoder::HopStage hs;
             std::vector<std::vector<FilteredResult>> all;
             bool first = true;
@@ -510,7 +559,9 @@ int main(int argc, char* const argv[])
                 warn_if_late(std::chrono::duration_cast<std::chrono::milliseconds>(Clock::now() - t0).count());
                 for(const FilteredResult& l : all[0]) std::cout << l.format_line() << std::endl;
             }
-            std::cerr << input_rate.summary() << std::endl;
+            if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
+            stream_stats.finish();
+            for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
             std::cout << "Done" << std::endl;
             return 0;
         }
@@ -578,6 +629,16 @@ int main(int argc, char* const argv[])
                 return 2;
             }
             loops[i]->use_input_rate(&input_rate);
+        }
+        if(stream_stats.on())
+        {
+            std::string why;
+            if(i > 0 && !stream_stats.configure(loops[i]->decoder().handle(), why))
+            {
+                std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
+                return 2;
+            }
+            loops[i]->decoder().use_stream_stats(&stream_stats, shares[i].first);
         }
         if(wideband) loops[i]->use_wideband(&wideband_run);
         else if(interleaved > 0) loops[i]->use_feed();
@@ -677,6 +738,8 @@ int main(int argc, char* const argv[])
     std::cerr << "msk144hipdecoder: " << batches << " batches, " << total_hops << " stream hops, " << total_late << " late, worst latency " << worst << " ms" << std::endl;
     if(wideband) wideband_run.print_summary(loops[0]->decoder().handle());
     if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
+    stream_stats.finish();
+    for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {

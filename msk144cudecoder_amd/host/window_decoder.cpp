@@ -1,6 +1,7 @@
 #include "window_decoder.h"
 
 #include "input_rate_cli.h"
+#include "stream_pings_cli.h"
 
 #include <chrono>
 #include <cstring>
@@ -125,6 +126,7 @@ bool WindowDecoder::submit_hops(int slot, int n)
     if(!hop_stage(slot, hs)) return false;
     streams_[slot].assign(hs.streams, hs.streams + n);
     gated_[slot] = false;
+    hops_[slot] = true;
     int rc = ir_ ? ir_->api.push(handle_, slot, n) : msk144_push_hops(handle_, slot, n);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
@@ -141,6 +143,7 @@ bool WindowDecoder::submit_wideband(int slot, bool first, int (*push)(msk144_han
     streams_[slot].resize(static_cast<size_t>(opt_.channels));
     for(int c = 0; c < opt_.channels; c++) streams_[slot][static_cast<size_t>(c)] = c;
     gated_[slot] = gate != nullptr;
+    hops_[slot] = false;
     int rc = push(handle_, slot, first ? 1 : 0);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK && gate)
@@ -164,6 +167,7 @@ bool WindowDecoder::submit(int slot, const std::vector<int>& streams)
 {
     streams_[slot] = streams;
     gated_[slot] = false;
+    hops_[slot] = false;
     int rc = msk144_submit_slot_n(handle_, slot, static_cast<int32_t>(streams.size()));
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
@@ -210,6 +214,8 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
         for(int32_t p = 0; p < positions; p++) sum += counts[p];
         ir_->clamped += sum;
     }
+    // ... and, with --stream-pings or --stream-levels, the records and levels of its push
+    if(stats_ && hops_[slot] && !stats_->take(handle_, slot, stats_base_, streams_[slot], error_)) return false;
     const auto t1 = Clock::now();
     const std::vector<int>& streams = streams_[slot];
     const size_t n_results = static_cast<size_t>(n);

@@ -16,6 +16,7 @@ namespace msk144host
 {
 
 struct InputRate;
+struct StreamStats;
 
 struct DecoderOptions
 {
@@ -118,6 +119,14 @@ public:
     // (msk144_push_rate_hops).  collect() adds the clamped samples of the slot's push to ir->clamped, behind msk144_fetch_wait
     // (msk144_input_rate_slot_clamped: no wait of its own).
     void use_input_rate(InputRate* ir) { ir_ = ir; }
+    // --stream-pings / --stream-levels (stream_pings_cli.h; `stats` has configured handle()): collect() hands the records, levels and
+    // block energies of the slot's submit_hops() push to stats->take(), behind msk144_fetch_wait (msk144_stream_pings_slot: no wait
+    // of its own); `base` is the program's number of this decoder's stream 0
+    void use_stream_stats(StreamStats* stats, int base)
+    {
+        stats_ = stats;
+        stats_base_ = base;
+    }
     // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
     // it at run time): every stream, in order.  `gate` (msk144_wideband_gate, with --wideband-gate): the decode covers the channels
     // of the gate's list, which is taken behind it; collect() then gives every stream its SNR update and its post-processing, the
@@ -147,6 +156,9 @@ private:
     size_t window_bytes_ = 0;           // of one stream
     bool last_overflow_ = false;
     InputRate* ir_ = nullptr;
+    StreamStats* stats_ = nullptr;
+    int stats_base_ = 0;
+    bool hops_[kSlots] = {};            // the slot's hop came through submit_hops()
 };
 
 }  // namespace msk144host
