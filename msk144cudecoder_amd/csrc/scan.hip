@@ -21,12 +21,14 @@
 //  2b. E[n] = C[n] + C[n + 336]: the two sync words of a frame, once per ring position (in place, one more barrier), so that
 //     S(pos, p) = sum_m E[(pos + 864 m) mod N] costs the fold one load and one add per frame;
 //  3. fold + |S|^2 per pattern along RUNS: a lane walks eleven consecutive positions of one 256-position slice and keeps a
-//     running maximum and its position per pattern (strict >: the lowest position keeps exact ties, as the reference's
-//     strict-> trees) - one compare, one max and one select per (position, pattern) and no cross-lane reduction, where
-//     the earlier form (positions across lanes, a 6-step DPP max + two ballots per 128 positions and pattern) spent half
-//     of the phase on reductions.  24 runs cover a slice = three aligned octets of lanes: each octet reduces in registers
-//     (3 DPP steps, first lane at the maximum wins) and one thread per (pattern, slice) merges three octets;
-//  4. xb = sqrt (correctly rounded) of the 21 x D slice maxima in parallel; then one wave, lane = 8*pattern + slot, runs the
+//     running maximum per pattern and no position - two positions per v_max3_f32 and no cross-lane reduction, where
+//     the earlier forms spent a compare, a max and a select per (position, pattern), or (positions across lanes, a 6-step DPP
+//     max + two ballots per 128 positions and pattern) half of the phase on reductions.  24 runs cover a slice = three aligned
+//     octets of lanes: each octet reduces in registers (3 DPP steps, first lane at the maximum wins) and parks (maximum, run);
+//  4a. the winners' pass: one lane per (pattern, slice), the pattern wave-uniform, takes the first strict maximum over the
+//     slice's three octets and walks the winning run once more for its position (strict >: the lowest position keeps exact
+//     ties, as the reference's strict-> trees); xb = sqrt (correctly rounded) of that maximum;
+//  4b. one wave, lane = 8*pattern + slot, runs the
 //     reference's 8-slot replacement rule in slice order (scan_kernel.cuh:276-353): arg-min over a pattern's 8 slots by
 //     three DPP min steps + ballot (lowest slot wins ties), conditional replace.
 #include "msk144_kernels.h"
@@ -102,75 +104,173 @@ static_assert(kOutGroups % 3 != 0 && (kOutSpan * 3) % 32 == kPulseHalf, "u -> 3u
 constexpr int kStreamPad = kOutSpan * (kOutGroups - 1) + kPulseHalf - 1 + kStream - (kWindowSamples + kWrapPad);
 static_assert(kStreamPad > 0 && kStreamPad < 64, "LDS buffer carries kStreamPad readable (unused) samples behind the wrap pad");
 
-template<int kSign>
-__device__ __forceinline__ void acc_signed(float2& acc, const float2 v)
+// acc (+/-)= v, or acc = v for an accumulator's first term: R_r opens with s1 P_r and Q_r with s0 B_r, and an accumulator that
+// started from zero paid an add for it.  The opening term goes in with a plus sign; R_r and Q_r are therefore kept as s1 R_r and
+// s0 Q_r, every later term carries its sign times that one, and the combination into C[r] takes the two signs back out.  Negating
+// every term of a sum negates each rounded partial sum exactly, so C keeps its bits (a zero may change its sign, which |S|^2 cannot see).
+template<int kSign, bool kFirst>
+__device__ __forceinline__ void acc_signed(v2f& acc, const v2f v)
 {
-    if constexpr(kSign > 0)
+    if constexpr(kFirst)
     {
-        acc.x += v.x;
-        acc.y += v.y;
+        static_assert(kSign > 0, "the opening term carries its own sign: plus");
+        acc = v;
     }
+    else if constexpr(kSign > 0)
+        acc += v;
     else
-    {
-        acc.x -= v.x;
-        acc.y -= v.y;
-    }
+        acc -= v;
 }
 
+// Complex values are two-float vectors from the load to the combination into C: every multiply-add and add below is one packed
+// instruction on a register pair as written.  Left as pairs of scalar expressions the same arithmetic went through the SLP
+// vectoriser, which packed most of it but bought its pairs with v_mov_b32 (88 of them and 15 v_pk_mov_b32 in this function).
 __device__ __forceinline__ void correlate_pulses(lds_f2_ptr xs, const float (&pp)[12], float2 (&c)[kOutPerThread])
 {
-    float2 racc[kOutPerThread], qacc[kOutPerThread];
-#pragma unroll
-    for(int r = 0; r < kOutPerThread; r++)
-    {
-        racc[r] = make_float2(0.0f, 0.0f);
-        qacc[r] = make_float2(0.0f, 0.0f);
-    }
-    float2 a_prev = make_float2(0.0f, 0.0f);
+    constexpr int kR = kSync8Pm[1], kQ = kSync8Pm[0];  // racc[r] holds kR R_r, qacc[r] holds kQ Q_r
+    v2f racc[kOutPerThread], qacc[kOutPerThread];
+    v2f a_prev = {0.0f, 0.0f};
     // Left alone, the scheduler clusters the 90 loads and sinks the arithmetic behind them (114 VGPRs; capping the registers
-    // spills, sched_barrier makes it worse).  The empty asm at the end of every half-pulse takes A_i and B_i as read-write
-    // operands together with `off`, an opaque zero in the next loads' address: the half-pulse's arithmetic must be complete -
-    // its six samples dead - before the loads of the next one can issue.
+    // spills, sched_barrier makes it worse).  The empty asm at the end of every half-pulse reads A_i and B_i, each a 64-bit
+    // operand, and takes `off`, an opaque zero in the next loads' address, as a read-write operand: the half-pulse's arithmetic
+    // must be complete - its six samples dead - before the loads of the next one can issue.  A_i and B_i are inputs only: as
+    // read-write operands each was copied in front of the statement, since its value lives on in an accumulator.
     int off = 0;
 #pragma unroll
     for(int i = 0; i < kHalfPulses; i++)
     {
-        float2 x[kPulseHalf];
+        v2f x[kPulseHalf];
 #pragma unroll
-        for(int d = 0; d < kPulseHalf; d++) x[d] = as_float2(xs[off + i * kPulseHalf + d]);
+        for(int d = 0; d < kPulseHalf; d++) x[d] = xs[off + i * kPulseHalf + d];
         // A_i (pp[0] = sin 0 = 0: five terms) and B_i (pp[6] = 1: the first term is the sample)
-        float2 av = make_float2(x[1].x * pp[1], x[1].y * pp[1]);
-        float2 bv = x[0];  // pp[6] = sin pi/2 = 1 exactly (checked at create)
+        v2f av = x[1] * pp[1];
+        v2f bv = x[0];  // pp[6] = sin pi/2 = 1 exactly (checked at create)
 #pragma unroll
-        for(int d = 2; d < kPulseHalf; d++)
-        {
-            av.x = fmaf(x[d].x, pp[d], av.x);
-            av.y = fmaf(x[d].y, pp[d], av.y);
-        }
+        for(int d = 2; d < kPulseHalf; d++) av = __builtin_elementwise_fma(x[d], v2f{pp[d], pp[d]}, av);
 #pragma unroll
-        for(int d = 1; d < kPulseHalf; d++)
-        {
-            bv.x = fmaf(x[d].x, pp[kPulseHalf + d], bv.x);
-            bv.y = fmaf(x[d].y, pp[kPulseHalf + d], bv.y);
-        }
-        if(i < kOutPerThread) acc_signed<kSync8Pm[0]>(qacc[i], bv);                                   // Q_i  += s0 B_i
+        for(int d = 1; d < kPulseHalf; d++) bv = __builtin_elementwise_fma(x[d], v2f{pp[kPulseHalf + d], pp[kPulseHalf + d]}, bv);
+        if(i < kOutPerThread) acc_signed<kQ * kSync8Pm[0], true>(qacc[i], bv);                              // Q_i  = s0 B_i
         if(i >= 1)
         {
-            const int j = i - 1;                                                                       // P_j = A_j + B_(j+1)
-            const float2 pv = make_float2(a_prev.x + bv.x, a_prev.y + bv.y);
-            if(j < kOutPerThread) acc_signed<kSync8Pm[1]>(racc[j], pv);                                // R_j     += s1 P_j
-            if(j >= 2 && j - 2 < kOutPerThread) acc_signed<kSync8Pm[3]>(racc[j - 2], pv);              // R_(j-2) += s3 P_j
-            if(j >= 4 && j - 4 < kOutPerThread) acc_signed<kSync8Pm[5]>(racc[j - 4], pv);              // R_(j-4) += s5 P_j
-            if(j >= 1 && j - 1 < kOutPerThread) acc_signed<kSync8Pm[2]>(qacc[j - 1], pv);              // Q_(j-1) += s2 P_j
-            if(j >= 3 && j - 3 < kOutPerThread) acc_signed<kSync8Pm[4]>(qacc[j - 3], pv);              // Q_(j-3) += s4 P_j
-            if(j >= 5 && j - 5 < kOutPerThread) acc_signed<kSync8Pm[6]>(qacc[j - 5], pv);              // Q_(j-5) += s6 P_j
+            const int j = i - 1;                                                                             // P_j = A_j + B_(j+1)
+            const v2f pv = a_prev + bv;
+            if(j < kOutPerThread) acc_signed<kR * kSync8Pm[1], true>(racc[j], pv);                           // R_j      = s1 P_j
+            if(j >= 2 && j - 2 < kOutPerThread) acc_signed<kR * kSync8Pm[3], false>(racc[j - 2], pv);        // R_(j-2) += s3 P_j
+            if(j >= 4 && j - 4 < kOutPerThread) acc_signed<kR * kSync8Pm[5], false>(racc[j - 4], pv);        // R_(j-4) += s5 P_j
+            if(j >= 1 && j - 1 < kOutPerThread) acc_signed<kQ * kSync8Pm[2], false>(qacc[j - 1], pv);        // Q_(j-1) += s2 P_j
+            if(j >= 3 && j - 3 < kOutPerThread) acc_signed<kQ * kSync8Pm[4], false>(qacc[j - 3], pv);        // Q_(j-3) += s4 P_j
+            if(j >= 5 && j - 5 < kOutPerThread) acc_signed<kQ * kSync8Pm[6], false>(qacc[j - 5], pv);        // Q_(j-5) += s6 P_j
         }
-        if(i >= 6) acc_signed<kSync8Pm[7]>(racc[i - 6], av);                                           // R_(i-6) += s7 A_i
+        if(i >= 6) acc_signed<kR * kSync8Pm[7], false>(racc[i - 6], av);                                     // R_(i-6) += s7 A_i
         a_prev = av;
-        asm volatile("" : "+v"(off), "+v"(av.x), "+v"(av.y), "+v"(bv.x), "+v"(bv.y));
+        asm volatile("" : "+v"(off) : "v"(av), "v"(bv));
     }
+    // C[r] = (R.x + Q.y, Q.x - R.y) with R = kR racc, Q = kQ qacc: a product by +-1 is the value or its negation, a source modifier
+    constexpr float fr = static_cast<float>(kR), fq = static_cast<float>(kQ);
 #pragma unroll
-    for(int r = 0; r < kOutPerThread; r++) c[r] = make_float2(racc[r].x + qacc[r].y, qacc[r].x - racc[r].y);
+    for(int r = 0; r < kOutPerThread; r++) c[r] = make_float2(fr * racc[r].x + fq * qacc[r].y, fq * qacc[r].x - fr * racc[r].y);
+}
+
+// ---- fold: |S|^2 of a position for a pattern, runs of positions ----
+// -DMSK144_SCAN_TRACK_POS=1 builds the earlier fold beside the present one (tools/ab_variants.py): every lane keeps the position
+// of its running maximum per pattern - one compare, one max and one select per (position, pattern) - and the octets pass
+// positions on.  Never in the product build.
+#ifndef MSK144_SCAN_TRACK_POS
+#define MSK144_SCAN_TRACK_POS 0
+#endif
+constexpr bool kScanTrackPos = MSK144_SCAN_TRACK_POS != 0;
+
+typedef const volatile __attribute__((address_space(3))) v2f* lds_run_ptr;
+
+// first position of run `run` (= the lane that walks it: 24 runs per slice, the last one restarts at 245 and overlaps), 0..5365
+__device__ __forceinline__ uint32_t run_start(int run)
+{
+    const int slice = run / kRunsPerSlice;
+    const int k = run - slice * kRunsPerSlice;
+    const int in_slice = k * kRun < kSlicePositions - kRun ? k * kRun : kSlicePositions - kRun;  // last run: 245..255
+    return static_cast<uint32_t>(slice * kSlicePositions + in_slice);
+}
+
+// E of frame m at the positions of the run that starts at `start`
+__device__ __forceinline__ lds_run_ptr run_frame(const float2* s_buf, uint32_t start, int m)
+{
+    uint32_t ta = start + static_cast<uint32_t>(kFrameSamples * m);  // < 2 * ring
+    ta = min(ta, ta - static_cast<uint32_t>(kWindowSamples));
+    ta = min(ta, ta - static_cast<uint32_t>(kWindowSamples));        // start itself may exceed the ring (positions reach 5375)
+    return (lds_run_ptr)(s_buf + ta);
+}
+
+// |S|^2 from the folded sum.  The value goes through an empty asm: with neighbouring patterns' values in sight the SLP vectoriser
+// pairs them into v_pk_mul_f32 + v_pk_fma_f32 and pays three v_mov_b32 per pair to line the operands up (16.0 priced cycles for
+// what two v_mul_f32 + v_fma_f32 do in 9.8).
+__device__ __forceinline__ float abs2_alone(float sr, float si)
+{
+    float v = fmaf(sr, sr, si * si);
+    asm("" : "+v"(v));
+    return v;
+}
+
+// |S|^2 of patterns 0 .. kD - 1 at one position from its frames.  Patterns 0..5 are nested prefixes: S accumulates across them;
+// 6 and 7 (100100, 100110) start from frame 0 again and take the frames of their mask in rising order.
+template<int kD, int kFrames>
+__device__ __forceinline__ void fold_position(const float2 (&ef)[kFrames], float (&v)[kD])
+{
+    float sr = 0.0f, si = 0.0f;
+#pragma unroll
+    for(int p = 0; p < kD; p++)
+    {
+        if(p == 0 || p >= kPatternBits)
+        {
+            sr = ef[0].x;
+            si = ef[0].y;
+        }
+#pragma unroll
+        for(int m = 1; m < kPatternBits; m++)
+        {
+            if(p < kPatternBits ? m == p : kPatternMask[p][m] != 0)
+            {
+                sr += ef[m].x;
+                si += ef[m].y;
+            }
+        }
+        v[p] = abs2_alone(sr, si);
+    }
+}
+
+// The winners' pass of one (pattern, slice): the run that holds the slice's maximum, walked once more for pattern kP alone with the
+// fold's rule - |S|^2 from the same sums in the same order, strict >, the maximum from 0, the index 0 when nothing is greater - so
+// the pair it returns is the one the run's lane would have kept had it tracked positions (NaN and all-zero windows included).
+template<int kP>
+__device__ __forceinline__ void walk_winning_run(const float2* s_buf, uint32_t start, float& best, uint32_t& pos)
+{
+    lds_run_ptr pe[kPatternBits];
+#pragma unroll
+    for(int m = 0; m < kPatternBits; m++)
+        if(kPatternMask[kP][m]) pe[m] = run_frame(s_buf, start, m);
+    best = 0.0f;
+    uint32_t idx = 0u;
+#pragma unroll
+    for(int i = 0; i < kRun; i++)
+    {
+        const float2 e0 = as_float2(pe[0][i]);
+        float sr = e0.x, si = e0.y;
+#pragma unroll
+        for(int m = 1; m < kPatternBits; m++)
+        {
+            if(kPatternMask[kP][m])
+            {
+                const float2 e = as_float2(pe[m][i]);
+                sr += e.x;
+                si += e.y;
+            }
+        }
+        asm("" : "+v"(sr), "+v"(si));  // out of the SLP vectoriser's sight, as in abs2_alone; on the sums here, so that v is known to be no signalling NaN
+        const float v = fmaf(sr, sr, si * si);
+        const bool better = v > best;  // strict >: the lowest position keeps exact ties
+        best = __builtin_fmaxf(v, best);
+        idx = better ? static_cast<uint32_t>(i) : idx;
+    }
+    pos = start + idx;
 }
 
 template<int kD>
@@ -281,9 +381,12 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     __syncthreads();
     MSK144_STAMP(5);
 
-    // ---- 3. fold per pattern, |S|^2, running arg-max along this lane's run of positions ----
+    // ---- 3. fold per pattern, |S|^2, running maximum along this lane's run of positions ----
     // kD is a template parameter: the pattern loop is straight-line code.  Patterns 7 and 8 (100100, 100110) reuse the frames
     // already loaded.  Lane stride = 11 positions = 22 dwords: the 32 lanes of a ds_read_b64 group tile all 64 banks.
+    // The run keeps the maximum alone: a position is wanted for the winner of each (pattern, slice) only, 21 D of the 5544 D
+    // (position, pattern) pairs of a tile, and the winners' pass (4a) walks those runs again.  Two positions go into one
+    // v_max3_f32 - five of them and one v_max_f32 per pattern and run, where compare + max + select took 33 instructions.
     constexpr int D = kD;
     constexpr int kFrames = kD < kPatternBits ? kD : kPatternBits;
     const bool has_run = tid < kScanSlices * kRunsPerSlice;
@@ -297,67 +400,52 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     }
     if(has_run)
     {
-        const int slice = tid / kRunsPerSlice;
-        const int k = tid - slice * kRunsPerSlice;
-        const int in_slice = k * kRun < kSlicePositions - kRun ? k * kRun : kSlicePositions - kRun;  // last run: 245..255
-        const uint32_t start = static_cast<uint32_t>(slice * kSlicePositions + in_slice);            // 0..5365
-        typedef const volatile __attribute__((address_space(3))) v2f* lds_run_ptr;
+        const uint32_t start = run_start(tid);
         lds_run_ptr pe[kFrames];
 #pragma unroll
-        for(int m = 0; m < kFrames; m++)
-        {
-            uint32_t ta = start + static_cast<uint32_t>(kFrameSamples * m);  // < 2 * ring
-            ta = min(ta, ta - static_cast<uint32_t>(kWindowSamples));
-            ta = min(ta, ta - static_cast<uint32_t>(kWindowSamples));        // start itself may exceed the ring (positions reach 5375)
-            pe[m] = (lds_run_ptr)(s_buf + ta);
-        }
+        for(int m = 0; m < kFrames; m++) pe[m] = run_frame(s_buf, start, m);
 #pragma unroll
-        for(int i = 0; i < kRun; i++)
+        for(int i = 0; i < kRun; i += 2)
         {
             float2 ef[kFrames];
+            float v0[D], v1[D];
 #pragma unroll
             for(int m = 0; m < kFrames; m++) ef[m] = as_float2(pe[m][i]);
-            float sr = 0.0f, si = 0.0f;
+            fold_position<D, kFrames>(ef, v0);
+            if(i + 1 < kRun)
+            {
+#pragma unroll
+                for(int m = 0; m < kFrames; m++) ef[m] = as_float2(pe[m][i + 1]);
+                fold_position<D, kFrames>(ef, v1);
+            }
 #pragma unroll
             for(int p = 0; p < D; p++)
             {
-                if(p == 0)
+                if constexpr(kScanTrackPos)
                 {
-                    sr = ef[0].x;
-                    si = ef[0].y;
-                }
-                else if(p < kPatternBits)
-                {
-                    sr += ef[p].x;  // nested prefix masks: add frame p
-                    si += ef[p].y;
-                }
-                else
-                {
-                    sr = ef[0].x;  // patterns 7 and 8 (100100, 100110) start from frame 0 again
-                    si = ef[0].y;
-#pragma unroll
-                    for(int m = 1; m < kPatternBits; m++)
+                    // strict >: the lowest position keeps exact ties
+                    const bool better0 = v0[p] > best[p];
+                    best[p] = __builtin_fmaxf(v0[p], best[p]);
+                    bidx[p] = better0 ? static_cast<uint32_t>(i) : bidx[p];
+                    if(i + 1 < kRun)
                     {
-                        if(kPatternMask[p][m])
-                        {
-                            sr += ef[m].x;
-                            si += ef[m].y;
-                        }
+                        const bool better1 = v1[p] > best[p];
+                        best[p] = __builtin_fmaxf(v1[p], best[p]);
+                        bidx[p] = better1 ? static_cast<uint32_t>(i + 1) : bidx[p];
                     }
                 }
-                const float v = fmaf(sr, sr, si * si);
-                // strict >: the lowest position keeps exact ties
-                const bool better = v > best[p];
-                best[p] = __builtin_fmaxf(v, best[p]);
-                bidx[p] = better ? static_cast<uint32_t>(i) : bidx[p];
+                else if(i + 1 < kRun)
+                    best[p] = __builtin_fmaxf(__builtin_fmaxf(v0[p], v1[p]), best[p]);  // v_max3_f32; NaN operands are ignored, as by v_max_f32
+                else
+                    best[p] = __builtin_fmaxf(v0[p], best[p]);
             }
-            // every pattern's running maximum of this position is complete before the next position's loads may issue
+            // every pattern's running maximum of these positions is complete before the next positions' loads may issue
             // (patterns 7 and 8 do not depend on all frames, so tying only the last sum would let the others pile up):
             // the window pointers are volatile, so the next position's loads stay behind this statement; its operands make
             // the statement wait for this position's arithmetic
             // (every fourth position rather than every one: two or three positions in flight hide the LDS latency of the next loads
-            // without costing a register - 76 VGPRs either way; none at all lets the loads pile up again: 9.42 -> 9.22 / 10.3 ms)
-            if(i % 4 == 3) asm volatile("" : "+v"(best[0]), "+v"(best[D - 1]), "+v"(best[D > 6 ? 5 : 0]), "+v"(best[D > 7 ? 6 : 0]));
+            // without costing a register; none at all lets the loads pile up again: 9.42 -> 9.22 / 10.3 ms)
+            if(i % 4 == 2) asm volatile("" : "+v"(best[0]), "+v"(best[D - 1]), "+v"(best[D > 6 ? 5 : 0]), "+v"(best[D > 7 ? 6 : 0]));
         }
 #pragma unroll
         for(int p = 0; p < D; p++) bidx[p] += start;
@@ -366,10 +454,10 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     // ---- 3b. the 24 runs of a slice meet: octet maxima in registers, three octets per slice through LDS ----
     // Runs sit in lane order (tid = 24 slice + run), so a slice is exactly three aligned groups of eight lanes.  Each octet reduces
     // its eight running maxima with three DPP steps and the FIRST lane holding the maximum (lowest position: the reference's
-    // strict-> trees keep the lowest position on exact ties) parks its (|S|^2, position) pair in s_oct - two masked stores per
+    // strict-> trees keep the lowest position on exact ties) parks its (|S|^2, run) pair in s_oct - two masked stores per
     // pattern instead of twelve unconditional ones per thread, and a three-element merge per (pattern, slice) instead of a
     // 24-element one that kept six of the eight waves waiting.  s_oct is its own 4 KB of LDS, so no barrier is needed between the
-    // fold loop (which still reads the window buffer) and these stores.
+    // fold loop (which still reads the window buffer) and these stores.  The run is named by its lane, tid.
     {
         float omax[D + (D & 1)];
 #pragma unroll
@@ -391,7 +479,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
             if(is_max && (eq & lower) == 0ull)
             {
                 s_oct_v[p][oct] = best[p];
-                s_oct_pos[p][oct] = bidx[p];
+                s_oct_pos[p][oct] = kScanTrackPos ? bidx[p] : static_cast<uint32_t>(tid);
             }
         }
     }
@@ -400,25 +488,71 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(const ScanArgs a)
     MSK144_STAMP(8);
 
     // ---- 4a. slice maximum = first strict maximum over its three octets in position order, xb = |S| (correctly rounded sqrt) ----
-    for(int e = tid; e < D * kScanSlices; e += kScanThreads)
+    // Job (pattern p, slice sl) is lane sl of wave p (D <= 8 = the number of waves): the pattern is wave-uniform, so the winners'
+    // pass - the winning run walked again for the position of its maximum, walk_winning_run - is straight-line code per pattern,
+    // with that pattern's loads alone.  The window buffer still holds E.
+    if constexpr(kScanTrackPos)
     {
-        const int p = e / kScanSlices;
-        const int sl = e - p * kScanSlices;
-        float bv = s_oct_v[p][3 * sl];
-        uint32_t bp = s_oct_pos[p][3 * sl];
-#pragma unroll
-        for(int k = 1; k < kRunsPerSlice / 8; k++)
+        for(int e = tid; e < D * kScanSlices; e += kScanThreads)
         {
-            const float v = s_oct_v[p][3 * sl + k];
-            const uint32_t q = s_oct_pos[p][3 * sl + k];
-            if(v > bv)
+            const int p = e / kScanSlices;
+            const int sl = e - p * kScanSlices;
+            float bv = s_oct_v[p][3 * sl];
+            uint32_t bp = s_oct_pos[p][3 * sl];
+#pragma unroll
+            for(int k = 1; k < kRunsPerSlice / 8; k++)
             {
-                bv = v;
-                bp = q;
+                const float v = s_oct_v[p][3 * sl + k];
+                const uint32_t q = s_oct_pos[p][3 * sl + k];
+                if(v > bv)
+                {
+                    bv = v;
+                    bp = q;
+                }
             }
+            s_xb[p][sl] = f32_sqrt(bv);
+            s_xpos[p][sl] = bp;
         }
-        s_xb[p][sl] = f32_sqrt(bv);
-        s_xpos[p][sl] = bp;
+    }
+    else
+    {
+        static_assert(D <= kScanThreads / 64, "one wave per pattern");
+        const int p = __builtin_amdgcn_readfirstlane(wave);
+        if(p < D && lane < kScanSlices)
+        {
+            const int sl = lane;
+            float bv = s_oct_v[p][3 * sl];
+            uint32_t run = s_oct_pos[p][3 * sl];
+#pragma unroll
+            for(int k = 1; k < kRunsPerSlice / 8; k++)
+            {
+                const float v = s_oct_v[p][3 * sl + k];
+                const uint32_t q = s_oct_pos[p][3 * sl + k];
+                if(v > bv)
+                {
+                    bv = v;
+                    run = q;
+                }
+            }
+            // a run of this slice, whatever the cell held: the walk below stays inside the window buffer
+            run = min(run - static_cast<uint32_t>(kRunsPerSlice * sl), static_cast<uint32_t>(kRunsPerSlice - 1)) + static_cast<uint32_t>(kRunsPerSlice * sl);
+            const uint32_t start = run_start(static_cast<int>(run));
+            float wv = 0.0f;
+            uint32_t wpos = 0u;
+            switch(p)
+            {
+            case 0: walk_winning_run<0>(s_buf, start, wv, wpos); break;
+            case 1: if constexpr(D > 1) walk_winning_run<1>(s_buf, start, wv, wpos); break;
+            case 2: if constexpr(D > 2) walk_winning_run<2>(s_buf, start, wv, wpos); break;
+            case 3: if constexpr(D > 3) walk_winning_run<3>(s_buf, start, wv, wpos); break;
+            case 4: if constexpr(D > 4) walk_winning_run<4>(s_buf, start, wv, wpos); break;
+            case 5: if constexpr(D > 5) walk_winning_run<5>(s_buf, start, wv, wpos); break;
+            case 6: if constexpr(D > 6) walk_winning_run<6>(s_buf, start, wv, wpos); break;
+            default: if constexpr(D > 7) walk_winning_run<7>(s_buf, start, wv, wpos); break;
+            }
+            s_xb[p][sl] = f32_sqrt(wv);
+            s_xpos[p][sl] = wpos;
+        }
     }
     __syncthreads();
     MSK144_STAMP(9);

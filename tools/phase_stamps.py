@@ -31,8 +31,11 @@ CSRC = os.path.join(ROOT, "msk144cudecoder_amd", "csrc")
 
 SCAN_PHASES = [  # (name, from slot, to slot)
     ("mix (global loads, sincos, LDS store)", 11, 1), ("barrier after mix", 1, 2), ("correlate (pulse decomposition)", 2, 3),
-    ("barrier, C store, barrier", 3, 4), ("E pass (read, barrier, write, barrier)", 4, 5), ("fold + running arg-max (11 positions x D)", 5, 6),
-    ("octet merge (DPP max, ballots, stores)", 6, 7), ("barrier after octet merge", 7, 8), ("slice merge 4a + barrier", 8, 9), ("8-slot rule (wave 0 only)", 9, 10)]
+    ("barrier, C store, barrier", 3, 4), ("E pass (read, barrier, write, barrier)", 4, 5), ("fold + running maxima (11 positions x D)", 5, 6),
+    ("octet merge (DPP max, ballots, stores)", 6, 7), ("barrier after octet merge", 7, 8),
+    # the winners' pass is one straight-line walk per pattern behind a switch on the wave: the listing segment holds all D of them and is
+    # priced whole, wave 0 (the stamped one) runs pattern 0's alone, the shortest
+    ("slice merge + winners' pass (priced: all D walks) + barrier", 8, 9), ("8-slot rule (wave 0 only)", 9, 10)]
 SOFTBITS_PHASES = [("mix (global loads, sincos, LDS store)", 11, 1), ("barrier after mix", 1, 2)]
 
 
