@@ -1045,7 +1045,8 @@ int msk144_input_rate_slot_clamped(msk144_handle* h, int32_t slot, const int32_t
  *             msk144_submit_* pushes carry whole windows: they leave no records and change no state.
  *   Refused:  MSK144_EINVAL on a read_mode 2 handle, on a handle in wideband mode and for parameters out of range; MSK144_ESTATE
  *             from the read entries while the option is off or before a push since the `set`.
- *   Not covered: read_mode 2 streams, a gate or a capture on these records, levels at the input rate, a band filter. */
+ *   Not covered: read_mode 2 streams, a capture on these records, levels at the input rate, a band filter.  The gate on these
+ *             records is the next section. */
 typedef struct msk144_stream_level
 {
     int64_t sum;               /* sum of x */
@@ -1077,6 +1078,68 @@ int msk144_stream_ping_blocks(msk144_handle* h, int32_t j, int32_t* out, int32_t
  * the handle owns.  The copy runs on the handle's stream right behind the kernel, so they are there once msk144_fetch_wait of that hop
  * has returned, and stay until the slot is pushed again.  MSK144_ESTATE before a push on the slot since the `set` */
 int msk144_stream_pings_slot(msk144_handle* h, int32_t slot, const msk144_wideband_ping** records, const msk144_stream_level** levels, const int32_t** energies, int32_t* n);
+
+/* ---- Stream gate: only the streams with activity are decoded (no reference counterpart) ----
+ *
+ * The wideband gate (above) for the audio streams of msk144_push_hops and msk144_push_rate_hops: a stream is noise for minutes and
+ * carries a ping for a fraction of a second, yet every listed stream's window goes through scan, softbits and LDPC on every push.
+ * With the stream gate on, the stream-ping records of a push pick the listed positions whose window is decoded, on the device; the
+ * decode then runs on those alone.  Staging copy, resampler, stream pings, hop ring and the audio front end run for every listed
+ * position as without it, so levels, ping records and the eight segment powers of every position are those of an ungated push.  The
+ * detector is less sensitive than the decoder: a ping it does not see is not decoded.  read_mode 1 handles only.  An opt-in extra:
+ * never set, or switched off again, every launch, copy and record of a push is what it is without this entry.  The rule is
+ * csrc/stream_gate.h on csrc/wideband.h gate_step, the kernels csrc/stream_gate.hip, the Python model stream_pings.StreamGate.
+ *
+ *   Rule:       per listed position j of a push, s = streams[j].
+ *               Mask: with ratio_q4 = 0, records[j].up_mask of the push's stream-ping record.  Otherwise bit b < records[j].blocks
+ *               is E[j][b] . 16 > records[j].reference . ratio_q4 (ping_up) on the block energies and the reference the detector
+ *               left for this push - the gate's own ratio, so that the log keeps a strict ratio while the gate triggers on a looser
+ *               one (the table in csrc/stream_gate.h: a CPU simulation, nothing measured on the air).  While stream pings are off
+ *               the mask is 0 whatever the ratio: then only the `always` streams are decoded.
+ *               Step: the wideband gate's, unchanged, on since[s]: a later hop walks bits 0..26, a first hop (is_first[j]) hops 0 and 1,
+ *               bits 0..26 and 27..53; a hop is active iff at least min_up of its 27 blocks are up; since = active ? 0 :
+ *               min(since + 1, 17); the window is decoded iff always[s] or since <= hold.  A first hop, and the stream's first listed hop
+ *               since msk144_set_stream_gate, start from since = 17.
+ *   State:      `since` is indexed by stream number.  A stream that a push does not list keeps it: it had no hop, its window did
+ *               not move.
+ *   Parameters: 0 <= hold <= 16 hops (default 1), 1 <= min_up <= 27 blocks (default 1), 1 <= max_streams <= channels or 0 = all,
+ *               ratio_q4 0 or 16..65535 (default 0: no new number), and an `always` flag per stream number, any subset.  hold and
+ *               min_up are the wideband gate's design parameters, not measurements.
+ *   Order:      the positions that are in, in ascending j.  Of `total` the first min(total, max_streams) are listed and decoded,
+ *               the rest dropped and only counted; `since` moves the same for every position either way.  The header is {count,
+ *               total, hop}, hop the number of gated pushes since the `set`, minus 1.  On the handle's stream: the staging copy, the
+ *               resampler where one is set, the stream-pings kernel and its copy, the gate's mask where ratio_q4 != 0, the plan, one
+ *               copy of header and list to the slot's pinned block, an event; then the hop ring and the front end for all n positions;
+ *               then the gather of the listed positions' analytic windows into a store of the gate's own: max_streams rows, or
+ *               `channels` rows when max_streams is 0, of 41 472 bytes each.  msk144_set_stream_gate allocates everything - a push
+ *               allocates nothing - and takes effect from the next push; (h, NULL, NULL) switches the gate off.
+ *   Decode:     msk144_decode_stages on such a push waits for that event - the one host wait the gate adds, as for the wideband
+ *               gate - and runs scan .. collect on `count` windows.  count = 0 launches nothing and leaves 0 records.  A record's
+ *               channel is its index i in the list: the caller maps index -> position -> stream.  msk144_copy_count,
+ *               msk144_dump_analytic and the candidate dumps go by list index too.  msk144_fetch_wait returns seg_power[n][8] by
+ *               position, for all n positions.  msk144_submit_* pushes carry whole windows: they are not gated and move no state.
+ *   Refused:    MSK144_EINVAL on a read_mode 2 handle, on a handle in wideband mode and for parameters out of range (a refused call
+ *               changes nothing, and a `set` that fails to allocate leaves the gate as it was); MSK144_ESTATE from the read entries
+ *               while the gate is off, and between an accepted
+ *               msk144_set_stream_gate and the next gated push (msk144_stream_gate_slot: the next one on that slot).
+ *   Not covered: read_mode 2 streams, a capture, a band filter, skipping the front end of unlisted streams (their segment powers
+ *               feed the SNR), rotating which streams are dropped over max_streams. */
+typedef struct msk144_stream_gate_params
+{
+    int32_t hold;         /* hops a stream stays in after its last active one, 0..16 (1) */
+    int32_t min_up;       /* up blocks that make a hop active, 1..27 (1) */
+    int32_t max_streams;  /* stream windows decoded per push, 1..channels; 0: all */
+    int32_t ratio_q4;     /* 0: the detector's own up mask; else 16..65535, the gate's own ratio (above) */
+} msk144_stream_gate_params;
+
+/* params NULL: off.  always[channels] BY STREAM NUMBER, nonzero = decoded on every push that lists the stream; NULL: none */
+int msk144_set_stream_gate(msk144_handle* h, const msk144_stream_gate_params* params, const uint8_t* always);
+/* the last push: positions_out[0 .. *count) the listed POSITIONS j (ascending), *total all that qualified; positions_out holds
+ * max_streams as last set, channels when 0.  Waits for the gate's event only, not for the stream */
+int msk144_stream_gate(msk144_handle* h, int32_t* positions_out, int32_t* count, int32_t* total);
+/* pipelined callers, no wait: the slot's last push, in pinned memory the handle owns; valid once msk144_fetch_wait of that hop
+ * has returned, until the slot is pushed again */
+int msk144_stream_gate_slot(msk144_handle* h, int32_t slot, const int32_t** positions, int32_t* count, int32_t* total);
 
 #ifdef __cplusplus
 }

@@ -39,10 +39,12 @@ SOURCES = [
     ("audio.hip", []),  # behind every older .hip: tests are parametrised by a kernel file's position in this list
     ("resample.hip", []),
     ("stream_pings.hip", []),
+    ("stream_gate.hip", []),
     ("msk144_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("msk144_wideband_api.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("msk144_input_rate_api.cpp", ["-x", "hip"]),
     ("msk144_stream_pings_api.cpp", ["-x", "hip"]),
+    ("msk144_stream_gate_api.cpp", ["-x", "hip"]),
 ]
 HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "msk144hip.h")]
 

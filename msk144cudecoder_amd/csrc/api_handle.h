@@ -1,6 +1,7 @@
 // The handle behind the C ABI of libmsk144hip.so, and what its host files share: msk144_api.cpp (handle lifetime, the narrowband
 // entries, the decode), msk144_wideband_api.cpp (every msk144_*wideband* entry), msk144_input_rate_api.cpp (the resampler in front
-// of the hop ring) and msk144_stream_pings_api.cpp (levels and pings of the audio hops).  Host code only: nothing here launches a kernel.
+// of the hop ring), msk144_stream_pings_api.cpp (levels and pings of the audio hops) and msk144_stream_gate_api.cpp (the gate on
+// those pings).  Host code only: nothing here launches a kernel.
 #pragma once
 
 #include "../../include/msk144hip.h"
@@ -254,6 +255,38 @@ struct StreamPings
     uint8_t* d_out = nullptr;                  // the results of the last push: channels x (32 + 32 + 54 x 4) bytes
     uint8_t* restart[MSK144_SLOTS] = {};       // pinned [channels]
     uint8_t* out[MSK144_SLOTS] = {};           // pinned, as d_out
+
+    // the one layout of d_out and out[] for a push of n positions - records [n], levels [n], energies [n][54] - in bytes from the
+    // start: what sp_push writes, the read entries take apart, and the stream gate reads its records and energies from
+    static size_t levels_at(int n) { return sizeof(msk144wb::PingRecord) * static_cast<size_t>(n); }
+    static size_t energies_at(int n) { return levels_at(n) + sizeof(msk144sp::Level) * static_cast<size_t>(n); }
+    static size_t out_bytes(int n) { return energies_at(n) + sizeof(int32_t) * msk144sp::kMaxBlocks * static_cast<size_t>(n); }
+};
+
+// The stream gate (msk144_set_stream_gate): one block, value-initialised is "off".  Everything is allocated by `set`, registered with
+// the handle's own owner and kept until the handle goes - the packed store for the largest row count set so far (`rows`; a larger
+// one frees it and allocates anew); a push allocates nothing.  Each slot has its pinned header with the list behind it, and its
+// event, recorded behind the copy of both: what msk144_decode_stages and the read entries wait for, not the stream.
+struct StreamGate
+{
+    bool on = false;              // what the next push does
+    bool pushed = false;          // a push has left a list since `set`: what msk144_stream_gate tests
+    msk144sg::Params params;
+    int rows = 0;                 // rows of d_analytic
+    long long pushes = 0;         // gated pushes since `set`
+    std::vector<uint8_t> seen;    // [channels] the stream has been listed since `set`
+    int last_slot = 0;            // the slot of the last push, ...
+    bool slot_pushed[MSK144_SLOTS] = {};  // ... and whether each slot has had one since `set`
+    uint8_t* d_always = nullptr;                // [channels] by stream
+    int32_t* d_since = nullptr;                 // [channels] by stream
+    uint8_t* d_restart = nullptr;               // [channels] by position
+    unsigned long long* d_masks = nullptr;      // [channels] by position: the gate's own masks (ratio_q4 != 0)
+    msk144wb::PlanHeader* d_header = nullptr;   // [1]
+    int32_t* d_list = nullptr;                  // [channels]
+    float2* d_analytic = nullptr;               // [rows][5184]: row i is the window of position list[i]
+    uint8_t* restart[MSK144_SLOTS] = {};                // pinned [channels]
+    msk144wb::PlanHeader* header[MSK144_SLOTS] = {};    // pinned: the header, and behind it the list, int32 [channels]
+    hipEvent_t planned[MSK144_SLOTS] = {};
 };
 
 struct msk144_handle
@@ -279,8 +312,15 @@ struct msk144_handle
     int active = 1;     // channels the current hop covers (msk144_submit_slot_n: the first n of the slot); <= st.channels
     bool have_window = false;
     bool decoded = false;
-    bool gated = false;  // the current hop is a wideband push made with the gate on (Wideband::Gate): the decode covers the listed channels ...
+    bool gated = false;  // the current hop is a push made with a gate on (Wideband::Gate, StreamGate): the decode covers the listed windows ...
     int gated_n = 0;     // ... this many, which the last decode read from the gate's header
+    // what the gate that made the current hop hands the decode and the dumps (set by wb_gate_gather, sg_gather)
+    struct GatedHop
+    {
+        const msk144wb::PlanHeader* header = nullptr;  // pinned
+        hipEvent_t planned = nullptr;                  // recorded behind the copy to it
+        float2* analytic = nullptr;                    // the packed store
+    } gate_of;
     bool profiling = false;
     // HIP-event pairs recorded around each stage; a pool so that many steps can be in flight
     // before the times are harvested at the next synchronisation point
@@ -338,6 +378,8 @@ struct msk144_handle
     InputRate ir;
     // levels and pings of the audio hops (msk144_set_stream_pings)
     StreamPings sp;
+    // the gate on those pings (msk144_set_stream_gate)
+    StreamGate sg;
 
     std::string error;
 };
@@ -358,6 +400,13 @@ void wb_release(msk144_handle* h);
 // defined in msk144_stream_pings_api.cpp: the levels and pings of a push of n audio hops, on the handle's stream behind the staging
 // copy or the resampler and ahead of the hop ring.  The two push entries call it only while h->sp.on
 int sp_push(msk144_handle* h, int32_t slot, int32_t n);
+// defined in msk144_stream_gate_api.cpp.  sg_plan: the gate's list of a push of n audio hops, on the handle's stream behind sp_push
+// and ahead of the hop ring, its header and list to the slot's pinned block, and the event.  sg_gather: behind run_frontend, the
+// listed positions' analytic windows into the gate's store; it makes the hop a gated one.  The two push entries call them only
+// while h->sg.on.  sg_release: the events, which no owner frees
+int sg_plan(msk144_handle* h, int32_t slot, int32_t n);
+int sg_gather(msk144_handle* h, int32_t n);
+void sg_release(msk144_handle* h);
 
 #define HIP_TRY(h, expr)                                                                                   \
     do                                                                                                     \

@@ -411,6 +411,7 @@ void msk144_destroy(msk144_handle* h)
     if(h->probe_stream) (void)hipStreamSynchronize(h->probe_stream);
     if(h->stream) (void)hipStreamSynchronize(h->stream);
     wb_release(h);
+    sg_release(h);
     h->mem.release();
     for(auto& sl : h->slots)
         if(sl.done) (void)hipEventDestroy(sl.done);
@@ -503,7 +504,7 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
     {
         // The one host wait the gate adds (include/msk144hip.h): the launches below are sized by the number of listed channels, and
         // the hot kernels are given neither an indirection nor an early exit.  It waits for the plan's event, not for the stream
-        const auto& g = h->wb.gate;
+        const auto& g = h->gate_of;
         HIP_TRY(h, hipEventSynchronize(g.planned));
         const int n = g.header->count;
         if(n < 0 || n > h->st.channels) return fail(h, MSK144_EHIP, "msk144_decode_stages: the device left a gate header out of range");
@@ -516,7 +517,7 @@ int msk144_decode_stages(msk144_handle* h, uint32_t stages)
             return MSK144_OK;
         }
         cur.channels = cur.nch = n;
-        cur.analytic = g.d_analytic;
+        cur.analytic = g.analytic;
     }
     if(stages & MSK144_STAGE_SCAN)
     {
@@ -741,8 +742,10 @@ int msk144_push_hops(msk144_handle* h, int32_t slot, int32_t n)
     ev_end(h, MSK144_T_H2D);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_hops: ") + hipGetErrorString(e));
     if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
+    if(h->sg.on && (rc = sg_plan(h, slot, n)) != MSK144_OK) return rc;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
-    return run_frontend(h, h->d_input);
+    if((rc = run_frontend(h, h->d_input)) != MSK144_OK || !h->sg.on) return rc;
+    return sg_gather(h, n);
 }
 
 int msk144_fetch_async(msk144_handle* h, int32_t slot)
@@ -800,7 +803,7 @@ int msk144_dump_analytic(msk144_handle* h, int32_t channel, float* out)
     if(!h || !out || channel < 0 || channel >= h->st.channels) return fail(h, MSK144_EINVAL, "bad argument");
     int rc = msk144_synchronize(h);
     if(rc != MSK144_OK) return rc;
-    HIP_TRY(h, hipMemcpy(out, (h->gated ? h->wb.gate.d_analytic : h->st.analytic) + static_cast<size_t>(channel) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out, (h->gated ? h->gate_of.analytic : h->st.analytic) + static_cast<size_t>(channel) * kWindowSamples, sizeof(float2) * kWindowSamples, hipMemcpyDeviceToHost));
     return MSK144_OK;
 }
 

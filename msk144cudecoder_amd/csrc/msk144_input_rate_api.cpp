@@ -172,8 +172,10 @@ int msk144_push_rate_hops(msk144_handle* h, int32_t slot, int32_t n)
     ir.pushed = true;
     ir.slot_n[slot] = n;
     if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
+    if(h->sg.on && (rc = sg_plan(h, slot, n)) != MSK144_OK) return rc;
     launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
-    return run_frontend(h, h->d_input);
+    if((rc = run_frontend(h, h->d_input)) != MSK144_OK || !h->sg.on) return rc;
+    return sg_gather(h, n);
 }
 
 int msk144_dump_rate_hop(msk144_handle* h, int32_t j, int16_t* out, int32_t* n)

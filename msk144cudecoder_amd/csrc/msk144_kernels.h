@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "msk144_protocol.h"
+#include "stream_gate.h"
 #include "stream_pings.h"
 #include "wideband.h"
 
@@ -198,6 +199,16 @@ void launch_audio_copy(const int16_t* audio, const int32_t* clamped, const msk14
 void launch_gate_plan(const msk144wb::PingRecord* records, const uint8_t* always, int32_t* since, int channels, int first, int clear, const msk144wb::GateParams& p,
                       long long newest, msk144wb::PlanHeader* header, int32_t* list, hipStream_t stream);
 void launch_gate_gather(const float2* analytic, const msk144wb::PlanHeader* header, const int32_t* list, int channels, float2* packed, hipStream_t stream);
+
+// the stream gate of a push of n audio hops (stream_gate.hip; contract in include/msk144hip.h and stream_gate.h), behind
+// launch_stream_pings on the same stream.  Mask, only with a ratio of the gate's own: masks[j] from records[n] and energies[n][54]
+// as the detector left them.  Plan: streams[n], is_first[n] and restart[n] by position on the device; records[n] or nullptr (the
+// detector is off), masks[n] or nullptr (the record's up mask decides); always[channels] and since[channels] by stream number;
+// writes the header {count, total, hop} and the first min(total, cap) positions of list.  The gather is launch_gate_gather with n.
+void launch_stream_gate_mask(const msk144wb::PingRecord* records, const int32_t* energies, int n, int ratio_q4, unsigned long long* masks, hipStream_t stream);
+void launch_stream_gate_plan(const int32_t* streams, const uint8_t* is_first, const uint8_t* restart, const msk144wb::PingRecord* records, const unsigned long long* masks,
+                             const uint8_t* always, int32_t* since, int n, const msk144sg::Params& p, int cap, long long hop, msk144wb::PlanHeader* header, int32_t* list,
+                             hipStream_t stream);
 
 // what the blanker counts on the device (blanker.hip): the last push's sum of powers, hits and blanked samples (zeroed by the host
 // before every push), the guard samples a push's last hit owes to the next one, by push parity, and the totals since the first push

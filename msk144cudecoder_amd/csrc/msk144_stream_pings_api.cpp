@@ -10,11 +10,6 @@ using namespace msk144;
 namespace
 {
 
-// the results of a push of n positions, on the device and in a slot's pinned block: records [n], levels [n], energies [n][54]
-size_t levels_at(int n) { return sizeof(msk144wb::PingRecord) * static_cast<size_t>(n); }
-size_t energies_at(int n) { return levels_at(n) + sizeof(msk144sp::Level) * static_cast<size_t>(n); }
-size_t out_bytes(int n) { return energies_at(n) + sizeof(int32_t) * msk144sp::kMaxBlocks * static_cast<size_t>(n); }
-
 // the read entries that wait: on, and a push has been made since the `set`
 int sp_read_ready(msk144_handle* h, const char* entry)
 {
@@ -43,11 +38,11 @@ int sp_push(msk144_handle* h, int32_t slot, int32_t n)
     if(e == hipSuccess)
     {
         launch_stream_pings(h->d_first, h->d_hops, h->d_streams, h->d_isfirst, sp.d_restart, n, sp.params, sp.d_state, reinterpret_cast<msk144wb::PingRecord*>(sp.d_out),
-                            reinterpret_cast<msk144sp::Level*>(sp.d_out + levels_at(n)), reinterpret_cast<int32_t*>(sp.d_out + energies_at(n)), h->stream);
+                            reinterpret_cast<msk144sp::Level*>(sp.d_out + StreamPings::levels_at(n)), reinterpret_cast<int32_t*>(sp.d_out + StreamPings::energies_at(n)), h->stream);
         e = hipGetLastError();
     }
     // the slot's own copy: complete when the slot's fetch is, whatever the other slot pushes meanwhile
-    if(e == hipSuccess) e = hipMemcpyAsync(sp.out[slot], sp.d_out, out_bytes(n), hipMemcpyDeviceToHost, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(sp.out[slot], sp.d_out, StreamPings::out_bytes(n), hipMemcpyDeviceToHost, h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("stream pings: ") + hipGetErrorString(e));
     sp.slot_n[slot] = n;
@@ -78,7 +73,7 @@ int msk144_set_stream_pings(msk144_handle* h, const msk144_stream_pings_params* 
     if(!p) return MSK144_OK;
 
     const size_t nch = static_cast<size_t>(h->st.channels);
-    const size_t bytes = out_bytes(h->st.channels);
+    const size_t bytes = StreamPings::out_bytes(h->st.channels);
     int rc;
     if(!sp.d_state && (rc = dev_alloc(h, h->mem, &sp.d_state, nch)) != MSK144_OK) return rc;
     if(!sp.d_restart && (rc = dev_alloc(h, h->mem, &sp.d_restart, nch)) != MSK144_OK) return rc;
@@ -102,7 +97,7 @@ int msk144_stream_pings(msk144_handle* h, msk144_wideband_ping* records, msk144_
     const StreamPings& sp = h->sp;
     const int count = sp.slot_n[sp.last_slot];
     std::memcpy(records, sp.out[sp.last_slot], sizeof(msk144wb::PingRecord) * static_cast<size_t>(count));
-    std::memcpy(levels, sp.out[sp.last_slot] + levels_at(count), sizeof(msk144sp::Level) * static_cast<size_t>(count));
+    std::memcpy(levels, sp.out[sp.last_slot] + StreamPings::levels_at(count), sizeof(msk144sp::Level) * static_cast<size_t>(count));
     *n = count;
     return MSK144_OK;
 }
@@ -113,7 +108,7 @@ int msk144_stream_ping_blocks(msk144_handle* h, int32_t j, int32_t* out, int32_t
     const StreamPings& sp = h->sp;
     const int count = sp.slot_n[sp.last_slot];
     if(!out || !nb || j < 0 || j >= count) return fail(h, MSK144_EINVAL, "bad argument: position must be below n of the last push");
-    std::memcpy(out, sp.out[sp.last_slot] + energies_at(count) + sizeof(int32_t) * msk144sp::kMaxBlocks * static_cast<size_t>(j), sizeof(int32_t) * msk144sp::kMaxBlocks);
+    std::memcpy(out, sp.out[sp.last_slot] + StreamPings::energies_at(count) + sizeof(int32_t) * msk144sp::kMaxBlocks * static_cast<size_t>(j), sizeof(int32_t) * msk144sp::kMaxBlocks);
     *nb = reinterpret_cast<const msk144wb::PingRecord*>(sp.out[sp.last_slot])[j].blocks;
     return MSK144_OK;
 }
@@ -126,8 +121,8 @@ int msk144_stream_pings_slot(msk144_handle* h, int32_t slot, const msk144_wideba
     const int count = sp.slot_n[slot];
     if(count == 0) return fail(h, MSK144_ESTATE, "msk144_stream_pings_slot before a push on this slot since msk144_set_stream_pings");
     *records = reinterpret_cast<const msk144_wideband_ping*>(sp.out[slot]);
-    *levels = reinterpret_cast<const msk144_stream_level*>(sp.out[slot] + levels_at(count));
-    *energies = reinterpret_cast<const int32_t*>(sp.out[slot] + energies_at(count));
+    *levels = reinterpret_cast<const msk144_stream_level*>(sp.out[slot] + StreamPings::levels_at(count));
+    *energies = reinterpret_cast<const int32_t*>(sp.out[slot] + StreamPings::energies_at(count));
     *n = count;
     return MSK144_OK;
 }

@@ -417,6 +417,7 @@ int wb_gate_gather(msk144_handle* h)
     auto& g = h->wb.gate;
     h->gated = g.on;
     if(!g.on) return MSK144_OK;
+    h->gate_of = {g.header, g.planned, g.d_analytic};
     ev_begin(h);
     launch_gate_gather(h->st.analytic, g.d_header, g.d_list, h->wb.channels, g.d_analytic, h->stream);
     ev_end(h, MSK144_T_FRONTEND);

@@ -123,6 +123,11 @@ class StreamPingsParams(C.Structure):
     _fields_ = [("ratio_q4", C.c_int32), ("memory", C.c_int32), ("min_ref", C.c_int32), ("shift", C.c_int32)]
 
 
+class StreamGateParams(C.Structure):
+    """msk144_stream_gate_params."""
+    _fields_ = [("hold", C.c_int32), ("min_up", C.c_int32), ("max_streams", C.c_int32), ("ratio_q4", C.c_int32)]
+
+
 class Params(C.Structure):
     _fields_ = [("center_hz", C.c_float), ("width_hz", C.c_float), ("step_hz", C.c_float), ("scan_depth", C.c_int32),
                 ("nbadsync_threshold", C.c_int32), ("read_mode", C.c_int32), ("analytic_method", C.c_int32), ("channels", C.c_int32),
@@ -213,6 +218,9 @@ PROTOTYPES = {
     "msk144_stream_pings": ([_vp, _P(WidebandPing), _vp, _P(_i32)], C.c_int),
     "msk144_stream_ping_blocks": ([_vp, _i32, _P(_i32), _P(_i32)], C.c_int),
     "msk144_stream_pings_slot": ([_vp, _i32, _P(_vp), _P(_vp), _P(_vp), _P(_i32)], C.c_int),
+    "msk144_set_stream_gate": ([_vp, _P(StreamGateParams), _P(C.c_uint8)], C.c_int),
+    "msk144_stream_gate": ([_vp, _P(_i32), _P(_i32), _P(_i32)], C.c_int),
+    "msk144_stream_gate_slot": ([_vp, _i32, _P(_vp), _P(_i32), _P(_i32)], C.c_int),
 }
 ABI_SYMBOLS = tuple(PROTOTYPES)
 
@@ -533,6 +541,41 @@ class HipDecoder:
         lev = np.frombuffer((C.c_uint8 * (k * STREAM_LEVEL_DTYPE.itemsize)).from_address(l.value), dtype=STREAM_LEVEL_DTYPE).copy()
         en = np.frombuffer((C.c_int32 * (k * PING_MAX_BLOCKS)).from_address(e.value), dtype=np.int32).reshape(k, PING_MAX_BLOCKS).copy()
         return rec, lev, en
+
+    # ---- the stream gate: only the streams with activity are decoded (read_mode 1 handles) ----
+    def set_stream_gate(self, hold=1, min_up=1, max_streams=None, ratio_q4=0, always=()):
+        """The stream gate from the next push_hops / push_rate_hops on (include/msk144hip.h "Stream gate"): a listed stream's window
+        is decoded while the stream had a hop with at least `min_up` up blocks within its last `hold` hops, or is one of the `always`
+        streams (stream numbers); at most `max_streams` per push (None: all); ratio_q4 0 takes the stream-ping records' up masks,
+        another value the gate's own ratio on their energies.  set_stream_gate(None) switches it off.  Either ends the last push's
+        list: stream_gate() raises (MSK144_ESTATE) until the next gated push.  Records of a gated decode carry list indices as
+        channel."""
+        if hold is None:
+            self._chk(self.L.msk144_set_stream_gate(self.h, None, None))
+            return
+        flags = np.zeros(self.channels, dtype=np.uint8)
+        for s in always:
+            if not 0 <= int(s) < self.channels:
+                raise ValueError(f"always stream {s} is out of range")
+            flags[int(s)] = 1
+        p = StreamGateParams(int(hold), int(min_up), 0 if max_streams is None else int(max_streams), int(ratio_q4))
+        self._chk(self.L.msk144_set_stream_gate(self.h, C.byref(p), flags.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def stream_gate(self):
+        """(positions, total) of the last push: the int32 positions j whose window it decodes, ascending - index i of the list is
+        what the decode's records carry as channel - and the number that qualified, of which total - len(positions) were dropped.
+        Waits for the gate's event only."""
+        out = np.zeros(self.channels, dtype=np.int32)
+        count, total = C.c_int32(), C.c_int32()
+        self._chk(self.L.msk144_stream_gate(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(count), C.byref(total)))
+        return out[:count.value].copy(), total.value
+
+    def stream_gate_slot(self, slot: int):
+        """The same for the slot's last push, without a wait: valid once fetch_wait(slot) of that hop has returned."""
+        p, count, total = C.c_void_p(), C.c_int32(), C.c_int32()
+        self._chk(self.L.msk144_stream_gate_slot(self.h, slot, C.byref(p), C.byref(count), C.byref(total)))
+        k = count.value
+        return (np.frombuffer((C.c_int32 * k).from_address(p.value), dtype=np.int32).copy() if k else np.zeros(0, dtype=np.int32)), total.value
 
     # ---- wideband channeliser (read_mode 2 handles) ----
     def set_wideband(self, rate_hz: int, offsets_hz, fmt: str = "cu8", taps=None, taps_per_phase: int = 16, gain: float = 100.0, bank_taps=None):

@@ -1,10 +1,12 @@
 // C entry points of the GPU-independent host logic, for the CPU test-suite (libmsk144host.so).
+#include "stream_gate_cli.h"
 #include "stream_pings_cli.h"
 #include "wideband_cli.h"
 #include "window_decoder.h"
 
 #include "../csrc/input_rate.h"
 #include "../csrc/msk144_tables.h"
+#include "../csrc/stream_gate.h"
 #include "../csrc/stream_pings.h"
 #include "../csrc/wideband.h"
 
@@ -687,6 +689,50 @@ int msk144host_stream_pings_parse(const char* arg, int32_t* out5)
     if(!parse_stream_pings(arg, file, p, min_blocks)) return -1;
     out5[0] = p.ratio_q4, out5[1] = min_blocks, out5[2] = p.memory, out5[3] = p.shift, out5[4] = static_cast<int32_t>(file.size());
     return 0;
+}
+
+// ---- the stream gate (csrc/stream_gate.h: what msk144_set_stream_gate checks and the plan kernel computes) ----
+// p = {hold, min_up, max_streams, ratio_q4}: 0 when msk144_set_stream_gate takes them on a handle of `streams` streams, else -1 with
+// the refusal text in why
+int msk144host_stream_gate_check(int streams, const int32_t* p, char* why, int why_len)
+{
+    return copy_why(msk144sg::check_params(msk144sg::Params{p[0], p[1], p[2], p[3]}, streams), why, why_len);
+}
+// the gate of `streams` streams with their `since` and seen-bits; always[streams] or NULL (NULL back for parameters the library refuses) ...
+void* msk144host_stream_gate_new(int streams, const int32_t* p, const uint8_t* always)
+{
+    const msk144sg::Params pp{p[0], p[1], p[2], p[3]};
+    if(streams < 1 || !msk144sg::check_params(pp, streams).empty()) return nullptr;
+    return new msk144sg::Model(streams, pp, always);
+}
+void msk144host_stream_gate_free(void* m) { delete static_cast<msk144sg::Model*>(m); }
+// ... and one push of n listed positions: ids[n] ascending, is_first[n], the detector's records[n] and energies[n][54], or both NULL
+// (the detector is off).  list[n] gets the listed positions; returns the total, or -1 for ids the model does not take.  since_out
+// (or NULL): since[streams] behind the push
+int msk144host_stream_gate_push(void* m, int n, const int32_t* ids, const uint8_t* is_first, const msk144wb::PingRecord* records, const int32_t* energies, int32_t* list,
+                                int32_t* count, int32_t* since_out)
+{
+    msk144sg::Model* pm = static_cast<msk144sg::Model*>(m);
+    if(!pm || n < 0 || n > pm->streams() || (records == nullptr) != (energies == nullptr)) return -1;
+    for(int j = 0; j < n; j++)
+        if(ids[j] < 0 || ids[j] >= pm->streams() || (j > 0 && ids[j] <= ids[j - 1])) return -1;
+    std::vector<int32_t> out;
+    const int32_t total = pm->push(n, ids, is_first, records, energies, out);
+    std::copy(out.begin(), out.end(), list);
+    *count = static_cast<int32_t>(out.size());
+    for(int s = 0; since_out && s < pm->streams(); s++) since_out[s] = pm->since(s);
+    return total;
+}
+// "[HOLD[:MIN_UP[:MAX[:RATIO[:ALWAYS]]]]]" as the program parses it: the number of ALWAYS streams (into always, at most cap of
+// them) and out4 = {hold, min_up, max_streams, ratio_q4}, else -1
+int msk144host_stream_gate_parse(const char* arg, int32_t* out4, int32_t* always, int cap)
+{
+    msk144sg::Params p;
+    std::vector<int32_t> a;
+    if(!parse_stream_gate(arg, p, a)) return -1;
+    out4[0] = p.hold, out4[1] = p.min_up, out4[2] = p.max_streams, out4[3] = p.ratio_q4;
+    for(size_t i = 0; i < a.size() && i < static_cast<size_t>(cap); i++) always[i] = a[i];
+    return static_cast<int>(a.size());
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // submits hop n+1 while the GPU decodes hop n and a second thread turns the records of hop n-1 into text.  --devices=0,1,... runs
 // one such loop per GPU, each on its contiguous share of the streams (the reference binds to one device, main.cu:115).
 #include "input_rate_cli.h"
+#include "stream_gate_cli.h"
 #include "stream_pings_cli.h"
 #include "stream_loop.h"
 #include "wideband_run.h"
@@ -88,6 +89,7 @@ void show_help(const char* prog)
     std::cout << "                   --input-rate=HZ|wav         With --read-mode=1: every audio stream (stdin, --inputs, --inputs-file, --interleaved) arrives at HZ samples per second and is resampled to 12000 on the GPU, in exact integers, ahead of the decoder. HZ is a multiple of 125 from 24000 to 192000 (e.g. 48000; the 44.1 kHz family is not supported): HZ = 12000 x P/Q, a hop is then 2592 x P/Q samples per stream and the first one 5184 x P/Q. 12000 is the program without the option. The filter is the channel filter's design, K x P integer taps with K = --taps-per-phase; it delays the signal by 0.67 ms at K = 16. 'wav', for the single stdin stream together with --skip-wav-header, takes HZ from the 44-byte header (PCM, one channel, 16 bits). At the end, on stderr, one line with the rate, P/Q, the taps, the shift and the samples clamped." << std::endl;
     std::cout << "                   --stream-pings=FILE[:RATIO[:MIN_BLOCKS[:MEMORY[:SHIFT]]]]  With --read-mode=1 (stdin, --inputs, --inputs-file, --interleaved, --devices, --input-rate): a ping detector on every audio stream, on the GPU, on the 12 kHz samples the decoder gets. Each hop is cut into blocks of 96 samples (8 ms) with energy E = min(2^22-1, sum of squares >> SHIFT) (0..24, default=12: audio of 30 to about 13000 LSB rms stays in range); a block is up when E exceeds RATIO (1..4095.9, default=3.5) x the stream's quiet level, the lowest lower-quartile E of this hop and the MEMORY (0..16, default=8) before it. A run of at least MIN_BLOCKS (1..64, default=2) up blocks is an event; when it closes one line is appended to FILE: ping ch=<stream> start=<s> dur=<s> blocks=<n> peak=<E> ref=<R> peak_db=<dB>, start counted from the stream's first sample. An empty field keeps its default. At the end, on stderr, one line with the events, the streams that had any, the blocks up and the three most active streams. A strong-ping detector, less sensitive than the decoder; the default RATIO comes from a CPU simulation on noise. Stdout is unchanged." << std::endl;
     std::cout << "                   --stream-levels             With --read-mode=1: at the end, on stderr, one line per stream - rms in LSB over the run, peak, full-scale samples, hops and all-zero hops, of the 12 kHz samples the decoder gets (behind the resampler with --input-rate) - and one line with the three streams with the most full-scale samples, the three quietest and every stream whose hops were all zero. Stdout is unchanged." << std::endl;
+    std::cout << "                   --stream-gate[=HOLD[:MIN_UP[:MAX[:RATIO[:ALWAYS]]]]]  With --read-mode=1 (stdin, --inputs, --inputs-file, --interleaved, --devices, --input-rate): decode only the streams with activity, picked on the GPU from the blocks of the --stream-pings detector (without --stream-pings the detector runs with its defaults and writes no log). A hop of a stream is active when at least MIN_UP (1..27, default=1) of its 27 blocks are up; the stream's window is decoded in that hop and for HOLD more hops (0..16, default=1; with HOLD >= 1 every window that contains an active hop is decoded). At most MAX stream windows are decoded per hop and device (default and 0: all); more are dropped in ascending stream order and counted. RATIO (1..4095.9; empty or 0: the detector's own blocks) gives the gate a threshold of its own on the detector's energies and quiet level, so that the log keeps a strict ratio while the gate triggers on a looser one. In a CPU simulation against the reference decoder's model (three-frame pings in 300..2700 Hz noise; nothing run on the air) the default lost no decode from +2 dB up, a quarter at 0 dB and nearly all below, and listed no noise window; RATIO 2.5 kept 98.7 % of the decodes and listed 4.6 % of the noise windows; 2.0 and below kept all and listed most noise windows. ALWAYS is a list of stream numbers s0,s1,... that are decoded on every hop. An empty field keeps its default. snr= of every stream stays that of a run without the gate; stdout carries the lines of the decoded windows. The detector is less sensitive than the decoder: a ping it does not see is not decoded. At the end, on stderr, one line with the stream windows decoded of those pushed, the dropped ones and the busiest hop." << std::endl;
     // clang-format on
 }
 
@@ -164,7 +166,8 @@ int main(int argc, char* const argv[])
     WidebandOptions wbo;
     InputRate input_rate;
     StreamStats stream_stats;
-    std::string input_rate_error, taps_per_phase_arg, stream_stats_error;
+    StreamGate stream_gate;
+    std::string input_rate_error, taps_per_phase_arg, stream_stats_error, stream_gate_error;
     int wideband_options = 0, taps_per_phase_options = 0;  // how many options went to take_wideband_option, and how many of them were --taps-per-phase
 
     static struct option long_options[] = {{"help", no_argument, 0, 0},
@@ -208,6 +211,7 @@ int main(int argc, char* const argv[])
                                            {"input-rate", required_argument, 0, 0},
                                            {"stream-pings", required_argument, 0, 0},
                                            {"stream-levels", no_argument, 0, 0},
+                                           {"stream-gate", optional_argument, 0, 0},
                                            {0, 0, 0, 0}};
     while(true)
     {
@@ -230,6 +234,12 @@ int main(int argc, char* const argv[])
         if(!strcmp(long_options[idx].name, "stream-levels"))
         {
             stream_stats.levels = true;
+            continue;
+        }
+        if(!strcmp(long_options[idx].name, "stream-gate"))
+        {
+            const std::string why = stream_gate.parse(optarg);
+            if(!why.empty() && stream_gate_error.empty()) stream_gate_error = why;
             continue;
         }
         if(!strcmp(long_options[idx].name, "taps-per-phase"))
@@ -359,6 +369,20 @@ int main(int argc, char* const argv[])
         }
     }
 
+    // --stream-gate: the same
+    if(stream_gate.on)
+    {
+        std::string why = stream_gate_error;
+        if(!why.empty()) ;  // the option's own value was bad
+        else if(wideband) why = "--stream-gate gates the audio streams' windows: it excludes --wideband-rate (whose channels have --wideband-gate)";
+        else if(opt.read_mode != 1) why = "--stream-gate reads the pings of 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
+        if(!why.empty())
+        {
+            std::cerr << why << std::endl;
+            return 2;
+        }
+    }
+
     if(!center_set)
     {
         if(opt.read_mode == 1) opt.center_hz = 1500.0f;
@@ -393,6 +417,17 @@ int main(int argc, char* const argv[])
     {
         std::cerr << why << std::endl;
         return 2;
+    }
+    // --stream-gate: MAX and ALWAYS against the streams of the run, and the entries resolved
+    if(stream_gate.on)
+    {
+        std::string why = stream_gate.check(nch);
+        if(why.empty()) stream_gate.api.resolve(why);
+        if(!why.empty())
+        {
+            std::cerr << why << std::endl;
+            return 2;
+        }
     }
     {
         // one descriptor per stream plus what the runtime opens: lift the soft limit when the hard limit allows
@@ -501,6 +536,16 @@ int main(int argc, char* const argv[])
         }
         dec.use_stream_stats(&stream_stats, 0);
     }
+    if(stream_gate.on)
+    {
+        std::string why;
+        if(!stream_gate.configure(dec.handle(), shares[0].first, shares[0].count, stream_stats.on(), why))
+        {
+            std::cerr << "msk144hip: " << why << std::endl;
+            return 2;
+        }
+        dec.use_stream_gate(&stream_gate);
+    }
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
@@ -518,7 +563,7 @@ int main(int argc, char* const argv[])
             unsigned char hdr[44];
             if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) std::cerr << "Incomplete read error. rc=0" << std::endl;
         }
-        if(input_rate.on || stream_stats.on())
+        if(input_rate.on || stream_stats.on() || stream_gate.on)
         {
             // the same loop over the library's hop ring (msk144_push_rate_hops at the input rate, msk144_push_hops for the levels and
             // pings of a 12 kHz stream, which a whole-window submit does not produce): a hop carries its new samples only
@@ -562,6 +607,7 @@ int main(int argc, char* const argv[])
             if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
             stream_stats.finish();
             for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
+            if(stream_gate.on) std::cerr << stream_gate.summary() << std::endl;
             std::cout << "Done" << std::endl;
             return 0;
         }
@@ -639,6 +685,16 @@ int main(int argc, char* const argv[])
                 return 2;
             }
             loops[i]->decoder().use_stream_stats(&stream_stats, shares[i].first);
+        }
+        if(stream_gate.on)
+        {
+            std::string why;
+            if(i > 0 && !stream_gate.configure(loops[i]->decoder().handle(), shares[i].first, shares[i].count, stream_stats.on(), why))
+            {
+                std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
+                return 2;
+            }
+            loops[i]->decoder().use_stream_gate(&stream_gate);
         }
         if(wideband) loops[i]->use_wideband(&wideband_run);
         else if(interleaved > 0) loops[i]->use_feed();
@@ -740,6 +796,7 @@ int main(int argc, char* const argv[])
     if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
     stream_stats.finish();
     for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
+    if(stream_gate.on) std::cerr << stream_gate.summary() << std::endl;
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {

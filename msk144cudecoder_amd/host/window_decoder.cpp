@@ -1,6 +1,7 @@
 #include "window_decoder.h"
 
 #include "input_rate_cli.h"
+#include "stream_gate_cli.h"
 #include "stream_pings_cli.h"
 
 #include <chrono>
@@ -216,18 +217,25 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
     }
     // ... and, with --stream-pings or --stream-levels, the records and levels of its push
     if(stats_ && hops_[slot] && !stats_->take(handle_, slot, stats_base_, streams_[slot], error_)) return false;
+    // ... and, with --stream-gate, the positions its decode covered
+    const bool sgated = sgate_ && hops_[slot];
+    const int32_t* listed_at = nullptr;
+    int32_t listed_n = 0;
+    if(sgated && !sgate_->take(handle_, slot, static_cast<int>(streams_[slot].size()), listed_at, listed_n, error_)) return false;
     const auto t1 = Clock::now();
     const std::vector<int>& streams = streams_[slot];
     const size_t n_results = static_cast<size_t>(n);
 
     // results arrive ordered by (position in the slot, item): walk them position by position
     // A gated wideband push: every stream takes part - its segment powers come by stream - and has records only where the gate
-    // listed it, at position j of the list; the others are post-processed with no candidates, as a window that decoded nothing
+    // listed it, at position j of the list; the others are post-processed with no candidates, as a window that decoded nothing.
+    // A gated push of stream hops: the same over the hop's positions u, stream streams[u], listed where the gate's list names u.
+    // Without a gate every position is listed and j = u
     const bool gated = gated_[slot];
     size_t r = 0, j = 0;
     for(size_t u = 0; u < (gated ? static_cast<size_t>(nch) : streams.size()); u++)
     {
-        const bool listed = !gated || (j < streams.size() && streams[j] == static_cast<int>(u));
+        const bool listed = gated ? j < streams.size() && streams[j] == static_cast<int>(u) : !sgated || (j < static_cast<size_t>(listed_n) && listed_at[j] == static_cast<int32_t>(u));
         const int c = gated ? static_cast<int>(u) : streams[u];
         std::vector<AcceptedCandidate> accepted;
         for(; listed && r < n_results && results[r].channel == static_cast<int32_t>(j); r++)
@@ -241,7 +249,7 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
             unpack_bits(res.message, a.bits);
             accepted.push_back(a);
         }
-        snr_[c].update(&seg[(gated ? u : j) * 8]);  // main.cu:388
+        snr_[c].update(&seg[u * 8]);  // main.cu:388
         if(listed) j++;
         lines[c] = postprocess_window(accepted, snr_[c].snr_int(), opt_.reference_cache_quirk, calls_[c], filter_[c]);
         if(opt_.print_bits)

@@ -17,6 +17,7 @@ namespace msk144host
 
 struct InputRate;
 struct StreamStats;
+struct StreamGate;
 
 struct DecoderOptions
 {
@@ -127,6 +128,10 @@ public:
         stats_ = stats;
         stats_base_ = base;
     }
+    // --stream-gate (stream_gate_cli.h; `gate` has configured handle()): the decode of a submit_hops() push covers the positions of
+    // the gate's list.  collect() takes the list behind msk144_fetch_wait (msk144_stream_gate_slot: no wait of its own) and gives
+    // every stream of the hop its SNR update and its post-processing, the streams that were not listed with no candidates
+    void use_stream_gate(StreamGate* gate) { sgate_ = gate; }
     // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
     // it at run time): every stream, in order.  `gate` (msk144_wideband_gate, with --wideband-gate): the decode covers the channels
     // of the gate's list, which is taken behind it; collect() then gives every stream its SNR update and its post-processing, the
@@ -158,6 +163,7 @@ private:
     InputRate* ir_ = nullptr;
     StreamStats* stats_ = nullptr;
     int stats_base_ = 0;
+    StreamGate* sgate_ = nullptr;
     bool hops_[kSlots] = {};            // the slot's hop came through submit_hops()
 };
 

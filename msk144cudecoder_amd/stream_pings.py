@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from .wideband import PING_BLOCK, PING_DTYPE, PING_MAX_BLOCKS, PING_MIN_BLOCKS, PingEvents, Pings
+from .wideband import GATE_MAX_HOLD, HOP_BLOCKS, PING_BLOCK, PING_DTYPE, PING_MAX_BLOCKS, PING_MIN_BLOCKS, SINCE_QUIET, PingEvents, Pings, since_next
 
 HOP_SAMPLES = 2592
 FIRST_SAMPLES = 5184
@@ -174,6 +174,72 @@ class StreamReport:
         return out + [line]
 
 
+# ---- the stream gate: only the streams with activity are decoded (msk144_set_stream_gate; csrc/stream_gate.h) ----
+
+def stream_gate_check(streams: int, hold: int = 1, min_up: int = 1, max_streams: int = 0, ratio_q4: int = 0) -> str:
+    """'' when msk144_set_stream_gate takes the parameters on a handle of `streams` streams, else why not."""
+    if not 0 <= int(hold) <= GATE_MAX_HOLD:
+        return "hold must lie within 0..16 hops"
+    if not 1 <= int(min_up) <= HOP_BLOCKS:
+        return "min_up must lie within 1..27 blocks"
+    if not 0 <= int(max_streams) <= int(streams):
+        return "max_streams must lie within 1..streams, or be 0 for all"
+    if int(ratio_q4) != 0 and not 16 <= int(ratio_q4) <= 65535:
+        return "ratio_q4 must be 0 or lie within 16..65535"
+    return ""
+
+
+class StreamGate:
+    """The stream gate rule of the contract (include/msk144hip.h "Stream gate") in Python integers, push by push.  Per STREAM
+    `since`, the hops since its last active one, saturating at SINCE_QUIET; a stream's first listed hop since the gate was made, and
+    every is_first hop, start from SINCE_QUIET; streams a push does not list keep theirs.  push() is fed what StreamPings.push
+    returns for the same hops and gives (positions int32, total): the listed POSITIONS j, ascending, at most max_streams of them,
+    and the number that qualified.  A new StreamGate stands for msk144_set_stream_gate."""
+
+    def __init__(self, streams: int, hold: int = 1, min_up: int = 1, max_streams=None, ratio_q4: int = 0, always=()):
+        streams = int(streams)
+        max_streams = 0 if not max_streams else int(max_streams)
+        why = stream_gate_check(streams, hold, min_up, max_streams, ratio_q4)
+        if why:
+            raise ValueError(why)
+        always = [int(s) for s in always]
+        if any(not 0 <= s < streams for s in always):
+            raise ValueError("an always stream is out of range")
+        self.streams, self.hold, self.min_up, self.ratio_q4 = streams, int(hold), int(min_up), int(ratio_q4)
+        self.max_streams = max_streams or streams
+        self.always = frozenset(always)
+        self.since = [SINCE_QUIET] * streams
+        self.seen = [False] * streams
+
+    def mask(self, record, energies) -> int:
+        """The up mask of one position: the record's, or with a ratio of the gate's own bit b < blocks set iff
+        E[b] x 16 > reference x ratio_q4."""
+        if self.ratio_q4 == 0:
+            return int(record["up_mask"])
+        R = int(record["reference"])
+        return sum(1 << b for b in range(int(record["blocks"])) if int(energies[b]) * 16 > R * self.ratio_q4)
+
+    def push(self, ids, is_first, records=None, energies=None):
+        """ids: ascending stream numbers; is_first[j]; records PING_DTYPE [n] and energies [n][54] of the detector for this push, or
+        None: the detector is off, every mask is 0."""
+        ids = [int(s) for s in ids]
+        if any(not 0 <= s < self.streams for s in ids) or any(b <= a for a, b in zip(ids, ids[1:])):
+            raise ValueError("streams must be ascending stream numbers below the stream count")
+        hop = (1 << HOP_BLOCKS) - 1
+        chosen = []
+        for j, s in enumerate(ids):
+            first = bool(is_first[j])
+            m = 0 if records is None else self.mask(records[j], energies[j])
+            since = SINCE_QUIET if first or not self.seen[s] else self.since[s]
+            self.seen[s] = True
+            for bits in ([m & hop, (m >> HOP_BLOCKS) & hop] if first else [m & hop]):
+                since = since_next(since, bin(bits).count("1") >= self.min_up)
+            self.since[s] = since
+            if s in self.always or since <= self.hold:
+                chosen.append(j)
+        return np.array(chosen[:self.max_streams], dtype=np.int32), len(chosen)
+
+
 # ---- the same contract as libmsk144host.so holds it (csrc/stream_pings.h), for the CPU tests ----
 
 def _host():
@@ -255,3 +321,68 @@ class HostStreamPings:
             if self.L.msk144host_stream_pings_push(self.m, int(s), 1 if is_first[j] else 0, x.ctypes.data, records[j:j + 1].ctypes.data, lev[j:j + 1].ctypes.data, energies[j].ctypes.data) != 0:
                 raise ValueError(f"no stream {s}")
         return records, lev, energies
+
+
+def host_gate_check(streams: int, hold: int = 1, min_up: int = 1, max_streams: int = 0, ratio_q4: int = 0) -> str:
+    """'' when msk144_set_stream_gate takes the parameters (csrc/stream_gate.h check_params), else its refusal."""
+    import ctypes as C
+    L = _host()
+    L.msk144host_stream_gate_check.argtypes = [C.c_int, C.c_void_p, C.c_char_p, C.c_int]
+    why = C.create_string_buffer(256)
+    L.msk144host_stream_gate_check(int(streams), np.array([hold, min_up, max_streams, ratio_q4], dtype=np.int32).ctypes.data, why, len(why))
+    return why.value.decode()
+
+
+def host_gate_parse(arg: str):
+    """"[HOLD[:MIN_UP[:MAX[:RATIO[:ALWAYS]]]]]" as the program parses it: dict(hold, min_up, max_streams, ratio_q4, always), or None."""
+    import ctypes as C
+    L = _host()
+    L.msk144host_stream_gate_parse.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int]
+    out, always = np.zeros(4, dtype=np.int32), np.zeros(4096, dtype=np.int32)
+    n = L.msk144host_stream_gate_parse(arg.encode(), out.ctypes.data, always.ctypes.data, len(always))
+    if n < 0:
+        return None
+    return dict(zip(("hold", "min_up", "max_streams", "ratio_q4"), (int(v) for v in out)), always=[int(v) for v in always[:n]])
+
+
+class HostStreamGate:
+    """msk144sg::Model of libmsk144host.so: push(ids, is_first, records, energies) -> (positions, total) as StreamGate.push; `since`
+    is the model's state behind the last push."""
+
+    def __init__(self, streams: int, hold: int = 1, min_up: int = 1, max_streams=None, ratio_q4: int = 0, always=()):
+        import ctypes as C
+        self.L = _host()
+        self.L.msk144host_stream_gate_new.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        self.L.msk144host_stream_gate_new.restype = C.c_void_p
+        self.L.msk144host_stream_gate_free.argtypes = [C.c_void_p]
+        self.L.msk144host_stream_gate_push.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        self.streams = int(streams)
+        flags = np.zeros(max(self.streams, 1), dtype=np.uint8)
+        if any(not 0 <= int(s) < self.streams for s in always):
+            raise ValueError("an always stream is out of range")
+        for s in always:
+            flags[int(s)] = 1
+        p = np.array([hold, min_up, max_streams or 0, ratio_q4], dtype=np.int32)
+        self.m = self.L.msk144host_stream_gate_new(self.streams, p.ctypes.data, flags.ctypes.data)
+        if not self.m:
+            raise ValueError("the host library refuses these parameters")
+        self.since = [SINCE_QUIET] * self.streams
+
+    def __del__(self):
+        if getattr(self, "m", None):
+            self.L.msk144host_stream_gate_free(self.m)
+            self.m = None
+
+    def push(self, ids, is_first, records=None, energies=None):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        first = np.ascontiguousarray([1 if f else 0 for f in is_first], dtype=np.uint8)
+        n = len(ids)
+        rec = None if records is None else np.ascontiguousarray(records, dtype=PING_DTYPE)
+        en = None if records is None else np.ascontiguousarray(energies, dtype=np.int32).reshape(n, PING_MAX_BLOCKS)
+        out, count, since = np.zeros(max(n, 1), dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(self.streams, dtype=np.int32)
+        total = self.L.msk144host_stream_gate_push(self.m, n, ids.ctypes.data, first.ctypes.data, None if rec is None else rec.ctypes.data, None if en is None else en.ctypes.data,
+                                                    out.ctypes.data, count.ctypes.data, since.ctypes.data)
+        if total < 0:
+            raise ValueError("streams must be ascending stream numbers below the stream count")
+        self.since = [int(v) for v in since]
+        return out[:int(count[0])].copy(), int(total)
