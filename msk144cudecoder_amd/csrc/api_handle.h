@@ -1,7 +1,8 @@
 // The handle behind the C ABI of libmsk144hip.so, and what its host files share: msk144_api.cpp (handle lifetime, the narrowband
-// entries, the decode), msk144_wideband_api.cpp (every msk144_*wideband* entry), msk144_input_rate_api.cpp (the resampler in front
-// of the hop ring), msk144_stream_pings_api.cpp (levels and pings of the audio hops) and msk144_stream_gate_api.cpp (the gate on
-// those pings).  Host code only: nothing here launches a kernel.
+// entries, the decode, and push_stream_hops, the one push behind msk144_push_hops and msk144_push_rate_hops),
+// msk144_wideband_api.cpp (every msk144_*wideband* entry), msk144_input_rate_api.cpp (the resampler in front of the hop ring),
+// msk144_stream_pings_api.cpp (levels and pings of the audio hops) and msk144_stream_gate_api.cpp (the gate on those pings); the
+// last three each give the push one step.  Host code only: nothing here launches a kernel.
 #pragma once
 
 #include "../../include/msk144hip.h"
@@ -238,6 +239,28 @@ struct InputRate
     int slot_n[MSK144_SLOTS] = {};             // n of that push; 0: none
 };
 
+// "The first listing since `set`": a stream's state on the device restarts at the first push that lists it after the option's
+// `set`.  stage() fills the slot's pinned row, which the push copies to d_restart ahead of its kernel; commit() marks the streams
+// seen, once the push's work has been enqueued - only a push that went out uses up a stream's restart.  The buffers are the
+// option's `set` to allocate.
+struct SinceSet
+{
+    std::vector<uint8_t> seen;             // [channels] the stream has been listed since `set`
+    uint8_t* restart[MSK144_SLOTS] = {};   // pinned [channels] by position
+    uint8_t* d_restart = nullptr;          // [channels] by position
+
+    void reset(size_t channels) { seen.assign(channels, 0); }
+    void stage(int32_t slot, const int32_t* streams, int32_t n)
+    {
+        uint8_t* row = restart[slot];
+        for(int32_t j = 0; j < n; j++) row[j] = seen[static_cast<size_t>(streams[j])] ? 0 : 1;
+    }
+    void commit(const int32_t* streams, int32_t n)
+    {
+        for(int32_t j = 0; j < n; j++) seen[static_cast<size_t>(streams[j])] = 1;
+    }
+};
+
 // Per-stream levels and pings on the audio hops (msk144_set_stream_pings): one block, value-initialised is "off".  Everything is
 // allocated by the first `set` that switches it on, registered with the handle's own owner, and kept until the handle goes; a push
 // allocates nothing.  The device results of a push are one block - records [n], levels [n], energies [n][54] - so that one copy takes
@@ -247,13 +270,11 @@ struct StreamPings
     bool on = false;              // what the next push does
     bool pushed = false;          // a push has left results since `set`: what the read entries test
     msk144sp::Params params;
-    std::vector<uint8_t> seen;    // [channels] the stream has been listed since `set`
+    SinceSet since;               // which positions of a push restart their stream's history
     int last_slot = 0;            // the slot of the last push, ...
     int slot_n[MSK144_SLOTS] = {};  // ... n of each slot's last push since `set`; 0: none
     msk144wb::PingHistory* d_state = nullptr;  // [channels] by stream
-    uint8_t* d_restart = nullptr;              // [channels] by position
     uint8_t* d_out = nullptr;                  // the results of the last push: channels x (32 + 32 + 54 x 4) bytes
-    uint8_t* restart[MSK144_SLOTS] = {};       // pinned [channels]
     uint8_t* out[MSK144_SLOTS] = {};           // pinned, as d_out
 
     // the one layout of d_out and out[] for a push of n positions - records [n], levels [n], energies [n][54] - in bytes from the
@@ -274,17 +295,15 @@ struct StreamGate
     msk144sg::Params params;
     int rows = 0;                 // rows of d_analytic
     long long pushes = 0;         // gated pushes since `set`
-    std::vector<uint8_t> seen;    // [channels] the stream has been listed since `set`
+    SinceSet since;               // which positions of a push restart their stream's count
     int last_slot = 0;            // the slot of the last push, ...
     bool slot_pushed[MSK144_SLOTS] = {};  // ... and whether each slot has had one since `set`
     uint8_t* d_always = nullptr;                // [channels] by stream
     int32_t* d_since = nullptr;                 // [channels] by stream
-    uint8_t* d_restart = nullptr;               // [channels] by position
     unsigned long long* d_masks = nullptr;      // [channels] by position: the gate's own masks (ratio_q4 != 0)
     msk144wb::PlanHeader* d_header = nullptr;   // [1]
     int32_t* d_list = nullptr;                  // [channels]
     float2* d_analytic = nullptr;               // [rows][5184]: row i is the window of position list[i]
-    uint8_t* restart[MSK144_SLOTS] = {};                // pinned [channels]
     msk144wb::PlanHeader* header[MSK144_SLOTS] = {};    // pinned: the header, and behind it the list, int32 [channels]
     hipEvent_t planned[MSK144_SLOTS] = {};
 };
@@ -395,15 +414,25 @@ int ensure_ring(msk144_handle* h);
 int check_hop_slot(msk144_handle* h, int32_t slot);
 int begin_hop(msk144_handle* h, int32_t slot, int32_t n);
 int run_frontend(msk144_handle* h, const void* d_in);
+// msk144_push_hops (rate = false) and msk144_push_rate_hops (rate = true): the checks, the staging copies, then the steps below
+// and the hop ring and front end, in one order for both; `entry` is the exported name, the prefix of its messages
+int push_stream_hops(msk144_handle* h, int32_t slot, int32_t n, const char* entry, bool rate);
+// the two refusals every msk144_set_* entry of an audio-stream option shares - read_mode 2, wideband mode; `what` is the entry's own
+// clause behind the semicolon of the first
+int streams_only(msk144_handle* h, const char* entry, const char* what);
 // defined in msk144_wideband_api.cpp: back to no wideband configuration, its buffers freed, every field reset
 void wb_release(msk144_handle* h);
-// defined in msk144_stream_pings_api.cpp: the levels and pings of a push of n audio hops, on the handle's stream behind the staging
-// copy or the resampler and ahead of the hop ring.  The two push entries call it only while h->sp.on
+// The steps of push_stream_hops that the options own, each on the handle's stream, in the order it runs them.
+// defined in msk144_input_rate_api.cpp: the n staged rows at the input rate to 12 kHz halves in d_first / d_hops, and the clamp counts
+// to the slot's pinned row; behind the staging copies.  Only for the rate entry
+int ir_resample(msk144_handle* h, int32_t slot, int32_t n, bool any_first);
+// defined in msk144_stream_pings_api.cpp: the levels and pings of a push of n audio hops, behind the staging copy or the resampler
+// and ahead of the hop ring.  Only while h->sp.on
 int sp_push(msk144_handle* h, int32_t slot, int32_t n);
-// defined in msk144_stream_gate_api.cpp.  sg_plan: the gate's list of a push of n audio hops, on the handle's stream behind sp_push
-// and ahead of the hop ring, its header and list to the slot's pinned block, and the event.  sg_gather: behind run_frontend, the
-// listed positions' analytic windows into the gate's store; it makes the hop a gated one.  The two push entries call them only
-// while h->sg.on.  sg_release: the events, which no owner frees
+// defined in msk144_stream_gate_api.cpp.  sg_plan: the gate's list of a push of n audio hops, behind sp_push and ahead of the hop
+// ring, its header and list to the slot's pinned block, and the event.  sg_gather: behind run_frontend, the listed positions'
+// analytic windows into the gate's store; it makes the hop a gated one.  Only while h->sg.on.  sg_release: the events, which no
+// owner frees
 int sg_plan(msk144_handle* h, int32_t slot, int32_t n);
 int sg_gather(msk144_handle* h, int32_t n);
 void sg_release(msk144_handle* h);

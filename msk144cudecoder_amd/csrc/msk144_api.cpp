@@ -1,6 +1,8 @@
 // C ABI of libmsk144hip.so (include/msk144hip.h): handle lifetime, buffers, launch order; the msk144_*wideband* entries are in
-// msk144_wideband_api.cpp.  Host-side restatement of the reference's setup code; compiled with -ffp-contract=off so that the
-// frequency grid, the sync template and the FFT mask are computed with the reference's float ops.
+// msk144_wideband_api.cpp.  The push of audio hops is here too (push_stream_hops); the steps its options add are in
+// msk144_input_rate_api.cpp, msk144_stream_pings_api.cpp and msk144_stream_gate_api.cpp.  Host-side restatement of the reference's
+// setup code; compiled with -ffp-contract=off so that the frequency grid, the sync template and the FFT mask are computed with the
+// reference's float ops.
 #include "api_handle.h"
 
 #include "msk144_tables.h"
@@ -143,7 +145,7 @@ int submit_windows(msk144_handle* h, const void* windows, int read_mode, bool ho
 
 }  // namespace
 
-// ---- shared with msk144_wideband_api.cpp (api_handle.h) ----
+// ---- shared with the other *_api.cpp files (api_handle.h) ----
 int fail(msk144_handle* h, int code, const std::string& msg)
 {
     if(h) h->error = msg;
@@ -229,6 +231,55 @@ int begin_hop(msk144_handle* h, int32_t slot, int32_t n)
     h->active = n;
     h->gated = false;
     return MSK144_OK;
+}
+
+int streams_only(msk144_handle* h, const char* entry, const char* what)
+{
+    if(h->params.read_mode != 1) return fail(h, MSK144_EINVAL, std::string(entry) + ": the handle reads complex int8 I/Q (read_mode 2); " + what);
+    if(h->wb.configured) return fail(h, MSK144_EINVAL, std::string(entry) + ": the handle is in wideband mode");
+    return MSK144_OK;
+}
+
+// The one push of audio hops.  With `rate` the n rows of the slot are at the handle's input rate (InputRate's pinned rows, staged in
+// its d_in_*), and ir_resample makes the 12 kHz halves in d_first / d_hops of them; without, the slot's own rows are those halves.
+int push_stream_hops(msk144_handle* h, int32_t slot, int32_t n, const char* entry, bool rate)
+{
+    int rc = check_hop_slot(h, slot);
+    if(rc != MSK144_OK) return rc;
+    const InputRate& ir = h->ir;
+    if(rate && !ir.on) return fail(h, MSK144_ESTATE, std::string(entry) + " before msk144_set_input_rate");
+    if(!h->ring_ready || (rate && !ir.hops[slot])) return fail(h, MSK144_ESTATE, std::string(entry) + (rate ? " before msk144_rate_hop_slot" : " before msk144_hop_slot"));
+    if(n < 1 || n > h->st.channels) return fail(h, MSK144_EINVAL, "n must be 1..channels");
+    const msk144_handle::Slot& sl = h->slots[slot];
+    bool any_first = false;
+    for(int32_t j = 0; j < n; j++)
+    {
+        if(sl.streams[j] < 0 || sl.streams[j] >= h->st.channels || (j > 0 && sl.streams[j] <= sl.streams[j - 1]))
+            return fail(h, MSK144_EINVAL, "streams must be ascending stream numbers below channels");
+        if(rate && !sl.is_first[j] && !ir.started[static_cast<size_t>(sl.streams[j])])
+            return fail(h, MSK144_ESTATE, std::string(entry) + ": stream " + std::to_string(sl.streams[j]) + " has a later hop before a first one (is_first = 0)");
+        any_first = any_first || sl.is_first[j] != 0;
+    }
+    if((rc = begin_hop(h, slot, n)) != MSK144_OK) return rc;
+    // the sample rows: the slot's halves straight to the hop ring's staging, or the input-rate rows to the resampler's
+    const void* hops = rate ? static_cast<const void*>(ir.hops[slot]) : sl.hops;
+    const void* first_halves = rate ? static_cast<const void*>(ir.first_halves[slot]) : sl.first_halves;
+    void* d_hops = rate ? static_cast<void*>(ir.d_in_hops) : h->d_hops;
+    void* d_first = rate ? static_cast<void*>(ir.d_in_first) : h->d_first;
+    const size_t row_bytes = rate ? static_cast<size_t>(ir.shape.row) * sizeof(int16_t) : window_bytes(h) / 2;
+    ev_begin(h);
+    hipError_t e = hipMemcpyAsync(d_hops, hops, row_bytes * n, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess && any_first) e = hipMemcpyAsync(d_first, first_halves, row_bytes * n, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, n, hipMemcpyHostToDevice, h->stream);
+    ev_end(h, MSK144_T_H2D);
+    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string(entry) + ": " + hipGetErrorString(e));
+    if(rate && (rc = ir_resample(h, slot, n, any_first)) != MSK144_OK) return rc;
+    if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
+    if(h->sg.on && (rc = sg_plan(h, slot, n)) != MSK144_OK) return rc;
+    launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
+    if((rc = run_frontend(h, h->d_input)) != MSK144_OK || !h->sg.on) return rc;
+    return sg_gather(h, n);
 }
 
 extern "C" {
@@ -720,32 +771,7 @@ int msk144_hop_slot(msk144_handle* h, int32_t slot, void** hops, void** first_ha
 
 int msk144_push_hops(msk144_handle* h, int32_t slot, int32_t n)
 {
-    int rc = check_hop_slot(h, slot);
-    if(rc != MSK144_OK) return rc;
-    if(!h->ring_ready) return fail(h, MSK144_ESTATE, "msk144_push_hops before msk144_hop_slot");
-    if(n < 1 || n > h->st.channels) return fail(h, MSK144_EINVAL, "n must be 1..channels");
-    msk144_handle::Slot& sl = h->slots[slot];
-    bool any_first = false;
-    for(int32_t j = 0; j < n; j++)
-    {
-        if(sl.streams[j] < 0 || sl.streams[j] >= h->st.channels || (j > 0 && sl.streams[j] <= sl.streams[j - 1]))
-            return fail(h, MSK144_EINVAL, "streams must be ascending stream numbers below channels");
-        any_first = any_first || sl.is_first[j] != 0;
-    }
-    if((rc = begin_hop(h, slot, n)) != MSK144_OK) return rc;
-    const size_t half = window_bytes(h) / 2;
-    ev_begin(h);
-    hipError_t e = hipMemcpyAsync(h->d_hops, sl.hops, half * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess && any_first) e = hipMemcpyAsync(h->d_first, sl.first_halves, half * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, n, hipMemcpyHostToDevice, h->stream);
-    ev_end(h, MSK144_T_H2D);
-    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_hops: ") + hipGetErrorString(e));
-    if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
-    if(h->sg.on && (rc = sg_plan(h, slot, n)) != MSK144_OK) return rc;
-    launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
-    if((rc = run_frontend(h, h->d_input)) != MSK144_OK || !h->sg.on) return rc;
-    return sg_gather(h, n);
+    return push_stream_hops(h, slot, n, "msk144_push_hops", false);
 }
 
 int msk144_fetch_async(msk144_handle* h, int32_t slot)

@@ -1,6 +1,6 @@
 // The input-rate entries of the C ABI (include/msk144hip.h, "Audio input at 24 to 192 kHz"): msk144_set_input_rate,
-// msk144_rate_hop_slot, msk144_push_rate_hops and the two read entries.  Everything behind the resampler - hop ring, front end,
-// decode, fetch - is msk144_api.cpp's, reached through api_handle.h.
+// msk144_rate_hop_slot, the read entries, and ir_resample, the step the push (push_stream_hops, msk144_api.cpp) runs for
+// msk144_push_rate_hops between the staging copies and everything else - pings, gate, hop ring, front end.
 #include "api_handle.h"
 
 #include <cstring>
@@ -40,6 +40,46 @@ int ir_read_ready(msk144_handle* h, const char* entry)
 
 }  // namespace
 
+int ir_resample(msk144_handle* h, int32_t slot, int32_t n, bool any_first)
+{
+    InputRate& ir = h->ir;
+    const msk144_handle::Slot& sl = h->slots[slot];
+    ev_begin(h);
+    hipError_t e = hipMemsetAsync(ir.d_clamped, 0, sizeof(int32_t) * n, h->stream);
+    if(e == hipSuccess)
+    {
+        ResampleArgs a{};
+        a.in_first = ir.d_in_first;
+        a.in_hops = ir.d_in_hops;
+        a.streams = h->d_streams;
+        a.is_first = h->d_isfirst;
+        a.taps = ir.d_taps;
+        a.hist = ir.d_hist;
+        a.out_first = reinterpret_cast<int16_t*>(h->d_first);
+        a.out_hops = reinterpret_cast<int16_t*>(h->d_hops);
+        a.clamped = ir.d_clamped;
+        a.P = ir.shape.P;
+        a.Q = ir.shape.Q;
+        a.H = ir.shape.H;
+        a.hist_stride = ir.hist_stride;
+        a.row = ir.shape.row;
+        a.dwords = ir.shape.dwords;
+        a.shift = ir.shift;
+        launch_resample(a, n, any_first, h->stream);
+        e = hipGetLastError();
+        // the slot's own copy of the counts: complete when the slot's fetch is, whatever the other slot pushes meanwhile
+        if(e == hipSuccess) e = hipMemcpyAsync(ir.slot_clamped[slot], ir.d_clamped, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream);
+    }
+    ev_end(h, MSK144_T_FRONTEND);
+    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_rate_hops: ") + hipGetErrorString(e));
+    ir.last_n = n;
+    ir.last_first.assign(sl.is_first, sl.is_first + n);
+    for(int32_t j = 0; j < n; j++) ir.started[static_cast<size_t>(sl.streams[j])] = 1;
+    ir.pushed = true;
+    ir.slot_n[slot] = n;
+    return MSK144_OK;
+}
+
 extern "C" {
 
 int msk144_set_input_rate(msk144_handle* h, const msk144_input_rate_params* p)
@@ -52,8 +92,7 @@ int msk144_set_input_rate(msk144_handle* h, const msk144_input_rate_params* p)
         ir_release(h);
         return MSK144_OK;
     }
-    if(h->params.read_mode != 1) return fail(h, MSK144_EINVAL, "msk144_set_input_rate: the handle reads complex int8 I/Q (read_mode 2); the resampler takes int16 audio");
-    if(h->wb.configured) return fail(h, MSK144_EINVAL, "msk144_set_input_rate: the handle is in wideband mode");
+    if(const int rc = streams_only(h, "msk144_set_input_rate", "the resampler takes int16 audio"); rc != MSK144_OK) return rc;
     const std::string why = msk144ir::check_config(p->rate_hz, p->shift, p->num_taps, p->taps);
     if(!why.empty()) return fail(h, MSK144_EINVAL, "msk144_set_input_rate: " + why);
 
@@ -112,70 +151,7 @@ int msk144_rate_hop_slot(msk144_handle* h, int32_t slot, void** hops, void** fir
 
 int msk144_push_rate_hops(msk144_handle* h, int32_t slot, int32_t n)
 {
-    int rc = check_hop_slot(h, slot);
-    if(rc != MSK144_OK) return rc;
-    InputRate& ir = h->ir;
-    if(!ir.on) return fail(h, MSK144_ESTATE, "msk144_push_rate_hops before msk144_set_input_rate");
-    if(!h->ring_ready || !ir.hops[slot]) return fail(h, MSK144_ESTATE, "msk144_push_rate_hops before msk144_rate_hop_slot");
-    if(n < 1 || n > h->st.channels) return fail(h, MSK144_EINVAL, "n must be 1..channels");
-    msk144_handle::Slot& sl = h->slots[slot];
-    bool any_first = false;
-    for(int32_t j = 0; j < n; j++)
-    {
-        if(sl.streams[j] < 0 || sl.streams[j] >= h->st.channels || (j > 0 && sl.streams[j] <= sl.streams[j - 1]))
-            return fail(h, MSK144_EINVAL, "streams must be ascending stream numbers below channels");
-        if(!sl.is_first[j] && !ir.started[static_cast<size_t>(sl.streams[j])])
-            return fail(h, MSK144_ESTATE, "msk144_push_rate_hops: stream " + std::to_string(sl.streams[j]) + " has a later hop before a first one (is_first = 0)");
-        any_first = any_first || sl.is_first[j] != 0;
-    }
-    if((rc = begin_hop(h, slot, n)) != MSK144_OK) return rc;
-    const size_t row_bytes = static_cast<size_t>(ir.shape.row) * sizeof(int16_t);
-    ev_begin(h);
-    hipError_t e = hipMemcpyAsync(ir.d_in_hops, ir.hops[slot], row_bytes * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess && any_first) e = hipMemcpyAsync(ir.d_in_first, ir.first_halves[slot], row_bytes * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess) e = hipMemcpyAsync(h->d_streams, sl.streams, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream);
-    if(e == hipSuccess) e = hipMemcpyAsync(h->d_isfirst, sl.is_first, n, hipMemcpyHostToDevice, h->stream);
-    ev_end(h, MSK144_T_H2D);
-    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_rate_hops: ") + hipGetErrorString(e));
-
-    ev_begin(h);
-    e = hipMemsetAsync(ir.d_clamped, 0, sizeof(int32_t) * n, h->stream);
-    if(e == hipSuccess)
-    {
-        ResampleArgs a{};
-        a.in_first = ir.d_in_first;
-        a.in_hops = ir.d_in_hops;
-        a.streams = h->d_streams;
-        a.is_first = h->d_isfirst;
-        a.taps = ir.d_taps;
-        a.hist = ir.d_hist;
-        a.out_first = reinterpret_cast<int16_t*>(h->d_first);
-        a.out_hops = reinterpret_cast<int16_t*>(h->d_hops);
-        a.clamped = ir.d_clamped;
-        a.P = ir.shape.P;
-        a.Q = ir.shape.Q;
-        a.H = ir.shape.H;
-        a.hist_stride = ir.hist_stride;
-        a.row = ir.shape.row;
-        a.dwords = ir.shape.dwords;
-        a.shift = ir.shift;
-        launch_resample(a, n, any_first, h->stream);
-        e = hipGetLastError();
-        // the slot's own copy of the counts: complete when the slot's fetch is, whatever the other slot pushes meanwhile
-        if(e == hipSuccess) e = hipMemcpyAsync(ir.slot_clamped[slot], ir.d_clamped, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream);
-    }
-    ev_end(h, MSK144_T_FRONTEND);
-    if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("msk144_push_rate_hops: ") + hipGetErrorString(e));
-    ir.last_n = n;
-    ir.last_first.assign(sl.is_first, sl.is_first + n);
-    for(int32_t j = 0; j < n; j++) ir.started[static_cast<size_t>(sl.streams[j])] = 1;
-    ir.pushed = true;
-    ir.slot_n[slot] = n;
-    if(h->sp.on && (rc = sp_push(h, slot, n)) != MSK144_OK) return rc;
-    if(h->sg.on && (rc = sg_plan(h, slot, n)) != MSK144_OK) return rc;
-    launch_hop_ring(h->d_ring, h->d_hops, h->d_first, h->d_streams, h->d_isfirst, h->d_input, n, h->stream);
-    if((rc = run_frontend(h, h->d_input)) != MSK144_OK || !h->sg.on) return rc;
-    return sg_gather(h, n);
+    return push_stream_hops(h, slot, n, "msk144_push_rate_hops", true);
 }
 
 int msk144_dump_rate_hop(msk144_handle* h, int32_t j, int16_t* out, int32_t* n)

@@ -1,6 +1,6 @@
 // The stream-gate entries of the C ABI (include/msk144hip.h, "Stream gate"): msk144_set_stream_gate, the two read entries, and
-// sg_plan / sg_gather, the steps msk144_push_hops and msk144_push_rate_hops run while the gate is on - the plan behind sp_push, the
-// gather behind run_frontend.  The decode of a gated hop is msk144_api.cpp's, which takes header, event and store from h->gate_of.
+// sg_plan / sg_gather, the steps the push (push_stream_hops, msk144_api.cpp) runs while the gate is on - the plan behind sp_push,
+// the gather behind run_frontend.  The decode of a gated hop is msk144_api.cpp's, which takes header, event and store from h->gate_of.
 #include "api_handle.h"
 
 #include <cstring>
@@ -34,8 +34,8 @@ int sg_plan(msk144_handle* h, int32_t slot, int32_t n)
 {
     StreamGate& g = h->sg;
     const StreamPings& sp = h->sp;
-    const msk144_handle::Slot& sl = h->slots[slot];
-    for(int32_t j = 0; j < n; j++) g.restart[slot][j] = g.seen[static_cast<size_t>(sl.streams[j])] ? 0 : 1;
+    const int32_t* streams = h->slots[slot].streams;
+    g.since.stage(slot, streams, n);
     // the detector's results of this push, where sp_push has just left them (the layout is StreamPings', api_handle.h); off: no
     // record, every mask 0
     const auto* records = sp.on ? reinterpret_cast<const msk144wb::PingRecord*>(sp.d_out) : nullptr;
@@ -43,11 +43,11 @@ int sg_plan(msk144_handle* h, int32_t slot, int32_t n)
     const bool own = records && g.params.ratio_q4 != 0;
     const int32_t most = msk144sg::cap(g.params, h->st.channels);
     ev_begin(h);
-    hipError_t e = hipMemcpyAsync(g.d_restart, g.restart[slot], static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream);
+    hipError_t e = hipMemcpyAsync(g.since.d_restart, g.since.restart[slot], static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess)
     {
         if(own) launch_stream_gate_mask(records, energies, n, g.params.ratio_q4, g.d_masks, h->stream);
-        launch_stream_gate_plan(h->d_streams, h->d_isfirst, g.d_restart, records, own ? g.d_masks : nullptr, g.d_always, g.d_since, n, g.params, most, g.pushes, g.d_header, g.d_list,
+        launch_stream_gate_plan(h->d_streams, h->d_isfirst, g.since.d_restart, records, own ? g.d_masks : nullptr, g.d_always, g.d_since, n, g.params, most, g.pushes, g.d_header, g.d_list,
                                 h->stream);
         e = hipGetLastError();
     }
@@ -58,8 +58,7 @@ int sg_plan(msk144_handle* h, int32_t slot, int32_t n)
     if(e == hipSuccess) e = hipEventRecord(g.planned[slot], h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("stream gate: ") + hipGetErrorString(e));
-    // only a push that went out uses up a stream's restart
-    for(int32_t j = 0; j < n; j++) g.seen[static_cast<size_t>(sl.streams[j])] = 1;
+    g.since.commit(streams, n);
     g.pushes++;
     g.slot_pushed[slot] = true;
     g.last_slot = slot;
@@ -84,8 +83,7 @@ extern "C" {
 int msk144_set_stream_gate(msk144_handle* h, const msk144_stream_gate_params* p, const uint8_t* always)
 {
     if(!h) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 1) return fail(h, MSK144_EINVAL, "msk144_set_stream_gate: the handle reads complex int8 I/Q (read_mode 2); the stream gate reads the pings of int16 audio");
-    if(h->wb.configured) return fail(h, MSK144_EINVAL, "msk144_set_stream_gate: the handle is in wideband mode");
+    if(const int rc = streams_only(h, "msk144_set_stream_gate", "the stream gate reads the pings of int16 audio"); rc != MSK144_OK) return rc;
     StreamGate& g = h->sg;
     msk144sg::Params gp;
     if(p)
@@ -104,7 +102,7 @@ int msk144_set_stream_gate(msk144_handle* h, const msk144_stream_gate_params* p,
         int rc;
         if(!g.d_always && (rc = dev_alloc(h, h->mem, &g.d_always, nch)) != MSK144_OK) return rc;
         if(!g.d_since && (rc = dev_alloc(h, h->mem, &g.d_since, nch)) != MSK144_OK) return rc;
-        if(!g.d_restart && (rc = dev_alloc(h, h->mem, &g.d_restart, nch)) != MSK144_OK) return rc;
+        if(!g.since.d_restart && (rc = dev_alloc(h, h->mem, &g.since.d_restart, nch)) != MSK144_OK) return rc;
         if(!g.d_masks && (rc = dev_alloc(h, h->mem, &g.d_masks, nch)) != MSK144_OK) return rc;
         if(!g.d_header)
         {
@@ -116,7 +114,7 @@ int msk144_set_stream_gate(msk144_handle* h, const msk144_stream_gate_params* p,
         }
         for(int s = 0; s < MSK144_SLOTS; s++)
         {
-            if(!g.restart[s] && (rc = host_alloc(h, h->mem, &g.restart[s], nch)) != MSK144_OK) return rc;
+            if(!g.since.restart[s] && (rc = host_alloc(h, h->mem, &g.since.restart[s], nch)) != MSK144_OK) return rc;
             if(!g.header[s])
             {
                 int32_t* block = nullptr;
@@ -146,7 +144,7 @@ int msk144_set_stream_gate(msk144_handle* h, const msk144_stream_gate_params* p,
     for(size_t s = 0; always && s < nch; s++) flags[s] = always[s] != 0;
     HIP_TRY(h, hipMemcpy(g.d_always, flags.data(), nch, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemset(g.d_since, 0, nch * sizeof(int32_t)));
-    g.seen.assign(nch, 0);
+    g.since.reset(nch);
     g.pushes = 0;
     g.params = gp;
     g.on = true;

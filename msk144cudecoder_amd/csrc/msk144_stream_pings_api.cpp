@@ -1,6 +1,5 @@
 // The stream-ping entries of the C ABI (include/msk144hip.h, "Stream levels and pings"): msk144_set_stream_pings, the three read
-// entries, and sp_push, the step msk144_push_hops and msk144_push_rate_hops run while the option is on.  Everything else of a push -
-// staging copy, resampler, hop ring, front end - stays where it is, reached through api_handle.h.
+// entries, and sp_push, the step the push (push_stream_hops, msk144_api.cpp) runs while the option is on.
 #include "api_handle.h"
 
 #include <cstring>
@@ -26,18 +25,13 @@ int sp_read_ready(msk144_handle* h, const char* entry)
 int sp_push(msk144_handle* h, int32_t slot, int32_t n)
 {
     StreamPings& sp = h->sp;
-    const msk144_handle::Slot& sl = h->slots[slot];
-    for(int32_t j = 0; j < n; j++)
-    {
-        uint8_t& seen = sp.seen[static_cast<size_t>(sl.streams[j])];
-        sp.restart[slot][j] = seen ? 0 : 1;
-        seen = 1;
-    }
+    const int32_t* streams = h->slots[slot].streams;
+    sp.since.stage(slot, streams, n);
     ev_begin(h);
-    hipError_t e = hipMemcpyAsync(sp.d_restart, sp.restart[slot], static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream);
+    hipError_t e = hipMemcpyAsync(sp.since.d_restart, sp.since.restart[slot], static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream);
     if(e == hipSuccess)
     {
-        launch_stream_pings(h->d_first, h->d_hops, h->d_streams, h->d_isfirst, sp.d_restart, n, sp.params, sp.d_state, reinterpret_cast<msk144wb::PingRecord*>(sp.d_out),
+        launch_stream_pings(h->d_first, h->d_hops, h->d_streams, h->d_isfirst, sp.since.d_restart, n, sp.params, sp.d_state, reinterpret_cast<msk144wb::PingRecord*>(sp.d_out),
                             reinterpret_cast<msk144sp::Level*>(sp.d_out + StreamPings::levels_at(n)), reinterpret_cast<int32_t*>(sp.d_out + StreamPings::energies_at(n)), h->stream);
         e = hipGetLastError();
     }
@@ -45,6 +39,7 @@ int sp_push(msk144_handle* h, int32_t slot, int32_t n)
     if(e == hipSuccess) e = hipMemcpyAsync(sp.out[slot], sp.d_out, StreamPings::out_bytes(n), hipMemcpyDeviceToHost, h->stream);
     ev_end(h, MSK144_T_FRONTEND);
     if(e != hipSuccess) return fail(h, MSK144_EHIP, std::string("stream pings: ") + hipGetErrorString(e));
+    sp.since.commit(streams, n);
     sp.slot_n[slot] = n;
     sp.last_slot = slot;
     sp.pushed = true;
@@ -56,8 +51,7 @@ extern "C" {
 int msk144_set_stream_pings(msk144_handle* h, const msk144_stream_pings_params* p)
 {
     if(!h) return fail(h, MSK144_EINVAL, "null argument");
-    if(h->params.read_mode != 1) return fail(h, MSK144_EINVAL, "msk144_set_stream_pings: the handle reads complex int8 I/Q (read_mode 2); stream pings take int16 audio");
-    if(h->wb.configured) return fail(h, MSK144_EINVAL, "msk144_set_stream_pings: the handle is in wideband mode");
+    if(const int rc = streams_only(h, "msk144_set_stream_pings", "stream pings take int16 audio"); rc != MSK144_OK) return rc;
     StreamPings& sp = h->sp;
     msk144sp::Params pp;
     if(p)
@@ -76,15 +70,15 @@ int msk144_set_stream_pings(msk144_handle* h, const msk144_stream_pings_params* 
     const size_t bytes = StreamPings::out_bytes(h->st.channels);
     int rc;
     if(!sp.d_state && (rc = dev_alloc(h, h->mem, &sp.d_state, nch)) != MSK144_OK) return rc;
-    if(!sp.d_restart && (rc = dev_alloc(h, h->mem, &sp.d_restart, nch)) != MSK144_OK) return rc;
+    if(!sp.since.d_restart && (rc = dev_alloc(h, h->mem, &sp.since.d_restart, nch)) != MSK144_OK) return rc;
     if(!sp.d_out && (rc = dev_alloc(h, h->mem, &sp.d_out, bytes)) != MSK144_OK) return rc;
     for(int s = 0; s < MSK144_SLOTS; s++)
     {
-        if(!sp.restart[s] && (rc = host_alloc(h, h->mem, &sp.restart[s], nch)) != MSK144_OK) return rc;
+        if(!sp.since.restart[s] && (rc = host_alloc(h, h->mem, &sp.since.restart[s], nch)) != MSK144_OK) return rc;
         if(!sp.out[s] && (rc = host_alloc(h, h->mem, &sp.out[s], bytes)) != MSK144_OK) return rc;
     }
     HIP_TRY(h, hipMemset(sp.d_state, 0, nch * sizeof(msk144wb::PingHistory)));
-    sp.seen.assign(nch, 0);
+    sp.since.reset(nch);
     sp.params = pp;
     sp.on = true;
     return MSK144_OK;

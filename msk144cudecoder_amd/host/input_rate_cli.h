@@ -5,8 +5,7 @@
 
 #include "../../include/msk144hip.h"
 #include "../csrc/input_rate.h"
-
-#include <dlfcn.h>
+#include "wideband_cli.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -26,23 +25,8 @@ struct InputRateApi
 
     bool resolve(std::string& err)
     {
-        struct Entry
-        {
-            const char* name;
-            void* pointer;
-        };
-        const Entry entries[] = {{"msk144_set_input_rate", &set}, {"msk144_rate_hop_slot", &slot}, {"msk144_push_rate_hops", &push}, {"msk144_input_rate_slot_clamped", &slot_clamped}};
-        for(const Entry& e : entries)
-        {
-            void* p = dlsym(RTLD_DEFAULT, e.name);
-            std::memcpy(e.pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
-            if(!p)
-            {
-                err = std::string("the loaded libmsk144hip has no input-rate resampler (") + e.name + "): --input-rate needs a library built from these sources";
-                return false;
-            }
-        }
-        return true;
+        const ApiEntry entries[] = {{"msk144_set_input_rate", &set}, {"msk144_rate_hop_slot", &slot}, {"msk144_push_rate_hops", &push}, {"msk144_input_rate_slot_clamped", &slot_clamped}};
+        return resolve_entries(entries, 4, "input-rate resampler", ": --input-rate needs a library built from these sources", err);
     }
 };
 

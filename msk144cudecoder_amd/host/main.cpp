@@ -6,10 +6,8 @@
 // multi-stream loop is pipelined over the library's two pinned staging slots (stream_loop.h): an ingest thread reads the streams and
 // submits hop n+1 while the GPU decodes hop n and a second thread turns the records of hop n-1 into text.  --devices=0,1,... runs
 // one such loop per GPU, each on its contiguous share of the streams (the reference binds to one device, main.cu:115).
-#include "input_rate_cli.h"
-#include "stream_gate_cli.h"
-#include "stream_pings_cli.h"
 #include "stream_loop.h"
+#include "stream_options.h"
 #include "wideband_run.h"
 
 #include <getopt.h>
@@ -164,10 +162,8 @@ int main(int argc, char* const argv[])
     std::vector<std::string> device_list;
     bool read_mode_set = false;
     WidebandOptions wbo;
-    InputRate input_rate;
-    StreamStats stream_stats;
-    StreamGate stream_gate;
-    std::string input_rate_error, taps_per_phase_arg, stream_stats_error, stream_gate_error;
+    StreamOptions so;  // --input-rate, --stream-pings, --stream-levels, --stream-gate
+    std::string taps_per_phase_arg;
     int wideband_options = 0, taps_per_phase_options = 0;  // how many options went to take_wideband_option, and how many of them were --taps-per-phase
 
     static struct option long_options[] = {{"help", no_argument, 0, 0},
@@ -221,25 +217,22 @@ int main(int argc, char* const argv[])
         if(c != 0) continue;  // unknown option: getopt has printed its own message, carry on like the reference
         if(!strcmp(long_options[idx].name, "input-rate"))
         {
-            const std::string why = input_rate.parse(optarg);
-            if(!why.empty() && input_rate_error.empty()) input_rate_error = why;
+            so.parse_input_rate(optarg);
             continue;
         }
         if(!strcmp(long_options[idx].name, "stream-pings"))
         {
-            const std::string why = stream_stats.parse_pings(optarg);
-            if(!why.empty() && stream_stats_error.empty()) stream_stats_error = why;
+            so.parse_stream_pings(optarg);
             continue;
         }
         if(!strcmp(long_options[idx].name, "stream-levels"))
         {
-            stream_stats.levels = true;
+            so.parse_stream_levels();
             continue;
         }
         if(!strcmp(long_options[idx].name, "stream-gate"))
         {
-            const std::string why = stream_gate.parse(optarg);
-            if(!why.empty() && stream_gate_error.empty()) stream_gate_error = why;
+            so.parse_stream_gate(optarg);
             continue;
         }
         if(!strcmp(long_options[idx].name, "taps-per-phase"))
@@ -293,10 +286,9 @@ int main(int argc, char* const argv[])
     }
 
     // --taps-per-phase with --input-rate and nothing else of the wideband options: the resampler's K, and no wideband run
-    if(input_rate.given && taps_per_phase_options > 0 && wideband_options == taps_per_phase_options)
+    if(so.input_rate_given() && taps_per_phase_options > 0 && wideband_options == taps_per_phase_options)
     {
-        if(!parse_int_in(taps_per_phase_arg, 1, msk144ir::kMaxTapsPerPhase, input_rate.taps_per_phase) && input_rate_error.empty())
-            input_rate_error = "bad value for --taps-per-phase: '" + taps_per_phase_arg + "'";
+        so.parse_taps_per_phase(taps_per_phase_arg);
         wbo = WidebandOptions();
     }
 
@@ -327,60 +319,12 @@ int main(int argc, char* const argv[])
         opt.read_mode = 2;
     }
 
-    // --input-rate: checked in full, and the header of --input-rate=wav read, before anything touches the library
+    // the options on the audio streams: checked in full, and the header of --input-rate=wav read, before anything touches the library
     bool wav_header_read = false;
-    if(input_rate.given)
+    if(const std::string why = so.check(wideband, opt.read_mode, !input_paths.empty(), interleaved, skip_wav, wav_header_read); !why.empty())
     {
-        std::string why = input_rate_error;
-        if(!why.empty()) ;  // the option's own value was bad
-        else if(wideband) why = "--input-rate resamples audio streams: it excludes --wideband-rate (whose rate is the I/Q stream's)";
-        else if(opt.read_mode != 1) why = "--input-rate resamples 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
-        else if(input_rate.from_wav && (!input_paths.empty() || interleaved != 0))
-            why = "--input-rate=wav reads the rate of the single stdin stream: with --inputs, --inputs-file or --interleaved give the rate in Hz";
-        else if(input_rate.from_wav && !skip_wav) why = "--input-rate=wav takes the rate from the stream's WAV header: it needs --skip-wav-header";
-        else if(input_rate.from_wav)
-        {
-            unsigned char hdr[44];
-            int64_t hz = 0;
-            if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) why = "--input-rate=wav: the stream ended inside its 44-byte WAV header";
-            else if((why = wav_header_rate(hdr, hz)).empty()) why = input_rate.set_rate(hz);
-            wav_header_read = true;
-        }
-        if(why.empty()) input_rate.prepare(why);
-        if(!why.empty())
-        {
-            std::cerr << why << std::endl;
-            return 2;
-        }
-    }
-
-    // --stream-pings, --stream-levels: checked in full before anything touches the library
-    if(stream_stats.on())
-    {
-        const std::string which = stream_stats.pings ? "--stream-pings" : "--stream-levels";
-        std::string why = stream_stats_error;
-        if(!why.empty()) ;  // the option's own value was bad
-        else if(wideband) why = which + " reads the audio streams' hops: it excludes --wideband-rate (whose channels have --wideband-pings and --wideband-levels)";
-        else if(opt.read_mode != 1) why = which + " reads 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
-        if(!why.empty())
-        {
-            std::cerr << why << std::endl;
-            return 2;
-        }
-    }
-
-    // --stream-gate: the same
-    if(stream_gate.on)
-    {
-        std::string why = stream_gate_error;
-        if(!why.empty()) ;  // the option's own value was bad
-        else if(wideband) why = "--stream-gate gates the audio streams' windows: it excludes --wideband-rate (whose channels have --wideband-gate)";
-        else if(opt.read_mode != 1) why = "--stream-gate reads the pings of 16-bit audio: it excludes --read-mode=" + std::to_string(opt.read_mode);
-        if(!why.empty())
-        {
-            std::cerr << why << std::endl;
-            return 2;
-        }
+        std::cerr << why << std::endl;
+        return 2;
     }
 
     if(!center_set)
@@ -412,22 +356,11 @@ int main(int argc, char* const argv[])
     const bool batched = interleaved > 0 || !input_paths.empty() || wideband;
     const int nch = wideband ? static_cast<int>(wbo.offsets.size()) : interleaved > 0 ? interleaved : (input_paths.empty() ? 1 : static_cast<int>(input_paths.size()));
     opt.profile = timing && batched;
-    // --stream-pings, --stream-levels: the entries resolved and the log opened before anything touches the library
-    if(std::string why; stream_stats.on() && !stream_stats.prepare(nch, why))
+    // the options on the audio streams: the entries resolved and the log opened before anything touches the library
+    if(std::string why; !so.prepare(nch, why))
     {
         std::cerr << why << std::endl;
         return 2;
-    }
-    // --stream-gate: MAX and ALWAYS against the streams of the run, and the entries resolved
-    if(stream_gate.on)
-    {
-        std::string why = stream_gate.check(nch);
-        if(why.empty()) stream_gate.api.resolve(why);
-        if(!why.empty())
-        {
-            std::cerr << why << std::endl;
-            return 2;
-        }
     }
     {
         // one descriptor per stream plus what the runtime opens: lift the soft limit when the hard limit allows
@@ -517,42 +450,21 @@ int main(int argc, char* const argv[])
               << F << " x 512, softbits " << F << " x 512, LDPC one wave per gated candidate" << std::endl;
     if(batched && !wideband) std::cerr << "msk144hipdecoder: " << nch << " input streams per GPU batch" << (interleaved > 0 ? " (interleaved on stdin)" : "") << ", hop timeout " << hop_timeout_ms << " ms" << std::endl;
     if(wideband && !wideband_run.configure(dec.handle())) return 2;
-    if(input_rate.on)
+    if(so.any())
     {
         std::string why;
-        if(!input_rate.configure(dec.handle(), why))
+        if(!so.configure(dec.handle(), shares[0].first, shares[0].count, why))
         {
             std::cerr << "msk144hip: " << why << std::endl;
             return 2;
         }
-    }
-    if(stream_stats.on())
-    {
-        std::string why;
-        if(!stream_stats.configure(dec.handle(), why))
-        {
-            std::cerr << "msk144hip: " << why << std::endl;
-            return 2;
-        }
-        dec.use_stream_stats(&stream_stats, 0);
-    }
-    if(stream_gate.on)
-    {
-        std::string why;
-        if(!stream_gate.configure(dec.handle(), shares[0].first, shares[0].count, stream_stats.on(), why))
-        {
-            std::cerr << "msk144hip: " << why << std::endl;
-            return 2;
-        }
-        dec.use_stream_gate(&stream_gate);
+        so.attach(dec, shares[0].first);
     }
     if(shares.size() > 1)
         for(const Share& sh : shares) std::cerr << "msk144hipdecoder: device " << sh.device << " decodes streams " << sh.first << ".." << sh.first + sh.count - 1 << std::endl;
 
-    const size_t sample_bytes = (opt.read_mode == 1) ? sizeof(int16_t) : 2 * sizeof(int8_t);
-    // with --input-rate a hop is 2592 x P/Q samples
-    const size_t win_bytes = input_rate.on ? 2 * input_rate.row_bytes() : MSK144_WINDOW_SAMPLES * sample_bytes;
-    const size_t half = win_bytes / 2;
+    const size_t half = dec.hop_bytes();  // with --input-rate a hop is 2592 x P/Q samples
+    const size_t win_bytes = 2 * half;
     const size_t unit = (opt.read_mode == 1) ? sizeof(int16_t) : sizeof(int8_t);  // the reference counts items of this size
 
     if(!batched)
@@ -563,11 +475,10 @@ int main(int argc, char* const argv[])
             unsigned char hdr[44];
             if(fread(hdr, 1, sizeof(hdr), stdin) != sizeof(hdr)) std::cerr << "Incomplete read error. rc=0" << std::endl;
         }
-        if(input_rate.on || stream_stats.on() || stream_gate.on)
+        if(so.any())
         {
             // the same loop over the library's hop ring (msk144_push_rate_hops at the input rate, msk144_push_hops for the levels and
             // pings of a 12 kHz stream, which a whole-window submit does not produce): a hop carries its new samples only
-            if(input_rate.on) dec.use_input_rate(&input_rate);
             WindowDecoder::HopStage hs;
             std::vector<std::vector<FilteredResult>> all;
             bool first = true;
@@ -604,10 +515,7 @@ int main(int argc, char* const argv[])
                 warn_if_late(std::chrono::duration_cast<std::chrono::milliseconds>(Clock::now() - t0).count());
                 for(const FilteredResult& l : all[0]) std::cout << l.format_line() << std::endl;
             }
-            if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
-            stream_stats.finish();
-            for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
-            if(stream_gate.on) std::cerr << stream_gate.summary() << std::endl;
+            so.finish(std::cerr);
             std::cout << "Done" << std::endl;
             return 0;
         }
@@ -666,35 +574,15 @@ int main(int argc, char* const argv[])
     }
     for(size_t i = 0; i < loops.size(); i++)
     {
-        if(input_rate.on)
+        if(i > 0 && so.any())
         {
             std::string why;
-            if(i > 0 && !input_rate.configure(loops[i]->decoder().handle(), why))
+            if(!so.configure(loops[i]->decoder().handle(), shares[i].first, shares[i].count, why))
             {
                 std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
                 return 2;
             }
-            loops[i]->use_input_rate(&input_rate);
-        }
-        if(stream_stats.on())
-        {
-            std::string why;
-            if(i > 0 && !stream_stats.configure(loops[i]->decoder().handle(), why))
-            {
-                std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
-                return 2;
-            }
-            loops[i]->decoder().use_stream_stats(&stream_stats, shares[i].first);
-        }
-        if(stream_gate.on)
-        {
-            std::string why;
-            if(i > 0 && !stream_gate.configure(loops[i]->decoder().handle(), shares[i].first, shares[i].count, stream_stats.on(), why))
-            {
-                std::cerr << "msk144hip: device " << shares[i].device << ": " << why << std::endl;
-                return 2;
-            }
-            loops[i]->decoder().use_stream_gate(&stream_gate);
+            so.attach(loops[i]->decoder(), shares[i].first);
         }
         if(wideband) loops[i]->use_wideband(&wideband_run);
         else if(interleaved > 0) loops[i]->use_feed();
@@ -793,10 +681,7 @@ int main(int argc, char* const argv[])
     }
     std::cerr << "msk144hipdecoder: " << batches << " batches, " << total_hops << " stream hops, " << total_late << " late, worst latency " << worst << " ms" << std::endl;
     if(wideband) wideband_run.print_summary(loops[0]->decoder().handle());
-    if(input_rate.on) std::cerr << input_rate.summary() << std::endl;
-    stream_stats.finish();
-    for(const std::string& l : stream_stats.summary()) std::cerr << l << std::endl;
-    if(stream_gate.on) std::cerr << stream_gate.summary() << std::endl;
+    so.finish(std::cerr);
     if(overflowed) std::cerr << "msk144hipdecoder: " << overflowed << " hops overflowed the result list (lists cut, see above)" << std::endl;
     if(timing)
     {

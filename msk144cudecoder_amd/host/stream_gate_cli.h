@@ -9,8 +9,6 @@
 #include "../csrc/stream_pings.h"
 #include "wideband_cli.h"
 
-#include <dlfcn.h>
-
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -27,23 +25,8 @@ struct StreamGateApi
 
     bool resolve(std::string& err)
     {
-        struct Entry
-        {
-            const char* name;
-            void* pointer;
-        };
-        const Entry entries[] = {{"msk144_set_stream_gate", &set}, {"msk144_stream_gate_slot", &slot}, {"msk144_set_stream_pings", &set_pings}};
-        for(const Entry& e : entries)
-        {
-            void* p = dlsym(RTLD_DEFAULT, e.name);
-            std::memcpy(e.pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
-            if(!p)
-            {
-                err = std::string("the loaded libmsk144hip has no stream gate (") + e.name + "): --stream-gate needs a library built from these sources";
-                return false;
-            }
-        }
-        return true;
+        const ApiEntry entries[] = {{"msk144_set_stream_gate", &set}, {"msk144_stream_gate_slot", &slot}, {"msk144_set_stream_pings", &set_pings}};
+        return resolve_entries(entries, 3, "stream gate", ": --stream-gate needs a library built from these sources", err);
     }
 };
 

@@ -1,6 +1,5 @@
 #include "stream_loop.h"
 
-#include "input_rate_cli.h"
 #include "wideband_run.h"
 
 #include <fcntl.h>
@@ -75,11 +74,16 @@ void LinePrinter::log(const std::string& line)
 DeviceLoop::DeviceLoop(const DecoderOptions& opt, int first_stream, const LoopOptions& lo, LinePrinter& printer)
     : dec_(opt), nch_(opt.channels < 1 ? 1 : opt.channels), base_(first_stream), device_(opt.device), lo_(lo), out_(printer)
 {
-    const size_t sample_bytes = (opt.read_mode == 1) ? sizeof(int16_t) : 2 * sizeof(int8_t);
-    win_bytes_ = MSK144_WINDOW_SAMPLES * sample_bytes;
-    half_ = win_bytes_ / 2;
     unit_ = (opt.read_mode == 1) ? sizeof(int16_t) : sizeof(int8_t);  // the reference counts items of this size
     st_.resize(nch_);
+    take_hop_size();
+}
+
+// the decoder's hop in bytes: at construction a plain 12 kHz hop, in start() that of the options attached since (--input-rate)
+void DeviceLoop::take_hop_size()
+{
+    half_ = dec_.hop_bytes();
+    win_bytes_ = 2 * half_;
     for(Stream& s : st_) s.pending.reserve(win_bytes_);
 }
 
@@ -108,14 +112,6 @@ bool DeviceLoop::open_inputs(const std::vector<std::string>& paths)
     return true;
 }
 
-void DeviceLoop::use_input_rate(InputRate* ir)
-{
-    half_ = ir->row_bytes();
-    win_bytes_ = 2 * half_;
-    for(Stream& s : st_) s.pending.reserve(win_bytes_);
-    dec_.use_input_rate(ir);
-}
-
 void DeviceLoop::fail(const std::string& what)
 {
     out_.log("msk144hip: " + what);
@@ -137,6 +133,7 @@ void DeviceLoop::fail(const std::string& what)
 void DeviceLoop::start()
 {
     opened_at_ = Clock::now();
+    take_hop_size();
     for(int k = 0; k < WindowDecoder::kSlots; k++)
     {
         // pinned, owned by the library handle; the stream windows themselves live on the device

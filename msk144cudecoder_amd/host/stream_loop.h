@@ -99,11 +99,9 @@ public:
         wb_ = run;
     }
 
-    // --input-rate (input_rate_cli.h): every stream arrives at the option's rate and is resampled on the GPU: a hop is 2592 x P/Q
-    // samples per stream (5184 x P/Q the first time), whether it comes from --inputs or through feed().  `ir` has configured
-    // decoder().handle().  Call it before open_inputs() / start().
-    void use_input_rate(InputRate* ir);
-
+    // With --input-rate (attached to decoder(), stream_options.h) every stream arrives at the option's rate and is resampled on the
+    // GPU: a hop is then 2592 x P/Q samples per stream (5184 x P/Q the first time), whether it comes from --inputs or through
+    // feed().  The loop takes the hop size from its decoder, at construction and again in start(): attach the options before start().
     void start();
     // One hop of every stream of this loop, stream after stream (bytes_per_stream each: a whole window the first time, half a
     // window afterwards).  Blocks while two blocks are already queued (back-pressure into the reader).  false once the loop failed.
@@ -154,6 +152,7 @@ private:
     void drain_descriptors(int& open_streams);
     bool take_fed_block(int& open_streams);
     void fail(const std::string& what);
+    void take_hop_size();
     bool enqueue(const unsigned char* data, size_t bytes, size_t bytes_per_stream);
     bool submit_wideband(Batch& b);
 

@@ -8,8 +8,6 @@
 #include "../csrc/stream_pings.h"
 #include "wideband_cli.h"
 
-#include <dlfcn.h>
-
 #include <cerrno>
 #include <cstring>
 #include <memory>
@@ -27,23 +25,8 @@ struct StreamPingsApi
 
     bool resolve(std::string& err)
     {
-        struct Entry
-        {
-            const char* name;
-            void* pointer;
-        };
-        const Entry entries[] = {{"msk144_set_stream_pings", &set}, {"msk144_stream_pings_slot", &slot}};
-        for(const Entry& e : entries)
-        {
-            void* p = dlsym(RTLD_DEFAULT, e.name);
-            std::memcpy(e.pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
-            if(!p)
-            {
-                err = std::string("the loaded libmsk144hip has no stream pings (") + e.name + "): --stream-pings and --stream-levels need a library built from these sources";
-                return false;
-            }
-        }
-        return true;
+        const ApiEntry entries[] = {{"msk144_set_stream_pings", &set}, {"msk144_stream_pings_slot", &slot}};
+        return resolve_entries(entries, 2, "stream pings", ": --stream-pings and --stream-levels need a library built from these sources", err);
     }
 };
 

@@ -71,6 +71,27 @@ struct WidebandOptions
     std::string parse_error;  // first malformed value
 };
 
+// One entry of the library that the program takes at run time: its name, and the function-pointer member that receives it
+struct ApiEntry
+{
+    const char* name;
+    void* pointer;
+};
+
+// Resolves every entry with dlsym; false with "the loaded libmsk144hip has no <feature> (<first missing symbol>)<needs>"
+inline bool resolve_entries(const ApiEntry* entries, size_t count, const char* feature, const char* needs, std::string& err)
+{
+    const char* missing = nullptr;
+    for(size_t i = 0; i < count; i++)
+    {
+        void* p = dlsym(RTLD_DEFAULT, entries[i].name);
+        std::memcpy(entries[i].pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
+        if(!p && !missing) missing = entries[i].name;
+    }
+    if(missing) err = std::string("the loaded libmsk144hip has no ") + feature + " (" + missing + ")" + needs;
+    return !missing;
+}
+
 // The library entries of wideband mode.  The four of the channeliser are always resolved, those of an option only when it is given.
 struct WidebandApi
 {
@@ -115,16 +136,11 @@ struct WidebandApi
     // one: "the loaded libmsk144hip has no <feature> (<first missing symbol>)[: <who> need(s) it]".
     bool resolve(const WidebandOptions& w, std::string& err)
     {
-        struct Entry
-        {
-            const char* name;
-            void* pointer;  // the member that receives it
-        };
         struct Group
         {
             bool wanted;
             const char *feature, *needs;
-            std::vector<Entry> entries;
+            std::vector<ApiEntry> entries;
         };
         const Group groups[] = {
             {true, "wideband channeliser", "", {{"msk144_set_wideband", &set}, {"msk144_wideband_slot", &slot}, {"msk144_push_wideband", &push}, {"msk144_wideband_clip_count", &clip}}},
@@ -143,19 +159,7 @@ struct WidebandApi
             {w.gate, "gate", ": --wideband-gate needs it", {{"msk144_set_wideband_gate", &set_gate}, {"msk144_wideband_gate", &gate}}},
         };
         for(const Group& g : groups)
-        {
-            if(!g.wanted) continue;
-            const char* missing = nullptr;
-            for(const Entry& e : g.entries)
-            {
-                void* p = dlsym(RTLD_DEFAULT, e.name);
-                std::memcpy(e.pointer, &p, sizeof(p));  // POSIX: a function pointer and void* have one representation
-                if(!p && !missing) missing = e.name;
-            }
-            if(!missing) continue;
-            err = std::string("the loaded libmsk144hip has no ") + g.feature + " (" + missing + ")" + g.needs;
-            return false;
-        }
+            if(g.wanted && !resolve_entries(g.entries.data(), g.entries.size(), g.feature, g.needs, err)) return false;
         return true;
     }
 };

@@ -1,8 +1,6 @@
 #include "window_decoder.h"
 
-#include "input_rate_cli.h"
-#include "stream_gate_cli.h"
-#include "stream_pings_cli.h"
+#include "stream_options.h"
 
 #include <chrono>
 #include <cstring>
@@ -107,11 +105,18 @@ void* WindowDecoder::stage(int slot)
     return p;
 }
 
+size_t WindowDecoder::hop_bytes() const
+{
+    const InputRate* ir = so_ ? so_->rate() : nullptr;
+    return ir ? ir->row_bytes() : window_bytes_ / 2;
+}
+
 bool WindowDecoder::hop_stage(int slot, HopStage& out)
 {
     void *hops = nullptr, *first = nullptr;
     int32_t row = 0;
-    if((ir_ ? ir_->api.slot(handle_, slot, &hops, &first, &out.streams, &out.is_first, &row) : msk144_hop_slot(handle_, slot, &hops, &first, &out.streams, &out.is_first)) != MSK144_OK)
+    InputRate* ir = so_ ? so_->rate() : nullptr;
+    if((ir ? ir->api.slot(handle_, slot, &hops, &first, &out.streams, &out.is_first, &row) : msk144_hop_slot(handle_, slot, &hops, &first, &out.streams, &out.is_first)) != MSK144_OK)
     {
         error_ = msk144_last_error(handle_);
         return false;
@@ -128,7 +133,8 @@ bool WindowDecoder::submit_hops(int slot, int n)
     streams_[slot].assign(hs.streams, hs.streams + n);
     gated_[slot] = false;
     hops_[slot] = true;
-    int rc = ir_ ? ir_->api.push(handle_, slot, n) : msk144_push_hops(handle_, slot, n);
+    InputRate* ir = so_ ? so_->rate() : nullptr;
+    int rc = ir ? ir->api.push(handle_, slot, n) : msk144_push_hops(handle_, slot, n);
     if(rc == MSK144_OK) rc = msk144_decode(handle_);
     if(rc == MSK144_OK) rc = msk144_fetch_async(handle_, slot);
     if(rc != MSK144_OK)
@@ -201,27 +207,30 @@ bool WindowDecoder::collect(int slot, std::vector<std::vector<FilteredResult>>& 
         return false;
     }
     last_overflow_ = rc == MSK144_EOVERFLOW;
-    if(ir_)
+    InputRate* ir = so_ ? so_->rate() : nullptr;
+    StreamStats* stats = so_ ? so_->stats() : nullptr;
+    StreamGate* sgate = so_ ? so_->gate() : nullptr;
+    if(ir)
     {
         // the slot's hop has arrived, and with it the resampler's clamp counts of that hop
         const int32_t* counts = nullptr;
         int32_t positions = 0;
-        if(ir_->api.slot_clamped(handle_, slot, &counts, &positions) != MSK144_OK)
+        if(ir->api.slot_clamped(handle_, slot, &counts, &positions) != MSK144_OK)
         {
             error_ = msk144_last_error(handle_);
             return false;
         }
         long long sum = 0;
         for(int32_t p = 0; p < positions; p++) sum += counts[p];
-        ir_->clamped += sum;
+        ir->clamped += sum;
     }
     // ... and, with --stream-pings or --stream-levels, the records and levels of its push
-    if(stats_ && hops_[slot] && !stats_->take(handle_, slot, stats_base_, streams_[slot], error_)) return false;
+    if(stats && hops_[slot] && !stats->take(handle_, slot, base_, streams_[slot], error_)) return false;
     // ... and, with --stream-gate, the positions its decode covered
-    const bool sgated = sgate_ && hops_[slot];
+    const bool sgated = sgate && hops_[slot];
     const int32_t* listed_at = nullptr;
     int32_t listed_n = 0;
-    if(sgated && !sgate_->take(handle_, slot, static_cast<int>(streams_[slot].size()), listed_at, listed_n, error_)) return false;
+    if(sgated && !sgate->take(handle_, slot, static_cast<int>(streams_[slot].size()), listed_at, listed_n, error_)) return false;
     const auto t1 = Clock::now();
     const std::vector<int>& streams = streams_[slot];
     const size_t n_results = static_cast<size_t>(n);

@@ -15,9 +15,7 @@
 namespace msk144host
 {
 
-struct InputRate;
-struct StreamStats;
-struct StreamGate;
+struct StreamOptions;
 
 struct DecoderOptions
 {
@@ -115,23 +113,22 @@ public:
     };
     bool hop_stage(int slot, HopStage& out);
     bool submit_hops(int slot, int n);  // the first n entries of the slot's hop stage
-    // --input-rate (input_rate_cli.h; `ir` has configured handle()): hop_stage() then gives the slot's rows at the input rate
-    // (msk144_rate_hop_slot: entry j at j * ir->row_bytes()) and submit_hops() pushes them through the resampler
-    // (msk144_push_rate_hops).  collect() adds the clamped samples of the slot's push to ir->clamped, behind msk144_fetch_wait
-    // (msk144_input_rate_slot_clamped: no wait of its own).
-    void use_input_rate(InputRate* ir) { ir_ = ir; }
-    // --stream-pings / --stream-levels (stream_pings_cli.h; `stats` has configured handle()): collect() hands the records, levels and
-    // block energies of the slot's submit_hops() push to stats->take(), behind msk144_fetch_wait (msk144_stream_pings_slot: no wait
-    // of its own); `base` is the program's number of this decoder's stream 0
-    void use_stream_stats(StreamStats* stats, int base)
+    // The options on the audio streams (stream_options.h; `so` has configured handle()); `base` is the program's number of this
+    // decoder's stream 0.  Each acts while it is on:
+    // --input-rate: hop_stage() gives the slot's rows at the input rate (msk144_rate_hop_slot: entry j at j * hop_bytes()) and
+    // submit_hops() pushes them through the resampler (msk144_push_rate_hops).  collect() adds the clamped samples of the slot's
+    // push to the option's count, behind msk144_fetch_wait (msk144_input_rate_slot_clamped: no wait of its own).
+    // --stream-pings / --stream-levels: collect() hands the records, levels and block energies of the slot's submit_hops() push to
+    // the stats' take(), behind msk144_fetch_wait (msk144_stream_pings_slot: no wait of its own).
+    // --stream-gate: the decode of a submit_hops() push covers the positions of the gate's list.  collect() takes the list behind
+    // msk144_fetch_wait (msk144_stream_gate_slot: no wait of its own) and gives every stream of the hop its SNR update and its
+    // post-processing, the streams that were not listed with no candidates
+    void use_streams(StreamOptions* so, int base)
     {
-        stats_ = stats;
-        stats_base_ = base;
+        so_ = so;
+        base_ = base;
     }
-    // --stream-gate (stream_gate_cli.h; `gate` has configured handle()): the decode of a submit_hops() push covers the positions of
-    // the gate's list.  collect() takes the list behind msk144_fetch_wait (msk144_stream_gate_slot: no wait of its own) and gives
-    // every stream of the hop its SNR update and its post-processing, the streams that were not listed with no candidates
-    void use_stream_gate(StreamGate* gate) { sgate_ = gate; }
+    size_t hop_bytes() const;  // of one entry of a hop stage: 2592 samples of one stream, x P/Q with --input-rate
     // the same for a hop the wideband channeliser wrote on the device (msk144_push_wideband, passed in because the program resolves
     // it at run time): every stream, in order.  `gate` (msk144_wideband_gate, with --wideband-gate): the decode covers the channels
     // of the gate's list, which is taken behind it; collect() then gives every stream its SNR update and its post-processing, the
@@ -160,10 +157,8 @@ private:
     bool gated_[kSlots] = {};           // the slot's hop is a gated wideband push: segment powers come by stream, for every stream
     size_t window_bytes_ = 0;           // of one stream
     bool last_overflow_ = false;
-    InputRate* ir_ = nullptr;
-    StreamStats* stats_ = nullptr;
-    int stats_base_ = 0;
-    StreamGate* sgate_ = nullptr;
+    StreamOptions* so_ = nullptr;
+    int base_ = 0;
     bool hops_[kSlots] = {};            // the slot's hop came through submit_hops()
 };
 
